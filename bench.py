@@ -7,9 +7,12 @@ plus one coarse-frequency kernel launch (the reference runs its 2^14-point estim
 no collective on the data path (weak scaling: `--channels` per GPU); the aggregate is all ranks' samples divided by
 the slowest rank's time.
 
-Printed JSON (one line, rank 0): metric Msamples/s (real 48 kHz PCM samples consumed per second, all channels),
-plus `roofline` for the dominant kernel (HIP-event timed inside libjaero_hip on the launch stream) and
-`cpu_baseline` (the unmodified reference, or the C port when the reference binary cannot run, on the host cores).
+Printed JSON (one line, rank 0): metric Msamples/s (real 48 kHz PCM samples consumed per second, all channels) and
+ms_per_step.  A plain run does only what that figure needs: set up, warm up, time --steps steps, write --dump-outputs,
+print.  With --full the line also carries `roofline` for the dominant kernel (HIP-event timed inside libjaero_hip on
+the launch stream), clocks / power and calibration kernels around the timed region, the BASELINE configs as written,
+the other workloads, the oracle check of sampled channels and `cpu_baseline` (the unmodified reference, or the C port
+when the reference binary cannot run, on the host cores).
 """
 from __future__ import annotations
 
@@ -75,6 +78,14 @@ def parse():
     ap.add_argument("--fb", type=float, default=1200.0, help="msk workload: 1200 or 600 bps")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-samples", type=int, default=500_000, help="samples per process for the CPU baseline leg (>= 10 s of signal)")
+    ap.add_argument("--full", action="store_true",
+                    help="continuous OQPSK workloads: also measure and check what the headline figure does not need -- clocks / power and the calibration "
+                         "kernels around the timed region, per-kernel times and the roofline blocks, the BASELINE configs as written, the other workloads, "
+                         "the edge collectives (N > 1), the oracle check of sampled channels and the CPU baseline.  Without it a run sets up, warms up, "
+                         "times --steps steps, writes --dump-outputs and prints the line.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="continuous OQPSK workloads: after the timed steps write what a caller of the bank receives, for a fixed seeded sample of "
+                         "channels, as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -112,11 +123,11 @@ def setup_ranks():
 MEAS = {}   # what run_timed recorded around the last timed region (gpu_state, calib, step_ms): attached to the line by emit()
 
 
-def run_timed(step, W, K, world, dev, before_timed=None, sustain=0):
+def run_timed(step, W, K, world, dev, before_timed=None, sustain=0, state=True):
     """`sustain` + W untimed steps back to back, then exactly K steps between barrier + device synchronisation on both sides.  Returns (max over
-    ranks of the wall time between the barriers, every rank's time for its own K steps).  Around the timed region (bench_state.py): a side
-    thread samples engine clock / socket power / throttle residency, the two calibration kernels run immediately before and after it, and an
-    event behind every step gives the per-step times -- all of it lands in MEAS."""
+    ranks of the wall time between the barriers, every rank's time for its own K steps).  Around the timed region (bench_state.py; `state`
+    and not --no-state): a side thread samples engine clock / socket power / throttle residency, the two calibration kernels run immediately
+    before and after it; an event behind every step gives the per-step times -- all of it lands in MEAS."""
     import torch
     import torch.distributed as dist
 
@@ -128,7 +139,7 @@ def run_timed(step, W, K, world, dev, before_timed=None, sustain=0):
     sampler = calib = None
     cal = {}
     stream = torch.cuda.current_stream().cuda_stream if gpu else 0
-    if gpu and not ARGS.no_state:
+    if gpu and state and not ARGS.no_state:
         try:
             pr = torch.cuda.get_device_properties(dev.index)
             bdf = ("%04x:%02x:%02x.0" % (getattr(pr, "pci_domain_id", 0), pr.pci_bus_id, pr.pci_device_id)) if hasattr(pr, "pci_bus_id") else None
@@ -1017,8 +1028,11 @@ def aerol_burst_bench():
 
 
 def host_cores():
-    """(logical CPUs, physical cores, model string) of this box, from /proc/cpuinfo."""
-    logical = os.cpu_count() or 1
+    """(logical CPUs, physical cores, model string) this process may use: the CPUs of its affinity mask, no more than OMP_NUM_THREADS where that
+    is set (the share of a shared host a command is given); physical cores from /proc/cpuinfo, at most as many."""
+    logical = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        logical = max(1, min(logical, int(os.environ["OMP_NUM_THREADS"])))
     phys, model = set(), ""
     try:
         pid = cid = None
@@ -1035,7 +1049,7 @@ def host_cores():
                 pid = cid = None
     except OSError:
         pass
-    return logical, (len(phys) or logical), model
+    return logical, min(len(phys) or logical, logical), model
 
 
 def cpu_baseline_continuous(chunk: int, fb: float):
@@ -1106,6 +1120,33 @@ def spread_channels(nch: int, k: int = 16):
             break
         got = sorted(set(got) | {c})
     return got[:max(k, 1)] if len(got) > k else got
+
+
+DUMP_SOFT_BYTES, DUMP_SEED = 60_000_000, 20240601   # --dump-outputs: bytes of soft bits (the other arrays add < 0.1 MB: 64 MB in all), seed of the channel sample
+
+
+def dump_channels(nch: int, softcap: int):
+    """The channels --dump-outputs writes: a fixed seeded sample of the bank, as many as fit the size limit at the bank's soft-bit capacity
+    (at most 1024)."""
+    m = max(1, min(nch, 1024, DUMP_SOFT_BYTES // (4 * softcap)))
+    return sorted(int(c) for c in np.random.default_rng(DUMP_SEED).choice(nch, size=m, replace=False))
+
+
+def dump_outputs(out_dir: str, bank, chans, soft_by_ch: dict):
+    """--dump-outputs: what a caller of the bank receives after the timed steps, for the channels of dump_channels.  softbits = the soft bits
+    jaero_read_softbits hands over (those of the warm-up and the timed steps, the last step's at the end), concatenated in channel order,
+    softbit_counts = how many of them belong to each channel; status = jaero_read_status after the last step, one row per channel
+    [mse, ebno, freq_est, freq_center, signal, n_estimates]; channels = the channel indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    limit = DUMP_SOFT_BYTES // (4 * len(chans))  # only binds when a single channel's soft bits exceed the limit (very long runs)
+    soft = [soft_by_ch[c][-limit:] for c in chans]
+    status = [bank.read_status(c) for c in chans]
+    arrays = {"channels": np.array(chans, dtype=np.float64),
+              "softbit_counts": np.array([len(x) for x in soft], dtype=np.float64),
+              "softbits": np.concatenate(soft).astype(np.float32),
+              "status": np.array([[s.mse, s.ebno, s.freq_est, s.freq_center, s.signal, s.n_estimates] for s in status], dtype=np.float64)}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def oracle_check(O, fb, pcm_by_ch, n_pre, soft_by_ch, bits_by_ch, chunk):
@@ -1386,7 +1427,7 @@ def other_workloads_pass(channels: int):
     t_all = time.time()
     for name, args, steps in OTHER_WORKLOADS:
         cmd = [sys.executable, os.path.abspath(__file__)] + ["--warmup", "2"] + args + ["--steps", str(steps or ARGS.other_steps), "--channels", str(channels), "--no-cpu-baseline",
-                                                                    "--as-written", "0", "--no-other-workloads", "--sustain", "0", "--gpus", "1"]
+                                                                    "--as-written", "0", "--no-other-workloads", "--sustain", "0", "--gpus", "1", "--full"]
         t0 = time.time()
         try:
             env = dict(os.environ)
@@ -1420,6 +1461,7 @@ def main():
     rank, world, local, dev, shared = setup_ranks()
     local = dev.index
     nch, chunk, K, W = ARGS.channels, ARGS.chunk, ARGS.steps, ARGS.warmup
+    full = ARGS.full
     lo, _ = jd.shard_range(nch * world, rank, world)
     stream = torch.cuda.current_stream().cuda_stream
 
@@ -1432,7 +1474,7 @@ def main():
     # them, so that the device has been at this load for ~--sustain seconds when the clock starts (a step of a 65536-channel bank is ~23 ms).
     est_step_s = 0.023 * max(nch, 4096) / 65536.0 * (1.5 if fb == 8400 else 1.0)
     S = int(np.ceil(ARGS.sustain / est_step_s)) if ARGS.sustain > 0 else 0
-    check = spread_channels(nch, ARGS.check_channels) if ARGS.check_channels > 0 else []
+    check = spread_channels(nch, ARGS.check_channels) if full and ARGS.check_channels > 0 else []
     cidx = torch.tensor(check, dtype=torch.long, device=dev)
     host_pcm = {c: [] for c in check}
 
@@ -1443,8 +1485,9 @@ def main():
                 host_pcm[c].append(cols[j])
 
     free0, hbm_total = torch.cuda.mem_get_info(dev.index)
+    softcap = int((W + K) * chunk * fb / 48000) + 64
     bank = DemodulatorBank(OqpskSettings(fb=fb, lockingbw=fb, coarsefreqest_fft_power=14), nch, device=local,
-                           ebno=bool(ARGS.ebno), max_write_samples=chunk, softbit_capacity=int((W + K) * chunk * fb / 48000) + 64)
+                           ebno=bool(ARGS.ebno), max_write_samples=chunk, softbit_capacity=softcap)
     free1, _ = torch.cuda.mem_get_info(dev.index)
     bytes_per_channel = max(free0 - free1, 1) / float(nch)
     step_bytes = chunk * nch * 2
@@ -1480,20 +1523,23 @@ def main():
         if i < S:
             bank.discard_softbits(stream)  # the soft bits of the sustain steps (the warm-up's and the timed steps' are the ones kept and checked)
 
-    dt, dts = run_timed(step, W, K, world, dev, before_timed=lambda: bank.profile_enable(True), sustain=S)
+    dt, dts = run_timed(step, W, K, world, dev, before_timed=(lambda: bank.profile_enable(True)) if full else None, sustain=S, state=full)
 
     samp_ms, samp_n = bank.profile_read(0)
     coarse_ms, coarse_n = bank.profile_read(1)
     kernel_names = {"sample_loop": bank.profile_kernel(0), "coarse_freq": bank.profile_kernel(1)}
     total_samples = float(K) * chunk * nch * world
     value = total_samples / dt / 1e6
-    soft_by_ch = {c: bank.read_softbits(c, cap=1 << 22) for c in check}
+    dump = dump_channels(nch, softcap) if ARGS.dump_outputs and rank == 0 else []
+    soft_by_ch = {c: bank.read_softbits(c, cap=softcap) for c in sorted(set(check) | set(dump))}
     locked = sum(int(bank.read_status(c).signal) for c in check)
+    if dump:
+        dump_outputs(ARGS.dump_outputs, bank, dump, soft_by_ch)
 
     edge = None
-    if world > 1 and shared:
+    if full and world > 1 and shared:
         edge = {"skipped": "ranks share a device: the control plane is gloo, the RCCL edge operations need one GPU per rank"}
-    elif world > 1:
+    elif full and world > 1:
         # the two edge operations of the path (north_star: "RCCL over xGMI used only to fan out shared IQ and gather decoded bits"),
         # once, untimed for the metric: rank 0 scatters one step of frames for ALL ranks' channels, rank 0 gathers every channel's
         # soft bits of the run
@@ -1522,11 +1568,12 @@ def main():
         dist.barrier()
     bank.close()
     del pcm
-    torch.cuda.empty_cache()
+    if full:
+        torch.cuda.empty_cache()  # room for the as-written banks
 
     # BASELINE configs as written: configs[2] / configs[1] at N = 1, configs[4] (32768 channels over 8 GPUs = 4096 per GPU) at N > 1
     as_written = None
-    if ARGS.as_written and fb == 10500:
+    if full and ARGS.as_written and fb == 10500:
         try:
             if world == 1:
                 as_written = {"configs[2] 4096-channel 10.5 kbps OQPSK": small_bank_run("oqpsk", 4096, chunk, K, W, dev, local),
@@ -1548,33 +1595,13 @@ def main():
     # The C-ABI edge operations LAST among the things that need every rank (the as-written banks above still use the control plane): if RCCL hangs in there,
     # every rank times out in the check's closing all-reduce, rank 0 prints the measured line with the failure in it, and all ranks leave without a barrier.
     edge_c = None
-    if world > 1 and shared:
+    if full and world > 1 and shared:
         edge_c = {"ok": None, "skipped": "ranks share a device (RCCL refuses two ranks on one GPU)"}
-    elif world > 1:
+    elif full and world > 1:
         edge_c = edge_c_abi_check(rank, world, dev)
 
     if rank == 0:
         with_eb = bool(ARGS.ebno)
-        b_samp = ALG_BYTES_SAMPLE_KERNEL + (ALG_BYTES_SAMPLE_KERNEL_EBNO if with_eb else 0.0)
-        if fb == 8400:
-            b_samp += 16.0  # the prefiltered complex sample the loop reads instead of forming PCM x mixer2 (k_pre8400_fir writes it: charged there)
-        dom = "sample_loop" if samp_ms >= coarse_ms else "coarse_freq"
-        per_sample = b_samp if dom == "sample_loop" else ALG_BYTES_COARSE_KERNEL
-        dom_ms = samp_ms if dom == "sample_loop" else coarse_ms
-        ms_per_step = dom_ms / K                       # this kernel's time per step (HIP events on the launch stream inside jaero_write)
-        samples_per_step = float(chunk) * nch           # what its launches of one step process together (this rank)
-        achieved = per_sample * samples_per_step / (ms_per_step * 1e-3) / 1e9
-        traffic, traffic_from = measured_traffic("pmc_summary.json" if fb != 8400 else "pmc_summary_8400.json", dom, kernel_names[dom], nch)
-        # fp64 side roof: the reference's arithmetic is ~350 fp64 flops per sample in the sample loop and 3 x 5 N log2 N
-        # per estimate (N = 2^14, one estimate per 4096 samples and channel) = 840 per sample; 78.6 TFLOP/s fp64 vector peak
-        fl_samp, fl_coarse = 350.0, 3.0 * 5.0 * 16384 * 14 / 4096.0
-        fp64 = {"bound": "fp64_valu", "peak": 78.6e12, "unit": "FLOP/s",
-                "achieved": round((fl_samp + fl_coarse) * value * 1e6 / world, 1), "frac": round((fl_samp + fl_coarse) * value * 1e6 / world / 78.6e12, 5),
-                "flops_per_sample": {"sample_loop": fl_samp, "coarse_freq": fl_coarse},
-                "per_kernel_frac": {"sample_loop": round(fl_samp * samples_per_step / (samp_ms / K * 1e-3) / 78.6e12, 5),
-                                    "coarse_freq": round(fl_coarse * samples_per_step / (coarse_ms / K * 1e-3) / 78.6e12, 5) if coarse_ms else None},
-                "note": "algorithmic flops (FMA = 2), not issued instructions: see roofline_fp64_issue"}
-        issue = issue_roofline({"sample_loop": samp_ms / K, "coarse_freq": coarse_ms / K}, kernel_names, nch)
         name = "10.5 kbps" if fb == 10500 else "8400 bps (C channel)"
         cfg_name = ("BASELINE configs[2] shape" if world == 1 else f"BASELINE configs[4] shape: {nch * world} channels sharded over {world} GPUs")
         line = {
@@ -1594,18 +1621,40 @@ def main():
                        "hbm_bytes_per_resident_channel": int(bytes_per_channel),
                        "resident_channels_max": int(hbm_total / bytes_per_channel),
                        "whole_path_hbm_frac_at_163B_per_sample": round(value * 1e6 * ALG_BYTES_WHOLE_PATH / 1e9 / (HBM_PEAK_GBS * world), 5),
-                       "kernel_ms_per_step": {"sample_loop": round(samp_ms / K, 4), "coarse_freq": round(coarse_ms / K, 4)},
-                       "kernel_ms_total": {"sample_loop": round(samp_ms, 3), "coarse_freq": round(coarse_ms, 3)},
-                       "kernel_launches": {"sample_loop": samp_n, "coarse_freq": coarse_n}, "kernels": kernel_names,
-                       "locked_of_checked": locked, "channels_checked": len(check)},
-            "roofline": {"bound": "hbm", "kernel": dom, "kernel_name": kernel_names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_from": traffic_from,
-                         "alg_bytes_per_sample": per_sample, "samples_per_step": samples_per_step, "kernel_ms_per_step": round(ms_per_step, 4),
-                         "launches_per_step": round((samp_n if dom == "sample_loop" else coarse_n) / float(K), 2),
-                         "note": "achieved = alg_bytes_per_sample x samples_per_step / kernel_ms_per_step (HIP events on the launch stream)"},
-            "roofline_fp64": fp64,
-            "roofline_fp64_issue": issue,
+                       "kernels": kernel_names},
         }
+        if full:  # the kernels were timed (HIP events inside jaero_write) only in a --full run
+            b_samp = ALG_BYTES_SAMPLE_KERNEL + (ALG_BYTES_SAMPLE_KERNEL_EBNO if with_eb else 0.0)
+            if fb == 8400:
+                b_samp += 16.0  # the prefiltered complex sample the loop reads instead of forming PCM x mixer2 (k_pre8400_fir writes it: charged there)
+            dom = "sample_loop" if samp_ms >= coarse_ms else "coarse_freq"
+            per_sample = b_samp if dom == "sample_loop" else ALG_BYTES_COARSE_KERNEL
+            dom_ms = samp_ms if dom == "sample_loop" else coarse_ms
+            ms_per_step = dom_ms / K                       # this kernel's time per step (HIP events on the launch stream inside jaero_write)
+            samples_per_step = float(chunk) * nch           # what its launches of one step process together (this rank)
+            achieved = per_sample * samples_per_step / (ms_per_step * 1e-3) / 1e9
+            traffic, traffic_from = measured_traffic("pmc_summary.json" if fb != 8400 else "pmc_summary_8400.json", dom, kernel_names[dom], nch)
+            # fp64 side roof: the reference's arithmetic is ~350 fp64 flops per sample in the sample loop and 3 x 5 N log2 N
+            # per estimate (N = 2^14, one estimate per 4096 samples and channel) = 840 per sample; 78.6 TFLOP/s fp64 vector peak
+            fl_samp, fl_coarse = 350.0, 3.0 * 5.0 * 16384 * 14 / 4096.0
+            fp64 = {"bound": "fp64_valu", "peak": 78.6e12, "unit": "FLOP/s",
+                    "achieved": round((fl_samp + fl_coarse) * value * 1e6 / world, 1), "frac": round((fl_samp + fl_coarse) * value * 1e6 / world / 78.6e12, 5),
+                    "flops_per_sample": {"sample_loop": fl_samp, "coarse_freq": fl_coarse},
+                    "per_kernel_frac": {"sample_loop": round(fl_samp * samples_per_step / (samp_ms / K * 1e-3) / 78.6e12, 5),
+                                        "coarse_freq": round(fl_coarse * samples_per_step / (coarse_ms / K * 1e-3) / 78.6e12, 5) if coarse_ms else None},
+                    "note": "algorithmic flops (FMA = 2), not issued instructions: see roofline_fp64_issue"}
+            issue = issue_roofline({"sample_loop": samp_ms / K, "coarse_freq": coarse_ms / K}, kernel_names, nch)
+            line["config"].update({"kernel_ms_per_step": {"sample_loop": round(samp_ms / K, 4), "coarse_freq": round(coarse_ms / K, 4)},
+                                   "kernel_ms_total": {"sample_loop": round(samp_ms, 3), "coarse_freq": round(coarse_ms, 3)},
+                                   "kernel_launches": {"sample_loop": samp_n, "coarse_freq": coarse_n},
+                                   "locked_of_checked": locked, "channels_checked": len(check)})
+            line["roofline"] = {"bound": "hbm", "kernel": dom, "kernel_name": kernel_names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_from": traffic_from,
+                                "alg_bytes_per_sample": per_sample, "samples_per_step": samples_per_step, "kernel_ms_per_step": round(ms_per_step, 4),
+                                "launches_per_step": round((samp_n if dom == "sample_loop" else coarse_n) / float(K), 2),
+                                "note": "achieved = alg_bytes_per_sample x samples_per_step / kernel_ms_per_step (HIP events on the launch stream)"}
+            line["roofline_fp64"] = fp64
+            line["roofline_fp64_issue"] = issue
         line["config"].update(rank_fields(world, shared, dts, float(K) * chunk * nch))
         if edge:
             line["config"]["edge_collectives"] = edge
@@ -1613,7 +1662,7 @@ def main():
             line["config"]["edge_collectives_c_abi"] = edge_c
         if as_written:
             line["config"]["as_written"] = as_written
-        if world == 1 and fb == 10500 and not ARGS.no_other_workloads:
+        if full and world == 1 and fb == 10500 and not ARGS.no_other_workloads:
             try:
                 line["config"]["other_workloads"] = other_workloads_pass(nch)
             except Exception as e:
@@ -1632,7 +1681,7 @@ def main():
                 raise
             except Exception as e:
                 line["config"]["oracle_check"] = {"error": str(e)}
-        if world == 1 and not ARGS.no_cpu_baseline:
+        if full and world == 1 and not ARGS.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline_continuous(chunk, fb)
             except Exception as e:  # never lose the GPU line because the CPU leg failed
@@ -1645,6 +1694,8 @@ def main():
 
 if __name__ == "__main__":
     ARGS = parse()
+    if ARGS.dump_outputs and ARGS.workload not in ("oqpsk", "oqpsk8400"):
+        raise SystemExit(f"bench.py: --dump-outputs is implemented for the continuous OQPSK workloads, not for --workload {ARGS.workload}")
     maybe_spawn()
     if ARGS.workload in ("burst_oqpsk", "burst_msk"):
         burst_bench(ARGS.workload == "burst_msk")

@@ -2,7 +2,7 @@
 # A/B of the lane skew in k_oqpsk_fb: same box, same library, JAERO_FB_SKEW=0 against the default; with --timing-phases 1 (all
 # channels symbol-synchronous) as the bound of what aligning the lanes can give.   usage: scripts/diag/skew_ab.sh <tag> [tests]
 TAG=${1:-skew}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; cd "$GRAFT_REPO_ROOT"
-B="--steps 12 --warmup 4 --no-cpu-baseline --as-written 0 --check-channels 16 --no-other-workloads --sustain 1 --no-state"
+B="--steps 12 --warmup 4 --no-cpu-baseline --as-written 0 --check-channels 16 --no-other-workloads --sustain 1 --no-state --full"
 if [[ " $* " == *" tests "* ]]; then
   timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_recording.py tests/test_c_abi.py -m gpu -x -q 2>&1 | tail -5 | tee "$OUT/pytest.log"
 fi

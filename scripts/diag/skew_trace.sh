@@ -1,7 +1,7 @@
 #!/bin/bash
 # phase traces (FB_TRACE, profiles/r5_fb_trace.md) of the sample loop with and without the lane skew, and of the library before it
 TAG=${1:-skewtr}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; cd "$GRAFT_REPO_ROOT"
-B="--steps 12 --warmup 4 --no-cpu-baseline --as-written 0 --check-channels 0 --no-other-workloads --sustain 0 --no-state"
+B="--steps 12 --warmup 4 --no-cpu-baseline --as-written 0 --check-channels 0 --no-other-workloads --sustain 0 --no-state --full"
 run() { # name lib skew extra
   JAERO_HIP_LIB=$2 JAERO_FB_SKEW=$3 timeout 300 python bench.py $B $4 2> "$OUT/err_$1.txt" | tail -1 > "$OUT/line_$1.json"
   python - "$OUT/line_$1.json" "$1" <<'PY'

@@ -4,7 +4,7 @@
 # usage: scripts/gpu_round.sh <tag> [bench flags...]
 set -u
 TAG=${1:-run}; shift || true
-BFLAGS="$*"
+BFLAGS="--full $*"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp

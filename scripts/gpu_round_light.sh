@@ -2,6 +2,7 @@
 # Bench line (with the CPU baseline) + rocprofv3 kernel stats of one workload, no test suite, no PMC.  usage: scripts/gpu_round_light.sh <tag> [bench flags]
 set -u
 TAG=${1:-light}; shift || true
+set -- --full "$@"  # the long form of the line: per-kernel figures, checks, CPU baseline
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 ( timeout 600 python bench.py "$@" 2> "$OUT/bench.err" | tail -1 ) > "$OUT/bench_line.json"; cat "$OUT/bench_line.json"

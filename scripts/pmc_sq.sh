@@ -2,6 +2,7 @@
 # SQ issue / wait counters of the two headline kernels (kernel-trace + --pmc only).  usage: scripts/pmc_sq.sh <tag> [bench flags]
 set -u
 TAG=${1:-sq}; shift || true
+set -- --full "$@"  # the long form of the line: per-kernel figures, checks, CPU baseline
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp; cd /tmp
 KRE='k_oqpsk|k_msk|k_coarse|k_burst|k_hilbert|k_trident|k_pre8400|k_viterbi|k_aerol'
 timeout 200 rocprofv3 --kernel-trace --kernel-include-regex "$KRE" --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU --output-format csv -d "$OUT/a" -o pmc -- python "$GRAFT_REPO_ROOT/bench.py" "$@" --no-cpu-baseline > "$OUT/a.log" 2>&1

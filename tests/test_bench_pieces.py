@@ -81,3 +81,35 @@ def test_emit_attaches_what_run_timed_recorded(bench, capsys, tmp_path, monkeypa
     assert out["step_ms"]["n"] == 20 and out["config"]["sustain_steps"] == 130
     assert os.path.exists(os.path.join(str(tmp_path), "gpurun_out", "bench_details.json"))
     bench.MEAS.clear()
+
+
+def test_dump_outputs_are_a_fixed_sample_within_64_mb(bench, tmp_path, monkeypatch):
+    """--dump-outputs: the same channels for the same arguments, float32 / float64 files, at most 64 MB in all; a channel whose soft bits alone
+    exceed the limit keeps its last ones."""
+    import numpy as np
+
+    class Status:
+        mse, ebno, freq_est, freq_center, signal, n_estimates = 0.25, 9.5, 8001.5, 8000.0, 1, 7
+
+    class Bank:
+        def read_status(self, c):
+            return Status()
+
+    for W, K in ((12, 24), (5, 200), (0, 100000)):
+        cap = int((W + K) * 4096 * 10500 / 48000) + 64
+        ch = bench.dump_channels(65536, cap)
+        assert ch == bench.dump_channels(65536, cap) and ch == sorted(set(ch)) and 0 <= ch[0] and ch[-1] < 65536
+        assert len(ch) == 1 or 4 * cap * len(ch) <= bench.DUMP_SOFT_BYTES
+    cap = int(36 * 4096 * 10500 / 48000) + 64
+    ch = bench.dump_channels(65536, cap)
+    soft = {c: np.full(cap, c % 256, dtype=np.int16) for c in ch}
+    bench.dump_outputs(str(tmp_path / "d"), Bank(), ch, soft)
+    files = {f[:-4]: np.load(str(tmp_path / "d" / f)) for f in os.listdir(str(tmp_path / "d"))}
+    assert sorted(files) == ["channels", "softbit_counts", "softbits", "status"]
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(str(tmp_path / "d" / (f + ".npy"))) for f in files) <= 64_000_000
+    assert files["channels"].tolist() == ch and files["softbit_counts"].sum() == len(files["softbits"]) == cap * len(ch)
+    assert files["softbits"][cap * 3] == ch[3] % 256 and files["status"].shape == (len(ch), 6) and files["status"][0, 4] == 1.0
+    monkeypatch.setattr(bench, "DUMP_SOFT_BYTES", 4000)
+    bench.dump_outputs(str(tmp_path / "e"), Bank(), [5], {5: np.arange(5000, dtype=np.int16)})
+    assert np.load(str(tmp_path / "e" / "softbits.npy")).tolist() == list(range(4000, 5000))

@@ -21,6 +21,8 @@ from conftest import assert_soft_bytes, load_golden
 
 NAME = "recording_burst_oqpsk_10k5"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the first 3.5 s (the ID3 tag and 134 whole frames) of the reference's samples/10.5k_burst_sample.mp3: what the decoder tests below read
+MP3_HEAD = os.path.join(ROOT, "tests", "golden", "10.5k_burst_sample_head.mp3")
 
 
 def burst_rows(packets):
@@ -61,10 +63,8 @@ def test_oracle_matches_reference_on_the_burst_recording(oracle_mod):
 
 
 def test_the_mp3_decoder_reproduces_the_fixture():
-    """Where the reference tree and scipy are present: the first two seconds of the fixture come out of the MP3 file again (guards the decoder)."""
-    path = "/root/reference/samples/10.5k_burst_sample.mp3"
-    if not os.path.exists(path):
-        pytest.skip("reference samples not present on this machine")
+    """Where scipy is present: the first two seconds of the fixture come out of the MP3 file again (guards the decoder)."""
+    path = MP3_HEAD
     scipy_signal = pytest.importorskip("scipy.signal")
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     import mp3_decode
@@ -81,9 +81,7 @@ def test_the_mp3_decoder_reproduces_the_fixture():
 
 def test_mp3_decoder_rejects_a_damaged_table():
     """The self-check the decoder's correctness rests on: with ONE code length of ONE Huffman table changed the recording no longer decodes cleanly."""
-    path = "/root/reference/samples/10.5k_burst_sample.mp3"
-    if not os.path.exists(path):
-        pytest.skip("reference samples not present on this machine")
+    path = MP3_HEAD
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     import importlib
 

@@ -1,8 +1,6 @@
 """CPU: the burst-demodulator restatement (oracle/jaero_oracle_burst.c) pinned against what the UNMODIFIED reference emitted
 (tests/golden/burst_*.npz, made by oracle/_ref) and, where oracle/_ref can run, against the reference itself on fresh cases.
 Bit-exact: soft bits (incl. the -1 start-of-burst markers) and every SignalStatus / EbNo / Plottables emission."""
-import os
-
 import numpy as np
 import pytest
 
@@ -129,14 +127,8 @@ def test_burst_oqpsk_random_vs_ref(R):
 
 @pytest.mark.parametrize("f", ["1200bps_burst_sample1", "1200bps_burst_sample2"])
 def test_bundled_recordings(oracle_mod, f):
-    """The reference's bundled 1200 bps burst recordings through the burst MSK demodulator (inputs stay in /root/reference)."""
-    path = f"/root/reference/samples/{f}.wav"
-    if not os.path.exists(path):
-        pytest.skip("reference samples not present on this machine")
-    import wave
-
-    w = wave.open(path)
-    x = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16)
+    """The reference's bundled 1200 bps burst recordings through the burst MSK demodulator (their PCM: tests/golden/<f>_pcm.npz)."""
+    x = load_golden(f + "_pcm")["pcm"]
     g = load_golden(f + "_burstmsk")
     assert int(g["nsamples"]) == len(x)
     o = oracle_mod.run_burst(oracle_mod.burst_msk_settings(), x, chunk=4096)

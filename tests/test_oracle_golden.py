@@ -1,6 +1,5 @@
 """CPU: the C restatement (oracle/) must reproduce, bit for bit, what the UNMODIFIED reference emitted for the
 committed golden inputs (tests/golden/*.npz, produced by oracle/_ref via tests/golden/make_golden.py)."""
-import os
 
 import numpy as np
 import pytest
@@ -30,16 +29,10 @@ def test_oracle_matches_reference_golden(oracle_mod, name):
 
 @pytest.mark.parametrize("name", ["1200bps_burst_sample1", "1200bps_burst_sample2"])
 def test_oracle_on_bundled_recordings(oracle_mod, name):
-    """The reference's own sample recordings (continuous MSK demod over burst audio): needs /root/reference."""
-    path = f"/root/reference/samples/{name}.wav"
-    if not os.path.exists(path):
-        pytest.skip("reference samples not present on this machine")
-    import wave
-
+    """The reference's own sample recordings (continuous MSK demod over burst audio); their PCM is tests/golden/<name>_pcm.npz."""
     O = oracle_mod
     g = load_golden(name + "_contmsk")
-    w = wave.open(path)
-    x = np.frombuffer(w.readframes(w.getnframes()), dtype=np.int16)
+    x = load_golden(name + "_pcm")["pcm"]
     assert len(x) == int(g["nsamples"])
     r = O.run_demod(O.msk_settings(), x)
     assert np.array_equal(r["soft"], g["soft"])
