@@ -94,28 +94,18 @@ extern "C" void jaero_aerol_destroy(jaero_aerol_ctx *c)
 #include "aerolc.h"
 static void aerolc_free(jaero_aerol_ctx *c) { delete (aerolc_state *)c->cmode; c->cmode = nullptr; }
 
-static int aerol_create(int device, int nchannels, int fb, int max_softbits_per_write, int su_capacity, int burst, jaero_aerol_ctx **out)
+// aerol_create behind `new jaero_aerol_ctx`: what it allocated before a failure goes with jaero_aerol_destroy
+static int aerol_init(jaero_aerol_ctx *c, int nchannels, int fb, int max_softbits_per_write, int su_capacity, int burst)
 {
-    if (!out || nchannels <= 0 || max_softbits_per_write <= 0) return fail(JAERO_EINVAL, "jaero_aerol_create: bad arguments");
-    *out = nullptr;
-    const bool cmode = fb == 8400 && !burst; // C channel (aerolc.h)
-    if (fb != 600 && fb != 1200 && fb != 10500 && !cmode) return fail(JAERO_ENOTSUP, "jaero_aerol_create: fb must be 600, 1200, 10500 or (continuous mode) 8400");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(JAERO_ENODEV, "device %d out of range", device);
-    HIPCHK(hipSetDevice(device));
-    jaero_aerol_ctx *c = new jaero_aerol_ctx();
-    c->device = device;
-    if (cmode)
+    int rc;
+    if (fb == 8400 && !burst) // C channel (aerolc.h)
     {
-        int rc = aerolc_create(c, nchannels, su_capacity);
-        if (!rc) rc = aalloc(c, &c->d_soft, (size_t)nchannels * max_softbits_per_write);
-        if (!rc) rc = aalloc(c, &c->d_counts, (size_t)(nchannels + 63) / 64 * 64);
-        if (rc) { jaero_aerol_destroy(c); return rc; }
+        if ((rc = aerolc_create(c, nchannels, su_capacity))) return rc;
+        if ((rc = aalloc(c, &c->d_soft, (size_t)nchannels * max_softbits_per_write))) return rc;
+        if ((rc = aalloc(c, &c->d_counts, (size_t)(nchannels + 63) / 64 * 64))) return rc;
         c->stage_stride = max_softbits_per_write;
         c->g.nch = nchannels; c->g.nchp = (nchannels + 63) / 64 * 64; c->g.fb = fb;
         HIPCHK(hipDeviceSynchronize());
-        *out = c;
         return 0;
     }
     AGeom &g = c->g;
@@ -140,8 +130,7 @@ static int aerol_create(int device, int nchannels, int fb, int max_softbits_per_
     g.info_cap = g.NumberOfBits / 16 + 16;
     if (su_capacity <= 0) su_capacity = burst ? 256 : 32 * (g.NumberOfBits / 2 / 96) + 8; // 32 frames (burst: 256 packet rows) between reads
     g.su_cap = su_capacity; g.ev_cap = 256;
-    int rc;
-#define AA(ptr, count) do { if ((rc = aalloc(c, &(ptr), (size_t)(count)))) { jaero_aerol_destroy(c); return rc; } } while (0)
+#define AA(ptr, count) do { if ((rc = aalloc(c, &(ptr), (size_t)(count)))) return rc; } while (0)
     AA(c->p.I, (size_t)AI_NFIELDS * g.nchp);
     AA(c->p.rx, (size_t)g.nchp * g.blocksz);
     AA(c->p.deint, (size_t)g.nchp * g.blocksz);
@@ -209,6 +198,23 @@ static int aerol_create(int device, int nchannels, int fb, int max_softbits_per_
         HIPCHK(hipMemcpy(c->p.events, ev.data(), ev.size() * sizeof(long long), hipMemcpyHostToDevice));
     }
     HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
+static int aerol_create(int device, int nchannels, int fb, int max_softbits_per_write, int su_capacity, int burst, jaero_aerol_ctx **out)
+{
+    if (!out || nchannels <= 0 || max_softbits_per_write <= 0) return fail(JAERO_EINVAL, "jaero_aerol_create: bad arguments");
+    *out = nullptr;
+    if (fb != 600 && fb != 1200 && fb != 10500 && !(fb == 8400 && !burst))
+        return fail(JAERO_ENOTSUP, "jaero_aerol_create: fb must be 600, 1200, 10500 or (continuous mode) 8400");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(JAERO_ENODEV, "device %d out of range", device);
+    HIPCHK(hipSetDevice(device));
+    jaero_aerol_ctx *c = new jaero_aerol_ctx();
+    c->device = device;
+    const int rc = aerol_init(c, nchannels, fb, max_softbits_per_write, su_capacity, burst);
+    if (rc) { jaero_aerol_destroy(c); return rc; }
     *out = c;
     return 0;
 }

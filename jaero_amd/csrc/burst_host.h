@@ -104,6 +104,13 @@ static void burst_fill_geometry(BGeom &g, const jaero_settings &s, int nch, unsi
     g.hist_len = (g.hil_lat + 2 * g.hil_ntaps + max_write + 64 + 3) & ~3;
 }
 
+template <int FIRN, int LDSN>
+static KernelRec<BurstDemodFn> burst_msk_rec(const BGeom &g, bool cs)
+{
+    return {cs ? k_burst_msk_fb<true, FIRN, LDSN> : k_burst_msk_fb<false, FIRN, LDSN>, g.ngroups, 128, bmsk_fb_lds_bytes<FIRN, LDSN>(g.d8_len), 0, "k_burst_msk_fb"};
+}
+
+// jaero_create of a burst bank, behind `new jaero_ctx`: what it allocated before a failure goes with jaero_destroy
 static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, const hipDeviceProp_t &prop, int softbit_capacity)
 {
     const jaero_settings &s0 = sets[0];
@@ -141,13 +148,10 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
     DA(p.evlog, (size_t)nchp * g.ev_cap * 3);
     DA(c->d_pcm_raw, (size_t)c->max_write * nch);
     DA(c->d_status, nchp);
-    c->tri_grid = 2 * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256); // two 256-thread workgroups per CU
-    if (c->tri_grid > nchp) c->tri_grid = nchp;
     if (!oq && ((g.agc2_len | g.eb_len) & 7))
         return fail(JAERO_ENOTSUP, "burst MSK at fb %g / Fs %g: the AGC2 / EbNo windows (%d, %d entries) are not whole cells of eight", g.fb, g.Fs, g.agc2_len, g.eb_len);
     if (oq && ((int)floor((0.25 * g.fb) / (g.Fs / (double)TRI_N) + 0.5)) % 4 != 0)
         return fail(JAERO_ENOTSUP, "burst OQPSK at fb %g / Fs %g: k_trident searches one residue class of bins at a time and needs round(fb / 4 / hzperbin) to be a multiple of 4", g.fb, g.Fs);
-    c->tri_lds = TRI_XCH * (int)sizeof(double); // wg_fft13_e32's exchange buffer (k_trident; one residue class of trident differences shares it)
     double2 *d_cis = nullptr, *d_tw = nullptr, *d_tw15 = nullptr;
     double *d_taps = nullptr, *d_hil = nullptr;
     DA(d_cis, JD_WTSIZE); DA(d_tw, TRI_H); DA(d_tw15, TRI_H); DA(d_taps, 2 * g.fir_n); DA(d_hil, g.hil_ntaps / 4);
@@ -189,8 +193,7 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
         std::vector<double> gk(N, 0.0);
         for (int k = 1; k < N; k += 2) gk[k] = (2.0 / ((double)N)) / (tan(M_PI * (((double)k) / ((double)N) - 0.5)));
         double2 *dH = nullptr, *dtw = nullptr;
-        if ((rc = fft4096_tables(gk, &dH, &dtw, (const void *)k_hilbert_fft))) return rc;
-        c->allocs.push_back(dH); c->allocs.push_back(dtw);
+        if ((rc = fft4096_tables(c, gk, &dH, &dtw, (const void *)k_hilbert_fft))) return rc;
         p.hilH = dH; p.tw12 = dtw;
         if (g.hil_ntaps != 2048) return fail(JAERO_ENOTSUP, "the overlap-save Hilbert kernel is built for QJHilbertFilter's 2048 taps");
     }
@@ -231,24 +234,17 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
     c->o_nrx = p.I + (size_t)BI_NRX * nchp;
     c->m.nch = nch; c->m.nchp = nchp;
     c->m.flags.assign(nchp, 0);
-    // burst OQPSK: BD_LDSN (36) of its 55 history slots + the taps in LDS; burst MSK: 39 of 80 (1200 bps) or all 160 (600 bps) slots
-    const int lds = oq ? (2 * BD_LDSN * 64 + 64) * (int)sizeof(double) : 2 * (g.fir_n == 80 ? BMSK_FB_LDSN_80 : BMSK_FB_LDSN_160) * 64 * (int)sizeof(double) + BMSK_FB_MAIL_BYTES + BMSK_FB_WC_BYTES(g.fir_n == 80) + BMSK_FB_D8_BYTES(g.fir_n == 80, g.d8_len);
-    if (oq)
-    {
-        HIPCHK(hipFuncSetAttribute((const void *)k_burst_oqpsk_demod<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipFuncSetAttribute((const void *)k_burst_oqpsk_demod<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    else
-    {
-        if (g.fir_n != 80 && g.fir_n != 160) return fail(JAERO_ENOTSUP, "burst MSK matched filter of %d taps has no kernel", g.fir_n);
-        // front / back wavefront pairs (k_burst_msk_fb.h): 72 of 80 (two pairs per CU) or 152 of 160 history slots in LDS + 4 KiB of mailboxes
-        HIPCHK(hipFuncSetAttribute((const void *)k_burst_msk_fb<false, 80, BMSK_FB_LDSN_80>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipFuncSetAttribute((const void *)k_burst_msk_fb<true, 80, BMSK_FB_LDSN_80>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipFuncSetAttribute((const void *)k_burst_msk_fb<false, 160, BMSK_FB_LDSN_160>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIPCHK(hipFuncSetAttribute((const void *)k_burst_msk_fb<true, 160, BMSK_FB_LDSN_160>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
-    HIPCHK(hipFuncSetAttribute((const void *)k_trident<true>, hipFuncAttributeMaxDynamicSharedMemorySize, c->tri_lds));
-    HIPCHK(hipFuncSetAttribute((const void *)k_trident<false>, hipFuncAttributeMaxDynamicSharedMemorySize, c->tri_lds));
+    // the tracking kernel: burst OQPSK keeps BD_LDSN of its 55 history slots and the taps in LDS (k_burst_demod.h); burst MSK runs front / back
+    // wavefront pairs (k_burst_msk_fb.h) with 48 of 80 (1200 bps) or 128 of 160 (600 bps) history slots, the mailboxes and the write-combining cells in LDS
+    const bool cs = (c->flags & JAERO_FLAG_CAPTURE_SYMBOLS) != 0;
+    if (oq) c->bdemod = {cs ? k_burst_oqpsk_demod<true> : k_burst_oqpsk_demod<false>, ng, 64, bd_lds_bytes(), 0, "k_burst_oqpsk_demod"};
+    else if (g.fir_n == 80) c->bdemod = burst_msk_rec<80, BMSK_FB_LDSN_80>(g, cs);
+    else { assert(g.fir_n == 160); c->bdemod = burst_msk_rec<160, BMSK_FB_LDSN_160>(g, cs); } // validate_settings: 600 or 1200 bps at 48 kHz
+    // k_trident: two 256-thread workgroups per CU, wg_fft13_e32's exchange buffer in LDS (one residue class of trident differences shares it)
+    const int tri_grid = 2 * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
+    c->trident = {oq ? k_trident<true> : k_trident<false>, tri_grid < nchp ? tri_grid : nchp, TRI_THREADS, TRI_XCH * (int)sizeof(double), 0, "k_trident"};
+    HIPCHK(set_lds_attribute(c->bdemod));
+    HIPCHK(set_lds_attribute(c->trident));
     HIPCHK(hipDeviceSynchronize());
     return 0;
 }
@@ -275,8 +271,8 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         LAUNCHCHK("the burst history push");
         prof_end(c, pi, st);
     }
-    const bool cs = (c->flags & JAERO_FLAG_CAPTURE_SYMBOLS) != 0;
-    const int lds = g.kind == JAERO_KIND_BURST_OQPSK ? (2 * 39 * 64 + 64) * (int)sizeof(double) : 2 * (g.fir_n == 80 ? BMSK_FB_LDSN_80 : BMSK_FB_LDSN_160) * 64 * (int)sizeof(double) + BMSK_FB_MAIL_BYTES + BMSK_FB_WC_BYTES(g.fir_n == 80) + BMSK_FB_D8_BYTES(g.fir_n == 80, g.d8_len);
+    const KernelRec<TridentFn> &tri = c->trident;
+    const KernelRec<BurstDemodFn> &dm = c->bdemod;
     int first = 1;
     c->poisoned = true; // the history push above is idempotent (same slots if the write is repeated); from here on state advances
     for (int pos = 0; pos < nsamples;)
@@ -303,29 +299,11 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         LAUNCHCHK("k_ev_compact");
         prof_end(c, pi, st);
         pi = prof_begin(c, 1, st);
-        if (g.kind == JAERO_KIND_BURST_OQPSK) hipLaunchKernelGGL(k_trident<true>, dim3(c->tri_grid), dim3(TRI_THREADS), c->tri_lds, st, g, p, n0);
-        else hipLaunchKernelGGL(k_trident<false>, dim3(c->tri_grid), dim3(TRI_THREADS), c->tri_lds, st, g, p, n0);
+        hipLaunchKernelGGL(tri.fn, dim3(tri.grid), dim3(tri.block), tri.lds, st, g, p, n0);
         LAUNCHCHK("k_trident");
         prof_end(c, pi, st);
         pi = prof_begin(c, 0, st);
-        if (g.kind == JAERO_KIND_BURST_OQPSK)
-        {
-            if (cs) hipLaunchKernelGGL((k_burst_oqpsk_demod<true>), dim3(g.ngroups), dim3(64), lds, st, g, p, n, n0, first);
-            else hipLaunchKernelGGL((k_burst_oqpsk_demod<false>), dim3(g.ngroups), dim3(64), lds, st, g, p, n, n0, first);
-        }
-        else
-        {
-            if (g.fir_n == 80)
-            {
-                if (cs) hipLaunchKernelGGL((k_burst_msk_fb<true, 80, BMSK_FB_LDSN_80>), dim3(g.ngroups), dim3(128), lds, st, g, p, n, n0, first);
-                else hipLaunchKernelGGL((k_burst_msk_fb<false, 80, BMSK_FB_LDSN_80>), dim3(g.ngroups), dim3(128), lds, st, g, p, n, n0, first);
-            }
-            else
-            {
-                if (cs) hipLaunchKernelGGL((k_burst_msk_fb<true, 160, BMSK_FB_LDSN_160>), dim3(g.ngroups), dim3(128), lds, st, g, p, n, n0, first);
-                else hipLaunchKernelGGL((k_burst_msk_fb<false, 160, BMSK_FB_LDSN_160>), dim3(g.ngroups), dim3(128), lds, st, g, p, n, n0, first);
-            }
-        }
+        hipLaunchKernelGGL(dm.fn, dim3(dm.grid), dim3(dm.block), dm.lds, st, g, p, n, n0, first);
         LAUNCHCHK("the burst demodulator");
         prof_end(c, pi, st);
         first = 0;

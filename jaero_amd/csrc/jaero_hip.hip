@@ -9,12 +9,14 @@
 //   * launch [sample kernel] [coarse kernel] [sample kernel] ... on the caller's stream.
 // No CPU fallback exists: without a HIP device jaero_create fails.
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/jaero_hip.h"
 #include "jaero_device.h"
@@ -60,10 +62,9 @@ static int fail(int code, const char *fmt, ...)
         if (_e != hipSuccess) return fail(JAERO_EHIP, "launch of %s failed: %s (%s:%d)", what, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
-#define OQ_LDSN 39 // matched-filter history slots kept in LDS (rest in VGPRs) + the taps: 39.5 KiB per wavefront -> 4 wavefronts per CU
-#define MSK_LDSN_1200 39 // of 80 taps: four wavefronts per CU (rings + the wavefront's copy of the taps: 39.6 KiB)
-#define MSK_LDSN_40 24   // of 40 taps (1200 bps at 24 kHz, 600 bps at 12 kHz)
-#define MSK_LDSN_20 12   // of 20 taps (1200 bps at 12 kHz)
+// k_msk_samples: matched-filter history slots kept in LDS (the rest in VGPRs)
+#define MSK_LDSN_40 24 // of 40 taps (1200 bps at 24 kHz, 600 bps at 12 kHz)
+#define MSK_LDSN_20 12 // of 20 taps (1200 bps at 12 kHz)
 
 struct ProfSlot { double ms = 0; int launches = 0; };
 
@@ -136,6 +137,26 @@ struct Mirror
     }
 };
 
+// One hot-path kernel of a bank as jaero_create / burst_create chose it: the instantiation, its launch shape, the dynamic LDS it is given
+// (set as its attribute at create and requested by every launch, from this one number) and the name bench.py finds its counters under in
+// profiles/ (jaero_profile_kernel).  What decides the choice is fixed for the bank's life: the flags, the bank's size, the rate -- a rate
+// change creates a new bank (rebank_with_carry_over, burst_rebank) and with it new records.
+template <class Fn>
+struct KernelRec
+{
+    Fn fn = nullptr;
+    int grid = 0; // workgroups (the coarse estimate: at most that many, persistent over the list)
+    int block = 0;
+    int lds = 0;  // dynamic LDS bytes
+    int ldsn = 0; // sample loop: filter history slots in LDS (a launch's first ring slot = B-parts so far mod ldsn)
+    const char *name = "";
+};
+using OqpskSampleFn = void (*)(JGeom, JPtrs, const int16_t *, int, int, int, int, int, JTaps28, const double2 *, int);
+using MskSampleFn = void (*)(JGeom, JPtrs, const int16_t *, int, int, int, int, int, int, int);
+using CoarseFn = void (*)(JGeom, JPtrs, const int *, int, const double2 *);
+using BurstDemodFn = void (*)(BGeom, BPtrs, int, long long, int);
+using TridentFn = void (*)(BGeom, BPtrs, long long);
+
 struct jaero_ctx
 {
     int device = 0;
@@ -150,19 +171,18 @@ struct jaero_ctx
     int16_t *d_pcm_raw = nullptr;    // [nch*max_write] staging for host input
     double2 *d_tw = nullptr;
     int *d_emitted = nullptr; // burst banks: per-channel count of soft bits already emitted (jaero_softbits_view)
-    int msk_ldsn = 0; // MSK: matched-filter inputs kept in LDS (the rest of fir_n in registers)
     std::vector<int> dly_t0; // MSK: shared delay-line slot at which each channel's delayedsmpl pointer last restarted (jaero_set_settings)
-    int msk_pairs = 0; // MSK with an 80-tap filter: front/back pairs per workgroup of k_msk_fb (0 = k_msk_samples)
-    int oq_pairs = 0; // 10.5 kbps OQPSK: front/back pairs per workgroup of k_oqpsk_fb (0 = the single-wavefront kernel k_oqpsk_samples)
-    int oq_ldsn = OQ_LDSN;
+    // the sample loop (OQPSK: k_oqpsk_fb; MSK: k_msk_fb, or k_msk_samples for 40 and 20 taps) and the coarse estimate (k_coarse6*)
+    KernelRec<OqpskSampleFn> oq_loop;
+    KernelRec<MskSampleFn> msk_loop;
+    KernelRec<CoarseFn> coarse;
     JTaps28 oq_taps{}; // the 28 distinct values of the (bitwise symmetric) 55-tap RRC, scalar operands of k_oqpsk_fb's filter
     // fb == 8400 (k_pre8400.h): prefilter buffers, samples written so far, size of the previous write
-    bool pre8400 = false, pre_direct = false;
+    bool pre8400 = false;
     JPre pre{};
     long long pre_n0 = 0;
     int pre_nprev = 0;
     int *d_chanlist = nullptr;
-    int coarse2_grid = 0; // workgroups of the persistent coarse-estimate kernels = CUs (k_coarse6_13: twice that)
     jaero_status *d_status = nullptr;
     int16_t *d_pack = nullptr; size_t pack_elems = 0;
     // host mirrors
@@ -172,7 +192,8 @@ struct jaero_ctx
     bool burst = false;
     BGeom bg{};
     BPtrs bp{};
-    int tri_grid = 0, tri_lds = 0;
+    KernelRec<BurstDemodFn> bdemod; // k_burst_oqpsk_demod or k_burst_msk_fb
+    KernelRec<TridentFn> trident;
     long long nsamples_total = 0; // samples written so far (uniform ring slots and event time stamps derive from it)
     int bt_hold_left = 0;         // burst: samples behind the last jaero_set_settings for which k_burst_front<true> must run (bt_d1 refilled with zeros)
     // generic views of the per-channel output buffers (either kind)
@@ -289,12 +310,6 @@ __global__ void k_status_burst(const BGeom g, const BPtrs p, int ch_first, int n
     st.signal = p.I[(size_t)BI_STARTSTOP * nchp + ch] > 0 ? 1 : 0; // between SignalStatus(true) and SignalStatus(false)
     st.n_estimates = p.I[(size_t)BI_EV_CNT * nchp + ch];
     out[k] = st;
-}
-
-__global__ void k_fill_int(int *p, int n, int v)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
 }
 
 // ------------------------------------------------------------------------------------------ helpers
@@ -451,9 +466,25 @@ static void fill_geometry(JGeom &g, const jaero_settings &s, int nch, unsigned f
     g.win_len = ((flags & JAERO_FLAG_EBNO) && g.ebno_len > g.agc_len) ? g.ebno_len : g.agc_len;
 }
 
-// Tables of the overlap-save filters (k_pre8400_fft, k_hilbert_fft): H = DFT_4096(taps, zero-padded) / 4096 and exp(-2 pi i k / 4096),
-// summed in long double on the host.  kernel_fn = the kernel whose dynamic LDS limit is raised to the 128 KiB exchange buffer.
-static int fft4096_tables(const std::vector<double> &taps, double2 **d_H, double2 **d_tw, const void *kernel_fn)
+template <class Fn>
+static hipError_t set_lds_attribute(const KernelRec<Fn> &r)
+{
+    return hipFuncSetAttribute((const void *)r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds);
+}
+
+// f(EBNO, CAPSYM) with the bank's two flags as std::true_type / std::false_type: the instantiation of a kernel family that serves the bank
+template <class F>
+static auto by_flags(unsigned flags, F f)
+{
+    const std::true_type y;
+    const std::false_type n;
+    const bool eb = (flags & JAERO_FLAG_EBNO) != 0, cs = (flags & JAERO_FLAG_CAPTURE_SYMBOLS) != 0;
+    return eb ? (cs ? f(y, y) : f(y, n)) : (cs ? f(n, y) : f(n, n));
+}
+
+// Tables of the overlap-save filters (k_pre8400_fft, k_hilbert_fft), in buffers of the bank: H = DFT_4096(taps, zero-padded) / 4096 and
+// exp(-2 pi i k / 4096), summed in long double on the host.  kernel_fn = the kernel whose dynamic LDS limit is raised to the 128 KiB exchange buffer.
+static int fft4096_tables(jaero_ctx *c, const std::vector<double> &taps, double2 **d_H, double2 **d_tw, const void *kernel_fn)
 {
     const int N = 2 * PRE_L;
     std::vector<long double> cr(N), ci(N);
@@ -466,8 +497,8 @@ static int fft4096_tables(const std::vector<double> &taps, double2 **d_H, double
         H[k].x = (double)(sr / N); H[k].y = (double)(si / N);
         tw[k].x = (double)cr[k]; tw[k].y = (double)ci[k];
     }
-    HIPCHK(hipMalloc((void **)d_H, sizeof(double2) * N));
-    HIPCHK(hipMalloc((void **)d_tw, sizeof(double2) * N));
+    int rc;
+    if ((rc = dalloc(c, d_H, N, false)) || (rc = dalloc(c, d_tw, N, false))) return rc;
     HIPCHK(hipMemcpy(*d_H, H.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(*d_tw, tw.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute(kernel_fn, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * PRE_L * (int)sizeof(double)));
@@ -528,54 +559,80 @@ extern "C" void jaero_destroy(jaero_ctx *c)
     delete c;
 }
 
-static void launch_pre8400_filter(const JGeom &g, const JPtrs &p, const JPre &q, int n, long long n0, bool direct, hipStream_t st)
+static void launch_pre8400_filter(const JGeom &g, const JPtrs &p, const JPre &q, int n, long long n0, hipStream_t st)
 {
-    (void)direct;
     hipLaunchKernelGGL(k_pre8400_fft, dim3(g.nchp / 4, (int)(((n0 + n - 1) >> 11) - (n0 >> 11) + 1)), dim3(PF_THREADS), 4 * 2 * PRE_L * (int)sizeof(double), st, g, p, q, n, n0);
 }
 
-extern "C" int jaero_create(int device, int nchannels, const jaero_settings *settings, int per_channel_stride, unsigned flags,
-                            int max_write_samples, int softbit_capacity, jaero_ctx **out)
+// The sample-loop records: front / back pair kernels (k_oqpsk_fb.h, k_msk_fb.h) and the single-wavefront MSK kernel (k_msk.h)
+template <int PAIRS, bool PRE8400>
+static KernelRec<OqpskSampleFn> oqpsk_fb_rec(const JGeom &g, unsigned flags)
 {
-    if (!out || !settings || nchannels <= 0 || max_write_samples <= 0) return fail(JAERO_EINVAL, "jaero_create: bad arguments");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(JAERO_ENODEV, "device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(JAERO_ENODEV, "device %d is %s; libjaero_hip is built for gfx950 (MI355X) only", device, prop.gcnArchName);
+    return {by_flags(flags, [](auto E, auto C) -> OqpskSampleFn { return k_oqpsk_fb<55, FB_LDSN, E, C, PAIRS, PRE8400>; }), (g.ngroups + PAIRS - 1) / PAIRS,
+            PAIRS * 128, PAIRS * fb_pair_doubles<FB_LDSN>() * (int)sizeof(double), FB_LDSN, "k_oqpsk_fb<"};
+}
+template <int FIRN, int LDSN, int PAIRS, int TB>
+static KernelRec<MskSampleFn> msk_fb_rec(const JGeom &g, unsigned flags)
+{
+    return {by_flags(flags, [](auto E, auto C) -> MskSampleFn { return k_msk_fb<FIRN, LDSN, E, C, PAIRS, TB>; }), (g.ngroups + PAIRS - 1) / PAIRS,
+            PAIRS * 128, PAIRS * mfb_pair_doubles<FIRN, LDSN, TB>() * (int)sizeof(double), LDSN, "k_msk_fb<"};
+}
+template <int FIRN, int LDSN>
+static KernelRec<MskSampleFn> msk_samples_rec(const JGeom &g, unsigned flags)
+{
+    return {by_flags(flags, [](auto E, auto C) -> MskSampleFn { return k_msk_samples<FIRN, LDSN, E, C>; }), g.ngroups, 64, msk_samples_lds_bytes<FIRN, LDSN>(),
+            LDSN, "k_msk_samples<"};
+}
 
-    auto sat = [&](int ch) -> const jaero_settings & {
-        return per_channel_stride ? *(const jaero_settings *)((const char *)settings + (size_t)ch * per_channel_stride) : settings[0];
-    };
-    const jaero_settings &s0 = sat(0);
-    int rc = validate_settings(s0);
-    if (rc) return rc;
-    for (int ch = 1; ch < nchannels; ch++)
+// The continuous bank's sample-loop and coarse-estimate kernels, with their LDS attributes
+static int choose_kernels(jaero_ctx *c, int ncu)
+{
+    const JGeom &g = c->g;
+    const bool big = g.ngroups > 2 * ncu;
+    if (g.kind == JAERO_KIND_OQPSK)
     {
-        const jaero_settings &s = sat(ch);
-        if (s.kind != s0.kind || s.fb != s0.fb || s.Fs != s0.Fs || s.coarsefreqest_fft_power != s0.coarsefreqest_fft_power)
-            return fail(JAERO_EINVAL, "channel %d: kind/fb/Fs/fft_power must match channel 0 within one bank", ch);
-        if ((rc = validate_settings(s))) return rc;
+        // front / back pairs (k_oqpsk_fb.h; at 8400 bps the two halves take turns, see there).  Four pairs per workgroup put one front and one
+        // back wavefront on every SIMD of a CU -- worth it once there are more channel groups than two per CU; smaller banks get one pair per
+        // workgroup (two SIMDs per 64 channels).
+        if (c->pre8400) c->oq_loop = big ? oqpsk_fb_rec<4, true>(g, c->flags) : oqpsk_fb_rec<1, true>(g, c->flags);
+        else c->oq_loop = big ? oqpsk_fb_rec<4, false>(g, c->flags) : oqpsk_fb_rec<1, false>(g, c->flags);
+        HIPCHK(set_lds_attribute(c->oq_loop));
     }
+    else
+    {
+        switch (g.fir_n) // 2 Fs / fb taps: validate_settings admits only the rates that give 160, 80, 40 or 20
+        {
+        case 160: // two pairs per workgroup, each wavefront alone on a SIMD (k_msk_fb.h, MFB2_*)
+            c->msk_loop = msk_fb_rec<160, MFB2_LDSN, 2, MFB2_TB>(g, c->flags);
+            break;
+        case 80:
+            // front / back pairs (k_msk_fb.h).  Banks of at most two channel groups per CU: one pair per workgroup, the halves on different
+            // SIMDs, 36 history entries per arm in LDS and 44 in registers (256 channels: 82 -> 113 Msamples/s).  Larger banks: four pairs per
+            // workgroup, each pair on one SIMD, 32 entries in LDS, 26 in the front half's and the 22 oldest in the back half's registers
+            // (65 536 channels: 9.2 -> 10.6 Gsamples/s).
+            c->msk_loop = big ? msk_fb_rec<80, MFB4_LDSN, 4, MFB4_TB>(g, c->flags) : msk_fb_rec<80, MFB_LDSN, 1, MFB1_TB>(g, c->flags);
+            break;
+        case 40: c->msk_loop = msk_samples_rec<40, MSK_LDSN_40>(g, c->flags); break;
+        default: assert(g.fir_n == 20); c->msk_loop = msk_samples_rec<20, MSK_LDSN_20>(g, c->flags);
+        }
+        HIPCHK(set_lds_attribute(c->msk_loop));
+    }
+    // register-resident FFTs persistent over the estimate list (k_coarse6.h): 2^14 = 32 x 32 x 16 on one 512-thread workgroup per CU (the whole
+    // register file, ~130 KiB of LDS; at 8400 bps the window table behind it), 2^13 = 32 x 16 x 16 on 256 threads, two workgroups per CU
+    if (g.nfft_log2 == 13) c->coarse = {k_coarse6_13, 2 * ncu, 256, C6_XCH13 * (int)sizeof(double), 0, "k_coarse6_13"};
+    else if (c->pre8400) c->coarse = {k_coarse6_w8400, ncu, C2_THREADS, (C6_XCH + C4_TABN) * (int)sizeof(double), 0, "k_coarse6_w8400"};
+    else c->coarse = {k_coarse6, ncu, C2_THREADS, C6_XCH * (int)sizeof(double), 0, "k_coarse6"};
+    HIPCHK(set_lds_attribute(c->coarse));
+    return 0;
+}
 
-    jaero_ctx *c = new jaero_ctx();
-    c->device = device;
-    c->flags = flags;
-    c->max_write = max_write_samples;
-    c->soft_cap_req = softbit_capacity;
-    if (s0.kind >= JAERO_KIND_BURST_MSK)
-    {
-        std::vector<jaero_settings> all(nchannels);
-        for (int ch = 0; ch < nchannels; ch++) all[ch] = sat(ch);
-        rc = burst_create(c, all, prop, softbit_capacity);
-        if (rc) { jaero_destroy(c); return rc; }
-        *out = c;
-        return 0;
-    }
+// jaero_create of a continuous bank, behind `new jaero_ctx`: what it allocated before a failure goes with jaero_destroy
+static int bank_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, const hipDeviceProp_t &prop, int softbit_capacity)
+{
+    const jaero_settings &s0 = sets[0];
+    const int nchannels = (int)sets.size(), max_write_samples = c->max_write;
+    const unsigned flags = c->flags;
+    int rc = 0;
     fill_geometry(c->g, s0, nchannels, flags);
     JGeom &g = c->g;
     if (softbit_capacity <= 0)
@@ -585,8 +642,7 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
     g.log_cap = (flags & JAERO_FLAG_STATUS_LOG) ? (int)ceil(g.soft_cap * g.Fs / g.fb / (g.nfft / 4)) + 16 : 0;
     const int nchp = g.nchp, ng = g.ngroups;
 
-#define DA(ptr, count)                                              \
-    do { if ((rc = dalloc(c, &(ptr), (size_t)(count)))) { jaero_destroy(c); return rc; } } while (0)
+#define DA(ptr, count) do { if ((rc = dalloc(c, &(ptr), (size_t)(count)))) return rc; } while (0)
     DA(c->p.S, (size_t)S_NFIELDS * nchp);
     DA(c->p.I, (size_t)I_NFIELDS * nchp);
     DA(c->p.win, (size_t)ng * g.win_len * 64);
@@ -612,19 +668,17 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
         double *d_pre_taps = nullptr;
         DA(d_pre_taps, PRE_K);
         const std::vector<double> pt = rrc_design(0.6, 2048, g.Fs, g.fb / 2); // rrc_pre_imp (oqpskdemodulator.cpp:281)
-        if ((int)pt.size() != PRE_K) { jaero_destroy(c); return fail(JAERO_EHIP, "prefilter design returned %zu taps", pt.size()); }
+        if ((int)pt.size() != PRE_K) return fail(JAERO_EHIP, "prefilter design returned %zu taps", pt.size());
         HIPCHK(hipMemcpy(d_pre_taps, pt.data(), sizeof(double) * PRE_K, hipMemcpyHostToDevice));
         c->pre.taps = d_pre_taps;
-        {
-            double2 *dH = nullptr, *dtw = nullptr;
-            if ((rc = fft4096_tables(pt, &dH, &dtw, (const void *)k_pre8400_fft))) { jaero_destroy(c); return rc; }
-            c->pre.H = dH; c->pre.tw = dtw;
-            c->allocs.push_back(dH); c->allocs.push_back(dtw);
-            c->pre_direct = false; // (the time-domain form k_pre8400_fir and its A/B switch left the library in round 3)
-        }
-        HIPCHK(hipFuncSetAttribute((const void *)k_coarse6_w8400, hipFuncAttributeMaxDynamicSharedMemorySize, (C6_XCH + C4_TABN) * (int)sizeof(double)));
+        double2 *dH = nullptr, *dtw = nullptr;
+        if ((rc = fft4096_tables(c, pt, &dH, &dtw, (const void *)k_pre8400_fft))) return rc;
+        c->pre.H = dH; c->pre.tw = dtw;
     }
     if (g.kind == JAERO_KIND_MSK) { DA(c->p.dly, (size_t)ng * (g.sps + 1) * 64); DA(c->p.dly8, (size_t)ng * (g.sps2 + 1) * 64); }
+    // k_oqpsk_fb keeps the symbol-instant windows marg / dt / pm / msema in one combined record ring
+    static_assert(JD_SYMREC_LEN == 800, "the combined symbol-record ring of k_oqpsk_fb assumes the reference's window lengths (800 / 400 / 400 / 400)");
+    if (g.kind == JAERO_KIND_OQPSK) DA(c->p.symrec, (size_t)nchp * JD_SYMREC_LEN * 8);
     DA(c->p.soft, (size_t)nchp * g.soft_cap);
     if (g.sym_cap) DA(c->p.sym, (size_t)nchp * g.sym_cap * 3);
     if (g.log_cap) DA(c->p.slog, (size_t)nchp * g.log_cap * 6);
@@ -632,9 +686,6 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
     DA(c->d_pcm_raw, (size_t)max_write_samples * nchannels);
     DA(c->d_chanlist, nchp);
     DA(c->d_status, nchp);
-    {
-        c->coarse2_grid = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
     DA(c->d_tw, g.nfft);
     double2 *d_cis = nullptr;
     double *d_taps = nullptr;
@@ -666,11 +717,11 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
         std::vector<double> t2(2 * g.fir_n);
         for (int i = 0; i < 2 * g.fir_n; i++) t2[i] = taps[i % g.fir_n];
         HIPCHK(hipMemcpy(d_taps, t2.data(), sizeof(double) * t2.size(), hipMemcpyHostToDevice));
-        if (g.kind == JAERO_KIND_OQPSK && g.fir_n == 55)
+        if (g.kind == JAERO_KIND_OQPSK)
         {
-            bool sym = true;
-            for (int i = 0; i < 55; i++) sym = sym && memcmp(&taps[i], &taps[54 - i], sizeof(double)) == 0;
-            c->oq_pairs = sym ? -1 : 0; // -1: front/back pairs allowed (decided below); 0: asymmetric taps -> the single-wavefront kernel reads them from LDS
+            for (int i = 0; i < 55; i++)
+                if (memcmp(&taps[i], &taps[54 - i], sizeof(double)) != 0)
+                    return fail(JAERO_ENOTSUP, "matched-filter taps are not bitwise symmetric: k_oqpsk_fb takes the 28 distinct taps as scalar arguments");
             for (int i = 0; i < 28; i++) c->oq_taps.t[i] = taps[i];
         }
     }
@@ -681,7 +732,7 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
         c->settings.resize(nchp);
         for (int ch = 0; ch < nchp; ch++)
         {
-            const jaero_settings &s = sat(ch < nchannels ? ch : 0);
+            const jaero_settings &s = sets[ch < nchannels ? ch : 0];
             c->settings[ch] = s;
             init_channel_scalars(c, s, S, I, ch, true);
         }
@@ -694,84 +745,46 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
     c->o_overflow = c->p.I + (size_t)I_OVERFLOW * nchp; c->o_flags = c->p.I + (size_t)I_FLAGS * nchp;
     c->m.nch = nchannels; c->m.nchp = nchp; c->m.nfft = g.nfft; c->m.Fs_int = g.Fs_int;
     c->m.flags.assign(nchp, 0); c->m.bbptr.assign(nchp, 0); c->m.cnt.assign(nchp, 0);
-    // dynamic LDS for the matched-filter rings
-    if (g.kind == JAERO_KIND_MSK)
-    {
-        if (g.fir_n != 20 && g.fir_n != 40 && g.fir_n != 80 && g.fir_n != 160)
-            return fail(JAERO_ENOTSUP, "MSK matched filter of %d taps (fb %g at Fs %g) has no kernel", g.fir_n, g.fb, g.Fs);
-#define MSK_ATTR(F, L) \
-    { \
-        const int lds_bytes = (2 * (L) * 64 + (F)) * (int)sizeof(double); \
-        HIPCHK(hipFuncSetAttribute((const void *)k_msk_samples<F, L, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)); \
-        HIPCHK(hipFuncSetAttribute((const void *)k_msk_samples<F, L, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)); \
-        HIPCHK(hipFuncSetAttribute((const void *)k_msk_samples<F, L, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)); \
-        HIPCHK(hipFuncSetAttribute((const void *)k_msk_samples<F, L, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)); \
-    }
-        c->msk_ldsn = g.fir_n == 40 ? MSK_LDSN_40 : MSK_LDSN_20; // 80 / 160 taps: set with the pair kernel below
-        if (g.fir_n == 40) MSK_ATTR(40, MSK_LDSN_40) else if (g.fir_n == 20) MSK_ATTR(20, MSK_LDSN_20) // 80 and 160 taps: k_msk_fb below
-#undef MSK_ATTR
-        if (g.fir_n == 160)
-        {
-            // 160 taps: two pairs per workgroup, each wavefront alone on a SIMD (k_msk_fb.h, MFB2_*)
-            c->msk_pairs = 2;
-            c->msk_ldsn = MFB2_LDSN;
-#define MFA(E, C) HIPCHK(hipFuncSetAttribute((const void *)k_msk_fb<160, MFB2_LDSN, E, C, 2, MFB2_TB>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * mfb_pair_doubles<160, MFB2_LDSN, MFB2_TB>() * (int)sizeof(double)))
-            MFA(false, false); MFA(false, true); MFA(true, false); MFA(true, true);
-#undef MFA
-        }
-        if (g.fir_n == 80)
-        {
-            // front / back pairs (k_msk_fb.h).  Banks of at most two channel groups per CU: one pair per workgroup, the halves on different
-            // SIMDs, 36 history entries per arm in LDS and 44 in the front half's registers (256 channels: 82 -> 113 Msamples/s).  Larger
-            // banks: four pairs per workgroup, each pair on one SIMD, 32 entries in LDS, 26 in the front half's and the 22 oldest in the
-            // back half's registers (65 536 channels: 9.2 -> 10.6 Gsamples/s).
-            const int ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            c->msk_pairs = g.ngroups > 2 * ncu ? 4 : 1;
-            if (c->msk_pairs == 1)
-            {
-                c->msk_ldsn = MFB_LDSN;
-#define MFA(E, C) HIPCHK(hipFuncSetAttribute((const void *)k_msk_fb<80, MFB_LDSN, E, C, 1, MFB1_TB>, hipFuncAttributeMaxDynamicSharedMemorySize, mfb_pair_doubles<80, MFB_LDSN, MFB1_TB>() * (int)sizeof(double)))
-                MFA(false, false); MFA(false, true); MFA(true, false); MFA(true, true);
-#undef MFA
-            }
-            else if (c->msk_pairs == 4)
-            {
-                c->msk_ldsn = MFB4_LDSN;
-#define MFA(E, C) HIPCHK(hipFuncSetAttribute((const void *)k_msk_fb<80, MFB4_LDSN, E, C, 4, MFB4_TB>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * mfb_pair_doubles<80, MFB4_LDSN, MFB4_TB>() * (int)sizeof(double)))
-                MFA(false, false); MFA(false, true); MFA(true, false); MFA(true, true);
-#undef MFA
-            }
-        }
-    }
-    if (g.kind == JAERO_KIND_OQPSK)
-    {
-        // front / back pairs (k_oqpsk_fb.h; at 8400 bps the two halves take turns, see there).  Four pairs per workgroup put one front and one back wavefront on every SIMD of a
-        // CU -- worth it once there are more channel groups than two per CU; smaller banks get one pair per workgroup (two SIMDs per
-        // 64 channels).  (The single-wavefront kernel of round 1 and its A/B switch left the library in round 3.)
-        const int ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        if (!c->oq_pairs) { jaero_destroy(c); return fail(JAERO_ENOTSUP, "matched-filter taps are not bitwise symmetric: k_oqpsk_fb takes the 28 distinct taps as scalar arguments"); }
-        c->oq_pairs = g.ngroups > 2 * ncu ? 4 : 1;
-        static_assert(JD_SYMREC_LEN == 800, "the combined symbol-record ring of k_oqpsk_fb assumes the reference's window lengths (800 / 400 / 400 / 400)");
-        if (c->oq_pairs)
-        {
-            if ((rc = dalloc(c, &c->p.symrec, (size_t)nchp * JD_SYMREC_LEN * 8))) { jaero_destroy(c); return rc; }
-#define FBA(E, C, PP, X) HIPCHK(hipFuncSetAttribute((const void *)k_oqpsk_fb<55, FB_LDSN, E, C, PP, X>, hipFuncAttributeMaxDynamicSharedMemorySize, PP * fb_pair_doubles<FB_LDSN>() * (int)sizeof(double)))
-            if (c->pre8400)
-            {
-                FBA(false, false, 1, true); FBA(false, true, 1, true); FBA(true, false, 1, true); FBA(true, true, 1, true);
-                FBA(false, false, 4, true); FBA(false, true, 4, true); FBA(true, false, 4, true); FBA(true, true, 4, true);
-            }
-            else
-            {
-                FBA(false, false, 1, false); FBA(false, true, 1, false); FBA(true, false, 1, false); FBA(true, true, 1, false);
-                FBA(false, false, 4, false); FBA(false, true, 4, false); FBA(true, false, 4, false); FBA(true, true, 4, false);
-            }
-#undef FBA
-        }
-    }
-    if (g.nfft_log2 == 14) HIPCHK(hipFuncSetAttribute((const void *)k_coarse6, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH * (int)sizeof(double)));
-    else HIPCHK(hipFuncSetAttribute((const void *)k_coarse6_13, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH13 * (int)sizeof(double)));
+    if ((rc = choose_kernels(c, prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256))) return rc;
     HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
+extern "C" int jaero_create(int device, int nchannels, const jaero_settings *settings, int per_channel_stride, unsigned flags,
+                            int max_write_samples, int softbit_capacity, jaero_ctx **out)
+{
+    if (!out || !settings || nchannels <= 0 || max_write_samples <= 0) return fail(JAERO_EINVAL, "jaero_create: bad arguments");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(JAERO_ENODEV, "device %d out of range (%d devices)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(JAERO_ENODEV, "device %d is %s; libjaero_hip is built for gfx950 (MI355X) only", device, prop.gcnArchName);
+
+    std::vector<jaero_settings> sets(nchannels);
+    for (int ch = 0; ch < nchannels; ch++)
+        sets[ch] = per_channel_stride ? *(const jaero_settings *)((const char *)settings + (size_t)ch * per_channel_stride) : settings[0];
+    const jaero_settings &s0 = sets[0];
+    int rc = validate_settings(s0);
+    if (rc) return rc;
+    for (int ch = 1; ch < nchannels; ch++)
+    {
+        const jaero_settings &s = sets[ch];
+        if (s.kind != s0.kind || s.fb != s0.fb || s.Fs != s0.Fs || s.coarsefreqest_fft_power != s0.coarsefreqest_fft_power)
+            return fail(JAERO_EINVAL, "channel %d: kind/fb/Fs/fft_power must match channel 0 within one bank", ch);
+        if ((rc = validate_settings(s))) return rc;
+    }
+
+    jaero_ctx *c = new jaero_ctx();
+    c->device = device;
+    c->flags = flags;
+    c->max_write = max_write_samples;
+    c->soft_cap_req = softbit_capacity;
+    rc = s0.kind >= JAERO_KIND_BURST_MSK ? burst_create(c, sets, prop, softbit_capacity) : bank_create(c, sets, prop, softbit_capacity);
+    if (rc) { jaero_destroy(c); return rc; }
     *out = c;
     return 0;
 }
@@ -1122,100 +1135,42 @@ extern "C" int jaero_profile_read(jaero_ctx *c, int which, double *total_ms, int
 extern "C" int jaero_profile_kernel(jaero_ctx *c, int which, char *buf, int cap)
 {
     if (!c || !buf || cap < 2 || which < 0 || which > 4) return fail(JAERO_EINVAL, "jaero_profile_kernel: bad arguments");
-    const JGeom &g = c->g;
     const char *nm = "";
     if (c->burst)
     {
-        static const char *bn[5] = {"k_burst_oqpsk_demod", "k_trident", "k_hist_push", "k_hilbert_fft", "k_burst_front"};
+        const char *bn[5] = {c->bdemod.name, c->trident.name, "k_hist_push", "k_hilbert_fft", "k_burst_front"};
         nm = bn[which];
-        if (which == 0 && c->bg.kind == JAERO_KIND_BURST_MSK) nm = "k_burst_msk_fb";
     }
-    else if (which == 0)
-    {
-        if (g.kind == JAERO_KIND_OQPSK) nm = "k_oqpsk_fb<";
-        else nm = c->msk_pairs ? "k_msk_fb<" : "k_msk_samples<";
-    }
-    else if (which == 1) nm = (g.nfft_log2 == 14) ? (c->pre8400 ? "k_coarse6_w8400" : "k_coarse6") : "k_coarse6_13";
+    else if (which == 0) nm = c->g.kind == JAERO_KIND_OQPSK ? c->oq_loop.name : c->msk_loop.name;
+    else if (which == 1) nm = c->coarse.name;
     else if (which == 2) nm = "k_transpose_pcm";
     snprintf(buf, (size_t)cap, "%s", nm);
     return 0;
 }
 
 // ------------------------------------------------------------------------------------------ write
-static void launch_samples(jaero_ctx *c, const int16_t *frames, int stride, int n, int skipA, int onlyA, hipStream_t st, int pos)
+// one segment of the sample loop; nb0 = B-parts executed before it (the ring slots it starts at derive from it)
+static void launch_samples(jaero_ctx *c, const int16_t *frames, int stride, int n, int skipA, int onlyA, long long nb0, int pos, hipStream_t st)
 {
     const JGeom &g = c->g;
-    const bool eb = (c->flags & JAERO_FLAG_EBNO) != 0, cs = (c->flags & JAERO_FLAG_CAPTURE_SYMBOLS) != 0;
-    const dim3 grid(g.ngroups), block(64);
     if (g.kind == JAERO_KIND_OQPSK)
     {
-        {
-            // front / back wavefront pairs (k_oqpsk_fb.h): PAIRS pairs per workgroup
-            const int fsb = (int)(c->m.nB_total % FB_LDSN);
-
-            const int P = c->oq_pairs;
-            const dim3 gridp((g.ngroups + P - 1) / P), blockp(P * 128);
-            const int ldsp = P * fb_pair_doubles<FB_LDSN>() * (int)sizeof(double);
-            const double2 *pf = c->pre8400 ? (const double2 *)(c->pre.out + (size_t)pos * 4) : nullptr; // row `pos` of every channel group (JD_G4)
-#define LFB(E, C, PP, X) hipLaunchKernelGGL((k_oqpsk_fb<55, FB_LDSN, E, C, PP, X>), gridp, blockp, ldsp, st, g, c->p, frames, stride, n, skipA, onlyA, fsb, c->oq_taps, pf, c->pre.cap)
-#define LFBP(E, C) { if (c->pre8400) { if (P == 4) LFB(E, C, 4, true); else LFB(E, C, 1, true); } else { if (P == 4) LFB(E, C, 4, false); else LFB(E, C, 1, false); } }
-            if (eb && cs) LFBP(true, true) else if (eb) LFBP(true, false) else if (cs) LFBP(false, true) else LFBP(false, false)
-#undef LFBP
-#undef LFB
-            return;
-        }
-        return; // (c->oq_pairs is always set: jaero_create refuses a bank it could not serve with k_oqpsk_fb)
+        const KernelRec<OqpskSampleFn> &r = c->oq_loop;
+        const double2 *pf = c->pre8400 ? (const double2 *)(c->pre.out + (size_t)pos * 4) : nullptr; // row `pos` of every channel group (JD_G4)
+        hipLaunchKernelGGL(r.fn, dim3(r.grid), dim3(r.block), r.lds, st, g, c->p, frames, stride, n, skipA, onlyA, (int)(nb0 % r.ldsn), c->oq_taps, pf, c->pre.cap);
     }
     else
     {
-        const int ldsn = c->msk_ldsn;
-        const int lds = (2 * ldsn * 64 + g.fir_n) * (int)sizeof(double); // rings + this wavefront's copy of the taps
-        const int fs = (int)(c->m.nB_total % ldsn), ds = (int)(c->m.nB_total % (g.sps + 1)), d8 = (int)(c->m.nB_total % (g.sps2 + 1));
-        if (c->msk_pairs)
-        {
-            const int P = c->msk_pairs;
-            const dim3 gridp((g.ngroups + P - 1) / P), blockp(P * 128);
-            const int ldsp = (P == 4 ? 4 * mfb_pair_doubles<80, MFB4_LDSN, MFB4_TB>() : (P == 2 ? 2 * mfb_pair_doubles<160, MFB2_LDSN, MFB2_TB>() : mfb_pair_doubles<80, MFB_LDSN, MFB1_TB>())) * (int)sizeof(double);
-#define LMF2(E, C) hipLaunchKernelGGL((k_msk_fb<160, MFB2_LDSN, E, C, 2, MFB2_TB>), gridp, blockp, ldsp, st, g, c->p, frames, stride, n, skipA, onlyA, fs, ds, d8)
-            if (P == 2)
-            {
-                if (eb && cs) LMF2(true, true); else if (eb) LMF2(true, false); else if (cs) LMF2(false, true); else LMF2(false, false);
-                return;
-            }
-#undef LMF2
-#define LMF(E, C, PP, LL, TT) hipLaunchKernelGGL((k_msk_fb<80, LL, E, C, PP, TT>), gridp, blockp, ldsp, st, g, c->p, frames, stride, n, skipA, onlyA, fs, ds, d8)
-#define LMFP(E, C) { if (P == 4) LMF(E, C, 4, MFB4_LDSN, MFB4_TB); else LMF(E, C, 1, MFB_LDSN, MFB1_TB); }
-            if (eb && cs) LMFP(true, true) else if (eb) LMFP(true, false) else if (cs) LMFP(false, true) else LMFP(false, false)
-#undef LMFP
-#undef LMF
-            return;
-        }
-#define LM(F, L, E, C) hipLaunchKernelGGL((k_msk_samples<F, L, E, C>), grid, block, lds, st, g, c->p, frames, stride, n, skipA, onlyA, fs, ds, d8)
-#define LMS(F, L) { if (eb && cs) LM(F, L, true, true); else if (eb) LM(F, L, true, false); else if (cs) LM(F, L, false, true); else LM(F, L, false, false); }
-        if (g.fir_n == 40) LMS(40, MSK_LDSN_40) else LMS(20, MSK_LDSN_20) // 80 and 160 taps never get here (k_msk_fb)
-#undef LMS
-#undef LM
+        const KernelRec<MskSampleFn> &r = c->msk_loop;
+        hipLaunchKernelGGL(r.fn, dim3(r.grid), dim3(r.block), r.lds, st, g, c->p, frames, stride, n, skipA, onlyA, (int)(nb0 % r.ldsn), (int)(nb0 % (g.sps + 1)),
+                           (int)(nb0 % (g.sps2 + 1)));
     }
 }
 
 static void launch_coarse(jaero_ctx *c, const int *d_list, int nlist, hipStream_t st)
 {
-    // register-resident FFTs: one 512-thread workgroup per CU (the whole register file, ~130 KiB of LDS), persistent over the list
-    const int grid = nlist < c->coarse2_grid ? nlist : c->coarse2_grid;
-    if (c->g.nfft_log2 == 14)
-    {
-        // 2^14 = 32 x 32 x 16 in registers, two LDS exchanges per transform, one plane at a time in LDS (k_coarse6.h)
-        if (c->pre8400)
-            hipLaunchKernelGGL(k_coarse6_w8400, dim3(grid), dim3(C2_THREADS), (C6_XCH + C4_TABN) * (int)sizeof(double), st, c->g, c->p, d_list, nlist, c->d_tw);
-        else
-            hipLaunchKernelGGL(k_coarse6, dim3(grid), dim3(C2_THREADS), C6_XCH * (int)sizeof(double), st, c->g, c->p, d_list, nlist, c->d_tw);
-    }
-    else
-    {
-        // 2^13 = 32 x 16 x 16 on 256 threads: two workgroups per CU (k_coarse6.h)
-        const int grid2 = nlist < 2 * c->coarse2_grid ? nlist : 2 * c->coarse2_grid;
-        hipLaunchKernelGGL(k_coarse6_13, dim3(grid2), dim3(256), C6_XCH13 * (int)sizeof(double), st, c->g, c->p, d_list, nlist, c->d_tw);
-    }
+    const KernelRec<CoarseFn> &r = c->coarse;
+    hipLaunchKernelGGL(r.fn, dim3(nlist < r.grid ? nlist : r.grid), dim3(r.block), r.lds, st, c->g, c->p, d_list, nlist, c->d_tw);
 }
 
 // Work enqueued on `st` is ordered behind everything the bank enqueued before (on last_stream), and `st` becomes last_stream: the rule for
@@ -1283,7 +1238,7 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
         LAUNCHCHK("k_pre8400_mix");
         hipLaunchKernelGGL(k_pre8400_commit, dim3(g.ngroups), dim3(64), 0, st, g, c->p, c->pre_nprev);
         LAUNCHCHK("k_pre8400_commit");
-        launch_pre8400_filter(g, c->p, c->pre, nsamples, c->pre_n0, c->pre_direct, st);
+        launch_pre8400_filter(g, c->p, c->pre, nsamples, c->pre_n0, st);
         LAUNCHCHK("the 8400 bps prefilter");
         c->pre_n0 += nsamples;
     }
@@ -1292,17 +1247,14 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
     while (pos < nsamples)
     {
         int n = 0, skip_a = 0, only_a = 0;
-        const long long nb_before = c->m.nB_total;
+        const long long nb0 = c->m.nB_total; // ring slots are those at the START of the segment
         const int next = c->m.next_segment(pos, nsamples, n, skip_a, only_a);
         if (n > 0)
         {
-            const long long nb_after = c->m.nB_total;
-            c->m.nB_total = nb_before; // ring slots are those at the START of the segment
             const int pi = prof_begin(c, 0, st);
-            launch_samples(c, frames + (size_t)pos * stride, stride, n, skip_a, only_a, st, pos);
+            launch_samples(c, frames + (size_t)pos * stride, stride, n, skip_a, only_a, nb0, pos, st);
             LAUNCHCHK("the sample loop");
             prof_end(c, pi, st);
-            c->m.nB_total = nb_after;
         }
         if (only_a)
         {
@@ -1439,14 +1391,15 @@ extern "C" int jaero_debug_prefilter(int device, const double *in_reim, int n, d
     HIPCHK(hipMemcpy2D(q.xring, sizeof(double2) * 4, in_reim, sizeof(double2), sizeof(double2), (size_t)n, hipMemcpyHostToDevice)); // channel 0 of every slot (PRE_XI)
     p.cis = d_cis; q.taps = d_taps;
     {
+        jaero_ctx t; // owns the two tables
         double2 *dH = nullptr, *dtw = nullptr;
-        int rc = fft4096_tables(taps, &dH, &dtw, (const void *)k_pre8400_fft);
+        int rc = fft4096_tables(&t, taps, &dH, &dtw, (const void *)k_pre8400_fft);
         if (rc) return rc;
         q.H = dH; q.tw = dtw;
-        launch_pre8400_filter(g, p, q, n, 0LL, false, 0);
+        launch_pre8400_filter(g, p, q, n, 0LL, 0);
         HIPCHK(hipGetLastError());
         HIPCHK(hipDeviceSynchronize());
-        hipFree(dH); hipFree(dtw);
+        for (void *a : t.allocs) hipFree(a);
     }
     HIPCHK(hipMemcpy2D(out_reim, sizeof(double2), q.out, sizeof(double2) * 4, sizeof(double2), (size_t)n, hipMemcpyDeviceToHost));
     hipFree(q.xring); hipFree(q.cidx); hipFree(q.out); hipFree(q.hold); hipFree(d_cis); hipFree(d_taps);

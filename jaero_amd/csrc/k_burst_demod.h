@@ -110,11 +110,13 @@ __device__ __forceinline__ void bd_fir_eval_v(const double *lre, const double *l
 #define BD_HYPOT(x, y) hypot(x, y)
 #define BD_ATAN2(y, x) atan2(y, x)
 #endif
+// dynamic LDS of k_burst_oqpsk_demod: the two rings [BD_LDSN][64] and the 55 taps (64 slots): 37 376 B, four wavefronts per CU
+constexpr int bd_lds_bytes() { return (2 * BD_LDSN * 64 + 64) * (int)sizeof(double); }
 template <bool CAPSYM>
 __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const BPtrs p, int n, long long n0, int first_of_write)
 {
     // matched-filter history as in k_oqpsk.h: the LDSN newest entries of each arm in LDS ([slot][lane]), the FIRN-LDSN oldest in a
-    // VGPR shift register, plus this wavefront's copy of the taps (jd_fir_eval) -> 39.5 KiB of LDS per wavefront, four per CU
+    // VGPR shift register, plus this wavefront's copy of the taps (jd_fir_eval) -> 36.5 KiB of LDS per wavefront (bd_lds_bytes), four per CU
     constexpr int FIRN = 55, LDSN = BD_LDSN, TAILN = FIRN - LDSN;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *lre = lds, *lim = lds + LDSN * 64, *ltap = lds + 2 * LDSN * 64;

@@ -48,6 +48,9 @@ struct BmskMail
 // 128 KiB of filter history); at 1200 bps delayt8's 21 entries per lane live in LDS for the launch (10.5 KiB) and cost HBM nothing per sample
 #define BMSK_FB_WC_BYTES(d8lds) (((d8lds) ? 3 : 4) * 8 * 64 * 8)
 #define BMSK_FB_D8_BYTES(d8lds, d8_len) ((d8lds) ? (d8_len) * 64 * 8 : 0)
+// dynamic LDS of k_burst_msk_fb<CAPSYM, FIRN, LDSN>: the two history rings [LDSN][64], the mailboxes, the cells and (1200 bps) delayt8's ring
+template <int FIRN, int LDSN>
+constexpr int bmsk_fb_lds_bytes(int d8_len) { return 2 * LDSN * 64 * (int)sizeof(double) + BMSK_FB_MAIL_BYTES + BMSK_FB_WC_BYTES(FIRN == 80) + BMSK_FB_D8_BYTES(FIRN == 80, d8_len); }
 
 template <int FIRN, int LDSN>
 __device__ __forceinline__ void bmsk_front(const BGeom &g, const BPtrs &p, double *lre, double *lim, const BmskMail &M, int n, long long n0, int grp, int lane)

@@ -6,14 +6,18 @@
 // PLL weighted by 1-|tanh(err)|, and at symbol instants the decision-directed carrier loop, residual rotation, MSE,
 // soft differential decode (DiffDecode::UpdateSoft) and soft-bit demap.
 //
-// Layout of the matched-filter history (as k_oqpsk_samples): the newest LDSN inputs in an LDS ring, the older
-// FIRN - LDSN in registers as a shift register.  1200 bps: 80 = 39 + 41 -> 39.6 KiB of LDS per wavefront with its copy of
-// the taps, four wavefronts per CU (one per SIMD); 600 bps: 160 = 78 + 82 -> two per CU.  The filter output of a sample does not contain that
+// Runs the 40- and 20-tap filters (MSK at 24 and 12 kHz); 80 and 160 taps run on the front / back pairs of k_msk_fb.h.
+// Layout of the matched-filter history: the newest LDSN inputs in an LDS ring, the older FIRN - LDSN in registers as a shift
+// register, and this wavefront's copy of the taps in LDS behind the ring (msk_samples_lds_bytes).  The filter output of a sample does not contain that
 // sample (the reference evaluates, then inserts), so it is evaluated one iteration ahead, and everything a sample reads
 // from HBM (PCM, the rows leaving the AGC / EbNo windows, the two delay lines) is requested one iteration ahead too:
 // written in reference order, every one of those reads was waited for on the spot, ~8 memory round trips per sample.
 #pragma once
 #include "jaero_device.h"
+
+// dynamic LDS of k_msk_samples<FIRN, LDSN, ...>: the two rings [LDSN][64] and the taps
+template <int FIRN, int LDSN>
+constexpr int msk_samples_lds_bytes() { return (2 * LDSN * 64 + FIRN) * (int)sizeof(double); }
 
 template <int FIRN, int LDSN, bool EBNO, bool CAPSYM>
 __global__ __launch_bounds__(64) void k_msk_samples(const JGeom g, const JPtrs p, const int16_t *__restrict__ pcm, int pcm_stride,

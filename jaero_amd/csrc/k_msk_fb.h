@@ -20,7 +20,7 @@
 // 44-deep tail does not fit, so the history is split three ways (MFB4_*, below).  Measured on an MI355X: 256 channels 82 -> 113
 // Msamples/s, 16 384 channels 4.07 -> 4.94 Gsamples/s, 65 536 channels 9.2 -> 10.6 Gsamples/s (sample loop 15.9 -> 12.1 ms per step); the
 // first four-pair version, with the whole tail in the front half, spilled 458 registers and ran at 6.6.  The 160-tap filter (600 bps
-// at 48 kHz) keeps k_msk_samples.
+// at 48 kHz) runs on two pairs per workgroup (MFB2_*, below); only the 40- and 20-tap filters keep k_msk_samples.
 #pragma once
 #include <type_traits>
 #include "jaero_device.h"
@@ -56,6 +56,7 @@
                      // 28.7 / 28.4 / 30.6 / 31.4 ms per step -- every further version of the 60-term sum is 3 KB more code in a loop that already fills
                      // the instruction cache two CUs share (front half 8 versions x ~600 instructions + back half ~2 600), and that costs more than the moves
 #endif
+static_assert(MFB_LAZY_K >= 1 && MFB_LAZY_K <= 8, "mfb_back spells out the tail phases 0..7 (MFB_TC / MFB_TS): MFB_LAZY_K must be 1..8");
 #ifndef MFB2_TB
 #define MFB2_TB 64 // round 5, with the filter op for op: 40 / 52 / 60 / 68 measured 5 621 / 5 998 / 6 145 / 6 130 Msamples/s at 65 536 channels (60 until round 6);
                    // round 6, with ring blocks of 4 and the tail moved every 2nd sample: 52 / 56 / 60 / 64 / 68 = 28.9 / 28.9 / 27.9 / 27.3 / 28.2 ms per step
@@ -416,6 +417,7 @@ __device__ __forceinline__ void mfb_back(const JGeom &g, const JPtrs &p, const M
                                          int grp, int lane)
 {
     constexpr int TF = FIRN - LDSN - TB;
+    static_assert(TB == 0 || TF >= 2, "the back half takes its first input from the front half's register tail (entry TF - 2): TB must leave it at least two entries");
     // TB > 0: the TB oldest history entries of each arm live in this half's registers.  They do not move one place per sample (60 entries of two arms:
     // ~450 register moves a sample at 600 bps, most of them in and out of accumulation registers -- profiles/r6_msk600_trace.md): entry j (0 = the
     // newest) is at tbr[tb_s + j], a new entry goes in BELOW the others (tb_s - 1), and only when tb_s is 0 do all move up, by KL places at once.
