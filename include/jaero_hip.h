@@ -286,6 +286,15 @@ int jaero_debug_read_prefiltered(jaero_ctx *ctx, int channel, double *out_reim, 
 /* Test hook: the Viterbi decoder picks its layout by size (one block per wavefront below 16 384 blocks, one per lane from there); tests
  * force one so that both meet the oracle at small sizes.  mode: 0 = by size (default), 1 = wave, 2 = lanes.  Process-wide. */
 int jaero_debug_viterbi_layout(int mode);
+/* Test hook: a continuous bank picks its sample-loop layout at jaero_create by size (one front / back pair per workgroup up to two channel
+ * groups per CU, four pairs above); tests force one so that both meet the oracle at small sizes.  mode: 0 = by size (default), 1 = one
+ * pair, 2 = four pairs.  Affects only the kernels chosen by size (k_oqpsk_fb at both rates, k_msk_fb at 80 taps), and only banks created
+ * (or re-created by a rate change) after the call.  Process-wide. */
+int jaero_debug_sample_loop_layout(int mode);
+/* Test hook: the whole instantiation of the kernel this bank launches for class `which` (0 = sample loop / burst demodulator, 1 = coarse
+ * estimate / trident check; jaero_profile_kernel's numbering), spelled as `nm -C` prints it, e.g. "k_oqpsk_fb<55, 36, true, false, 4, false>";
+ * kernels that are not templates give their plain name.  JAERO_EOVERFLOW if it does not fit in cap bytes. */
+int jaero_debug_kernel_variant(jaero_ctx *ctx, int which, char *buf, int cap);
 
 /* ------------------------------------------------------------------------------------------------ multi-GPU edge operations
  * The path shards by channel with no steady-state exchange (the reference runs its two stereo burst channels as two unrelated objects,

@@ -107,7 +107,8 @@ static void burst_fill_geometry(BGeom &g, const jaero_settings &s, int nch, unsi
 template <int FIRN, int LDSN>
 static KernelRec<BurstDemodFn> burst_msk_rec(const BGeom &g, bool cs)
 {
-    return {cs ? k_burst_msk_fb<true, FIRN, LDSN> : k_burst_msk_fb<false, FIRN, LDSN>, g.ngroups, 128, bmsk_fb_lds_bytes<FIRN, LDSN>(g.d8_len), 0, "k_burst_msk_fb"};
+    return {cs ? k_burst_msk_fb<true, FIRN, LDSN> : k_burst_msk_fb<false, FIRN, LDSN>, g.ngroups, 128, bmsk_fb_lds_bytes<FIRN, LDSN>(g.d8_len), 0, "k_burst_msk_fb",
+            instantiation("k_burst_msk_fb", cs, FIRN, LDSN)};
 }
 
 // jaero_create of a burst bank, behind `new jaero_ctx`: what it allocated before a failure goes with jaero_destroy
@@ -237,12 +238,13 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
     // the tracking kernel: burst OQPSK keeps BD_LDSN of its 55 history slots and the taps in LDS (k_burst_demod.h); burst MSK runs front / back
     // wavefront pairs (k_burst_msk_fb.h) with 48 of 80 (1200 bps) or 128 of 160 (600 bps) history slots, the mailboxes and the write-combining cells in LDS
     const bool cs = (c->flags & JAERO_FLAG_CAPTURE_SYMBOLS) != 0;
-    if (oq) c->bdemod = {cs ? k_burst_oqpsk_demod<true> : k_burst_oqpsk_demod<false>, ng, 64, bd_lds_bytes(), 0, "k_burst_oqpsk_demod"};
+    if (oq) c->bdemod = {cs ? k_burst_oqpsk_demod<true> : k_burst_oqpsk_demod<false>, ng, 64, bd_lds_bytes(), 0, "k_burst_oqpsk_demod", instantiation("k_burst_oqpsk_demod", cs)};
     else if (g.fir_n == 80) c->bdemod = burst_msk_rec<80, BMSK_FB_LDSN_80>(g, cs);
     else { assert(g.fir_n == 160); c->bdemod = burst_msk_rec<160, BMSK_FB_LDSN_160>(g, cs); } // validate_settings: 600 or 1200 bps at 48 kHz
     // k_trident: two 256-thread workgroups per CU, wg_fft13_e32's exchange buffer in LDS (one residue class of trident differences shares it)
     const int tri_grid = 2 * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
-    c->trident = {oq ? k_trident<true> : k_trident<false>, tri_grid < nchp ? tri_grid : nchp, TRI_THREADS, TRI_XCH * (int)sizeof(double), 0, "k_trident"};
+    c->trident = {oq ? k_trident<true> : k_trident<false>, tri_grid < nchp ? tri_grid : nchp, TRI_THREADS, TRI_XCH * (int)sizeof(double), 0, "k_trident",
+                  instantiation("k_trident", oq)};
     HIPCHK(set_lds_attribute(c->bdemod));
     HIPCHK(set_lds_attribute(c->trident));
     HIPCHK(hipDeviceSynchronize());

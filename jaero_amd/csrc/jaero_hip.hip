@@ -150,7 +150,20 @@ struct KernelRec
     int lds = 0;  // dynamic LDS bytes
     int ldsn = 0; // sample loop: filter history slots in LDS (a launch's first ring slot = B-parts so far mod ldsn)
     const char *name = "";
+    std::string variant; // the whole instantiation as `nm -C` spells it (test hook jaero_debug_kernel_variant)
 };
+
+// "k<a, b, ...>" with the template arguments spelled as `nm -C` prints them (bool as true / false)
+static std::string targ(bool v) { return v ? "true" : "false"; }
+static std::string targ(int v) { return std::to_string(v); }
+template <class... T>
+static std::string instantiation(const char *kernel, T... args)
+{
+    std::string s = kernel;
+    const char *sep = "<";
+    ((s += sep, s += targ(args), sep = ", "), ...);
+    return s + ">";
+}
 using OqpskSampleFn = void (*)(JGeom, JPtrs, const int16_t *, int, int, int, int, int, JTaps28, const double2 *, int);
 using MskSampleFn = void (*)(JGeom, JPtrs, const int16_t *, int, int, int, int, int, int, int);
 using CoarseFn = void (*)(JGeom, JPtrs, const int *, int, const double2 *);
@@ -564,31 +577,49 @@ static void launch_pre8400_filter(const JGeom &g, const JPtrs &p, const JPre &q,
     hipLaunchKernelGGL(k_pre8400_fft, dim3(g.nchp / 4, (int)(((n0 + n - 1) >> 11) - (n0 >> 11) + 1)), dim3(PF_THREADS), 4 * 2 * PRE_L * (int)sizeof(double), st, g, p, q, n, n0);
 }
 
-// The sample-loop records: front / back pair kernels (k_oqpsk_fb.h, k_msk_fb.h) and the single-wavefront MSK kernel (k_msk.h)
+// The sample-loop records: front / back pair kernels (k_oqpsk_fb.h, k_msk_fb.h) and the single-wavefront MSK kernel (k_msk.h).  The kernel
+// and its spelled-out name come from the same E / C pick of by_flags.
 template <int PAIRS, bool PRE8400>
 static KernelRec<OqpskSampleFn> oqpsk_fb_rec(const JGeom &g, unsigned flags)
 {
-    return {by_flags(flags, [](auto E, auto C) -> OqpskSampleFn { return k_oqpsk_fb<55, FB_LDSN, E, C, PAIRS, PRE8400>; }), (g.ngroups + PAIRS - 1) / PAIRS,
-            PAIRS * 128, PAIRS * fb_pair_doubles<FB_LDSN>() * (int)sizeof(double), FB_LDSN, "k_oqpsk_fb<"};
+    return by_flags(flags, [&](auto E, auto C) -> KernelRec<OqpskSampleFn> {
+        return {k_oqpsk_fb<55, FB_LDSN, E, C, PAIRS, PRE8400>, (g.ngroups + PAIRS - 1) / PAIRS, PAIRS * 128,
+                PAIRS * fb_pair_doubles<FB_LDSN>() * (int)sizeof(double), FB_LDSN, "k_oqpsk_fb<",
+                instantiation("k_oqpsk_fb", 55, FB_LDSN, (bool)E, (bool)C, PAIRS, PRE8400)};
+    });
 }
 template <int FIRN, int LDSN, int PAIRS, int TB>
 static KernelRec<MskSampleFn> msk_fb_rec(const JGeom &g, unsigned flags)
 {
-    return {by_flags(flags, [](auto E, auto C) -> MskSampleFn { return k_msk_fb<FIRN, LDSN, E, C, PAIRS, TB>; }), (g.ngroups + PAIRS - 1) / PAIRS,
-            PAIRS * 128, PAIRS * mfb_pair_doubles<FIRN, LDSN, TB>() * (int)sizeof(double), LDSN, "k_msk_fb<"};
+    return by_flags(flags, [&](auto E, auto C) -> KernelRec<MskSampleFn> {
+        return {k_msk_fb<FIRN, LDSN, E, C, PAIRS, TB>, (g.ngroups + PAIRS - 1) / PAIRS, PAIRS * 128,
+                PAIRS * mfb_pair_doubles<FIRN, LDSN, TB>() * (int)sizeof(double), LDSN, "k_msk_fb<",
+                instantiation("k_msk_fb", FIRN, LDSN, (bool)E, (bool)C, PAIRS, TB)};
+    });
 }
 template <int FIRN, int LDSN>
 static KernelRec<MskSampleFn> msk_samples_rec(const JGeom &g, unsigned flags)
 {
-    return {by_flags(flags, [](auto E, auto C) -> MskSampleFn { return k_msk_samples<FIRN, LDSN, E, C>; }), g.ngroups, 64, msk_samples_lds_bytes<FIRN, LDSN>(),
-            LDSN, "k_msk_samples<"};
+    return by_flags(flags, [&](auto E, auto C) -> KernelRec<MskSampleFn> {
+        return {k_msk_samples<FIRN, LDSN, E, C>, g.ngroups, 64, msk_samples_lds_bytes<FIRN, LDSN>(), LDSN, "k_msk_samples<",
+                instantiation("k_msk_samples", FIRN, LDSN, (bool)E, (bool)C)};
+    });
+}
+
+// test hook jaero_debug_sample_loop_layout: 0 = by size (the product behaviour), 1 = one pair per workgroup, 2 = four pairs per workgroup
+static int g_sample_loop_layout = 0;
+extern "C" int jaero_debug_sample_loop_layout(int mode)
+{
+    if (mode < 0 || mode > 2) return fail(JAERO_EINVAL, "jaero_debug_sample_loop_layout: mode must be 0 (by size), 1 (one pair) or 2 (four pairs)");
+    g_sample_loop_layout = mode;
+    return 0;
 }
 
 // The continuous bank's sample-loop and coarse-estimate kernels, with their LDS attributes
 static int choose_kernels(jaero_ctx *c, int ncu)
 {
     const JGeom &g = c->g;
-    const bool big = g.ngroups > 2 * ncu;
+    const bool big = g_sample_loop_layout ? g_sample_loop_layout == 2 : g.ngroups > 2 * ncu;
     if (g.kind == JAERO_KIND_OQPSK)
     {
         // front / back pairs (k_oqpsk_fb.h; at 8400 bps the two halves take turns, see there).  Four pairs per workgroup put one front and one
@@ -619,9 +650,9 @@ static int choose_kernels(jaero_ctx *c, int ncu)
     }
     // register-resident FFTs persistent over the estimate list (k_coarse6.h): 2^14 = 32 x 32 x 16 on one 512-thread workgroup per CU (the whole
     // register file, ~130 KiB of LDS; at 8400 bps the window table behind it), 2^13 = 32 x 16 x 16 on 256 threads, two workgroups per CU
-    if (g.nfft_log2 == 13) c->coarse = {k_coarse6_13, 2 * ncu, 256, C6_XCH13 * (int)sizeof(double), 0, "k_coarse6_13"};
-    else if (c->pre8400) c->coarse = {k_coarse6_w8400, ncu, C2_THREADS, (C6_XCH + C4_TABN) * (int)sizeof(double), 0, "k_coarse6_w8400"};
-    else c->coarse = {k_coarse6, ncu, C2_THREADS, C6_XCH * (int)sizeof(double), 0, "k_coarse6"};
+    if (g.nfft_log2 == 13) c->coarse = {k_coarse6_13, 2 * ncu, 256, C6_XCH13 * (int)sizeof(double), 0, "k_coarse6_13", "k_coarse6_13"};
+    else if (c->pre8400) c->coarse = {k_coarse6_w8400, ncu, C2_THREADS, (C6_XCH + C4_TABN) * (int)sizeof(double), 0, "k_coarse6_w8400", "k_coarse6_w8400"};
+    else c->coarse = {k_coarse6, ncu, C2_THREADS, C6_XCH * (int)sizeof(double), 0, "k_coarse6", "k_coarse6"};
     HIPCHK(set_lds_attribute(c->coarse));
     return 0;
 }
@@ -1145,6 +1176,18 @@ extern "C" int jaero_profile_kernel(jaero_ctx *c, int which, char *buf, int cap)
     else if (which == 1) nm = c->coarse.name;
     else if (which == 2) nm = "k_transpose_pcm";
     snprintf(buf, (size_t)cap, "%s", nm);
+    return 0;
+}
+
+extern "C" int jaero_debug_kernel_variant(jaero_ctx *c, int which, char *buf, int cap)
+{
+    if (!c || !buf || cap < 2 || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_debug_kernel_variant: bad arguments (which: 0 or 1)");
+    const std::string *v;
+    if (c->burst) v = which == 0 ? &c->bdemod.variant : &c->trident.variant;
+    else if (which == 0) v = c->g.kind == JAERO_KIND_OQPSK ? &c->oq_loop.variant : &c->msk_loop.variant;
+    else v = &c->coarse.variant;
+    if ((int)v->size() >= cap) return fail(JAERO_EOVERFLOW, "jaero_debug_kernel_variant: %zu characters do not fit in %d", v->size(), cap);
+    snprintf(buf, (size_t)cap, "%s", v->c_str());
     return 0;
 }
 

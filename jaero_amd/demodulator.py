@@ -217,6 +217,12 @@ class DemodulatorBank:
         capi.check(self.L.jaero_profile_kernel(self.h, which, buf, 96))
         return buf.value.decode()
 
+    def kernel_variant(self, which: int) -> str:
+        """The whole instantiation of the kernel this bank launches for class `which` (jaero_debug_kernel_variant: 0 or 1)."""
+        buf = C.create_string_buffer(128)
+        capi.check(self.L.jaero_debug_kernel_variant(self.h, which, buf, 128))
+        return buf.value.decode()
+
 
 class Ingest:
     """Batched ingest in front of a DemodulatorBank (jaero_ingest_*): dataReceived(audio, sampleRate) per channel

@@ -1205,6 +1205,7 @@ int jo_demod_pending_soft(jo_demod *d) { return d->nrx; }
 double jo_demod_get_mse(jo_demod *d) { return d->mse; }
 double jo_demod_get_freq_est(jo_demod *d) { return d->mixer2.freq; }
 double jo_demod_get_freq_center(jo_demod *d) { return d->mixer_center.freq; }
+double jo_demod_get_ebno(jo_demod *d) { return d->ebno.EbNo; }
 
 /* JFastFir::SetKernel(rrc(alpha, K, Fs, fsym), nfft) + update(x) on n complex samples (re, im interleaved): the operation
  * JAERO/tests/jfastfir_tests.cpp:31-58 checks against the recorded output of JAERO v1.0.4.11 */

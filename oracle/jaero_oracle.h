@@ -52,6 +52,7 @@ int jo_demod_pending_soft(jo_demod *d);
 double jo_demod_get_mse(jo_demod *d);
 double jo_demod_get_freq_est(jo_demod *d);
 double jo_demod_get_freq_center(jo_demod *d);
+double jo_demod_get_ebno(jo_demod *d); /* the EbNo meter's value (EbNoMeasurmentSignal), updated between estimates too */
 
 /* stand-alone pieces for unit tests */
 /* RootRaisedCosine::design (JAERO/DSP.h:316-338); returns number of points written */

@@ -84,7 +84,7 @@ def lib():
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
         L.jo_demod_capture_symbols.argtypes = [C.c_void_p, C.c_int]
         L.jo_demod_pending_soft.argtypes = [C.c_void_p]
-        for name in ("jo_demod_get_mse", "jo_demod_get_freq_est", "jo_demod_get_freq_center"):
+        for name in ("jo_demod_get_mse", "jo_demod_get_freq_est", "jo_demod_get_freq_center", "jo_demod_get_ebno"):
             f = getattr(L, name)
             f.restype = C.c_double
             f.argtypes = [C.c_void_p]
@@ -226,6 +226,10 @@ class Demod:
         return self.L.jo_demod_get_freq_center(self.h)
 
     @property
+    def ebno(self):
+        return self.L.jo_demod_get_ebno(self.h)
+
+    @property
     def pending(self):
         return self.L.jo_demod_pending_soft(self.h)
 
@@ -265,7 +269,7 @@ def run_demod(settings: Settings, pcm: np.ndarray, chunk=4096, afc=False, cpu_re
         d.write(pcm[s:s + m])
         s += m
     out = {"soft": d.take_soft(), "status": d.take_status(), "pending": d.pending, "mse": d.mse,
-           "freq_est": d.freq_est, "freq_center": d.freq_center}
+           "freq_est": d.freq_est, "freq_center": d.freq_center, "ebno": d.ebno}
     if capture_symbols:
         out["symbols"] = d.take_symbols()
     return out

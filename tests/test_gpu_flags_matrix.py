@@ -69,7 +69,8 @@ def signals(kind):
     return _SIG[kind]
 
 
-def run_matrix(B, O, kind, nch, check, capture):
+def run_matrix(B, O, kind, nch, check, capture, variant=None):
+    """variant: the sample-loop instantiation the bank must have chosen (jaero_debug_kernel_variant), asserted before any write."""
     sig = signals(kind)
     src = np.arange(nch) % NSIG
     plans = [plan(c, kind) for c in range(nch)]
@@ -77,6 +78,8 @@ def run_matrix(B, O, kind, nch, check, capture):
     chunk = 4096
     cap = int(NSAMP * (10500 if kind == "oqpsk" else 1200) / 48000) + 64
     bank = B.DemodulatorBank(bs, nch, ebno=True, status_log=True, capture_symbols=capture, max_write_samples=chunk, softbit_capacity=cap)
+    if variant is not None:
+        assert bank.kernel_variant(0) == variant
     for c in range(nch):
         a, s, r = plans[c][0]
         bank.set_flags(a, s, r, channel=c)
@@ -170,4 +173,20 @@ def test_oqpsk_bank_33091_flags_matrix(B, oracle_mod):
     nch = 33091
     check = spread(nch)
     seen, plans = run_matrix(B, oracle_mod, "oqpsk", nch, check, capture=False)
+    _assert_covered(seen, plans, check)
+
+
+def test_msk_bank_130_flags_matrix_four_pairs(B, oracle_mod):
+    """The 130-channel MSK matrix in the four-pair kernel (k_msk_fb<80, 32, ...>, chosen by size only above 32 768 channels; forced here
+    through jaero_debug_sample_loop_layout): one workgroup with three live pairs and one that only keeps the barrier count."""
+    import kernel_variants as KV
+    from jaero_amd import capi
+
+    L = capi.lib()
+    check = spread(130)
+    try:
+        capi.check(L.jaero_debug_sample_loop_layout(2))
+        seen, plans = run_matrix(B, oracle_mod, "msk", 130, check, capture=True, variant=KV.find("msk_1200", True, True, 2).kernel0)
+    finally:
+        L.jaero_debug_sample_loop_layout(0)
     _assert_covered(seen, plans, check)
