@@ -173,6 +173,54 @@ __device__ __forceinline__ bool jd_wt_passed(double last_ptr, double ptr, double
     }
     return false;
 }
+// x / d for a positive constant d with rd = 1.0 / d (correctly rounded): q = x*rd is within an ulp, two Newton corrections through exact
+// fma residuals give the correctly rounded quotient (Markstein) while it is a normal number; the sign of a zero result is x's.  Checked on the
+// device against x / d for every (d, rd) the kernels pass, 2^24 operands each (tests/test_gpu_device_math.py, tests/device_prims.py: DIV_CONSTS).
+__device__ __forceinline__ double jd_div_const(double x, double d, double rd)
+{
+    double q = x * rd;
+    double r = fma(-d, q, x);
+    q = fma(r, rd, q);
+    r = fma(-d, q, x);
+    q = fma(r, rd, q);
+    return copysign(q, x);
+}
+// WaveTable::SetFreq(double) with the division by the (constant) sample rate done by jd_div_const
+__device__ __forceinline__ void fb_wt_setfreq(double &freq, double &step, double f, double samplerate, double r_samplerate)
+{
+    freq = f;
+    if (freq < 0) freq = 0;
+    step = jd_div_const((freq) * ((double)JD_WTSIZE), samplerate, r_samplerate);
+}
+// WaveTable::WTnextFrame (DSP.cpp:70-77): one step of an oscillator.  ptr < WTSIZE before, step < WTSIZE (a frequency below the sample
+// rate), so the reference's `while ((int)ptr >= WTSIZE) ptr -= WTSIZE` runs at most once; written as a select plus a loop that is
+// never entered it costs a handful of instructions instead of a divergent loop (same result for any ptr, step).
+__device__ __forceinline__ void fb_wt_next(double &ptr, double &step)
+{
+    if (step < 0) step = 0;
+    ptr += step;
+    if (((int)ptr) >= JD_WTSIZE)
+    {
+        ptr -= JD_WTSIZE;
+        while (((int)ptr) >= JD_WTSIZE) ptr -= JD_WTSIZE;
+    }
+}
+// fmod(x, 360.0): exact by definition, so any exact evaluation gives the same bits; |x| < 720 covers every value the carrier loop
+// produces (360 * ptr / 19999 + a clamped error), the general case falls back to the library
+__device__ __forceinline__ double fb_fmod360(double x)
+{
+    const double ax = fabs(x);
+    if (ax < 360.0) return x;
+    if (ax < 720.0) return copysign(ax - 360.0, x);
+    return fmod(x, 360.0);
+}
+
+__device__ __forceinline__ void bd_set_phase_deg(double &ptr, double phase_deg) // WaveTable::SetPhaseDeg (DSP.cpp:175-180)
+{
+    phase_deg = fb_fmod360(phase_deg);
+    while (phase_deg < 0) phase_deg += 360.0;
+    ptr = jd_div_const(phase_deg, 360.0, 1.0 / 360.0) * ((double)JD_WTSIZE);
+}
 // Qt 5.9 qRound (qglobal.h:525-526)
 __device__ __forceinline__ int jd_qround(double d)
 {
@@ -378,7 +426,7 @@ __device__ __forceinline__ void jd_fir_eval_sym_static_but_last(const double *lr
 
 // tanh as glibc 2.35 computes it (sysdeps/ieee754/dbl-64/s_tanh.c over s_expm1.c, the fdlibm algorithms with glibc's grouping of the
 // expm1 polynomial), operation for operation: with correctly rounded +, *, / and no contraction the result is the reference
-// libm's, bit for bit (scripts/tanh_check.c: 0 differences from the host's tanh / expm1 on 2e8 arguments) -- and it is half the
+// libm's, bit for bit (on the device: tests/test_gpu_device_math.py, both sides of every branch point and reduction index) -- and it is half the
 // instructions of the device library's tanh (~90 against ~180 wave instructions), which the carrier detector calls twice per symbol.
 __device__ __forceinline__ double jd_with_hi(double x, int h) { return __hiloint2double(h, __double2loint(x)); }
 __device__ __forceinline__ double jd_expm1(double x)
@@ -491,7 +539,7 @@ __device__ __noinline__ double jd_tanh_full(double x)
 // The same function for 2^-55 <= |x| < 6.5 (everything an AGC'd constellation point can be) as straight-line code: glibc's branches on
 // the reduction index k -- k = 0, -1, <= -2 for the arguments below 1, 2..19 above -- become four short tails and a select, and the
 // quick reduction for |x| < 1.5 ln 2 is the general one with t = +-1 (t * ln2_hi is exact).  Every lane performs exactly the operations
-// the branchy form performs for its k, so the result is still the host libm's (scripts/tanh_check.c -DFAST: 0 differences on 3e8
+// the branchy form performs for its k, so the result is still the host libm's (tests/test_gpu_device_math.py: 0 differences on 1.5e6
 // arguments).  Written with branches, the few lanes at a symbol instant sat on both sides of |x| = 1 (constellation points are there)
 // and of the k boundaries: every path ran every time, and the carrier detector cost more than with the device library's tanh.
 __device__ __forceinline__ double jd_tanh(double xin)

@@ -17,7 +17,8 @@
 //   needs it.  Not kept.)
 //   Zeros, infinities, NaN, exponents outside 2^+-300: the device library's atan2, as before.
 // scripts/atan2_check.c compiles THIS header for the host (the hardware hooks replaced by portable C, the reciprocal seed deliberately
-// bad) and compares with the host libm and with __float128.
+// bad) and compares with the host libm and with __float128; tests/test_gpu_device_math.py runs it on the device against __float128 (2^22
+// calls) and under partial exec masks (jda_fetch's table-in-memory path).
 #pragma once
 #include <stdint.h>
 
@@ -137,7 +138,7 @@ JDA_FN double jd_atan2(double y, double x, const JdAtanLane &T) { return jd_atan
 // instructions below are the same operations on the same values: the same bits as a / b (a zero quotient comes out as +0 where IEEE gives -0
 // for a = -0; every call site takes the magnitude of the quotient or subtracts it from a non-zero value).  Three instructions and two links of
 // the dependency chain less per division: jd_tanh has two of them on the carrier loop's critical path in every sample.
-// Checked on the device against `/`: scripts/ubench/div_check.hip, 2^33 operand pairs incl. quotients next to a rounding boundary and the
+// Checked on the device against `/`: tests/test_gpu_device_math.py (2^21 pairs) and scripts/ubench/div_check.hip, 2^33 operand pairs incl. quotients next to a rounding boundary and the
 // operands of each call site's kind: no difference.  Call sites (each with |b| far inside the range): jd_tanh (b = t + 2 in [1, 4.5e5] and
 // b = 6 - x t3 in [2, 6.1]), jd_hypot (b = 2 h, only taken for 2^-200 < h < 2^200), the AGC gain (b >= 1e-6), MSEcalc (mu >= 1e-6).
 JDA_FN double jd_div(double a, double b)
@@ -155,7 +156,7 @@ JDA_FN double jd_div(double a, double b)
 // Both forms of (t1, t2) are written as straight-line code and selected (a wavefront of 64 channels has lanes on both sides in
 // nearly every call); operands outside glibc's unscaled range (2^-459 < ay, ax < 2^511), infinities and NaN take the device library's
 // value, patched in afterwards; ax >= ay 2^54 returns ax + ay as glibc does.  Bit-identical to the host libm on 6.4e8 operand pairs
-// (scripts/atan2_check.c -DHYPOT).  This -- not atan2 -- is what decides whether the loops track the reference: DESIGN 9 item 18.
+// (scripts/atan2_check.c -DHYPOT; on the device: tests/test_gpu_device_math.py).  This -- not atan2 -- is what decides whether the loops track the reference: DESIGN 9 item 18.
 JDA_FN double jd_hypot(double x, double y)
 {
     x = __builtin_fabs(x); y = __builtin_fabs(y);

@@ -7,14 +7,7 @@
 #include "burst_device.h"
 #include "jaero_device.h"
 #include "k_burst_front.h"
-#include "k_oqpsk_fb.h" // jd_div_const, fb_wt_setfreq, fb_fmod360: exact rewrites (bit-identical results, fewer instructions)
 
-__device__ __forceinline__ void bd_set_phase_deg(double &ptr, double phase_deg) // WaveTable::SetPhaseDeg (DSP.cpp:175-180)
-{
-    phase_deg = fb_fmod360(phase_deg);
-    while (phase_deg < 0) phase_deg += 360.0;
-    ptr = jd_div_const(phase_deg, 360.0, 1.0 / 360.0) * ((double)JD_WTSIZE);
-}
 __device__ __forceinline__ void bd_event(const BGeom &g, const BPtrs &p, int ch, int &ev_cnt, int &overflow, long long sample, int kind, double value)
 {
     if (ev_cnt < g.ev_cap)

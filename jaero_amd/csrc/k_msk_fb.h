@@ -24,7 +24,7 @@
 #pragma once
 #include <type_traits>
 #include "jaero_device.h"
-#include "k_oqpsk_fb.h" // fb_barrier, fb_wt_next, jd_div_const
+#include "k_oqpsk_fb.h" // fb_barrier
 
 #define MFB_LDSN 36  // one pair per workgroup (small banks): 36 history entries of each arm in LDS, 44 in registers
 // ... of which the MFB1_TB oldest in the BACK half's (round 5): in a small bank the halves sit on different SIMDs and the front half is the long pole

@@ -67,48 +67,6 @@ __device__ unsigned long long g_fb_trace[2][10];
 #endif
 #define FB_LDSN 36 // filter history slots in LDS: 36 KiB + 3.5 KiB of mailboxes = 40 448 B per pair, four pairs per CU (161 792 of 163 840 B)
 
-// x / d for a positive constant d with rd = 1.0 / d (correctly rounded): q = x*rd is within an ulp, two Newton corrections through exact
-// fma residuals give the correctly rounded quotient (Markstein); the sign of a zero result is x's.  Checked against x / d on 2e9
-// random, near-multiple and near-midpoint operands per constant (scripts/div_const_check.c): no difference.
-__device__ __forceinline__ double jd_div_const(double x, double d, double rd)
-{
-    double q = x * rd;
-    double r = fma(-d, q, x);
-    q = fma(r, rd, q);
-    r = fma(-d, q, x);
-    q = fma(r, rd, q);
-    return copysign(q, x);
-}
-// WaveTable::SetFreq(double) with the division by the (constant) sample rate done by jd_div_const
-__device__ __forceinline__ void fb_wt_setfreq(double &freq, double &step, double f, double samplerate, double r_samplerate)
-{
-    freq = f;
-    if (freq < 0) freq = 0;
-    step = jd_div_const((freq) * ((double)JD_WTSIZE), samplerate, r_samplerate);
-}
-// WaveTable::WTnextFrame (DSP.cpp:70-77): one step of an oscillator.  ptr < WTSIZE before, step < WTSIZE (a frequency below the sample
-// rate), so the reference's `while ((int)ptr >= WTSIZE) ptr -= WTSIZE` runs at most once; written as a select plus a loop that is
-// never entered it costs a handful of instructions instead of a divergent loop (same result for any ptr, step).
-__device__ __forceinline__ void fb_wt_next(double &ptr, double &step)
-{
-    if (step < 0) step = 0;
-    ptr += step;
-    if (((int)ptr) >= JD_WTSIZE)
-    {
-        ptr -= JD_WTSIZE;
-        while (((int)ptr) >= JD_WTSIZE) ptr -= JD_WTSIZE;
-    }
-}
-// fmod(x, 360.0): exact by definition, so any exact evaluation gives the same bits; |x| < 720 covers every value the carrier loop
-// produces (360 * ptr / 19999 + a clamped error), the general case falls back to the library
-__device__ __forceinline__ double fb_fmod360(double x)
-{
-    const double ax = fabs(x);
-    if (ax < 360.0) return x;
-    if (ax < 720.0) return copysign(ax - 360.0, x);
-    return fmod(x, 360.0);
-}
-
 struct FbLds
 {
     double *lre, *lim;        // [LDSN][64], [LDSN][64]   (the taps are scalar kernel arguments: JTaps28)
