@@ -1,115 +1,106 @@
 // aerol_host.h -- C ABI of the Aero-L bit pipeline bank; included at the end of jaero_hip.hip.
 #pragma once
 
+#include "aerolc.h"
+
 struct jaero_aerol_ctx
 {
     int device = 0;
-    AGeom g{};
+    AGeom g{}; // fb = 8400: nch, nchp and fb only
     APtrs p{};
-    std::vector<void *> allocs;
+    bool cchan = false; // fb = 8400: the C-channel pipeline (aerolc.h) on cg / cp
+    CGeom cg{};
+    CPtrs cp{};
+    DevMem mem;
     int16_t *d_soft = nullptr; int *d_counts = nullptr; int stage_stride = 0;
     unsigned long long *d_vhist = nullptr; // k_viterbi_lanes history scratch (large banks only)
     hipStream_t last_stream = nullptr;
-    // HIP-event timing of the three kernel classes (0 = k_aerol_bits, 1 = k_viterbi + overlap update, 2 = k_aerol_post)
-    bool prof = false;
-    double prof_ms[3] = {0, 0, 0};
-    int prof_n[3] = {0, 0, 0};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    std::vector<int> ev_which;
-    void *cmode = nullptr; // fb = 8400: C-channel state (aerolc_state, aerolc.h); g / p above stay unused
+    KernelTimer timer{3}; // the three kernel classes: 0 = the bit walk, 1 = k_viterbi + overlap update, 2 = the end of a block / frame
 };
 
-static void aprof_begin(jaero_aerol_ctx *c, int which, hipStream_t st)
-{
-    if (!c->prof) return;
-    hipEvent_t a, b;
-    if (c->ev_which.size() < c->ev_pool.size()) { a = c->ev_pool[c->ev_which.size()].first; }
-    else
-    {
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-        c->ev_pool.push_back({a, b});
-    }
-    c->ev_which.push_back(which);
-    hipEventRecord(c->ev_pool[c->ev_which.size() - 1].first, st);
-}
-static void aprof_end(jaero_aerol_ctx *c, hipStream_t st)
-{
-    if (!c->prof || c->ev_which.empty()) return;
-    hipEventRecord(c->ev_pool[c->ev_which.size() - 1].second, st);
-}
-static void aprof_collect(jaero_aerol_ctx *c)
-{
-    for (size_t i = 0; i < c->ev_which.size(); i++)
-    {
-        float ms = 0;
-        hipEventSynchronize(c->ev_pool[i].second);
-        if (hipEventElapsedTime(&ms, c->ev_pool[i].first, c->ev_pool[i].second) == hipSuccess) { c->prof_ms[c->ev_which[i]] += ms; c->prof_n[c->ev_which[i]]++; }
-    }
-    c->ev_which.clear();
-}
 extern "C" int jaero_aerol_profile_enable(jaero_aerol_ctx *c, int on)
 {
     if (!c) return fail(JAERO_EINVAL, "null ctx");
-    c->prof = on != 0;
+    c->timer.on = on != 0;
     return 0;
 }
 extern "C" int jaero_aerol_profile_read(jaero_aerol_ctx *c, int which, double *total_ms, int *launches, int reset)
 {
     if (!c || which < 0 || which > 2) return fail(JAERO_EINVAL, "jaero_aerol_profile_read: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    aprof_collect(c);
-    if (total_ms) *total_ms = c->prof_ms[which];
-    if (launches) *launches = c->prof_n[which];
-    if (reset) { c->prof_ms[which] = 0; c->prof_n[which] = 0; }
-    return 0;
+    return c->timer.read(c->device, which, total_ms, launches, reset);
 }
 
-template <class T>
-static int aalloc(jaero_aerol_ctx *c, T **ptr, size_t count)
-{
-    void *q = nullptr;
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(JAERO_ENOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-    e = hipMemset(q, 0, bytes);
-    if (e != hipSuccess) return fail(JAERO_EHIP, "hipMemset failed: %s", hipGetErrorString(e));
-    c->allocs.push_back(q);
-    *ptr = (T *)q;
-    return 0;
-}
-
-static void aerolc_free(jaero_aerol_ctx *c);
 extern "C" void jaero_aerol_destroy(jaero_aerol_ctx *c)
 {
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    for (void *q : c->allocs) hipFree(q);
-    for (auto &e : c->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    aerolc_free(c);
-    delete c;
+    delete c; // its device memory and timing events with it
 }
 
-#include "aerolc.h"
-static void aerolc_free(jaero_aerol_ctx *c) { delete (aerolc_state *)c->cmode; c->cmode = nullptr; }
+// the C-channel state (aerolc.h) of a bank whose g.nch / g.nchp are set
+static int aerolc_init(jaero_aerol_ctx *c, int su_capacity, const std::vector<uint8_t> &scr)
+{
+    CGeom &g = c->cg;
+    CPtrs &p = c->cp;
+    DevMem &m = c->mem;
+    g.nch = c->g.nch; g.nchp = c->g.nchp;
+    g.su_cap = su_capacity > 0 ? su_capacity : 3 * 64; // 64 frames between reads
+    g.v_cap = (g.su_cap + 2) / 3;
+    g.ev_cap = 256;
+    int rc;
+    DA(m, p.I, (size_t)CI_NFIELDS * g.nchp);
+    DA(m, p.B, (size_t)4 * g.nchp);
+    DA(m, p.dep, (size_t)g.nchp * CC_PITCH);
+    DA(m, p.vbits, (size_t)g.nchp * (CC_NSOFT / 2));
+    DA(m, p.overlap, (size_t)g.nchp * 64);
+    DA(m, p.dl2, (size_t)CC_PREV_PITCH * g.nchp + 64);
+    DA(m, p.sus, (size_t)g.nchp * g.su_cap * 16);
+    DA(m, p.voice, (size_t)g.nchp * g.v_cap * 304);
+    DA(m, p.events, (size_t)g.nchp * g.ev_cap * 3);
+    if (viterbi_use_lanes(g.nch, CC_NSOFT, 24)) DA(m, c->d_vhist, viterbi_hist_bytes(g.nch) / sizeof(unsigned long long));
+    uint8_t *d_scr = nullptr;
+    DA(m, d_scr, 5000);
+    unsigned long long *d_scrf = nullptr;
+    DA(m, d_scrf, 50);
+    p.scr = d_scr; p.scrf = d_scrf;
+    HIPCHK(hipMemcpy(d_scr, scr.data(), 5000, hipMemcpyHostToDevice));
+    std::vector<unsigned long long> scrf(50, 0ull);
+    for (int y = 0; y < 25; y++)
+        for (int i = 0; i < 108; i++) scrf[2 * y + i / 64] |= (unsigned long long)(scr[109 * y + 1 + i] & 1) << (i % 64);
+    HIPCHK(hipMemcpy(d_scrf, scrf.data(), scrf.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    // the depunctured buffer: every 4th symbol an erasure, for good (the walk only writes the other three)
+    std::vector<uint8_t> dep((size_t)g.nchp * CC_PITCH, 0);
+    for (size_t k = 0; k < dep.size(); k++) if ((k % CC_PITCH) % 4 == 3) dep[k] = 128;
+    HIPCHK(hipMemcpy(p.dep, dep.data(), dep.size(), hipMemcpyHostToDevice));
+    std::vector<int> I((size_t)CI_NFIELDS * g.nchp, 0);
+    for (int ch = 0; ch < g.nchp; ch++)
+    {
+        I[(size_t)CI_CNTR * g.nchp + ch] = 1000000000; // AeroL constructor (aerol.cpp:907)
+        I[(size_t)CI_EV_CNT * g.nchp + ch] = 1;        // row 0 = [0, DCD, 0]: DataCarrierDetect(false) emitted by the constructor
+    }
+    HIPCHK(hipMemcpy(p.I, I.data(), I.size() * sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
 
 // aerol_create behind `new jaero_aerol_ctx`: what it allocated before a failure goes with jaero_aerol_destroy
 static int aerol_init(jaero_aerol_ctx *c, int nchannels, int fb, int max_softbits_per_write, int su_capacity, int burst)
 {
     int rc;
+    DevMem &m = c->mem;
+    AGeom &g = c->g;
+    g.nch = nchannels; g.nchp = (nchannels + 63) / 64 * 64; g.fb = fb;
+    c->stage_stride = max_softbits_per_write;
+    DA(m, c->d_soft, (size_t)g.nch * max_softbits_per_write);
+    DA(m, c->d_counts, g.nchp);
+    const std::vector<uint8_t> scr = scrambler_bits();
     if (fb == 8400 && !burst) // C channel (aerolc.h)
     {
-        if ((rc = aerolc_create(c, nchannels, su_capacity))) return rc;
-        if ((rc = aalloc(c, &c->d_soft, (size_t)nchannels * max_softbits_per_write))) return rc;
-        if ((rc = aalloc(c, &c->d_counts, (size_t)(nchannels + 63) / 64 * 64))) return rc;
-        c->stage_stride = max_softbits_per_write;
-        c->g.nch = nchannels; c->g.nchp = (nchannels + 63) / 64 * 64; c->g.fb = fb;
+        c->cchan = true;
+        if ((rc = aerolc_init(c, su_capacity, scr))) return rc;
         HIPCHK(hipDeviceSynchronize());
         return 0;
     }
-    AGeom &g = c->g;
-    g.nch = nchannels; g.nchp = (nchannels + 63) / 64 * 64; g.fb = fb;
     // AeroL::setSettings (JAERO/aerol.cpp:990-1072), burstmode = false
     switch (fb)
     {
@@ -130,50 +121,35 @@ static int aerol_init(jaero_aerol_ctx *c, int nchannels, int fb, int max_softbit
     g.info_cap = g.NumberOfBits / 16 + 16;
     if (su_capacity <= 0) su_capacity = burst ? 256 : 32 * (g.NumberOfBits / 2 / 96) + 8; // 32 frames (burst: 256 packet rows) between reads
     g.su_cap = su_capacity; g.ev_cap = 256;
-#define AA(ptr, count) do { if ((rc = aalloc(c, &(ptr), (size_t)(count)))) return rc; } while (0)
-    AA(c->p.I, (size_t)AI_NFIELDS * g.nchp);
-    AA(c->p.rx, (size_t)g.nchp * g.blocksz);
-    AA(c->p.deint, (size_t)g.nchp * g.blocksz);
-    AA(c->p.vbits, (size_t)g.nchp * (g.blocksz / 2));
-    AA(c->p.overlap, (size_t)g.nchp * 64);
-    AA(c->p.dl2, (size_t)g.nchp * g.dl2_sz);
-    AA(c->p.info, (size_t)g.nchp * g.info_cap);
-    AA(c->p.sus, (size_t)g.nchp * g.su_cap * 16);
-    AA(c->p.events, (size_t)g.nchp * g.ev_cap * 3);
+    DA(m, c->p.I, (size_t)AI_NFIELDS * g.nchp);
+    DA(m, c->p.rx, (size_t)g.nchp * g.blocksz);
+    DA(m, c->p.deint, (size_t)g.nchp * g.blocksz);
+    DA(m, c->p.vbits, (size_t)g.nchp * (g.blocksz / 2));
+    DA(m, c->p.overlap, (size_t)g.nchp * 64);
+    DA(m, c->p.dl2, (size_t)g.nchp * g.dl2_sz);
+    DA(m, c->p.info, (size_t)g.nchp * g.info_cap);
+    DA(m, c->p.sus, (size_t)g.nchp * g.su_cap * 16);
+    DA(m, c->p.events, (size_t)g.nchp * g.ev_cap * 3);
     uint8_t *d_scr = nullptr;
-    AA(d_scr, 5000);
-    c->stage_stride = max_softbits_per_write;
-    AA(c->d_soft, (size_t)g.nch * max_softbits_per_write);
-    AA(c->d_counts, g.nchp);
+    DA(m, d_scr, 5000);
     unsigned *d_scrw = nullptr;
-    AA(d_scrw, 5000 / 32 + 2);
+    DA(m, d_scrw, 5000 / 32 + 2);
     if (!burst && viterbi_use_lanes(g.nch, g.blocksz, 24))
     {
         // large bank: one block per lane in the Viterbi, tiled deinterleaver output, decoded bits and delay line packed 32 per word
-        AA(c->d_vhist, viterbi_hist_bytes(g.nch) / sizeof(unsigned long long));
+        DA(m, c->d_vhist, viterbi_hist_bytes(g.nch) / sizeof(unsigned long long));
         g.packed = 1;
         // deinterleaver output: row-major.  The tiled layout ([wavefront][16-byte group][lane][16], k_viterbi_lanes reads 8 x 1 KiB per chunk)
         // was built when cold rows cost the decoder 0.85 ms; with its chunk prefetch it no longer gains anything and the tiled writes cost
         // 0.14 ms (3.51 vs 3.36 ms per step): not used (its switch left the library in round 3; the kernels keep the code path).
         g.tiled = 0;
         g.dl2_words = (g.dl2_sz + 31) / 32 + 1;
-        AA(c->p.dl2w, (size_t)g.nchp * g.dl2_words);
+        DA(m, c->p.dl2w, (size_t)g.nchp * g.dl2_words);
     }
     // R/T packet search in a large bank: the trial decodes (each channel's own length) one block per lane as well, bits out one per byte
-    if (burst && viterbi_use_lanes(g.nch, 128, 0)) AA(c->d_vhist, viterbi_hist_bytes(g.nch) / sizeof(unsigned long long));
-#undef AA
+    if (burst && viterbi_use_lanes(g.nch, 128, 0)) DA(m, c->d_vhist, viterbi_hist_bytes(g.nch) / sizeof(unsigned long long));
     c->p.scr = d_scr;
     {
-        // AeroLScrambler (JAERO/aerol.h:397-420)
-        std::vector<uint8_t> scr(5000);
-        int state[15] = {1, 1, 0, 1, 0, 0, 1, 0, 1, 0, 1, 1, 0, 0, 1};
-        for (int k = 0; k < 5000; k++)
-        {
-            const int val0 = state[0] ^ state[14];
-            scr[k] = (uint8_t)val0;
-            for (int i = 14; i > 0; i--) state[i] = state[i - 1];
-            state[0] = val0;
-        }
         HIPCHK(hipMemcpy(d_scr, scr.data(), 5000, hipMemcpyHostToDevice));
         std::vector<unsigned> scrw(5000 / 32 + 2, 0u);
         for (int k = 0; k < 5000; k++) scrw[k >> 5] |= (unsigned)scr[k] << (k & 31);
@@ -207,13 +183,11 @@ static int aerol_create(int device, int nchannels, int fb, int max_softbits_per_
     *out = nullptr;
     if (fb != 600 && fb != 1200 && fb != 10500 && !(fb == 8400 && !burst))
         return fail(JAERO_ENOTSUP, "jaero_aerol_create: fb must be 600, 1200, 10500 or (continuous mode) 8400");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(JAERO_ENODEV, "device %d out of range", device);
-    HIPCHK(hipSetDevice(device));
+    int rc = open_device(device);
+    if (rc) return rc;
     jaero_aerol_ctx *c = new jaero_aerol_ctx();
     c->device = device;
-    const int rc = aerol_init(c, nchannels, fb, max_softbits_per_write, su_capacity, burst);
+    rc = aerol_init(c, nchannels, fb, max_softbits_per_write, su_capacity, burst);
     if (rc) { jaero_aerol_destroy(c); return rc; }
     *out = c;
     return 0;
@@ -227,7 +201,39 @@ extern "C" int jaero_aerol_create_burst(int device, int nchannels, int fb, int m
 {
     return aerol_create(device, nchannels, fb, max_softbits_per_write, packet_row_capacity, 1, out);
 }
-extern "C" int jaero_aerol_read_packets(jaero_aerol_ctx *c, int ch, int32_t *rows, int caprows, int *nrows);
+// the C-channel pipeline's rounds of jaero_aerol_write
+static int aerolc_write(jaero_aerol_ctx *c, const int16_t *dsoft, const int *dcounts, int stride, int max_count, hipStream_t st)
+{
+    const CGeom &g = c->cg;
+    const CPtrs &p = c->cp;
+    // a round finishes at most one frame per channel.  Frame ends are at least 4098 soft bits apart: the detector window reopens at
+    // cntr > CC_FRAME - 112, so a (false or real) unique word can fire two bits after a completed frame and the next frame ends
+    // CC_FRAME bits after that -- not CC_FRAME + 104 as in a clean stream.
+    // A lane's round also ends when it meets a third jumpable stretch (k_aerolc_bits): it has then consumed at least one whole frame body
+    // (CC_FRAME - 112 soft bits), so the bound below covers that too.
+    const int rounds = max_count / (CC_FRAME - 112) + 2;
+    const int *valid = p.I + (size_t)CI_HAS_BLOCK * g.nchp;
+    const dim3 grid(g.nchp / 64), block(64);
+    for (int r = 0; r < rounds; r++)
+    {
+        int pi = c->timer.begin(0, st);
+        hipLaunchKernelGGL(k_aerolc_bits, grid, block, 0, st, g, p, dsoft, dcounts, stride);
+        hipLaunchKernelGGL(k_aerolc_bulk, dim3((g.nch + 3) / 4), dim3(256), 0, st, g, p, dsoft, stride, -1, -1); // both stretches of a round, in order
+        c->timer.end(pi, st);
+        pi = c->timer.begin(1, st);
+        // one block per wavefront for small banks, one per lane (k_viterbi_lanes) from 16 384 channels on, as the P-channel pipeline
+        viterbi_launch(st, (const uint8_t *)p.dep, CC_NSOFT, (const uint8_t *)p.overlap, 24, p.vbits, CC_NSOFT / 2, 25, CC_NSOFT / 2, g.nch, valid,
+                       c->d_vhist, 0, 0, 0, CC_PITCH);
+        hipLaunchKernelGGL(k_viterbi_overlap_update, dim3(g.nch), dim3(64), 0, st, (const uint8_t *)p.dep, CC_NSOFT, p.overlap, g.nch, valid, 0, CC_PITCH);
+        c->timer.end(pi, st);
+        pi = c->timer.begin(2, st);
+        hipLaunchKernelGGL(k_aerolc_post, grid, block, 0, st, g, p);
+        c->timer.end(pi, st);
+    }
+    hipLaunchKernelGGL(k_aerolc_end_write, grid, block, 0, st, g, p, dcounts);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 
 // = processDemodulatedSoftBits for every channel: soft[ch * stride + k], k < counts[ch]
 extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const int *counts, int stride, int max_count, int is_device_ptr, void *stream)
@@ -249,7 +255,7 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
         dsoft = c->d_soft; dcounts = c->d_counts;
     }
     if (max_count == 0) return 0;
-    if (c->cmode) return aerolc_write(c, dsoft, dcounts, stride, max_count, st);
+    if (c->cchan) return aerolc_write(c, dsoft, dcounts, stride, max_count, st);
     if (g.burst)
     {
         // R/T packet search: a round per trial length a channel can reach in this write (every 192 soft bits, plus 128 and 320)
@@ -259,19 +265,19 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
         const dim3 grid(g.nchp / 64), block(64);
         for (int r = 0; r < rounds; r++)
         {
-            aprof_begin(c, 0, st);
+            int pi = c->timer.begin(0, st);
             if (((((size_t)dsoft) | ((size_t)stride * 2)) & 15) == 0) hipLaunchKernelGGL(k_aerolb_bits<true>, grid, block, 0, st, g, c->p, dsoft, dcounts, stride);
             else hipLaunchKernelGGL(k_aerolb_bits<false>, grid, block, 0, st, g, c->p, dsoft, dcounts, stride);
             hipLaunchKernelGGL(k_aerolb_deint, dim3((g.nch + 3) / 4), dim3(256), 0, st, g, c->p);
-            aprof_end(c, st);
-            aprof_begin(c, 1, st);
+            c->timer.end(pi, st);
+            pi = c->timer.begin(1, st);
             // trial lengths are 128, 320, 512, .. (k_aerolb_bits): never below the lane layout's minimum of 4 * VT_ORDER steps
             viterbi_launch(st, (const uint8_t *)c->p.deint, RT_BLOCKSZ, (const uint8_t *)nullptr, 0, c->p.vbits, RT_BLOCKSZ / 2, 0, RT_BLOCKSZ / 2, g.nch, valid,
                            c->d_vhist, 0, 0, c->d_vhist != nullptr, 0, lens);
-            aprof_end(c, st);
-            aprof_begin(c, 2, st);
+            c->timer.end(pi, st);
+            pi = c->timer.begin(2, st);
             hipLaunchKernelGGL(k_aerolb_post, grid, block, 0, st, g, c->p);
-            aprof_end(c, st);
+            c->timer.end(pi, st);
         }
         hipLaunchKernelGGL(k_aerol_end_write, grid, block, 0, st, g, c->p, dcounts);
         HIPCHK(hipGetLastError());
@@ -286,7 +292,7 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
     if (bulk) hipLaunchKernelGGL(k_aerol_scan, dim3((g.nch + 3) / 4), dim3(256), 0, st, g, c->p, dsoft, dcounts, stride);
     for (int r = 0; r < rounds; r++)
     {
-        aprof_begin(c, 0, st);
+        int pi = c->timer.begin(0, st);
         if (bulk)
         {
             hipLaunchKernelGGL(k_aerol_bits<true>, grid, block, 0, st, g, c->p, dsoft, dcounts, stride);
@@ -294,68 +300,56 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
         }
         else hipLaunchKernelGGL(k_aerol_bits<false>, grid, block, 0, st, g, c->p, dsoft, dcounts, stride);
         hipLaunchKernelGGL(k_aerol_deint, dim3((g.nch + 3) / 4), dim3(256), 0, st, g, c->p);
-        aprof_end(c, st);
-        aprof_begin(c, 1, st);
+        c->timer.end(pi, st);
+        pi = c->timer.begin(1, st);
         viterbi_launch(st, (const uint8_t *)c->p.deint, g.blocksz, (const uint8_t *)c->p.overlap, 24, c->p.vbits, g.blocksz / 2, 25, g.blocksz / 2,
                        g.nch, valid, c->d_vhist, g.tiled, g.packed /* bits out, 32 per word */, g.packed /* lane layout */);
         hipLaunchKernelGGL(k_viterbi_overlap_update, dim3(g.nch), dim3(64), 0, st, (const uint8_t *)c->p.deint, g.blocksz, c->p.overlap, g.nch, valid, g.tiled);
-        aprof_end(c, st);
-        aprof_begin(c, 2, st);
+        c->timer.end(pi, st);
+        pi = c->timer.begin(2, st);
         if (g.packed) hipLaunchKernelGGL(k_aerol_post_packed, grid, block, 0, st, g, c->p);
         else hipLaunchKernelGGL(k_aerol_post, grid, block, 0, st, g, c->p);
-        aprof_end(c, st);
+        c->timer.end(pi, st);
     }
     hipLaunchKernelGGL(k_aerol_end_write, grid, block, 0, st, g, c->p, dcounts);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-static int aerol_read_rows(jaero_aerol_ctx *c, int ch, void *rows, int caprows, int *nrows, int cnt_field, const void *base, int cap, size_t rowbytes, int ovbit)
+// the readers of an Aero-L bank's per-channel outputs: drain channel ch of the rows whose count is column `cnt_field` of the bank's counters
+// (the C channel's or the P / R/T banks'), then report `ovbit` of its overflow word
+static int aerol_read(jaero_aerol_ctx *c, const char *who, int cnt_field, void *base, int cap, size_t rowbytes, int ch, void *rows, int caprows, int *nrows, int ovbit)
 {
-    if (!c || !rows || !nrows || ch < 0 || ch >= c->g.nch || caprows < 0) return fail(JAERO_EINVAL, "bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
-    int cnt = 0;
-    int *dcnt = c->p.I + (size_t)cnt_field * c->g.nchp + ch;
-    HIPCHK(hipMemcpy(&cnt, dcnt, sizeof(int), hipMemcpyDeviceToHost));
-    const int take = cnt < caprows ? cnt : caprows;
-    char *src = (char *)base + (size_t)ch * cap * rowbytes;
-    if (take) HIPCHK(hipMemcpy(rows, src, rowbytes * take, hipMemcpyDeviceToHost));
-    if (take < cnt)
-    {
-        std::vector<char> tmp(rowbytes * (size_t)(cnt - take));
-        HIPCHK(hipMemcpy(tmp.data(), src + rowbytes * take, tmp.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(src, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-    }
-    const int rest = cnt - take;
-    HIPCHK(hipMemcpy(dcnt, &rest, sizeof(int), hipMemcpyHostToDevice));
-    *nrows = take;
-    int ov = 0;
-    int *dov = c->p.I + (size_t)AI_OVERFLOW * c->g.nchp + ch;
-    HIPCHK(hipMemcpy(&ov, dov, sizeof(int), hipMemcpyDeviceToHost));
-    if (ov & ovbit)
-    {
-        const int z = ov & ~ovbit;
-        HIPCHK(hipMemcpy(dov, &z, sizeof(int), hipMemcpyHostToDevice));
-        return fail(JAERO_EOVERFLOW, "Aero-L channel %d overflowed an output buffer (flag %d); rows were dropped", ch, ovbit);
-    }
-    return 0;
+    int *I = c->cchan ? c->cp.I : c->p.I;
+    const size_t nchp = c->g.nchp;
+    const int rc = drain_rows(who, c->device, c->last_stream, c->g.nch, {base, I + cnt_field * nchp, cap, rowbytes}, ch, rows, caprows, nrows);
+    return rc ? rc : report_overflow(I + (c->cchan ? CI_OVERFLOW : AI_OVERFLOW) * nchp + ch, ovbit, ch);
 }
 extern "C" int jaero_aerol_read_sus(jaero_aerol_ctx *c, int ch, int32_t *rows, int caprows, int *nrows)
 {
-    if (c && c->cmode) { aerolc_state *cs = (aerolc_state *)c->cmode; return aerolc_read(c, ch, rows, caprows, nrows, CI_SU_CNT, cs->p.sus, cs->g.su_cap, 16 * sizeof(int32_t), 1); }
-    if (c && c->g.burst) return fail(JAERO_ENOTSUP, "jaero_aerol_read_sus: burst-mode bank (use jaero_aerol_read_packets)");
-    return aerol_read_rows(c, ch, rows, caprows, nrows, AI_SU_CNT, c ? c->p.sus : nullptr, c ? c->g.su_cap : 0, 16 * sizeof(int32_t), 1);
+    const char *who = "jaero_aerol_read_sus";
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (c->cchan) return aerol_read(c, who, CI_SU_CNT, c->cp.sus, c->cg.su_cap, 16 * sizeof(int32_t), ch, rows, caprows, nrows, 1);
+    if (c->g.burst) return fail(JAERO_ENOTSUP, "jaero_aerol_read_sus: burst-mode bank (use jaero_aerol_read_packets)");
+    return aerol_read(c, who, AI_SU_CNT, c->p.sus, c->g.su_cap, 16 * sizeof(int32_t), ch, rows, caprows, nrows, 1);
 }
 extern "C" int jaero_aerol_read_packets(jaero_aerol_ctx *c, int ch, int32_t *rows, int caprows, int *nrows)
 {
-    if (c && !c->g.burst) return fail(JAERO_ENOTSUP, "jaero_aerol_read_packets: not a burst-mode bank (use jaero_aerol_read_sus)");
-    return aerol_read_rows(c, ch, rows, caprows, nrows, AI_SU_CNT, c ? c->p.sus : nullptr, c ? c->g.su_cap : 0, 16 * sizeof(int32_t), 1);
+    if (!c) return fail(JAERO_EINVAL, "jaero_aerol_read_packets: null ctx");
+    if (!c->g.burst) return fail(JAERO_ENOTSUP, "jaero_aerol_read_packets: not a burst-mode bank (use jaero_aerol_read_sus)");
+    return aerol_read(c, "jaero_aerol_read_packets", AI_SU_CNT, c->p.sus, c->g.su_cap, 16 * sizeof(int32_t), ch, rows, caprows, nrows, 1);
 }
 extern "C" int jaero_aerol_read_events(jaero_aerol_ctx *c, int ch, long long *rows, int caprows, int *nrows)
 {
-    if (c && c->cmode) { aerolc_state *cs = (aerolc_state *)c->cmode; return aerolc_read(c, ch, rows, caprows, nrows, CI_EV_CNT, cs->p.events, cs->g.ev_cap, 3 * sizeof(long long), 2); }
-    return aerol_read_rows(c, ch, rows, caprows, nrows, AI_EV_CNT, c ? c->p.events : nullptr, c ? c->g.ev_cap : 0, 3 * sizeof(long long), 2);
+    const char *who = "jaero_aerol_read_events";
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (c->cchan) return aerol_read(c, who, CI_EV_CNT, c->cp.events, c->cg.ev_cap, 3 * sizeof(long long), ch, rows, caprows, nrows, 2);
+    return aerol_read(c, who, AI_EV_CNT, c->p.events, c->g.ev_cap, 3 * sizeof(long long), ch, rows, caprows, nrows, 2);
+}
+extern "C" int jaero_aerol_read_voice(jaero_aerol_ctx *c, int ch, uint8_t *rows, int caprows, int *nrows)
+{
+    if (!c || !c->cchan) return fail(JAERO_EINVAL, "jaero_aerol_read_voice: not a C-channel (fb = 8400) bank");
+    return aerol_read(c, "jaero_aerol_read_voice", CI_V_CNT, c->cp.voice, c->cg.v_cap, 304, ch, rows, caprows, nrows, 4);
 }
 // = AeroL::updateDCD (aerol.cpp:1109-1122), which the reference drives from a 1 s wall-clock QTimer: the caller ticks it once per
 // second of signal time.  dcd_out (optional, [nchannels]) receives the datacd flags afterwards.
@@ -379,19 +373,9 @@ extern "C" int jaero_aerol_tick_dcd(jaero_aerol_ctx *c, int *dcd_out_host)
 {
     if (!c) return fail(JAERO_EINVAL, "null ctx");
     HIPCHK(hipSetDevice(c->device));
-    if (c->cmode)
-    {
-        aerolc_state *cs = (aerolc_state *)c->cmode;
-        hipLaunchKernelGGL(k_aerolc_tick_dcd, dim3(cs->g.nchp / 64), dim3(64), 0, c->last_stream, cs->g, cs->p, dcd_out_host ? c->d_counts : nullptr);
-        if (dcd_out_host)
-        {
-            HIPCHK(hipMemcpyAsync(dcd_out_host, c->d_counts, sizeof(int) * cs->g.nch, hipMemcpyDeviceToHost, c->last_stream));
-            HIPCHK(hipStreamSynchronize(c->last_stream));
-        }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    hipLaunchKernelGGL(k_aerol_tick_dcd, dim3(c->g.nchp / 64), dim3(64), 0, c->last_stream, c->g, c->p, dcd_out_host ? c->d_counts : nullptr);
+    int *dout = dcd_out_host ? c->d_counts : nullptr;
+    if (c->cchan) hipLaunchKernelGGL(k_aerolc_tick_dcd, dim3(c->g.nchp / 64), dim3(64), 0, c->last_stream, c->cg, c->cp, dout);
+    else hipLaunchKernelGGL(k_aerol_tick_dcd, dim3(c->g.nchp / 64), dim3(64), 0, c->last_stream, c->g, c->p, dout);
     if (dcd_out_host)
     {
         HIPCHK(hipMemcpyAsync(dcd_out_host, c->d_counts, sizeof(int) * c->g.nch, hipMemcpyDeviceToHost, c->last_stream));

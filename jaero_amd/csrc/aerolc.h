@@ -1,5 +1,5 @@
 // aerolc.h -- Aero-L C-channel bit pipeline (8400 bps): AeroL::DecodeC (JAERO/aerol.cpp:2187-2502) for a bank of channels.
-// SURVEY 8 row f4, second half.  Included by jaero_hip.hip after aerol_host.h; reached through jaero_aerol_create(fb = 8400).
+// SURVEY 8 row f4, second half.  Device code only, included by aerol_host.h (which holds the host side); reached through jaero_aerol_create(fb = 8400).
 //
 // Written from the oracle restatement (oracle/aerol_oracle.c, c_write / c_frame_done), which is pinned against the unmodified AeroL.
 // Golden + banks of 5 / 70 / 65 536 channels in both Viterbi layouts are green on the GPU (tests/test_gpu_aerol_c.py, test_gpu_scale_aerol.py);
@@ -211,7 +211,7 @@ __device__ __forceinline__ int cc_cntr_of_src(int src)
 // Round 6, second half: driven by the OUTPUT.  Source order meant one byte store per soft bit, the 64 lanes of every store instruction in 64 different
 // 64-byte lines of the frame buffer (the interleaver spreads neighbours 85 positions apart): 4096 partial-line writes per frame, 0.97 ms per 65 536-channel
 // step.  Now the stretch is staged in LDS (16-byte loads, coalesced), and a lane forms four consecutive bytes of the frame buffer -- three soft bits
-// looked up in LDS through the inverse permutation and the erasure byte every fourth position holds (128, never anything else: aerolc_create) -- and
+// looked up in LDS through the inverse permutation and the erasure byte every fourth position holds (128, never anything else: aerolc_init) -- and
 // stores them as one word, 256 contiguous bytes per store instruction; words with a position outside the stretch (the 112 positions of the unique-word
 // window, and stretches cut by a write boundary) store their bytes singly.
 // phase: -1 = stage, then emit (the device); 0 / 1 = one of the two (tests/host_emul runs a workgroup's threads one after the other: every thread stages
@@ -452,148 +452,3 @@ __global__ void k_aerolc_tick_dcd(const CGeom g, const CPtrs p, int *dcd_out)
     CLD(CI_DCDCOUNT) = dcdcount; CLD(CI_DATACD) = datacd; CLD(CI_EV_CNT) = ev_cnt; CLD(CI_OVERFLOW) = overflow;
     if (dcd_out) dcd_out[ch] = datacd;
 }
-
-#ifndef AEROLC_KERNELS_ONLY // tests/host_emul/aerolc_emul.cpp compiles the kernels above as host functions
-// ------------------------------------------------------------------------------------------------ host side
-struct aerolc_state
-{
-    CGeom g{};
-    CPtrs p{};
-    unsigned long long *d_vhist = nullptr; // k_viterbi_lanes history scratch (banks large enough for the lane layout)
-};
-
-static int aerolc_create(jaero_aerol_ctx *c, int nchannels, int su_capacity)
-{
-    aerolc_state *cs = new aerolc_state();
-    c->cmode = cs;
-    CGeom &g = cs->g;
-    g.nch = nchannels; g.nchp = (nchannels + 63) / 64 * 64;
-    g.su_cap = su_capacity > 0 ? su_capacity : 3 * 64; // 64 frames between reads
-    g.v_cap = (g.su_cap + 2) / 3;
-    g.ev_cap = 256;
-    int rc;
-#define CA(ptr, count) do { if ((rc = aalloc(c, &(ptr), (size_t)(count)))) return rc; } while (0)
-    CA(cs->p.I, (size_t)CI_NFIELDS * g.nchp);
-    CA(cs->p.B, (size_t)4 * g.nchp);
-    CA(cs->p.dep, (size_t)g.nchp * CC_PITCH);
-    CA(cs->p.vbits, (size_t)g.nchp * (CC_NSOFT / 2));
-    CA(cs->p.overlap, (size_t)g.nchp * 64);
-    CA(cs->p.dl2, (size_t)CC_PREV_PITCH * g.nchp + 64);
-    CA(cs->p.sus, (size_t)g.nchp * g.su_cap * 16);
-    CA(cs->p.voice, (size_t)g.nchp * g.v_cap * 304);
-    CA(cs->p.events, (size_t)g.nchp * g.ev_cap * 3);
-    if (viterbi_use_lanes(g.nch, CC_NSOFT, 24)) CA(cs->d_vhist, viterbi_hist_bytes(g.nch) / sizeof(unsigned long long));
-    uint8_t *d_scr = nullptr;
-    CA(d_scr, 5000);
-    unsigned long long *d_scrf = nullptr;
-    CA(d_scrf, 50);
-#undef CA
-    cs->p.scr = d_scr;
-    {
-        std::vector<uint8_t> scr(5000);
-        int state[15] = {1, 1, 0, 1, 0, 0, 1, 0, 1, 0, 1, 1, 0, 0, 1};
-        for (int k = 0; k < 5000; k++)
-        {
-            const int val0 = state[0] ^ state[14];
-            scr[k] = (uint8_t)val0;
-            for (int i = 14; i > 0; i--) state[i] = state[i - 1];
-            state[0] = val0;
-        }
-        HIPCHK(hipMemcpy(d_scr, scr.data(), 5000, hipMemcpyHostToDevice));
-        std::vector<unsigned long long> scrf(50, 0ull);
-        for (int y = 0; y < 25; y++)
-            for (int i = 0; i < 108; i++) scrf[2 * y + i / 64] |= (unsigned long long)(scr[109 * y + 1 + i] & 1) << (i % 64);
-        HIPCHK(hipMemcpy(d_scrf, scrf.data(), scrf.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        cs->p.scrf = d_scrf;
-        // the depunctured buffer: every 4th symbol an erasure, for good (the walk only writes the other three)
-        std::vector<uint8_t> dep((size_t)g.nchp * CC_PITCH, 0);
-        for (size_t k = 0; k < dep.size(); k++) if ((k % CC_PITCH) % 4 == 3) dep[k] = 128;
-        HIPCHK(hipMemcpy(cs->p.dep, dep.data(), dep.size(), hipMemcpyHostToDevice));
-        std::vector<int> I((size_t)CI_NFIELDS * g.nchp, 0);
-        for (int ch = 0; ch < g.nchp; ch++)
-        {
-            I[(size_t)CI_CNTR * g.nchp + ch] = 1000000000; // AeroL constructor (aerol.cpp:907)
-            I[(size_t)CI_EV_CNT * g.nchp + ch] = 1;        // row 0 = [0, DCD, 0]: DataCarrierDetect(false) emitted by the constructor
-        }
-        HIPCHK(hipMemcpy(cs->p.I, I.data(), I.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
-static int aerolc_write(jaero_aerol_ctx *c, const int16_t *dsoft, const int *dcounts, int stride, int max_count, hipStream_t st)
-{
-    aerolc_state *cs = (aerolc_state *)c->cmode;
-    const CGeom &g = cs->g;
-    // a round finishes at most one frame per channel.  Frame ends are at least 4098 soft bits apart: the detector window reopens at
-    // cntr > CC_FRAME - 112, so a (false or real) unique word can fire two bits after a completed frame and the next frame ends
-    // CC_FRAME bits after that -- not CC_FRAME + 104 as in a clean stream.
-    // A lane's round also ends when it meets a third jumpable stretch (k_aerolc_bits): it has then consumed at least one whole frame body
-    // (CC_FRAME - 112 soft bits), so the bound below covers that too.
-    const int rounds = max_count / (CC_FRAME - 112) + 2;
-    const int *valid = cs->p.I + (size_t)CI_HAS_BLOCK * g.nchp;
-    const dim3 grid(g.nchp / 64), block(64);
-    for (int r = 0; r < rounds; r++)
-    {
-        aprof_begin(c, 0, st);
-        hipLaunchKernelGGL(k_aerolc_bits, grid, block, 0, st, g, cs->p, dsoft, dcounts, stride);
-        hipLaunchKernelGGL(k_aerolc_bulk, dim3((g.nch + 3) / 4), dim3(256), 0, st, g, cs->p, dsoft, stride, -1, -1); // both stretches of a round, in order
-        aprof_end(c, st);
-        aprof_begin(c, 1, st);
-        // one block per wavefront for small banks, one per lane (k_viterbi_lanes) from 16 384 channels on, as the P-channel pipeline
-        viterbi_launch(st, (const uint8_t *)cs->p.dep, CC_NSOFT, (const uint8_t *)cs->p.overlap, 24, cs->p.vbits, CC_NSOFT / 2, 25, CC_NSOFT / 2, g.nch, valid,
-                       cs->d_vhist, 0, 0, 0, CC_PITCH);
-        hipLaunchKernelGGL(k_viterbi_overlap_update, dim3(g.nch), dim3(64), 0, st, (const uint8_t *)cs->p.dep, CC_NSOFT, cs->p.overlap, g.nch, valid, 0, CC_PITCH);
-        aprof_end(c, st);
-        aprof_begin(c, 2, st);
-        hipLaunchKernelGGL(k_aerolc_post, grid, block, 0, st, g, cs->p);
-        aprof_end(c, st);
-    }
-    hipLaunchKernelGGL(k_aerolc_end_write, grid, block, 0, st, g, cs->p, dcounts);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// drains rows of one channel: copies min(count, caprows) rows, keeps the rest (as aerol_read_rows does for the other modes)
-static int aerolc_read(jaero_aerol_ctx *c, int ch, void *rows, int caprows, int *nrows, int cnt_field, const void *base, int cap, size_t rowbytes, int ovbit)
-{
-    aerolc_state *cs = (aerolc_state *)c->cmode;
-    const CGeom &g = cs->g;
-    if (ch < 0 || ch >= g.nch || caprows < 0 || !nrows) return fail(JAERO_EINVAL, "jaero_aerol read: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
-    int cnt = 0;
-    int *dcnt = cs->p.I + (size_t)cnt_field * g.nchp + ch;
-    HIPCHK(hipMemcpy(&cnt, dcnt, sizeof(int), hipMemcpyDeviceToHost));
-    const int take = cnt < caprows ? cnt : caprows;
-    const char *src = (const char *)base + (size_t)ch * cap * rowbytes;
-    if (take > 0 && rows) HIPCHK(hipMemcpy(rows, src, rowbytes * take, hipMemcpyDeviceToHost));
-    const int left = cnt - take;
-    if (left > 0)
-    {
-        std::vector<char> tmp(rowbytes * left);
-        HIPCHK(hipMemcpy(tmp.data(), src + rowbytes * take, tmp.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy((void *)src, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(dcnt, &left, sizeof(int), hipMemcpyHostToDevice));
-    *nrows = take;
-    // rows the kernels had to drop because the caller fell behind (CI_OVERFLOW: 1 signal units, 2 events, 4 voice frames):
-    // reported once, then cleared, as aerol_read_rows does for the P and R/T banks
-    int ov = 0;
-    int *dov = cs->p.I + (size_t)CI_OVERFLOW * g.nchp + ch;
-    HIPCHK(hipMemcpy(&ov, dov, sizeof(int), hipMemcpyDeviceToHost));
-    if (ov & ovbit)
-    {
-        const int z = ov & ~ovbit;
-        HIPCHK(hipMemcpy(dov, &z, sizeof(int), hipMemcpyHostToDevice));
-        return fail(JAERO_EOVERFLOW, "Aero-L C-channel %d overflowed an output buffer (flag %d); rows were dropped", ch, ovbit);
-    }
-    return 0;
-}
-
-extern "C" int jaero_aerol_read_voice(jaero_aerol_ctx *c, int ch, uint8_t *rows, int caprows, int *nrows)
-{
-    if (!c || !c->cmode) return fail(JAERO_EINVAL, "jaero_aerol_read_voice: not a C-channel (fb = 8400) bank");
-    aerolc_state *cs = (aerolc_state *)c->cmode;
-    return aerolc_read(c, ch, rows, caprows, nrows, CI_V_CNT, cs->p.voice, cs->g.v_cap, 304, 4);
-}
-#endif // AEROLC_KERNELS_ONLY

@@ -1,10 +1,10 @@
-// burst_host.h -- host side of the burst banks (included by jaero_hip.hip after jaero_ctx / dalloc / fail are defined).
+// burst_host.h -- host side of the burst banks (included by jaero_hip.hip after jaero_ctx, fail and host_common.h are defined).
 // Geometry = what BurstOqpskDemodulator::setSettings / BurstMskDemodulator::setSettings compute
 // (JAERO/burstoqpskdemodulator.cpp:202-277, JAERO/burstmskdemodulator.cpp:150-325); initial scalar state = their constructors.
+// The bank's device buffers belong to c->mem, burst_write's launches are timed by c->timer (jaero_profile_read's classes 0 - 4: demodulator,
+// k_trident, history push, k_hilbert_fft, k_burst_front with k_ev_compact), and a bit-rate change (burst_rebank) ends in swap_in, as the
+// continuous bank's does.
 #pragma once
-
-static int prof_begin(jaero_ctx *c, int which, hipStream_t st);
-static void prof_end(jaero_ctx *c, int idx, hipStream_t st);
 
 static int host_qround(double d) { return d >= 0.0 ? (int)(d + 0.5) : (int)(d - (double)((int)(d - 1)) + 0.5) + (int)(d - 1); }
 
@@ -127,60 +127,42 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
     g.ev_cap = (c->flags & JAERO_FLAG_TRACE) ? 4096 : 256;
     const int nchp = g.nchp, ng = g.ngroups;
     const bool oq = g.kind == JAERO_KIND_BURST_OQPSK;
-#define DA(ptr, count) do { if ((rc = dalloc(c, &(ptr), (size_t)(count)))) return rc; } while (0)
-    DA(p.S, (size_t)BS_NFIELDS * nchp);
-    DA(p.I, (size_t)BI_NFIELDS * nchp);
-    DA(p.pcmhist, (size_t)g.hist_len * nchp);
-    DA(p.him, (size_t)ng * g.maxseg * 64);
-    DA(p.agc_ring, (size_t)ng * g.agc_len * 64);
-    DA(p.cvre, (size_t)ng * g.cv_len * 64); DA(p.cvim, (size_t)ng * g.cv_len * 64);
-    DA(p.ma1re, (size_t)ng * g.ma1_len * 64); DA(p.ma1im, (size_t)ng * g.ma1_len * 64);
-    DA(p.mav1, (size_t)ng * g.mav1_len * 64);
-    DA(p.fa, (size_t)ng * g.fa_len * 64);
-    DA(p.bt, (size_t)ng * g.bt_len * 64);
-    DA(p.ev_list, nchp); DA(p.ev_count, 4); DA(p.ev_mask, ng);
-    DA(p.tri, nchp);
-    DA(p.eb_e, (size_t)nchp * g.win_ring);
-    DA(p.firsave, (size_t)nchp * 2 * g.fir_n);
-    if (!oq) { DA(p.dly, (size_t)nchp * g.dly_ring); DA(p.dly8, (size_t)nchp * g.d8_ring); DA(p.a1, (size_t)nchp * g.d8_len); }
-    DA(p.msema, (size_t)nchp * g.msema_len);
-    DA(p.soft, (size_t)nchp * g.soft_cap);
-    if (g.sym_cap) DA(p.sym, (size_t)nchp * g.sym_cap * 3);
-    DA(p.evlog, (size_t)nchp * g.ev_cap * 3);
-    DA(c->d_pcm_raw, (size_t)c->max_write * nch);
-    DA(c->d_status, nchp);
+    DevMem &m = c->mem;
+    DA(m, p.S, (size_t)BS_NFIELDS * nchp);
+    DA(m, p.I, (size_t)BI_NFIELDS * nchp);
+    DA(m, p.pcmhist, (size_t)g.hist_len * nchp);
+    DA(m, p.him, (size_t)ng * g.maxseg * 64);
+    DA(m, p.agc_ring, (size_t)ng * g.agc_len * 64);
+    DA(m, p.cvre, (size_t)ng * g.cv_len * 64); DA(m, p.cvim, (size_t)ng * g.cv_len * 64);
+    DA(m, p.ma1re, (size_t)ng * g.ma1_len * 64); DA(m, p.ma1im, (size_t)ng * g.ma1_len * 64);
+    DA(m, p.mav1, (size_t)ng * g.mav1_len * 64);
+    DA(m, p.fa, (size_t)ng * g.fa_len * 64);
+    DA(m, p.bt, (size_t)ng * g.bt_len * 64);
+    DA(m, p.ev_list, nchp); DA(m, p.ev_count, 4); DA(m, p.ev_mask, ng);
+    DA(m, p.tri, nchp);
+    DA(m, p.eb_e, (size_t)nchp * g.win_ring);
+    DA(m, p.firsave, (size_t)nchp * 2 * g.fir_n);
+    if (!oq) { DA(m, p.dly, (size_t)nchp * g.dly_ring); DA(m, p.dly8, (size_t)nchp * g.d8_ring); DA(m, p.a1, (size_t)nchp * g.d8_len); }
+    DA(m, p.msema, (size_t)nchp * g.msema_len);
+    DA(m, p.soft, (size_t)nchp * g.soft_cap);
+    if (g.sym_cap) DA(m, p.sym, (size_t)nchp * g.sym_cap * 3);
+    DA(m, p.evlog, (size_t)nchp * g.ev_cap * 3);
+    DA(m, c->d_pcm_raw, (size_t)c->max_write * nch);
+    DA(m, c->d_status, nchp);
     if (!oq && ((g.agc2_len | g.eb_len) & 7))
         return fail(JAERO_ENOTSUP, "burst MSK at fb %g / Fs %g: the AGC2 / EbNo windows (%d, %d entries) are not whole cells of eight", g.fb, g.Fs, g.agc2_len, g.eb_len);
     if (oq && ((int)floor((0.25 * g.fb) / (g.Fs / (double)TRI_N) + 0.5)) % 4 != 0)
         return fail(JAERO_ENOTSUP, "burst OQPSK at fb %g / Fs %g: k_trident searches one residue class of bins at a time and needs round(fb / 4 / hzperbin) to be a multiple of 4", g.fb, g.Fs);
     double2 *d_cis = nullptr, *d_tw = nullptr, *d_tw15 = nullptr;
     double *d_taps = nullptr, *d_hil = nullptr;
-    DA(d_cis, JD_WTSIZE); DA(d_tw, TRI_H); DA(d_tw15, TRI_H); DA(d_taps, 2 * g.fir_n); DA(d_hil, g.hil_ntaps / 4);
-#undef DA
+    DA(m, d_cis, JD_WTSIZE); DA(m, d_tw, TRI_H); DA(m, d_tw15, TRI_H); DA(m, d_taps, 2 * g.fir_n); DA(m, d_hil, g.hil_ntaps / 4);
     p.cis = d_cis; p.tw14 = d_tw; p.tw15 = d_tw15; p.taps2 = d_taps; p.hil_taps = d_hil;
     {
-        std::vector<double2> cis(JD_WTSIZE);
-        for (int i = 0; i < JD_WTSIZE; i++)
-        {
-            cis[i].y = (sin(2 * M_PI * ((double)i) / JD_WTSIZE));
-            cis[i].x = (sin(M_PI_2 + 2 * M_PI * ((double)i) / JD_WTSIZE));
-        }
-        HIPCHK(hipMemcpy(d_cis, cis.data(), sizeof(double2) * JD_WTSIZE, hipMemcpyHostToDevice));
-        std::vector<double2> tw(TRI_H);
-        for (int i = 0; i < 8192; i++) { double a = -2.0 * M_PI * ((double)i) / 8192.0; tw[i].x = cos(a); tw[i].y = sin(a); }
-        HIPCHK(hipMemcpy(d_tw, tw.data(), sizeof(double2) * 8192, hipMemcpyHostToDevice));
-        for (int i = 0; i < TRI_H; i++) { double a = -2.0 * M_PI * ((double)i) / ((double)TRI_N); tw[i].x = cos(a); tw[i].y = sin(a); }
-        HIPCHK(hipMemcpy(d_tw15, tw.data(), sizeof(double2) * TRI_H, hipMemcpyHostToDevice));
-        std::vector<double> taps;
-        if (oq) taps = rrc_design(1.0, 55, g.Fs, g.fb / 2.0);
-        else
-        {
-            taps.resize(g.fir_n);
-            for (int i = 0; i < g.fir_n; i++) taps[i] = sin(M_PI * i / (2.0 * g.SPS)) / (2.0 * g.SPS);
-        }
-        std::vector<double> t2(2 * g.fir_n);
-        for (int i = 0; i < 2 * g.fir_n; i++) t2[i] = taps[i % g.fir_n];
-        HIPCHK(hipMemcpy(d_taps, t2.data(), sizeof(double) * t2.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_cis, cis_table().data(), sizeof(double2) * JD_WTSIZE, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_tw, twiddles(8192, 8192).data(), sizeof(double2) * 8192, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_tw15, twiddles(TRI_N, TRI_H).data(), sizeof(double2) * TRI_H, hipMemcpyHostToDevice));
+        const std::vector<double> taps = oq ? rrc_design(1.0, 55, g.Fs, g.fb / 2.0) : half_sine_taps((int)g.SPS);
+        HIPCHK(hipMemcpy(d_taps, doubled_taps(taps).data(), sizeof(double) * 2 * g.fir_n, hipMemcpyHostToDevice));
         // QJHilbertFilter::setSize (JAERO/DSP.cpp:760-787): imaginary part of the odd taps
         const int N = g.hil_ntaps;
         std::vector<double> hil(N / 4);
@@ -194,7 +176,7 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
         std::vector<double> gk(N, 0.0);
         for (int k = 1; k < N; k += 2) gk[k] = (2.0 / ((double)N)) / (tan(M_PI * (((double)k) / ((double)N) - 0.5)));
         double2 *dH = nullptr, *dtw = nullptr;
-        if ((rc = fft4096_tables(c, gk, &dH, &dtw, (const void *)k_hilbert_fft))) return rc;
+        if ((rc = fft4096_tables(m, gk, &dH, &dtw, (const void *)k_hilbert_fft))) return rc;
         p.hilH = dH; p.tw12 = dtw;
         if (g.hil_ntaps != 2048) return fail(JAERO_ENOTSUP, "the overlap-save Hilbert kernel is built for QJHilbertFilter's 2048 taps");
     }
@@ -264,14 +246,14 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
     }
     // new samples -> PCM history ring (the Hilbert FIR only ever reads the ring)
     {
-        const int pi = prof_begin(c, 2, st);
+        const int pi = c->timer.begin(2, st);
         const int slot0 = (int)(c->nsamples_total % g.hist_len);
         if (layout == JAERO_PCM_FRAME_MAJOR)
             hipLaunchKernelGGL(k_hist_push_frames, dim3((nchp + 255) / 256, nsamples), dim3(256), 0, st, dsrc, nch, nch, p.pcmhist, nchp, g.hist_len, slot0, nsamples);
         else
             hipLaunchKernelGGL(k_hist_push_chmajor, dim3(nchp / 64, (nsamples + 63) / 64), dim3(256), 0, st, dsrc, nch, nsamples, p.pcmhist, nchp, g.hist_len, slot0);
         LAUNCHCHK("the burst history push");
-        prof_end(c, pi, st);
+        c->timer.end(pi, st);
     }
     const KernelRec<TridentFn> &tri = c->trident;
     const KernelRec<BurstDemodFn> &dm = c->bdemod;
@@ -281,11 +263,11 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
     {
         const int n = (nsamples - pos) < g.maxseg ? (nsamples - pos) : g.maxseg;
         const long long n0 = c->nsamples_total;
-        int pi = prof_begin(c, 3, st);
+        int pi = c->timer.begin(3, st);
         hipLaunchKernelGGL(k_hilbert_fft, dim3(g.nchp / 8, (int)(((n0 + n - 1) >> 11) - (n0 >> 11) + 1)), dim3(PF_THREADS), 4 * 2 * PRE_L * (int)sizeof(double), st, g, p, n, n0);
         LAUNCHCHK("k_hilbert_fft");
-        prof_end(c, pi, st);
-        pi = prof_begin(c, 4, st);
+        c->timer.end(pi, st);
+        pi = c->timer.begin(4, st);
         // bt_hold_left is an UPPER BOUND of every lane's BI_BT_HOLD (the per-lane, per-sample counter the kernel obeys): each setSettings sets
         // both to bt_lag at the same moment, the lane's falls by one per sample, this one by n per segment of n samples -- so while any lane
         // still holds, the HOLD instantiation runs (for all lanes: those whose counter is 0 compute what <false> computes).  A write that
@@ -299,15 +281,15 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         LAUNCHCHK("k_burst_front");
         hipLaunchKernelGGL(k_ev_compact, dim3(1), dim3(1024), 0, st, (const unsigned long long *)p.ev_mask, g.ngroups, p.ev_list, p.ev_count);
         LAUNCHCHK("k_ev_compact");
-        prof_end(c, pi, st);
-        pi = prof_begin(c, 1, st);
+        c->timer.end(pi, st);
+        pi = c->timer.begin(1, st);
         hipLaunchKernelGGL(tri.fn, dim3(tri.grid), dim3(tri.block), tri.lds, st, g, p, n0);
         LAUNCHCHK("k_trident");
-        prof_end(c, pi, st);
-        pi = prof_begin(c, 0, st);
+        c->timer.end(pi, st);
+        pi = c->timer.begin(0, st);
         hipLaunchKernelGGL(dm.fn, dim3(dm.grid), dim3(dm.block), dm.lds, st, g, p, n, n0, first);
         LAUNCHCHK("the burst demodulator");
-        prof_end(c, pi, st);
+        c->timer.end(pi, st);
         first = 0;
         c->nsamples_total += n;
         pos += n;
@@ -320,7 +302,6 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
 // burstmskdemodulator.cpp:150-325): a sibling bank for the new rate takes the old one's place behind the handle; the scalar state comes
 // across as whole columns, k_burst_carry moves the DelayThings' contents in storage order and applies what setSettings re-creates, msema and
 // the outputs not read yet are copied.  Control plane: allocates and synchronises.
-static void prof_collect(jaero_ctx *c);
 static int burst_rebank(jaero_ctx *c, const jaero_settings *s)
 {
     if (c->poisoned) return fail(JAERO_EHIP, "jaero_set_settings: a launch inside an earlier jaero_write failed; this bank's state cannot be carried over");
@@ -330,42 +311,34 @@ static int burst_rebank(jaero_ctx *c, const jaero_settings *s)
     jaero_ctx *n = nullptr;
     int rc = jaero_create(c->device, og.nch, s, 0, c->flags, c->max_write, c->soft_cap_req, &n);
     if (rc) return rc;
+    BankPtr nb(n, jaero_destroy); // goes again on every early return
     const BGeom &ng = n->bg;
     const int nchp = og.nchp;
-    auto fin = [&](int code) { jaero_destroy(n); return code; };
-#define BCP(dst, src, bytes) do { if (hipMemcpy((dst), (src), (bytes), hipMemcpyDeviceToDevice) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: carry-over copy failed")); } while (0)
-#define BCP2(dst, dpitch, src, spitch, width, rows) do { if (hipMemcpy2D((dst), (dpitch), (src), (spitch), (width), (rows), hipMemcpyDeviceToDevice) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: carry-over copy failed")); } while (0)
     {
         // outputs not read yet: soft bits (RxDataBits' pending tail included), captured symbols, event rows
         std::vector<int> cnt(2 * (size_t)nchp);
         static_assert(BI_SYM_CNT == BI_SOFT_CNT + 1, "output counters are consecutive columns");
-        if (hipMemcpy(cnt.data(), c->bp.I + (size_t)BI_SOFT_CNT * nchp, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: reading the output counters failed"));
+        HIPCHK(hipMemcpy(cnt.data(), c->bp.I + (size_t)BI_SOFT_CNT * nchp, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
         int mx[2] = {0, 0};
         for (int k = 0; k < 2; k++) for (int ch = 0; ch < og.nch; ch++) mx[k] = cnt[(size_t)k * nchp + ch] > mx[k] ? cnt[(size_t)k * nchp + ch] : mx[k];
         if (mx[0] > ng.soft_cap || mx[1] > ng.sym_cap)
-            return fin(fail(JAERO_EINVAL, "jaero_set_settings: unread outputs (%d soft bits, %d symbols) exceed the new bank's buffers; read them first", mx[0], mx[1]));
-        if (mx[0]) BCP2(n->bp.soft, sizeof(int16_t) * ng.soft_cap, c->bp.soft, sizeof(int16_t) * og.soft_cap, sizeof(int16_t) * mx[0], (size_t)nchp);
-        if (mx[1]) BCP2(n->bp.sym, sizeof(double) * 3 * ng.sym_cap, c->bp.sym, sizeof(double) * 3 * og.sym_cap, sizeof(double) * 3 * mx[1], (size_t)nchp);
-        BCP(n->bp.evlog, c->bp.evlog, sizeof(double) * (size_t)nchp * og.ev_cap * 3);
+            return fail(JAERO_EINVAL, "jaero_set_settings: unread outputs (%d soft bits, %d symbols) exceed the new bank's buffers; read them first", mx[0], mx[1]);
+        if ((rc = carry_rows(n->bp.soft, ng.soft_cap, c->bp.soft, og.soft_cap, sizeof(int16_t), mx[0], nchp)) ||
+            (rc = carry_rows(n->bp.sym, ng.sym_cap, c->bp.sym, og.sym_cap, 3 * sizeof(double), mx[1], nchp)) ||
+            (rc = carry(n->bp.evlog, c->bp.evlog, sizeof(double) * (size_t)nchp * og.ev_cap * 3)))
+            return rc;
     }
-    BCP(n->bp.S, c->bp.S, sizeof(double) * (size_t)BS_NFIELDS * nchp);
-    BCP(n->bp.I, c->bp.I, sizeof(int) * (size_t)BI_NFIELDS * nchp);
-    BCP(n->bp.msema, c->bp.msema, sizeof(double) * (size_t)nchp * og.msema_len); // msema is made once, in the constructor
+    if ((rc = carry(n->bp.S, c->bp.S, sizeof(double) * (size_t)BS_NFIELDS * nchp)) || (rc = carry(n->bp.I, c->bp.I, sizeof(int) * (size_t)BI_NFIELDS * nchp)) ||
+        (rc = carry(n->bp.msema, c->bp.msema, sizeof(double) * (size_t)nchp * og.msema_len))) // msema is made once, in the constructor
+        return rc;
     BSetVals v;
     v.freq_center = s->freq_center; v.lockingbw = s->lockingbw; v.signalthreshold = s->signalthreshold;
     hipLaunchKernelGGL(k_burst_carry, dim3(nchp / 64), dim3(64), 0, 0, og, c->bp, ng, n->bp, v, (long long)c->nsamples_total);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: carry-over failed"));
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return fail(JAERO_EHIP, "jaero_set_settings: carry-over failed");
     n->nsamples_total = c->nsamples_total;
-    n->m.flags = c->m.flags;
-    for (int ch = 0; ch < nchp; ch++) n->m.flags[ch] &= ~JF_DCD;
     n->bt_hold_left = ng.bt_lag;
-    if (c->prof) prof_collect(c);
-    n->prof = c->prof;
-    for (size_t k = 0; k < sizeof(c->slots) / sizeof(c->slots[0]); k++) n->slots[k] = c->slots[k];
-#undef BCP
-#undef BCP2
-    std::swap(*c, *n);
-    jaero_destroy(n); // the old bank
+    swap_in(c, std::move(nb));
+    for (int &f : c->m.flags) f &= ~JF_DCD; // dcd = false at the end of BurstMskDemodulator::setSettings
     return 0;
 }
 

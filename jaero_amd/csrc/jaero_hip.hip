@@ -15,6 +15,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -61,12 +62,11 @@ static int fail(int code, const char *fmt, ...)
         hipError_t _e = hipGetLastError();                                                               \
         if (_e != hipSuccess) return fail(JAERO_EHIP, "launch of %s failed: %s (%s:%d)", what, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
+#include "host_common.h"
 
 // k_msk_samples: matched-filter history slots kept in LDS (the rest in VGPRs)
 #define MSK_LDSN_40 24 // of 40 taps (1200 bps at 24 kHz, 600 bps at 12 kHz)
 #define MSK_LDSN_20 12 // of 20 taps (1200 bps at 12 kHz)
-
-struct ProfSlot { double ms = 0; int launches = 0; };
 
 // Host mirror of the two integer counters that decide WHEN the reference runs its coarse-frequency estimate
 // (bbcycbuff_ptr and coarseCounter, JAERO/oqpskdemodulator.cpp:410-431 == JAERO/mskdemodulator.cpp:350-368).
@@ -178,7 +178,7 @@ struct jaero_ctx
     unsigned flags = 0;
     int max_write = 0;
     int soft_cap_req = 0; // softbit_capacity as given to jaero_create (0 = default for the rate): a re-created bank asks for the same
-    std::vector<void *> allocs;
+    DevMem mem;
     // device helpers
     int16_t *d_pcm_frames = nullptr; // [max_write][nchp] staging for channel-major / host input
     int16_t *d_pcm_raw = nullptr;    // [nch*max_write] staging for host input
@@ -214,13 +214,7 @@ struct jaero_ctx
     int16_t *o_soft = nullptr; double *o_sym = nullptr;
     int *o_soft_cnt = nullptr, *o_sym_cnt = nullptr, *o_overflow = nullptr, *o_flags = nullptr;
     int *o_nrx = nullptr; // burst: soft bits pushed but not yet emitted (RxDataBits.size()), kept at the tail of the buffer
-    // profiling
-    bool prof = false;
-    ProfSlot slots[5];
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    struct EvUse { int which; int idx; };
-    std::vector<EvUse> ev_used;
-    size_t ev_next = 0;
+    KernelTimer timer{5}; // jaero_profile_read's five kernel classes
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr; // a write on another stream than the previous one waits for what was enqueued on that one (setters included)
     bool poisoned = false;         // a launch inside a write failed: the host's schedule mirror has advanced past the device state
@@ -326,18 +320,24 @@ __global__ void k_status_burst(const BGeom g, const BPtrs p, int ch_first, int n
 }
 
 // ------------------------------------------------------------------------------------------ helpers
-template <class T>
-static int dalloc(jaero_ctx *c, T **ptr, size_t count, bool zero = true)
+// the readers of a bank's per-channel outputs: drain channel ch of `b`, then report `ovbit` of its overflow word
+static int read_output(jaero_ctx *c, const char *who, const RowBuf &b, int ch, void *rows, int caprows, int *nrows, int ovbit, const int *pending = nullptr)
 {
-    void *q = nullptr;
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess) return fail(JAERO_ENOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-    if (zero) { e = hipMemset(q, 0, bytes); if (e != hipSuccess) return fail(JAERO_EHIP, "hipMemset failed: %s", hipGetErrorString(e)); }
-    c->allocs.push_back(q);
-    *ptr = (T *)q;
-    return 0;
+    const int rc = drain_rows(who, c->device, c->last_stream, c->o_nch, b, ch, rows, caprows, nrows, pending);
+    return rc ? rc : report_overflow(c->o_overflow + ch, ovbit, ch);
+}
+
+// The end of a rate change (rebank_with_carry_over, burst_rebank): the new bank takes the old one's place behind the handle and keeps the
+// handle's kernel timings -- the launches since the last jaero_profile_read included, whose events go with the old bank -- and host flag
+// mirror.  The old bank goes when `n` does.
+using BankPtr = std::unique_ptr<jaero_ctx, void (*)(jaero_ctx *)>;
+static void swap_in(jaero_ctx *c, BankPtr n)
+{
+    c->timer.collect();
+    n->timer.on = c->timer.on;
+    n->timer.slots = c->timer.slots;
+    n->m.flags = c->m.flags;
+    std::swap(*c, *n);
 }
 
 // RootRaisedCosine::design (JAERO/DSP.h:316-338)
@@ -495,9 +495,9 @@ static auto by_flags(unsigned flags, F f)
     return eb ? (cs ? f(y, y) : f(y, n)) : (cs ? f(n, y) : f(n, n));
 }
 
-// Tables of the overlap-save filters (k_pre8400_fft, k_hilbert_fft), in buffers of the bank: H = DFT_4096(taps, zero-padded) / 4096 and
+// Tables of the overlap-save filters (k_pre8400_fft, k_hilbert_fft), in buffers of `m`: H = DFT_4096(taps, zero-padded) / 4096 and
 // exp(-2 pi i k / 4096), summed in long double on the host.  kernel_fn = the kernel whose dynamic LDS limit is raised to the 128 KiB exchange buffer.
-static int fft4096_tables(jaero_ctx *c, const std::vector<double> &taps, double2 **d_H, double2 **d_tw, const void *kernel_fn)
+static int fft4096_tables(DevMem &m, const std::vector<double> &taps, double2 **d_H, double2 **d_tw, const void *kernel_fn)
 {
     const int N = 2 * PRE_L;
     std::vector<long double> cr(N), ci(N);
@@ -511,7 +511,7 @@ static int fft4096_tables(jaero_ctx *c, const std::vector<double> &taps, double2
         tw[k].x = (double)cr[k]; tw[k].y = (double)ci[k];
     }
     int rc;
-    if ((rc = dalloc(c, d_H, N, false)) || (rc = dalloc(c, d_tw, N, false))) return rc;
+    if ((rc = dalloc(m, d_H, N, false)) || (rc = dalloc(m, d_tw, N, false))) return rc;
     HIPCHK(hipMemcpy(*d_H, H.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(*d_tw, tw.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute(kernel_fn, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * PRE_L * (int)sizeof(double)));
@@ -566,10 +566,8 @@ extern "C" void jaero_destroy(jaero_ctx *c)
         hipMemcpyToSymbol(HIP_SYMBOL(g_fb_trace), z, sizeof(z));
     }
 #endif
-    for (void *q : c->allocs) hipFree(q);
-    for (auto &e : c->ev_pool) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (c->order_ev) hipEventDestroy(c->order_ev);
-    delete c;
+    delete c; // its device memory and timing events with it
 }
 
 static void launch_pre8400_filter(const JGeom &g, const JPtrs &p, const JPre &q, int n, long long n0, hipStream_t st)
@@ -673,17 +671,17 @@ static int bank_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, co
     g.log_cap = (flags & JAERO_FLAG_STATUS_LOG) ? (int)ceil(g.soft_cap * g.Fs / g.fb / (g.nfft / 4)) + 16 : 0;
     const int nchp = g.nchp, ng = g.ngroups;
 
-#define DA(ptr, count) do { if ((rc = dalloc(c, &(ptr), (size_t)(count)))) return rc; } while (0)
-    DA(c->p.S, (size_t)S_NFIELDS * nchp);
-    DA(c->p.I, (size_t)I_NFIELDS * nchp);
-    DA(c->p.win, (size_t)ng * g.win_len * 64);
-    DA(c->p.bbring, (size_t)nchp * g.nfft);
-    DA(c->p.y, (size_t)nchp * g.nfft);
-    DA(c->p.marg, (size_t)nchp * g.marg_len);
-    DA(c->p.dt, (size_t)nchp * g.dt_len);
-    DA(c->p.pm, (size_t)nchp * g.pm_len);
-    DA(c->p.msema, (size_t)nchp * g.msema_len);
-    DA(c->p.firsave, (size_t)ng * 2 * g.fir_n * 64);
+    DevMem &m = c->mem;
+    DA(m, c->p.S, (size_t)S_NFIELDS * nchp);
+    DA(m, c->p.I, (size_t)I_NFIELDS * nchp);
+    DA(m, c->p.win, (size_t)ng * g.win_len * 64);
+    DA(m, c->p.bbring, (size_t)nchp * g.nfft);
+    DA(m, c->p.y, (size_t)nchp * g.nfft);
+    DA(m, c->p.marg, (size_t)nchp * g.marg_len);
+    DA(m, c->p.dt, (size_t)nchp * g.dt_len);
+    DA(m, c->p.pm, (size_t)nchp * g.pm_len);
+    DA(m, c->p.msema, (size_t)nchp * g.msema_len);
+    DA(m, c->p.firsave, (size_t)ng * 2 * g.fir_n * 64);
     if (g.kind == JAERO_KIND_OQPSK && g.fb == 8400)
     {
         c->pre8400 = true;
@@ -692,62 +690,43 @@ static int bank_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, co
         while (ring < max_write_samples + 3 * PRE_L) ring <<= 1;
         c->pre.ring = ring;
         c->pre.cap = max_write_samples;
-        DA(c->pre.xring, (size_t)ring * nchp);
-        DA(c->pre.cidx, (size_t)max_write_samples * nchp);
-        DA(c->pre.out, (size_t)max_write_samples * nchp);
-        DA(c->pre.hold, (size_t)nchp); // zeros (DA clears): nothing held
+        DA(m, c->pre.xring, (size_t)ring * nchp);
+        DA(m, c->pre.cidx, (size_t)max_write_samples * nchp);
+        DA(m, c->pre.out, (size_t)max_write_samples * nchp);
+        DA(m, c->pre.hold, (size_t)nchp); // zeros (DA clears): nothing held
         double *d_pre_taps = nullptr;
-        DA(d_pre_taps, PRE_K);
+        DA(m, d_pre_taps, PRE_K);
         const std::vector<double> pt = rrc_design(0.6, 2048, g.Fs, g.fb / 2); // rrc_pre_imp (oqpskdemodulator.cpp:281)
         if ((int)pt.size() != PRE_K) return fail(JAERO_EHIP, "prefilter design returned %zu taps", pt.size());
         HIPCHK(hipMemcpy(d_pre_taps, pt.data(), sizeof(double) * PRE_K, hipMemcpyHostToDevice));
         c->pre.taps = d_pre_taps;
         double2 *dH = nullptr, *dtw = nullptr;
-        if ((rc = fft4096_tables(c, pt, &dH, &dtw, (const void *)k_pre8400_fft))) return rc;
+        if ((rc = fft4096_tables(m, pt, &dH, &dtw, (const void *)k_pre8400_fft))) return rc;
         c->pre.H = dH; c->pre.tw = dtw;
     }
-    if (g.kind == JAERO_KIND_MSK) { DA(c->p.dly, (size_t)ng * (g.sps + 1) * 64); DA(c->p.dly8, (size_t)ng * (g.sps2 + 1) * 64); }
+    if (g.kind == JAERO_KIND_MSK) { DA(m, c->p.dly, (size_t)ng * (g.sps + 1) * 64); DA(m, c->p.dly8, (size_t)ng * (g.sps2 + 1) * 64); }
     // k_oqpsk_fb keeps the symbol-instant windows marg / dt / pm / msema in one combined record ring
     static_assert(JD_SYMREC_LEN == 800, "the combined symbol-record ring of k_oqpsk_fb assumes the reference's window lengths (800 / 400 / 400 / 400)");
-    if (g.kind == JAERO_KIND_OQPSK) DA(c->p.symrec, (size_t)nchp * JD_SYMREC_LEN * 8);
-    DA(c->p.soft, (size_t)nchp * g.soft_cap);
-    if (g.sym_cap) DA(c->p.sym, (size_t)nchp * g.sym_cap * 3);
-    if (g.log_cap) DA(c->p.slog, (size_t)nchp * g.log_cap * 6);
-    DA(c->d_pcm_frames, (size_t)max_write_samples * nchp);
-    DA(c->d_pcm_raw, (size_t)max_write_samples * nchannels);
-    DA(c->d_chanlist, nchp);
-    DA(c->d_status, nchp);
-    DA(c->d_tw, g.nfft);
+    if (g.kind == JAERO_KIND_OQPSK) DA(m, c->p.symrec, (size_t)nchp * JD_SYMREC_LEN * 8);
+    DA(m, c->p.soft, (size_t)nchp * g.soft_cap);
+    if (g.sym_cap) DA(m, c->p.sym, (size_t)nchp * g.sym_cap * 3);
+    if (g.log_cap) DA(m, c->p.slog, (size_t)nchp * g.log_cap * 6);
+    DA(m, c->d_pcm_frames, (size_t)max_write_samples * nchp);
+    DA(m, c->d_pcm_raw, (size_t)max_write_samples * nchannels);
+    DA(m, c->d_chanlist, nchp);
+    DA(m, c->d_status, nchp);
+    DA(m, c->d_tw, g.nfft);
     double2 *d_cis = nullptr;
     double *d_taps = nullptr;
-    DA(d_cis, JD_WTSIZE);
-    DA(d_taps, 2 * g.fir_n);
-#undef DA
+    DA(m, d_cis, JD_WTSIZE);
+    DA(m, d_taps, 2 * g.fir_n);
     c->p.cis = d_cis; c->p.taps2 = d_taps;
 
-    // TrigLookUp (JAERO/DSP.cpp:11-30): generated on the host so the table bits match the reference's libm
     {
-        std::vector<double2> cis(JD_WTSIZE);
-        for (int i = 0; i < JD_WTSIZE; i++)
-        {
-            cis[i].y = (sin(2 * M_PI * ((double)i) / JD_WTSIZE));
-            cis[i].x = (sin(M_PI_2 + 2 * M_PI * ((double)i) / JD_WTSIZE));
-        }
-        HIPCHK(hipMemcpy(d_cis, cis.data(), sizeof(double2) * JD_WTSIZE, hipMemcpyHostToDevice));
-        std::vector<double2> tw(g.nfft);
-        for (int i = 0; i < g.nfft; i++) { double a = -2.0 * M_PI * ((double)i) / ((double)g.nfft); tw[i].x = cos(a); tw[i].y = sin(a); }
-        HIPCHK(hipMemcpy(c->d_tw, tw.data(), sizeof(double2) * g.nfft, hipMemcpyHostToDevice));
-        std::vector<double> taps;
-        if (g.kind == JAERO_KIND_OQPSK) taps = rrc_design(g.fb == 8400 ? 0.6 : 1.0, 55, g.Fs, g.fb / 2);
-        else
-        {
-            taps.resize(g.fir_n);
-            const double SPS = (double)g.sps;
-            for (int i = 0; i < 2 * SPS; i++) taps[i] = sin(M_PI * i / (2.0 * SPS)) / (2.0 * SPS);
-        }
-        std::vector<double> t2(2 * g.fir_n);
-        for (int i = 0; i < 2 * g.fir_n; i++) t2[i] = taps[i % g.fir_n];
-        HIPCHK(hipMemcpy(d_taps, t2.data(), sizeof(double) * t2.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_cis, cis_table().data(), sizeof(double2) * JD_WTSIZE, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(c->d_tw, twiddles(g.nfft, g.nfft).data(), sizeof(double2) * g.nfft, hipMemcpyHostToDevice));
+        const std::vector<double> taps = g.kind == JAERO_KIND_OQPSK ? rrc_design(g.fb == 8400 ? 0.6 : 1.0, 55, g.Fs, g.fb / 2) : half_sine_taps(g.sps);
+        HIPCHK(hipMemcpy(d_taps, doubled_taps(taps).data(), sizeof(double) * 2 * g.fir_n, hipMemcpyHostToDevice));
         if (g.kind == JAERO_KIND_OQPSK)
         {
             for (int i = 0; i < 55; i++)
@@ -786,21 +765,15 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
 {
     if (!out || !settings || nchannels <= 0 || max_write_samples <= 0) return fail(JAERO_EINVAL, "jaero_create: bad arguments");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(JAERO_ENODEV, "device %d out of range (%d devices)", device, ndev);
-    HIPCHK(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(JAERO_ENODEV, "device %d is %s; libjaero_hip is built for gfx950 (MI355X) only", device, prop.gcnArchName);
+    int rc = open_device(device, &prop);
+    if (rc) return rc;
 
     std::vector<jaero_settings> sets(nchannels);
     for (int ch = 0; ch < nchannels; ch++)
         sets[ch] = per_channel_stride ? *(const jaero_settings *)((const char *)settings + (size_t)ch * per_channel_stride) : settings[0];
     const jaero_settings &s0 = sets[0];
-    int rc = validate_settings(s0);
-    if (rc) return rc;
+    if ((rc = validate_settings(s0))) return rc;
     for (int ch = 1; ch < nchannels; ch++)
     {
         const jaero_settings &s = sets[ch];
@@ -992,7 +965,6 @@ __global__ void k_carry_dly(const double2 *__restrict__ od, int Lo, const int *_
 // 175-289, mskdemodulator.cpp:135-263).  Here: a sibling bank is created for the new settings, those survivors are copied into it, the same
 // in-place setSettings as above runs on it, and it takes the place of the old bank behind the handle.  Whole banks only; control plane (it
 // allocates and synchronises).  Outputs not read yet move along; device pointers obtained from the views are stale.
-static void prof_collect(jaero_ctx *c);
 static int rebank_with_carry_over(jaero_ctx *c, const jaero_settings *s)
 {
     const JGeom og = c->g;
@@ -1003,57 +975,58 @@ static int rebank_with_carry_over(jaero_ctx *c, const jaero_settings *s)
     jaero_ctx *n = nullptr;
     int rc = jaero_create(c->device, og.nch, s, 0, c->flags, c->max_write, c->soft_cap_req, &n);
     if (rc) return rc;
+    BankPtr nb(n, jaero_destroy); // goes again on every early return
     const JGeom &ng = n->g;
     const int nchp = og.nchp;
-    auto fin = [&](int code) { jaero_destroy(n); return code; };
-#define CP(dst, src, bytes) do { if (hipMemcpy((dst), (src), (bytes), hipMemcpyDeviceToDevice) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: carry-over copy failed")); } while (0)
-#define CP2(dst, dpitch, src, spitch, width, rows) do { if (hipMemcpy2D((dst), (dpitch), (src), (spitch), (width), (rows), hipMemcpyDeviceToDevice) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: carry-over copy failed")); } while (0)
-    CP(n->p.S, c->p.S, sizeof(double) * (size_t)S_NFIELDS * nchp);
-    CP(n->p.I, c->p.I, sizeof(int) * (size_t)I_NFIELDS * nchp);
+    if ((rc = carry(n->p.S, c->p.S, sizeof(double) * (size_t)S_NFIELDS * nchp)) || (rc = carry(n->p.I, c->p.I, sizeof(int) * (size_t)I_NFIELDS * nchp))) return rc;
     {
         // outputs not read yet (soft bits, captured symbols, status rows) move to the new bank's buffers; its capacities follow the new rate
         std::vector<int> cnt(3 * (size_t)nchp);
         static_assert(I_SYM_CNT == I_SOFT_CNT + 1 && I_LOG_CNT == I_SOFT_CNT + 2, "output counters are consecutive columns");
-        if (hipMemcpy(cnt.data(), c->p.I + (size_t)I_SOFT_CNT * nchp, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: reading the output counters failed"));
+        HIPCHK(hipMemcpy(cnt.data(), c->p.I + (size_t)I_SOFT_CNT * nchp, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
         int mx[3] = {0, 0, 0};
         for (int k = 0; k < 3; k++) for (int ch = 0; ch < og.nch; ch++) mx[k] = cnt[(size_t)k * nchp + ch] > mx[k] ? cnt[(size_t)k * nchp + ch] : mx[k];
         if (mx[0] > ng.soft_cap || mx[1] > ng.sym_cap || mx[2] > ng.log_cap)
-            return fin(fail(JAERO_EINVAL, "jaero_set_settings: unread outputs (%d soft bits, %d symbols, %d status rows) exceed the new bank's buffers; read them first", mx[0], mx[1], mx[2]));
-        if (mx[0]) CP2(n->p.soft, sizeof(int16_t) * ng.soft_cap, c->p.soft, sizeof(int16_t) * og.soft_cap, sizeof(int16_t) * mx[0], (size_t)nchp);
-        if (mx[1]) CP2(n->p.sym, sizeof(double) * 3 * ng.sym_cap, c->p.sym, sizeof(double) * 3 * og.sym_cap, sizeof(double) * 3 * mx[1], (size_t)nchp);
-        if (mx[2]) CP2(n->p.slog, sizeof(double) * 6 * ng.log_cap, c->p.slog, sizeof(double) * 6 * og.log_cap, sizeof(double) * 6 * mx[2], (size_t)nchp);
+            return fail(JAERO_EINVAL, "jaero_set_settings: unread outputs (%d soft bits, %d symbols, %d status rows) exceed the new bank's buffers; read them first", mx[0], mx[1], mx[2]);
+        if ((rc = carry_rows(n->p.soft, ng.soft_cap, c->p.soft, og.soft_cap, sizeof(int16_t), mx[0], nchp)) ||
+            (rc = carry_rows(n->p.sym, ng.sym_cap, c->p.sym, og.sym_cap, 3 * sizeof(double), mx[1], nchp)) ||
+            (rc = carry_rows(n->p.slog, ng.log_cap, c->p.slog, og.log_cap, 6 * sizeof(double), mx[2], nchp)))
+            return rc;
     }
     // windows that survive: msema (both kinds); marg / dt / pm of the OQPSK demodulator (MSK: marg is new, dt keeps a prefix, below)
-    CP(n->p.msema, c->p.msema, sizeof(double) * (size_t)nchp * og.msema_len);
+    if ((rc = carry(n->p.msema, c->p.msema, sizeof(double) * (size_t)nchp * og.msema_len))) return rc;
     if (og.kind == JAERO_KIND_OQPSK)
     {
-        CP(n->p.marg, c->p.marg, sizeof(double) * (size_t)nchp * og.marg_len);
-        CP(n->p.dt, c->p.dt, sizeof(double2) * (size_t)nchp * og.dt_len);
-        CP(n->p.pm, c->p.pm, sizeof(double) * (size_t)nchp * og.pm_len);
-        if (c->p.symrec && n->p.symrec) CP(n->p.symrec, c->p.symrec, sizeof(double) * (size_t)nchp * JD_SYMREC_LEN * 8); // k_oqpsk_fb keeps the four windows in one record ring
+        if ((rc = carry(n->p.marg, c->p.marg, sizeof(double) * (size_t)nchp * og.marg_len)) || (rc = carry(n->p.dt, c->p.dt, sizeof(double2) * (size_t)nchp * og.dt_len)) ||
+            (rc = carry(n->p.pm, c->p.pm, sizeof(double) * (size_t)nchp * og.pm_len)))
+            return rc;
+        // k_oqpsk_fb keeps the four windows in one record ring
+        if (c->p.symrec && n->p.symrec && (rc = carry(n->p.symrec, c->p.symrec, sizeof(double) * (size_t)nchp * JD_SYMREC_LEN * 8))) return rc;
         // the OQPSK EbNo meter is only told the new rates (setup_update, DSP.cpp:723-727): its window -- the newest ebno_len entries of the window
         // ring, at the position that came over with I -- stays; the AGC is new (I_AGC_HOLD, set by apply_live_settings below)
-        if ((c->flags & JAERO_FLAG_EBNO) && og.win_len == ng.win_len) CP(n->p.win, c->p.win, sizeof(double) * (size_t)og.ngroups * og.win_len * 64);
+        if ((c->flags & JAERO_FLAG_EBNO) && og.win_len == ng.win_len && (rc = carry(n->p.win, c->p.win, sizeof(double) * (size_t)og.ngroups * og.win_len * 64))) return rc;
     }
     else
     {
         const int keep = og.dt_len < ng.dt_len ? og.dt_len : ng.dt_len; // dt.setLength: DelayThing keeps the first entries (DSP.h:446-453)
-        CP2(n->p.dt, sizeof(double2) * ng.dt_len, c->p.dt, sizeof(double2) * og.dt_len, sizeof(double2) * keep, (size_t)nchp);
-        CP(n->p.pm, c->p.pm, sizeof(double) * (size_t)nchp * (og.pm_len < ng.pm_len ? og.pm_len : ng.pm_len));
+        if ((rc = carry_rows(n->p.dt, ng.dt_len, c->p.dt, og.dt_len, sizeof(double2), keep, nchp)) ||
+            (rc = carry(n->p.pm, c->p.pm, sizeof(double) * (size_t)nchp * (og.pm_len < ng.pm_len ? og.pm_len : ng.pm_len))))
+            return rc;
+        DevMem tmp;
         int *d_t0 = nullptr;
         if (c->dly_t0.empty()) c->dly_t0.assign(nchp, 0);
-        if (hipMalloc(&d_t0, sizeof(int) * nchp) != hipSuccess) return fin(fail(JAERO_ENOMEM, "jaero_set_settings: out of device memory"));
-        hipMemcpy(d_t0, c->dly_t0.data(), sizeof(int) * nchp, hipMemcpyHostToDevice);
+        DA(tmp, d_t0, nchp);
+        HIPCHK(hipMemcpy(d_t0, c->dly_t0.data(), sizeof(int) * nchp, hipMemcpyHostToDevice));
         // the old bank's shared slot counter stands at nB_total: a channel whose pointer restarted at slot t0 has its buffer index 0 there
         hipLaunchKernelGGL(k_carry_dly, dim3((nchp + 255) / 256), dim3(256), 0, 0, (const double2 *)c->p.dly, og.sps + 1, (const int *)d_t0, (double2 *)n->p.dly, ng.sps + 1, nchp);
         hipStreamSynchronize(0); // this copy's stream only: other banks on the GPU keep running
-        hipFree(d_t0);
     }
     {
         // bbcycbuff.resize / y.resize: same size = untouched, otherwise the first entries stay (new ones are zero)
         const int keep = og.nfft < ng.nfft ? og.nfft : ng.nfft;
-        CP2(n->p.bbring, sizeof(double2) * ng.nfft, c->p.bbring, sizeof(double2) * og.nfft, sizeof(double2) * keep, (size_t)nchp);
-        CP2(n->p.y, sizeof(double) * ng.nfft, c->p.y, sizeof(double) * og.nfft, sizeof(double) * keep, (size_t)nchp);
+        if ((rc = carry_rows(n->p.bbring, ng.nfft, c->p.bbring, og.nfft, sizeof(double2), keep, nchp)) ||
+            (rc = carry_rows(n->p.y, ng.nfft, c->p.y, og.nfft, sizeof(double), keep, nchp)))
+            return rc;
     }
     if (og.kind == JAERO_KIND_OQPSK)
     {
@@ -1062,20 +1035,11 @@ static int rebank_with_carry_over(jaero_ctx *c, const jaero_settings *s)
         // only grows in the 8400 bps branch (:447): after a write at another rate the reference's prefilter oscillator stands at 0 Hz, which
         // is what its first 8400 bps write then mixes with.  Same here: sum 0 over the length of the last write.
         n->pre_nprev = c->pre_nprev;
-        if (!c->pre8400 && hipMemset(n->p.S + (size_t)S_PRE_FSUM * nchp, 0, sizeof(double) * (size_t)nchp) != hipSuccess) return fin(fail(JAERO_EHIP, "memset"));
+        if (!c->pre8400) HIPCHK(hipMemset(n->p.S + (size_t)S_PRE_FSUM * nchp, 0, sizeof(double) * (size_t)nchp));
     }
-#undef CP
-#undef CP2
-    n->m.flags = c->m.flags;
-    // kernel timings of the launches since the last jaero_profile_read belong to the handle, not to the bank behind it: drained into the
-    // totals here (their events go with the old bank)
-    if (c->prof) prof_collect(c);
-    n->prof = c->prof;
-    for (size_t k = 0; k < sizeof(c->slots) / sizeof(c->slots[0]); k++) n->slots[k] = c->slots[k];
-    if ((rc = apply_live_settings(n, 0, ng.nchp, s))) return fin(rc); // the padding lanes too: their window positions came over with I and must fit the new lengths
-    if (hipStreamSynchronize(n->last_stream) != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return fin(fail(JAERO_EHIP, "jaero_set_settings: carry-over failed"));
-    std::swap(*c, *n);
-    jaero_destroy(n); // the old bank
+    if ((rc = apply_live_settings(n, 0, ng.nchp, s))) return rc; // the padding lanes too: their window positions came over with I and must fit the new lengths
+    if (hipStreamSynchronize(n->last_stream) != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return fail(JAERO_EHIP, "jaero_set_settings: carry-over failed");
+    swap_in(c, std::move(nb));
     return 0;
 }
 
@@ -1112,55 +1076,17 @@ extern "C" int jaero_set_settings(jaero_ctx *c, int channel, const jaero_setting
     return apply_live_settings(c, channel < 0 ? 0 : channel, channel < 0 ? g.nch : channel + 1, s);
 }
 
-// ------------------------------------------------------------------------------------------ profiling helpers
-static int prof_begin(jaero_ctx *c, int which, hipStream_t st)
-{
-    if (!c->prof) return -1;
-    if (c->ev_next >= c->ev_pool.size())
-    {
-        hipEvent_t a, b;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -1;
-        c->ev_pool.push_back({a, b});
-    }
-    const int idx = (int)c->ev_next++;
-    hipEventRecord(c->ev_pool[idx].first, st);
-    c->ev_used.push_back({which, idx});
-    return idx;
-}
-static void prof_end(jaero_ctx *c, int idx, hipStream_t st)
-{
-    if (idx >= 0) hipEventRecord(c->ev_pool[idx].second, st);
-}
-static void prof_collect(jaero_ctx *c)
-{
-    for (auto &u : c->ev_used)
-    {
-        float ms = 0;
-        hipEventSynchronize(c->ev_pool[u.idx].second);
-        if (hipEventElapsedTime(&ms, c->ev_pool[u.idx].first, c->ev_pool[u.idx].second) == hipSuccess)
-        {
-            c->slots[u.which].ms += ms;
-            c->slots[u.which].launches++;
-        }
-    }
-    c->ev_used.clear();
-    c->ev_next = 0;
-}
+// ------------------------------------------------------------------------------------------ profiling
 extern "C" int jaero_profile_enable(jaero_ctx *c, int on)
 {
     if (!c) return fail(JAERO_EINVAL, "null ctx");
-    c->prof = on != 0;
+    c->timer.on = on != 0;
     return 0;
 }
 extern "C" int jaero_profile_read(jaero_ctx *c, int which, double *total_ms, int *launches, int reset)
 {
     if (!c || which < 0 || which > 4) return fail(JAERO_EINVAL, "jaero_profile_read: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    prof_collect(c);
-    if (total_ms) *total_ms = c->slots[which].ms;
-    if (launches) *launches = c->slots[which].launches;
-    if (reset) c->slots[which] = ProfSlot();
-    return 0;
+    return c->timer.read(c->device, which, total_ms, launches, reset);
 }
 
 extern "C" int jaero_profile_kernel(jaero_ctx *c, int which, char *buf, int cap)
@@ -1263,10 +1189,10 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
     if (layout == JAERO_PCM_FRAME_MAJOR) { frames = dsrc; stride = nch; }
     else
     {
-        const int pi = prof_begin(c, 2, st);
+        const int pi = c->timer.begin(2, st);
         hipLaunchKernelGGL(k_transpose_pcm, dim3(nchp / 64, (nsamples + 63) / 64), dim3(256), 0, st, dsrc, c->d_pcm_frames, nch, nchp, nsamples);
         LAUNCHCHK("k_transpose_pcm");
-        prof_end(c, pi, st);
+        c->timer.end(pi, st);
         frames = c->d_pcm_frames; stride = nchp;
     }
 
@@ -1294,10 +1220,10 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
         const int next = c->m.next_segment(pos, nsamples, n, skip_a, only_a);
         if (n > 0)
         {
-            const int pi = prof_begin(c, 0, st);
+            const int pi = c->timer.begin(0, st);
             launch_samples(c, frames + (size_t)pos * stride, stride, n, skip_a, only_a, nb0, pos, st);
             LAUNCHCHK("the sample loop");
-            prof_end(c, pi, st);
+            c->timer.end(pi, st);
         }
         if (only_a)
         {
@@ -1308,10 +1234,10 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
                 HIPCHK(hipMemcpyAsync(c->d_chanlist, c->m.fired.data(), sizeof(int) * nlist, hipMemcpyHostToDevice, st));
                 dl = c->d_chanlist;
             }
-            const int pi = prof_begin(c, 1, st);
+            const int pi = c->timer.begin(1, st);
             launch_coarse(c, dl, nlist, st);
             LAUNCHCHK("the coarse-frequency estimate");
-            prof_end(c, pi, st);
+            c->timer.end(pi, st);
         }
         pos = next;
     }
@@ -1406,9 +1332,8 @@ extern "C" int jaero_debug_schedule_lanes(int fft_power, int Fs, int nch, const 
 extern "C" int jaero_debug_prefilter(int device, const double *in_reim, int n, double alpha, double fsym, double *out_reim)
 {
     if (!in_reim || !out_reim || n <= 0) return fail(JAERO_EINVAL, "jaero_debug_prefilter: bad arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available");
-    HIPCHK(hipSetDevice(device));
+    int rc = open_device(device);
+    if (rc) return rc;
     const std::vector<double> taps = rrc_design(alpha, 2048, 48000.0, fsym);
     if ((int)taps.size() != PRE_K) return fail(JAERO_EINVAL, "prefilter design returned %zu taps", taps.size());
     JGeom g{}; g.nch = 1; g.nchp = 64; g.ngroups = 1;
@@ -1418,34 +1343,26 @@ extern "C" int jaero_debug_prefilter(int device, const double *in_reim, int n, d
     while (ring < n + 3 * PRE_L + 64) ring <<= 1;
     q.ring = ring;
     q.cap = n;
-    double2 *d_cis = nullptr; double *d_taps = nullptr;
-    HIPCHK(hipMalloc((void **)&q.xring, sizeof(double2) * (size_t)ring * 64));
-    HIPCHK(hipMalloc((void **)&q.cidx, sizeof(unsigned short) * (size_t)n * 64));
-    HIPCHK(hipMalloc((void **)&q.out, sizeof(double2) * (size_t)n * 64));
-    HIPCHK(hipMalloc((void **)&d_cis, sizeof(double2) * 4));
-    HIPCHK(hipMalloc((void **)&d_taps, sizeof(double) * PRE_K));
-    HIPCHK(hipMemset(q.xring, 0, sizeof(double2) * (size_t)ring * 64));
-    HIPCHK(hipMemset(q.cidx, 0, sizeof(unsigned short) * (size_t)n * 64));
-    HIPCHK(hipMalloc((void **)&q.hold, sizeof(long long) * 64));
-    HIPCHK(hipMemset(q.hold, 0, sizeof(long long) * 64));
+    DevMem m;
+    double2 *d_cis = nullptr, *dH = nullptr, *dtw = nullptr;
+    double *d_taps = nullptr;
+    DA(m, q.xring, (size_t)ring * 64);
+    DA(m, q.cidx, (size_t)n * 64);
+    DA(m, q.out, (size_t)n * 64);
+    DA(m, q.hold, 64);
+    DA(m, d_cis, 4);
+    DA(m, d_taps, PRE_K);
     const double2 one[4] = {{1.0, 0.0}, {1.0, 0.0}, {1.0, 0.0}, {1.0, 0.0}}; // table entry 0 = cis(0): the up-mix multiplies by its conjugate
     HIPCHK(hipMemcpy(d_cis, one, sizeof one, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_taps, taps.data(), sizeof(double) * PRE_K, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy2D(q.xring, sizeof(double2) * 4, in_reim, sizeof(double2), sizeof(double2), (size_t)n, hipMemcpyHostToDevice)); // channel 0 of every slot (PRE_XI)
     p.cis = d_cis; q.taps = d_taps;
-    {
-        jaero_ctx t; // owns the two tables
-        double2 *dH = nullptr, *dtw = nullptr;
-        int rc = fft4096_tables(&t, taps, &dH, &dtw, (const void *)k_pre8400_fft);
-        if (rc) return rc;
-        q.H = dH; q.tw = dtw;
-        launch_pre8400_filter(g, p, q, n, 0LL, 0);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        for (void *a : t.allocs) hipFree(a);
-    }
+    if ((rc = fft4096_tables(m, taps, &dH, &dtw, (const void *)k_pre8400_fft))) return rc;
+    q.H = dH; q.tw = dtw;
+    launch_pre8400_filter(g, p, q, n, 0LL, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy2D(out_reim, sizeof(double2), q.out, sizeof(double2) * 4, sizeof(double2), (size_t)n, hipMemcpyDeviceToHost));
-    hipFree(q.xring); hipFree(q.cidx); hipFree(q.out); hipFree(q.hold); hipFree(d_cis); hipFree(d_taps);
     return 0;
 }
 
@@ -1459,44 +1376,11 @@ extern "C" int jaero_debug_read_prefiltered(jaero_ctx *c, int ch, double *out_re
 }
 
 // ------------------------------------------------------------------------------------------ outputs
-static int check_overflow(jaero_ctx *c, int ch, int bit)
-{
-    int ov = 0;
-    HIPCHK(hipMemcpy(&ov, c->o_overflow + ch, sizeof(int), hipMemcpyDeviceToHost));
-    if (ov & bit)
-    {
-        int z = ov & ~bit;
-        HIPCHK(hipMemcpy(c->o_overflow + ch, &z, sizeof(int), hipMemcpyHostToDevice));
-        return fail(JAERO_EOVERFLOW, "channel %d overflowed its output buffer (flag %d); data was dropped", ch, bit);
-    }
-    return 0;
-}
-
 extern "C" int jaero_read_softbits(jaero_ctx *c, int ch, int16_t *dst, int cap, int *n)
 {
     POISONCHK(c, "jaero_read_softbits");
-    if (!c || !dst || !n || ch < 0 || ch >= c->o_nch || cap < 0) return fail(JAERO_EINVAL, "jaero_read_softbits: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
-    int cnt = 0;
-    int *dcnt = c->o_soft_cnt + ch;
-    HIPCHK(hipMemcpy(&cnt, dcnt, sizeof(int), hipMemcpyDeviceToHost));
-    int pend = 0;
-    if (c->o_nrx) HIPCHK(hipMemcpy(&pend, c->o_nrx + ch, sizeof(int), hipMemcpyDeviceToHost));
-    const int emitted = cnt - pend;
-    const int take = emitted < cap ? emitted : cap;
-    int16_t *src = c->o_soft + (size_t)ch * c->o_soft_cap;
-    if (take) HIPCHK(hipMemcpy(dst, src, sizeof(int16_t) * take, hipMemcpyDeviceToHost));
-    if (take < cnt)
-    {
-        std::vector<int16_t> tmp(cnt - take);
-        HIPCHK(hipMemcpy(tmp.data(), src + take, sizeof(int16_t) * (cnt - take), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(src, tmp.data(), sizeof(int16_t) * (cnt - take), hipMemcpyHostToDevice));
-    }
-    const int rest = cnt - take;
-    HIPCHK(hipMemcpy(dcnt, &rest, sizeof(int), hipMemcpyHostToDevice));
-    *n = take;
-    return check_overflow(c, ch, 1);
+    if (!c) return fail(JAERO_EINVAL, "jaero_read_softbits: null ctx");
+    return read_output(c, "jaero_read_softbits", {c->o_soft, c->o_soft_cnt, c->o_soft_cap, sizeof(int16_t)}, ch, dst, cap, n, 1, c->o_nrx);
 }
 
 extern "C" int jaero_read_softbits_all(jaero_ctx *c, int16_t *dst, int capc, int *counts)
@@ -1509,10 +1393,9 @@ extern "C" int jaero_read_softbits_all(jaero_ctx *c, int16_t *dst, int capc, int
     const size_t need = (size_t)nch * capc;
     if (need > c->pack_elems)
     {
-        int16_t *q = nullptr;
-        if (hipMalloc((void **)&q, need * sizeof(int16_t)) != hipSuccess) return fail(JAERO_ENOMEM, "pack buffer");
-        c->allocs.push_back(q);
-        c->d_pack = q; c->pack_elems = need;
+        const int rc = dalloc(c->mem, &c->d_pack, need, false);
+        if (rc) return rc;
+        c->pack_elems = need;
     }
     hipLaunchKernelGGL(k_pack_soft, dim3(nch), dim3(256), 0, st, c->o_soft_cnt, c->o_soft, c->o_soft_cap, c->d_pack, capc);
     HIPCHK(hipMemcpyAsync(dst, c->d_pack, need * sizeof(int16_t), hipMemcpyDeviceToHost, st));
@@ -1569,10 +1452,8 @@ extern "C" int jaero_softbits_view(jaero_ctx *c, void **dev_softbits, void **dev
         HIPCHK(hipSetDevice(c->device));
         if (!c->d_emitted)
         {
-            void *q = nullptr;
-            if (hipMalloc(&q, sizeof(int) * c->o_nchp) != hipSuccess) return fail(JAERO_ENOMEM, "emitted counts");
-            c->allocs.push_back(q);
-            c->d_emitted = (int *)q;
+            const int rc = dalloc(c->mem, &c->d_emitted, c->o_nchp, false);
+            if (rc) return rc;
         }
         hipLaunchKernelGGL(k_burst_emitted, dim3((c->o_nch + 255) / 256), dim3(256), 0, c->last_stream, c->o_soft_cnt, c->o_nrx, c->d_emitted, c->o_nch);
         *dev_counts = c->d_emitted;
@@ -1614,45 +1495,25 @@ extern "C" int jaero_read_status(jaero_ctx *c, int ch, jaero_status *stt)
     return 0;
 }
 
-static int read_rows(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows, int *cnt_base, double *base, int cap, int w, int ovbit)
-{
-    if (!c || !rows || !nrows || ch < 0 || ch >= c->o_nch) return fail(JAERO_EINVAL, "bad arguments");
-    if (!base || !cnt_base) return fail(JAERO_EINVAL, "this output was not enabled in jaero_create flags (or does not exist for this kind)");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
-    int cnt = 0;
-    int *dcnt = cnt_base + ch;
-    HIPCHK(hipMemcpy(&cnt, dcnt, sizeof(int), hipMemcpyDeviceToHost));
-    const int take = cnt < caprows ? cnt : caprows;
-    double *src = base + (size_t)ch * cap * w;
-    if (take) HIPCHK(hipMemcpy(rows, src, sizeof(double) * w * take, hipMemcpyDeviceToHost));
-    if (take < cnt)
-    {
-        std::vector<double> tmp((size_t)w * (cnt - take));
-        HIPCHK(hipMemcpy(tmp.data(), src + (size_t)take * w, sizeof(double) * tmp.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(src, tmp.data(), sizeof(double) * tmp.size(), hipMemcpyHostToDevice));
-    }
-    const int rest = cnt - take;
-    HIPCHK(hipMemcpy(dcnt, &rest, sizeof(int), hipMemcpyHostToDevice));
-    *nrows = take;
-    return check_overflow(c, ch, ovbit);
-}
 extern "C" int jaero_read_status_log(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows)
 {
     POISONCHK(c, "jaero_read_status_log");
-    if (c && c->burst) return fail(JAERO_ENOTSUP, "burst banks have an event log (jaero_read_events), not a status log");
-    return read_rows(c, ch, rows, caprows, nrows, c ? c->p.I + (size_t)I_LOG_CNT * c->g.nchp : nullptr, c ? c->p.slog : nullptr, c ? c->g.log_cap : 0, 6, 4);
+    if (!c) return fail(JAERO_EINVAL, "jaero_read_status_log: null ctx");
+    if (c->burst) return fail(JAERO_ENOTSUP, "burst banks have an event log (jaero_read_events), not a status log");
+    return read_output(c, "jaero_read_status_log", {c->p.slog, c->p.I + (size_t)I_LOG_CNT * c->g.nchp, c->g.log_cap, 6 * sizeof(double)}, ch, rows, caprows, nrows, 4);
 }
 extern "C" int jaero_read_symbols(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows)
 {
     POISONCHK(c, "jaero_read_symbols");
-    return read_rows(c, ch, rows, caprows, nrows, c ? c->o_sym_cnt : nullptr, c ? c->o_sym : nullptr, c ? c->o_sym_cap : 0, 3, 2);
+    if (!c) return fail(JAERO_EINVAL, "jaero_read_symbols: null ctx");
+    return read_output(c, "jaero_read_symbols", {c->o_sym, c->o_sym_cnt, c->o_sym_cap, 3 * sizeof(double)}, ch, rows, caprows, nrows, 2);
 }
 extern "C" int jaero_read_events(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows)
 {
     POISONCHK(c, "jaero_read_events");
-    if (c && !c->burst) return fail(JAERO_ENOTSUP, "continuous banks have a status log (jaero_read_status_log), not an event log");
-    return read_rows(c, ch, rows, caprows, nrows, c ? c->bp.I + (size_t)BI_EV_CNT * c->bg.nchp : nullptr, c ? c->bp.evlog : nullptr, c ? c->bg.ev_cap : 0, 3, 4);
+    if (!c) return fail(JAERO_EINVAL, "jaero_read_events: null ctx");
+    if (!c->burst) return fail(JAERO_ENOTSUP, "continuous banks have a status log (jaero_read_status_log), not an event log");
+    return read_output(c, "jaero_read_events", {c->bp.evlog, c->bp.I + (size_t)BI_EV_CNT * c->bg.nchp, c->bg.ev_cap, 3 * sizeof(double)}, ch, rows, caprows, nrows, 4);
 }
 
 // ------------------------------------------------------------------------------------------ Viterbi
@@ -1697,36 +1558,34 @@ static void viterbi_launch(hipStream_t st, const uint8_t *d_soft, int nsoft, con
 static int viterbi_run(int device, const uint8_t *soft, int nblocks, int nsoft, int pad, uint8_t *overlap, uint8_t *bits_out,
                        int out_stride, int out_start, int out_want, int is_device_ptr, hipStream_t st)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JAERO_ENODEV, "no HIP device available");
-    HIPCHK(hipSetDevice(device));
+    int rc = open_device(device);
+    if (rc) return rc;
     const uint8_t *d_soft = soft; uint8_t *d_out = bits_out; uint8_t *d_ov = overlap;
-    void *t_soft = nullptr, *t_out = nullptr, *t_ov = nullptr;
     const size_t out_bytes = (size_t)nblocks * out_stride;
+    DevMem stage; // host input: staged in device buffers of this call
     if (!is_device_ptr)
     {
-        HIPCHK(hipMalloc(&t_soft, (size_t)nblocks * nsoft));
-        HIPCHK(hipMalloc(&t_out, out_bytes));
+        uint8_t *t_soft = nullptr;
+        if ((rc = dalloc(stage, &t_soft, (size_t)nblocks * nsoft, false)) || (rc = dalloc(stage, &d_out, out_bytes, false))) return rc;
         HIPCHK(hipMemcpyAsync(t_soft, soft, (size_t)nblocks * nsoft, hipMemcpyHostToDevice, st));
-        d_soft = (const uint8_t *)t_soft; d_out = (uint8_t *)t_out;
+        d_soft = t_soft;
         if (overlap)
         {
-            HIPCHK(hipMalloc(&t_ov, (size_t)nblocks * 64));
-            HIPCHK(hipMemcpyAsync(t_ov, overlap, (size_t)nblocks * 64, hipMemcpyHostToDevice, st));
-            d_ov = (uint8_t *)t_ov;
+            if ((rc = dalloc(stage, &d_ov, (size_t)nblocks * 64, false))) return rc;
+            HIPCHK(hipMemcpyAsync(d_ov, overlap, (size_t)nblocks * 64, hipMemcpyHostToDevice, st));
         }
     }
     HIPCHK(hipMemsetAsync(d_out, 0, out_bytes, st));
     void *t_hist = nullptr;
     if (viterbi_use_lanes(nblocks, nsoft, pad)) HIPCHK(hipMallocAsync(&t_hist, viterbi_hist_bytes(nblocks), st));
     viterbi_launch(st, d_soft, nsoft, (const uint8_t *)d_ov, pad, d_out, out_stride, out_start, out_want, nblocks, nullptr, (unsigned long long *)t_hist);
-    HIPCHK(hipGetLastError());
-    if (t_hist) HIPCHK(hipFreeAsync(t_hist, st));
+    const hipError_t le = hipGetLastError();
+    if (t_hist) HIPCHK(hipFreeAsync(t_hist, st)); // stream-ordered, behind the launch (or in place of it)
+    if (le != hipSuccess) return fail(JAERO_EHIP, "launch of the Viterbi decoder failed: %s", hipGetErrorString(le));
     if (!is_device_ptr)
     {
         HIPCHK(hipMemcpyAsync(bits_out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        hipFree(t_soft); hipFree(t_out); if (t_ov) hipFree(t_ov);
     }
     return 0;
 }

@@ -57,6 +57,25 @@ def test_ingest_and_aerol_argument_checks_need_no_device():
     assert L.jaero_ingest_stats(None, None) == capi.E_INVAL
     assert b"jaero_ingest" in L.jaero_last_error()
     assert L.jaero_write(None, None, 0, 0, 0, None) == capi.E_INVAL
+    n = C.c_int(0)
+    buf = (C.c_double * 64)()
+    for name in ("jaero_read_softbits", "jaero_read_status_log", "jaero_read_symbols", "jaero_read_events", "jaero_aerol_read_sus",
+                 "jaero_aerol_read_packets", "jaero_aerol_read_events", "jaero_aerol_read_voice"):
+        assert getattr(L, name)(None, 0, buf, 4, C.byref(n)) == capi.E_INVAL, name
+
+
+def test_aerol_create_without_a_device():
+    """jaero_aerol_create fails with ENODEV without a HIP device, as jaero_create does."""
+    try:
+        import torch
+        if torch.cuda.is_available():
+            pytest.skip("a GPU is present")
+    except ImportError:
+        pass
+    L = capi.lib()
+    h = C.c_void_p()
+    assert L.jaero_aerol_create(0, 4, 10500, 4096, 0, C.byref(h)) == capi.E_NODEV and not h.value
+    assert L.jaero_aerol_create(0, 4, 8400, 4096, 0, C.byref(h)) == capi.E_NODEV and not h.value
 
 
 def _oracle_triggers(O, kind, cpu_reduce, writes):

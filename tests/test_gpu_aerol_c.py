@@ -80,6 +80,14 @@ def test_bank_vs_oracle(D, oracle_mod, force_viterbi_layout, nch, write, layout)
     bank.close()
 
 
+def _raw_read(bank, fn, width, dtype, cap=1 << 16):
+    import ctypes as C
+    buf = np.empty((cap, width), dtype)
+    n = C.c_int(0)
+    rc = getattr(bank.L, fn)(bank.h, 0, buf.ctypes.data, cap, C.byref(n))
+    return rc, n.value
+
+
 def test_overflow_is_reported(D):
     """A caller that falls behind: with room for 3 signal units (= 1 voice frame) per channel the second frame's rows are dropped, and
     the next read says so once (JAERO_EOVERFLOW), as the P and R/T banks do."""
@@ -95,4 +103,31 @@ def test_overflow_is_reported(D):
     assert len(bank.read_sus(0)) == 0  # reported once; the three rows of the first frame were handed over by the failing call's copy
     with pytest.raises(capi.JaeroError):
         bank.read_voice(0)
+    bank.close()
+
+
+@pytest.mark.parametrize("what", ["softbits", "symbols", "p_sus"])
+def test_overflow_is_reported_by_the_other_readers(D, what):
+    """The same for a continuous bank's soft bits and symbols and a P-channel bank's signal units: the rows that fit are handed over by the
+    failing call, the report comes once, then the flag is clear."""
+    from jaero_amd import capi
+    from jaero_amd import signalgen as G
+
+    if what == "p_sus":
+        bits, _ = AF.p_channel_bits(AF.random_payloads(4, 10500, seed=6002), 10500)
+        soft = AF.to_soft(bits, sigma=10.0, seed=6002)
+        bank = D.AeroLBank(1, 10500, max_softbits_per_write=6000, su_capacity=8)
+        for s in range(0, len(soft), 6000):
+            bank.write(soft[s:s + 6000].reshape(1, -1))
+        fn, width, dtype, cap = "jaero_aerol_read_sus", 16, np.int32, 8
+    else:
+        pcm = G.oqpsk(30000, seed=G.SEED_BASE + 6003)[0].reshape(1, -1)
+        bank = D.DemodulatorBank(D.OqpskSettings(), 1, capture_symbols=True, max_write_samples=8192, softbit_capacity=512)
+        for s in range(0, pcm.shape[1], 8192):
+            bank.write(pcm[:, s:s + 8192])
+        fn, width, dtype = ("jaero_read_softbits", 1, np.int16) if what == "softbits" else ("jaero_read_symbols", 3, np.float64)
+        cap = 512 if what == "softbits" else 512 // 2 + 8
+    rc, n = _raw_read(bank, fn, width, dtype)
+    assert rc == capi.E_OVERFLOW and n == cap, (rc, n)  # the full buffer handed over, then the report
+    assert _raw_read(bank, fn, width, dtype) == (capi.E_OK, 0)  # reported once
     bank.close()
