@@ -296,6 +296,28 @@ int jaero_debug_sample_loop_layout(int mode);
  * kernels that are not templates give their plain name.  JAERO_EOVERFLOW if it does not fit in cap bytes. */
 int jaero_debug_kernel_variant(jaero_ctx *ctx, int which, char *buf, int cap);
 
+/* Test hooks: a continuous bank's own coarse-estimate kernel (jaero_debug_kernel_variant(ctx, 1): the function, block, dynamic LDS and twiddles
+ * jaero_write launches) run on state the test supplies.  All three synchronise the bank first and mark it as a bank whose write failed part-way
+ * (its schedule mirror no longer describes the device): a later jaero_write or setter returns JAERO_EHIP; only these hooks, the readers of the
+ * status log and jaero_destroy go on working.  JAERO_EINVAL: null ctx, burst bank, channel outside [0, nchannels), values out of range.
+ *   jaero_debug_coarse_poke   one channel's ring (nfft re, im pairs in RING order: entry k is bbcycbuff[k]) and smoothed spectrum y (nfft), each
+ *                             optional (NULL: left alone), and, when st != NULL, the scalars the estimate's slot reads: bb_ptr in [0, nfft),
+ *                             emptying, flags (1 AFC, 2 SQL, 4 cpuReduce, 8 DCD), countdown, countdown2, coarse_cnt, mse, m2_freq, mc_freq (both
+ *                             >= 0; the wave tables' steps are set to match, as jaero_create forms them).  nest and log_cnt are outputs only.
+ *   jaero_debug_coarse_launch one launch over channels[0 .. nlist) (distinct; NULL: all channels in order, nlist = nchannels) with `grid`
+ *                             workgroups: 0 = as jaero_write (min(nlist, one or two per CU)), else 1 <= grid <= that number, so that a few
+ *                             channels run as several persistent estimates of one workgroup.
+ *   jaero_debug_coarse_peek   the same values back for any channel; ring / y / st each optional. */
+typedef struct jaero_coarse_state
+{
+    int bb_ptr, emptying, flags, countdown, countdown2, coarse_cnt;
+    int nest, log_cnt; /* estimates so far; status-log rows stored (JAERO_FLAG_STATUS_LOG) */
+    double mse, m2_freq, mc_freq;
+} jaero_coarse_state;
+int jaero_debug_coarse_poke(jaero_ctx *ctx, int channel, const double *ring_reim, const double *y, const jaero_coarse_state *st);
+int jaero_debug_coarse_launch(jaero_ctx *ctx, const int *channels, int nlist, int grid);
+int jaero_debug_coarse_peek(jaero_ctx *ctx, int channel, double *ring_reim, double *y, jaero_coarse_state *st);
+
 /* ------------------------------------------------------------------------------------------------ multi-GPU edge operations
  * The path shards by channel with no steady-state exchange (the reference runs its two stereo burst channels as two unrelated objects,
  * JAERO/audioburstoqpskdemodulator.cpp:8-10); the north star names two operations at the edges: fan out shared PCM, gather decoded bits.

@@ -26,6 +26,7 @@ EXPORTS = [
     "jaero_read_symbols", "jaero_viterbi_decode_soft", "jaero_viterbi_continuous", "jaero_abi_version",
     "jaero_num_channels", "jaero_strerror", "jaero_last_error", "jaero_profile_enable", "jaero_profile_read", "jaero_profile_kernel", "jaero_debug_viterbi_layout",
     "jaero_debug_sample_loop_layout", "jaero_debug_kernel_variant",
+    "jaero_debug_coarse_poke", "jaero_debug_coarse_launch", "jaero_debug_coarse_peek",
     "jaero_debug_schedule", "jaero_debug_schedule_lanes", "jaero_debug_prefilter", "jaero_debug_read_prefiltered", "jaero_read_events",
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
@@ -58,6 +59,13 @@ class Status(C.Structure):
         ("signal", C.c_int),
         ("n_estimates", C.c_int),
     ]
+
+
+class CoarseState(C.Structure):
+    """struct jaero_coarse_state: what jaero_debug_coarse_poke / _peek exchange besides a channel's ring and y."""
+
+    _fields_ = [(n, C.c_int) for n in ("bb_ptr", "emptying", "flags", "countdown", "countdown2", "coarse_cnt", "nest", "log_cnt")] + [
+        (n, C.c_double) for n in ("mse", "m2_freq", "mc_freq")]
 
 
 class JaeroError(RuntimeError):
@@ -117,6 +125,9 @@ def lib():
     L.jaero_debug_viterbi_layout.argtypes = [ip]
     L.jaero_debug_sample_loop_layout.argtypes = [ip]
     L.jaero_debug_kernel_variant.argtypes = [vp, ip, C.c_char_p, ip]
+    L.jaero_debug_coarse_poke.argtypes = [vp, ip, vp, vp, C.POINTER(CoarseState)]
+    L.jaero_debug_coarse_launch.argtypes = [vp, vp, ip, ip]
+    L.jaero_debug_coarse_peek.argtypes = [vp, ip, vp, vp, C.POINTER(CoarseState)]
     L.jaero_debug_schedule.argtypes = [ip, ip, ip, vp, ip, vp, ip, C.POINTER(ip)]
     L.jaero_debug_schedule_lanes.argtypes = [ip, ip, ip, vp, vp, ip, vp, ip, vp, ip, C.POINTER(ip)]
     L.jaero_debug_prefilter.argtypes = [ip, vp, ip, dp, dp, vp]

@@ -227,3 +227,13 @@ static std::vector<uint8_t> scrambler_bits()
     }
     return scr;
 }
+
+// validate_settings: lockingbw in (0, Fs / 2] and freq_center >= 0.  The estimate's band limit keeps bins below startbin = round(lockingbw /
+// hzperbin) and above nfft - startbin: past Fs / 2 the two meet, and the reference's window loop (coarsefreqestimate.cpp:61-74) then
+// overwrites its own entries -- not the symmetric window the kernels apply.
+static int check_tuning_range(double lockingbw, double freq_center, double Fs)
+{
+    if (!(lockingbw > 0) || !(freq_center >= 0)) return fail(JAERO_EINVAL, "bad lockingbw/freq_center");
+    if (lockingbw > Fs / 2) return fail(JAERO_EINVAL, "lockingbw %g Hz exceeds Fs / 2 = %g Hz", lockingbw, Fs / 2);
+    return 0;
+}

@@ -386,7 +386,7 @@ static int validate_settings(const jaero_settings &s)
     if (!oq && s.fb != 600 && s.fb != 1200) return fail(JAERO_ENOTSUP, "MSK: fb must be 600 or 1200");
     const bool burst = s.kind >= JAERO_KIND_BURST_MSK;
     if (!burst && s.coarsefreqest_fft_power != 13 && s.coarsefreqest_fft_power != 14) return fail(JAERO_ENOTSUP, "coarsefreqest_fft_power must be 13 or 14");
-    if (!(s.lockingbw > 0) || !(s.freq_center >= 0)) return fail(JAERO_EINVAL, "bad lockingbw/freq_center");
+    if (const int rc = check_tuning_range(s.lockingbw, s.freq_center, s.Fs)) return rc; // lockingbw in (0, Fs / 2], freq_center >= 0
     return 0;
 }
 
@@ -765,15 +765,13 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
 {
     if (!out || !settings || nchannels <= 0 || max_write_samples <= 0) return fail(JAERO_EINVAL, "jaero_create: bad arguments");
     *out = nullptr;
-    hipDeviceProp_t prop;
-    int rc = open_device(device, &prop);
-    if (rc) return rc;
-
+    // the settings are judged before the device is opened: what they refuse does not depend on one
     std::vector<jaero_settings> sets(nchannels);
     for (int ch = 0; ch < nchannels; ch++)
         sets[ch] = per_channel_stride ? *(const jaero_settings *)((const char *)settings + (size_t)ch * per_channel_stride) : settings[0];
     const jaero_settings &s0 = sets[0];
-    if ((rc = validate_settings(s0))) return rc;
+    int rc = validate_settings(s0);
+    if (rc) return rc;
     for (int ch = 1; ch < nchannels; ch++)
     {
         const jaero_settings &s = sets[ch];
@@ -781,6 +779,8 @@ extern "C" int jaero_create(int device, int nchannels, const jaero_settings *set
             return fail(JAERO_EINVAL, "channel %d: kind/fb/Fs/fft_power must match channel 0 within one bank", ch);
         if ((rc = validate_settings(s))) return rc;
     }
+    hipDeviceProp_t prop;
+    if ((rc = open_device(device, &prop))) return rc;
 
     jaero_ctx *c = new jaero_ctx();
     c->device = device;
@@ -1136,11 +1136,14 @@ static void launch_samples(jaero_ctx *c, const int16_t *frames, int stride, int 
     }
 }
 
-static void launch_coarse(jaero_ctx *c, const int *d_list, int nlist, hipStream_t st)
+// the bank's estimate kernel over a list (d_list = nullptr: channels 0 .. nlist - 1) on `grid` workgroups, each persistent over its share
+static void launch_coarse_grid(jaero_ctx *c, const int *d_list, int nlist, int grid, hipStream_t st)
 {
     const KernelRec<CoarseFn> &r = c->coarse;
-    hipLaunchKernelGGL(r.fn, dim3(nlist < r.grid ? nlist : r.grid), dim3(r.block), r.lds, st, c->g, c->p, d_list, nlist, c->d_tw);
+    hipLaunchKernelGGL(r.fn, dim3(grid), dim3(r.block), r.lds, st, c->g, c->p, d_list, nlist, c->d_tw);
 }
+static int coarse_grid(const jaero_ctx *c, int nlist) { return nlist < c->coarse.grid ? nlist : c->coarse.grid; }
+static void launch_coarse(jaero_ctx *c, const int *d_list, int nlist, hipStream_t st) { launch_coarse_grid(c, d_list, nlist, coarse_grid(c, nlist), st); }
 
 // Work enqueued on `st` is ordered behind everything the bank enqueued before (on last_stream), and `st` becomes last_stream: the rule for
 // every entry point that takes a caller stream and touches device state (jaero_write, jaero_discard_softbits) -- a discard on stream X
@@ -1243,6 +1246,86 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
     }
     HIPCHK(hipGetLastError());
     c->poisoned = false;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ test hooks: the estimate kernel alone
+// (tests/test_gpu_coarse.py).  A poked bank's schedule mirror (Mirror::bbptr, flags) no longer matches the device: poisoned, as after a
+// write that failed part-way.
+static int coarse_hook_enter(jaero_ctx *c, const char *who, int channel)
+{
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (c->burst) return fail(JAERO_EINVAL, "%s: a burst bank has no coarse-frequency estimate", who);
+    if (channel < 0 || channel >= c->g.nch) return fail(JAERO_EINVAL, "%s: channel %d outside [0, %d)", who, channel, c->g.nch);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    c->poisoned = true;
+    return 0;
+}
+extern "C" int jaero_debug_coarse_poke(jaero_ctx *c, int ch, const double *ring_reim, const double *y, const jaero_coarse_state *st)
+{
+    int rc = coarse_hook_enter(c, "jaero_debug_coarse_poke", ch);
+    if (rc) return rc;
+    const JGeom &g = c->g;
+    const size_t N = (size_t)g.nfft, nchp = (size_t)g.nchp;
+    if (st && (st->bb_ptr < 0 || st->bb_ptr >= g.nfft || !(st->m2_freq >= 0) || !(st->mc_freq >= 0) || st->emptying < 0 || st->countdown < 0 ||
+               st->countdown2 < 0 || st->coarse_cnt < 0 || (st->flags & ~(JF_AFC | JF_SQL | JF_CPUREDUCE | JF_DCD))))
+        return fail(JAERO_EINVAL, "jaero_debug_coarse_poke: state out of range (bb_ptr in [0, nfft), counters and frequencies >= 0, flags 0..15)");
+    if (ring_reim) HIPCHK(hipMemcpy(c->p.bbring + (size_t)ch * N, ring_reim, sizeof(double2) * N, hipMemcpyHostToDevice));
+    if (y) HIPCHK(hipMemcpy(c->p.y + (size_t)ch * N, y, sizeof(double) * N, hipMemcpyHostToDevice));
+    if (st)
+    {
+        const double wt = ((double)JD_WTSIZE) / ((float)(double)g.Fs_int); // WaveTable::SetFreq's step, as init_channel_scalars forms it
+        const std::pair<int, int> iv[] = {{I_BB_PTR, st->bb_ptr}, {I_EMPTYING, st->emptying}, {I_FLAGS, st->flags}, {I_COUNTDOWN, st->countdown},
+                                          {I_COUNTDOWN2, st->countdown2}, {I_COARSE_CNT, st->coarse_cnt}};
+        const std::pair<int, double> dv[] = {{S_MSE, st->mse}, {S_M2_FREQ, st->m2_freq}, {S_M2_STEP, st->m2_freq * wt}, {S_MC_FREQ, st->mc_freq},
+                                             {S_MC_STEP, st->mc_freq * wt}};
+        for (const auto &[f, v] : iv) HIPCHK(hipMemcpy(c->p.I + (size_t)f * nchp + ch, &v, sizeof(int), hipMemcpyHostToDevice));
+        for (const auto &[f, v] : dv) HIPCHK(hipMemcpy(c->p.S + (size_t)f * nchp + ch, &v, sizeof(double), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+extern "C" int jaero_debug_coarse_peek(jaero_ctx *c, int ch, double *ring_reim, double *y, jaero_coarse_state *st)
+{
+    int rc = coarse_hook_enter(c, "jaero_debug_coarse_peek", ch);
+    if (rc) return rc;
+    const JGeom &g = c->g;
+    const size_t N = (size_t)g.nfft, nchp = (size_t)g.nchp;
+    if (ring_reim) HIPCHK(hipMemcpy(ring_reim, c->p.bbring + (size_t)ch * N, sizeof(double2) * N, hipMemcpyDeviceToHost));
+    if (y) HIPCHK(hipMemcpy(y, c->p.y + (size_t)ch * N, sizeof(double) * N, hipMemcpyDeviceToHost));
+    if (st)
+    {
+        const std::pair<int, int *> iv[] = {{I_BB_PTR, &st->bb_ptr}, {I_EMPTYING, &st->emptying}, {I_FLAGS, &st->flags}, {I_COUNTDOWN, &st->countdown},
+                                            {I_COUNTDOWN2, &st->countdown2}, {I_COARSE_CNT, &st->coarse_cnt}, {I_NEST, &st->nest}, {I_LOG_CNT, &st->log_cnt}};
+        const std::pair<int, double *> dv[] = {{S_MSE, &st->mse}, {S_M2_FREQ, &st->m2_freq}, {S_MC_FREQ, &st->mc_freq}};
+        for (const auto &[f, v] : iv) HIPCHK(hipMemcpy(v, c->p.I + (size_t)f * nchp + ch, sizeof(int), hipMemcpyDeviceToHost));
+        for (const auto &[f, v] : dv) HIPCHK(hipMemcpy(v, c->p.S + (size_t)f * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+extern "C" int jaero_debug_coarse_launch(jaero_ctx *c, const int *channels, int nlist, int grid)
+{
+    int rc = coarse_hook_enter(c, "jaero_debug_coarse_launch", 0);
+    if (rc) return rc;
+    const int nch = c->g.nch;
+    if (channels ? (nlist < 1 || nlist > nch) : nlist != nch)
+        return fail(JAERO_EINVAL, "jaero_debug_coarse_launch: nlist %d (a list of 1 .. %d channels, or NULL with all %d)", nlist, nch, nch);
+    if (channels)
+    {
+        std::vector<char> seen((size_t)nch, 0);
+        for (int k = 0; k < nlist; k++)
+        {
+            if (channels[k] < 0 || channels[k] >= nch || seen[(size_t)channels[k]])
+                return fail(JAERO_EINVAL, "jaero_debug_coarse_launch: entry %d (channel %d) is outside [0, %d) or listed twice", k, channels[k], nch);
+            seen[(size_t)channels[k]] = 1;
+        }
+    }
+    const int gmax = coarse_grid(c, nlist);
+    if (grid < 0 || grid > gmax) return fail(JAERO_EINVAL, "jaero_debug_coarse_launch: grid %d (0 = as jaero_write, else 1 .. %d for %d channels)", grid, gmax, nlist);
+    if (channels) HIPCHK(hipMemcpy(c->d_chanlist, channels, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice));
+    launch_coarse_grid(c, channels ? c->d_chanlist : nullptr, nlist, grid ? grid : gmax, c->last_stream);
+    LAUNCHCHK("the coarse-frequency estimate");
+    HIPCHK(hipStreamSynchronize(c->last_stream));
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // k_coarse2.h -- the register-FFT building blocks: CV<L> (L complex points in registers), regfft<L> (radix-4 / radix-2 DFT of them),
-// c2_log10, c4_twiddle16, c4_lds_barrier (wg_fft<LOG2N>, the 512-thread E x 32 x 16 transform k_trident used until round 4, left with it).  The coarse-frequency estimator kernels themselves are in k_coarse6.h (round 3); the first
+// c4_twiddle16, c4_lds_barrier (wg_fft<LOG2N>, the 512-thread E x 32 x 16 transform k_trident used until round 4, left with it).  The coarse-frequency estimator kernels themselves are in k_coarse6.h (round 3); the first
 // register-resident one, k_coarse2<LOG2N>, lived here (rounds 1-2).
 #pragma once
 #include "jaero_device.h"
@@ -113,35 +113,6 @@ __device__ __forceinline__ void twiddle_powers(const double2 base, const double2
     A[0] = make_double2(1.0, 0.0);
     A[1] = s4; A[2] = cmul2(s4, s4); A[3] = cmul2(A[2], s4); A[4] = cmul2(A[2], A[2]);
     A[5] = cmul2(A[4], s4); A[6] = cmul2(A[3], A[3]); A[7] = cmul2(A[4], A[3]);
-}
-
-// log10(x) for x >= 1, ~2 ulp, ~30 instructions (ocml's correctly-rounded log10 costs ~110 and the kernel needs N of them per
-// estimate).  x = m 2^e with m in [sqrt(1/2), sqrt(2)); log(m) = 2 atanh(s), s = (m-1)/(m+1), |s| <= 0.1716: odd series to s^19.
-// The smoothed dB spectrum y[] only feeds an arg-max over bins (the emitted estimate is a bin index), so the last ulps of y never
-// reach an output.
-__device__ __forceinline__ double c2_log10(double x)
-{
-#pragma clang fp contract(fast)
-    int e;
-    double m = frexp(x, &e);
-    if (m < 0.70710678118654752440) { m *= 2.0; e -= 1; }
-    const double d = m + 1.0;
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    const double sx = (m - 1.0) * r;
-    const double z = sx * sx;
-    double q = 1.0 / 19.0;
-    q = fma(q, z, 1.0 / 17.0);
-    q = fma(q, z, 1.0 / 15.0);
-    q = fma(q, z, 1.0 / 13.0);
-    q = fma(q, z, 1.0 / 11.0);
-    q = fma(q, z, 1.0 / 9.0);
-    q = fma(q, z, 1.0 / 7.0);
-    q = fma(q, z, 1.0 / 5.0);
-    q = fma(q, z, 1.0 / 3.0);
-    const double lnm = 2.0 * fma(sx * z, q, sx);
-    return fma((double)e, 0.30102999566398119521, lnm * 0.43429448190325182765);
 }
 
 // (The estimator kernel built on wg_fft, k_coarse2<LOG2N>, served the MSK rates until round 3: 6.76 ms per 65 536 estimates of 2^13 points,

@@ -430,8 +430,10 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             for (int s = 0; s < E; s++)
             {
                 const int ib = (s * NT) ^ (N / 2);
-                // 10*log10(max(|X|,1)) == 5*log10(max(|X|^2,1)): no hypot; differs from the reference expression by <= 1 ulp
-                const double yn = yv[s] * 0.9 + 5.0 * c2_log10(fmax(d.r[s], 1.0));
+                // 0.1*10*log10(max(|X|,1)) -- C multiplies left to right: (0.1 * 10) * log10 = 1.0 * log10 -- == 0.5*log10(max(|X|^2,1)): no
+                // hypot.  (Until tests/test_gpu_coarse.py compared y itself this line had 5.0, ten times the reference's increment: the same
+                // peak bin as long as every candidate folds six terms, another one when y was 20 and the fold left the spectrum.)
+                const double yn = yv[s] * 0.9 + 0.5 * jd_log10(fmax(d.r[s], 1.0));
                 __builtin_nontemporal_store(yn, (y + ib) + t);
                 (xch + ib)[t] = yn;
                 {

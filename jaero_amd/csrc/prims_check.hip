@@ -96,6 +96,11 @@ __global__ void __launch_bounds__(TPB) k_jp_expm1(const double *x, double *o, lo
     JP_IDX;
     if (i < n) o[i] = jd_expm1(x[i]);
 }
+__global__ void __launch_bounds__(TPB) k_jp_log10(const double *x, double *o, long n)
+{
+    JP_IDX;
+    if (i < n) o[i] = jd_log10(x[i]);
+}
 __global__ void __launch_bounds__(TPB) k_jp_qround(const double *x, int *o, long n)
 {
     JP_IDX;
@@ -231,6 +236,7 @@ JP_2IN_1OUT(jp_hypot, double)
 JP_1IN_1OUT(jp_tanh, double)
 JP_1IN_1OUT(jp_tanh_full, double)
 JP_1IN_1OUT(jp_expm1, double)
+JP_1IN_1OUT(jp_log10, double)
 JP_1IN_1OUT(jp_qround, int)
 JP_1IN_1OUT(jp_softbit, int)
 JP_1IN_1OUT(jp_cisidx, int)

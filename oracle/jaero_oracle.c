@@ -501,6 +501,8 @@ void jo_coarse_bigchange(jo_coarse *c) /* :84-88 */
     for (int i = 0; i < (int)c->nfft; i++) c->y[i] = 20;
 }
 void jo_coarse_get_y(jo_coarse *c, double *y) { memcpy(y, c->y, sizeof(double) * (size_t)c->nfft); }
+/* test access: start the next estimate from a given smoothed spectrum (tests/test_gpu_coarse.py) */
+void jo_coarse_set_y(jo_coarse *c, const double *y) { memcpy(c->y, y, sizeof(double) * (size_t)c->nfft); }
 /* ProcessBasebandData :90-137; returns the value passed to emit FreqOffsetEstimate */
 static double coarse_process(jo_coarse *c, const cpx *data)
 {

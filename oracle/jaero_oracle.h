@@ -68,6 +68,7 @@ void jo_coarse_destroy(jo_coarse *c);
 void jo_coarse_bigchange(jo_coarse *c);
 double jo_coarse_process(jo_coarse *c, const double *re_im);
 void jo_coarse_get_y(jo_coarse *c, double *y);
+void jo_coarse_set_y(jo_coarse *c, const double *y);
 
 /* ---- burst demodulators (jaero_oracle_burst.c): BurstOqpskDemodulator / BurstMskDemodulator ---- */
 typedef struct jo_burst jo_burst;

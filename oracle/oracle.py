@@ -98,6 +98,7 @@ def lib():
         L.jo_coarse_process.restype = C.c_double
         L.jo_coarse_process.argtypes = [C.c_void_p, C.c_void_p]
         L.jo_coarse_get_y.argtypes = [C.c_void_p, C.c_void_p]
+        L.jo_coarse_set_y.argtypes = [C.c_void_p, C.c_void_p]
         L.jo_codec_create.restype = C.c_void_p
         L.jo_codec_create.argtypes = [C.c_int]
         L.jo_codec_destroy.argtypes = [C.c_void_p]
@@ -232,6 +233,44 @@ class Demod:
     @property
     def pending(self):
         return self.L.jo_demod_pending_soft(self.h)
+
+
+class Coarse:
+    """One CoarseFreqEstimate object (coarsefreqestimate.cpp) on its own: process() takes nfft complex samples in time order and returns what
+    the object emits as FreqOffsetEstimate (0 while its emptying countdown runs: 1 after construction, 4 after bigchange)."""
+
+    def __init__(self, power: int, lockingbw: float, fb: float, Fs: float):
+        self.L = lib()
+        self.n = 1 << power
+        self.hzperbin = Fs / self.n
+        self.h = self.L.jo_coarse_create(int(power), float(lockingbw), float(fb), float(Fs))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.jo_coarse_destroy(self.h)
+            self.h = None
+
+    def process(self, x: np.ndarray) -> float:
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        assert x.shape == (self.n,)
+        return float(self.L.jo_coarse_process(self.h, x.ctypes.data))
+
+    def peak_bin(self, est: float) -> int:
+        """zmaxloc behind an estimate that was not zeroed by the countdown: est = -(zmaxloc - n/2) * hzperbin / 2"""
+        return self.n // 2 - int(round(2.0 * est / self.hzperbin))
+
+    def bigchange(self):
+        self.L.jo_coarse_bigchange(self.h)
+
+    def get_y(self) -> np.ndarray:
+        y = np.empty(self.n, dtype=np.float64)
+        self.L.jo_coarse_get_y(self.h, y.ctypes.data)
+        return y
+
+    def set_y(self, y: np.ndarray):
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        assert y.shape == (self.n,)
+        self.L.jo_coarse_set_y(self.h, y.ctypes.data)
 
 
 def run_demod(settings: Settings, pcm: np.ndarray, chunk=4096, afc=False, cpu_reduce=False,

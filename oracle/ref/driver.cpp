@@ -343,7 +343,12 @@ int main(int argc, char **argv)
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         writeall(argv[3], sink.data().constData(), sink.data().size());
         printf("%.6f %ld\n", secs, n); // seconds inside processDemodulatedSoftBits (bench.py's cpu_baseline)
-        return 0;
+        // Everything is written.  AeroL's plane database starts a worker thread (JAERO/databasetext.cpp:66) that may still be coming up when a
+        // short input is through: returning from main then runs exit()'s destructors under it (one run in four of a 24-sample input ended in
+        // SIGSEGV or a heap-check abort AFTER its output was complete, which tests/test_aerol_oracle.py's availability probe took for "_ref
+        // cannot run here" and skipped on).  Leave without them.
+        fflush(stdout);
+        _Exit(0);
     }
     if (mode == "time")
     {

@@ -271,7 +271,7 @@ __device__ __forceinline__ void coarse4_body(const JGeom g, const JPtrs p, const
             __builtin_amdgcn_sched_barrier(0); // or the scheduler sinks every load to its use again
             // 10*log10(max(|X|,1)) == 5*log10(max(|X|^2,1)): no hypot; differs from the reference expression by <= 1 ulp
 #pragma unroll
-            for (int s = 0; s < E; s++) d.r[s] = 5.0 * c2_log10(fmax(d.r[s], 1.0));
+            for (int s = 0; s < E; s++) d.r[s] = 5.0 * jd_log10(fmax(d.r[s], 1.0));
 #pragma unroll
             for (int s = 0; s < E; s++)
             {

@@ -22,6 +22,7 @@ LAUNCHERS = {
     "jp_tanh": "jd_tanh",
     "jp_tanh_full": "jd_tanh_full",
     "jp_expm1": "jd_expm1",
+    "jp_log10": "jd_log10",
     "jp_qround": "jd_qround",
     "jp_softbit": "jd_softbit",
     "jp_cisidx": "jd_cisidx",
@@ -113,7 +114,7 @@ def prims():
         "jp_wt_passed": [P, P, P, P, P, P, n],
         "jp_bd_set_phase_deg": [P, P, n],
     }
-    for name in ("jp_tanh", "jp_tanh_full", "jp_expm1", "jp_qround", "jp_softbit", "jp_cisidx", "jp_fb_fmod360"):
+    for name in ("jp_tanh", "jp_tanh_full", "jp_expm1", "jp_log10", "jp_qround", "jp_softbit", "jp_cisidx", "jp_fb_fmod360"):
         sig[name] = [P, P, n]
     for r in FIR_ROWS:
         sig[r.export] = [P] * 7

@@ -64,6 +64,45 @@ def test_ingest_and_aerol_argument_checks_need_no_device():
         assert getattr(L, name)(None, 0, buf, 4, C.byref(n)) == capi.E_INVAL, name
 
 
+def test_coarse_hooks_refuse_a_null_context():
+    """jaero_debug_coarse_poke / _launch / _peek: JAERO_EINVAL before any HIP call (burst bank, bad channel, bad grid: tests/test_gpu_coarse.py)."""
+    L = capi.lib()
+    st = capi.CoarseState()
+    buf = (C.c_double * 8)()
+    assert C.sizeof(capi.CoarseState) == 56  # 8 ints + 3 doubles
+    assert L.jaero_debug_coarse_poke(None, 0, buf, buf, C.byref(st)) == capi.E_INVAL
+    assert b"jaero_debug_coarse_poke" in L.jaero_last_error()
+    assert L.jaero_debug_coarse_launch(None, None, 1, 0) == capi.E_INVAL
+    assert b"jaero_debug_coarse_launch" in L.jaero_last_error()
+    assert L.jaero_debug_coarse_peek(None, 0, buf, buf, C.byref(st)) == capi.E_INVAL
+    assert b"jaero_debug_coarse_peek" in L.jaero_last_error()
+
+
+@pytest.mark.parametrize("kind,power,fb,Fs,lbw,ok", [
+    (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.0, True), (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.5, False),
+    (capi.KIND_OQPSK, 14, 8400.0, 48000.0, 30000.0, False), (capi.KIND_MSK, 13, 1200.0, 48000.0, 24001.0, False),
+    (capi.KIND_MSK, 13, 1200.0, 12000.0, 6000.0, True), (capi.KIND_MSK, 13, 1200.0, 12000.0, 6000.1, False),
+    (capi.KIND_MSK, 13, 600.0, 24000.0, 12000.0, True), (capi.KIND_MSK, 13, 600.0, 24000.0, 18000.0, False),
+    (capi.KIND_BURST_OQPSK, 13, 10500.0, 48000.0, 25000.0, False), (capi.KIND_BURST_MSK, 13, 1200.0, 48000.0, 48000.0, False),
+])
+def test_locking_bandwidth_above_half_the_sample_rate_is_refused(kind, power, fb, Fs, lbw, ok):
+    """lockingbw > Fs / 2: the band limit's two edges meet and the reference's window loop overwrites its own entries,
+    so jaero_create refuses it with JAERO_EINVAL -- for any channel of the bank, and before it looks for a device.  Up to Fs / 2 the settings
+    pass (what comes back then is the device's answer)."""
+    L = capi.lib()
+    good = capi.Settings(kind, power, 1000.0, min(lbw, 1000.0), fb, Fs, 0.5)
+    for sets in ([capi.Settings(kind, power, 1000.0, lbw, fb, Fs, 0.5)], [good, good, capi.Settings(kind, power, 1000.0, lbw, fb, Fs, 0.5)]):
+        arr = (capi.Settings * len(sets))(*sets)
+        h = C.c_void_p()
+        rc = L.jaero_create(0, len(sets), C.addressof(arr), C.sizeof(capi.Settings), 0, 4096, 0, C.byref(h))
+        if h.value:
+            L.jaero_destroy(h)
+        if ok:
+            assert rc in (0, capi.E_NODEV)
+        else:
+            assert rc == capi.E_INVAL and not h.value and b"lockingbw" in L.jaero_last_error() and b"Fs / 2" in L.jaero_last_error()
+
+
 def test_aerol_create_without_a_device():
     """jaero_aerol_create fails with ENODEV without a HIP device, as jaero_create does."""
     try:
