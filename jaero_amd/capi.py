@@ -32,6 +32,8 @@ EXPORTS = [
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
     "jaero_ingest_create", "jaero_ingest_destroy", "jaero_ingest_push", "jaero_ingest_queued", "jaero_ingest_pump",
     "jaero_ingest_stats",
+    "jaero_chan_create", "jaero_chan_destroy", "jaero_chan_write", "jaero_chan_pcm_view", "jaero_chan_read_pcm", "jaero_chan_retune",
+    "jaero_chan_feed", "jaero_chan_profile_enable", "jaero_chan_profile_read",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -66,6 +68,12 @@ class CoarseState(C.Structure):
 
     _fields_ = [(n, C.c_int) for n in ("bb_ptr", "emptying", "flags", "countdown", "countdown2", "coarse_cnt", "nest", "log_cnt")] + [
         (n, C.c_double) for n in ("mse", "m2_freq", "mc_freq")]
+
+
+class ChanChannel(C.Structure):
+    """struct jaero_chan_channel: tuning word (centre = tune * Fs_in / 2^32, signed), audio word (offset = audio * 48000 / 2^32), gain."""
+
+    _fields_ = [("tune", C.c_uint32), ("audio", C.c_uint32), ("gain", C.c_double)]
 
 
 class JaeroError(RuntimeError):
@@ -151,6 +159,16 @@ def lib():
     L.jaero_ingest_queued.argtypes = [vp, ip]
     L.jaero_ingest_pump.argtypes = [vp, ip, vp, C.POINTER(ip)]
     L.jaero_ingest_stats.argtypes = [vp, vp]
+    L.jaero_chan_create.argtypes = [ip, ip, ip, vp, vp, ip, ip, C.POINTER(vp)]
+    L.jaero_chan_destroy.argtypes = [vp]
+    L.jaero_chan_destroy.restype = None
+    L.jaero_chan_write.argtypes = [vp, vp, ip, ip, vp, C.POINTER(ip)]
+    L.jaero_chan_pcm_view.argtypes = [vp, C.POINTER(vp), C.POINTER(ip)]
+    L.jaero_chan_read_pcm.argtypes = [vp, vp, ip, C.POINTER(ip)]
+    L.jaero_chan_retune.argtypes = [vp, ip, C.POINTER(ChanChannel)]
+    L.jaero_chan_feed.argtypes = [vp, vp, vp, ip, ip, vp, C.POINTER(ip)]
+    L.jaero_chan_profile_enable.argtypes = [vp, ip]
+    L.jaero_chan_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_shard_range.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.jaero_comm_get_unique_id.argtypes = [vp]
     L.jaero_comm_create.argtypes = [ip, ip, ip, vp, C.POINTER(vp)]

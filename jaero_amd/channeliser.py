@@ -1,0 +1,143 @@
+"""Wideband I/Q channeliser in front of the demodulator banks (jaero_chan_*, include/jaero_hip.h).
+
+`Channeliser` cuts one int16 I/Q capture at 48 kHz x decim into the 48 kHz int16 audio of every channel of a bank, on the
+GPU: `feed(bank, iq)` hands its output straight to `DemodulatorBank` (device to device), `write` / `read_pcm` give it to the
+caller.  Frequencies are 32-bit words: `tune_word(hz, fs)` is the word nearest a frequency, `word_hz(word, fs)` the
+frequency a word really is, `channel_words(tune, audio, decim)` the integers the kernels derive from a channel's words.
+All arithmetic happens in libjaero_hip.so; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import capi
+
+N = 16384          # transform length
+HP = N // 2        # hop, input samples
+DECIMS = (16, 32, 64)
+FS_OUT = 48000.0
+
+
+def tune_word(hz: float, fs: float) -> int:
+    """The uint32 word nearest `hz` at sample rate `fs` (negative frequencies wrap: the word is read as a signed number)."""
+    return int(round(hz / fs * 4294967296.0)) % (1 << 32)
+
+
+def word_hz(word: int, fs: float) -> float:
+    """The frequency a word stands for: the word as a signed 32-bit number times fs / 2^32."""
+    w = int(word) % (1 << 32)
+    if w >= 1 << 31:
+        w -= 1 << 32
+    return w * fs / 4294967296.0
+
+
+def channel_words(tune: int, audio: int, decim: int) -> Tuple[int, int, int]:
+    """(b, rho, w) of a channel: nearest bin of the tuning word, what is left of it, phase word per output sample."""
+    t = int(tune) % (1 << 32)
+    if t >= 1 << 31:
+        t -= 1 << 32
+    b = (t + (1 << 17)) >> 18
+    rho = t - (b << 18)
+    return b, rho, (int(audio) - rho * decim) % (1 << 32)
+
+
+def design_taps(decim: int, cutoff_hz: float = 9000.0, ntaps: int = 8193, beta: float = 16.0) -> np.ndarray:
+    """Kaiser-windowed sinc low-pass at the capture rate 48 kHz x decim: 2 fc sinc(2 fc k) kaiser(beta), unit sum."""
+    fc = cutoff_hz / (FS_OUT * decim)
+    k = np.arange(ntaps) - (ntaps - 1) / 2
+    h = 2 * fc * np.sinc(2 * fc * k) * np.kaiser(ntaps, beta)
+    return h / h.sum()
+
+
+def _channel_array(channels: Sequence) -> "C.Array":
+    rows = [c if isinstance(c, capi.ChanChannel) else capi.ChanChannel(int(c[0]) % (1 << 32), int(c[1]) % (1 << 32), float(c[2]))
+            for c in channels]
+    return (capi.ChanChannel * len(rows))(*rows)
+
+
+class Channeliser:
+    """A bank of `len(channels)` channel filters over one capture (thin wrapper over jaero_chan).
+
+    channels: (tune word, audio word, gain) per channel.  taps: the prototype low-pass at the capture rate
+    (None: design_taps(decim)).  max_write_iq: most I/Q pairs one write may bring."""
+
+    def __init__(self, decim: int, channels: Sequence, taps: Optional[np.ndarray] = None, device: int = 0,
+                 max_write_iq: int = 16 * HP):
+        self.L = capi.lib()
+        t = design_taps(decim) if taps is None else np.ascontiguousarray(taps, dtype=np.float64)
+        arr = _channel_array(channels)
+        h = C.c_void_p()
+        capi.check(self.L.jaero_chan_create(device, int(decim), len(arr), C.cast(arr, C.c_void_p), t.ctypes.data, int(t.size),
+                                            int(max_write_iq), C.byref(h)))
+        self.h = h
+        self.decim, self.nch, self.device, self.max_write_iq = int(decim), len(arr), device, int(max_write_iq)
+        self.M = N // self.decim
+        self.Mo = self.M // 2
+        self.last_nout = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.jaero_chan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _input(iq):
+        """(pointer, I/Q pairs, is_device_ptr, keep-alive) of a numpy int16 array [n, 2] / [2 n] or a torch int16 tensor on the device."""
+        if isinstance(iq, np.ndarray):
+            a = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+            assert a.size % 2 == 0
+            return a.ctypes.data, a.size // 2, 0, a
+        t = iq
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == 2 and t.numel() % 2 == 0
+        return t.data_ptr(), t.numel() // 2, 1, t
+
+    def write(self, iq, stream: int = 0) -> int:
+        """Consumes the I/Q pairs; returns the samples per channel this write produced (a multiple of Mo, possibly 0)."""
+        ptr, n, dev, _keep = self._input(iq)
+        nout = C.c_int(0)
+        capi.check(self.L.jaero_chan_write(self.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
+        self.last_nout = nout.value
+        return nout.value
+
+    def feed(self, bank, iq, stream: int = 0) -> int:
+        """write, then the bank's write of what came out (device to device, no synchronisation).  Returns samples per channel."""
+        ptr, n, dev, _keep = self._input(iq)
+        nout = C.c_int(0)
+        capi.check(self.L.jaero_chan_feed(self.h, bank.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
+        self.last_nout = nout.value
+        return nout.value
+
+    def read_pcm(self) -> np.ndarray:
+        """The last write's output, int16 [nch, nout], on the host (synchronises)."""
+        out = np.empty((self.nch, max(self.last_nout, 1)), dtype=np.int16)
+        n = C.c_int(0)
+        capi.check(self.L.jaero_chan_read_pcm(self.h, out.ctypes.data, out.shape[1], C.byref(n)))
+        return out[:, : n.value].copy()
+
+    def pcm_view(self) -> Tuple[int, int]:
+        """(device pointer, samples per channel) of the last write's output, int16 [nch][nsamples]."""
+        p, n = C.c_void_p(), C.c_int(0)
+        capi.check(self.L.jaero_chan_pcm_view(self.h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def retune(self, channel: int, tune: int, audio: int, gain: float):
+        ch = capi.ChanChannel(int(tune) % (1 << 32), int(audio) % (1 << 32), float(gain))
+        capi.check(self.L.jaero_chan_retune(self.h, channel, C.byref(ch)))
+
+    def profile_enable(self, on: bool = True):
+        capi.check(self.L.jaero_chan_profile_enable(self.h, int(on)))
+
+    def profile_read(self, which: int, reset: bool = False):
+        """(total ms, launches) of kernel `which`: 0 = forward transform, 1 = per-channel synthesis."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.L.jaero_chan_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value

@@ -1,0 +1,243 @@
+// chan_host.h -- host side of the wideband I/Q channeliser (k_chan.h; SURVEY 8 row f3, the channeliser half).
+//
+// One jaero_chan turns interleaved int16 I/Q at 48 kHz x D into one compact channel-major int16 array per write: exactly what jaero_write
+// takes with JAERO_PCM_CHANNEL_MAJOR, is_device_ptr = 1.  State between writes: the input history (previous hop + the partial hop a ragged
+// write leaves; two buffers, the tail of one is copied to the head of the other behind every write that completed a block), the number of
+// blocks done, and the channels' parameters.  Everything about frequency is integer arithmetic on the host (chan_param).
+#pragma once
+#include "k_chan.h" // (here and not among the kernel headers at the top of jaero_hip.hip: tests cite that file's lines by number)
+
+struct jaero_chan
+{
+    int device = 0;
+    int decim = 0, nch = 0, max_write_iq = 0;
+    int M = 0, Mo = 0, nblk_max = 0;
+    DevMem mem;
+    int *d_in[2] = {nullptr, nullptr}; // [2 Hp + max_write_iq] dwords (I, Q) each; d_in[cur] holds: previous hop, then `pending` samples
+    int cur = 0, pending = 0;
+    long long blocks_done = 0;
+    double2 *d_spec = nullptr; // [nblk_max][N]
+    double2 *d_gm = nullptr;   // [M]
+    double2 *d_twm = nullptr;  // [32]
+    double2 *d_tw = nullptr;   // [N]: W_N^k (wg_fft14_e32)
+    ChanParam *d_par = nullptr;
+    int16_t *d_pcm = nullptr;  // [nch][nout of the last write], capacity nch * nblk_max * Mo
+    int last_nout = 0;
+    std::vector<jaero_chan_channel> channels;
+    KernelTimer timer{2};
+    hipStream_t last_stream = nullptr;
+    hipEvent_t order_ev = nullptr;
+    bool poisoned = false;
+};
+
+#define CHANPOISONCHK(c, who) do { if ((c)->poisoned) return fail(JAERO_EHIP, who ": an earlier write of this channeliser failed part-way; destroy it and create a new one"); } while (0)
+
+static bool chan_channel_ok(const jaero_chan_channel &ch) { return __builtin_isfinite(ch.gain) && ch.gain > 0; }
+
+// b = nearest bin of the tuning word read as a signed number, rho = what is left, w = audio - rho D (mod 2^32)
+static ChanParam chan_param(const jaero_chan_channel &ch, int decim)
+{
+    const long long t = (long long)(int32_t)ch.tune;
+    const long long b = (t + (1ll << 17)) >> 18; // arithmetic shift
+    const long long rho = t - b * (1ll << 18);
+    ChanParam p;
+    p.b = (int)b;
+    p.w = (unsigned)((unsigned long long)((long long)ch.audio - rho * decim)); // mod 2^32
+    p.gain = ch.gain;
+    return p;
+}
+
+// G[q mod N] / N for the M bins a channel keeps, in the inverse transform's input order (k < M / 2: q = k, else q = k - M); G = DFT_N of the
+// zero-padded taps, summed directly (M x L products) from one table of exp(-2 pi i k / N)
+static std::vector<double2> chan_response(const double *taps, int ntaps, int M)
+{
+    const std::vector<double2> tw = twiddles(CHAN_N, CHAN_N);
+    std::vector<double2> g(M);
+    for (int k = 0; k < M; k++)
+    {
+        const int q = (k < M / 2 ? k : k - M) & (CHAN_N - 1);
+        double re = 0, im = 0;
+        for (int n = 0; n < ntaps; n++)
+        {
+            const double2 w = tw[(unsigned)(q * n) & (CHAN_N - 1)];
+            re += taps[n] * w.x; im += taps[n] * w.y;
+        }
+        g[k] = make_double2(re / CHAN_N, im / CHAN_N);
+    }
+    return g;
+}
+
+extern "C" void jaero_chan_destroy(jaero_chan *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->last_stream);
+    if (c->order_ev) (void)hipEventDestroy(c->order_ev);
+    delete c;
+}
+
+extern "C" int jaero_chan_create(int device, int decim, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps,
+                                 int max_write_iq, jaero_chan **out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_chan_create: out is null");
+    *out = nullptr;
+    if (!ch || !taps) return fail(JAERO_EINVAL, "jaero_chan_create: null channels / taps");
+    if (decim != 16 && decim != 32 && decim != 64) return fail(JAERO_EINVAL, "jaero_chan_create: decim %d is not 16, 32 or 64", decim);
+    if (nchannels < 1) return fail(JAERO_EINVAL, "jaero_chan_create: nchannels %d < 1", nchannels);
+    if (ntaps < 1 || ntaps > CHAN_N / 2 + 1) return fail(JAERO_EINVAL, "jaero_chan_create: ntaps %d outside [1, %d]", ntaps, CHAN_N / 2 + 1);
+    if (max_write_iq < 1) return fail(JAERO_EINVAL, "jaero_chan_create: max_write_iq %d < 1", max_write_iq);
+    for (int i = 0; i < nchannels; i++)
+        if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "jaero_chan_create: channel %d: gain %g is not finite and positive", i, ch[i].gain);
+    for (int i = 0; i < ntaps; i++)
+        if (!__builtin_isfinite(taps[i])) return fail(JAERO_EINVAL, "jaero_chan_create: tap %d is not finite", i);
+    { const int rc = open_device(device); if (rc) return rc; }
+
+    std::unique_ptr<jaero_chan> c(new (std::nothrow) jaero_chan());
+    if (!c) return fail(JAERO_ENOMEM, "jaero_chan_create: out of memory");
+    int rc = 0;
+    c->device = device; c->decim = decim; c->nch = nchannels; c->max_write_iq = max_write_iq;
+    c->M = CHAN_N / decim; c->Mo = c->M / 2;
+    c->nblk_max = max_write_iq / CHAN_HP + 1;
+    c->channels.assign(ch, ch + nchannels);
+    const size_t nin = 2 * (size_t)CHAN_HP + (size_t)max_write_iq;
+    DA(c->mem, c->d_in[0], nin);
+    DA(c->mem, c->d_in[1], nin);
+    DA(c->mem, c->d_spec, (size_t)c->nblk_max * CHAN_N);
+    DA(c->mem, c->d_gm, c->M);
+    DA(c->mem, c->d_twm, 32);
+    DA(c->mem, c->d_tw, CHAN_N);
+    DA(c->mem, c->d_par, nchannels);
+    DA(c->mem, c->d_pcm, (size_t)nchannels * c->nblk_max * c->Mo);
+    std::vector<ChanParam> par(nchannels);
+    for (int i = 0; i < nchannels; i++) par[i] = chan_param(ch[i], decim);
+    HIPCHK(hipMemcpy(c->d_par, par.data(), sizeof(ChanParam) * nchannels, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_gm, chan_response(taps, ntaps, c->M).data(), sizeof(double2) * c->M, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_twm, twiddles(c->M, 32).data(), sizeof(double2) * 32, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_tw, twiddles(CHAN_N, CHAN_N).data(), sizeof(double2) * CHAN_N, hipMemcpyHostToDevice));
+    HIPCHK(hipFuncSetAttribute((const void *)k_chan_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH * (int)sizeof(double)));
+    *out = c.release();
+    return 0;
+}
+
+static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipStream_t st)
+{
+    const long long nitems = (long long)c->nch * nblk;
+    auto go = [&](auto kernel, int items, int threads) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((nitems + items - 1) / items)), dim3(threads), 0, st, (const double2 *)c->d_spec,
+                           (const double2 *)c->d_gm, (const double2 *)c->d_twm, (const ChanParam *)c->d_par, c->d_pcm, c->nch, nblk, p0);
+    };
+    if (c->decim == 16) go(k_chan_synth<16>, ChanShape<16>::ITEMS, ChanShape<16>::THREADS);
+    else if (c->decim == 32) go(k_chan_synth<32>, ChanShape<32>::ITEMS, ChanShape<32>::THREADS);
+    else go(k_chan_synth<64>, ChanShape<64>::ITEMS, ChanShape<64>::THREADS);
+}
+
+extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
+{
+    if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "jaero_chan_write: bad arguments");
+    if (niq > c->max_write_iq) return fail(JAERO_EINVAL, "jaero_chan_write: niq %d exceeds max_write_iq %d", niq, c->max_write_iq);
+    CHANPOISONCHK(c, "jaero_chan_write");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (st != c->last_stream) // a write on another stream than the previous one waits for what was enqueued there (a bank fed from it included)
+    {
+        if (!c->order_ev) HIPCHK(hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->order_ev, c->last_stream));
+        HIPCHK(hipStreamWaitEvent(st, c->order_ev, 0));
+        c->last_stream = st;
+    }
+    *nout = 0;
+    c->last_nout = 0;
+    if (niq == 0) return 0;
+    int *in = c->d_in[c->cur];
+    HIPCHK(hipMemcpyAsync(in + CHAN_HP + c->pending, iq, sizeof(int) * (size_t)niq, is_device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    c->poisoned = true; // from here on the history, the block count and the device buffers advance together or not at all
+    const int total = c->pending + niq;
+    const int nblk = total / CHAN_HP;
+    c->pending = total;
+    if (nblk > 0)
+    {
+        int pi = c->timer.begin(0, st);
+        hipLaunchKernelGGL(k_chan_fwd, dim3(nblk), dim3(C2_THREADS), C6_XCH * sizeof(double), st, (const int *)in, c->d_spec, (const double2 *)c->d_tw);
+        LAUNCHCHK("k_chan_fwd");
+        c->timer.end(pi, st);
+        pi = c->timer.begin(1, st);
+        chan_launch_synth(c, nblk, c->blocks_done, st);
+        LAUNCHCHK("k_chan_synth");
+        c->timer.end(pi, st);
+        // the last hop and what lies behind it become the other buffer's head
+        const int rest = total - nblk * CHAN_HP;
+        HIPCHK(hipMemcpyAsync(c->d_in[c->cur ^ 1], in + (size_t)nblk * CHAN_HP, sizeof(int) * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
+        c->cur ^= 1;
+        c->pending = rest;
+        c->blocks_done += nblk;
+    }
+    HIPCHK(hipGetLastError());
+    c->last_nout = *nout = nblk * c->Mo;
+    c->poisoned = false;
+    return 0;
+}
+
+extern "C" int jaero_chan_pcm_view(jaero_chan *c, void **dev_pcm, int *nsamples)
+{
+    if (!c || !dev_pcm || !nsamples) return fail(JAERO_EINVAL, "jaero_chan_pcm_view: null argument");
+    CHANPOISONCHK(c, "jaero_chan_pcm_view");
+    *dev_pcm = c->d_pcm;
+    *nsamples = c->last_nout;
+    return 0;
+}
+
+extern "C" int jaero_chan_read_pcm(jaero_chan *c, int16_t *dst, int cap_per_channel, int *nsamples)
+{
+    if (!c || !dst || !nsamples || cap_per_channel < 0) return fail(JAERO_EINVAL, "jaero_chan_read_pcm: bad arguments");
+    CHANPOISONCHK(c, "jaero_chan_read_pcm");
+    if (cap_per_channel < c->last_nout)
+        return fail(JAERO_EINVAL, "jaero_chan_read_pcm: cap_per_channel %d is below the last write's %d samples", cap_per_channel, c->last_nout);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    *nsamples = c->last_nout;
+    if (c->last_nout > 0)
+        HIPCHK(hipMemcpy2D(dst, sizeof(int16_t) * (size_t)cap_per_channel, c->d_pcm, sizeof(int16_t) * (size_t)c->last_nout,
+                           sizeof(int16_t) * (size_t)c->last_nout, (size_t)c->nch, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_channel *ch)
+{
+    if (!c || !ch || channel < 0 || channel >= c->nch) return fail(JAERO_EINVAL, "jaero_chan_retune: bad arguments");
+    if (!chan_channel_ok(*ch)) return fail(JAERO_EINVAL, "jaero_chan_retune: gain %g is not finite and positive", ch->gain);
+    CHANPOISONCHK(c, "jaero_chan_retune");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far keep the old words
+    const ChanParam p = chan_param(*ch, c->decim);
+    HIPCHK(hipMemcpy(c->d_par + channel, &p, sizeof p, hipMemcpyHostToDevice));
+    c->channels[channel] = *ch;
+    return 0;
+}
+
+extern "C" int jaero_chan_feed(jaero_chan *c, jaero_ctx *bank, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
+{
+    if (!c || !bank || !nout) return fail(JAERO_EINVAL, "jaero_chan_feed: null argument");
+    if (bank->device != c->device) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank is on device %d, the channeliser on %d", bank->device, c->device);
+    if (bank->o_nch != c->nch) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank has %d channels, the channeliser %d", bank->o_nch, c->nch);
+    for (const jaero_settings &s : bank->settings)
+        if (s.Fs != 48000.0) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank runs at Fs = %g; the channeliser's output is 48000", s.Fs);
+    if (bank->max_write < c->nblk_max * c->Mo)
+        return fail(JAERO_EINVAL, "jaero_chan_feed: the bank's max_write_samples %d is below (max_write_iq / %d + 1) * %d = %d", bank->max_write,
+                    CHAN_HP, c->Mo, c->nblk_max * c->Mo);
+    int rc = jaero_chan_write(c, iq, niq, is_device_ptr, stream, nout);
+    if (rc || *nout <= 0) return rc;
+    return jaero_write(bank, c->d_pcm, *nout, JAERO_PCM_CHANNEL_MAJOR, 1, stream);
+}
+
+extern "C" int jaero_chan_profile_enable(jaero_chan *c, int on)
+{
+    if (!c) return fail(JAERO_EINVAL, "jaero_chan_profile_enable: null ctx");
+    c->timer.on = on != 0;
+    return 0;
+}
+
+extern "C" int jaero_chan_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset)
+{
+    if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_chan_profile_read: bad arguments");
+    return c->timer.read(c->device, which, total_ms, launches, reset);
+}

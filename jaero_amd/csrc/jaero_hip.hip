@@ -1752,3 +1752,4 @@ extern "C" int jaero_viterbi_continuous(int device, const uint8_t *soft, int nst
 #include "aerol_host.h"
 #include "ingest_host.h"
 #include "edge_host.h"
+#include "chan_host.h"

@@ -1,0 +1,188 @@
+// k_chan.h -- the wideband I/Q channeliser in front of the demodulator banks: a fast-convolution (overlap-save) filter bank, DESIGN 18.
+//
+// No counterpart in the reference (it only has the receiving end of per-channel audio, zmq_audioreceiver.cpp:40-79); the definition is
+// include/jaero_hip.h's, and tests/chan_oracle.py implements it literally in numpy.  Fixed geometry: N = 16384-point forward transform every
+// Hp = N / 2 input samples, shared by all channels (k_chan_fwd); per channel and block the M = N / D bins around the channel's nearest grid
+// frequency times the prototype's response, an M-point inverse transform of which the second half is kept (overlap-save), the sign that
+// makes the bin shift continuous in absolute time, the rotation to the audio offset by an integer phase, gain, rint, clamp (k_chan_synth).
+//
+// The M-point transform: M = R1 x R2, T = R2 threads per (channel, block) item, all inside one wavefront.
+//   n = R2 n1 + n2        r = k1 + R1 k2        (n1, k1 < R1;  n2, k2 < R2)
+//   pass 1 (thread n2): FFT_R1 over n1, x W_M^(n2 k1)       exchange through LDS, a plane at a time: L = k1 (R2 + 1) + n2
+//   pass 2 (thread k1, h): FFT over n2 -> k2; only k2 >= R2 / 2 (r >= M / 2) is kept, what leads to the other outputs is dead code
+//   256 = 16 x 16 (T = 16), 1024 = 32 x 32 (T = 32): thread k1 does the R2-point FFT.  512 = 16 x 32 (T = 32): the 32-point FFT of row k1
+//   is split over two threads by one decimation-in-frequency step: thread (k1, h) forms (a[n] + (-1)^h a[n + 16]) W_32^(h n) and its FFT16
+//   gives k2 = 2 j + h -- sign and twiddle are per-thread VALUES, so both halves run the same instructions.
+// The inverse transform is the forward one on swapped planes.  Index maps and bank behaviour: tests/test_chan_fft_model.py.
+#pragma once
+#include "k_coarse6.h"
+
+#define CHAN_N 16384
+#define CHAN_HP 8192
+
+struct ChanParam // one channel, from (tune, audio, gain) on the host (chan_host.h)
+{
+    int b;          // nearest bin of the tuning word: (t + 2^17) >> 18
+    unsigned w;     // phase word per output sample: audio - rho * D  (mod 2^32)
+    double gain;
+};
+
+// ------------------------------------------------------------------------------------------ forward transform
+// One workgroup per block of the write: window j = in[j * Hp .. j * Hp + N) of the history buffer (previous hop, the partial hop left by
+// ragged writes, the new samples; interleaved int16 I, Q read as one dword) -> fp64 -> wg_fft14_e32 -> spec[j][N].
+__global__ __launch_bounds__(C2_THREADS) void k_chan_fwd(const int *__restrict__ in, double2 *__restrict__ spec, const double2 *__restrict__ tw)
+{
+    extern __shared__ __attribute__((aligned(16))) double xch[];
+    const int t = threadIdx.x;
+    const int *__restrict__ src = in + (size_t)blockIdx.x * CHAN_HP;
+    double2 *__restrict__ dst = spec + (size_t)blockIdx.x * CHAN_N;
+    CV<32> d;
+#pragma unroll
+    for (int s = 0; s < 32; s++)
+    {
+        const int v = src[s * C2_THREADS + t];
+        d.r[s] = (double)(short)(v & 0xffff);
+        d.i[s] = (double)(v >> 16);
+    }
+    wg_fft14_e32(d, xch, tw, t);
+#pragma unroll
+    for (int s = 0; s < 32; s++) dst[s * C2_THREADS + t] = make_double2(d.r[s], d.i[s]);
+}
+
+// ------------------------------------------------------------------------------------------ per-channel synthesis
+template <int D>
+struct ChanShape
+{
+    static constexpr int M = CHAN_N / D, MO = M / 2;
+    static constexpr int R1 = M == 1024 ? 32 : 16;     // pass 1: points per thread
+    static constexpr int R2 = M == 256 ? 16 : 32;      // = T, threads per item
+    static constexpr int P2 = M == 1024 ? 32 : 16;     // pass 2: points per thread's FFT
+    static constexpr int SPLIT = R2 / P2;              // 2: a row's FFT_R2 shared by two threads
+    static constexpr int T = R2;
+    static constexpr int ITEMS = M == 1024 ? 4 : 256 / T; // (channel, block) items per workgroup
+    static constexpr int THREADS = ITEMS * T;          // 256, 256, 128
+    static constexpr int ROW = R2 + 1;                 // odd row stride of the exchange: 16 lanes that differ in k1 hit 16 bank pairs
+    static constexpr int XCH = R1 * ROW;               // doubles per item
+    static constexpr int OUTS = MO / T;                // int16 each thread stores: 8, 8, 16
+};
+
+// exchange address of (k1, n2)
+template <int D> __device__ __forceinline__ constexpr int chan_xaddr(int k1, int n2) { return k1 * ChanShape<D>::ROW + n2; }
+
+// v[k] *= step^k (k < 32), the powers by products of depth <= 6 as c4_twiddle16
+__device__ __forceinline__ void chan_twiddle32(CV<32> &v, const double2 step)
+{
+#pragma clang fp contract(fast)
+    double2 B[4], A[8];
+    twiddle_powers<32>(make_double2(1.0, 0.0), step, B, A);
+#pragma unroll
+    for (int k = 1; k < 32; k++)
+    {
+        const double2 w = (k < 4) ? B[k & 3] : cmul2(A[k >> 2], B[k & 3]);
+        const double r = v.r[k] * w.x - v.i[k] * w.y, i = v.r[k] * w.y + v.i[k] * w.x;
+        v.r[k] = r; v.i[k] = i;
+    }
+}
+
+template <int L> __device__ __forceinline__ void chan_fft(CV<L> &in, CV<L> &out)
+{
+    if constexpr (L == 32) regfft32_seq(in, out);
+    else regfft<L>(in, out);
+}
+
+// spec: [nblk][N] of this write; gm: [M] the prototype's response at q = k (k < M / 2), k - M (else), already / N; twm: W_M^k, k < 32;
+// pcm: [nch][nblk * MO]; p0: absolute index of the write's first block.
+template <int D>
+__global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const double2 *__restrict__ spec, const double2 *__restrict__ gm,
+                                                                      const double2 *__restrict__ twm, const ChanParam *__restrict__ par,
+                                                                      int16_t *__restrict__ pcm, int nch, int nblk, long long p0)
+{
+#pragma clang fp contract(fast)
+    using S = ChanShape<D>;
+    constexpr int M = S::M, MO = S::MO, R1 = S::R1, R2 = S::R2, P2 = S::P2, T = S::T;
+    __shared__ __attribute__((aligned(16))) double xch_all[S::ITEMS * S::XCH];
+    const int u = threadIdx.x % T, li = threadIdx.x / T;
+    double *xch = xch_all + li * S::XCH;
+    const long long nitems = (long long)nch * nblk;
+    const long long item_raw = (long long)blockIdx.x * S::ITEMS + li;
+    const bool live = item_raw < nitems;
+    const long long item = live ? item_raw : nitems - 1; // a workgroup's spare lanes redo the last item and store nothing: every barrier is met
+    const int j = (int)(item / nch), c = (int)(item - (long long)j * nch); // block-major: a block's spectrum stays in L2 for all channels
+    const ChanParam cp = par[c];
+    const double2 *__restrict__ X = spec + (size_t)j * CHAN_N;
+
+    // ---- gather + pass 1: thread n2 = u holds k = R2 n1 + u ----
+    CV<R1> a, A;
+#pragma unroll
+    for (int n1 = 0; n1 < R1; n1++)
+    {
+        const int k = R2 * n1 + u;
+        const int q = k < M / 2 ? k : k - M;
+        const double2 x = X[(cp.b + q) & (CHAN_N - 1)], g = gm[k];
+        // Y = X G; the inverse transform is the forward one of the swapped planes
+        a.i[n1] = x.x * g.x - x.y * g.y;
+        a.r[n1] = x.x * g.y + x.y * g.x;
+    }
+    chan_fft<R1>(a, A);
+    {
+        const double2 st = twm[u]; // W_M^n2
+        if constexpr (R1 == 32) chan_twiddle32(A, st);
+        else c4_twiddle16(A, st);
+    }
+    // ---- exchange (a plane at a time) + the split's radix-2 step ----
+    const int k1 = u % R1, h = u / R1; // h = 0 unless SPLIT == 2
+    CV<P2> e, E;
+    const double sg = h ? -1.0 : 1.0;
+#pragma unroll
+    for (int k = 0; k < R1; k++) xch[chan_xaddr<D>(k, u)] = A.r[k];
+    c4_lds_barrier();
+#pragma unroll
+    for (int n = 0; n < P2; n++)
+    {
+        if constexpr (S::SPLIT == 2) e.r[n] = xch[chan_xaddr<D>(k1, n)] + sg * xch[chan_xaddr<D>(k1, n + P2)];
+        else e.r[n] = xch[chan_xaddr<D>(k1, n)];
+    }
+    c4_lds_barrier();
+#pragma unroll
+    for (int k = 0; k < R1; k++) xch[chan_xaddr<D>(k, u)] = A.i[k];
+    c4_lds_barrier();
+#pragma unroll
+    for (int n = 0; n < P2; n++)
+    {
+        if constexpr (S::SPLIT == 2) e.i[n] = xch[chan_xaddr<D>(k1, n)] + sg * xch[chan_xaddr<D>(k1, n + P2)];
+        else e.i[n] = xch[chan_xaddr<D>(k1, n)];
+    }
+    if constexpr (S::SPLIT == 2) c4_twiddle16(e, h ? make_double2(jd_w64r(2), jd_w64i(2)) : make_double2(1.0, 0.0)); // W_32^(h n)
+    // ---- pass 2: only the outputs with k2 >= R2 / 2 are used below ----
+    chan_fft<P2>(e, E);
+
+    // ---- sign, rotation to the audio offset, gain, rint, clamp; through LDS so that every thread stores one contiguous run ----
+    c4_lds_barrier(); // the exchange buffer is free
+    int16_t *stage = (int16_t *)xch;
+    const long long p = p0 + j;
+    const double sgn = ((cp.b & 1) && ((p + 1) & 1)) ? -cp.gain : cp.gain; // (-1)^(b (p - 1)) g
+    const unsigned m0 = (unsigned)((unsigned long long)p * (unsigned)MO);  // m mod 2^32 of the block's first output
+#pragma unroll
+    for (int jj = 0; jj < P2 / 2; jj++)
+    {
+        const int k2 = S::SPLIT == 2 ? 2 * (jj + P2 / 2) + h : jj + P2 / 2; // >= R2 / 2
+        const int ml = k1 + R1 * (k2 - R2 / 2);                             // r - MO
+        const int s = jj + P2 / 2;
+        const double vr = E.i[s], vi = E.r[s]; // swapped back
+        const unsigned ph = cp.w * (m0 + (unsigned)ml);
+        double sn, cs;
+        sincospi((double)(int)ph * (1.0 / 2147483648.0), &sn, &cs); // 2 pi ph / 2^32, ph as a signed word: (-pi, pi]
+        double y = rint(sgn * (vr * cs - vi * sn));
+        y = fmin(fmax(y, -32768.0), 32767.0);
+        stage[ml] = (int16_t)(int)y;
+    }
+    c4_lds_barrier();
+    if (live)
+    {
+        typedef int chan_v4 __attribute__((ext_vector_type(4)));
+        const chan_v4 *sv = (const chan_v4 *)stage;
+        chan_v4 *__restrict__ dst = (chan_v4 *)(pcm + ((size_t)c * nblk + j) * MO);
+#pragma unroll
+        for (int v = 0; v < S::OUTS / 8; v++) dst[v * T + u] = sv[v * T + u];
+    }
+}

@@ -11,7 +11,8 @@ The reference has no modulator; these follow the signal definitions its demodula
   equal the FSK data bits directly.
 
 Everything here is numpy on the host (used by tests, the oracle legs and small benches).  `oqpsk_torch`
-produces the same waveform family on a torch device for large resident bench inputs.
+produces the same waveform family on a torch device for large resident bench inputs.  `wideband_oqpsk` is the capture
+the channeliser cuts such channels out of: complex int16 I/Q at 48 kHz x decim.
 """
 from __future__ import annotations
 
@@ -378,3 +379,41 @@ def burst_oqpsk_torch(nch: int, nsamples: int, device, *, period: int = 48000, n
     scale = peak / (3.0 * np.sqrt(P)) * 32768.0
     out = _render_oqpsk_torch(a_i, a_q, carriers, nsamples, device, fb=fb, Fs=Fs, sigma=sigma, scale=scale, gen=gen, block=block)
     return out, carriers, (off.to(torch.float64) * T)
+
+
+def wideband_oqpsk(bits_list, centres, amps, decim: int, *, fb: float = 10500.0, ebno_db: float | None = 13.0, rms: float = 0.1,
+                   seed: int = 7, nsamples: int | None = None, chunk: int = 1 << 20, return_info: bool = False):
+    """A synthetic capture for the channeliser: int16 I/Q [nsamples, 2] at 48 kHz x decim holding one OQPSK channel per entry of
+    `bits_list` -- the complex baseband i(t) + j q(t) of `oqpsk` (even bits on I, odd on Q, Q half a symbol late) at the capture
+    rate, times amps[c], shifted to centres[c] Hz -- summed, white noise added at `ebno_db` for a channel of amplitude min(amps),
+    scaled to `rms` of full scale per complex sample, rounded and clipped.  Generated `chunk` samples at a time.  return_info: also
+    {"scale": LSB per unit of the sum, "p_unit": power of a unit-amplitude channel's complex baseband}."""
+    fs = 48000.0 * decim
+    T = fs / (fb / 2.0)
+    if nsamples is None:
+        nsamples = int(np.ceil(max(len(b) for b in bits_list) / 2 * T))
+    x = np.zeros(nsamples, dtype=np.complex128)
+    p_unit = 0.0
+    for bits, fc, amp in zip(bits_list, centres, amps):
+        bits = np.asarray(bits)
+        nsym = len(bits) // 2
+        a_i = 2.0 * bits[0::2][:nsym].astype(np.float64) - 1.0
+        a_q = 2.0 * bits[1::2][:nsym].astype(np.float64) - 1.0
+        for s in range(0, nsamples, chunk):
+            n = np.arange(s, min(nsamples, s + chunk), dtype=np.float64)
+            bb = _shape(a_i, n, T, 0.0) + 1j * _shape(a_q, n, T, T / 2.0)
+            x[s:s + len(n)] += amp * bb * np.exp(2j * np.pi * ((fc * n / fs) % 1.0))
+        if not p_unit:
+            n = np.arange(0, min(nsamples, 100000), dtype=np.float64)
+            p_unit = 2.0 * float(np.mean(_shape(a_i, n, T, 0.0) ** 2))  # power of a unit-amplitude channel (both arms)
+    if ebno_db is not None:
+        rng = np.random.default_rng(seed)
+        sigma2 = min(amps) ** 2 * p_unit * fs / (fb * 10.0 ** (ebno_db / 10.0))
+        x = x + np.sqrt(sigma2 / 2.0) * (rng.normal(size=nsamples) + 1j * rng.normal(size=nsamples))
+    scale = rms * 32768.0 / np.sqrt(np.mean(np.abs(x) ** 2))
+    out = np.empty((nsamples, 2), dtype=np.int16)
+    out[:, 0] = np.clip(np.rint(x.real * scale), -32768, 32767)
+    out[:, 1] = np.clip(np.rint(x.imag * scale), -32768, 32767)
+    if return_info:
+        return out, {"scale": float(scale), "p_unit": p_unit}
+    return out

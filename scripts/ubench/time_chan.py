@@ -1,0 +1,56 @@
+"""Timing of the channeliser in front of the headline OQPSK bank: Channeliser.feed of 16 hops (131 072 I/Q pairs at D = 32 -> 4096 samples per
+channel) per step.  Prints one JSON line: HIP-event time per step of k_chan_fwd and k_chan_synth, of the bank's sample loop and coarse estimate
+from the same steps, their ratio (the yardstick: the two channeliser kernels together against the demodulator bank's own step time), the
+engine clock over the timed steps.
+usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup]"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+from bench_state import GpuStateSampler  # noqa: E402
+from jaero_amd.channeliser import HP, Channeliser  # noqa: E402
+from jaero_amd.demodulator import DemodulatorBank, OqpskSettings  # noqa: E402
+
+nch = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
+K = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+W = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+decim, hops = 32, 16
+rng = np.random.default_rng(1)
+iq = torch.from_numpy(rng.integers(-8000, 8000, size=(hops * HP, 2), dtype=np.int16)).cuda()
+chans = [(int(t), 715827883, 1.0) for t in rng.integers(0, 1 << 32, size=nch, dtype=np.uint64)]
+chan = Channeliser(decim, chans, max_write_iq=hops * HP)
+bank = DemodulatorBank(OqpskSettings(), nch, ebno=True, max_write_samples=(hops + 1) * chan.Mo, softbit_capacity=4096)
+st = torch.cuda.current_stream().cuda_stream
+for _ in range(W):
+    chan.feed(bank, iq, stream=st)
+    bank.discard_softbits(st)
+torch.cuda.synchronize()
+chan.profile_enable(True)
+bank.profile_enable(True)
+state = GpuStateSampler().start("timed")
+t0 = time.perf_counter()
+for _ in range(K):
+    assert chan.feed(bank, iq, stream=st) == hops * chan.Mo
+    bank.discard_softbits(st)
+torch.cuda.synchronize()
+dt = time.perf_counter() - t0
+state.stop()
+fwd, nf = chan.profile_read(0)
+syn, ns = chan.profile_read(1)
+loop, nl = bank.profile_read(0)
+coarse, nc = bank.profile_read(1)
+chan_ms, bank_ms = (fwd + syn) / K, (loop + coarse) / K
+print(json.dumps({
+    "channels": nch, "decim": decim, "steps": K, "warmup": W, "samples_per_channel_per_step": hops * chan.Mo,
+    "k_chan_fwd_ms_per_step": round(fwd / K, 4), "k_chan_fwd_launches": nf,
+    "k_chan_synth_ms_per_step": round(syn / K, 4), "k_chan_synth_launches": ns,
+    "bank_sample_loop_ms_per_step": round(loop / K, 4), "bank_sample_loop_launches": nl,
+    "bank_coarse_ms_per_step": round(coarse / K, 4), "bank_coarse_launches": nc,
+    "chan_ms_per_step": round(chan_ms, 4), "bank_ms_per_step": round(bank_ms, 4), "chan_over_bank": round(chan_ms / bank_ms, 4),
+    "wall_ms_per_step": round(1e3 * dt / K, 3), "gpu_state": state.summary()}))
