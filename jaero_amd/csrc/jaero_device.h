@@ -234,6 +234,47 @@ __device__ __forceinline__ int jd_softbit(double v)
     return ibit;
 }
 
+// IIR::update (JAERO/DSP.cpp) for the second-order sections the demodulators use (the symbol-timing resonator, the OQPSK loop filter):
+// the reference's sum, term by term and each rounded, then its shift of the state
+__device__ __forceinline__ double jd_biquad(double x, double &x1, double &x2, double &y1, double &y2, double b0, double b1, double b2, double a1,
+                                            double a2)
+{
+    double y = 0;
+    y += x2 * b2; y += x1 * b1; y += x * b0;
+    y -= y2 * a2; y -= y1 * a1;
+    x2 = x1; x1 = x; y2 = y1; y1 = y;
+    return y;
+}
+// DiffDecode::UpdateSoft (JAERO/DSP.cpp:531-563)
+__device__ __forceinline__ double jd_diff_soft(double soft_in, double &diff_last)
+{
+    double r;
+    if (soft_in < 0 && diff_last < 0) r = diff_last;
+    else if (soft_in > 0 && diff_last > 0) r = -diff_last;
+    else r = fabs(diff_last);
+    diff_last = soft_in;
+    return r;
+}
+// WaveTable::WTnextFrame (JAERO/DSP.cpp:70-77) with the last_WTptr bookkeeping IfHavePassedPoint needs: one step of a symbol oscillator
+// (the wrap written as in fb_wt_next)
+__device__ __forceinline__ void jd_wt_next_symbol(double &ptr, double &step, double &last_ptr)
+{
+    if (step < 0) step = 0;
+    last_ptr = ptr;
+    ptr += step;
+    if (((int)ptr) >= JD_WTSIZE)
+    {
+        ptr -= JD_WTSIZE;
+        while (((int)ptr) >= JD_WTSIZE) ptr -= JD_WTSIZE;
+    }
+}
+// The LDS-only workgroup barrier of the front / back pairs and the workgroup FFTs: LDS traffic of this wavefront done, then the barrier.
+// NOT __syncthreads(): that also drains vmcnt, i.e. every HBM row requested ahead.
+__device__ __forceinline__ void jd_lds_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
 // The EbNo meters (OQPSKEbNoMeasure / MSKEbNoMeasure, JAERO/DSP.cpp:729-744,493-505) never feed back into the signal path; their
 // output EbNo = 0.8 EbNo + 0.2 t[n] forgets a term after k samples as 0.8^k (0.8^192 = 2.5e-19).  The ring sums are kept up to
 // date on every sample, but the divide/log10 part is only evaluated over the last JD_EBNO_TAIL samples of a launch -- the value

@@ -6,6 +6,7 @@
 #pragma once
 #include "burst_device.h"
 #include "jaero_device.h"
+#include "demod_stages.h"
 #include "k_burst_front.h"
 
 __device__ __forceinline__ void bd_event(const BGeom &g, const BPtrs &p, int ch, int &ev_cnt, int &overflow, long long sample, int kind, double value)
@@ -108,7 +109,7 @@ constexpr int bd_lds_bytes() { return (2 * BD_LDSN * 64 + 64) * (int)sizeof(doub
 template <bool CAPSYM>
 __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const BPtrs p, int n, long long n0, int first_of_write)
 {
-    // matched-filter history as in k_oqpsk.h: the LDSN newest entries of each arm in LDS ([slot][lane]), the FIRN-LDSN oldest in a
+    // matched-filter history as in k_oqpsk_fb.h: the LDSN newest entries of each arm in LDS ([slot][lane]), the FIRN-LDSN oldest in a
     // VGPR shift register, plus this wavefront's copy of the taps (jd_fir_eval) -> 36.5 KiB of LDS per wavefront (bd_lds_bytes), four per CU
     constexpr int FIRN = 55, LDSN = BD_LDSN, TAILN = FIRN - LDSN;
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -157,12 +158,7 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
     double *msema_ring = p.msema + (size_t)ch * g.msema_len;
     int16_t *__restrict__ soft = p.soft + (size_t)ch * g.soft_cap;
 
-    {
-        const double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++) { lre[k * 64 + lane] = fs[(size_t)k * 64]; lim[k * 64 + lane] = fs[(size_t)(FIRN + k) * 64]; }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++) { tre[j] = fs[(size_t)(LDSN + j) * 64]; tim[j] = fs[(size_t)(FIRN + LDSN + j) * 64]; }
-    }
+    stg_hist_load<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
     if (lane < FIRN) ltap[lane] = taps[lane];
     int tapz; // a zero in a vector register: tap reads become `register + immediate offset` (bd_fir_eval_v)
     asm volatile("v_mov_b32 %0, 0" : "=v"(tapz));
@@ -300,19 +296,7 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
             // IIR forgets a term after k samples as 0.8^k, so the divide/log10 runs only in the JD_EBNO_TAIL samples before either.
             const double to_emit = ((128.0 + 128.0 + 128.0) * SPS) - (double)cntr;
             if (i >= n - JD_EBNO_TAIL || (to_emit > -1.0 && to_emit < (double)JD_EBNO_TAIL))
-            {
-                const double e2val = eb_e2sum / eb_len_d, mean = eb_esum / eb_len_d;
-                const double meansq = mean * mean;
-                double var = e2val - (mean * mean);
-                var -= (0.024709 * meansq);
-                double mvr = (((g.Fs * meansq / (2.0 * g.fb * var))) * 0.13743);
-                if (mvr < 0.000000001) mvr = 0.000000001;
-                double tebno = 10.0 * log10(mvr);
-                if (isnan(tebno)) tebno = 50;
-                if (tebno > 50.0) tebno = 50;
-                if (tebno < 0.0) tebno = 0;
-                eb_ebno = eb_ebno * 0.8 + 0.2 * tebno;
-            }
+                eb_ebno = stg_ebno_oqpsk(eb_ebno, eb_e2sum / eb_len_d, eb_esum / eb_len_d, g.Fs, g.fb);
         }
         if (fabs(cntr - ((128.0 + 128.0 + 128.0) * SPS)) < 0.5) bd_event(g, p, ch, ev_cnt, overflow, sample, BEV_EBNO, eb_ebno);
         {
@@ -326,16 +310,9 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
         if (abval > 2.84) { const double k = (2.84 / abval); sre = k * sre; sim = k * sim; }
 
         // ---- symbol timer (:592-612) ----
-        const double ab2 = abval * abval;
-        const double st_diff = d1 - ab2; d1 = ab2;
-        const double st_d1out = w4 * d41_2 + w4c * d41_3; d41_3 = d41_2; d41_2 = d41_1; d41_1 = st_diff;
-        const double st_d2out = w4 * d42_2 + w4c * d42_3; d42_3 = d42_2; d42_2 = d42_1; d42_1 = st_d1out;
-        double st_eta = (st_d2out - st_diff) * st_d1out;
+        double st_eta = stg_oqpsk_t4_pair(abval, d1, d41_1, d41_2, d41_3, d42_1, d42_2, d42_3, w4, w4c);
         {
-            double y = 0;
-            y += res_x2 * g.res_b2; y += res_x1 * g.res_b1; y += st_eta * g.res_b0;
-            y -= res_y2 * g.res_a2; y -= res_y1 * g.res_a1;
-            res_x2 = res_x1; res_x1 = st_eta; res_y2 = res_y1; res_y1 = y;
+            const double y = jd_biquad(st_eta, res_x1, res_x2, res_y1, res_y2, g.res_b0, g.res_b1, g.res_b2, g.res_a1, g.res_a2);
             if (cntr > SPS * (128 + 128)) st_eta = y;
         }
         const double d8out = w8 * d8_1 + w8c * d8_2; d8_2 = d8_1; d8_1 = st_eta;
@@ -416,10 +393,7 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
         sig2l_re = sre; sig2l_im = sim;
         // ---- advance the oscillators (:727-730) ----
         jd_wt_next(m2_ptr, m2_step);
-        if (st_step < 0) st_step = 0;
-        st_last = st_ptr;
-        st_ptr += st_step;
-        while (((int)st_ptr) >= JD_WTSIZE) st_ptr -= JD_WTSIZE;
+        jd_wt_next_symbol(st_ptr, st_step, st_last);
         stq_ptr += g.stq_step;
         while (((int)stq_ptr) >= JD_WTSIZE) stq_ptr -= JD_WTSIZE;
         s_val++; if (s_val >= g.cv_len) s_val = 0;
@@ -440,12 +414,7 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
     BLDI(BI_STARTSTOP) = startstop; BLDI(BI_CNTR) = cntr; BLDI(BI_YUI) = yui; BLDI(BI_INSERTPRE) = insertpre;
     BLDI(BI_MSEMA_POS) = msema_pos; BLDI(BI_NRX) = nrx;
     BLDI(BI_SOFT_CNT) = soft_cnt; BLDI(BI_SYM_CNT) = sym_cnt; BLDI(BI_EV_CNT) = ev_cnt; BLDI(BI_OVERFLOW) = overflow;
-    {
-        double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++) { fs[(size_t)k * 64] = lre[k * 64 + lane]; fs[(size_t)(FIRN + k) * 64] = lim[k * 64 + lane]; }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++) { fs[(size_t)(LDSN + j) * 64] = tre[j]; fs[(size_t)(FIRN + LDSN + j) * 64] = tim[j]; }
-    }
+    stg_hist_save<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
 }
 
 // ------------------------------------------------------------------------------------------------ burst MSK

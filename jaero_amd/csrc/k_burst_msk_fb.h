@@ -61,12 +61,8 @@ __device__ __forceinline__ void bmsk_front(const BGeom &g, const BPtrs &p, doubl
     jd_cdouble *taps = (jd_cdouble *)p.taps2; // this bank's own half-sine taps through the constant address space: scalar loads
     int fir_pos = BLDI(BI_FIR_POS);
     const double *__restrict__ cvre = p.cvre + (size_t)grp * g.cv_len * 64 + lane;
-    {
-        const double *fs = p.firsave + (size_t)ch * 2 * FIRN; // [0, LDSN): the LDS ring's slots, [LDSN, FIRN): the register tail
-        for (int k = 0; k < LDSN; k++) { lre[k * 64 + lane] = fs[k]; lim[k * 64 + lane] = fs[FIRN + k]; }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++) { tre[j] = fs[LDSN + j]; tim[j] = fs[FIRN + LDSN + j]; }
-    }
+    // this kernel's saved history is per channel: [0, LDSN): the LDS ring's slots, [LDSN, FIRN): the register tail
+    stg_hist_load<FIRN, LDSN, TAILN, 1>(p.firsave + (size_t)ch * 2 * FIRN, lre, lim, lane, tre, tim);
     int s_val = (int)((n0 - g.D1 - g.D2 + 8LL * g.cv_len) % g.cv_len);
     double nx_val = cvre[(size_t)s_val * 64];
     // output from x[n-FIRN .. n-1], taps[t] <-> x[n-FIRN+t], oldest first: the register tail, then the LDS ring from this lane's oldest slot.
@@ -117,7 +113,7 @@ __device__ __forceinline__ void bmsk_front(const BGeom &g, const BPtrs &p, doubl
     M.out[lane] = osre; M.out[64 + lane] = osim; // for sample 0: the history as the previous launch left it
     for (int i = 0; i < n; i++)
     {
-        fb_barrier();
+        jd_lds_barrier();
         const int gate = M.gate[(i & 1) * 64 + lane];
         const double *in = M.in + (i & 1) * 192 + lane;
         const double cx = in[0], cy = in[64], vg = in[128];
@@ -145,12 +141,7 @@ __device__ __forceinline__ void bmsk_front(const BGeom &g, const BPtrs &p, doubl
         }
     }
     BLDI(BI_FIR_POS) = fir_pos;
-    {
-        double *fs = p.firsave + (size_t)ch * 2 * FIRN;
-        for (int k = 0; k < LDSN; k++) { fs[k] = lre[k * 64 + lane]; fs[FIRN + k] = lim[k * 64 + lane]; }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++) { fs[LDSN + j] = tre[j]; fs[FIRN + LDSN + j] = tim[j]; }
-    }
+    stg_hist_save<FIRN, LDSN, TAILN, 1>(p.firsave + (size_t)ch * 2 * FIRN, lre, lim, lane, tre, tim);
 }
 
 template <bool CAPSYM, bool D8LDS>
@@ -278,7 +269,7 @@ __device__ __forceinline__ void bmsk_back(const BGeom &g, const BPtrs &p, const 
             in[0] = c2.x; in[64] = c2.y; in[128] = vol_gain;
             M.gate[(i & 1) * 64 + lane] = gate ? 1 : 0;
         }
-        fb_barrier();
+        jd_lds_barrier();
         {
             // mixer2 advances at the end of a gated sample and only there (:736-740): its entry for the next sample can be requested now
             double m2n = m2_ptr;
@@ -340,15 +331,7 @@ __device__ __forceinline__ void bmsk_back(const BGeom &g, const BPtrs &p, const 
                 // its IIR forgets a term after k samples as 0.8^k, so the arithmetic runs only in the JD_EBNO_TAIL samples before those
                 const int to_emit = (g.endRotation + (int)(200 * SPS)) - cntr;
                 if (i >= n - JD_EBNO_TAIL || (to_emit >= 0 && to_emit < JD_EBNO_TAIL) || startstop <= JD_EBNO_TAIL)
-                {
-                    const double e2val = eb_e2sum / eb_len_d, mean = eb_esum / eb_len_d;
-                    const double var = e2val - (mean * mean);
-                    const double alpha = sqrt(2.0) / mean;
-                    double tebno = 10.0 * (log10(2.0) - log10(((var * alpha * alpha) - 0.0085))) - 5.0;
-                    if (isnan(tebno)) tebno = 50;
-                    if (tebno > 50.0) tebno = 50;
-                    eb_ebno = eb_ebno * 0.8 + 0.2 * tebno;
-                }
+                    eb_ebno = stg_ebno_msk(eb_ebno, eb_e2sum / eb_len_d, eb_esum / eb_len_d);
             }
             if (cntr == g.endRotation + (200 * SPS)) bd_event(g, p, ch, ev_cnt, overflow, sample, BEV_EBNO, eb_ebno);
             {
@@ -364,13 +347,7 @@ __device__ __forceinline__ void bmsk_back(const BGeom &g, const BPtrs &p, const 
             const double2 ptd = ptd_pre; // the oldest entry, not the one just written (dly_len >= 2)
             const double pm_re = sre, pm_im = ptd.y;
             double st_eta = hypot(pm_re, pm_im);
-            {
-                double y = 0;
-                y += res_x2 * g.res_b2; y += res_x1 * g.res_b1; y += st_eta * g.res_b0;
-                y -= res_y2 * g.res_a2; y -= res_y1 * g.res_a1;
-                res_x2 = res_x1; res_x1 = st_eta; res_y2 = res_y1; res_y1 = y;
-                st_eta = y;
-            }
+            st_eta = jd_biquad(st_eta, res_x1, res_x2, res_y1, res_y2, g.res_b0, g.res_b1, g.res_b2, g.res_a1, g.res_a2);
             // delayt8.update(st_eta): integer delay SPS/2
             if constexpr (D8LDS) d8l[d8_pos * 64] = st_eta; else wc_at(WC_D8, ph) = st_eta;
             const double d8out = 0.0 * d8_a + 1.0 * d8_b; // the two oldest entries of a ring of d8_len: older than the entry just written (d8_len >= 3)
@@ -423,22 +400,8 @@ __device__ __forceinline__ void bmsk_back(const BGeom &g, const BPtrs &p, const 
                     else overflow |= 2;
                 }
                 // DiffDecode::UpdateSoft x2 (DSP.cpp:531-563)
-                double imagin, realv;
-                {
-                    const double sf = pm_im;
-                    if (sf < 0 && diff_last < 0) imagin = diff_last;
-                    else if (sf > 0 && diff_last > 0) imagin = -diff_last;
-                    else imagin = fabs(diff_last);
-                    diff_last = sf;
-                }
-                {
-                    const double sf = pm_re;
-                    if (sf < 0 && diff_last < 0) realv = diff_last;
-                    else if (sf > 0 && diff_last > 0) realv = -diff_last;
-                    else realv = fabs(diff_last);
-                    diff_last = sf;
-                }
-                realv = -realv;
+                const double imagin = jd_diff_soft(pm_im, diff_last);
+                const double realv = -jd_diff_soft(pm_re, diff_last);
                 const int b0 = jd_softbit((imagin) * 127.0 + 128.0);
                 const int b1 = jd_softbit((realv) * 127.0 + 128.0);
                 if (soft_cnt + 2 <= g.soft_cap) { soft[soft_cnt] = (int16_t)b0; soft[soft_cnt + 1] = (int16_t)b1; soft_cnt += 2; nrx += 2; }

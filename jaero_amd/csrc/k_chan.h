@@ -135,17 +135,17 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
     const double sg = h ? -1.0 : 1.0;
 #pragma unroll
     for (int k = 0; k < R1; k++) xch[chan_xaddr<D>(k, u)] = A.r[k];
-    c4_lds_barrier();
+    jd_lds_barrier();
 #pragma unroll
     for (int n = 0; n < P2; n++)
     {
         if constexpr (S::SPLIT == 2) e.r[n] = xch[chan_xaddr<D>(k1, n)] + sg * xch[chan_xaddr<D>(k1, n + P2)];
         else e.r[n] = xch[chan_xaddr<D>(k1, n)];
     }
-    c4_lds_barrier();
+    jd_lds_barrier();
 #pragma unroll
     for (int k = 0; k < R1; k++) xch[chan_xaddr<D>(k, u)] = A.i[k];
-    c4_lds_barrier();
+    jd_lds_barrier();
 #pragma unroll
     for (int n = 0; n < P2; n++)
     {
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
     chan_fft<P2>(e, E);
 
     // ---- sign, rotation to the audio offset, gain, rint, clamp; through LDS so that every thread stores one contiguous run ----
-    c4_lds_barrier(); // the exchange buffer is free
+    jd_lds_barrier(); // the exchange buffer is free
     int16_t *stage = (int16_t *)xch;
     const long long p = p0 + j;
     const double sgn = ((cp.b & 1) && ((p + 1) & 1)) ? -cp.gain : cp.gain; // (-1)^(b (p - 1)) g
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
         y = fmin(fmax(y, -32768.0), 32767.0);
         stage[ml] = (int16_t)(int)y;
     }
-    c4_lds_barrier();
+    jd_lds_barrier();
     if (live)
     {
         typedef int chan_v4 __attribute__((ext_vector_type(4)));

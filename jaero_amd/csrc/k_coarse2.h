@@ -1,6 +1,6 @@
 // k_coarse2.h -- the register-FFT building blocks: CV<L> (L complex points in registers), regfft<L> (radix-4 / radix-2 DFT of them),
-// c4_twiddle16, c4_lds_barrier (wg_fft<LOG2N>, the 512-thread E x 32 x 16 transform k_trident used until round 4, left with it).  The coarse-frequency estimator kernels themselves are in k_coarse6.h (round 3); the first
-// register-resident one, k_coarse2<LOG2N>, lived here (rounds 1-2).
+// c4_twiddle16.  Their users: the coarse-frequency estimator (k_coarse6.h), the 8400 bps prefilter (k_pre8400.h) and the channeliser
+// (k_chan.h); the workgroup barrier between their LDS exchanges is jd_lds_barrier (jaero_device.h).
 #pragma once
 #include "jaero_device.h"
 #include "fft_consts.h"
@@ -116,7 +116,7 @@ __device__ __forceinline__ void twiddle_powers(const double2 base, const double2
 }
 
 // (The estimator kernel built on wg_fft, k_coarse2<LOG2N>, served the MSK rates until round 3: 6.76 ms per 65 536 estimates of 2^13 points,
-// half of its threads idle in the 32-point pass.  k_coarse6.h replaces it: k_coarse6_13, 5.64 ms.  wg_fft stays for k_trident.)
+// half of its threads idle in the 32-point pass.  k_coarse6.h replaces it: k_coarse6_13, 5.64 ms; wg_fft left the library with k_trident's use of it in round 4.)
 
 // v[k] *= step^k (k < 16), the powers by products of depth <= 6 (k_pre8400.h's 4096-point transform)
 __device__ __forceinline__ void c4_twiddle16(CV<16> &v, const double2 step) // v[k] *= step^k
@@ -131,13 +131,4 @@ __device__ __forceinline__ void c4_twiddle16(CV<16> &v, const double2 step) // v
         const double r = v.r[k] * w.x - v.i[k] * w.y, i = v.r[k] * w.y + v.i[k] * w.x;
         v.r[k] = r; v.i[k] = i;
     }
-}
-
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. waits for every global load and STORE in
-// flight: behind the y[] update that is 32 stores per thread on their way to HBM, behind the ring prefetch 32 loads -- the prefetch
-// was issued early precisely so that the peak search would run under it.
-__device__ __forceinline__ void c4_lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }

@@ -21,7 +21,6 @@
 #ifndef C4_TABN
 #define C4_TABN 3584 // W8400: window table entries kept in LDS behind the exchange buffer (28 KiB): lockingbw < 10.49 kHz
 #endif
-__device__ __forceinline__ void c6_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 #define C6_FENCE __builtin_amdgcn_sched_barrier(0)
 __device__ __forceinline__ double2 c6_sq(const double2 a)
 {
@@ -131,16 +130,16 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
     c6_twiddle32(d, st1);
     C6_FENCE;
     // ---- exchange 1, a plane at a time ----
-    c6_bar(); // the buffer is free (previous transform's last reads / the fold)
+    jd_lds_barrier(); // the buffer is free (previous transform's last reads / the fold)
 #pragma unroll
     for (int s = 0; s < 32; s++) xch[c6_k(s) * 512 + ((c6_k(s) & 1) ? e1w1 : e1w0)] = d.r[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = xch[(m < 31 ? e1r + 16 * m : e1rw)];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 32; s++) xch[c6_k(s) * 512 + ((c6_k(s) & 1) ? e1w1 : e1w0)] = d.i[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = xch[(m < 31 ? e1r + 16 * m : e1rw)];
     C6_FENCE;
@@ -149,16 +148,16 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
     c6_twiddle32(d, st2);
     C6_FENCE;
     // ---- exchange 2 ----
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 32; s++) xch[e2w + (c6_k(s) & 15) * 32 + (c6_k(s) >> 4) * 8208] = d.r[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = xch[e2r + (m & 15) * 513 + (m >> 4) * 8208]; // slot m = n3 + 16 k2hi
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 32; s++) xch[e2w + (c6_k(s) & 15) * 32 + (c6_k(s) >> 4) * 8208] = d.i[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = xch[e2r + (m & 15) * 513 + (m >> 4) * 8208];
     C6_FENCE;
@@ -200,16 +199,16 @@ __device__ __forceinline__ void wg_fft13_e32(CV<32> &d, double *xch, const doubl
     c6_twiddle32(d, st1);
     C6_FENCE;
     // ---- exchange 1, a plane at a time ----
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 32; s++) (xch + c6_k(s) * 256)[t] = d.r[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = (xch + (m >> 4) * 4096 + (m & 15) * 16)[e1r];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 32; s++) (xch + c6_k(s) * 256)[t] = d.i[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = (xch + (m >> 4) * 4096 + (m & 15) * 16)[e1r];
     C6_FENCE;
@@ -227,16 +226,16 @@ __device__ __forceinline__ void wg_fft13_e32(CV<32> &d, double *xch, const doubl
         C6_FENCE;
     }
     // ---- exchange 2: slot 16 g + k2 -> L = (k1a + 16 g) + 32 k2 + 513 n3; reader t3 = k1 + 32 k2lo, slot 16 h + n3 ----
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 32; s++) (xch + (s >> 4) * 16 + (s & 15) * 32)[e2w] = d.r[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = (xch + (m >> 4) * 256 + (m & 15) * 513)[t];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 32; s++) (xch + (s >> 4) * 16 + (s & 15) * 32)[e2w] = d.i[s];
-    c6_bar();
+    jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = (xch + (m >> 4) * 256 + (m & 15) * 513)[t];
     C6_FENCE;
@@ -348,9 +347,9 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             double *wt = persistent ? xch + XCH : xch;
             if (!persistent || startbin != tab_startbin)
             {
-                c6_bar();
+                jd_lds_barrier();
                 c6_build_window(wt, startbin, t, NT);
-                c6_bar();
+                jd_lds_barrier();
                 if (persistent) tab_startbin = startbin; // (a scalar register: startbin is one)
             }
 #pragma unroll
@@ -367,7 +366,7 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
                 }
                 C6_FENCE;
             }
-            if (!persistent) c6_bar(); // the next transform's exchanges reuse the buffer
+            if (!persistent) jd_lds_barrier(); // the next transform's exchanges reuse the buffer
         }
         else
         {
@@ -399,7 +398,7 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         // stores take a wavefront 7-8 us to issue), and no registers are free to request any of it a transform earlier (the transform needs
         // 196 of 256; holding 20 y values across it made it slower than the wait they save, touching the lines with one-dword loads cost more
         // issue time than it saved).  What is here now: 13.2 -> 12.4 ms per 65 536 estimates.
-        c6_bar(); // the exchange buffer is free: it receives a copy of y for the fold below
+        jd_lds_barrier(); // the exchange buffer is free: it receives a copy of y for the fold below
         // smooth with fftshift: y[i] = y[i]*0.9 + 0.1*10*log10(fmax(abs(out[i]),1)), out[i] = X[i ^ N/2]
         // all 32 old y values are requested before the log10s (their registers: the imaginary plane, dead once only |X|^2 is kept); y and the
         // ring are streamed (read once, written once per estimate): non-temporal accesses
@@ -445,7 +444,7 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
                 if ((s & 3) == 3) C6_FENCE; // four slots at a time: the scheduler may not gather the loads at either end again
             }
             C6_TRACE(4);
-            c6_bar(); // the fold reads the LDS copy; the stores to y[] drain in the background
+            jd_lds_barrier(); // the fold reads the LDS copy; the stores to y[] drain in the background
             C6_TRACE(5);
         }
         C6_TRACE(6);
@@ -514,7 +513,7 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             c6_wave_argmax(bv, bi);
             if ((t & 63) == 0) { red_val[t >> 6] = bv; red_idx[t >> 6] = bi; }
             C6_TRACE(8);
-            c6_bar();
+            jd_lds_barrier();
             bv = red_val[0]; bi = red_idx[0];
 #pragma unroll
             for (int w = 1; w < NT / 64; w++)

@@ -14,6 +14,7 @@
 // written in reference order, every one of those reads was waited for on the spot, ~8 memory round trips per sample.
 #pragma once
 #include "jaero_device.h"
+#include "demod_stages.h"
 
 // dynamic LDS of k_msk_samples<FIRN, LDSN, ...>: the two rings [LDSN][64] and the taps
 template <int FIRN, int LDSN>
@@ -69,20 +70,7 @@ __global__ __launch_bounds__(64) void k_msk_samples(const JGeom g, const JPtrs p
     double2 *__restrict__ dly_ring = p.dly + (size_t)grp * dly_len * 64 + lane;
     double *__restrict__ d8_ring = p.dly8 + (size_t)grp * d8_len * 64 + lane;
 
-    {
-        const double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++)
-        {
-            lre[k * 64 + lane] = fs[(size_t)k * 64];
-            lim[k * 64 + lane] = fs[(size_t)(FIRN + k) * 64];
-        }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++)
-        {
-            tre[j] = fs[(size_t)(LDSN + j) * 64];
-            tim[j] = fs[(size_t)(FIRN + LDSN + j) * 64];
-        }
-    }
+    stg_hist_load<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
     int fir_slot = fir_slot0, dly_slot = dly_slot0, d8_slot = d8_slot0; // wave-uniform ring phases
     const double agc_len_d = (double)g.agc_len, eb_len_d = (double)g.ebno_len;
 
@@ -143,72 +131,13 @@ __global__ __launch_bounds__(64) void k_msk_samples(const JGeom g, const JPtrs p
 
         // mix + matched filter (:369-370): this sample's output was evaluated one iteration ago; x[n] is pushed at the end
         double sre = ycur_re, sim = ycur_im;
-        const double dabval = sqrt(sre * sre + sim * sim);
-
-        // MSKEbNoMeasure::Update (DSP.cpp:493-505)
-        if (EBNO)
-        {
-            const double sq = dabval * dabval;
-            eb_e2sum = eb_e2sum - e2_old; eb_e2sum = eb_e2sum + fabs(sq);
-            eb_esum = eb_esum - e_old; eb_esum = eb_esum + fabs(dabval);
-            if (i >= n - JD_EBNO_TAIL) // wave-uniform; see JD_EBNO_TAIL
-            {
-                const double e2val = eb_e2sum / eb_len_d, mean = eb_esum / eb_len_d;
-                const double var = e2val - (mean * mean);
-                const double alpha = sqrt(2.0) / mean;
-                double tebno = 10.0 * (log10(2.0) - log10(((var * alpha * alpha) - 0.0085))) - 5.0;
-                if (isnan(tebno)) tebno = 50;
-                if (tebno > 50.0) tebno = 50;
-                eb_ebno = eb_ebno * 0.8 + 0.2 * tebno;
-            }
-        }
-
-        // AGC + clip (:378-382)
-        {
-            double *ap = win + (size_t)agc_pos * 64;
-            agc_sum = agc_sum - agc_old;
-            agc_sum = agc_sum + fabs(dabval);
-            *ap = fabs(dabval); // the one store: the EbNo meter above pushed the same value
-            agc_pos++; if (agc_pos >= g.win_len) agc_pos = 0;
-        }
-        double gain = jd_div(1.414213562, fmax(agc_sum / agc_len_d, 0.000001));
-        gain = fmax(gain, 0.000001);
-        sre *= gain; sim *= gain;
-        const double abval = sqrt(sre * sre + sim * sim);
-        if (abval > 2.84) { const double k = jd_div(2.84, abval); sre = k * sre; sim = k * sim; }
-
-        // pt_d = delayedsmpl.update_dont_touch(sig2) (:384): SPS-sample delay on a ring of SPS+1
-        {
-            dly_ring[(size_t)dly_slot * 64] = make_double2(sre, sim);
-            dly_slot++; if (dly_slot >= dly_len) dly_slot = 0; // ptd = the entry at the new dly_slot, requested one iteration ago
-        }
-        double q_re = sre, q_im = ptd.y; // pt_msk
-
-        // symbol timing (:387-405)
-        double st_eta;
-        {
-            const double x0 = jd_hypot(q_re, q_im);
-            double y = 0;
-            y += res_x2 * g.res_b2; y += res_x1 * g.res_b1; y += x0 * g.res_b0;
-            y -= res_y2 * g.res_a2; y -= res_y1 * g.res_a1;
-            res_x2 = res_x1; res_x1 = x0; res_y2 = res_y1; res_y1 = y;
-            st_eta = y;
-        }
-        {
-            // Delay<double>(SPS/2): integer delay, weighting 0 -> returns x[n-SPS/2] (d8out, requested one iteration ago)
-            d8_ring[(size_t)d8_slot * 64] = st_eta;
-            d8_slot++; if (d8_slot >= d8_len) d8_slot = 0;
-        }
-        {
-            const double2 so = c_st;
-            const double m_re = st_eta, m_im = -d8out;
-            const double o_re = so.x * m_re - so.y * m_im;
-            const double o_im = so.x * m_im + so.y * m_re;
-            const double st_angle_error = jd_atan2(o_im, o_re, atl);
-            const double weighting = fabs(jd_tanh(st_angle_error));
-            if (!dcd) jd_wt_advance_fraction(st_ptr, -(1.0 - weighting) * st_angle_error * (0.05 / 360.0));
-            else jd_wt_advance_fraction(st_ptr, -(1.0 - weighting) * st_angle_error * (0.003 / 360.0));
-        }
+        // MSKEbNoMeasure::Update, AGC + clip (:375-382)
+        stg_msk_meter_agc_clip<EBNO>(sre, sim, agc_old, e_old, e2_old, i >= n - JD_EBNO_TAIL /* wave-uniform */, eb_len_d, agc_len_d, eb_esum, eb_e2sum,
+                                     eb_ebno, agc_sum, win, agc_pos, g.win_len);
+        // the SPS-sample delayed arm and symbol timing (:384-405); ptd and d8out were requested one iteration ago
+        double q_re, q_im; // pt_msk
+        stg_msk_timing(g, sre, sim, ptd, d8out, c_st, dcd, atl, dly_ring, dly_slot, dly_len, d8_ring, d8_slot, d8_len, res_x1, res_x2, res_y1, res_y2,
+                       st_ptr, q_re, q_im);
 
         double frac;
         if (jd_wt_passed(st_last, st_ptr, st_step, g.ee, frac))
@@ -218,79 +147,9 @@ __global__ __launch_bounds__(64) void k_msk_samples(const JGeom g, const JPtrs p
             int dn = dt_pos + 1; if (dn >= g.dt_len) dn = 0;
             const double2 dt_old = dt_ring[dn]; // dt_len = SPS/2 + 1 > 1
             const double ms_old = msema_ring[msema_pos];
-            // carrier tracking (:411-426)
-            const double ct_xt = jd_tanh(sim) * sre;
-            const double ct_xt_d = jd_tanh(ptd.x) * ptd.y;
-            double ct_ec = ct_xt_d - ct_xt;
-            if (ct_ec > M_PI) ct_ec = M_PI;
-            if (ct_ec < -M_PI) ct_ec = -M_PI;
-            if (ct_ec > M_PI_2) ct_ec = M_PI_2;
-            if (ct_ec < -M_PI_2) ct_ec = -M_PI_2;
-            double carrier_aggression = 12.0 * g.correctionfactor;
-            if (dcd) carrier_aggression = 8.0 * g.correctionfactor;
-            jd_wt_inc_phase_deg(m2_ptr, carrier_aggression * 1.0 * ct_ec);
-            jd_wt_setfreq(m2_freq, m2_step, (carrier_aggression * 0.01 * ct_ec) + m2_freq, samplerate);
-
-            {
-                const double v = ct_ec / 2.0;
-                double *mp = marg_ring + marg_pos;
-                marg_sum = marg_sum - marg_old; marg_sum = marg_sum + v; *mp = v;
-                marg_pos++; if (marg_pos >= g.marg_len) marg_pos = 0;
-            }
-            const double marg_val = marg_sum / ((double)g.marg_len);
-            {
-                dt_ring[dt_pos] = make_double2(q_re, q_im);
-                dt_pos++; if (dt_pos >= g.dt_len) dt_pos = 0;
-                q_re = dt_old.x; q_im = dt_old.y;
-            }
-            {
-                const double cr = cos(marg_val), sr = sin(marg_val);
-                const double nr = q_re * cr - q_im * sr;
-                const double ni = q_re * sr + q_im * cr;
-                q_re = nr; q_im = ni;
-            }
-            {
-                const double tda = (fabs(q_re * 0.75) - 1.0), tdb = (fabs(q_im * 0.75) - 1.0);
-                const double e = (tda * tda) + (tdb * tdb);
-                double *ep = msema_ring + msema_pos;
-                msema_sum = msema_sum - ms_old; msema_sum = msema_sum + fabs(e); *ep = fabs(e);
-                msema_pos++; if (msema_pos >= g.msema_len) msema_pos = 0;
-                mse = msema_sum / ((double)g.msema_len);
-            }
-            if (CAPSYM)
-            {
-                if (sym_cnt < g.sym_cap)
-                {
-                    double *sp = p.sym + ((size_t)ch * g.sym_cap + sym_cnt) * 3;
-                    sp[0] = q_re; sp[1] = q_im; sp[2] = mse;
-                    sym_cnt++;
-                }
-                else overflow |= 2;
-            }
-            // soft differential decode + demap (:450-469, DSP.cpp:531-563)
-            int b0, b1;
-            {
-                double soft_in = q_im, r;
-                if (soft_in < 0 && diff_last < 0) r = diff_last;
-                else if (soft_in > 0 && diff_last > 0) r = -diff_last;
-                else r = fabs(diff_last);
-                diff_last = soft_in;
-                b0 = jd_softbit((r) * 127.0 + 128.0);
-                soft_in = q_re;
-                if (soft_in < 0 && diff_last < 0) r = diff_last;
-                else if (soft_in > 0 && diff_last > 0) r = -diff_last;
-                else r = fabs(diff_last);
-                diff_last = soft_in;
-                r = -r;
-                b1 = jd_softbit((r) * 127.0 + 128.0);
-            }
-            if (soft_cnt + 2 <= g.soft_cap)
-            {
-                soft[soft_cnt] = (int16_t)b0;
-                soft[soft_cnt + 1] = (int16_t)b1;
-                soft_cnt += 2;
-            }
-            else overflow |= 1;
+            const double ct_ec = stg_msk_carrier(g, sre, sim, ptd, dcd, samplerate, m2_ptr, m2_freq, m2_step);
+            stg_msk_output_half<CAPSYM>(g, p, ch, ct_ec, q_re, q_im, marg_old, dt_old, ms_old, marg_ring, dt_ring, msema_ring, soft, marg_sum, marg_pos,
+                                        dt_pos, msema_sum, msema_pos, mse, diff_last, soft_cnt, sym_cnt, overflow);
         }
 
         // push x[n] (mixed with the carrier phase this sample started with) and evaluate the filter for n+1
@@ -312,10 +171,7 @@ __global__ __launch_bounds__(64) void k_msk_samples(const JGeom g, const JPtrs p
 
         jd_wt_next(m2_ptr, m2_step);
         jd_wt_next(mc_ptr, mc_step);
-        if (st_step < 0) st_step = 0;
-        st_last = st_ptr;
-        st_ptr += st_step;
-        while (((int)st_ptr) >= JD_WTSIZE) st_ptr -= JD_WTSIZE;
+        jd_wt_next_symbol(st_ptr, st_step, st_last);
     }
 
     LDF(S_M2_PTR) = m2_ptr; LDF(S_M2_STEP) = m2_step; LDF(S_M2_FREQ) = m2_freq;
@@ -329,18 +185,5 @@ __global__ __launch_bounds__(64) void k_msk_samples(const JGeom g, const JPtrs p
     LDI(I_AGC_POS) = agc_pos; LDI(I_BB_PTR) = bb_ptr; LDI(I_COARSE_CNT) = coarse_cnt;
     LDI(I_MARG_POS) = marg_pos; LDI(I_DT_POS) = dt_pos; LDI(I_MSEMA_POS) = msema_pos;
     LDI(I_SOFT_CNT) = soft_cnt; LDI(I_SYM_CNT) = sym_cnt; LDI(I_OVERFLOW) = overflow;
-    {
-        double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++)
-        {
-            fs[(size_t)k * 64] = lre[k * 64 + lane];
-            fs[(size_t)(FIRN + k) * 64] = lim[k * 64 + lane];
-        }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++)
-        {
-            fs[(size_t)(LDSN + j) * 64] = tre[j];
-            fs[(size_t)(FIRN + LDSN + j) * 64] = tim[j];
-        }
-    }
+    stg_hist_save<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
 }

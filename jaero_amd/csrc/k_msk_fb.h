@@ -24,7 +24,8 @@
 #pragma once
 #include <type_traits>
 #include "jaero_device.h"
-#include "k_oqpsk_fb.h" // fb_barrier
+#include "demod_stages.h"
+#include "k_oqpsk_fb.h" // FB_TRACE
 
 #define MFB_LDSN 36  // one pair per workgroup (small banks): 36 history entries of each arm in LDS, 44 in registers
 // ... of which the MFB1_TB oldest in the BACK half's (round 5): in a small bank the halves sit on different SIMDs and the front half is the long pole
@@ -184,7 +185,8 @@ __device__ __forceinline__ void mfb_front(const JGeom &g, const JPtrs &p, const 
     double *__restrict__ win = p.win + (size_t)grp * g.win_len * 64 + lane;
     auto wslot = [&](int pos, int lag) { const int q = pos - lag; return q < 0 ? q + g.win_len : q; };
 
-    // coarse ring fill, four entries at a time as one complete 64-byte sector (see k_oqpsk_fb.h)
+    // coarse ring fill, four entries at a time as one complete 64-byte sector: StgSectorQueue (demod_stages.h) written out.  As the struct it
+    // cost two of this kernel's instantiations a spilled queue entry inside the front half's loop (profiles/stages_refactor_isa.md).
     double2 cq1 = make_double2(0.0, 0.0), cq2 = cq1, cq3 = cq1;
     int cq_n = 0;
     auto ring_fill = [&](const double2 v) __attribute__((always_inline)) {
@@ -213,21 +215,8 @@ __device__ __forceinline__ void mfb_front(const JGeom &g, const JPtrs &p, const 
     };
 
     double *lre = L.lre, *lim = L.lim, *ltap = L.ltap;
-    {
-        const double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++)
-        {
-            lre[k * 64 + lane] = fs[(size_t)k * 64];
-            lim[k * 64 + lane] = fs[(size_t)(FIRN + k) * 64];
-        }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++)
-        {
-            tre[j] = fs[(size_t)(LDSN + j) * 64];
-            tim[j] = fs[(size_t)(FIRN + LDSN + j) * 64];
-        }
-        for (int k = lane; k < FIRN; k += 64) ltap[k] = p.taps2[k];
-    }
+    stg_hist_load<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
+    for (int k = lane; k < FIRN; k += 64) ltap[k] = p.taps2[k];
     int fir_slot = fir_slot0; // wave-uniform: LDS slot holding the oldest LDS entry, overwritten by the next input
     int tapz;                 // a zero in a vector register: tap reads become `register + immediate offset` (mfb_fir_continue_v)
     asm volatile("v_mov_b32 %0, 0" : "=v"(tapz));
@@ -268,36 +257,9 @@ __device__ __forceinline__ void mfb_front(const JGeom &g, const JPtrs &p, const 
 
     // MSKEbNoMeasure::Update (DSP.cpp:493-505), AGC + clip (mskdemodulator.cpp:378-382) for one sample; hands {sre, sim} to the back half
     auto front_sample = [&](double sre, double sim, double agc_old, double e_old, int j, int buf) __attribute__((always_inline)) {
-        const double dabval = sqrt(sre * sre + sim * sim);
-        if (EBNO)
-        {
-            const double sq = dabval * dabval;
-            const double e2_old = e_old * e_old; // E2's buffer holds fabs(sig * sig) of the same samples (MovingAverage::Update, DSP.cpp:408-416)
-            eb_e2sum = eb_e2sum - e2_old; eb_e2sum = eb_e2sum + fabs(sq);
-            eb_esum = eb_esum - e_old; eb_esum = eb_esum + fabs(dabval);
-            if (j >= n - JD_EBNO_TAIL) // wave-uniform; see JD_EBNO_TAIL
-            {
-                const double e2val = eb_e2sum / eb_len_d, mean = eb_esum / eb_len_d;
-                const double var = e2val - (mean * mean);
-                const double alpha = sqrt(2.0) / mean;
-                double tebno = 10.0 * (log10(2.0) - log10(((var * alpha * alpha) - 0.0085))) - 5.0;
-                if (isnan(tebno)) tebno = 50;
-                if (tebno > 50.0) tebno = 50;
-                eb_ebno = eb_ebno * 0.8 + 0.2 * tebno;
-            }
-        }
-        {
-            double *ap = win + (size_t)agc_pos * 64;
-            agc_sum = agc_sum - agc_old;
-            agc_sum = agc_sum + fabs(dabval);
-            *ap = fabs(dabval); // the one store: the EbNo meter above pushed the same value
-            agc_pos++; if (agc_pos >= g.win_len) agc_pos = 0;
-        }
-        double gain = jd_div(1.414213562, fmax(agc_sum / agc_len_d, 0.000001));
-        gain = fmax(gain, 0.000001);
-        sre *= gain; sim *= gain;
-        const double abval = sqrt(sre * sre + sim * sim);
-        if (abval > 2.84) { const double k = jd_div(2.84, abval); sre = k * sre; sim = k * sim; }
+        // e_old * e_old: E2's buffer holds the squares of E's entries (MovingAverage::Update, DSP.cpp:408-416); unused, and gone, without EBNO
+        stg_msk_meter_agc_clip<EBNO>(sre, sim, agc_old, e_old, e_old * e_old, j >= n - JD_EBNO_TAIL /* wave-uniform */, eb_len_d, agc_len_d, eb_esum,
+                                     eb_e2sum, eb_ebno, agc_sum, win, agc_pos, g.win_len);
         double *d = L.data + buf * 2 * 64 + lane;
         d[0] = sre; d[64] = sim;
     };
@@ -309,7 +271,7 @@ __device__ __forceinline__ void mfb_front(const JGeom &g, const JPtrs &p, const 
     short nx_pcm = (live && n > 0) ? pcm[ch] : (short)0;
     double2 nx_cc = cis[jd_cisidx(mc_ptr)];
 
-    if constexpr (TB > 0) fb_barrier(); // the back half has published its partial sums for samples 0 and 1
+    if constexpr (TB > 0) jd_lds_barrier(); // the back half has published its partial sums for samples 0 and 1
     // prologue: sample 0's filter output comes from the saved history
     if (nB > 0)
     {
@@ -319,7 +281,7 @@ __device__ __forceinline__ void mfb_front(const JGeom &g, const JPtrs &p, const 
         r1_agc = win[(size_t)wslot(agc_pos, g.agc_len) * 64];
         if (EBNO) r1_e = win[(size_t)wslot(agc_pos, g.ebno_len) * 64];
     }
-    fb_barrier();
+    jd_lds_barrier();
 
     FB_TRACE_DECL; // phase trace build (k_oqpsk_fb.h): empty in the product
     for (int i = 0; i < nB; i++)
@@ -380,7 +342,7 @@ __device__ __forceinline__ void mfb_front(const JGeom &g, const JPtrs &p, const 
             r1_agc = r2_agc; r1_e = r2_e;
             FB_TRACE(4); // EbNo sums, AGC, clip, mailbox
         }
-        fb_barrier();
+        jd_lds_barrier();
     }
     FB_TRACE_FLUSH(0, nB);
     if (only_a_last) // the coarse estimate runs now; the next launch resumes with this sample's B-part
@@ -395,20 +357,7 @@ __device__ __forceinline__ void mfb_front(const JGeom &g, const JPtrs &p, const 
     LDF(S_AGC_SUM) = agc_sum;
     LDF(S_EB_ESUM) = eb_esum; LDF(S_EB_E2SUM) = eb_e2sum; LDF(S_EB_EBNO) = eb_ebno;
     LDI(I_AGC_POS) = agc_pos; LDI(I_BB_PTR) = bb_ptr; LDI(I_COARSE_CNT) = coarse_cnt;
-    {
-        double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++)
-        {
-            fs[(size_t)k * 64] = lre[k * 64 + lane];
-            fs[(size_t)(FIRN + k) * 64] = lim[k * 64 + lane];
-        }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++)
-        {
-            fs[(size_t)(LDSN + j) * 64] = tre[j];
-            fs[(size_t)(FIRN + LDSN + j) * 64] = tim[j];
-        }
-    }
+    stg_hist_save<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- back half
@@ -526,6 +475,7 @@ __device__ __forceinline__ void mfb_back(const JGeom &g, const JPtrs &p, const M
         need_px = false;
     };
     auto output_half = [&]() __attribute__((always_inline)) {
+        // stg_msk_output_half (demod_stages.h) written out: as the call it cost the 160-tap kernel one more spilled value (profiles/stages_refactor_isa.md)
         const double ct_ec = pd_ec;
         double q_re = pd_re, q_im = pd_im;
         {
@@ -565,22 +515,8 @@ __device__ __forceinline__ void mfb_back(const JGeom &g, const JPtrs &p, const M
             else overflow |= 2;
         }
         // soft differential decode + demap (:450-469, DSP.cpp:531-563)
-        int b0, b1;
-        {
-            double soft_in = q_im, r;
-            if (soft_in < 0 && diff_last < 0) r = diff_last;
-            else if (soft_in > 0 && diff_last > 0) r = -diff_last;
-            else r = fabs(diff_last);
-            diff_last = soft_in;
-            b0 = jd_softbit((r) * 127.0 + 128.0);
-            soft_in = q_re;
-            if (soft_in < 0 && diff_last < 0) r = diff_last;
-            else if (soft_in > 0 && diff_last > 0) r = -diff_last;
-            else r = fabs(diff_last);
-            diff_last = soft_in;
-            r = -r;
-            b1 = jd_softbit((r) * 127.0 + 128.0);
-        }
+        const int b0 = jd_softbit((jd_diff_soft(q_im, diff_last)) * 127.0 + 128.0);
+        const int b1 = jd_softbit((-jd_diff_soft(q_re, diff_last)) * 127.0 + 128.0);
         if (soft_cnt + 2 <= g.soft_cap)
         {
             soft[soft_cnt] = (int16_t)b0;
@@ -595,8 +531,8 @@ __device__ __forceinline__ void mfb_back(const JGeom &g, const JPtrs &p, const M
     double2 nx_cst = cis[jd_cisidx(st_ptr)];
     double2 nx_ptd = dly_ring[(size_t)ring_next(dly_slot, dly_len) * 64]; // slot read after this sample's write to dly_slot
     double nx_d8 = d8_ring[(size_t)ring_next(d8_slot, d8_len) * 64];
-    if constexpr (TB > 0) fb_barrier(); // partial sums of samples 0 and 1 published; the front half forms sample 0 now
-    fb_barrier();
+    if constexpr (TB > 0) jd_lds_barrier(); // partial sums of samples 0 and 1 published; the front half forms sample 0 now
+    jd_lds_barrier();
 
     FB_TRACE_DECL;
     for (int i = 0; i < nB; i++)
@@ -630,38 +566,10 @@ __device__ __forceinline__ void mfb_back(const JGeom &g, const JPtrs &p, const M
         }
 
         FB_TRACE(1); // mailbox read, this half's share of the matched filter (the TB oldest terms), ring requests
-        // pt_d = delayedsmpl.update_dont_touch(sig2) (:384): SPS-sample delay on a ring of SPS+1
-        {
-            dly_ring[(size_t)dly_slot * 64] = make_double2(sre, sim);
-            dly_slot++; if (dly_slot >= dly_len) dly_slot = 0; // ptd = the entry at the new dly_slot, requested one iteration ago
-        }
-        double q_re = sre, q_im = ptd.y; // pt_msk
-
-        // symbol timing (:387-405)
-        double st_eta;
-        {
-            const double x0 = jd_hypot(q_re, q_im);
-            double y = 0;
-            y += res_x2 * g.res_b2; y += res_x1 * g.res_b1; y += x0 * g.res_b0;
-            y -= res_y2 * g.res_a2; y -= res_y1 * g.res_a1;
-            res_x2 = res_x1; res_x1 = x0; res_y2 = res_y1; res_y1 = y;
-            st_eta = y;
-        }
-        {
-            // Delay<double>(SPS/2): integer delay, weighting 0 -> returns x[n-SPS/2] (d8out, requested one iteration ago)
-            d8_ring[(size_t)d8_slot * 64] = st_eta;
-            d8_slot++; if (d8_slot >= d8_len) d8_slot = 0;
-        }
-        {
-            const double2 so = c_st;
-            const double m_re = st_eta, m_im = -d8out;
-            const double o_re = so.x * m_re - so.y * m_im;
-            const double o_im = so.x * m_im + so.y * m_re;
-            const double st_angle_error = jd_atan2(o_im, o_re, atl);
-            const double weighting = fabs(jd_tanh(st_angle_error));
-            if (!dcd) jd_wt_advance_fraction(st_ptr, -(1.0 - weighting) * st_angle_error * (0.05 / 360.0));
-            else jd_wt_advance_fraction(st_ptr, -(1.0 - weighting) * st_angle_error * (0.003 / 360.0));
-        }
+        // the SPS-sample delayed arm and symbol timing (:384-405); ptd and d8out were requested one iteration ago
+        double q_re, q_im; // pt_msk
+        stg_msk_timing(g, sre, sim, ptd, d8out, c_st, dcd, atl, dly_ring, dly_slot, dly_len, d8_ring, d8_slot, d8_len, res_x1, res_x2, res_y1, res_y2,
+                       st_ptr, q_re, q_im);
 
         FB_TRACE(2); // symbol timing: hypot, resonator, atan2, tanh, oscillator nudge
         if (need_px) request_px(); // for the symbol queued in the previous sample
@@ -672,30 +580,17 @@ __device__ __forceinline__ void mfb_back(const JGeom &g, const JPtrs &p, const M
         if (inst)
         {
             // carrier tracking (:411-426): the half of the symbol that feeds back
-            const double ct_xt = jd_tanh(sim) * sre;
-            const double ct_xt_d = jd_tanh(ptd.x) * ptd.y;
-            double ct_ec = ct_xt_d - ct_xt;
-            if (ct_ec > M_PI) ct_ec = M_PI;
-            if (ct_ec < -M_PI) ct_ec = -M_PI;
-            if (ct_ec > M_PI_2) ct_ec = M_PI_2;
-            if (ct_ec < -M_PI_2) ct_ec = -M_PI_2;
-            double carrier_aggression = 12.0 * g.correctionfactor;
-            if (dcd) carrier_aggression = 8.0 * g.correctionfactor;
-            jd_wt_inc_phase_deg(m2_ptr, carrier_aggression * 1.0 * ct_ec);
-            jd_wt_setfreq(m2_freq, m2_step, (carrier_aggression * 0.01 * ct_ec) + m2_freq, samplerate);
+            const double ct_ec = stg_msk_carrier(g, sre, sim, ptd, dcd, samplerate, m2_ptr, m2_freq, m2_step);
             pend = true; need_px = true; pd_ec = ct_ec; pd_re = q_re; pd_im = q_im;
         }
 
         // advance the NCOs (:480-483) and hand the next sample's carrier table index to the front half
         jd_wt_next(m2_ptr, m2_step);
         L.idx[((i + 1) & 1) * 64 + lane] = jd_cisidx(m2_ptr);
-        if (st_step < 0) st_step = 0;
-        st_last = st_ptr;
-        st_ptr += st_step;
-        while (((int)st_ptr) >= JD_WTSIZE) st_ptr -= JD_WTSIZE;
+        jd_wt_next_symbol(st_ptr, st_step, st_last);
         nx_cst = cis[jd_cisidx(st_ptr)]; // the symbol NCO's table value for the next sample: in flight across the barrier
         FB_TRACE(4); // instant block (two tanh, carrier phase and frequency), oscillators, hand-back
-        fb_barrier();
+        jd_lds_barrier();
     }
     FB_TRACE_FLUSH(1, nB);
     if (need_px) request_px();
@@ -744,7 +639,7 @@ __global__ __launch_bounds__(PAIRS * 128) void k_msk_fb(const JGeom g, const JPt
     if (grp >= g.ngroups)
     {
         const int nB = n - (only_a_last ? 1 : 0);
-        for (int i = 0; i <= nB + (TB > 0 ? 1 : 0); i++) fb_barrier();
+        for (int i = 0; i <= nB + (TB > 0 ? 1 : 0); i++) jd_lds_barrier();
         return;
     }
     if (back) mfb_back<CAPSYM, FIRN, LDSN, TB>(g, p, L, n, only_a_last, dly_slot0, d8_slot0, grp, lane);

@@ -1,7 +1,7 @@
 // k_oqpsk_fb.h -- sample-loop kernel for the continuous OQPSK demodulator (10.5 kbps; 8400 bps with PRE8400), front / back wavefront pairs.
 //
-// Same arithmetic as k_oqpsk.h (OqpskDemodulator::writeData's per-sample loop, JAERO/oqpskdemodulator.cpp:388-605, fb > 8400), one
-// channel per lane, but the per-sample work of 64 channels is shared by TWO wavefronts that run concurrently:
+// OqpskDemodulator::writeData's per-sample loop (JAERO/oqpskdemodulator.cpp:388-605), one channel per lane, the per-sample work of 64
+// channels shared by TWO wavefronts that run concurrently (the stages other kernels run too are in demod_stages.h):
 //
 //   F ("front"):  K1 PCM -> double, K3 coarse ring fill (mixer_center), K2 mix with the carrier NCO value the back half hands over,
 //                 K6 RRC matched filter (history in LDS + registers), K7 EbNo meter, K8 AGC + clip.   Owns every HBM stream
@@ -15,13 +15,14 @@
 // B runs sample n, F forms x[n], pushes it and produces the AGC'd, clipped sample n+1.  One s_barrier per sample, two mailboxes in
 // LDS (double buffered): B -> F the carrier table index of the next sample, F -> B {sre, sim, |.|} of the next sample.
 //
-// Why it pays: a wavefront issues one instruction every ~4 cycles; the single-wavefront kernel is ~1700 instructions per sample, of which
-// fewer than half are fp64 VALU work.  It fills a SIMD's register file (512) and 40 KiB of LDS, so nothing else can run beside it.
+// Why it pays: a wavefront issues one instruction every ~4 cycles; the single-wavefront kernel this one replaced (k_oqpsk.h, which left the
+// library in round 3) was ~1700 instructions per sample, fewer than half of them fp64 VALU work.  It filled a SIMD's register file (512) and
+// 40 KiB of LDS, so nothing else could run beside it.
 // Split, each half fits 256 registers, only F needs LDS, and a 512-thread workgroup (four pairs) puts one F and one B wavefront on
 // every SIMD (waves w and w+4 of a workgroup share a SIMD): the halves' instruction streams interleave, and the serial chain of
 // a channel is spread over two instruction streams.  Small banks use one pair per workgroup (two SIMDs per 64 channels).
 //
-// Second change against k_oqpsk.h: the OUTPUT half of the symbol block (averages, residual rotation, MSE, soft bits -- nothing
+// Second change against that kernel: the OUTPUT half of the symbol block (averages, residual rotation, MSE, soft bits -- nothing
 // of it feeds back into the signal path) is queued per lane and run for all lanes together every FB_DEFER samples: with channels
 // that are not symbol-synchronous some lane is at a symbol instant in nearly every sample, and the whole block used to run each
 // time for ~5 % of the lanes.  The feedback half (tanh detector, loop filter, carrier NCO) still runs at the instant.
@@ -29,6 +30,7 @@
 // the IEEE quotient; fmod(x, 360) takes the exact shortcut for |x| < 720.
 #pragma once
 #include "jaero_device.h"
+#include "demod_stages.h"
 
 // The queue is ONE symbol deep, so the batch interval must not exceed the distance between two symbols of a lane (48 000 / 5 250 = 9.14
 // samples at 10.5 kbps, 11.4 at 8400 bps): with 16 (rounds 2-4) a lane's next symbol arrived before the batch in 43 % of the cases, took the
@@ -76,14 +78,8 @@ struct FbLds
 template <int LDSN>
 constexpr int fb_pair_doubles() { return 2 * LDSN * 64 + 2 * 3 * 64 + 64; }
 
-// one LDS-only barrier per sample; waiting for the partner half alone through sequence words in LDS measured slower (13.9 against 12.8 ms)
-#define FB_SYNC(L) fb_barrier()
-__device__ __forceinline__ void fb_barrier()
-{
-    // LDS traffic of this wavefront done, then the workgroup barrier.  NOT __syncthreads(): that also drains vmcnt, i.e. every
-    // HBM row requested ahead for the next sample.
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+// One LDS-only barrier per sample (jd_lds_barrier); waiting for the partner half alone through sequence words in LDS measured slower (13.9
+// against 12.8 ms).
 
 // ------------------------------------------------------------------------------------------------------------------ front half
 // PRE8400 (fb == 8400, k_pre8400.h): there is no matched filter in the loop -- the sample is the prefiltered complex value times the
@@ -106,7 +102,7 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
     double mc_ptr = LDF(S_MC_PTR), mc_step = LDF(S_MC_STEP);
     double agc_sum = LDF(S_AGC_SUM);
     double eb_esum = LDF(S_EB_ESUM), eb_e2sum = LDF(S_EB_E2SUM), eb_ebno = LDF(S_EB_EBNO);
-    int agc_pos = LDI(I_AGC_POS), bb_ptr = LDI(I_BB_PTR), coarse_cnt = LDI(I_COARSE_CNT);
+    int agc_pos = LDI(I_AGC_POS), coarse_cnt = LDI(I_COARSE_CNT);
     int agc_hold = LDI(I_AGC_HOLD); // samples for which the AGC's buffer (re-created by setSettings: zeros) still returns zeros while the meter's keeps its values
     const int flags = LDI(I_FLAGS);
     const int nfft_mask = g.nfft - 1;
@@ -116,53 +112,10 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
     double *__restrict__ win = p.win + (size_t)grp * g.win_len * 64 + lane;
     auto wslot = [&](int pos, int lag) { const int q = pos - lag; return q < 0 ? q + g.win_len : q; };
 
-    // Coarse ring fill, four entries at a time: a 16-byte store into the per-channel ring is a quarter of a 64-byte sector; issued one per
-    // sample (3.5 us apart) every one of them cost the L2 a sector fill from HBM plus a sector write (measured: 23 GB written and
-    // 15 GB of extra reads per 4096-sample launch for 4.3 GB of ring entries).  The last three entries wait in registers and go out with
-    // the fourth, back to back, as one complete sector; what is left at the end of the launch (at most three) goes out singly.
-    double2 cq1 = make_double2(0.0, 0.0), cq2 = cq1, cq3 = cq1;
-    int cq_n = 0; // entries waiting (they are the ring positions just below bb_ptr)
-    auto ring_fill = [&](const double2 v) __attribute__((always_inline)) {
-        if ((bb_ptr & 3) == 3)
-        {
-            double2 *dst = bbring + bb_ptr;
-            if (cq_n >= 3) dst[-3] = cq3;
-            if (cq_n >= 2) dst[-2] = cq2;
-            if (cq_n >= 1) dst[-1] = cq1;
-            dst[0] = v;
-            cq_n = 0;
-        }
-        else
-        {
-            cq3 = cq2; cq2 = cq1; cq1 = v;
-            cq_n++;
-        }
-        bb_ptr = (bb_ptr + 1) & nfft_mask;
-    };
-    auto ring_flush = [&]() __attribute__((always_inline)) {
-        double2 *dst = bbring + bb_ptr;
-        if (cq_n >= 3) dst[-3] = cq3;
-        if (cq_n >= 2) dst[-2] = cq2;
-        if (cq_n >= 1) dst[-1] = cq1;
-        cq_n = 0;
-    };
+    StgSectorQueue cq(LDI(I_BB_PTR)); // coarse ring fill, four entries at a time as one complete 64-byte sector
 
     double *lre = L.lre, *lim = L.lim;
-    if constexpr (!PRE8400)
-    {
-        const double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++)
-        {
-            lre[k * 64 + lane] = fs[(size_t)k * 64];
-            lim[k * 64 + lane] = fs[(size_t)(FIRN + k) * 64];
-        }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++)
-        {
-            tre[j] = fs[(size_t)(LDSN + j) * 64];
-            tim[j] = fs[(size_t)(FIRN + LDSN + j) * 64];
-        }
-    }
+    if constexpr (!PRE8400) stg_hist_load<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
     int fir_slot = fir_slot0; // wave-uniform: LDS slot holding the oldest LDS entry, overwritten by the next input
 
     const double agc_len_d = (double)g.agc_len, eb_len_d = (double)g.ebno_len;
@@ -179,19 +132,7 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
             eb_e2sum = eb_e2sum - e2_old; eb_e2sum = eb_e2sum + fabs(sq);
             eb_esum = eb_esum - e_old; eb_esum = eb_esum + fabs(dabval);
             if (j >= n - JD_EBNO_TAIL) // wave-uniform; see JD_EBNO_TAIL
-            {
-                const double e2val = jd_div_const(eb_e2sum, eb_len_d, r_eb_len), mean = jd_div_const(eb_esum, eb_len_d, r_eb_len);
-                const double meansq = mean * mean;
-                double var = e2val - (mean * mean);
-                var -= (0.024709 * meansq);
-                double mvr = (((g.Fs * meansq / (2.0 * g.fb * var))) * 0.13743);
-                if (mvr < 0.000000001) mvr = 0.000000001;
-                double tebno = 10.0 * log10(mvr);
-                if (isnan(tebno)) tebno = 50;
-                if (tebno > 50.0) tebno = 50;
-                if (tebno < 0.0) tebno = 0;
-                eb_ebno = eb_ebno * 0.8 + 0.2 * tebno;
-            }
+                eb_ebno = stg_ebno_oqpsk(eb_ebno, jd_div_const(eb_e2sum, eb_len_d, r_eb_len), jd_div_const(eb_esum, eb_len_d, r_eb_len), g.Fs, g.fb);
         }
         {
             if (agc_hold > 0) { agc_old = 0.0; agc_hold--; }
@@ -223,7 +164,7 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
     if constexpr (PRE8400)
     {
         double2 nx_pf = (nB > 0) ? prefilt[JD_G4(0, ch, pf_rows)] : make_double2(0.0, 0.0); // (prefilt already points at this launch's first row)
-        FB_SYNC(L); // the back half has published the carrier table index of sample 0
+        jd_lds_barrier(); // the back half has published the carrier table index of sample 0
         for (int i = 0; i < nB; i++)
         {
             // sig2 = mixer2.WTCISValue() * cval_prefiltered[i], then EbNo, AGC, clip -> mailbox: the back half waits for this
@@ -232,12 +173,12 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
             const double2 pf = nx_pf;
             const double sre = c_m2.x * pf.x - c_m2.y * pf.y, sim = c_m2.x * pf.y + c_m2.y * pf.x;
             front_sample(sre, sim, r1_agc, r1_e, i, i & 1);
-            FB_SYNC(L);
+            jd_lds_barrier();
             // under the back half's sample i: this sample's coarse ring entry (K3, :410-415) and the next sample's inputs
             const double dval = ((double)nx_pcm) / 32768.0;
             const double2 cc = nx_cc;
             const bool do_fill = !(i == 0 && skip_a_first) && ((coarse_cnt >= g.Fs_int) || !(flags & JF_CPUREDUCE));
-            if (do_fill) ring_fill(make_double2(cc.x * dval, cc.y * dval));
+            if (do_fill) cq.fill(bbring, nfft_mask, make_double2(cc.x * dval, cc.y * dval));
             coarse_cnt++; // :431
             fb_wt_next(mc_ptr, mc_step);
             if (i + 1 < n)
@@ -251,7 +192,7 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
                 r1_agc = win[(size_t)wslot(agc_pos, g.agc_len) * 64];
                 if (EBNO) r1_e = win[(size_t)wslot(agc_pos, g.ebno_len) * 64];
             }
-            FB_SYNC(L); // the back half has published the carrier table index of sample i + 1
+            jd_lds_barrier(); // the back half has published the carrier table index of sample i + 1
         }
     }
     else
@@ -265,7 +206,7 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
         r1_agc = win[(size_t)wslot(agc_pos, g.agc_len) * 64];
         if (EBNO) r1_e = win[(size_t)wslot(agc_pos, g.ebno_len) * 64];
     }
-    FB_SYNC(L);
+    jd_lds_barrier();
 
     FB_TRACE_DECL;
     for (int i = 0; i < nB; i++)
@@ -302,7 +243,7 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
         }
         __builtin_amdgcn_sched_barrier(0);
         FB_TRACE(1); // mailbox read, gather of the carrier table value, mix, push
-        if (do_fill) ring_fill(make_double2(cc.x * dval, cc.y * dval));
+        if (do_fill) cq.fill(bbring, nfft_mask, make_double2(cc.x * dval, cc.y * dval));
         coarse_cnt++; // :431
         fb_wt_next(mc_ptr, mc_step);
         if (i + 1 < n)
@@ -328,7 +269,7 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
             r1_agc = r2_agc; r1_e = r2_e;
             FB_TRACE(4); // EbNo sums, AGC, clip, mailbox write
         }
-        FB_SYNC(L);
+        jd_lds_barrier();
     }
     FB_TRACE_FLUSH(0, nB);
     } // !PRE8400
@@ -336,30 +277,16 @@ __device__ __forceinline__ void fb_front(const JGeom &g, const JPtrs &p, FbLds &
     {
         const double dval = ((double)nx_pcm) / 32768.0;
         const bool do_fill = !(nB == 0 && skip_a_first) && ((coarse_cnt >= g.Fs_int) || !(flags & JF_CPUREDUCE));
-        if (do_fill) ring_fill(make_double2(nx_cc.x * dval, nx_cc.y * dval));
+        if (do_fill) cq.fill(bbring, nfft_mask, make_double2(nx_cc.x * dval, nx_cc.y * dval));
     }
-    ring_flush();
+    cq.flush(bbring);
 
     LDF(S_MC_PTR) = mc_ptr; LDF(S_MC_STEP) = mc_step;
     LDF(S_AGC_SUM) = agc_sum;
     LDF(S_EB_ESUM) = eb_esum; LDF(S_EB_E2SUM) = eb_e2sum; LDF(S_EB_EBNO) = eb_ebno;
-    LDI(I_AGC_POS) = agc_pos; LDI(I_BB_PTR) = bb_ptr; LDI(I_COARSE_CNT) = coarse_cnt;
+    LDI(I_AGC_POS) = agc_pos; LDI(I_BB_PTR) = cq.bb_ptr; LDI(I_COARSE_CNT) = coarse_cnt;
     LDI(I_AGC_HOLD) = agc_hold;
-    if constexpr (!PRE8400)
-    {
-        double *fs = p.firsave + (size_t)grp * 2 * FIRN * 64 + lane;
-        for (int k = 0; k < LDSN; k++)
-        {
-            fs[(size_t)k * 64] = lre[k * 64 + lane];
-            fs[(size_t)(FIRN + k) * 64] = lim[k * 64 + lane];
-        }
-#pragma unroll
-        for (int j = 0; j < TAILN; j++)
-        {
-            fs[(size_t)(LDSN + j) * 64] = tre[j];
-            fs[(size_t)(FIRN + LDSN + j) * 64] = tim[j];
-        }
-    }
+    if constexpr (!PRE8400) stg_hist_save<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
 }
 
 // ------------------------------------------------------------------------------------------------------------------- back half
@@ -490,7 +417,7 @@ __device__ __forceinline__ void fb_back(const JGeom &g, const JPtrs &p, FbLds &L
     // mailbox: the table index of mixer2 for sample 0
     L.idx[lane] = jd_cisidx(m2_ptr);
     double2 nx_cst = cis[jd_cisidx(st_ptr)];
-    FB_SYNC(L);
+    jd_lds_barrier();
 
     double m2fsum = 0; // PRE8400: mixer2_freq_sum of this launch (:447,607)
     FB_TRACE_DECL;
@@ -499,7 +426,7 @@ __device__ __forceinline__ void fb_back(const JGeom &g, const JPtrs &p, FbLds &L
         if constexpr (!PRE8400) FB_TRACE(0); // the barrier
         if constexpr (PRE8400)
         {
-            FB_SYNC(L); // the front half has formed this sample with the table index published one barrier ago
+            jd_lds_barrier(); // the front half has formed this sample with the table index published one barrier ago
             m2fsum += m2_freq;
         }
         const double2 c_st = nx_cst; // requested at the end of the previous sample
@@ -508,18 +435,8 @@ __device__ __forceinline__ void fb_back(const JGeom &g, const JPtrs &p, FbLds &L
         const double abval = d[128];
 
         // ---- K9 symbol timing (:473-484) ----
-        const double ab2 = abval * abval;
-        const double st_diff = d1 - ab2; d1 = ab2;
-        const double st_d1out = w4 * d41_2 + w4c * d41_3; d41_3 = d41_2; d41_2 = d41_1; d41_1 = st_diff;
-        const double st_d2out = w4 * d42_2 + w4c * d42_3; d42_3 = d42_2; d42_2 = d42_1; d42_1 = st_d1out;
-        double st_eta = (st_d2out - st_diff) * st_d1out;
-        {
-            double y = 0;
-            y += res_x2 * g.res_b2; y += res_x1 * g.res_b1; y += st_eta * g.res_b0;
-            y -= res_y2 * g.res_a2; y -= res_y1 * g.res_a1;
-            res_x2 = res_x1; res_x1 = st_eta; res_y2 = res_y1; res_y1 = y;
-            st_eta = y;
-        }
+        double st_eta = stg_oqpsk_t4_pair(abval, d1, d41_1, d41_2, d41_3, d42_1, d42_2, d42_3, w4, w4c);
+        st_eta = jd_biquad(st_eta, res_x1, res_x2, res_y1, res_y2, g.res_b0, g.res_b1, g.res_b2, g.res_a1, g.res_a2);
         const double d8out = w8 * d8_1 + w8c * d8_2; d8_2 = d8_1; d8_1 = st_eta;
         {
             const double2 so = c_st;
@@ -565,14 +482,7 @@ __device__ __forceinline__ void fb_back(const JGeom &g, const JPtrs &p, FbLds &L
                 double ct_ec = ct_xt_d - ct_xt;
                 if (ct_ec > M_PI) ct_ec = M_PI;
                 if (ct_ec < -M_PI) ct_ec = -M_PI;
-                double lf_y;
-                {
-                    double y = 0;
-                    y += lf_x2 * g.lf_b2; y += lf_x1 * g.lf_b1; y += ct_ec * g.lf_b0;
-                    y -= lf_y2 * g.lf_a2; y -= lf_y1 * g.lf_a1;
-                    lf_x2 = lf_x1; lf_x1 = ct_ec; lf_y2 = lf_y1; lf_y1 = y;
-                    lf_y = y;
-                }
+                const double lf_y = jd_biquad(ct_ec, lf_x1, lf_x2, lf_y1, lf_y2, g.lf_b0, g.lf_b1, g.lf_b2, g.lf_a1, g.lf_a2);
                 if constexpr (!PRE8400)
                 {
                     ct_ec = lf_y;
@@ -599,17 +509,10 @@ __device__ __forceinline__ void fb_back(const JGeom &g, const JPtrs &p, FbLds &L
         // ---- advance the NCOs (:600-603) and hand the next sample's carrier table index to the front half ----
         fb_wt_next(m2_ptr, m2_step);
         L.idx[((i + 1) & 1) * 64 + lane] = jd_cisidx(m2_ptr);
-        if (st_step < 0) st_step = 0;
-        st_last = st_ptr;
-        st_ptr += st_step;
-        if (((int)st_ptr) >= JD_WTSIZE)
-        {
-            st_ptr -= JD_WTSIZE;
-            while (((int)st_ptr) >= JD_WTSIZE) st_ptr -= JD_WTSIZE;
-        }
+        jd_wt_next_symbol(st_ptr, st_step, st_last);
         nx_cst = cis[jd_cisidx(st_ptr)]; // the symbol NCO's table value for the next sample: in flight across the barrier
         if constexpr (!PRE8400) FB_TRACE(4); // oscillators advance, hand-back of the carrier table index
-        FB_SYNC(L);
+        jd_lds_barrier();
     }
     if constexpr (!PRE8400) FB_TRACE_FLUSH(1, nB);
     if (need_px) request_px();
@@ -653,7 +556,7 @@ __global__ __launch_bounds__(PAIRS * 128) void k_oqpsk_fb(const JGeom g, const J
     {
         const int nB = n - (only_a_last ? 1 : 0);
         const int nbar = PRE8400 ? 2 * nB + 1 : nB + 1;
-        for (int i = 0; i < nbar; i++) fb_barrier();
+        for (int i = 0; i < nbar; i++) jd_lds_barrier();
         return;
     }
     if (back) fb_back<CAPSYM, PRE8400>(g, p, L, n, only_a_last, grp, lane);

@@ -1,8 +1,8 @@
 // k_pre8400.h -- prefilter of the 8400 bps C-channel branch of OqpskDemodulator::writeData.
 //
 // Written from the oracle restatement (oracle/jaero_oracle.c, fb == 8400); on an MI355X it reproduces the two reference goldens
-// (every soft byte, estimate frequencies to 5e-12) and, in banks of 5 and 67 channels, the oracle (tests/test_gpu_parity.py).  Not
-// measured or tuned yet: the prefilter costs about as much as the rest of the path, and k_coarse4_w8400 spills.
+// (every soft byte, estimate frequencies to 5e-12) and, in banks of 5 and 67 channels, the oracle (tests/test_gpu_parity.py).
+// Measured and tuned in rounds 2 and 6: k_pre8400_mix 2.4 ms + k_pre8400_fft 4.9 ms of an 8400 bps step.
 //
 // Reference (JAERO/oqpskdemodulator.cpp:343-381): for the whole write, PCM is mixed down with mixer_fir_pre, filtered with
 // JFastFir (kernel RRC alpha 0.6, 2049 taps, nfft 4096: out[m] = sum_k h[k] x[m - L - k], L = nfft - K + 1 = 2048, the behaviour
@@ -16,7 +16,7 @@
 //                  filter of the burst path.  (The direct form k_pre8400_fir, 127 ms per step, left the library in round 3.)
 #pragma once
 #include "jaero_device.h"
-#include "k_coarse2.h" // CV<>, regfft<16>, c4_twiddle16, c4_lds_barrier
+#include "k_coarse2.h" // CV<>, regfft<16>, c4_twiddle16
 
 #define PRE_K 2049                 // taps
 #define PRE_L 2048                 // JFastFir latency nfft - K + 1
@@ -150,10 +150,10 @@ __device__ __forceinline__ void pf_exchange1(double (&v)[16], double *xch, int T
     const int wb = T * 4 + c, rb = ((T >> 4) * 256 + (T & 15)) * 4 + c;
 #pragma unroll
     for (int s = 0; s < 16; s++) xch[wb + s * 1024] = v[s];
-    c4_lds_barrier();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 16; s++) v[s] = xch[rb + s * 64];
-    c4_lds_barrier();
+    jd_lds_barrier();
 }
 
 __device__ __forceinline__ void pf_exchange2(double (&v)[16], double *xch, int T, int c)
@@ -163,10 +163,10 @@ __device__ __forceinline__ void pf_exchange2(double (&v)[16], double *xch, int T
     const int wb = (lo * 16 + (hi ^ lo)) * 4 + c;
 #pragma unroll
     for (int s = 0; s < 16; s++) xch[wb + s * 1024] = v[s];
-    c4_lds_barrier();
+    jd_lds_barrier();
 #pragma unroll
     for (int s = 0; s < 16; s++) v[s] = xch[((hi * 16 + s) * 16 + (lo ^ s)) * 4 + c];
-    c4_lds_barrier();
+    jd_lds_barrier();
 }
 
 __device__ __forceinline__ void pf_fft4096(CV<16> &d, double *xch, const double2 *__restrict__ tw, int T, int c)

@@ -157,6 +157,27 @@ __global__ void __launch_bounds__(TPB) k_jp_fb_fmod360(const double *x, double *
     JP_IDX;
     if (i < n) o[i] = fb_fmod360(x[i]);
 }
+// `steps` consecutive updates per lane: x and y are [steps][n], st is [4][n] = x1, x2, y1, y2 (in and out); the coefficients are wave-uniform
+// kernel arguments, as JGeom's are in the sample kernels
+__global__ void __launch_bounds__(TPB) k_jp_biquad(const double *x, double *st, double *y, long n, int steps, double b0, double b1, double b2,
+                                                   double a1, double a2)
+{
+    JP_IDX;
+    if (i >= n) return;
+    double x1 = st[i], x2 = st[n + i], y1 = st[2 * n + i], y2 = st[3 * n + i];
+    for (int k = 0; k < steps; k++) y[(long)k * n + i] = jd_biquad(x[(long)k * n + i], x1, x2, y1, y2, b0, b1, b2, a1, a2);
+    st[i] = x1; st[n + i] = x2; st[2 * n + i] = y1; st[3 * n + i] = y2;
+}
+__global__ void __launch_bounds__(TPB) k_jp_diff_soft(const double *soft_in, double *diff_last, double *o, long n)
+{
+    JP_IDX;
+    if (i < n) { double d = diff_last[i]; o[i] = jd_diff_soft(soft_in[i], d); diff_last[i] = d; }
+}
+__global__ void __launch_bounds__(TPB) k_jp_wt_next_symbol(double *ptr, double *step, double *last_ptr, long n)
+{
+    JP_IDX;
+    if (i < n) { double p = ptr[i], s = step[i], l = last_ptr[i]; jd_wt_next_symbol(p, s, l); ptr[i] = p; step[i] = s; last_ptr[i] = l; }
+}
 __global__ void __launch_bounds__(TPB) k_jp_bd_set_phase_deg(const double *phase_deg, double *ptr, long n)
 {
     JP_IDX;
@@ -310,6 +331,29 @@ int jp_wt_passed(const double *last_ptr, const double *ptr, const double *step, 
     double *dfr = b.io(frac, n);
     int *dpa = b.io(passed, n);
     if (b.ok() && n > 0) k_jp_wt_passed<<<nblocks(n), TPB>>>(dl, dp, ds, dw, dfr, dpa, n);
+    return b.sync();
+}
+int jp_biquad(const double *x, double *st, double *y, long n, int steps, double b0, double b1, double b2, double a1, double a2)
+{
+    Bufs b;
+    const double *dx = b.in(x, n * steps);
+    double *ds = b.io(st, 4 * n), *dy = b.io(y, n * steps);
+    if (b.ok() && n > 0) k_jp_biquad<<<nblocks(n), TPB>>>(dx, ds, dy, n, steps, b0, b1, b2, a1, a2);
+    return b.sync();
+}
+int jp_diff_soft(const double *soft_in, double *diff_last, double *o, long n)
+{
+    Bufs b;
+    const double *dsi = b.in(soft_in, n);
+    double *dd = b.io(diff_last, n), *d = b.io(o, n);
+    if (b.ok() && n > 0) k_jp_diff_soft<<<nblocks(n), TPB>>>(dsi, dd, d, n);
+    return b.sync();
+}
+int jp_wt_next_symbol(double *ptr, double *step, double *last_ptr, long n)
+{
+    Bufs b;
+    double *dp = b.io(ptr, n), *ds = b.io(step, n), *dl = b.io(last_ptr, n);
+    if (b.ok() && n > 0) k_jp_wt_next_symbol<<<nblocks(n), TPB>>>(dp, ds, dl, n);
     return b.sync();
 }
 int jp_bd_set_phase_deg(const double *phase_deg, double *ptr, long n)

@@ -14,7 +14,7 @@
 //                 mixer2 only changes at a trident verdict), so the front half needs no mailbox from the back half at all.
 //   B ("back"):   everything behind the filter: burst timing, the preamble's symbol tone, carrier rotator, EbNo meter, AGC, symbol timer, sample
 //                 instants, soft bits, emissions.  The chain of k_burst_oqpsk_demod minus the filter.
-// One LDS-only barrier per sample (fb_barrier), F one sample ahead, {sre, sim} through a double-buffered mailbox.
+// One LDS-only barrier per sample (jd_lds_barrier), F one sample ahead, {sre, sim} through a double-buffered mailbox.
 // Arithmetic: the front half's filter is the continuous kernels' (one multiplication and one addition per tap, each rounded, as the reference's
 // build executes it) -- the front half has the time; the back half keeps the device library's hypot / atan2 (on the reference's
 // own off-air recording neither choice moves a soft byte or a soft symbol beyond 1e-9, profiles/r6_burst_recording_ab.json).
@@ -80,11 +80,11 @@ __device__ __forceinline__ void bfb_front(const BGeom &g, const BPtrs &p, double
         jd_wt_next(m2_ptr, m2_step);
     };
     if (n > 0) produce(0, true);
-    fb_barrier();
+    jd_lds_barrier();
     for (int i = 0; i < n; i++)
     {
         if (i + 1 < n) produce(i + 1, false);
-        fb_barrier();
+        jd_lds_barrier();
     }
     BLDF(BS_M2_PTR) = m2_ptr; BLDF(BS_M2_STEP) = m2_step; BLDF(BS_M2_FREQ) = m2_freq; BLDF(BS_VOL_GAIN) = vol_gain;
     {
@@ -152,7 +152,7 @@ __device__ __forceinline__ void bfb_back(const BGeom &g, const BPtrs &p, const d
     // ring entries of sample i+1 are requested at the top of iteration i (all slots are wave-uniform and data independent)
     double nx_agc2 = ebe_ring[(size_t)s_agc2 * 64];
     double nx_e = ebe_ring[(size_t)s_e * 64];
-    fb_barrier(); // the front half has formed sample 0
+    jd_lds_barrier(); // the front half has formed sample 0
     for (int i = 0; i < n; i++)
     {
         const long long sample = n0 + i;
@@ -368,7 +368,7 @@ __device__ __forceinline__ void bfb_back(const BGeom &g, const BPtrs &p, const d
         while (((int)st_ptr) >= JD_WTSIZE) st_ptr -= JD_WTSIZE;
         stq_ptr += g.stq_step;
         while (((int)stq_ptr) >= JD_WTSIZE) stq_ptr -= JD_WTSIZE;
-        fb_barrier();
+        jd_lds_barrier();
     }
 
     BLDF(BS_ST_PTR) = st_ptr; BLDF(BS_ST_STEP) = st_step; BLDF(BS_ST_FREQ) = st_freq; BLDF(BS_ST_LAST) = st_last;
@@ -403,7 +403,7 @@ __global__ __launch_bounds__(PAIRS * 128) void k_burst_oqpsk_fb(const BGeom g, c
     double *lre = base, *lim = base + BFB_LDSN * 64, *mail = base + 2 * BFB_LDSN * 64;
     if (grp >= g.ngroups)
     {
-        for (int i = 0; i <= n; i++) fb_barrier();
+        for (int i = 0; i <= n; i++) jd_lds_barrier();
         return;
     }
     if (back) bfb_back<CAPSYM>(g, p, mail, n, n0, first_of_write, grp, lane);

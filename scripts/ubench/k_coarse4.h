@@ -209,13 +209,13 @@ __device__ __forceinline__ void coarse4_body(const JGeom g, const JPtrs p, const
             double *wt = persistent ? xch + 64 * 257 : xch;
             if (!persistent || startbin != tab_startbin)
             {
-                c4_lds_barrier();
+                jd_lds_barrier();
                 for (int i = t; i <= startbin + 1; i += C2_THREADS)
                 {
                     const double c = cos(M_PI_2 * ((double)i) / ((double)startbin));
                     wt[i] = (i == 0) ? 1.0 : ((i <= startbin) ? c * c : 0.0);
                 }
-                c4_lds_barrier();
+                jd_lds_barrier();
                 if (persistent) tab_startbin = startbin;
             }
             // applied eight at a time as they are read: all 32 weights in registers beside the 32 points spill (and without the fence the
@@ -234,7 +234,7 @@ __device__ __forceinline__ void coarse4_body(const JGeom g, const JPtrs p, const
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (!persistent) c4_lds_barrier(); // the next transform's exchanges reuse the buffer
+            if (!persistent) jd_lds_barrier(); // the next transform's exchanges reuse the buffer
         }
         else
         {
@@ -257,7 +257,7 @@ __device__ __forceinline__ void coarse4_body(const JGeom g, const JPtrs p, const
             d.i[s] = re * im + im * re;
         }
         c4_fft(d, xch, tw, t);
-        c4_lds_barrier(); // the exchange buffer is free: it receives a copy of y for the fold below
+        jd_lds_barrier(); // the exchange buffer is free: it receives a copy of y for the fold below
         // smooth with fftshift: y[i] = y[i]*0.9 + 0.1*10*log10(fmax(abs(out[i]),1)), out[i] = X[i ^ N/2]
         // all 32 old y values are requested before the log10s (64 registers, free once only |X|^2 is kept of d): written as one
         // load-compute-store per element, every element waited out a full HBM round trip (vmcnt counts the stores too)
@@ -281,7 +281,7 @@ __device__ __forceinline__ void coarse4_body(const JGeom g, const JPtrs p, const
                 (xch + ib)[t] = yn;
             }
         }
-        c4_lds_barrier(); // the fold reads the LDS copy; the stores to y[] drain in the background
+        jd_lds_barrier(); // the fold reads the LDS copy; the stores to y[] drain in the background
         {
             const int ln = li + (int)gridDim.x;
             if (ln < nlist)
@@ -328,7 +328,7 @@ __device__ __forceinline__ void coarse4_body(const JGeom g, const JPtrs p, const
                 if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
             }
             if ((t & 63) == 0) { red_val[t >> 6] = bv; red_idx[t >> 6] = bi; }
-            c4_lds_barrier();
+            jd_lds_barrier();
             if (t == 0)
             {
                 for (int w = 1; w < C2_THREADS / 64; w++)
@@ -341,13 +341,13 @@ __device__ __forceinline__ void coarse4_body(const JGeom g, const JPtrs p, const
             }
         }
         if (t == 0) sh_bigchange = coarse_slot(g, p, ch, (red_idx[0] >= 0) ? red_idx[0] : (N / 2), N, hzperbin, lockingbw);
-        c4_lds_barrier();
+        jd_lds_barrier();
         if (sh_bigchange)
         {
             double2 *ringw = p.bbring + (size_t)ch * N;
             for (int i = t; i < N; i += C2_THREADS) { y[i] = 20; ringw[i] = make_double2(0.0, 0.0); }
         }
-        c4_lds_barrier(); // LDS reuse only: the next estimate is another channel, and its ring rows are already on their way
+        jd_lds_barrier(); // LDS reuse only: the next estimate is another channel, and its ring rows are already on their way
     }
 }
 

@@ -110,11 +110,11 @@ __device__ __forceinline__ void wg_fft14_e64(CV<64> &d, double *xch, const doubl
 #pragma unroll
         for (int half = 0; half < 2; half++)
         {
-            c6_bar();
+            jd_lds_barrier();
 #pragma unroll
             for (int s = 0; s < 64; s++)
                 if ((c7_k(s) >> 5) == half) (xch + (c7_k(s) & 31) * 256)[t] = v[s];
-            c6_bar();
+            jd_lds_barrier();
 #pragma unroll
             for (int g = 2 * half; g < 2 * half + 2; g++)
 #pragma unroll
@@ -151,12 +151,12 @@ __device__ __forceinline__ void wg_fft14_e64(CV<64> &d, double *xch, const doubl
 #pragma unroll
         for (int half = 0; half < 2; half++)
         {
-            c6_bar();
+            jd_lds_barrier();
 #pragma unroll
             for (int g = 0; g < 4; g++)
 #pragma unroll
                 for (int k2 = 8 * half; k2 < 8 * half + 8; k2++) (xch + 16 * g + 64 * (k2 & 7))[e2w] = v[16 * g + k2];
-            c6_bar();
+            jd_lds_barrier();
 #pragma unroll
             for (int h = 2 * half; h < 2 * half + 2; h++)
 #pragma unroll

@@ -35,6 +35,9 @@ LAUNCHERS = {
     "jp_fb_wt_next": "fb_wt_next",
     "jp_fb_fmod360": "fb_fmod360",
     "jp_bd_set_phase_deg": "bd_set_phase_deg",
+    "jp_biquad": "jd_biquad",
+    "jp_diff_soft": "jd_diff_soft",
+    "jp_wt_next_symbol": "jd_wt_next_symbol",
 }
 
 
@@ -51,12 +54,12 @@ class FirRow:
 
 # every matched-filter instantiation of jaero_device.h a kernel launches, plus the FUSED form of jd_fir_eval, which the template offers
 FIR_ROWS = [
-    FirRow("jp_fir_eval_40_24_8", "jd_fir_eval", 40, 24, 8, False, "k_msk.h:92"),  # MSK_LDSN_40: 1200 bps at 24 kHz, 600 bps at 12 kHz
-    FirRow("jp_fir_eval_20_12_8", "jd_fir_eval", 20, 12, 8, False, "k_msk.h:92"),  # MSK_LDSN_20: 1200 bps at 12 kHz
+    FirRow("jp_fir_eval_40_24_8", "jd_fir_eval", 40, 24, 8, False, "k_msk.h:80"),  # MSK_LDSN_40: 1200 bps at 24 kHz, 600 bps at 12 kHz
+    FirRow("jp_fir_eval_20_12_8", "jd_fir_eval", 20, 12, 8, False, "k_msk.h:80"),  # MSK_LDSN_20: 1200 bps at 12 kHz
     FirRow("jp_fir_eval_fused_55_36_8", "jd_fir_eval", 55, 36, 8, True, ""),  # no kernel launches it (the burst demodulator has bd_fir_eval_v)
-    FirRow("jp_fir_eval_sym_55_36_6", "jd_fir_eval_sym", 55, 36, 6, False, "k_oqpsk_fb.h:263"),  # FB_LDSN
-    FirRow("jp_fir_eval_sym_static_55_36_6", "jd_fir_eval_sym_static", 55, 36, 6, False, "k_oqpsk_fb.h:325"),
-    FirRow("jp_fir_eval_sym_static_but_last_55_36_6", "jd_fir_eval_sym_static_but_last", 55, 36, 6, False, "k_oqpsk_fb.h:295"),  # D = FB_SOLO_D
+    FirRow("jp_fir_eval_sym_55_36_6", "jd_fir_eval_sym", 55, 36, 6, False, "k_oqpsk_fb.h:204"),  # FB_LDSN
+    FirRow("jp_fir_eval_sym_static_55_36_6", "jd_fir_eval_sym_static", 55, 36, 6, False, "k_oqpsk_fb.h:266"),
+    FirRow("jp_fir_eval_sym_static_but_last_55_36_6", "jd_fir_eval_sym_static_but_last", 55, 36, 6, False, "k_oqpsk_fb.h:236"),  # D = FB_SOLO_D
 ]
 
 NOT_LAUNCHED = {
@@ -64,6 +67,7 @@ NOT_LAUNCHED = {
     "jd_with_hi": "replaces a high word; every use is inside jd_expm1 / jd_tanh, which are checked bit for bit",
     "jd_atan_lane_table": "built at entry of jp_atan2's kernel exactly as the sample kernels build it",
     "jd_atan2_t": "the template behind jd_atan2 (its only instantiation)",
+    "jd_lds_barrier": "s_waitcnt lgkmcnt(0) + s_barrier, no arithmetic; every front / back pair and workgroup FFT the kernel tests run goes through it",
     "jd_fir_lds_part": "the ring part of jd_fir_eval_sym_static and _but_last, checked through them at every ring position",
 }
 
@@ -79,17 +83,35 @@ class DivConst:
 # every (d, rd = 1.0 / d) that reaches jd_div_const: k_oqpsk_fb (continuous OQPSK, 10 500 and 8400 bps, Fs = 48 000 only: jaero_hip.hip:380-384),
 # k_burst_demod (burst OQPSK, 10 500 bps at 48 000 only) and bd_set_phase_deg (both burst kinds)
 DIV_CONSTS = [
-    DivConst(192000.0, "OQPSK agc_len = round(4 Fs), k_oqpsk_fb.h:169", "jaero_hip.hip:431", "g.agc_len = (int)round(4 * s.Fs)"),
-    DivConst(96000.0, "OQPSK ebno_len = 2 Fs, k_oqpsk_fb.h:169", "jaero_hip.hip:426", "g.ebno_len = (int)(2 * s.Fs)"),
-    DivConst(800.0, "OQPSK marg_len, k_oqpsk_fb.h:395", "jaero_hip.hip:432", "g.marg_len = 800"),
-    DivConst(400.0, "OQPSK pm_len and msema_len, k_oqpsk_fb.h:395", "jaero_hip.hip:432", "g.pm_len = 400; g.msema_len = 400"),
-    DivConst(48000.0, "samplerate = Fs (also k_burst_demod.h:176)", "k_oqpsk_fb.h:392", "r_samplerate = 1.0 / samplerate"),
-    DivConst(360.0, "degrees (also k_burst_demod.h:176)", "k_oqpsk_fb.h:393", "r_360 = 1.0 / 360.0"),
+    DivConst(192000.0, "OQPSK agc_len = round(4 Fs), k_oqpsk_fb.h:122", "jaero_hip.hip:431", "g.agc_len = (int)round(4 * s.Fs)"),
+    DivConst(96000.0, "OQPSK ebno_len = 2 Fs, k_oqpsk_fb.h:122", "jaero_hip.hip:426", "g.ebno_len = (int)(2 * s.Fs)"),
+    DivConst(800.0, "OQPSK marg_len, k_oqpsk_fb.h:322", "jaero_hip.hip:432", "g.marg_len = 800"),
+    DivConst(400.0, "OQPSK pm_len and msema_len, k_oqpsk_fb.h:322", "jaero_hip.hip:432", "g.pm_len = 400; g.msema_len = 400"),
+    DivConst(48000.0, "samplerate = Fs (also k_burst_demod.h:172)", "k_oqpsk_fb.h:319", "r_samplerate = 1.0 / samplerate"),
+    DivConst(360.0, "degrees (also k_burst_demod.h:172)", "k_oqpsk_fb.h:320", "r_360 = 1.0 / 360.0"),
     DivConst(360.0, "degrees in bd_set_phase_deg", "jaero_device.h:222", "jd_div_const(phase_deg, 360.0, 1.0 / 360.0)"),
-    DivConst(19999.0, "JD_WTSIZE (also k_burst_demod.h:176)", "k_oqpsk_fb.h:393", "r_wtsize = 1.0 / wtsize_d"),
-    DivConst(585.0, "burst OQPSK agc2_len = round(64 SPS), SPS = 2 Fs / fb, k_burst_demod.h:176", "burst_host.h:23",
+    DivConst(19999.0, "JD_WTSIZE (also k_burst_demod.h:172)", "k_oqpsk_fb.h:320", "r_wtsize = 1.0 / wtsize_d"),
+    DivConst(585.0, "burst OQPSK agc2_len = round(64 SPS), SPS = 2 Fs / fb, k_burst_demod.h:172", "burst_host.h:23",
              "g.agc2_len = (int)round((SPS * 64.0 / s.Fs) * s.Fs)"),
-    DivConst(128.0, "burst OQPSK msema_len, k_burst_demod.h:177", "burst_host.h:36", "g.msema_len = 128"),
+    DivConst(128.0, "burst OQPSK msema_len, k_burst_demod.h:173", "burst_host.h:36", "g.msema_len = 128"),
+]
+
+
+@dataclass(frozen=True)
+class Biquad:
+    what: str
+    site: str  # file:line under jaero_amd/csrc of the line that sets b0 (the a's are on the line next to it)
+    b: tuple  # b0, b1, b2
+    a: tuple  # a1, a2
+
+
+# the second-order sections fill_geometry gives the banks that jd_biquad serves: 10.5 kbps OQPSK (resonator, loop filter), MSK at 48 kHz
+BIQUADS = [
+    Biquad("OQPSK 10.5k resonator", "jaero_hip.hip:436", (0.00032714218939589035, 0.0, 0.00032714218939589035), (-0.39005299948210803, 0.99934571562120822)),
+    Biquad("OQPSK loop filter", "jaero_hip.hip:444", (0.0010275610653672064, 0.0020551221307344128, 0.0010275610653672064),
+           (-1.9207386815577139, 0.92509247310306331)),
+    Biquad("MSK 1200 resonator", "jaero_hip.hip:460", (2.617308727964618e-04, 0.0, -2.617308727964618e-04), (-1.993312819378528, 0.999476538254407)),
+    Biquad("MSK 600 resonator", "jaero_hip.hip:468", (1.308825621597620e-04, 0.0, -1.308825621597620e-04), (-1.998196509168551, 0.999738234875681)),
 ]
 # the sample rates the oscillators divide by (jaero_hip.hip:380: continuous MSK also runs at 24 and 12 kHz)
 SAMPLE_RATES = (48000.0, 24000.0, 12000.0)
@@ -113,6 +135,9 @@ def prims():
         "jp_wt_advance_fraction": [P, P, n],
         "jp_wt_passed": [P, P, P, P, P, P, n],
         "jp_bd_set_phase_deg": [P, P, n],
+        "jp_biquad": [P, P, P, n, C.c_int, f, f, f, f, f],
+        "jp_diff_soft": [P, P, P, n],
+        "jp_wt_next_symbol": [P, P, P, n],
     }
     for name in ("jp_tanh", "jp_tanh_full", "jp_expm1", "jp_log10", "jp_qround", "jp_softbit", "jp_cisidx", "jp_fb_fmod360"):
         sig[name] = [P, P, n]

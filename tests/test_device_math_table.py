@@ -29,6 +29,11 @@ def defined_primitives():
     return names
 
 
+def kernel_headers():
+    """The headers that hold kernel text: every k_*.h and demod_stages.h, the stages several of them share."""
+    return sorted(f for f in os.listdir(DP.CSRC) if (f.startswith("k_") and f.endswith(".h")) or f == "demod_stages.h")
+
+
 def test_every_primitive_has_a_launcher_or_a_reason():
     have = defined_primitives()
     assert {"jd_atan2", "jd_hypot", "jd_div_const", "bd_set_phase_deg", "jd_fir_eval"} <= have, have
@@ -44,7 +49,8 @@ def test_helpers_live_beside_the_primitives_not_in_kernel_headers():
     """The test library includes no kernel header, so nothing it runs may be defined in one."""
     src = read("prims_check.hip")
     assert re.findall(r'#include\s+"([^"]+)"', src) == ["jaero_device.h"]
-    for k in sorted(f for f in os.listdir(DP.CSRC) if f.startswith("k_") and f.endswith(".h")):
+    assert "demod_stages.h" in kernel_headers()
+    for k in kernel_headers():
         dup = set(_DEF.findall(read(k))) & defined_primitives()
         assert not dup, f"{k} defines {dup}"
 
@@ -105,7 +111,7 @@ def test_div_const_rows_cite_where_each_divisor_is_computed():
     assert round(4 * Fs) == 192000 and int(2 * Fs) == 96000 and round((sps * 64.0 / Fs) * Fs) == 585
     assert sorted({dc.d for dc in DP.DIV_CONSTS}) == sorted({192000.0, 96000.0, 800.0, 400.0, 48000.0, 360.0, 19999.0, 585.0, 128.0})
     # every kernel header that calls jd_div_const is one whose divisors are listed
-    users = sorted(f for f in os.listdir(DP.CSRC) if f.startswith("k_") and "jd_div_const(" in read(f))
+    users = [f for f in kernel_headers() if "jd_div_const(" in read(f)]
     assert users == ["k_burst_demod.h", "k_oqpsk_fb.h"], users
 
 

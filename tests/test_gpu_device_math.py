@@ -6,6 +6,8 @@ one element per lane.  References: glibc's hypot / tanh / expm1 and __float128's
 Bit identity with libm is defined against glibc 2.35: on another glibc only those assertions skip, with the version in the reason.
 """
 import math
+import os
+import re
 from fractions import Fraction
 
 import numpy as np
@@ -411,8 +413,8 @@ def test_qround_and_softbit_are_qts(L):
 
 # Outside int's range the C casts of qRound are undefined; what each machine gives (x86-64 cvttsd2si: 0x80000000 for NaN and out of range;
 # gfx950 v_cvt_i32_f64: 0 for NaN, saturated otherwise).  Only +inf and v >= 2^31 differ, and no call site reaches them: every jd_softbit
-# argument is 128 + 127 k s (k = 1 or 0.75) with s a symbol formed from AGC'd samples clipped to magnitude 2.84 (k_msk.h:178 and its
-# copies in every kernel), i.e. finite and small -- or NaN, where both give 0.  jd_qround's other call (k_burst_front.h:386-387) rounds
+# argument is 128 + 127 k s (k = 1 or 0.75) with s a symbol formed from AGC'd samples clipped to magnitude 2.84 (demod_stages.h:161 and its
+# counterparts in the OQPSK and burst kernels), i.e. finite and small -- or NaN, where both give 0.  jd_qround's other call (k_burst_front.h:386-387) rounds
 # constants of the bank's geometry.
 #            v:        (device qRound, x86 qRound, device soft bit, x86 soft bit)
 QROUND_OUTSIDE = {
@@ -580,6 +582,87 @@ def test_passed_point_and_table_index_are_wavetables(L):
     idx = np.zeros(len(p), np.int32)
     call(L, "jp_cisidx", p, idx, len(p))
     assert np.array_equal(idx, [cisidx(float(v)) for v in p])
+
+
+# ---- the stages' primitives: IIR::update, DiffDecode::UpdateSoft, the symbol oscillator's step --------------------------------------
+@pytest.mark.parametrize("bq", DP.BIQUADS, ids=lambda bq: bq.what)
+def test_biquad_is_iir_update_term_by_term(L, bq):
+    """jd_biquad against IIR::update restated operation by operation in numpy (which does not fuse), 64 consecutive steps per lane."""
+    src, ln = bq.site.split(":")
+    with open(os.path.join(DP.CSRC, src)) as fh:
+        text = " ".join(fh.read().splitlines()[int(ln) - 2:int(ln) + 1])  # the a's are set on the line before or after the b's
+    coef = {k: float(v) for k, v in re.findall(r"g\.(?:res|lf)_([ab][012]) = (-?[0-9.e+-]+);", text)}
+    assert coef == dict(zip(("b0", "b1", "b2", "a1", "a2"), bq.b + bq.a)), (bq.site, coef)
+    n, steps = 4096, 64
+    rng = np.random.default_rng(31)
+    special = f64([0.0, -0.0, 1e-300, -1e-300, 1e300, -1e300])
+    draw = lambda *shape: f64(rng.standard_normal(shape) * np.exp2(rng.uniform(-8, 8, shape)))  # noqa: E731
+    x, st = draw(steps, n), draw(4, n)
+    mix = rng.random((steps, n)) < 0.05
+    x[mix] = rng.choice(special, int(mix.sum()))
+    st[:, :len(special)] = special  # each special value in every state slot of some lane ...
+    st[:, len(special):2 * len(special)] = special[::-1]
+    x[0, :2 * len(special)] = np.tile(special, 2)  # ... and as the first input of a lane
+    (b0, b1, b2), (a1, a2) = bq.b, bq.a
+    x1, x2, y1, y2 = (v.copy() for v in st)
+    want = np.zeros((steps, n))
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        for k in range(steps):
+            y = np.zeros(n)
+            y = y + x2 * b2
+            y = y + x1 * b1
+            y = y + x[k] * b0
+            y = y - y2 * a2
+            y = y - y1 * a1
+            x2, x1, y2, y1 = x1, x[k].copy(), y1, y
+            want[k] = y
+    got_st, got = f64(st.copy()), np.full((steps, n), np.nan)
+    call(L, "jp_biquad", f64(x), got_st, got, n, steps, b0, b1, b2, a1, a2)
+    assert_same(f"jd_biquad y ({bq.what})", got.ravel(), want.ravel(), x.ravel())
+    assert_same(f"jd_biquad state ({bq.what})", got_st.ravel(), np.concatenate([x1, x2, y1, y2]), st.ravel())
+
+
+def test_diff_soft_is_diffdecodes_updatesoft(L):
+    """jd_diff_soft against DiffDecode::UpdateSoft (DSP.cpp:531-563): every sign combination with +-0 on either side, then random pairs."""
+    rng = np.random.default_rng(32)
+    signs = f64([-2.5, -0.0, 0.0, 3.5, -1e-300, 1e-300])
+    si = f64(np.concatenate([np.repeat(signs, len(signs)), rng.standard_normal(4096)]))
+    dl = f64(np.concatenate([np.tile(signs, len(signs)), rng.standard_normal(4096)]))
+    want = np.where((si < 0) & (dl < 0), dl, np.where((si > 0) & (dl > 0), -dl, np.fabs(dl)))
+    got, got_dl = np.full(len(si), np.nan), dl.copy()
+    call(L, "jp_diff_soft", si, got_dl, got, len(si))
+    assert_same("jd_diff_soft value", got, want, si, dl)
+    assert_same("jd_diff_soft diff_last", got_dl, si, si, dl)
+
+
+def wt_next_symbol(ptr, step):  # WTnextFrame with last_WTptr (DSP.cpp:70-77)
+    if step < 0:
+        step = 0.0
+    last = ptr
+    ptr += step
+    while int(ptr) >= W:
+        ptr -= W
+    return ptr, step, last
+
+
+def test_symbol_oscillator_step_is_wavetables(L):
+    """jd_wt_next_symbol: step negative, zero, just below / at / just above JD_WTSIZE - ptr, and beyond two table lengths (the `while`)."""
+    rng = np.random.default_rng(33)
+    ptrs = f64(np.concatenate([[0.0, 0.5, 1234.56789, W - 1, W - 0.5, np.nextafter(W, 0)], rng.uniform(0, W, 250)]))
+    p, s = [], []
+    for q in ptrs:
+        gap = W - q
+        for st in (-1.0, -1e-300, -0.0, 0.0, np.nextafter(gap, 0), gap, np.nextafter(gap, 2 * W), gap - 1e-9, gap + 1e-9, 2 * W + 0.25, 2.5 * W,
+                   3 * W + gap, 761.9, 2187.4):
+            p.append(q)
+            s.append(st)
+    p, s = f64(p), f64(s)
+    want = [wt_next_symbol(float(a), float(b)) for a, b in zip(p, s)]
+    assert sum(1 for a, b in zip(p, s) if a + max(b, 0.0) >= 2 * W) > 500  # the loop behind the first subtraction runs
+    pp, ss, ll = p.copy(), s.copy(), np.full(len(p), -7.0)
+    call(L, "jp_wt_next_symbol", pp, ss, ll, len(p))
+    for k, what, got in ((0, "ptr", pp), (1, "step", ss), (2, "last", ll)):
+        check_elementwise(f"jd_wt_next_symbol {what}", got, [w[k] for w in want], p, s)
 
 
 # ---- matched-filter evaluators --------------------------------------------------------------------------------------------------
