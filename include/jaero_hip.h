@@ -264,15 +264,17 @@ int jaero_ingest_queued(const jaero_ingest *ing, int channel);
 int jaero_ingest_pump(jaero_ingest *ing, int flush, void *stream, int *chunks);
 int jaero_ingest_stats(const jaero_ingest *ing, long long *three);
 
-/* ---- wideband I/Q channeliser (the other half): one capture in, the per-channel 48 kHz int16 audio of a whole bank out,
- * on the device.  No counterpart in the reference (it has only the receiving end of per-channel audio); this text is the definition, and
+/* ---- wideband I/Q channeliser (the other half): one capture in, the per-channel int16 audio of a whole bank out (at 48 kHz,
+ * or at the 24 / 12 kHz of the reference's default MSK set-ups), on the device.  No counterpart in the reference (it has only the receiving end of per-channel audio); this text is the definition, and
  * tests/chan_oracle.py implements it literally in numpy.  A fast-convolution filter bank of fixed geometry: transform length N = 16384, hop
- * Hp = 8192 input samples, decimation D = decim in {16, 32, 64} (capture rate Fs_in = 48000 D), M = N / D bins per channel, Mo = M / 2
- * output samples per hop and channel.
+ * Hp = 8192 input samples, D = decim in {16, 32, 64, 128, 256} the TOTAL decimation from the capture to the output, out_rate in {48000, 24000, 12000}
+ * the output's rate (capture rate Fs_in = out_rate D; out_rate is a label: it enters no arithmetic below and exists so that jaero_chan_feed
+ * can check the bank), M = N / D bins per channel, Mo = M / 2 output samples per hop and channel.  jaero_chan_create is the 48 kHz channeliser of
+ * D <= 64; jaero_chan2_create takes every D and out_rate.
  *   input      interleaved int16 I, Q; x[n] = I[n] + j Q[n], n counted from create, x[n] = 0 for n < 0
  *   taps       real prototype low-pass h[0 .. ntaps), 1 <= ntaps <= 8193, at the capture rate; G = DFT_N(h, zero padded), formed on the host
  *   channel c  tune  (uint32, centre = tune Fs_in / 2^32, read as a SIGNED 32-bit number t: negative centres exist),
- *              audio (uint32, audio offset = audio 48000 / 2^32), gain g > 0.
+ *              audio (uint32, audio offset = audio out_rate / 2^32), gain g > 0.
  *              b = (t + 2^17) >> 18 (arithmetic: the nearest bin), rho = t - b 2^18, w = (audio - rho D) mod 2^32.  Integer arithmetic only:
  *              no phase accumulator, no per-channel state besides these three numbers.
  *   block p    exists once (p + 1) Hp samples have been written.  s_p[i] = x[(p - 1) Hp + i], i < N; X_p = DFT_N(s_p) (forward), shared by
@@ -280,12 +282,15 @@ int jaero_ingest_stats(const jaero_ingest *ing, long long *three);
  *              v[p Mo + r - Mo] = w[r] (-1)^(b (p - 1)) for Mo <= r < 2 Mo (the sign keeps the bin shift's phase continuous in time)
  *   output     y[m] = sat16(rint(g Re(v[m] e^(j 2 pi ((w m) mod 2^32) / 2^32)))), m the absolute (64-bit) output index, rint = round half to
  *              even, sat16 = clamp to [-32768, 32767]
- * i.e. a band-pass at the grid frequency nearest the requested centre (at most Fs_in / (2 N) = 23 .. 94 Hz off it), an exact shift of the
+ * i.e. a band-pass at the grid frequency nearest the requested centre (at most Fs_in / (2 N) off it: 23 .. 94 Hz at the capture rates of 48000 x 16 .. 64), an exact shift of the
  * requested centre to the audio offset, the real part.  After T input samples exactly floor(T / Hp) Mo samples per channel have been
  * produced, however the writes were cut; the rest of the input waits in the handle (latency below one hop).
  *   jaero_chan_create    arguments are checked before a device is looked for (JAERO_EINVAL: decim not 16 / 32 / 64, nchannels < 1, ntaps
  *                        outside [1, 8193], max_write_iq < 1, null pointers, a gain that is not finite and positive, a tap that is not
  *                        finite), then JAERO_ENODEV off gfx950 (no CPU fallback).  ch: nchannels entries.  max_write_iq: most I/Q pairs per write.
+ *   jaero_chan2_create   the same checks in the same order with decim in {16, 32, 64, 128, 256} and, behind decim, out_rate in {48000, 24000,
+ *                        12000}; jaero_chan_create(.., decim, ..) = jaero_chan2_create(.., decim, 48000, ..) behind its own check of decim.  The
+ *                        handle is the same jaero_chan: every call below works on it.
  *   jaero_chan_write     niq I/Q pairs (2 niq int16; host or device pointer), enqueued on `stream`; *nout = samples per channel this write
  *                        produced (a multiple of Mo, at most (max_write_iq / Hp + 1) Mo; 0 when no block was completed).  niq < 0 or
  *                        niq > max_write_iq: JAERO_EINVAL, nothing consumed.  An error behind the first launch that advances the state
@@ -299,16 +304,18 @@ int jaero_ingest_stats(const jaero_ingest *ing, long long *three);
  *                        writes already enqueued keep the old words).  The phase is absolute in m, so nothing else is carried.
  *   jaero_chan_feed      = jaero_chan_write followed, when *nout > 0, by jaero_write(bank, that output, *nout, JAERO_PCM_CHANNEL_MAJOR, 1,
  *                        stream): no host copy, no synchronisation.  JAERO_EINVAL, before anything advances, for a bank on another device,
- *                        with another channel count, with Fs != 48000, or whose max_write_samples is below (max_write_iq / Hp + 1) Mo.
+ *                        with another channel count, with a channel whose Fs is not the handle's out_rate, or whose max_write_samples is below (max_write_iq / Hp + 1) Mo.
  *   jaero_chan_profile_* HIP-event time per kernel since the last reset: which 0 = forward transform (k_chan_fwd), 1 = per-channel
  *                        synthesis (k_chan_synth).
- * Deliberately not here: sockets and SDR drivers, input formats other than int16 I/Q, other decimations, per-channel filters, output rates
- * other than 48 kHz (MSK banks at 24 / 12 kHz keep being fed by the caller), the multi-GPU fan-out of a capture (every rank creates a
+ * Deliberately not here: sockets and SDR drivers, input formats other than int16 I/Q, other decimations, other N or hop, per-channel filters,
+ * burst and OQPSK banks at other rates than 48 kHz (the reference has none either), the multi-GPU fan-out of a capture (every rank creates a
  * channeliser over its shard and is handed the same I/Q). */
 typedef struct jaero_chan jaero_chan;
 typedef struct jaero_chan_channel { uint32_t tune, audio; double gain; } jaero_chan_channel;
 int jaero_chan_create(int device, int decim, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps, int max_write_iq,
                       jaero_chan **out);
+int jaero_chan2_create(int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps,
+                       int max_write_iq, jaero_chan **out);
 void jaero_chan_destroy(jaero_chan *c);
 int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout);
 int jaero_chan_pcm_view(jaero_chan *c, void **dev_pcm, int *nsamples);

@@ -33,7 +33,7 @@ EXPORTS = [
     "jaero_ingest_create", "jaero_ingest_destroy", "jaero_ingest_push", "jaero_ingest_queued", "jaero_ingest_pump",
     "jaero_ingest_stats",
     "jaero_chan_create", "jaero_chan_destroy", "jaero_chan_write", "jaero_chan_pcm_view", "jaero_chan_read_pcm", "jaero_chan_retune",
-    "jaero_chan_feed", "jaero_chan_profile_enable", "jaero_chan_profile_read",
+    "jaero_chan_feed", "jaero_chan_profile_enable", "jaero_chan_profile_read", "jaero_chan2_create",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -71,7 +71,7 @@ class CoarseState(C.Structure):
 
 
 class ChanChannel(C.Structure):
-    """struct jaero_chan_channel: tuning word (centre = tune * Fs_in / 2^32, signed), audio word (offset = audio * 48000 / 2^32), gain."""
+    """struct jaero_chan_channel: tuning word (centre = tune * Fs_in / 2^32, signed), audio word (offset = audio * out_rate / 2^32), gain."""
 
     _fields_ = [("tune", C.c_uint32), ("audio", C.c_uint32), ("gain", C.c_double)]
 
@@ -160,6 +160,7 @@ def lib():
     L.jaero_ingest_pump.argtypes = [vp, ip, vp, C.POINTER(ip)]
     L.jaero_ingest_stats.argtypes = [vp, vp]
     L.jaero_chan_create.argtypes = [ip, ip, ip, vp, vp, ip, ip, C.POINTER(vp)]
+    L.jaero_chan2_create.argtypes = [ip, ip, ip, ip, vp, vp, ip, ip, C.POINTER(vp)]
     L.jaero_chan_destroy.argtypes = [vp]
     L.jaero_chan_destroy.restype = None
     L.jaero_chan_write.argtypes = [vp, vp, ip, ip, vp, C.POINTER(ip)]

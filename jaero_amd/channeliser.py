@@ -1,7 +1,7 @@
 """Wideband I/Q channeliser in front of the demodulator banks (jaero_chan_*, include/jaero_hip.h).
 
-`Channeliser` cuts one int16 I/Q capture at 48 kHz x decim into the 48 kHz int16 audio of every channel of a bank, on the
-GPU: `feed(bank, iq)` hands its output straight to `DemodulatorBank` (device to device), `write` / `read_pcm` give it to the
+`Channeliser` cuts one int16 I/Q capture at fs_out x decim into the int16 audio at fs_out (48, 24 or 12 kHz) of every channel
+of a bank, on the GPU: `feed(bank, iq)` hands its output straight to `DemodulatorBank` (device to device), `write` / `read_pcm` give it to the
 caller.  Frequencies are 32-bit words: `tune_word(hz, fs)` is the word nearest a frequency, `word_hz(word, fs)` the
 frequency a word really is, `channel_words(tune, audio, decim)` the integers the kernels derive from a channel's words.
 All arithmetic happens in libjaero_hip.so; there is no CPU fallback.
@@ -17,8 +17,9 @@ from . import capi
 
 N = 16384          # transform length
 HP = N // 2        # hop, input samples
-DECIMS = (16, 32, 64)
+DECIMS = (16, 32, 64, 128, 256)   # total decimation, capture to output
 FS_OUT = 48000.0
+FS_OUTS = (48000.0, 24000.0, 12000.0)
 
 
 def tune_word(hz: float, fs: float) -> int:
@@ -44,9 +45,12 @@ def channel_words(tune: int, audio: int, decim: int) -> Tuple[int, int, int]:
     return b, rho, (int(audio) - rho * decim) % (1 << 32)
 
 
-def design_taps(decim: int, cutoff_hz: float = 9000.0, ntaps: int = 8193, beta: float = 16.0) -> np.ndarray:
-    """Kaiser-windowed sinc low-pass at the capture rate 48 kHz x decim: 2 fc sinc(2 fc k) kaiser(beta), unit sum."""
-    fc = cutoff_hz / (FS_OUT * decim)
+def design_taps(decim: int, cutoff_hz: Optional[float] = None, ntaps: int = 8193, beta: float = 16.0, fs_out: float = FS_OUT) -> np.ndarray:
+    """Kaiser-windowed sinc low-pass at the capture rate fs_out x decim: 2 fc sinc(2 fc k) kaiser(beta), unit sum.
+    cutoff_hz None: 9000 at 48 kHz, 0.3125 fs_out otherwise."""
+    if cutoff_hz is None:
+        cutoff_hz = 9000.0 if fs_out == FS_OUT else 0.3125 * fs_out
+    fc = cutoff_hz / (fs_out * decim)
     k = np.arange(ntaps) - (ntaps - 1) / 2
     h = 2 * fc * np.sinc(2 * fc * k) * np.kaiser(ntaps, beta)
     return h / h.sum()
@@ -61,18 +65,22 @@ def _channel_array(channels: Sequence) -> "C.Array":
 class Channeliser:
     """A bank of `len(channels)` channel filters over one capture (thin wrapper over jaero_chan).
 
-    channels: (tune word, audio word, gain) per channel.  taps: the prototype low-pass at the capture rate
-    (None: design_taps(decim)).  max_write_iq: most I/Q pairs one write may bring."""
+    channels: (tune word, audio word, gain) per channel; the audio word is relative to fs_out.  taps: the prototype low-pass
+    at the capture rate (None: design_taps(decim, fs_out=fs_out)).  max_write_iq: most I/Q pairs one write may bring.
+    fs_out: the output rate, 48000, 24000 or 12000 -- a label (the capture rate is fs_out x decim) that `feed` checks
+    against the bank's Fs; it enters no arithmetic."""
 
     def __init__(self, decim: int, channels: Sequence, taps: Optional[np.ndarray] = None, device: int = 0,
-                 max_write_iq: int = 16 * HP):
+                 max_write_iq: int = 16 * HP, fs_out: float = FS_OUT):
         self.L = capi.lib()
-        t = design_taps(decim) if taps is None else np.ascontiguousarray(taps, dtype=np.float64)
+        t = design_taps(decim, fs_out=fs_out) if taps is None else np.ascontiguousarray(taps, dtype=np.float64)
         arr = _channel_array(channels)
         h = C.c_void_p()
-        capi.check(self.L.jaero_chan_create(device, int(decim), len(arr), C.cast(arr, C.c_void_p), t.ctypes.data, int(t.size),
-                                            int(max_write_iq), C.byref(h)))
+        rate = int(fs_out) if float(fs_out) == int(fs_out) else 0  # a rate that is no integer is none of the three
+        capi.check(self.L.jaero_chan2_create(device, int(decim), rate, len(arr), C.cast(arr, C.c_void_p), t.ctypes.data, int(t.size),
+                                             int(max_write_iq), C.byref(h)))
         self.h = h
+        self.fs_out = float(fs_out)
         self.decim, self.nch, self.device, self.max_write_iq = int(decim), len(arr), device, int(max_write_iq)
         self.M = N // self.decim
         self.Mo = self.M // 2

@@ -1,6 +1,6 @@
 // chan_host.h -- host side of the wideband I/Q channeliser (k_chan.h; SURVEY 8 row f3, the channeliser half).
 //
-// One jaero_chan turns interleaved int16 I/Q at 48 kHz x D into one compact channel-major int16 array per write: exactly what jaero_write
+// One jaero_chan turns interleaved int16 I/Q at out_rate x D (out_rate 48, 24 or 12 kHz: a label that enters no arithmetic) into one compact channel-major int16 array per write: exactly what jaero_write
 // takes with JAERO_PCM_CHANNEL_MAJOR, is_device_ptr = 1.  State between writes: the input history (previous hop + the partial hop a ragged
 // write leaves; two buffers, the tail of one is copied to the head of the other behind every write that completed a block), the number of
 // blocks done, and the channels' parameters.  Everything about frequency is integer arithmetic on the host (chan_param).
@@ -10,7 +10,7 @@
 struct jaero_chan
 {
     int device = 0;
-    int decim = 0, nch = 0, max_write_iq = 0;
+    int decim = 0, out_rate = 0, nch = 0, max_write_iq = 0;
     int M = 0, Mo = 0, nblk_max = 0;
     DevMem mem;
     int *d_in[2] = {nullptr, nullptr}; // [2 Hp + max_write_iq] dwords (I, Q) each; d_in[cur] holds: previous hop, then `pending` samples
@@ -76,26 +76,30 @@ extern "C" void jaero_chan_destroy(jaero_chan *c)
     delete c;
 }
 
-extern "C" int jaero_chan_create(int device, int decim, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps,
-                                 int max_write_iq, jaero_chan **out)
+// decim: the total decimation from the capture to the output; out_rate: what the output is called (jaero_chan_feed compares it with the bank's Fs)
+extern "C" int jaero_chan2_create(int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps,
+                                  int max_write_iq, jaero_chan **out)
 {
-    if (!out) return fail(JAERO_EINVAL, "jaero_chan_create: out is null");
+    if (!out) return fail(JAERO_EINVAL, "jaero_chan2_create: out is null");
     *out = nullptr;
-    if (!ch || !taps) return fail(JAERO_EINVAL, "jaero_chan_create: null channels / taps");
-    if (decim != 16 && decim != 32 && decim != 64) return fail(JAERO_EINVAL, "jaero_chan_create: decim %d is not 16, 32 or 64", decim);
-    if (nchannels < 1) return fail(JAERO_EINVAL, "jaero_chan_create: nchannels %d < 1", nchannels);
-    if (ntaps < 1 || ntaps > CHAN_N / 2 + 1) return fail(JAERO_EINVAL, "jaero_chan_create: ntaps %d outside [1, %d]", ntaps, CHAN_N / 2 + 1);
-    if (max_write_iq < 1) return fail(JAERO_EINVAL, "jaero_chan_create: max_write_iq %d < 1", max_write_iq);
+    if (!ch || !taps) return fail(JAERO_EINVAL, "jaero_chan2_create: null channels / taps");
+    if (decim != 16 && decim != 32 && decim != 64 && decim != 128 && decim != 256)
+        return fail(JAERO_EINVAL, "jaero_chan2_create: decim %d is not 16, 32, 64, 128 or 256", decim);
+    if (out_rate != 48000 && out_rate != 24000 && out_rate != 12000)
+        return fail(JAERO_EINVAL, "jaero_chan2_create: out_rate %d is not 48000, 24000 or 12000", out_rate);
+    if (nchannels < 1) return fail(JAERO_EINVAL, "jaero_chan2_create: nchannels %d < 1", nchannels);
+    if (ntaps < 1 || ntaps > CHAN_N / 2 + 1) return fail(JAERO_EINVAL, "jaero_chan2_create: ntaps %d outside [1, %d]", ntaps, CHAN_N / 2 + 1);
+    if (max_write_iq < 1) return fail(JAERO_EINVAL, "jaero_chan2_create: max_write_iq %d < 1", max_write_iq);
     for (int i = 0; i < nchannels; i++)
-        if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "jaero_chan_create: channel %d: gain %g is not finite and positive", i, ch[i].gain);
+        if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "jaero_chan2_create: channel %d: gain %g is not finite and positive", i, ch[i].gain);
     for (int i = 0; i < ntaps; i++)
-        if (!__builtin_isfinite(taps[i])) return fail(JAERO_EINVAL, "jaero_chan_create: tap %d is not finite", i);
+        if (!__builtin_isfinite(taps[i])) return fail(JAERO_EINVAL, "jaero_chan2_create: tap %d is not finite", i);
     { const int rc = open_device(device); if (rc) return rc; }
 
     std::unique_ptr<jaero_chan> c(new (std::nothrow) jaero_chan());
-    if (!c) return fail(JAERO_ENOMEM, "jaero_chan_create: out of memory");
+    if (!c) return fail(JAERO_ENOMEM, "jaero_chan2_create: out of memory");
     int rc = 0;
-    c->device = device; c->decim = decim; c->nch = nchannels; c->max_write_iq = max_write_iq;
+    c->device = device; c->decim = decim; c->out_rate = out_rate; c->nch = nchannels; c->max_write_iq = max_write_iq;
     c->M = CHAN_N / decim; c->Mo = c->M / 2;
     c->nblk_max = max_write_iq / CHAN_HP + 1;
     c->channels.assign(ch, ch + nchannels);
@@ -119,6 +123,15 @@ extern "C" int jaero_chan_create(int device, int decim, int nchannels, const jae
     return 0;
 }
 
+// the 48 kHz channeliser of ABI 1: its own range of decim, everything else is jaero_chan2_create's
+extern "C" int jaero_chan_create(int device, int decim, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps,
+                                 int max_write_iq, jaero_chan **out)
+{
+    if (out) *out = nullptr;
+    if (decim != 16 && decim != 32 && decim != 64) return fail(JAERO_EINVAL, "jaero_chan_create: decim %d is not 16, 32 or 64", decim);
+    return jaero_chan2_create(device, decim, 48000, nchannels, ch, taps, ntaps, max_write_iq, out);
+}
+
 static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipStream_t st)
 {
     const long long nitems = (long long)c->nch * nblk;
@@ -128,7 +141,9 @@ static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipSt
     };
     if (c->decim == 16) go(k_chan_synth<16>, ChanShape<16>::ITEMS, ChanShape<16>::THREADS);
     else if (c->decim == 32) go(k_chan_synth<32>, ChanShape<32>::ITEMS, ChanShape<32>::THREADS);
-    else go(k_chan_synth<64>, ChanShape<64>::ITEMS, ChanShape<64>::THREADS);
+    else if (c->decim == 64) go(k_chan_synth<64>, ChanShape<64>::ITEMS, ChanShape<64>::THREADS);
+    else if (c->decim == 128) go(k_chan_synth<128>, ChanShape<128>::ITEMS, ChanShape<128>::THREADS);
+    else go(k_chan_synth<256>, ChanShape<256>::ITEMS, ChanShape<256>::THREADS);
 }
 
 extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
@@ -220,7 +235,8 @@ extern "C" int jaero_chan_feed(jaero_chan *c, jaero_ctx *bank, const int16_t *iq
     if (bank->device != c->device) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank is on device %d, the channeliser on %d", bank->device, c->device);
     if (bank->o_nch != c->nch) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank has %d channels, the channeliser %d", bank->o_nch, c->nch);
     for (const jaero_settings &s : bank->settings)
-        if (s.Fs != 48000.0) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank runs at Fs = %g; the channeliser's output is 48000", s.Fs);
+        if (s.Fs != (double)c->out_rate)
+            return fail(JAERO_EINVAL, "jaero_chan_feed: the bank runs at Fs = %g; the channeliser's output is %d", s.Fs, c->out_rate);
     if (bank->max_write < c->nblk_max * c->Mo)
         return fail(JAERO_EINVAL, "jaero_chan_feed: the bank's max_write_samples %d is below (max_write_iq / %d + 1) * %d = %d", bank->max_write,
                     CHAN_HP, c->Mo, c->nblk_max * c->Mo);

@@ -13,7 +13,11 @@
 //   256 = 16 x 16 (T = 16), 1024 = 32 x 32 (T = 32): thread k1 does the R2-point FFT.  512 = 16 x 32 (T = 32): the 32-point FFT of row k1
 //   is split over two threads by one decimation-in-frequency step: thread (k1, h) forms (a[n] + (-1)^h a[n + 16]) W_32^(h n) and its FFT16
 //   gives k2 = 2 j + h -- sign and twiddle are per-thread VALUES, so both halves run the same instructions.
-// The inverse transform is the forward one on swapped planes.  Index maps and bank behaviour: tests/test_chan_fft_model.py.
+//   D is the TOTAL decimation from the capture to the output, whatever the output rate is called (48, 24 or 12 kHz).  The two small shapes
+//   mirror two of the above with 8-point transforms: 64 = 8 x 8 (T = 8) is the 256 case, 128 = 8 x 16 (T = 16) the 512 case with
+//   W_16^(h n) in the split step.  Their threads hold 4 outputs each and store them as one 8-byte word.
+// The inverse transform is the forward one on swapped planes.  Index maps and bank behaviour: tests/test_chan_fft_model.py,
+// tests/test_chan_rates_fft_model.py (the two small shapes).
 #pragma once
 #include "k_coarse6.h"
 
@@ -54,16 +58,16 @@ template <int D>
 struct ChanShape
 {
     static constexpr int M = CHAN_N / D, MO = M / 2;
-    static constexpr int R1 = M == 1024 ? 32 : 16;     // pass 1: points per thread
-    static constexpr int R2 = M == 256 ? 16 : 32;      // = T, threads per item
-    static constexpr int P2 = M == 1024 ? 32 : 16;     // pass 2: points per thread's FFT
+    static constexpr int R1 = M == 1024 ? 32 : M >= 256 ? 16 : 8;             // pass 1: points per thread
+    static constexpr int R2 = M == 64 ? 8 : (M == 256 || M == 128) ? 16 : 32; // = T, threads per item
+    static constexpr int P2 = M == 1024 ? 32 : M >= 256 ? 16 : 8;             // pass 2: points per thread's FFT
     static constexpr int SPLIT = R2 / P2;              // 2: a row's FFT_R2 shared by two threads
     static constexpr int T = R2;
     static constexpr int ITEMS = M == 1024 ? 4 : 256 / T; // (channel, block) items per workgroup
-    static constexpr int THREADS = ITEMS * T;          // 256, 256, 128
+    static constexpr int THREADS = ITEMS * T;          // 128 (M = 1024), else 256
     static constexpr int ROW = R2 + 1;                 // odd row stride of the exchange: 16 lanes that differ in k1 hit 16 bank pairs
     static constexpr int XCH = R1 * ROW;               // doubles per item
-    static constexpr int OUTS = MO / T;                // int16 each thread stores: 8, 8, 16
+    static constexpr int OUTS = MO / T;                // int16 each thread stores: 16 (M = 1024), 8 (512, 256), 4 (128, 64)
 };
 
 // exchange address of (k1, n2)
@@ -82,6 +86,28 @@ __device__ __forceinline__ void chan_twiddle32(CV<32> &v, const double2 step)
         const double r = v.r[k] * w.x - v.i[k] * w.y, i = v.r[k] * w.y + v.i[k] * w.x;
         v.r[k] = r; v.i[k] = i;
     }
+}
+
+// v[k] *= step^k (k < 8)
+__device__ __forceinline__ void chan_twiddle8(CV<8> &v, const double2 step)
+{
+#pragma clang fp contract(fast)
+    double2 w[8];
+    w[1] = step; w[2] = cmul2(step, step); w[3] = cmul2(w[2], step); w[4] = cmul2(w[2], w[2]);
+    w[5] = cmul2(w[4], step); w[6] = cmul2(w[4], w[2]); w[7] = cmul2(w[4], w[3]);
+#pragma unroll
+    for (int k = 1; k < 8; k++)
+    {
+        const double r = v.r[k] * w[k].x - v.i[k] * w[k].y, i = v.r[k] * w[k].y + v.i[k] * w[k].x;
+        v.r[k] = r; v.i[k] = i;
+    }
+}
+
+template <int L> __device__ __forceinline__ void chan_twiddle(CV<L> &v, const double2 step)
+{
+    if constexpr (L == 32) chan_twiddle32(v, step);
+    else if constexpr (L == 16) c4_twiddle16(v, step);
+    else chan_twiddle8(v, step);
 }
 
 template <int L> __device__ __forceinline__ void chan_fft(CV<L> &in, CV<L> &out)
@@ -124,11 +150,7 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
         a.r[n1] = x.x * g.y + x.y * g.x;
     }
     chan_fft<R1>(a, A);
-    {
-        const double2 st = twm[u]; // W_M^n2
-        if constexpr (R1 == 32) chan_twiddle32(A, st);
-        else c4_twiddle16(A, st);
-    }
+    chan_twiddle<R1>(A, twm[u]); // W_M^n2
     // ---- exchange (a plane at a time) + the split's radix-2 step ----
     const int k1 = u % R1, h = u / R1; // h = 0 unless SPLIT == 2
     CV<P2> e, E;
@@ -152,7 +174,7 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
         if constexpr (S::SPLIT == 2) e.i[n] = xch[chan_xaddr<D>(k1, n)] + sg * xch[chan_xaddr<D>(k1, n + P2)];
         else e.i[n] = xch[chan_xaddr<D>(k1, n)];
     }
-    if constexpr (S::SPLIT == 2) c4_twiddle16(e, h ? make_double2(jd_w64r(2), jd_w64i(2)) : make_double2(1.0, 0.0)); // W_32^(h n)
+    if constexpr (S::SPLIT == 2) chan_twiddle<P2>(e, h ? make_double2(jd_w64r(64 / R2), jd_w64i(64 / R2)) : make_double2(1.0, 0.0)); // W_R2^(h n)
     // ---- pass 2: only the outputs with k2 >= R2 / 2 are used below ----
     chan_fft<P2>(e, E);
 
@@ -179,10 +201,21 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
     jd_lds_barrier();
     if (live)
     {
-        typedef int chan_v4 __attribute__((ext_vector_type(4)));
-        const chan_v4 *sv = (const chan_v4 *)stage;
-        chan_v4 *__restrict__ dst = (chan_v4 *)(pcm + ((size_t)c * nblk + j) * MO);
+        if constexpr (S::OUTS % 8 == 0)
+        {
+            typedef int chan_v4 __attribute__((ext_vector_type(4)));
+            const chan_v4 *sv = (const chan_v4 *)stage;
+            chan_v4 *__restrict__ dst = (chan_v4 *)(pcm + ((size_t)c * nblk + j) * MO);
 #pragma unroll
-        for (int v = 0; v < S::OUTS / 8; v++) dst[v * T + u] = sv[v * T + u];
+            for (int v = 0; v < S::OUTS / 8; v++) dst[v * T + u] = sv[v * T + u];
+        }
+        else // OUTS == 4: the item's Mo samples are T 8-byte words, one per lane
+        {
+            static_assert(S::OUTS == 4, "a thread's outputs are whole 16-byte words or one 8-byte word");
+            typedef int chan_v2 __attribute__((ext_vector_type(2)));
+            const chan_v2 *sv = (const chan_v2 *)stage;
+            chan_v2 *__restrict__ dst = (chan_v2 *)(pcm + ((size_t)c * nblk + j) * MO);
+            dst[u] = sv[u];
+        }
     }
 }

@@ -417,3 +417,36 @@ def wideband_oqpsk(bits_list, centres, amps, decim: int, *, fb: float = 10500.0,
     if return_info:
         return out, {"scale": float(scale), "p_unit": p_unit}
     return out
+
+
+def wideband_msk(bits_list, centres, amps, fs_in: float, *, fb: float = 600.0, ebno_db: float | None = 13.0, rms: float = 0.1,
+                 seed: int = 7, nsamples: int | None = None, return_info: bool = False):
+    """A synthetic capture of continuous MSK channels for the channeliser: int16 I/Q [nsamples, 2] at `fs_in` holding one channel
+    per entry of `bits_list` -- the complex CPFSK of `msk` (h = 0.5: bit k holds the frequency at +-fb / 4 for fs_in / fb samples,
+    the phase is continuous) times amps[c], shifted to centres[c] Hz -- summed, white noise added at `ebno_db` for a channel of
+    amplitude min(amps), scaled to `rms` of full scale per complex sample, rounded and clipped as `wideband_oqpsk` does.
+    return_info: also {"scale": LSB per unit of the sum, "p_unit": power of a unit-amplitude channel's complex baseband (1)}."""
+    sps = fs_in / fb
+    if nsamples is None:
+        nsamples = int(np.ceil(max(len(b) for b in bits_list) * sps))
+    n = np.arange(nsamples, dtype=np.float64)
+    kbit = (n / sps).astype(np.int64)
+    x = np.zeros(nsamples, dtype=np.complex128)
+    p_unit = 1.0
+    for bits, fc, amp in zip(bits_list, centres, amps):
+        bits = np.asarray(bits)
+        k = np.minimum(kbit, bits.shape[0] - 1)
+        dev = (2.0 * bits[k].astype(np.float64) - 1.0) * (fb / 4.0)  # +-fb/4 Hz
+        cyc = np.cumsum(dev / fs_in) + (fc * n / fs_in) % 1.0
+        x += amp * np.exp(2j * np.pi * (cyc % 1.0))
+    if ebno_db is not None:
+        rng = np.random.default_rng(seed)
+        sigma2 = min(amps) ** 2 * p_unit * fs_in / (fb * 10.0 ** (ebno_db / 10.0))
+        x = x + np.sqrt(sigma2 / 2.0) * (rng.normal(size=nsamples) + 1j * rng.normal(size=nsamples))
+    scale = rms * 32768.0 / np.sqrt(np.mean(np.abs(x) ** 2))
+    out = np.empty((nsamples, 2), dtype=np.int16)
+    out[:, 0] = np.clip(np.rint(x.real * scale), -32768, 32767)
+    out[:, 1] = np.clip(np.rint(x.imag * scale), -32768, 32767)
+    if return_info:
+        return out, {"scale": float(scale), "p_unit": p_unit}
+    return out

@@ -1,8 +1,9 @@
-"""Timing of the channeliser in front of the headline OQPSK bank: Channeliser.feed of 16 hops (131 072 I/Q pairs at D = 32 -> 4096 samples per
+"""Timing of the channeliser in front of a demodulator bank: Channeliser.feed of 16 hops (131 072 I/Q pairs; at D = 32 -> 4096 samples per
 channel) per step.  Prints one JSON line: HIP-event time per step of k_chan_fwd and k_chan_synth, of the bank's sample loop and coarse estimate
 from the same steps, their ratio (the yardstick: the two channeliser kernels together against the demodulator bank's own step time), the
-engine clock over the timed steps.
-usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup]"""
+same per second of signal and per output sample, the engine clock over the timed steps.  Defaults: the headline OQPSK bank behind D = 32.
+usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup] [--decim D] [--fs-out 48000|24000|12000] [--bank oqpsk|msk600|msk1200]"""
+import argparse
 import json
 import os
 import sys
@@ -15,17 +16,27 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from bench_state import GpuStateSampler  # noqa: E402
 from jaero_amd.channeliser import HP, Channeliser  # noqa: E402
-from jaero_amd.demodulator import DemodulatorBank, OqpskSettings  # noqa: E402
+from jaero_amd.demodulator import DemodulatorBank, MskSettings, OqpskSettings  # noqa: E402
 
-nch = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-K = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-W = int(sys.argv[3]) if len(sys.argv) > 3 else 5
-decim, hops = 32, 16
+ap = argparse.ArgumentParser()
+ap.add_argument("channels", nargs="?", type=int, default=65536)
+ap.add_argument("steps", nargs="?", type=int, default=50)
+ap.add_argument("warmup", nargs="?", type=int, default=5)
+ap.add_argument("--decim", type=int, default=32, help="total decimation, capture to output")
+ap.add_argument("--fs-out", type=float, default=48000.0, help="the channeliser's output rate = the bank's Fs")
+ap.add_argument("--bank", choices=("oqpsk", "msk600", "msk1200"), default="oqpsk")
+args = ap.parse_args()
+nch, K, W, decim, fs_out, hops = args.channels, args.steps, args.warmup, args.decim, args.fs_out, 16
 rng = np.random.default_rng(1)
 iq = torch.from_numpy(rng.integers(-8000, 8000, size=(hops * HP, 2), dtype=np.int16)).cuda()
 chans = [(int(t), 715827883, 1.0) for t in rng.integers(0, 1 << 32, size=nch, dtype=np.uint64)]
-chan = Channeliser(decim, chans, max_write_iq=hops * HP)
-bank = DemodulatorBank(OqpskSettings(), nch, ebno=True, max_write_samples=(hops + 1) * chan.Mo, softbit_capacity=4096)
+chan = Channeliser(decim, chans, max_write_iq=hops * HP, fs_out=fs_out)
+if args.bank == "oqpsk":
+    settings = OqpskSettings(Fs=fs_out)
+else:
+    fb = 600.0 if args.bank == "msk600" else 1200.0
+    settings = MskSettings(fb=fb, lockingbw=1.5 * fb, Fs=fs_out)
+bank = DemodulatorBank(settings, nch, ebno=True, max_write_samples=(hops + 1) * chan.Mo, softbit_capacity=4096)
 st = torch.cuda.current_stream().cuda_stream
 for _ in range(W):
     chan.feed(bank, iq, stream=st)
@@ -46,8 +57,13 @@ syn, ns = chan.profile_read(1)
 loop, nl = bank.profile_read(0)
 coarse, nc = bank.profile_read(1)
 chan_ms, bank_ms = (fwd + syn) / K, (loop + coarse) / K
+signal_s = hops * HP / (fs_out * decim)  # seconds of signal per step
 print(json.dumps({
-    "channels": nch, "decim": decim, "steps": K, "warmup": W, "samples_per_channel_per_step": hops * chan.Mo,
+    "channels": nch, "decim": decim, "fs_out": fs_out, "bank": args.bank, "bank_kernels": [bank.profile_kernel(0), bank.profile_kernel(1)],
+    "steps": K, "warmup": W, "samples_per_channel_per_step": hops * chan.Mo, "signal_ms_per_step": round(1e3 * signal_s, 4),
+    "k_chan_fwd_ms_per_signal_s": round(fwd / K / signal_s, 3), "k_chan_synth_ms_per_signal_s": round(syn / K / signal_s, 3),
+    "bank_ms_per_signal_s": round(bank_ms / signal_s, 3),
+    "k_chan_synth_ps_per_output_sample": round(1e9 * syn / K / (nch * hops * chan.Mo), 3),
     "k_chan_fwd_ms_per_step": round(fwd / K, 4), "k_chan_fwd_launches": nf,
     "k_chan_synth_ms_per_step": round(syn / K, 4), "k_chan_synth_launches": ns,
     "bank_sample_loop_ms_per_step": round(loop / K, 4), "bank_sample_loop_launches": nl,
