@@ -309,7 +309,9 @@ int jaero_ingest_stats(const jaero_ingest *ing, long long *three);
  *                        synthesis (k_chan_synth).
  * Deliberately not here: sockets and SDR drivers, input formats other than int16 I/Q, other decimations, other N or hop, per-channel filters,
  * burst and OQPSK banks at other rates than 48 kHz (the reference has none either), the multi-GPU fan-out of a capture (every rank creates a
- * channeliser over its shard and is handed the same I/Q). */
+ * channeliser over its shard and is handed the same I/Q), automatic gain control inside the synthesis (it would change the output's
+ * definition: the survey below measures, the caller sets the gains), carrier finding on the device (jaero_amd.channeliser.find_carriers is
+ * host numpy over the surveyed spectrum), modulation recognition. */
 typedef struct jaero_chan jaero_chan;
 typedef struct jaero_chan_channel { uint32_t tune, audio; double gain; } jaero_chan_channel;
 int jaero_chan_create(int device, int decim, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps, int max_write_iq,
@@ -324,6 +326,40 @@ int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_channel *ch);
 int jaero_chan_feed(jaero_chan *c, jaero_ctx *bank, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout);
 int jaero_chan_profile_enable(jaero_chan *c, int on);
 int jaero_chan_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset);
+
+/* ---- survey of a channeliser's capture: where the carriers are and how strong each channel is, measured on the device from the forward
+ * transforms X_p every write leaves behind (the notation is the channeliser's above).  Off at create; while off, a write launches and
+ * allocates nothing more than before.  This text is the definition; tests/chan_survey_oracle.py implements it literally in numpy.
+ *   spectrum   (Welch, the Hann window applied in the frequency domain)
+ *              H_p[k] = X_p[k] / 2 - (X_p[(k - 1) mod N] + X_p[(k + 1) mod N]) / 4;   S[k] = sum_p |H_p[k]|^2, k < N, over every block
+ *              completed since the spectrum was enabled or reset, added in ascending p.  S[k] / (nblocks N^2 3 / 8) is LSB^2 per bin and
+ *              sums to the mean |x|^2 of a stationary input.
+ *   level      E_c = sum_p sum_{-M/2 <= q < M/2} |X_p[(b_c + q) mod N] G[q mod N] / N|^2 over the n_c blocks completed since the levels
+ *              were enabled or reset, or since a retune last changed channel c's TUNE word (b changes: sum and count start again with the
+ *              next write); a retune that changes only audio or gain keeps both.  E_c / n_c is the mean square of the channel's complex
+ *              output sample w[r] before sign, rotation and gain (Parseval over the M-point transform, both halves of the circular block),
+ *              so the int16 output at gain g has an RMS of about g sqrt(E_c / (2 n_c)).
+ *   determinism  both sums are independent of how the writes were cut, bit for bit: a block's terms are formed by the same instructions
+ *              whatever the launch shape, the reduction over q has a fixed shape, terms join the running sum strictly in block order,
+ *              and there are no floating-point atomics.
+ *   jaero_survey_enable        what: bit 0 spectrum, bit 1 levels, 0 = off (JAERO_EINVAL for bits outside 0..3).  Synchronises, allocates what
+ *                              is enabled for the first time, clears the sums and counts of what is enabled.
+ *   jaero_survey_reset         synchronises, then clears the sums and counts of what is enabled.
+ *   jaero_survey_read_psd      synchronises on the handle's last stream; sums[16384] = S, *nblocks = the blocks in it.
+ *   jaero_survey_read_levels   the same for sums[nchannels] = E_c, nblocks[nchannels] = n_c.  Reading a part that is not enabled: JAERO_EINVAL.
+ *   jaero_survey_profile_read  HIP-event time since the last reset: which 0 = k_chan_psd, 1 = k_chan_level; switched by
+ *                              jaero_chan_profile_enable.
+ *   jaero_chan2_retune_all     jaero_chan_retune of every channel (ch: nchannels entries) behind one synchronisation, with one copy: the
+ *                              call that applies surveyed centres and gains to a bank.  Every gain is checked before anything changes;
+ *                              a channel's level restarts by the same rule.
+ * Null arguments: JAERO_EINVAL.  A poisoned handle: JAERO_EHIP; a HIP failure inside the survey's launches poisons the handle as any other
+ * failure inside a write. */
+int jaero_survey_enable(jaero_chan *c, int what);
+int jaero_survey_reset(jaero_chan *c);
+int jaero_survey_read_psd(jaero_chan *c, double *sums, long long *nblocks);
+int jaero_survey_read_levels(jaero_chan *c, double *sums, long long *nblocks);
+int jaero_survey_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset);
+int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *ch);
 
 /* Host-only debugging aid (no device needed): the sample indices at which jaero_write would run the coarse-frequency
  * estimate for a fresh channel fed `nwrites` writes of write_sizes[i] samples.  Returns the number of triggers

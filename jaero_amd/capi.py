@@ -34,6 +34,8 @@ EXPORTS = [
     "jaero_ingest_stats",
     "jaero_chan_create", "jaero_chan_destroy", "jaero_chan_write", "jaero_chan_pcm_view", "jaero_chan_read_pcm", "jaero_chan_retune",
     "jaero_chan_feed", "jaero_chan_profile_enable", "jaero_chan_profile_read", "jaero_chan2_create",
+    "jaero_survey_enable", "jaero_survey_reset", "jaero_survey_read_psd", "jaero_survey_read_levels", "jaero_survey_profile_read",
+    "jaero_chan2_retune_all",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -170,6 +172,12 @@ def lib():
     L.jaero_chan_feed.argtypes = [vp, vp, vp, ip, ip, vp, C.POINTER(ip)]
     L.jaero_chan_profile_enable.argtypes = [vp, ip]
     L.jaero_chan_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
+    L.jaero_survey_enable.argtypes = [vp, ip]
+    L.jaero_survey_reset.argtypes = [vp]
+    L.jaero_survey_read_psd.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
+    L.jaero_survey_read_levels.argtypes = [vp, vp, vp]
+    L.jaero_survey_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
+    L.jaero_chan2_retune_all.argtypes = [vp, vp]
     L.jaero_shard_range.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.jaero_comm_get_unique_id.argtypes = [vp]
     L.jaero_comm_create.argtypes = [ip, ip, ip, vp, C.POINTER(vp)]

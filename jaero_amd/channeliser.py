@@ -4,7 +4,9 @@
 of a bank, on the GPU: `feed(bank, iq)` hands its output straight to `DemodulatorBank` (device to device), `write` / `read_pcm` give it to the
 caller.  Frequencies are 32-bit words: `tune_word(hz, fs)` is the word nearest a frequency, `word_hz(word, fs)` the
 frequency a word really is, `channel_words(tune, audio, decim)` the integers the kernels derive from a channel's words.
-All arithmetic happens in libjaero_hip.so; there is no CPU fallback.
+The survey (`survey_enable`, `read_psd`, `read_levels`) measures the capture's spectrum and every channel's level on the device;
+`find_carriers` (host numpy, no hot path) turns the spectrum into centre frequencies, `suggest_gains` the levels into gains, and
+`retune_all` applies both.  All device arithmetic happens in libjaero_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -60,6 +62,39 @@ def _channel_array(channels: Sequence) -> "C.Array":
     rows = [c if isinstance(c, capi.ChanChannel) else capi.ChanChannel(int(c[0]) % (1 << 32), int(c[1]) % (1 << 32), float(c[2]))
             for c in channels]
     return (capi.ChanChannel * len(rows))(*rows)
+
+
+def find_carriers(psd: np.ndarray, fs_in: float, bw_hz: float, threshold_db: float = 6.0) -> list:
+    """Sorted centre frequencies in Hz (signed) of the carriers of width `bw_hz` in a spectrum of N bins in natural order (`read_psd`).
+
+    Smooth by a circular boxcar mean of bw_hz (in bins, forced odd); the noise floor is the median of `psd`; repeatedly take the largest
+    smoothed bin that lies at least `threshold_db` above the floor, refine it by the centroid of max(psd - floor, 0) over +-bw / 2 around
+    it and once more around the rounded first estimate, blank +-bw around the pick.  The median is the noise floor only while carriers
+    fill less than half of the band: in a fuller capture it lies on the carriers and nothing is found."""
+    psd = np.asarray(psd, dtype=np.float64)
+    n = psd.size
+    w = int(round(bw_hz / fs_in * n)) | 1
+    h = w // 2
+    cs = np.concatenate([[0.0], np.cumsum(np.concatenate([psd[n - h:], psd, psd[:h]]))])
+    smooth = (cs[w:] - cs[:-w]) / w
+    floor = float(np.median(psd))
+    excess = np.maximum(psd - floor, 0.0)
+    off = np.arange(-h, h + 1)
+    found = []
+    while True:
+        k = int(np.argmax(smooth))
+        if not smooth[k] > 0.0 or not smooth[k] >= floor * 10.0 ** (threshold_db / 10.0):
+            break
+        centre = float(k)
+        for _ in range(2):
+            k0 = int(round(centre))
+            e = excess[(k0 + off) % n]
+            if e.sum() > 0.0:
+                centre = k0 + float((e * off).sum() / e.sum())
+        smooth[(k + np.arange(-w, w + 1)) % n] = -1.0
+        c = centre % n
+        found.append((c - n if c >= n / 2 else c) * fs_in / n)
+    return sorted(found)
 
 
 class Channeliser:
@@ -140,6 +175,57 @@ class Channeliser:
     def retune(self, channel: int, tune: int, audio: int, gain: float):
         ch = capi.ChanChannel(int(tune) % (1 << 32), int(audio) % (1 << 32), float(gain))
         capi.check(self.L.jaero_chan_retune(self.h, channel, C.byref(ch)))
+
+    def retune_all(self, channels: Sequence):
+        """retune of every channel (tune word, audio word, gain) behind one synchronisation; nothing changes unless every gain is valid."""
+        arr = _channel_array(channels)
+        if len(arr) != self.nch:
+            raise ValueError(f"retune_all takes {self.nch} channels, not {len(arr)}")
+        capi.check(self.L.jaero_chan2_retune_all(self.h, C.cast(arr, C.c_void_p)))
+
+    def survey_enable(self, psd: bool = True, levels: bool = True):
+        """Switches the survey's two parts on or off; clears the sums and counts of what is on."""
+        capi.check(self.L.jaero_survey_enable(self.h, int(bool(psd)) | int(bool(levels)) << 1))
+
+    def survey_reset(self):
+        capi.check(self.L.jaero_survey_reset(self.h))
+
+    def read_psd_sums(self) -> Tuple[np.ndarray, int]:
+        """(S[N] raw, nblocks) as the ABI returns them."""
+        s, n = np.empty(N, dtype=np.float64), C.c_longlong(0)
+        capi.check(self.L.jaero_survey_read_psd(self.h, s.ctypes.data, C.byref(n)))
+        return s, n.value
+
+    def read_psd(self) -> Tuple[np.ndarray, int]:
+        """(psd[N], nblocks): S / (nblocks N^2 3 / 8), LSB^2 per bin in natural bin order (nan before the first block)."""
+        s, n = self.read_psd_sums()
+        return (s / (n * float(N) * N * 0.375) if n else np.full(N, np.nan)), n
+
+    def read_level_sums(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(E[nch] raw, counts[nch]) as the ABI returns them."""
+        e, n = np.empty(self.nch, dtype=np.float64), np.empty(self.nch, dtype=np.int64)
+        capi.check(self.L.jaero_survey_read_levels(self.h, e.ctypes.data, n.ctypes.data))
+        return e, n
+
+    def read_levels(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(level[nch] = E / n, nan where n == 0; counts[nch]): the mean square of each channel's complex output before rotation and gain."""
+        e, n = self.read_level_sums()
+        return np.where(n > 0, e / np.maximum(n, 1), np.nan), n
+
+    def suggest_gains(self, target_rms: float = 0.1 * 32768) -> np.ndarray:
+        """The gain that brings each channel's int16 output to `target_rms`: target / sqrt(level / 2).  Raises ValueError for a
+        channel that has no block yet or whose level is 0: it has no such gain (and retune_all would refuse the whole set for it)."""
+        level, counts = self.read_levels()
+        empty = np.nonzero((counts == 0) | ~(level > 0.0))[0]
+        if empty.size:
+            raise ValueError(f"suggest_gains: channels {empty[:8].tolist()} have no surveyed block or a level of 0")
+        return target_rms / np.sqrt(level / 2.0)
+
+    def survey_profile_read(self, which: int, reset: bool = False):
+        """(total ms, launches) of survey kernel `which`: 0 = spectrum (k_chan_psd), 1 = levels (k_chan_level)."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.L.jaero_survey_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
 
     def profile_enable(self, on: bool = True):
         capi.check(self.L.jaero_chan_profile_enable(self.h, int(on)))

@@ -24,7 +24,15 @@ struct jaero_chan
     int16_t *d_pcm = nullptr;  // [nch][nout of the last write], capacity nch * nblk_max * Mo
     int last_nout = 0;
     std::vector<jaero_chan_channel> channels;
-    KernelTimer timer{2};
+    KernelTimer timer{4};      // 0 k_chan_fwd, 1 k_chan_synth, 2 k_chan_psd, 3 k_chan_level
+    // the survey (jaero_survey_*): nothing below exists before the first enable
+    int survey = 0;            // bit 0 spectrum, bit 1 levels
+    double *d_psd = nullptr;   // [N]: S
+    double *d_lvl = nullptr;   // [nch]: E
+    double *d_g2 = nullptr;    // [M]: |G[q mod N]|^2 / N^2 at q = i - M / 2
+    long long psd_blocks = 0;  // blocks in S
+    long long lvl_blocks = 0;  // blocks surveyed for levels since enable / reset; channel c's count is lvl_blocks - lvl_start[c]
+    std::vector<long long> lvl_start;
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
     bool poisoned = false;
@@ -132,6 +140,20 @@ extern "C" int jaero_chan_create(int device, int decim, int nchannels, const jae
     return jaero_chan2_create(device, decim, 48000, nchannels, ch, taps, ntaps, max_write_iq, out);
 }
 
+static void chan_launch_level(const jaero_chan *c, int nblk, hipStream_t st)
+{
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((c->nch + CHAN_LVL_THREADS / CHAN_LVL_T - 1) / (CHAN_LVL_THREADS / CHAN_LVL_T))),
+                           dim3(CHAN_LVL_THREADS), 0, st, (const double2 *)c->d_spec, (const double *)c->d_g2, (const ChanParam *)c->d_par,
+                           c->d_lvl, c->nch, nblk);
+    };
+    if (c->decim == 16) go(k_chan_level<16>);
+    else if (c->decim == 32) go(k_chan_level<32>);
+    else if (c->decim == 64) go(k_chan_level<64>);
+    else if (c->decim == 128) go(k_chan_level<128>);
+    else go(k_chan_level<256>);
+}
+
 static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipStream_t st)
 {
     const long long nitems = (long long)c->nch * nblk;
@@ -179,6 +201,22 @@ extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int i
         chan_launch_synth(c, nblk, c->blocks_done, st);
         LAUNCHCHK("k_chan_synth");
         c->timer.end(pi, st);
+        if (c->survey & 1)
+        {
+            pi = c->timer.begin(2, st);
+            hipLaunchKernelGGL(k_chan_psd, dim3(CHAN_N / CHAN_PSD_THREADS), dim3(CHAN_PSD_THREADS), 0, st, (const double2 *)c->d_spec, c->d_psd, nblk);
+            LAUNCHCHK("k_chan_psd");
+            c->timer.end(pi, st);
+            c->psd_blocks += nblk;
+        }
+        if (c->survey & 2)
+        {
+            pi = c->timer.begin(3, st);
+            chan_launch_level(c, nblk, st);
+            LAUNCHCHK("k_chan_level");
+            c->timer.end(pi, st);
+            c->lvl_blocks += nblk;
+        }
         // the last hop and what lies behind it become the other buffer's head
         const int rest = total - nblk * CHAN_HP;
         HIPCHK(hipMemcpyAsync(c->d_in[c->cur ^ 1], in + (size_t)nblk * CHAN_HP, sizeof(int) * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
@@ -224,8 +262,48 @@ extern "C" int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_ch
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far keep the old words
     const ChanParam p = chan_param(*ch, c->decim);
+    c->poisoned = true; // the words, the sum and the count change together or not at all
     HIPCHK(hipMemcpy(c->d_par + channel, &p, sizeof p, hipMemcpyHostToDevice));
+    if ((c->survey & 2) && ch->tune != c->channels[channel].tune) // another b: the level starts again with the next write
+    {
+        HIPCHK(hipMemset(c->d_lvl + channel, 0, sizeof(double)));
+        c->lvl_start[channel] = c->lvl_blocks;
+    }
     c->channels[channel] = *ch;
+    c->poisoned = false;
+    return 0;
+}
+
+// jaero_chan_retune of every channel behind one synchronisation, with one copy; nothing changes unless every gain is valid
+extern "C" int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *ch)
+{
+    if (!c || !ch) return fail(JAERO_EINVAL, "jaero_chan2_retune_all: null argument");
+    for (int i = 0; i < c->nch; i++)
+        if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "jaero_chan2_retune_all: channel %d: gain %g is not finite and positive", i, ch[i].gain);
+    CHANPOISONCHK(c, "jaero_chan2_retune_all");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far keep the old words
+    std::vector<ChanParam> par(c->nch);
+    for (int i = 0; i < c->nch; i++) par[i] = chan_param(ch[i], c->decim);
+    c->poisoned = true; // the words, the sums and the counts change together or not at all
+    HIPCHK(hipMemcpy(c->d_par, par.data(), sizeof(ChanParam) * c->nch, hipMemcpyHostToDevice));
+    if (c->survey & 2)
+    {
+        int first = -1; // the channels whose tune word changes, zeroed a run at a time
+        for (int i = 0; i <= c->nch; i++)
+        {
+            const bool moved = i < c->nch && ch[i].tune != c->channels[i].tune;
+            if (moved && first < 0) first = i;
+            if (!moved && first >= 0)
+            {
+                HIPCHK(hipMemset(c->d_lvl + first, 0, sizeof(double) * (size_t)(i - first)));
+                first = -1;
+            }
+            if (moved) c->lvl_start[i] = c->lvl_blocks;
+        }
+    }
+    c->channels.assign(ch, ch + c->nch);
+    c->poisoned = false;
     return 0;
 }
 
@@ -256,4 +334,92 @@ extern "C" int jaero_chan_profile_read(jaero_chan *c, int which, double *total_m
 {
     if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_chan_profile_read: bad arguments");
     return c->timer.read(c->device, which, total_ms, launches, reset);
+}
+
+// ------------------------------------------------------------------------------------------ survey
+static int survey_clear(jaero_chan *c)
+{
+    if (c->survey & 1)
+    {
+        HIPCHK(hipMemset(c->d_psd, 0, sizeof(double) * CHAN_N));
+        c->psd_blocks = 0;
+    }
+    if (c->survey & 2)
+    {
+        HIPCHK(hipMemset(c->d_lvl, 0, sizeof(double) * (size_t)c->nch));
+        c->lvl_blocks = 0;
+        c->lvl_start.assign(c->nch, 0);
+    }
+    return 0;
+}
+
+extern "C" int jaero_survey_enable(jaero_chan *c, int what)
+{
+    if (what < 0 || what > 3) return fail(JAERO_EINVAL, "jaero_survey_enable: what %d has bits outside 0..3", what);
+    if (!c) return fail(JAERO_EINVAL, "jaero_survey_enable: null ctx");
+    CHANPOISONCHK(c, "jaero_survey_enable");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far are surveyed as they were enqueued
+    int rc = 0;
+    if ((what & 1) && !c->d_psd) DA(c->mem, c->d_psd, CHAN_N);
+    if ((what & 2) && !c->d_g2)
+    {
+        if (!c->d_lvl) DA(c->mem, c->d_lvl, c->nch);
+        double *d_g2 = nullptr;
+        DA(c->mem, d_g2, c->M);
+        // |G / N|^2 of the response the synthesis multiplies by, from its order (k < M / 2: q = k, else q = k - M) to ascending q
+        std::vector<double2> gm(c->M);
+        std::vector<double> g2(c->M);
+        HIPCHK(hipMemcpy(gm.data(), c->d_gm, sizeof(double2) * c->M, hipMemcpyDeviceToHost));
+        for (int i = 0; i < c->M; i++)
+        {
+            const double2 g = gm[(i - c->M / 2) & (c->M - 1)];
+            g2[i] = g.x * g.x + g.y * g.y;
+        }
+        HIPCHK(hipMemcpy(d_g2, g2.data(), sizeof(double) * c->M, hipMemcpyHostToDevice));
+        c->d_g2 = d_g2; // the levels can be enabled only with the table in place
+    }
+    c->survey = what;
+    rc = survey_clear(c);
+    if (rc) c->survey = 0; // a failed clear leaves the survey off
+    return rc;
+}
+
+extern "C" int jaero_survey_reset(jaero_chan *c)
+{
+    if (!c) return fail(JAERO_EINVAL, "jaero_survey_reset: null ctx");
+    CHANPOISONCHK(c, "jaero_survey_reset");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    return survey_clear(c);
+}
+
+extern "C" int jaero_survey_read_psd(jaero_chan *c, double *sums, long long *nblocks)
+{
+    if (!c || !sums || !nblocks) return fail(JAERO_EINVAL, "jaero_survey_read_psd: null argument");
+    if (!(c->survey & 1)) return fail(JAERO_EINVAL, "jaero_survey_read_psd: the spectrum is not enabled (jaero_survey_enable bit 0)");
+    CHANPOISONCHK(c, "jaero_survey_read_psd");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    HIPCHK(hipMemcpy(sums, c->d_psd, sizeof(double) * CHAN_N, hipMemcpyDeviceToHost));
+    *nblocks = c->psd_blocks;
+    return 0;
+}
+
+extern "C" int jaero_survey_read_levels(jaero_chan *c, double *sums, long long *nblocks)
+{
+    if (!c || !sums || !nblocks) return fail(JAERO_EINVAL, "jaero_survey_read_levels: null argument");
+    if (!(c->survey & 2)) return fail(JAERO_EINVAL, "jaero_survey_read_levels: the levels are not enabled (jaero_survey_enable bit 1)");
+    CHANPOISONCHK(c, "jaero_survey_read_levels");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    HIPCHK(hipMemcpy(sums, c->d_lvl, sizeof(double) * (size_t)c->nch, hipMemcpyDeviceToHost));
+    for (int i = 0; i < c->nch; i++) nblocks[i] = c->lvl_blocks - c->lvl_start[i];
+    return 0;
+}
+
+extern "C" int jaero_survey_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset)
+{
+    if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_survey_profile_read: bad arguments");
+    return c->timer.read(c->device, 2 + which, total_ms, launches, reset);
 }

@@ -219,3 +219,72 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------ survey (jaero_survey_*, DESIGN 18 "Survey")
+// Two running sums over the forward transforms k_chan_fwd has just left in spec, launched behind k_chan_synth when enabled.  Both are
+// independent of how the writes were cut: a block's term is formed by the same instructions whatever the launch shape, and a sum takes its
+// terms strictly in block order (one owner per sum, no atomics).  The library is built with -ffp-contract=off and nothing here turns
+// contraction on: every product and sum below rounds once, as the numpy definition's (tests/chan_survey_oracle.py).
+
+// Capture spectrum: S[k] += |H_p[k]|^2, H_p[k] = X_p[k] / 2 - (X_p[k - 1] + X_p[k + 1]) / 4 (indices mod N): the Hann window applied in the
+// frequency domain.  Thread k owns bin k over the write's blocks in order; one load and one store of S[k] per write.  The neighbours are
+// plain loads: a wavefront's three loads cover bins k0 - 1 .. k0 + 64, so the outer two ask for the lines the centre load asks for, and
+// the kernel moves 256 KB per block whatever is done here.  One wavefront per workgroup, 256 workgroups: with three loads in flight per
+// thread and block the walk over the blocks is bound by latency, and this spreads it over every CU.  Neither choice has been measured
+// against its alternative (neighbours by shuffle, wider workgroups); the whole kernel is timed in DESIGN 18.
+#define CHAN_PSD_THREADS 64
+__global__ __launch_bounds__(CHAN_PSD_THREADS) void k_chan_psd(const double2 *__restrict__ spec, double *__restrict__ S, int nblk)
+{
+    const int k = blockIdx.x * CHAN_PSD_THREADS + threadIdx.x; // the grid is N / CHAN_PSD_THREADS workgroups: k < N
+    const int km = (k - 1) & (CHAN_N - 1), kp = (k + 1) & (CHAN_N - 1);
+    double s = S[k];
+    for (int j = 0; j < nblk; j++)
+    {
+        const double2 *__restrict__ X = spec + (size_t)j * CHAN_N;
+        const double2 a = X[km], x = X[k], b = X[kp];
+        const double hr = 0.5 * x.x - 0.25 * (a.x + b.x), hi = 0.5 * x.y - 0.25 * (a.y + b.y);
+        s += hr * hr + hi * hi;
+    }
+    S[k] = s;
+}
+
+// Per-channel level: E[c] += sum_q |X_p[(b + q) mod N]|^2 g2[q + M / 2], -M/2 <= q < M/2, g2 = |G[q mod N]|^2 / N^2 (built at enable from
+// the response k_chan_synth multiplies by), for the write's blocks in order.  One channel per group of T = 16 lanes: lane u takes the bins
+// q = -M/2 + u + 16 i in ascending i (a load instruction of the group reads 256 contiguous bytes of the bin run, which may wrap at N as
+// k_chan_synth's), one accumulator per lane, then a 4-step xor butterfly inside the group (every lane ends with the same sum: the shape is
+// fixed), and lane 0 adds the block's sum to the running one it loaded once and stores once.  T = 16 for every M: 16 channels per
+// workgroup fill the chip from 4096 channels on, and M / 16 = 4 .. 64 independent 16-byte loads per lane and block hide the L2 latency.
+// The table sits in LDS (M doubles).  Spare groups of the last workgroup redo the last channel and store nothing.
+#define CHAN_LVL_T 16
+#define CHAN_LVL_THREADS 256
+template <int D>
+__global__ __launch_bounds__(CHAN_LVL_THREADS) void k_chan_level(const double2 *__restrict__ spec, const double *__restrict__ g2,
+                                                                 const ChanParam *__restrict__ par, double *__restrict__ E, int nch, int nblk)
+{
+    constexpr int M = CHAN_N / D, T = CHAN_LVL_T, PER = M / T, UNROLL = PER < 8 ? PER : 8;
+    __shared__ double tbl[M];
+    for (int i = threadIdx.x; i < M; i += CHAN_LVL_THREADS) tbl[i] = g2[i];
+    __syncthreads();
+    const int u = threadIdx.x % T;
+    const int c_raw = blockIdx.x * (CHAN_LVL_THREADS / T) + threadIdx.x / T;
+    const bool live = c_raw < nch;
+    const int c = live ? c_raw : nch - 1;
+    const int k0 = par[c].b - M / 2 + u;
+    const bool owner = live && u == 0;
+    double e = owner ? E[c] : 0.0;
+    for (int j = 0; j < nblk; j++)
+    {
+        const double2 *__restrict__ X = spec + (size_t)j * CHAN_N;
+        double acc = 0.0;
+#pragma unroll UNROLL
+        for (int i = 0; i < PER; i++)
+        {
+            const double2 x = X[(k0 + i * T) & (CHAN_N - 1)];
+            acc += (x.x * x.x + x.y * x.y) * tbl[i * T + u];
+        }
+#pragma unroll
+        for (int m = T / 2; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, T);
+        e += acc;
+    }
+    if (owner) E[c] = e;
+}

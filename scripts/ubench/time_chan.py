@@ -2,7 +2,8 @@
 channel) per step.  Prints one JSON line: HIP-event time per step of k_chan_fwd and k_chan_synth, of the bank's sample loop and coarse estimate
 from the same steps, their ratio (the yardstick: the two channeliser kernels together against the demodulator bank's own step time), the
 same per second of signal and per output sample, the engine clock over the timed steps.  Defaults: the headline OQPSK bank behind D = 32.
-usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup] [--decim D] [--fs-out 48000|24000|12000] [--bank oqpsk|msk600|msk1200]"""
+--survey: the survey (spectrum and levels) is on during the same steps; k_chan_psd and k_chan_level per step are printed beside the rest.
+usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup] [--decim D] [--fs-out 48000|24000|12000] [--bank oqpsk|msk600|msk1200] [--survey]"""
 import argparse
 import json
 import os
@@ -25,6 +26,7 @@ ap.add_argument("warmup", nargs="?", type=int, default=5)
 ap.add_argument("--decim", type=int, default=32, help="total decimation, capture to output")
 ap.add_argument("--fs-out", type=float, default=48000.0, help="the channeliser's output rate = the bank's Fs")
 ap.add_argument("--bank", choices=("oqpsk", "msk600", "msk1200"), default="oqpsk")
+ap.add_argument("--survey", action="store_true", help="survey the capture (spectrum and levels) in every step and time its two kernels")
 args = ap.parse_args()
 nch, K, W, decim, fs_out, hops = args.channels, args.steps, args.warmup, args.decim, args.fs_out, 16
 rng = np.random.default_rng(1)
@@ -36,6 +38,8 @@ if args.bank == "oqpsk":
 else:
     fb = 600.0 if args.bank == "msk600" else 1200.0
     settings = MskSettings(fb=fb, lockingbw=1.5 * fb, Fs=fs_out)
+if args.survey:
+    chan.survey_enable(psd=True, levels=True)
 bank = DemodulatorBank(settings, nch, ebno=True, max_write_samples=(hops + 1) * chan.Mo, softbit_capacity=4096)
 st = torch.cuda.current_stream().cuda_stream
 for _ in range(W):
@@ -56,6 +60,12 @@ fwd, nf = chan.profile_read(0)
 syn, ns = chan.profile_read(1)
 loop, nl = bank.profile_read(0)
 coarse, nc = bank.profile_read(1)
+survey = {}
+if args.survey:
+    (psd, npsd), (lvl, nlvl) = chan.survey_profile_read(0), chan.survey_profile_read(1)
+    survey = {"k_chan_psd_ms_per_step": round(psd / K, 4), "k_chan_psd_launches": npsd,
+              "k_chan_level_ms_per_step": round(lvl / K, 4), "k_chan_level_launches": nlvl,
+              "k_chan_level_over_synth": round(lvl / syn, 4), "survey_blocks": int(chan.read_psd()[1])}
 chan_ms, bank_ms = (fwd + syn) / K, (loop + coarse) / K
 signal_s = hops * HP / (fs_out * decim)  # seconds of signal per step
 print(json.dumps({
@@ -65,7 +75,7 @@ print(json.dumps({
     "bank_ms_per_signal_s": round(bank_ms / signal_s, 3),
     "k_chan_synth_ps_per_output_sample": round(1e9 * syn / K / (nch * hops * chan.Mo), 3),
     "k_chan_fwd_ms_per_step": round(fwd / K, 4), "k_chan_fwd_launches": nf,
-    "k_chan_synth_ms_per_step": round(syn / K, 4), "k_chan_synth_launches": ns,
+    "k_chan_synth_ms_per_step": round(syn / K, 4), "k_chan_synth_launches": ns, **survey,
     "bank_sample_loop_ms_per_step": round(loop / K, 4), "bank_sample_loop_launches": nl,
     "bank_coarse_ms_per_step": round(coarse / K, 4), "bank_coarse_launches": nc,
     "chan_ms_per_step": round(chan_ms, 4), "bank_ms_per_step": round(bank_ms, 4), "chan_over_bank": round(chan_ms / bank_ms, 4),
