@@ -380,6 +380,31 @@ int jaero_debug_prefilter(int device, const double *in_reim, int n, double alpha
 /* Test hook: the first n prefiltered complex samples (re, im pairs) of the last jaero_write of an 8400 bps bank, channel ch
  * (cval_prefiltered, JAERO/oqpskdemodulator.cpp:343-381). */
 int jaero_debug_read_prefiltered(jaero_ctx *ctx, int channel, double *out_reim, int n);
+/* Test hooks: the prefilter stage of an 8400 bps bank on its own (k_pre8400_mix, k_pre8400_commit, k_pre8400_fft, k_pre8400_restart), launched by
+ * the code jaero_write and jaero_set_settings launch it with.  JAERO_EINVAL before any launch: null ctx, a bank that is not 8400 bps, a channel
+ * outside [0, nchannels), nsamples outside 1 .. max_write_samples, stretches outside {0, 1, 8}, a state out of range, a ring window that is
+ * not wholly among the last `ring` samples written.  write / poke / restart mark the bank as the coarse hooks do (a later jaero_write or setter
+ * returns JAERO_EHIP); peek, read_ring and jaero_debug_read_prefiltered only read and may be called between real writes.
+ *   jaero_debug_pre8400_write     the prefilter stage of one write of host PCM for the whole bank and nothing behind it; advances the bank's
+ *                                 sample count and previous write length.  stretches: 0 = as jaero_write chooses, 1 or 8 = forced.
+ *   jaero_debug_pre8400_poke      one channel's oscillator pointer and step (both in [0, 19999)), the sum of mixer2's frequency over the
+ *                                 previous write (the next write's oscillator runs at fsum / nprev) and hold, the absolute sample index up
+ *                                 to which the channel's outputs are exact zeros.  n0 / nprev / ring / cap are outputs of peek only.
+ *   jaero_debug_pre8400_peek      the same back, with the bank's samples written so far, previous write length, ring length and capacity.
+ *   jaero_debug_pre8400_restart   the launch jaero_set_settings makes for one channel of several.
+ *   jaero_debug_pre8400_read_ring n down-mixed samples (re, im pairs) of a channel's history from absolute sample index first_abs_index on. */
+typedef struct jaero_pre8400_state
+{
+    double ptr, step, fsum;
+    long long hold;
+    long long n0;
+    int nprev, ring, cap;
+} jaero_pre8400_state;
+int jaero_debug_pre8400_write(jaero_ctx *ctx, const int16_t *pcm, int layout, int nsamples, int stretches);
+int jaero_debug_pre8400_poke(jaero_ctx *ctx, int channel, const jaero_pre8400_state *st);
+int jaero_debug_pre8400_peek(jaero_ctx *ctx, int channel, jaero_pre8400_state *st);
+int jaero_debug_pre8400_restart(jaero_ctx *ctx, int channel);
+int jaero_debug_pre8400_read_ring(jaero_ctx *ctx, int channel, long long first_abs_index, int n, double *out_reim);
 /* Test hook: the Viterbi decoder picks its layout by size (one block per wavefront below 16 384 blocks, one per lane from there); tests
  * force one so that both meet the oracle at small sizes.  mode: 0 = by size (default), 1 = wave, 2 = lanes.  Process-wide. */
 int jaero_debug_viterbi_layout(int mode);

@@ -28,6 +28,7 @@ EXPORTS = [
     "jaero_debug_sample_loop_layout", "jaero_debug_kernel_variant",
     "jaero_debug_coarse_poke", "jaero_debug_coarse_launch", "jaero_debug_coarse_peek",
     "jaero_debug_schedule", "jaero_debug_schedule_lanes", "jaero_debug_prefilter", "jaero_debug_read_prefiltered", "jaero_read_events",
+    "jaero_debug_pre8400_write", "jaero_debug_pre8400_poke", "jaero_debug_pre8400_peek", "jaero_debug_pre8400_restart", "jaero_debug_pre8400_read_ring",
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
     "jaero_ingest_create", "jaero_ingest_destroy", "jaero_ingest_push", "jaero_ingest_queued", "jaero_ingest_pump",
@@ -70,6 +71,13 @@ class CoarseState(C.Structure):
 
     _fields_ = [(n, C.c_int) for n in ("bb_ptr", "emptying", "flags", "countdown", "countdown2", "coarse_cnt", "nest", "log_cnt")] + [
         (n, C.c_double) for n in ("mse", "m2_freq", "mc_freq")]
+
+
+class Pre8400State(C.Structure):
+    """struct jaero_pre8400_state: what jaero_debug_pre8400_poke / _peek exchange (n0, nprev, ring, cap: outputs of peek only)."""
+
+    _fields_ = [("ptr", C.c_double), ("step", C.c_double), ("fsum", C.c_double), ("hold", C.c_longlong), ("n0", C.c_longlong),
+                ("nprev", C.c_int), ("ring", C.c_int), ("cap", C.c_int)]
 
 
 class ChanChannel(C.Structure):
@@ -142,6 +150,11 @@ def lib():
     L.jaero_debug_schedule_lanes.argtypes = [ip, ip, ip, vp, vp, ip, vp, ip, vp, ip, C.POINTER(ip)]
     L.jaero_debug_prefilter.argtypes = [ip, vp, ip, dp, dp, vp]
     L.jaero_debug_read_prefiltered.argtypes = [vp, ip, vp, ip]
+    L.jaero_debug_pre8400_write.argtypes = [vp, vp, ip, ip, ip]
+    L.jaero_debug_pre8400_poke.argtypes = [vp, ip, C.POINTER(Pre8400State)]
+    L.jaero_debug_pre8400_peek.argtypes = [vp, ip, C.POINTER(Pre8400State)]
+    L.jaero_debug_pre8400_restart.argtypes = [vp, ip]
+    L.jaero_debug_pre8400_read_ring.argtypes = [vp, ip, C.c_longlong, ip, vp]
     L.jaero_aerol_create.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_create_burst.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_read_packets.argtypes = [vp, ip, vp, ip, C.POINTER(ip)]

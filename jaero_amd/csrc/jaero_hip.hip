@@ -575,6 +575,53 @@ static void launch_pre8400_filter(const JGeom &g, const JPtrs &p, const JPre &q,
     hipLaunchKernelGGL(k_pre8400_fft, dim3(g.nchp / 4, (int)(((n0 + n - 1) >> 11) - (n0 >> 11) + 1)), dim3(PF_THREADS), 4 * 2 * PRE_L * (int)sizeof(double), st, g, p, q, n, n0);
 }
 
+// The launches of a write in front of the sample loop, shared by jaero_write / jaero_set_settings and the test hooks jaero_debug_pre8400_*
+// (tests/test_gpu_pre8400.py runs these, not a copy of them).
+// The write's PCM on the device as frames: uploaded unless it is there already, transposed unless it is frame-major.
+static int stage_pcm(jaero_ctx *c, const int16_t *pcm, int nsamples, int layout, int is_device_ptr, hipStream_t st, const int16_t **frames, int *stride)
+{
+    const int nch = c->g.nch, nchp = c->g.nchp;
+    const int16_t *dsrc = pcm;
+    if (!is_device_ptr)
+    {
+        HIPCHK(hipMemcpyAsync(c->d_pcm_raw, pcm, sizeof(int16_t) * (size_t)nch * nsamples, hipMemcpyHostToDevice, st));
+        dsrc = c->d_pcm_raw;
+    }
+    if (layout == JAERO_PCM_FRAME_MAJOR) { *frames = dsrc; *stride = nch; }
+    else
+    {
+        const int pi = c->timer.begin(2, st);
+        hipLaunchKernelGGL(k_transpose_pcm, dim3(nchp / 64, (nsamples + 63) / 64), dim3(256), 0, st, dsrc, c->d_pcm_frames, nch, nchp, nsamples);
+        LAUNCHCHK("k_transpose_pcm");
+        c->timer.end(pi, st);
+        *frames = c->d_pcm_frames; *stride = nchp;
+    }
+    return 0;
+}
+// eight stretches per write once there are fewer channel groups than eight per SIMD (k_pre8400.h)
+static int pre8400_stretches(const JGeom &g, int nsamples) { return (g.ngroups >= 8192 || nsamples < 512) ? 1 : 8; }
+// the whole write is prefiltered first (oqpskdemodulator.cpp:343-381); its oscillator takes the mean of mixer2's frequency over the
+// previous write (:607-608).  Advances pre_n0.
+static int launch_pre8400_stage(jaero_ctx *c, const int16_t *frames, int stride, int nsamples, int ntb, hipStream_t st)
+{
+    const JGeom &g = c->g;
+    hipLaunchKernelGGL(k_pre8400_mix, dim3(g.ngroups, ntb), dim3(64), 0, st, g, c->p, c->pre, frames, stride, nsamples, c->pre_n0, c->pre_nprev);
+    LAUNCHCHK("k_pre8400_mix");
+    hipLaunchKernelGGL(k_pre8400_commit, dim3(g.ngroups), dim3(64), 0, st, g, c->p, c->pre_nprev);
+    LAUNCHCHK("k_pre8400_commit");
+    launch_pre8400_filter(g, c->p, c->pre, nsamples, c->pre_n0, st);
+    LAUNCHCHK("the 8400 bps prefilter");
+    c->pre_n0 += nsamples;
+    return 0;
+}
+// setSettings on one channel of several: its prefilter starts again at the bank's current sample (k_pre8400_restart)
+static int launch_pre8400_restart(jaero_ctx *c, int channel, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_pre8400_restart, dim3(16), dim3(256), 0, st, c->g, c->pre, channel, c->pre_n0);
+    LAUNCHCHK("k_pre8400_restart");
+    return 0;
+}
+
 // The sample-loop records: front / back pair kernels (k_oqpsk_fb.h, k_msk_fb.h) and the single-wavefront MSK kernel (k_msk.h).  The kernel
 // and its spelled-out name come from the same E / C pick of by_flags.
 template <int PAIRS, bool PRE8400>
@@ -1068,8 +1115,7 @@ extern "C" int jaero_set_settings(jaero_ctx *c, int channel, const jaero_setting
         // stay on the bank's grid (round 5; refused until then)
         if (whole) return rebank_with_carry_over(c, s);
         HIPCHK(hipSetDevice(c->device));
-        hipLaunchKernelGGL(k_pre8400_restart, dim3(16), dim3(256), 0, c->last_stream, g, c->pre, channel, c->pre_n0);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch_pre8400_restart(c, channel, c->last_stream))) return rc;
         return apply_live_settings(c, channel, channel + 1, s);
     }
     HIPCHK(hipSetDevice(c->device));
@@ -1179,40 +1225,17 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
         return rc;
     }
     const JGeom &g = c->g;
-    const int nch = g.nch, nchp = g.nchp;
+    const int nch = g.nch;
 
     const int16_t *frames = nullptr;
     int stride = 0;
-    const int16_t *dsrc = pcm;
-    if (!is_device_ptr)
-    {
-        HIPCHK(hipMemcpyAsync(c->d_pcm_raw, pcm, sizeof(int16_t) * (size_t)nch * nsamples, hipMemcpyHostToDevice, st));
-        dsrc = c->d_pcm_raw;
-    }
-    if (layout == JAERO_PCM_FRAME_MAJOR) { frames = dsrc; stride = nch; }
-    else
-    {
-        const int pi = c->timer.begin(2, st);
-        hipLaunchKernelGGL(k_transpose_pcm, dim3(nchp / 64, (nsamples + 63) / 64), dim3(256), 0, st, dsrc, c->d_pcm_frames, nch, nchp, nsamples);
-        LAUNCHCHK("k_transpose_pcm");
-        c->timer.end(pi, st);
-        frames = c->d_pcm_frames; stride = nchp;
-    }
+    { const int rc = stage_pcm(c, pcm, nsamples, layout, is_device_ptr, st, &frames, &stride); if (rc) return rc; }
 
     c->poisoned = true; // from here on device state and mirror advance together or not at all
     if (c->pre8400)
     {
-        // the whole write is prefiltered first (oqpskdemodulator.cpp:343-381); its oscillator takes the mean of mixer2's frequency over
-        // the previous write (:607-608)
-        // eight stretches per write once there are fewer channel groups than eight per SIMD (k_pre8400.h)
-        const int ntb = (g.ngroups >= 8192 || nsamples < 512) ? 1 : 8;
-        hipLaunchKernelGGL(k_pre8400_mix, dim3(g.ngroups, ntb), dim3(64), 0, st, g, c->p, c->pre, frames, stride, nsamples, c->pre_n0, c->pre_nprev);
-        LAUNCHCHK("k_pre8400_mix");
-        hipLaunchKernelGGL(k_pre8400_commit, dim3(g.ngroups), dim3(64), 0, st, g, c->p, c->pre_nprev);
-        LAUNCHCHK("k_pre8400_commit");
-        launch_pre8400_filter(g, c->p, c->pre, nsamples, c->pre_n0, st);
-        LAUNCHCHK("the 8400 bps prefilter");
-        c->pre_n0 += nsamples;
+        const int rc = launch_pre8400_stage(c, frames, stride, nsamples, pre8400_stretches(g, nsamples), st);
+        if (rc) return rc;
     }
     if (g.kind == JAERO_KIND_OQPSK) c->pre_nprev = nsamples; // (at every rate: a bank re-created for 8400 bps needs the length of the last write, rebank_with_carry_over)
     int pos = 0;
@@ -1446,6 +1469,82 @@ extern "C" int jaero_debug_prefilter(int device, const double *in_reim, int n, d
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy2D(out_reim, sizeof(double2), q.out, sizeof(double2) * 4, sizeof(double2), (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ test hooks: the 8400 bps prefilter stage alone
+// (tests/test_gpu_pre8400.py), through stage_pcm / launch_pre8400_stage / launch_pre8400_restart as jaero_write and jaero_set_settings call them.
+static int pre8400_hook_enter(jaero_ctx *c, const char *who, int channel, bool poison)
+{
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (c->burst || !c->pre8400) return fail(JAERO_EINVAL, "%s: not an 8400 bps bank", who);
+    if (channel < 0 || channel >= c->g.nch) return fail(JAERO_EINVAL, "%s: channel %d outside [0, %d)", who, channel, c->g.nch);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    if (poison) c->poisoned = true;
+    return 0;
+}
+extern "C" int jaero_debug_pre8400_write(jaero_ctx *c, const int16_t *pcm, int layout, int nsamples, int stretches)
+{
+    if (c && c->pre8400 && (!pcm || nsamples <= 0 || nsamples > c->max_write))
+        return fail(JAERO_EINVAL, "jaero_debug_pre8400_write: nsamples %d (1 .. max_write_samples %d of host PCM)", nsamples, c->max_write);
+    if (layout != JAERO_PCM_CHANNEL_MAJOR && layout != JAERO_PCM_FRAME_MAJOR) return fail(JAERO_EINVAL, "jaero_debug_pre8400_write: bad layout");
+    if (stretches != 0 && stretches != 1 && stretches != 8) return fail(JAERO_EINVAL, "jaero_debug_pre8400_write: stretches %d (0 = as jaero_write, 1 or 8)", stretches);
+    int rc = pre8400_hook_enter(c, "jaero_debug_pre8400_write", 0, true);
+    if (rc) return rc;
+    hipStream_t st = c->last_stream;
+    const int16_t *frames = nullptr;
+    int stride = 0;
+    if ((rc = stage_pcm(c, pcm, nsamples, layout, 0, st, &frames, &stride))) return rc;
+    if ((rc = launch_pre8400_stage(c, frames, stride, nsamples, stretches ? stretches : pre8400_stretches(c->g, nsamples), st))) return rc;
+    c->pre_nprev = nsamples;
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+extern "C" int jaero_debug_pre8400_poke(jaero_ctx *c, int ch, const jaero_pre8400_state *st)
+{
+    if (!st) return fail(JAERO_EINVAL, "jaero_debug_pre8400_poke: null state");
+    if (!(st->ptr >= 0 && st->ptr < (double)JD_WTSIZE) || !(st->step >= 0 && st->step < (double)JD_WTSIZE) || !(fabs(st->fsum) < 1e300) || st->hold < 0)
+        return fail(JAERO_EINVAL, "jaero_debug_pre8400_poke: state out of range (ptr and step in [0, %d), fsum finite, hold >= 0)", JD_WTSIZE);
+    int rc = pre8400_hook_enter(c, "jaero_debug_pre8400_poke", ch, true);
+    if (rc) return rc;
+    const size_t nchp = (size_t)c->g.nchp;
+    const std::pair<int, double> dv[] = {{S_PRE_PTR, st->ptr}, {S_PRE_STEP, st->step}, {S_PRE_FSUM, st->fsum}};
+    for (const auto &[f, v] : dv) HIPCHK(hipMemcpy(c->p.S + (size_t)f * nchp + ch, &v, sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->pre.hold + ch, &st->hold, sizeof(long long), hipMemcpyHostToDevice));
+    return 0;
+}
+extern "C" int jaero_debug_pre8400_peek(jaero_ctx *c, int ch, jaero_pre8400_state *st)
+{
+    if (!st) return fail(JAERO_EINVAL, "jaero_debug_pre8400_peek: null state");
+    int rc = pre8400_hook_enter(c, "jaero_debug_pre8400_peek", ch, false);
+    if (rc) return rc;
+    const size_t nchp = (size_t)c->g.nchp;
+    const std::pair<int, double *> dv[] = {{S_PRE_PTR, &st->ptr}, {S_PRE_STEP, &st->step}, {S_PRE_FSUM, &st->fsum}};
+    for (const auto &[f, v] : dv) HIPCHK(hipMemcpy(v, c->p.S + (size_t)f * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&st->hold, c->pre.hold + ch, sizeof(long long), hipMemcpyDeviceToHost));
+    st->n0 = c->pre_n0; st->nprev = c->pre_nprev; st->ring = c->pre.ring; st->cap = c->pre.cap;
+    return 0;
+}
+extern "C" int jaero_debug_pre8400_restart(jaero_ctx *c, int ch)
+{
+    int rc = pre8400_hook_enter(c, "jaero_debug_pre8400_restart", ch, true);
+    if (rc) return rc;
+    if ((rc = launch_pre8400_restart(c, ch, c->last_stream))) return rc;
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    return 0;
+}
+extern "C" int jaero_debug_pre8400_read_ring(jaero_ctx *c, int ch, long long first, int n, double *out_reim)
+{
+    if (!out_reim) return fail(JAERO_EINVAL, "jaero_debug_pre8400_read_ring: null output");
+    int rc = pre8400_hook_enter(c, "jaero_debug_pre8400_read_ring", ch, false);
+    if (rc) return rc;
+    const long long ring = c->pre.ring, oldest = c->pre_n0 > ring ? c->pre_n0 - ring : 0;
+    if (n <= 0 || first < oldest || first > c->pre_n0 - n)
+        return fail(JAERO_EINVAL, "jaero_debug_pre8400_read_ring: samples [%lld, %lld + %d) are not all among the last %lld of the %lld written", first, first, n, ring, c->pre_n0);
+    const int slot = (int)(first & (ring - 1)), n1 = n < (int)(ring - slot) ? n : (int)(ring - slot);
+    HIPCHK(hipMemcpy2D(out_reim, sizeof(double2), c->pre.xring + PRE_XI(slot, ch, c->pre.ring), sizeof(double2) * 4, sizeof(double2), (size_t)n1, hipMemcpyDeviceToHost));
+    if (n > n1) HIPCHK(hipMemcpy2D(out_reim + 2 * (size_t)n1, sizeof(double2), c->pre.xring + PRE_XI(0, ch, c->pre.ring), sizeof(double2) * 4, sizeof(double2), (size_t)(n - n1), hipMemcpyDeviceToHost));
     return 0;
 }
 

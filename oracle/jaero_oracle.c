@@ -665,8 +665,9 @@ struct jo_demod
     /* RxDataBits */
     short rx[64]; int nrx;
     /* captures */
-    gbuf soft, status, symbols;
-    int capture_symbols;
+    gbuf soft, status, symbols, prefiltered;
+    int capture_symbols, capture_prefiltered;
+    double pre_freq_sum; /* mixer2_freq_sum of the last OQPSK write (:447, :607-608) */
     double nest;
 };
 
@@ -730,6 +731,7 @@ static void oqpsk_ctor(jo_demod *d) /* oqpskdemodulator.cpp:8-117 */
     }
 }
 
+static void pre8400_set_kernel(fastfir_t *f, double fb, double Fs);
 static void oqpsk_set_settings(jo_demod *d, const jo_settings *s) /* oqpskdemodulator.cpp:175-289 */
 {
     d->Fs = s->Fs;
@@ -769,12 +771,7 @@ static void oqpsk_set_settings(jo_demod *d, const jo_settings *s) /* oqpskdemodu
     wt_setfreq_sr(&d->st_osc_ref, d->fb, (int)d->Fs);
     d->ebno.Fs = d->Fs; d->ebno.fb = d->fb;
     /* prefilter kernel (:278-283); built for every rate, used at 8400 */
-    {
-        double *pp = (double *)malloc(sizeof(double) * 2100);
-        int npp = jo_rrc_design(d->fb == 8400 ? 0.6 : 1.0, 2048, d->Fs, d->fb / 2, pp);
-        fastfir_set_kernel_real(&d->fir_pre, pp, npp, 4096);
-        free(pp);
-    }
+    pre8400_set_kernel(&d->fir_pre, d->fb, d->Fs);
     d->coarseCounter = 0;
 }
 
@@ -840,6 +837,62 @@ static void coarse_ring_step(jo_demod *d, double dval, int is_oqpsk)
     d->coarseCounter++;
 }
 
+/* The prefilter block of OqpskDemodulator::writeData at 8400 bps (oqpskdemodulator.cpp:343-381): the write mixed down with mixer_fir_pre
+ * (:354-364), JFastFir::update over the whole write (:366-368), and mixed up again with the conjugate of the same oscillator restarted from
+ * the phase it had before the write (:371-379).  buf receives cval_prefiltered; down (optional) the samples that went into the filter. */
+static void pre8400_write(wavetable *osc, fastfir_t *fir, const int16_t *ptr, long n, cpx *buf, cpx *down)
+{
+    const double savedphase = wt_get_phase_deg(osc);
+    for (long i = 0; i < n; i++)
+    {
+        double dval = ((double)ptr[i]) / 32768.0;
+        buf[i] = cscale(wt_cis(osc), dval);
+        wt_next(osc);
+    }
+    if (down) memcpy(down, buf, sizeof(cpx) * (size_t)n);
+    fastfir_update(fir, buf, n);
+    wt_set_phase_deg(osc, savedphase);
+    for (long i = 0; i < n; i++)
+    {
+        cpx cj = wt_cis_conj(osc);
+        buf[i] = cmul(buf[i], cj);
+        wt_next(osc);
+    }
+}
+/* the kernel setSettings gives the prefilter (oqpskdemodulator.cpp:278-283): JFastFir::SetKernel(rrc(alpha, 2048, Fs, fb / 2), 4096) */
+static void pre8400_set_kernel(fastfir_t *f, double fb, double Fs)
+{
+    double *pp = (double *)malloc(sizeof(double) * 2100);
+    int npp = jo_rrc_design(fb == 8400 ? 0.6 : 1.0, 2048, Fs, fb / 2, pp);
+    fastfir_set_kernel_real(f, pp, npp, 4096);
+    free(pp);
+}
+
+/* ---------------- the 8400 bps prefilter on its own (tests/test_gpu_pre8400.py): mixer_fir_pre and fir_pre of an OqpskDemodulator */
+struct jo_pre8400 { wavetable osc; fastfir_t fir; double fb, Fs; };
+jo_pre8400 *jo_pre8400_create(void)
+{
+    trig_init();
+    jo_pre8400 *p = (jo_pre8400 *)calloc(1, sizeof(jo_pre8400));
+    p->fb = 8400; p->Fs = 48000;
+    /* the constructor's oscillator (oqpskdemodulator.cpp:110-115: freq_center 8000 at Fs 48000, phase 0; setSettings leaves it alone) and
+     * setSettings' kernel at 8400 bps (:278-283) */
+    wt_init(&p->osc);
+    wt_setfreq_sr(&p->osc, 8000, 48000);
+    pre8400_set_kernel(&p->fir, p->fb, p->Fs);
+    return p;
+}
+void jo_pre8400_destroy(jo_pre8400 *p) { if (!p) return; fastfir_free(&p->fir); free(p); }
+void jo_pre8400_write(jo_pre8400 *p, const int16_t *pcm, long n, double *down_re_im, double *out_re_im)
+{
+    pre8400_write(&p->osc, &p->fir, pcm, n, (cpx *)out_re_im, (cpx *)down_re_im);
+}
+/* mixer_fir_pre.SetFreq(mixer2_freq_sum / i) at the end of a write of n samples (oqpskdemodulator.cpp:607-608) */
+void jo_pre8400_end_of_write(jo_pre8400 *p, double mixer2_freq_sum, long n) { wt_setfreq(&p->osc, mixer2_freq_sum / ((double)n)); }
+/* fir_pre.SetKernel as setSettings calls it (oqpskdemodulator.cpp:278-283): empty history, L zeros queued, blocks re-aligned */
+void jo_pre8400_restart(jo_pre8400 *p) { pre8400_set_kernel(&p->fir, p->fb, p->Fs); }
+void jo_pre8400_get_state(const jo_pre8400 *p, double *wtptr, double *wtstep) { *wtptr = p->osc.WTptr; *wtstep = p->osc.WTstep; }
+
 static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodulator.cpp:334-627 */
 {
     if (!n) return;
@@ -847,21 +900,8 @@ static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodul
     if (d->fb == 8400)
     {
         if (d->prefilt_cap < n) { d->prefilt = (cpx *)realloc(d->prefilt, sizeof(cpx) * (size_t)n); d->prefilt_cap = n; }
-        const double savedphase = wt_get_phase_deg(&d->mixer_fir_pre);
-        for (long i = 0; i < n; i++)
-        {
-            double dval = ((double)ptr[i]) / 32768.0;
-            d->prefilt[i] = cscale(wt_cis(&d->mixer_fir_pre), dval);
-            wt_next(&d->mixer_fir_pre);
-        }
-        fastfir_update(&d->fir_pre, d->prefilt, n);
-        wt_set_phase_deg(&d->mixer_fir_pre, savedphase);
-        for (long i = 0; i < n; i++)
-        {
-            cpx cj = wt_cis_conj(&d->mixer_fir_pre);
-            d->prefilt[i] = cmul(d->prefilt[i], cj);
-            wt_next(&d->mixer_fir_pre);
-        }
+        pre8400_write(&d->mixer_fir_pre, &d->fir_pre, ptr, n, d->prefilt, NULL);
+        if (d->capture_prefiltered) gpush(&d->prefiltered, d->prefilt, sizeof(cpx) * (size_t)n);
     }
     double mixer2_freq_sum = 0;
     for (long i = 0; i < n; i++)
@@ -967,6 +1007,7 @@ static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodul
     }
     /* update the 8400bps pre filter with better estimates of carrier (:607-608; runs at every rate) */
     wt_setfreq(&d->mixer_fir_pre, mixer2_freq_sum / ((double)n));
+    d->pre_freq_sum = mixer2_freq_sum;
 }
 
 static void center_freq_changed(jo_demod *d, double freq_center) /* oqpsk :291-310, msk :265-282 */
@@ -1188,7 +1229,7 @@ void jo_demod_destroy(jo_demod *d)
     jo_coarse_destroy(d->coarse); agc_free(d->agc); ma_free(d->ebno.E); ma_free(d->ebno.E2); ma_free(d->marg);
     ma_free(d->msema); ma_free(d->msecalc.pointmean); ma_free(d->msecalc.msema);
     free(d->dt.buffer); free(d->delayedsmpl.buffer);
-    free(d->soft.p); free(d->status.p); free(d->symbols.p);
+    free(d->soft.p); free(d->status.p); free(d->symbols.p); free(d->prefiltered.p);
     free(d);
 }
 void jo_demod_set_flags(jo_demod *d, int afc, int sql, int cpu_reduce) { d->afc = afc; d->sql = sql; d->cpuReduce = cpu_reduce; }
@@ -1208,6 +1249,12 @@ double jo_demod_get_mse(jo_demod *d) { return d->mse; }
 double jo_demod_get_freq_est(jo_demod *d) { return d->mixer2.freq; }
 double jo_demod_get_freq_center(jo_demod *d) { return d->mixer_center.freq; }
 double jo_demod_get_ebno(jo_demod *d) { return d->ebno.EbNo; }
+/* cval_prefiltered of every 8400 bps write (oqpskdemodulator.cpp:343-381), concatenated: rows of (re, im) */
+void jo_demod_capture_prefiltered(jo_demod *d, int on) { d->capture_prefiltered = on; }
+long jo_demod_take_prefiltered(jo_demod *d, double *dst, long caprows) { return gtake(&d->prefiltered, dst, 2 * sizeof(double), caprows); }
+/* mixer_fir_pre's frequency, and the mixer2_freq_sum the last write set it from (oqpskdemodulator.cpp:607-608) */
+double jo_demod_get_pre_freq(jo_demod *d) { return d->mixer_fir_pre.freq; }
+double jo_demod_get_pre_freq_sum(jo_demod *d) { return d->pre_freq_sum; }
 
 /* JFastFir::SetKernel(rrc(alpha, K, Fs, fsym), nfft) + update(x) on n complex samples (re, im interleaved): the operation
  * JAERO/tests/jfastfir_tests.cpp:31-58 checks against the recorded output of JAERO v1.0.4.11 */

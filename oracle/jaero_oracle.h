@@ -53,6 +53,12 @@ double jo_demod_get_mse(jo_demod *d);
 double jo_demod_get_freq_est(jo_demod *d);
 double jo_demod_get_freq_center(jo_demod *d);
 double jo_demod_get_ebno(jo_demod *d); /* the EbNo meter's value (EbNoMeasurmentSignal), updated between estimates too */
+/* cval_prefiltered of every 8400 bps write (JAERO/oqpskdemodulator.cpp:343-381), concatenated over writes: rows of (re, im) */
+void jo_demod_capture_prefiltered(jo_demod *d, int on);
+long jo_demod_take_prefiltered(jo_demod *d, double *dst, long caprows);
+/* mixer_fir_pre's frequency and the mixer2_freq_sum of the last write, which it was set from (JAERO/oqpskdemodulator.cpp:607-608) */
+double jo_demod_get_pre_freq(jo_demod *d);
+double jo_demod_get_pre_freq_sum(jo_demod *d);
 
 /* stand-alone pieces for unit tests */
 /* RootRaisedCosine::design (JAERO/DSP.h:316-338); returns number of points written */
@@ -69,6 +75,20 @@ void jo_coarse_bigchange(jo_coarse *c);
 double jo_coarse_process(jo_coarse *c, const double *re_im);
 void jo_coarse_get_y(jo_coarse *c, double *y);
 void jo_coarse_set_y(jo_coarse *c, const double *y);
+
+/* The 8400 bps prefilter of OqpskDemodulator::writeData on its own (JAERO/oqpskdemodulator.cpp:343-381): mixer_fir_pre as the constructor
+ * leaves it (8000 Hz, phase 0, :110-115) and fir_pre with setSettings' kernel (RRC 0.6, 2049 taps, nfft 4096 at fb / 2, :278-283).
+ *   write         n int16 samples; down_re_im (optional) receives the down-mixed samples that went into the filter, out_re_im cval_prefiltered
+ *   end_of_write  mixer_fir_pre.SetFreq(mixer2_freq_sum / n) (:607-608)
+ *   restart       fir_pre.SetKernel as setSettings calls it (:278-283)
+ *   get_state     mixer_fir_pre's WTptr and WTstep */
+typedef struct jo_pre8400 jo_pre8400;
+jo_pre8400 *jo_pre8400_create(void);
+void jo_pre8400_destroy(jo_pre8400 *p);
+void jo_pre8400_write(jo_pre8400 *p, const int16_t *pcm, long n, double *down_re_im, double *out_re_im);
+void jo_pre8400_end_of_write(jo_pre8400 *p, double mixer2_freq_sum, long n);
+void jo_pre8400_restart(jo_pre8400 *p);
+void jo_pre8400_get_state(const jo_pre8400 *p, double *wtptr, double *wtstep);
 
 /* ---- burst demodulators (jaero_oracle_burst.c): BurstOqpskDemodulator / BurstMskDemodulator ---- */
 typedef struct jo_burst jo_burst;

@@ -88,6 +88,20 @@ def lib():
             f = getattr(L, name)
             f.restype = C.c_double
             f.argtypes = [C.c_void_p]
+        L.jo_demod_capture_prefiltered.argtypes = [C.c_void_p, C.c_int]
+        L.jo_demod_take_prefiltered.restype = C.c_long
+        L.jo_demod_take_prefiltered.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+        for name in ("jo_demod_get_pre_freq", "jo_demod_get_pre_freq_sum"):
+            f = getattr(L, name)
+            f.restype = C.c_double
+            f.argtypes = [C.c_void_p]
+        L.jo_pre8400_create.restype = C.c_void_p
+        L.jo_pre8400_create.argtypes = []
+        L.jo_pre8400_destroy.argtypes = [C.c_void_p]
+        L.jo_pre8400_write.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
+        L.jo_pre8400_end_of_write.argtypes = [C.c_void_p, C.c_double, C.c_long]
+        L.jo_pre8400_restart.argtypes = [C.c_void_p]
+        L.jo_pre8400_get_state.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.jo_rrc_design.argtypes = [C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p]
         L.jo_cis_table.argtypes = [C.c_void_p]
         L.jo_fft.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -156,12 +170,13 @@ def lib():
 class Demod:
     """One reference-semantics demodulator object (OqpskDemodulator or MskDemodulator)."""
 
-    def __init__(self, settings: Settings, afc=False, sql=False, cpu_reduce=False, capture_symbols=False):
+    def __init__(self, settings: Settings, afc=False, sql=False, cpu_reduce=False, capture_symbols=False, capture_prefiltered=False):
         self.L = lib()
         self.h = self.L.jo_demod_create(C.byref(settings))
         self.L.jo_demod_set_flags(self.h, int(afc), int(sql), int(cpu_reduce))
         self.L.jo_demod_set_dcd(self.h, 0)
         self.L.jo_demod_capture_symbols(self.h, int(capture_symbols))
+        self.L.jo_demod_capture_prefiltered(self.h, int(capture_prefiltered))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -213,6 +228,20 @@ class Demod:
             if n < buf.shape[0]:
                 break
         return np.concatenate(out)
+
+    def take_prefiltered(self) -> np.ndarray:
+        """cval_prefiltered of the 8400 bps writes so far (oqpskdemodulator.cpp:343-381), concatenated; needs capture_prefiltered"""
+        return _drain(self.L.jo_demod_take_prefiltered, self.h, 2, np.float64).reshape(-1, 2).copy().view(np.complex128).reshape(-1)
+
+    @property
+    def pre_freq(self):
+        """mixer_fir_pre's frequency (set at the end of every write, oqpskdemodulator.cpp:607-608)"""
+        return self.L.jo_demod_get_pre_freq(self.h)
+
+    @property
+    def pre_freq_sum(self):
+        """mixer2_freq_sum of the last write (oqpskdemodulator.cpp:447, 607-608)"""
+        return self.L.jo_demod_get_pre_freq_sum(self.h)
 
     @property
     def mse(self):
@@ -275,11 +304,14 @@ class Coarse:
 
 def run_demod(settings: Settings, pcm: np.ndarray, chunk=4096, afc=False, cpu_reduce=False,
               dcd_at: int = -1, capture_symbols=False, center_at: int = -1, center_hz: float = 0.0,
-              set_at: int = -1, set_settings: Settings = None, sql=False, flags_events=(), dcd_off_at: int = -1):
+              set_at: int = -1, set_settings: Settings = None, sql=False, flags_events=(), dcd_off_at: int = -1,
+              capture_prefiltered=False):
     """Convenience: feed pcm in `chunk`-sample writes (an int, or the list of successive write sizes),
     return dict(soft, status[, symbols]).  set_at / set_settings: setSettings on the live object before the write that starts at or
-    after that sample."""
-    d = Demod(settings, afc=afc, sql=sql, cpu_reduce=cpu_reduce, capture_symbols=capture_symbols)
+    after that sample.  capture_prefiltered (8400 bps): also `prefiltered` (cval_prefiltered, concatenated over the writes), `write_sizes`, and
+    per write `pre_freq` (mixer_fir_pre's frequency after it) and `pre_freq_sum` (the mixer2_freq_sum it was set from)."""
+    d = Demod(settings, afc=afc, sql=sql, cpu_reduce=cpu_reduce, capture_symbols=capture_symbols, capture_prefiltered=capture_prefiltered)
+    wsizes, pre_freq, pre_freq_sum = [], [], []
     flags_events = sorted(list(flags_events))  # [(sample, afc, sql, cpu_reduce)]: set_flags before the write that starts at or after that sample
     n = pcm.shape[0]
     s = 0
@@ -307,11 +339,58 @@ def run_demod(settings: Settings, pcm: np.ndarray, chunk=4096, afc=False, cpu_re
         m = min(chunk, n - s)
         d.write(pcm[s:s + m])
         s += m
+        if capture_prefiltered:
+            wsizes.append(m); pre_freq.append(d.pre_freq); pre_freq_sum.append(d.pre_freq_sum)
     out = {"soft": d.take_soft(), "status": d.take_status(), "pending": d.pending, "mse": d.mse,
            "freq_est": d.freq_est, "freq_center": d.freq_center, "ebno": d.ebno}
     if capture_symbols:
         out["symbols"] = d.take_symbols()
+    if capture_prefiltered:
+        out.update(prefiltered=d.take_prefiltered(), write_sizes=wsizes, pre_freq=np.array(pre_freq), pre_freq_sum=np.array(pre_freq_sum))
     return out
+
+
+class Pre8400:
+    """The 8400 bps prefilter of OqpskDemodulator::writeData on its own (oqpskdemodulator.cpp:343-381): mixer_fir_pre as the constructor leaves
+    it (8000 Hz, phase 0, :110-115) and fir_pre with setSettings' kernel (:278-283)."""
+
+    def __init__(self):
+        self.L = lib()
+        self.h = self.L.jo_pre8400_create()
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.jo_pre8400_destroy(self.h)
+            self.h = None
+
+    def write(self, pcm: np.ndarray):
+        """(down-mixed samples that went into the filter, cval_prefiltered) of one write (:354-364, :366-379)"""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        down, out = np.empty(pcm.shape[0], dtype=np.complex128), np.empty(pcm.shape[0], dtype=np.complex128)
+        self.L.jo_pre8400_write(self.h, pcm.ctypes.data, pcm.shape[0], down.ctypes.data, out.ctypes.data)
+        return down, out
+
+    def end_of_write(self, freq_sum: float, n: int):
+        """mixer_fir_pre.SetFreq(mixer2_freq_sum / n) (:607-608)"""
+        self.L.jo_pre8400_end_of_write(self.h, float(freq_sum), int(n))
+
+    def restart(self):
+        """fir_pre.SetKernel as setSettings calls it (:278-283)"""
+        self.L.jo_pre8400_restart(self.h)
+
+    @property
+    def state(self):
+        """(WTptr, WTstep) of mixer_fir_pre"""
+        a, b = C.c_double(), C.c_double()
+        self.L.jo_pre8400_get_state(self.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+
+def rrc_taps(alpha=0.6, firsize=2048, Fs=48000.0, fsym=4200.0) -> np.ndarray:
+    """RootRaisedCosine::design (DSP.h:316-338); the default is the 8400 bps prefilter's kernel (oqpskdemodulator.cpp:281)"""
+    pts = np.empty(firsize + 8, dtype=np.float64)
+    n = lib().jo_rrc_design(float(alpha), int(firsize), float(Fs), float(fsym), pts.ctypes.data)
+    return pts[:n].copy()
 
 
 def _drain(fn, h, width, dtype, rows=1 << 14):

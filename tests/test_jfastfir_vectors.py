@@ -1,9 +1,9 @@
 """The third of the reference's golden-vector tests for the JFFT stand-in: JAERO/tests/jfastfir_tests.cpp:31-58 feeds a
 recorded input through JFastFir with the kernel RRC(0.6, 2049 taps, 48 kHz, 5250 sym/s), nfft 4096, and requires the output recorded
 from JAERO v1.0.4.11 from sample 4096 on, at 1e-5.  Same vectors (tests/golden/jfastfir.npz, made by make_golden.py jfastfir), same
-bar, for: the unmodified JFastFir over the stand-in (oracle/_ref), the oracle's restatement, and the GPU's prefilter kernels -- the
-overlap-save FFT form k_pre8400_fft the 8400 bps C-channel path runs (exactly this filter at alpha 0.6) and the direct form
-k_pre8400_fir kept beside it."""
+bar, for: the unmodified JFastFir over the stand-in (oracle/_ref), the oracle's restatement, and the GPU's prefilter kernel -- the
+overlap-save FFT form k_pre8400_fft the 8400 bps C-channel path runs (exactly this filter at alpha 0.6; the direct form k_pre8400_fir
+left the library in round 3).  tests/test_gpu_pre8400.py compares the same kernel with an exact sum inside a bank."""
 import numpy as np
 import pytest
 
