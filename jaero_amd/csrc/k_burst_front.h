@@ -452,7 +452,7 @@ __global__ __launch_bounds__(TRI_THREADS, 2) void k_trident(const BGeom g, const
                     d.r[s] = fr * w.x - fi * w.y; d.i[s] = fr * w.y + fi * w.x;
                 }
             }
-            wg_fft13_e32(d, xch, p.tw14, t);
+            wg_fft13_e32<0>(d, xch, p.tw14, t); // the output-twiddle form: the acquisition keeps its arithmetic
             // thread t slot s holds X[4 (s*256 + t) + r]
             if (which == 0)
             {

@@ -15,6 +15,9 @@
 // X[2j + 1]), which only changes compile-time addresses of the exchange behind them.  Twiddles: even powers by a chain of products with
 // step^2, each odd power one product more -- two live values instead of a table of 31.  Index maps, twiddles and bank behaviour:
 // tests/test_coarse_fft14_e32_model.py.
+// That is the form with the twiddles on a pass's OUTPUTS (C6_ABSORB 0; the burst acquisition's k_trident keeps it).  The estimate kernels and
+// the channeliser run the form that moves them to the inputs of the next pass and absorbs them into its butterflies (C6_ABSORB 2 below,
+// DESIGN 9 item 32): no twiddle products and no power chains, 842 of 8 021 vector instructions per estimate less.
 #pragma once
 #include "k_coarse2.h"
 
@@ -110,12 +113,151 @@ __device__ __forceinline__ void c6_twiddle32(CV<32> &x, const double2 p1)
     }
 }
 
-// In-place forward 2^14-point DFT of the workgroup's data, natural distribution in and out.  xch: C6_XCH doubles.
+// ---- absorbed twiddles.  The twiddle a pass used to apply to its outputs is moved to the inputs of the pass behind the exchange, where
+// one thread's factors form a geometric sequence r^j -- and a decimation-in-frequency butterfly absorbs such a modulation: for a block of
+// length M whose input j is meant times rho^j,
+//     u = a + rho^(M/2) b,   v = a - rho^(M/2) b = 2 a - u          (6 fused multiply-adds)
+// and the two halves are blocks of length M / 2 with ratios rho and rho W_M.  The 2 L - 1 multipliers of an L-point transform are constant
+// roots times r^(L/2), .., r^2, r (squarings of the base), and a factor -i between two of them costs nothing.  Outputs stay in place, in
+// BIT-REVERSED order, which only changes compile-time addresses behind them.  0: twiddles applied to the outputs as until now (both forms
+// stay buildable: DESIGN 9 item 32), 1: only pass 2 absorbs and its outputs keep a twiddle, 2: every pass behind an exchange absorbs.
+#ifndef C6_ABSORB
+#define C6_ABSORB 2
+#endif
+
+__device__ __forceinline__ constexpr int c6_brev(int v, int bits)
+{
+    int r = 0;
+    for (int i = 0; i < bits; i++) r |= ((v >> i) & 1) << (bits - 1 - i);
+    return r;
+}
+
+// p * W_64^idx, 0 <= idx < 32: idx and idx + 16 share one product
+__device__ __forceinline__ double2 c6_root_mul(const double2 p, int idx)
+{
+#pragma clang fp contract(fast)
+    const int e = idx & 15;
+    double2 r = p;
+    if (e != 0)
+    {
+        const double wr = jd_w64r(e), wi = jd_w64i(e);
+        r = make_double2(p.x * wr - p.y * wi, p.x * wi + p.y * wr);
+    }
+    return (idx & 16) ? make_double2(r.y, -r.x) : r;
+}
+
+// P[i] = r^(2^i), i < 5
+__device__ __forceinline__ void c6_ratio_powers(const double2 r, double2 (&P)[5])
+{
+    P[0] = r;
+#pragma unroll
+    for (int i = 1; i < 5; i++) P[i] = c6_sq(P[i - 1]);
+}
+
+// In-place forward L-point DFT (L = 32, 16) of x[OFF .. OFF + L) times (r W_64^Z)^j, r^(2^i) in P; X[k] is left in slot OFF + c6_brev(k).
+template <int L, int OFF, int Z>
+__device__ __forceinline__ void c6_afft(CV<32> &x, const double2 (&P)[5])
+{
+    constexpr int LG = L == 32 ? 5 : 4, S = 64 / L;
+#pragma unroll
+    for (int lv = 0; lv < LG; lv++)
+    {
+#pragma unroll
+        for (int b = 0; b < (1 << lv); b++)
+        {
+            const int half = L >> (lv + 1);
+            const double2 w = c6_root_mul(P[LG - 1 - lv], half * (S * c6_brev(b, lv) + Z)); // (r W_64^Z W_L^q)^half, q = c6_brev(b)
+#pragma unroll
+            for (int j = 0; j < half; j++)
+            {
+                const int ia = OFF + 2 * half * b + j, ib = ia + half;
+                const double ar = x.r[ia], ai = x.i[ia], br = x.r[ib], bi = x.i[ib];
+                const double ur = __builtin_fma(-w.y, bi, __builtin_fma(w.x, br, ar));
+                const double ui = __builtin_fma(w.x, bi, __builtin_fma(w.y, br, ai));
+                x.r[ia] = ur; x.i[ia] = ui;
+                x.r[ib] = __builtin_fma(2.0, ar, -ur); x.i[ib] = __builtin_fma(2.0, ai, -ui);
+            }
+        }
+        C6_FENCE;
+    }
+}
+
+// two 16-point transforms, of slots 0..15 times r^j and of slots 16..31 times (r W_32)^j
+__device__ __forceinline__ void c6_afft16x2(CV<32> &x, const double2 r)
+{
+    double2 P[5];
+    c6_ratio_powers(r, P);
+    c6_afft<16, 0, 0>(x, P);
+    c6_afft<16, 16, 2>(x, P);
+}
+
+// x[slot OFF + c6_brev(k)] *= c s^k for k < L: what is left of a pass's output twiddle when only the pass in front of it absorbs (C6_ABSORB 1)
+template <int L, int OFF>
+__device__ __forceinline__ void c6_twiddle_brev(CV<32> &x, const double2 c, const double2 s)
+{
+#pragma clang fp contract(fast)
+    constexpr int LG = L == 32 ? 5 : 4;
+    auto app = [&](int slot, const double2 w) __attribute__((always_inline)) {
+        const double r = x.r[slot] * w.x - x.i[slot] * w.y, i = x.r[slot] * w.y + x.i[slot] * w.x;
+        x.r[slot] = r; x.i[slot] = i;
+    };
+    const double2 s2 = c6_sq(s);
+    double2 e = c;
+#pragma unroll
+    for (int j = 0; j < L / 2; j++)
+    {
+        app(OFF + c6_brev(2 * j, LG), e);
+        app(OFF + c6_brev(2 * j + 1, LG), cmul2(e, s));
+        if (j < L / 2 - 1) e = cmul2(e, s2);
+    }
+}
+
+// The last pass of both workgroup transforms: slots 16 h + n3 -> FFT16 over n3 for h = 0, 1 -> X[.. k3 ..] in slot 2 k3 + h (natural order).
+// ABSORBED: the inputs are meant times (r W_32^h)^n3.
+template <bool ABSORBED>
+__device__ __forceinline__ void c6_pass3(CV<32> &d, const double2 r)
+{
+    if constexpr (ABSORBED)
+    {
+        c6_afft16x2(d, r);
+        const CV<32> o = d;
+#pragma unroll
+        for (int k3 = 0; k3 < 16; k3++)
+        {
+            d.r[2 * k3] = o.r[c6_brev(k3, 4)]; d.i[2 * k3] = o.i[c6_brev(k3, 4)];
+            d.r[2 * k3 + 1] = o.r[16 + c6_brev(k3, 4)]; d.i[2 * k3 + 1] = o.i[16 + c6_brev(k3, 4)];
+        }
+    }
+    else
+    {
+        CV<16> in, o0, o1;
+#pragma unroll
+        for (int j = 0; j < 16; j++) { in.r[j] = d.r[j]; in.i[j] = d.i[j]; }
+        regfft<16>(in, o0);
+        C6_FENCE;
+#pragma unroll
+        for (int j = 0; j < 16; j++) { in.r[j] = d.r[16 + j]; in.i[j] = d.i[16 + j]; }
+        regfft<16>(in, o1);
+#pragma unroll
+        for (int k3 = 0; k3 < 16; k3++) { d.r[2 * k3] = o0.r[k3]; d.i[2 * k3] = o0.i[k3]; d.r[2 * k3 + 1] = o1.r[k3]; d.i[2 * k3 + 1] = o1.i[k3]; }
+    }
+}
+
+// In-place forward 2^14-point DFT of the workgroup's data, natural distribution in and out.  xch: C6_XCH doubles.  AB > 0 (above):
+//   pass 1: FFT32 over n1      exchange 1      pass 2: FFT32 over n2 of its input x W_1024^(k1 n2)      exchange 2
+//   pass 3: two FFT16 over n3 of their input x W_N^((k1 + 32 k2) n3)
+// (AB 1: pass 2's outputs x W_N^((k1 + 32 k2) n3) instead, pass 3 as for AB 0.)  Index maps, ratios and bank behaviour of this form:
+// tests/test_coarse_fft14_absorbed_model.py.
+template <int AB = C6_ABSORB>
 __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const double2 *__restrict__ tw, int t)
 {
 #pragma clang fp contract(fast)
-    const double2 st1 = tw[t], st2 = tw[32 * (t & 15)]; // W_N^(n mod 512); W_512^n3 -- requested before the first butterfly
     const int k1u = t >> 4, n3 = t & 15, odd = k1u & 1;
+    // requested before the first butterfly.  AB 0: W_N^(n mod 512); W_512^n3.  Else W_1024^k1, the ratio pass 2 absorbs, and W_N^(k1 + 32
+    // k2lo), pass 3's (its thread is t = k1 + 32 k2lo; the upper half of k2 has W_32 more), or for AB 1 the output twiddle's W_512^n3
+    const double2 st1 = tw[AB ? 16 * k1u : t], st2 = tw[AB == 2 ? t : 32 * n3];
+    double2 st3 = st2;
+    if constexpr (AB == 1) st3 = tw[k1u * n3]; // W_N^(k1 n3)
     const int e1w0 = t, e1w1 = (t + 16) & 511;                  // exchange 1 writer: even / odd k1 rows (odd rows rotated by one n2 row)
     const int e1r = k1u * 512 + odd * 16 + n3;                  // reader: + 16 m, except the one row that wraps
     const int e1rw = e1r + 496 - 512 * odd;                     //   m = 31
@@ -124,10 +266,11 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
     // per launch: SQ_LDS_BANK_CONFLICT)
     const int e2w = k1u + n3 * 513;                             // writer: + (k2 & 15) * 32 + (k2 >> 4) * 8208
     const int e2r = t;                                          // reader: + n3 * 513 + k2hi * 8208
+    auto k2of = [](int s) __attribute__((always_inline)) { return AB ? c6_brev(s, 5) : c6_k(s); }; // the k2 that slot s holds behind pass 2
 
     // ---- pass 1 ----
     c6_fft32(d);
-    c6_twiddle32(d, st1);
+    if constexpr (AB == 0) c6_twiddle32(d, st1);
     C6_FENCE;
     // ---- exchange 1, a plane at a time ----
     jd_lds_barrier(); // the buffer is free (previous transform's last reads / the fold)
@@ -144,36 +287,35 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
     for (int m = 0; m < 32; m++) d.i[m] = xch[(m < 31 ? e1r + 16 * m : e1rw)];
     C6_FENCE;
     // ---- pass 2 ----
-    c6_fft32(d);
-    c6_twiddle32(d, st2);
+    if constexpr (AB == 0)
+    {
+        c6_fft32(d);
+        c6_twiddle32(d, st2);
+    }
+    else
+    {
+        double2 P[5];
+        c6_ratio_powers(st1, P);
+        c6_afft<32, 0, 0>(d, P);
+        if constexpr (AB == 1) c6_twiddle_brev<32, 0>(d, st3, st2);
+    }
     C6_FENCE;
     // ---- exchange 2 ----
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) xch[e2w + (c6_k(s) & 15) * 32 + (c6_k(s) >> 4) * 8208] = d.r[s];
+    for (int s = 0; s < 32; s++) xch[e2w + (k2of(s) & 15) * 32 + (k2of(s) >> 4) * 8208] = d.r[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = xch[e2r + (m & 15) * 513 + (m >> 4) * 8208]; // slot m = n3 + 16 k2hi
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) xch[e2w + (c6_k(s) & 15) * 32 + (c6_k(s) >> 4) * 8208] = d.i[s];
+    for (int s = 0; s < 32; s++) xch[e2w + (k2of(s) & 15) * 32 + (k2of(s) >> 4) * 8208] = d.i[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = xch[e2r + (m & 15) * 513 + (m >> 4) * 8208];
     C6_FENCE;
     // ---- pass 3: FFT16 over n3 for k2hi = 0, 1; X[.. + 1024 k3] -> slot 2 k3 + k2hi (= natural: k = slot * 512 + t) ----
-    {
-        CV<16> in, o0, o1;
-#pragma unroll
-        for (int j = 0; j < 16; j++) { in.r[j] = d.r[j]; in.i[j] = d.i[j]; }
-        regfft<16>(in, o0);
-        C6_FENCE;
-#pragma unroll
-        for (int j = 0; j < 16; j++) { in.r[j] = d.r[16 + j]; in.i[j] = d.i[16 + j]; }
-        regfft<16>(in, o1);
-#pragma unroll
-        for (int k3 = 0; k3 < 16; k3++) { d.r[2 * k3] = o0.r[k3]; d.i[2 * k3] = o0.i[k3]; d.r[2 * k3 + 1] = o1.r[k3]; d.i[2 * k3 + 1] = o1.i[k3]; }
-    }
+    c6_pass3<AB == 2>(d, st2);
 }
 
 
@@ -182,21 +324,26 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
 // (2 x 64 KiB of LDS, one wavefront of each per SIMD): while one is in an exchange or waits for HBM the other computes -- the overlap a
 // single workgroup cannot have.  k_coarse2<13> (16 x 32 x 16 on 512 threads) left half of them idle in its 32-point pass.
 //   n = 256 n1 + 16 n2 + n3        k = k1 + 32 k2 + 512 k3        (n1, k1 < 32;  n2, n3, k2, k3 < 16)
-//   pass 1: FFT32 over n1, x W_N^(k1 (n mod 256))     exchange 1     pass 2: two FFT16 over n2 (k1 = k1a, k1a + 16), x W_256^(k2 n3)
-//   exchange 2     pass 3: two FFT16 over n3 (k2 = k2lo, k2lo + 8)
+//   AB 0: pass 1: FFT32 over n1, x W_N^(k1 (n mod 256))     exchange 1     pass 2: two FFT16 over n2 (k1 = k1a, k1a + 16), x W_256^(k2 n3)
+//         exchange 2     pass 3: two FFT16 over n3 (k2 = k2lo, k2lo + 8)
+//   else: pass 1: FFT32 over n1     exchange 1     pass 2: two FFT16 over n2 of their input x W_512^(k1 n2)     exchange 2
+//         pass 3: two FFT16 over n3 of their input x W_N^((k1 + 32 k2) n3)       (AB 1: pass 2's outputs x that instead)
 // Exchange 1: L = k1 * 256 + 16 n2 + n3 (both sides touch consecutive doubles per 16 lanes).  Exchange 2: L = k1 + 32 k2 + 513 n3 (the 16
 // lanes of a writer group differ in n3 only: the odd stride spreads them over the 16 bank pairs; readers touch 64 consecutive doubles).
 #define C6_XCH13 8208
+template <int AB = C6_ABSORB>
 __device__ __forceinline__ void wg_fft13_e32(CV<32> &d, double *xch, const double2 *__restrict__ tw, int t)
 {
 #pragma clang fp contract(fast)
-    const double2 st1 = tw[t], st2 = tw[32 * (t & 15)]; // W_N^(n mod 256); W_256^n3
     const int k1a = t >> 4, n3 = t & 15;
+    // AB 0: W_N^(n mod 256); W_256^n3.  Else W_512^k1a, the ratio pass 2 absorbs (k1a + 16: W_32 more), and W_N^(k1 + 32 k2lo), pass 3's
+    const double2 st1 = tw[AB ? 16 * k1a : t], st2 = tw[AB == 2 ? t : 32 * n3];
     const int e1r = k1a * 256 + n3;   // reader of exchange 1: + (m >> 4) * 4096 + (m & 15) * 16
     const int e2w = k1a + 513 * n3;   // writer of exchange 2: + 16 g + 32 k2
+    auto k2of = [](int s) __attribute__((always_inline)) { return AB ? c6_brev(s & 15, 4) : (s & 15); }; // the k2 slot s holds behind pass 2
     // ---- pass 1 ----
     c6_fft32(d);
-    c6_twiddle32(d, st1);
+    if constexpr (AB == 0) c6_twiddle32(d, st1);
     C6_FENCE;
     // ---- exchange 1, a plane at a time ----
     jd_lds_barrier();
@@ -213,45 +360,47 @@ __device__ __forceinline__ void wg_fft13_e32(CV<32> &d, double *xch, const doubl
     for (int m = 0; m < 32; m++) d.i[m] = (xch + (m >> 4) * 4096 + (m & 15) * 16)[e1r];
     C6_FENCE;
     // ---- pass 2: slots 0..15 = n2 for k1 = k1a, 16..31 for k1 = k1a + 16 ----
-#pragma unroll
-    for (int g2 = 0; g2 < 2; g2++)
+    if constexpr (AB == 0)
     {
-        CV<16> in, out;
 #pragma unroll
-        for (int j = 0; j < 16; j++) { in.r[j] = d.r[16 * g2 + j]; in.i[j] = d.i[16 * g2 + j]; }
-        regfft<16>(in, out);
-        c4_twiddle16(out, st2);
+        for (int g2 = 0; g2 < 2; g2++)
+        {
+            CV<16> in, out;
 #pragma unroll
-        for (int j = 0; j < 16; j++) { d.r[16 * g2 + j] = out.r[j]; d.i[16 * g2 + j] = out.i[j]; }
+            for (int j = 0; j < 16; j++) { in.r[j] = d.r[16 * g2 + j]; in.i[j] = d.i[16 * g2 + j]; }
+            regfft<16>(in, out);
+            c4_twiddle16(out, st2);
+#pragma unroll
+            for (int j = 0; j < 16; j++) { d.r[16 * g2 + j] = out.r[j]; d.i[16 * g2 + j] = out.i[j]; }
+            C6_FENCE;
+        }
+    }
+    else
+    {
+        c6_afft16x2(d, st1);
+        if constexpr (AB == 1)
+        {
+            c6_twiddle_brev<16, 0>(d, tw[n3 * k1a], st2);         // W_N^(k1 n3) W_256^(k2 n3)
+            c6_twiddle_brev<16, 16>(d, tw[n3 * (k1a + 16)], st2);
+        }
         C6_FENCE;
     }
     // ---- exchange 2: slot 16 g + k2 -> L = (k1a + 16 g) + 32 k2 + 513 n3; reader t3 = k1 + 32 k2lo, slot 16 h + n3 ----
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) (xch + (s >> 4) * 16 + (s & 15) * 32)[e2w] = d.r[s];
+    for (int s = 0; s < 32; s++) (xch + (s >> 4) * 16 + k2of(s) * 32)[e2w] = d.r[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = (xch + (m >> 4) * 256 + (m & 15) * 513)[t];
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) (xch + (s >> 4) * 16 + (s & 15) * 32)[e2w] = d.i[s];
+    for (int s = 0; s < 32; s++) (xch + (s >> 4) * 16 + k2of(s) * 32)[e2w] = d.i[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = (xch + (m >> 4) * 256 + (m & 15) * 513)[t];
     C6_FENCE;
     // ---- pass 3: FFT16 over n3 for h = 0, 1; X[t + 256 h + 512 k3] -> slot 2 k3 + h (natural) ----
-    {
-        CV<16> in, o0, o1;
-#pragma unroll
-        for (int j = 0; j < 16; j++) { in.r[j] = d.r[j]; in.i[j] = d.i[j]; }
-        regfft<16>(in, o0);
-        C6_FENCE;
-#pragma unroll
-        for (int j = 0; j < 16; j++) { in.r[j] = d.r[16 + j]; in.i[j] = d.i[16 + j]; }
-        regfft<16>(in, o1);
-#pragma unroll
-        for (int k3 = 0; k3 < 16; k3++) { d.r[2 * k3] = o0.r[k3]; d.i[2 * k3] = o0.i[k3]; d.r[2 * k3 + 1] = o1.r[k3]; d.i[2 * k3 + 1] = o1.i[k3]; }
-    }
+    c6_pass3<AB == 2>(d, st2);
 }
 
 template <int LOG2N>
