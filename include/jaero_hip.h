@@ -307,7 +307,7 @@ int jaero_ingest_stats(const jaero_ingest *ing, long long *three);
  *                        with another channel count, with a channel whose Fs is not the handle's out_rate, or whose max_write_samples is below (max_write_iq / Hp + 1) Mo.
  *   jaero_chan_profile_* HIP-event time per kernel since the last reset: which 0 = forward transform (k_chan_fwd), 1 = per-channel
  *                        synthesis (k_chan_synth).
- * Deliberately not here: sockets and SDR drivers, input formats other than int16 I/Q, other decimations, other N or hop, per-channel filters,
+ * Deliberately not here: sockets and SDR drivers, other decimations, other N or hop, per-channel filters,
  * burst and OQPSK banks at other rates than 48 kHz (the reference has none either), the multi-GPU fan-out of a capture (every rank creates a
  * channeliser over its shard and is handed the same I/Q), automatic gain control inside the synthesis (it would change the output's
  * definition: the survey below measures, the caller sets the gains), carrier finding on the device (jaero_amd.channeliser.find_carriers is
@@ -326,6 +326,59 @@ int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_channel *ch);
 int jaero_chan_feed(jaero_chan *c, jaero_ctx *bank, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout);
 int jaero_chan_profile_enable(jaero_chan *c, int on);
 int jaero_chan_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset);
+
+/* ---- capture front end of the channeliser: SDR captures in their native formats and rates.  A handle from jaero_chan3_create takes cs16, cu8,
+ * cs8 or cf32 I/Q at an integer rate fs_in, shifts the capture's centre by an exact integer phase word and resamples by the exact rational
+ * ratio to the channeliser's rate Fs_c = out_rate D, on the device; everything behind that (synthesis, survey, feed, retune, pcm_view) is the
+ * channeliser's above, unchanged.  This text is the definition; tests/chan_capture_oracle.py implements it literally in numpy.
+ *   convert    x[n] in int16 LSB units, exact in fp64, per component v:  CS16 x = v;  CU8 x = (2 v - 255) 128;  CS8 x = 256 v;
+ *              CF32 x = (double)v 32768, a component that is not finite is 0.  n counted from create (64-bit), x[n] = 0 for n < 0.
+ *   mix        x'[n] = x[n] e^(j 2 pi ((shift n) mod 2^32) / 2^32), the phase read as a signed word as the synthesis reads its own;
+ *              shift == 0: x' = x exactly, no multiplication happens.  (shift = cycles per input sample x 2^32; read as signed: either way.)
+ *   resample   L / Mr = Fs_c / fs_in in lowest terms; only when L != 1 or Mr != 1.  For the staged index m (64-bit, from create):
+ *              n_m = floor(m Mr / L), phi_m = (m Mr) mod L, z[m] = sum_{j = 0 .. K - 1} h[phi_m + j L] x'[n_m - j]: ascending j from 0.0, real
+ *              and imaginary parts summed separately, every product and every sum rounded once.  z[m] exists once n_m <= T - 1: after T
+ *              input samples exactly ceil(T L / Mr) staged samples exist, however the writes were cut.  h = rtaps[0 .. L K), K =
+ *              taps_per_phase; jaero_amd.channeliser.design_resampler(fs_in, Fs_c, K, beta) is the design the tests use: n = L K,
+ *              fc = 0.5 min(fs_in, Fs_c) / (fs_in L), h[i] = 2 fc sinc(2 fc (i - (n - 1) / 2)) kaiser(n, beta), scaled to sum h = L.
+ *              The group delay (L K - 1) / (2 L fs_in) seconds is not compensated.  With L = Mr = 1, z = x'.
+ *   channelise z takes the place of x in the channeliser's definition, in fp64 (never re-quantised).  Tune words are relative to Fs_c, after
+ *              the shift.  After T input samples floor(ceil(T L / Mr) / Hp) Mo samples per channel have been produced.
+ * Everything is a function of absolute indices only: staged samples and int16 output are bit-identical however the writes are cut.
+ *   jaero_chan3_create       returns the same jaero_chan.  All arguments are checked before a device is looked for, JAERO_EINVAL in this
+ *                            order: out null; cap null; unknown format; fs_in < 1; (with Fs_c = out_rate decim, where both are >= 1:)
+ *                            L > 1024; fs_in > 8 Fs_c or Fs_c > 8 fs_in; (rates differ:) taps_per_phase outside 1 .. 64, rtaps null, a
+ *                            resampler tap that is not finite; then jaero_chan2_create's own checks in its order; then a max_write_iq whose
+ *                            ceil(max_write_iq L / Mr) + 1 + 2 Hp staged samples reach 2^31; then JAERO_ENODEV off gfx950 (no CPU fallback).  max_write_iq counts CAPTURE samples; a write completes at most
+ *                            (ceil(max_write_iq L / Mr) + 1) / Hp + 1 blocks, and jaero_chan_feed / jaero_chan3_feed ask the bank for
+ *                            that many times Mo as max_write_samples.
+ *   jaero_chan3_write / _feed  jaero_chan_write / jaero_chan_feed with niq raw pairs in the handle's format.  They work on every handle: on
+ *                            one from the older creates they forward to the old calls.  jaero_chan_write / jaero_chan_feed work on a
+ *                            capture handle only when its format is JAERO_IQ_CS16; otherwise JAERO_EINVAL, nothing consumed.
+ *   jaero_chan3_read_staged  synchronises, then copies what the last write staged: *npairs (re, im) pairs, the first being z[*first_index].
+ *                            A reader (tests rest on it); JAERO_EINVAL on a handle without a capture front end or when cap_pairs is too small.
+ *   jaero_chan3_profile_read HIP-event time since the last reset: which 0 = the staging kernel (k_capture_stage), 1 = the forward transform
+ *                            over the fp64 history (k_capture_fwd); switched by jaero_chan_profile_enable.  jaero_chan_profile_read's
+ *                            which = 0 stays k_chan_fwd (never launched by a capture handle), 1 the synthesis of either kind of handle.
+ * Poisoning, stream ordering, retune, survey and pcm_view are the channeliser's.  Deliberately not here: real-valued (non-I/Q) captures, rates
+ * whose reduced L exceeds 1024, ratios beyond 8, file containers (WAV, SigMF), SDR drivers, compensation of the resampler's delay. */
+#define JAERO_IQ_CS16 0   /* int16 I, Q                       x = v                  */
+#define JAERO_IQ_CU8  1   /* uint8 I, Q (offset binary)       x = (2 v - 255) * 128  */
+#define JAERO_IQ_CS8  2   /* int8 I, Q                        x = v * 256            */
+#define JAERO_IQ_CF32 3   /* float I, Q, full scale +-1.0     x = (double)v * 32768; a component that is not finite is 0 */
+typedef struct jaero_capture {
+    int format;            /* JAERO_IQ_*                                                                  */
+    int fs_in;             /* capture rate, Hz                                                            */
+    uint32_t shift;        /* centre shift, cycles per input sample * 2^32 (signed reading: either way)   */
+    int taps_per_phase;    /* K, 1 .. 64; ignored when fs_in == out_rate * decim                          */
+    const double *rtaps;   /* resampler prototype h[0 .. L K), NULL when fs_in == out_rate * decim        */
+} jaero_capture;
+int jaero_chan3_create(int device, const jaero_capture *cap, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch,
+                       const double *taps, int ntaps, int max_write_iq, jaero_chan **out);   /* returns the same jaero_chan */
+int jaero_chan3_write(jaero_chan *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout);
+int jaero_chan3_feed(jaero_chan *c, jaero_ctx *bank, const void *iq, int niq, int is_device_ptr, void *stream, int *nout);
+int jaero_chan3_read_staged(jaero_chan *c, double *reim, int cap_pairs, int *npairs, long long *first_index);
+int jaero_chan3_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset); /* 0 = staging kernel, 1 = forward transform */
 
 /* ---- survey of a channeliser's capture: where the carriers are and how strong each channel is, measured on the device from the forward
  * transforms X_p every write leaves behind (the notation is the channeliser's above).  Off at create; while off, a write launches and

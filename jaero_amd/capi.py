@@ -17,6 +17,7 @@ FLAG_EBNO, FLAG_STATUS_LOG, FLAG_CAPTURE_SYMBOLS, FLAG_TRACE = 1, 2, 4, 8
 EV_SIGNAL, EV_EBNO, EV_FREQ, EV_PEAK, EV_TRIDENT = 0, 1, 2, 3, 4
 PCM_CHANNEL_MAJOR, PCM_FRAME_MAJOR = 0, 1
 W_RATE = 1  # jaero_ingest_push: sample rate differs from the bank (warning, data queued)
+IQ_CS16, IQ_CU8, IQ_CS8, IQ_CF32 = 0, 1, 2, 3
 E_OK, E_INVAL, E_NODEV, E_NOMEM, E_HIP, E_OVERFLOW, E_NOTSUP = 0, -1, -2, -3, -4, -5, -6
 
 EXPORTS = [
@@ -37,6 +38,7 @@ EXPORTS = [
     "jaero_chan_feed", "jaero_chan_profile_enable", "jaero_chan_profile_read", "jaero_chan2_create",
     "jaero_survey_enable", "jaero_survey_reset", "jaero_survey_read_psd", "jaero_survey_read_levels", "jaero_survey_profile_read",
     "jaero_chan2_retune_all",
+    "jaero_chan3_create", "jaero_chan3_write", "jaero_chan3_feed", "jaero_chan3_read_staged", "jaero_chan3_profile_read",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -84,6 +86,13 @@ class ChanChannel(C.Structure):
     """struct jaero_chan_channel: tuning word (centre = tune * Fs_in / 2^32, signed), audio word (offset = audio * out_rate / 2^32), gain."""
 
     _fields_ = [("tune", C.c_uint32), ("audio", C.c_uint32), ("gain", C.c_double)]
+
+
+class Capture(C.Structure):
+    """struct jaero_capture: format (IQ_*), capture rate in Hz, centre shift (cycles per input sample x 2^32), taps per phase K and the
+    resampler prototype h[0 .. L K) (null when the capture already runs at out_rate x decim)."""
+
+    _fields_ = [("format", C.c_int), ("fs_in", C.c_int), ("shift", C.c_uint32), ("taps_per_phase", C.c_int), ("rtaps", C.c_void_p)]
 
 
 class JaeroError(RuntimeError):
@@ -191,6 +200,11 @@ def lib():
     L.jaero_survey_read_levels.argtypes = [vp, vp, vp]
     L.jaero_survey_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_chan2_retune_all.argtypes = [vp, vp]
+    L.jaero_chan3_create.argtypes = [ip, C.POINTER(Capture), ip, ip, ip, vp, vp, ip, ip, C.POINTER(vp)]
+    L.jaero_chan3_write.argtypes = [vp, vp, ip, ip, vp, C.POINTER(ip)]
+    L.jaero_chan3_feed.argtypes = [vp, vp, vp, ip, ip, vp, C.POINTER(ip)]
+    L.jaero_chan3_read_staged.argtypes = [vp, vp, ip, C.POINTER(ip), C.POINTER(C.c_longlong)]
+    L.jaero_chan3_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_shard_range.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.jaero_comm_get_unique_id.argtypes = [vp]
     L.jaero_comm_create.argtypes = [ip, ip, ip, vp, C.POINTER(vp)]

@@ -6,11 +6,16 @@ caller.  Frequencies are 32-bit words: `tune_word(hz, fs)` is the word nearest a
 frequency a word really is, `channel_words(tune, audio, decim)` the integers the kernels derive from a channel's words.
 The survey (`survey_enable`, `read_psd`, `read_levels`) measures the capture's spectrum and every channel's level on the device;
 `find_carriers` (host numpy, no hot path) turns the spectrum into centre frequencies, `suggest_gains` the levels into gains, and
-`retune_all` applies both.  All device arithmetic happens in libjaero_hip.so; there is no CPU fallback.
+`retune_all` applies both.  `Channeliser(..., capture=Capture(fs_in=..., fmt=...))` takes an SDR capture in its own format (cs16, cu8, cs8,
+cf32) and at its own integer rate: the device converts, shifts the centre by an exact phase word and resamples by the exact rational ratio
+to fs_out x decim (jaero_chan3_*); `design_resampler` is the prototype it uses by default.  All device arithmetic happens in
+libjaero_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -56,6 +61,41 @@ def design_taps(decim: int, cutoff_hz: Optional[float] = None, ntaps: int = 8193
     k = np.arange(ntaps) - (ntaps - 1) / 2
     h = 2 * fc * np.sinc(2 * fc * k) * np.kaiser(ntaps, beta)
     return h / h.sum()
+
+
+FORMATS = {"cs16": capi.IQ_CS16, "cu8": capi.IQ_CU8, "cs8": capi.IQ_CS8, "cf32": capi.IQ_CF32}
+_FORMAT_DTYPE = {"cs16": np.int16, "cu8": np.uint8, "cs8": np.int8, "cf32": np.float32}
+
+
+def resample_ratio(fs_in: int, fs_c: int) -> Tuple[int, int]:
+    """(L, Mr): fs_c / fs_in in lowest terms."""
+    fs_in, fs_c = int(fs_in), int(fs_c)
+    g = math.gcd(fs_in, fs_c)
+    return fs_c // g, fs_in // g
+
+
+def design_resampler(fs_in: int, fs_c: int, taps_per_phase: int = 32, beta: float = 10.0) -> Tuple[np.ndarray, int, int]:
+    """(h, L, Mr): the polyphase prototype of the capture front end (include/jaero_hip.h cites this).  L / Mr = fs_c / fs_in in lowest
+    terms, n = L K taps at the rate fs_in L, cut-off fc = 0.5 min(fs_in, fs_c) / (fs_in L) cycles per sample:
+    h[i] = 2 fc sinc(2 fc (i - (n - 1) / 2)) kaiser(n, beta), scaled so that sum h = L (every phase has a DC gain near 1)."""
+    L, Mr = resample_ratio(fs_in, fs_c)
+    n = L * int(taps_per_phase)
+    fc = 0.5 * min(fs_in, fs_c) / (float(fs_in) * L)
+    i = np.arange(n) - (n - 1) / 2
+    h = 2 * fc * np.sinc(2 * fc * i) * np.kaiser(n, beta)
+    return h * (L / h.sum()), L, Mr
+
+
+@dataclass
+class Capture:
+    """What `Channeliser(capture=...)` is told about the capture: rate in Hz (an integer), format ("cs16", "cu8", "cs8", "cf32"), the shift
+    of its centre in Hz (rounded to the nearest phase word of fs_in; positive moves the spectrum up), taps per phase of the resampler and
+    its prototype (None: design_resampler(fs_in, fs_c, taps_per_phase))."""
+    fs_in: int
+    fmt: str = "cs16"
+    shift_hz: float = 0.0
+    taps_per_phase: int = 32
+    rtaps: Optional[np.ndarray] = None
 
 
 def _channel_array(channels: Sequence) -> "C.Array":
@@ -106,14 +146,34 @@ class Channeliser:
     against the bank's Fs; it enters no arithmetic."""
 
     def __init__(self, decim: int, channels: Sequence, taps: Optional[np.ndarray] = None, device: int = 0,
-                 max_write_iq: int = 16 * HP, fs_out: float = FS_OUT):
+                 max_write_iq: int = 16 * HP, fs_out: float = FS_OUT, capture: Optional[Capture] = None):
         self.L = capi.lib()
         t = design_taps(decim, fs_out=fs_out) if taps is None else np.ascontiguousarray(taps, dtype=np.float64)
         arr = _channel_array(channels)
         h = C.c_void_p()
         rate = int(fs_out) if float(fs_out) == int(fs_out) else 0  # a rate that is no integer is none of the three
-        capi.check(self.L.jaero_chan2_create(device, int(decim), rate, len(arr), C.cast(arr, C.c_void_p), t.ctypes.data, int(t.size),
-                                             int(max_write_iq), C.byref(h)))
+        self.capture = capture
+        self.fmt = "cs16"
+        self.shift_word = 0
+        if capture is None:
+            capi.check(self.L.jaero_chan2_create(device, int(decim), rate, len(arr), C.cast(arr, C.c_void_p), t.ctypes.data, int(t.size),
+                                                 int(max_write_iq), C.byref(h)))
+            self._fs_in = float(fs_out) * int(decim)
+        else:
+            if capture.fmt not in FORMATS:
+                raise ValueError(f"capture format {capture.fmt!r} is none of {sorted(FORMATS)}")
+            fs_in, fs_c = int(capture.fs_in), rate * int(decim)
+            rt = capture.rtaps
+            if rt is None and fs_in != fs_c and fs_in >= 1 and fs_c >= 1 and resample_ratio(fs_in, fs_c)[0] <= 1024:
+                rt = design_resampler(fs_in, fs_c, capture.taps_per_phase)[0]
+            rt = None if rt is None else np.ascontiguousarray(rt, dtype=np.float64)
+            self.shift_word = tune_word(capture.shift_hz, float(fs_in)) if fs_in >= 1 else 0
+            cs = capi.Capture(FORMATS[capture.fmt], fs_in, self.shift_word, int(capture.taps_per_phase), None if rt is None else rt.ctypes.data)
+            capi.check(self.L.jaero_chan3_create(device, C.byref(cs), int(decim), rate, len(arr), C.cast(arr, C.c_void_p), t.ctypes.data,
+                                                 int(t.size), int(max_write_iq), C.byref(h)))
+            self.fmt = capture.fmt
+            self._fs_in = float(fs_in)
+            self.rtaps = rt
         self.h = h
         self.fs_out = float(fs_out)
         self.decim, self.nch, self.device, self.max_write_iq = int(decim), len(arr), device, int(max_write_iq)
@@ -132,22 +192,52 @@ class Channeliser:
         except Exception:
             pass
 
-    @staticmethod
-    def _input(iq):
-        """(pointer, I/Q pairs, is_device_ptr, keep-alive) of a numpy int16 array [n, 2] / [2 n] or a torch int16 tensor on the device."""
+    @property
+    def fs_c(self) -> float:
+        """The channeliser's own rate, fs_out x decim: what tune words are relative to."""
+        return self.fs_out * self.decim
+
+    @property
+    def fs_in(self) -> float:
+        """The capture's rate: fs_c unless a `Capture` said otherwise."""
+        return self._fs_in
+
+    def capture_tune_word(self, hz: float) -> int:
+        """The tune word of a frequency `hz` of the CAPTURE (relative to its centre, at fs_in): the shift the device applies is added (the
+        frequency its word really is), the sum is taken relative to fs_c."""
+        return tune_word(hz + word_hz(self.shift_word, self._fs_in), self.fs_c)
+
+    def _input(self, iq):
+        """(pointer, I/Q pairs, is_device_ptr, keep-alive) of a numpy array [n, 2] / [2 n] of the handle's format (uint8, int8, int16,
+        float32; complex64 [n] for cf32) or a torch tensor of that element size on the device."""
+        want = _FORMAT_DTYPE[self.fmt]
         if isinstance(iq, np.ndarray):
-            a = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+            if iq.dtype == np.complex64:
+                if self.fmt != "cf32":
+                    raise TypeError(f"a complex64 array on a {self.fmt} channeliser")
+                a = np.ascontiguousarray(iq).view(np.float32).reshape(-1)
+            elif self.fmt == "cs16" and self.capture is None:
+                a = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1)
+            else:
+                if iq.dtype != want:
+                    raise TypeError(f"a {iq.dtype} array on a {self.fmt} channeliser (takes {np.dtype(want)})")
+                a = np.ascontiguousarray(iq).reshape(-1)
             assert a.size % 2 == 0
             return a.ctypes.data, a.size // 2, 0, a
         t = iq
-        assert t.is_cuda and t.is_contiguous() and t.element_size() == 2 and t.numel() % 2 == 0
+        size = np.dtype(want).itemsize
+        if t.is_complex():
+            assert self.fmt == "cf32" and t.element_size() == 8 and t.is_cuda and t.is_contiguous()
+            return t.data_ptr(), t.numel(), 1, t
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == size and t.numel() % 2 == 0
         return t.data_ptr(), t.numel() // 2, 1, t
 
     def write(self, iq, stream: int = 0) -> int:
         """Consumes the I/Q pairs; returns the samples per channel this write produced (a multiple of Mo, possibly 0)."""
         ptr, n, dev, _keep = self._input(iq)
         nout = C.c_int(0)
-        capi.check(self.L.jaero_chan_write(self.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
+        fn = self.L.jaero_chan_write if self.capture is None else self.L.jaero_chan3_write
+        capi.check(fn(self.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
         self.last_nout = nout.value
         return nout.value
 
@@ -155,9 +245,27 @@ class Channeliser:
         """write, then the bank's write of what came out (device to device, no synchronisation).  Returns samples per channel."""
         ptr, n, dev, _keep = self._input(iq)
         nout = C.c_int(0)
-        capi.check(self.L.jaero_chan_feed(self.h, bank.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
+        fn = self.L.jaero_chan_feed if self.capture is None else self.L.jaero_chan3_feed
+        capi.check(fn(self.h, bank.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
         self.last_nout = nout.value
         return nout.value
+
+    def read_staged(self) -> Tuple[np.ndarray, int]:
+        """(z, first): what the last write staged for the forward transform, complex128, and the absolute staged index of z[0]
+        (synchronises; only on a channeliser with a `Capture`)."""
+        L, Mr = resample_ratio(int(self._fs_in), int(self.fs_c))
+        buf = np.empty((-(-self.max_write_iq * L // Mr) + 1, 2), dtype=np.float64)
+        n, first = C.c_int(0), C.c_longlong(0)
+        capi.check(self.L.jaero_chan3_read_staged(self.h, buf.ctypes.data, buf.shape[0], C.byref(n), C.byref(first)))
+        z = np.empty(n.value, dtype=np.complex128)  # component by component: a sum with 1j would turn -0.0 into 0.0
+        z.real, z.imag = buf[: n.value, 0], buf[: n.value, 1]
+        return z, first.value
+
+    def capture_profile_read(self, which: int, reset: bool = False):
+        """(total ms, launches) of capture kernel `which`: 0 = staging (k_capture_stage), 1 = forward transform (k_capture_fwd)."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.L.jaero_chan3_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
 
     def read_pcm(self) -> np.ndarray:
         """The last write's output, int16 [nch, nout], on the host (synchronises)."""

@@ -6,6 +6,23 @@
 // blocks done, and the channels' parameters.  Everything about frequency is integer arithmetic on the host (chan_param).
 #pragma once
 #include "k_chan.h" // (here and not among the kernel headers at the top of jaero_hip.hip: tests cite that file's lines by number)
+#include "k_chan_capture.h"
+
+// What jaero_chan3_create adds to a handle (capture_host.h): the capture's description in lowest terms, the raw history and the counts.
+struct ChanCapture
+{
+    int format = 0, fs_in = 0, K = 1, L = 1, Mr = 1, bps = 4; // bps: bytes per raw I/Q pair
+    unsigned shift = 0;
+    bool resample = false;
+    char *d_raw[2] = {nullptr, nullptr}; // [K - 1 + max_write_iq] raw pairs each; d_raw[rcur] holds the last K - 1 pairs, then the write's
+    int rcur = 0;
+    double *d_hp = nullptr;              // [L][K]: hp[phi K + j] = h[phi + j L]
+    double2 *d_z[2] = {nullptr, nullptr}; // the channeliser's history in fp64, [2 Hp + smax] each, used as d_in is
+    long long T = 0, m = 0;              // capture samples taken, staged samples made
+    const double2 *last_ptr = nullptr;   // what the last write staged (jaero_chan3_read_staged)
+    int last_n = 0;
+    long long last_first = 0;
+};
 
 struct jaero_chan
 {
@@ -24,7 +41,8 @@ struct jaero_chan
     int16_t *d_pcm = nullptr;  // [nch][nout of the last write], capacity nch * nblk_max * Mo
     int last_nout = 0;
     std::vector<jaero_chan_channel> channels;
-    KernelTimer timer{4};      // 0 k_chan_fwd, 1 k_chan_synth, 2 k_chan_psd, 3 k_chan_level
+    KernelTimer timer{6};      // 0 k_chan_fwd, 1 k_chan_synth, 2 k_chan_psd, 3 k_chan_level, 4 k_capture_stage, 5 k_capture_fwd
+    std::unique_ptr<ChanCapture> cap; // null unless the handle came from jaero_chan3_create
     // the survey (jaero_survey_*): nothing below exists before the first enable
     int survey = 0;            // bit 0 spectrum, bit 1 levels
     double *d_psd = nullptr;   // [N]: S
@@ -84,12 +102,8 @@ extern "C" void jaero_chan_destroy(jaero_chan *c)
     delete c;
 }
 
-// decim: the total decimation from the capture to the output; out_rate: what the output is called (jaero_chan_feed compares it with the bank's Fs)
-extern "C" int jaero_chan2_create(int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps,
-                                  int max_write_iq, jaero_chan **out)
+static int chan_check_create(int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps, int max_write_iq)
 {
-    if (!out) return fail(JAERO_EINVAL, "jaero_chan2_create: out is null");
-    *out = nullptr;
     if (!ch || !taps) return fail(JAERO_EINVAL, "jaero_chan2_create: null channels / taps");
     if (decim != 16 && decim != 32 && decim != 64 && decim != 128 && decim != 256)
         return fail(JAERO_EINVAL, "jaero_chan2_create: decim %d is not 16, 32, 64, 128 or 256", decim);
@@ -102,18 +116,25 @@ extern "C" int jaero_chan2_create(int device, int decim, int out_rate, int nchan
         if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "jaero_chan2_create: channel %d: gain %g is not finite and positive", i, ch[i].gain);
     for (int i = 0; i < ntaps; i++)
         if (!__builtin_isfinite(taps[i])) return fail(JAERO_EINVAL, "jaero_chan2_create: tap %d is not finite", i);
-    { const int rc = open_device(device); if (rc) return rc; }
+    return 0;
+}
 
-    std::unique_ptr<jaero_chan> c(new (std::nothrow) jaero_chan());
-    if (!c) return fail(JAERO_ENOMEM, "jaero_chan2_create: out of memory");
+// Everything behind the checks and the device.  smax = 0: an int16 handle (history d_in, max_write_iq samples a write); smax > 0: a capture
+// handle, whose fp64 history (capture_host.h) takes at most smax staged samples a write -- d_in is not allocated.
+static int chan_build(std::unique_ptr<jaero_chan> &c, int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch,
+                      const double *taps, int ntaps, int max_write_iq, long long smax)
+{
     int rc = 0;
     c->device = device; c->decim = decim; c->out_rate = out_rate; c->nch = nchannels; c->max_write_iq = max_write_iq;
     c->M = CHAN_N / decim; c->Mo = c->M / 2;
-    c->nblk_max = max_write_iq / CHAN_HP + 1;
+    c->nblk_max = smax > 0 ? (int)((smax + 1) / CHAN_HP + 1) : max_write_iq / CHAN_HP + 1;
     c->channels.assign(ch, ch + nchannels);
-    const size_t nin = 2 * (size_t)CHAN_HP + (size_t)max_write_iq;
-    DA(c->mem, c->d_in[0], nin);
-    DA(c->mem, c->d_in[1], nin);
+    if (smax == 0)
+    {
+        const size_t nin = 2 * (size_t)CHAN_HP + (size_t)max_write_iq;
+        DA(c->mem, c->d_in[0], nin);
+        DA(c->mem, c->d_in[1], nin);
+    }
     DA(c->mem, c->d_spec, (size_t)c->nblk_max * CHAN_N);
     DA(c->mem, c->d_gm, c->M);
     DA(c->mem, c->d_twm, 32);
@@ -127,6 +148,21 @@ extern "C" int jaero_chan2_create(int device, int decim, int out_rate, int nchan
     HIPCHK(hipMemcpy(c->d_twm, twiddles(c->M, 32).data(), sizeof(double2) * 32, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_tw, twiddles(CHAN_N, CHAN_N).data(), sizeof(double2) * CHAN_N, hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute((const void *)k_chan_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH * (int)sizeof(double)));
+    return 0;
+}
+
+// decim: the total decimation from the capture to the output; out_rate: what the output is called (jaero_chan_feed compares it with the bank's Fs)
+extern "C" int jaero_chan2_create(int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps,
+                                  int max_write_iq, jaero_chan **out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_chan2_create: out is null");
+    *out = nullptr;
+    { const int rc = chan_check_create(decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq); if (rc) return rc; }
+    { const int rc = open_device(device); if (rc) return rc; }
+    std::unique_ptr<jaero_chan> c(new (std::nothrow) jaero_chan());
+    if (!c) return fail(JAERO_ENOMEM, "jaero_chan2_create: out of memory");
+    const int rc = chan_build(c, device, decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq, 0);
+    if (rc) return rc;
     *out = c.release();
     return 0;
 }
@@ -168,9 +204,49 @@ static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipSt
     else go(k_chan_synth<256>, ChanShape<256>::ITEMS, ChanShape<256>::THREADS);
 }
 
+// What every write does behind its forward transform of nblk > 0 blocks: the synthesis, the survey's kernels when enabled, then the last
+// hop and what lies behind it (`total` samples wait in `hist`, of `elem` bytes each) become the head of the other history buffer `other`.
+static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, void *other, size_t elem, hipStream_t st)
+{
+    int pi = c->timer.begin(1, st);
+    chan_launch_synth(c, nblk, c->blocks_done, st);
+    LAUNCHCHK("k_chan_synth");
+    c->timer.end(pi, st);
+    if (c->survey & 1)
+    {
+        pi = c->timer.begin(2, st);
+        hipLaunchKernelGGL(k_chan_psd, dim3(CHAN_N / CHAN_PSD_THREADS), dim3(CHAN_PSD_THREADS), 0, st, (const double2 *)c->d_spec, c->d_psd, nblk);
+        LAUNCHCHK("k_chan_psd");
+        c->timer.end(pi, st);
+        c->psd_blocks += nblk;
+    }
+    if (c->survey & 2)
+    {
+        pi = c->timer.begin(3, st);
+        chan_launch_level(c, nblk, st);
+        LAUNCHCHK("k_chan_level");
+        c->timer.end(pi, st);
+        c->lvl_blocks += nblk;
+    }
+    const int rest = total - nblk * CHAN_HP;
+    HIPCHK(hipMemcpyAsync(other, (const char *)hist + (size_t)nblk * CHAN_HP * elem, elem * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
+    c->cur ^= 1;
+    c->pending = rest;
+    c->blocks_done += nblk;
+    return 0;
+}
+
+static int capture_write(jaero_chan *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who);
+
 extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "jaero_chan_write: bad arguments");
+    if (c->cap)
+    {
+        if (c->cap->format != JAERO_IQ_CS16)
+            return fail(JAERO_EINVAL, "jaero_chan_write: the handle's capture format is %d, not int16 I/Q; use jaero_chan3_write", c->cap->format);
+        return capture_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
+    }
     if (niq > c->max_write_iq) return fail(JAERO_EINVAL, "jaero_chan_write: niq %d exceeds max_write_iq %d", niq, c->max_write_iq);
     CHANPOISONCHK(c, "jaero_chan_write");
     HIPCHK(hipSetDevice(c->device));
@@ -193,36 +269,11 @@ extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int i
     c->pending = total;
     if (nblk > 0)
     {
-        int pi = c->timer.begin(0, st);
+        const int pi = c->timer.begin(0, st);
         hipLaunchKernelGGL(k_chan_fwd, dim3(nblk), dim3(C2_THREADS), C6_XCH * sizeof(double), st, (const int *)in, c->d_spec, (const double2 *)c->d_tw);
         LAUNCHCHK("k_chan_fwd");
         c->timer.end(pi, st);
-        pi = c->timer.begin(1, st);
-        chan_launch_synth(c, nblk, c->blocks_done, st);
-        LAUNCHCHK("k_chan_synth");
-        c->timer.end(pi, st);
-        if (c->survey & 1)
-        {
-            pi = c->timer.begin(2, st);
-            hipLaunchKernelGGL(k_chan_psd, dim3(CHAN_N / CHAN_PSD_THREADS), dim3(CHAN_PSD_THREADS), 0, st, (const double2 *)c->d_spec, c->d_psd, nblk);
-            LAUNCHCHK("k_chan_psd");
-            c->timer.end(pi, st);
-            c->psd_blocks += nblk;
-        }
-        if (c->survey & 2)
-        {
-            pi = c->timer.begin(3, st);
-            chan_launch_level(c, nblk, st);
-            LAUNCHCHK("k_chan_level");
-            c->timer.end(pi, st);
-            c->lvl_blocks += nblk;
-        }
-        // the last hop and what lies behind it become the other buffer's head
-        const int rest = total - nblk * CHAN_HP;
-        HIPCHK(hipMemcpyAsync(c->d_in[c->cur ^ 1], in + (size_t)nblk * CHAN_HP, sizeof(int) * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
-        c->cur ^= 1;
-        c->pending = rest;
-        c->blocks_done += nblk;
+        { const int rc = chan_after_fwd(c, nblk, total, in, c->d_in[c->cur ^ 1], sizeof(int), st); if (rc) return rc; }
     }
     HIPCHK(hipGetLastError());
     c->last_nout = *nout = nblk * c->Mo;
@@ -307,17 +358,24 @@ extern "C" int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *c
     return 0;
 }
 
+// what a feed checks on the bank before anything advances
+static int chan_feed_check(const jaero_chan *c, const jaero_ctx *bank, const char *who)
+{
+    if (bank->device != c->device) return fail(JAERO_EINVAL, "%s: the bank is on device %d, the channeliser on %d", who, bank->device, c->device);
+    if (bank->o_nch != c->nch) return fail(JAERO_EINVAL, "%s: the bank has %d channels, the channeliser %d", who, bank->o_nch, c->nch);
+    for (const jaero_settings &s : bank->settings)
+        if (s.Fs != (double)c->out_rate)
+            return fail(JAERO_EINVAL, "%s: the bank runs at Fs = %g; the channeliser's output is %d", who, s.Fs, c->out_rate);
+    if (bank->max_write < c->nblk_max * c->Mo)
+        return fail(JAERO_EINVAL, "%s: the bank's max_write_samples %d is below the %d blocks a write can complete * %d = %d", who, bank->max_write,
+                    c->nblk_max, c->Mo, c->nblk_max * c->Mo);
+    return 0;
+}
+
 extern "C" int jaero_chan_feed(jaero_chan *c, jaero_ctx *bank, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !bank || !nout) return fail(JAERO_EINVAL, "jaero_chan_feed: null argument");
-    if (bank->device != c->device) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank is on device %d, the channeliser on %d", bank->device, c->device);
-    if (bank->o_nch != c->nch) return fail(JAERO_EINVAL, "jaero_chan_feed: the bank has %d channels, the channeliser %d", bank->o_nch, c->nch);
-    for (const jaero_settings &s : bank->settings)
-        if (s.Fs != (double)c->out_rate)
-            return fail(JAERO_EINVAL, "jaero_chan_feed: the bank runs at Fs = %g; the channeliser's output is %d", s.Fs, c->out_rate);
-    if (bank->max_write < c->nblk_max * c->Mo)
-        return fail(JAERO_EINVAL, "jaero_chan_feed: the bank's max_write_samples %d is below (max_write_iq / %d + 1) * %d = %d", bank->max_write,
-                    CHAN_HP, c->Mo, c->nblk_max * c->Mo);
+    { const int rc = chan_feed_check(c, bank, "jaero_chan_feed"); if (rc) return rc; }
     int rc = jaero_chan_write(c, iq, niq, is_device_ptr, stream, nout);
     if (rc || *nout <= 0) return rc;
     return jaero_write(bank, c->d_pcm, *nout, JAERO_PCM_CHANNEL_MAJOR, 1, stream);
@@ -423,3 +481,5 @@ extern "C" int jaero_survey_profile_read(jaero_chan *c, int which, double *total
     if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_survey_profile_read: bad arguments");
     return c->timer.read(c->device, 2 + which, total_ms, launches, reset);
 }
+
+#include "capture_host.h"

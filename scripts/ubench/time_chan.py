@@ -3,7 +3,10 @@ channel) per step.  Prints one JSON line: HIP-event time per step of k_chan_fwd 
 from the same steps, their ratio (the yardstick: the two channeliser kernels together against the demodulator bank's own step time), the
 same per second of signal and per output sample, the engine clock over the timed steps.  Defaults: the headline OQPSK bank behind D = 32.
 --survey: the survey (spectrum and levels) is on during the same steps; k_chan_psd and k_chan_level per step are printed beside the rest.
-usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup] [--decim D] [--fs-out 48000|24000|12000] [--bank oqpsk|msk600|msk1200] [--survey]"""
+--capture FMT:FS_IN: the channeliser takes a capture of that format (cs16, cu8, cs8, cf32) at that rate through its capture front end; a step
+is then the capture samples that stage 16 hops, and k_capture_stage and k_capture_fwd are timed beside k_chan_synth (k_chan_fwd does not run).
+usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup] [--decim D] [--fs-out 48000|24000|12000] [--bank oqpsk|msk600|msk1200] [--survey]
+       [--capture FMT:FS_IN]"""
 import argparse
 import json
 import os
@@ -16,7 +19,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from bench_state import GpuStateSampler  # noqa: E402
-from jaero_amd.channeliser import HP, Channeliser  # noqa: E402
+from jaero_amd.channeliser import HP, Capture, Channeliser, resample_ratio  # noqa: E402
 from jaero_amd.demodulator import DemodulatorBank, MskSettings, OqpskSettings  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -27,12 +30,28 @@ ap.add_argument("--decim", type=int, default=32, help="total decimation, capture
 ap.add_argument("--fs-out", type=float, default=48000.0, help="the channeliser's output rate = the bank's Fs")
 ap.add_argument("--bank", choices=("oqpsk", "msk600", "msk1200"), default="oqpsk")
 ap.add_argument("--survey", action="store_true", help="survey the capture (spectrum and levels) in every step and time its two kernels")
+ap.add_argument("--capture", default=None, metavar="FMT:FS_IN", help="feed a capture of this format and rate through the capture front end")
 args = ap.parse_args()
 nch, K, W, decim, fs_out, hops = args.channels, args.steps, args.warmup, args.decim, args.fs_out, 16
 rng = np.random.default_rng(1)
-iq = torch.from_numpy(rng.integers(-8000, 8000, size=(hops * HP, 2), dtype=np.int16)).cuda()
 chans = [(int(t), 715827883, 1.0) for t in rng.integers(0, 1 << 32, size=nch, dtype=np.uint64)]
-chan = Channeliser(decim, chans, max_write_iq=hops * HP, fs_out=fs_out)
+capture = None
+if args.capture:
+    fmt, fs_in = args.capture.split(":")
+    capture = Capture(fs_in=int(fs_in), fmt=fmt)
+    L, Mr = resample_ratio(int(fs_in), int(fs_out * decim))
+    nin = hops * HP * Mr // L  # the largest count of capture samples that stages no more than 16 hops; exactly 16 when L divides it
+    assert -(-nin * L // Mr) == hops * HP, "choose a rate whose 16 hops are a whole number of capture samples"
+    if fmt == "cf32":
+        raw = (0.25 * rng.normal(size=(nin, 2))).astype(np.float32)
+    else:
+        lo, hi, dt = {"cs16": (-8000, 8000, np.int16), "cu8": (64, 192, np.uint8), "cs8": (-64, 64, np.int8)}[fmt]
+        raw = rng.integers(lo, hi, size=(nin, 2), dtype=dt)
+    iq = torch.from_numpy(raw).cuda()
+    chan = Channeliser(decim, chans, max_write_iq=nin, fs_out=fs_out, capture=capture)
+else:
+    iq = torch.from_numpy(rng.integers(-8000, 8000, size=(hops * HP, 2), dtype=np.int16)).cuda()
+    chan = Channeliser(decim, chans, max_write_iq=hops * HP, fs_out=fs_out)
 if args.bank == "oqpsk":
     settings = OqpskSettings(Fs=fs_out)
 else:
@@ -66,7 +85,16 @@ if args.survey:
     survey = {"k_chan_psd_ms_per_step": round(psd / K, 4), "k_chan_psd_launches": npsd,
               "k_chan_level_ms_per_step": round(lvl / K, 4), "k_chan_level_launches": nlvl,
               "k_chan_level_over_synth": round(lvl / syn, 4), "survey_blocks": int(chan.read_psd()[1])}
-chan_ms, bank_ms = (fwd + syn) / K, (loop + coarse) / K
+cap = {}
+if capture is not None:
+    (stg, nstg), (cfwd, ncf) = chan.capture_profile_read(0), chan.capture_profile_read(1)
+    cap = {"capture": args.capture, "capture_samples_per_step": int(iq.shape[0]),
+           "k_capture_stage_ms_per_step": round(stg / K, 4), "k_capture_stage_launches": nstg,
+           "k_capture_fwd_ms_per_step": round(cfwd / K, 4), "k_capture_fwd_launches": ncf}
+front = fwd  # what stands in front of the synthesis: k_chan_fwd, or on a capture handle (where it never runs) the two capture kernels
+if capture is not None:
+    front = stg + cfwd
+chan_ms, bank_ms = (front + syn) / K, (loop + coarse) / K
 signal_s = hops * HP / (fs_out * decim)  # seconds of signal per step
 print(json.dumps({
     "channels": nch, "decim": decim, "fs_out": fs_out, "bank": args.bank, "bank_kernels": [bank.profile_kernel(0), bank.profile_kernel(1)],
@@ -75,7 +103,7 @@ print(json.dumps({
     "bank_ms_per_signal_s": round(bank_ms / signal_s, 3),
     "k_chan_synth_ps_per_output_sample": round(1e9 * syn / K / (nch * hops * chan.Mo), 3),
     "k_chan_fwd_ms_per_step": round(fwd / K, 4), "k_chan_fwd_launches": nf,
-    "k_chan_synth_ms_per_step": round(syn / K, 4), "k_chan_synth_launches": ns, **survey,
+    "k_chan_synth_ms_per_step": round(syn / K, 4), "k_chan_synth_launches": ns, **survey, **cap,
     "bank_sample_loop_ms_per_step": round(loop / K, 4), "bank_sample_loop_launches": nl,
     "bank_coarse_ms_per_step": round(coarse / K, 4), "bank_coarse_launches": nc,
     "chan_ms_per_step": round(chan_ms, 4), "bank_ms_per_step": round(bank_ms, 4), "chan_over_bank": round(chan_ms / bank_ms, 4),
