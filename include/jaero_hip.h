@@ -493,6 +493,42 @@ int jaero_debug_coarse_poke(jaero_ctx *ctx, int channel, const double *ring_reim
 int jaero_debug_coarse_launch(jaero_ctx *ctx, const int *channels, int nlist, int grid);
 int jaero_debug_coarse_peek(jaero_ctx *ctx, int channel, double *ring_reim, double *y, jaero_coarse_state *st);
 
+/* Test hooks: a burst bank's transform kernels on their own (k_hist_push_frames / _chmajor, k_hilbert_fft, k_ev_compact and the bank's k_trident
+ * instantiation, jaero_debug_kernel_variant(ctx, 1)), launched by the lines jaero_write launches them with.  All synchronise the bank first.
+ * JAERO_EINVAL before any launch: null ctx, a bank that is not a burst bank, a channel outside [0, nchannels), values out of range.  hilbert,
+ * poke_cv and trident mark the bank as the coarse hooks do (a later jaero_write or setter returns JAERO_EHIP); geom and read_hist only read and
+ * may be called between real writes.
+ *   jaero_debug_burst_geom      the geometry the kernels run with, the trident grid jaero_write uses and the samples written so far.
+ *   jaero_debug_burst_hilbert   one write's history push (either layout, host PCM, 1 .. max_write_samples) and the k_hilbert_fft launch of each of
+ *                               its segments, cut as jaero_write cuts them; nothing behind it.  Advances the bank's sample count.  out_im
+ *                               [nchannels][nsamples] (host) receives im y of every segment.
+ *   jaero_debug_burst_read_hist n samples of a channel's PCM history from absolute sample index first_abs_index on; the window lies wholly
+ *                               among the last hist_len samples written.
+ *   jaero_debug_burst_poke_cv   real parts of the ring of AGC'd analytic samples by absolute sample index: sample a lives at slot a mod cv_len
+ *                               (mathematical modulo; a may be negative: the trident window of an early event starts before the stream);
+ *                               1 <= n <= cv_len.
+ *   jaero_debug_burst_trident   fills every trident result of the bank (padding channels included) with a sentinel, gives the listed channels
+ *                               (distinct, any order, nlist in 0 .. nchannels) their event positions ev_pos[k] in [0, maxseg) and every other
+ *                               channel none, then launches k_ev_compact and the trident kernel for a segment that starts at sample n0 >= 0 with
+ *                               `grid` workgroups (0 = as jaero_write, else 1 .. tri_grid).  results[k] = the result of channels[k]; *nchanged =
+ *                               the entries of the whole bank that no longer hold the sentinel. */
+typedef struct jaero_burst_geom
+{
+    int kind, nch, nchp, maxseg, hist_len, hil_lat, cv_len, D1, tri_sz, nb, nt, tri_grid;
+    long long nsamples;
+} jaero_burst_geom;
+typedef struct jaero_trident_result
+{
+    int ok, pad; /* ok: the part of the acceptance test that depends on the window alone */
+    double freq, phase_deg, vol_gain, metric;
+} jaero_trident_result;
+int jaero_debug_burst_geom(jaero_ctx *ctx, jaero_burst_geom *out);
+int jaero_debug_burst_hilbert(jaero_ctx *ctx, const int16_t *pcm, int layout, int nsamples, double *out_im);
+int jaero_debug_burst_read_hist(jaero_ctx *ctx, int channel, long long first_abs_index, int n, int16_t *out);
+int jaero_debug_burst_poke_cv(jaero_ctx *ctx, int channel, long long first_abs_index, int n, const double *re);
+int jaero_debug_burst_trident(jaero_ctx *ctx, const int *channels, const int *ev_pos, int nlist, long long n0, int grid,
+                              jaero_trident_result *results, int *nchanged);
+
 /* ------------------------------------------------------------------------------------------------ multi-GPU edge operations
  * The path shards by channel with no steady-state exchange (the reference runs its two stereo burst channels as two unrelated objects,
  * JAERO/audioburstoqpskdemodulator.cpp:8-10); the north star names two operations at the edges: fan out shared PCM, gather decoded bits.

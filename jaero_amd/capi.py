@@ -29,6 +29,7 @@ EXPORTS = [
     "jaero_debug_sample_loop_layout", "jaero_debug_kernel_variant",
     "jaero_debug_coarse_poke", "jaero_debug_coarse_launch", "jaero_debug_coarse_peek",
     "jaero_debug_schedule", "jaero_debug_schedule_lanes", "jaero_debug_prefilter", "jaero_debug_read_prefiltered", "jaero_read_events",
+    "jaero_debug_burst_geom", "jaero_debug_burst_hilbert", "jaero_debug_burst_read_hist", "jaero_debug_burst_poke_cv", "jaero_debug_burst_trident",
     "jaero_debug_pre8400_write", "jaero_debug_pre8400_poke", "jaero_debug_pre8400_peek", "jaero_debug_pre8400_restart", "jaero_debug_pre8400_read_ring",
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
@@ -80,6 +81,19 @@ class Pre8400State(C.Structure):
 
     _fields_ = [("ptr", C.c_double), ("step", C.c_double), ("fsum", C.c_double), ("hold", C.c_longlong), ("n0", C.c_longlong),
                 ("nprev", C.c_int), ("ring", C.c_int), ("cap", C.c_int)]
+
+
+class BurstGeom(C.Structure):
+    """struct jaero_burst_geom: what jaero_debug_burst_geom reports."""
+
+    _fields_ = [(n, C.c_int) for n in ("kind", "nch", "nchp", "maxseg", "hist_len", "hil_lat", "cv_len", "D1", "tri_sz", "nb", "nt", "tri_grid")] + [
+        ("nsamples", C.c_longlong)]
+
+
+class TridentResult(C.Structure):
+    """struct jaero_trident_result: one channel's result of jaero_debug_burst_trident."""
+
+    _fields_ = [("ok", C.c_int), ("pad", C.c_int), ("freq", C.c_double), ("phase_deg", C.c_double), ("vol_gain", C.c_double), ("metric", C.c_double)]
 
 
 class ChanChannel(C.Structure):
@@ -164,6 +178,11 @@ def lib():
     L.jaero_debug_pre8400_peek.argtypes = [vp, ip, C.POINTER(Pre8400State)]
     L.jaero_debug_pre8400_restart.argtypes = [vp, ip]
     L.jaero_debug_pre8400_read_ring.argtypes = [vp, ip, C.c_longlong, ip, vp]
+    L.jaero_debug_burst_geom.argtypes = [vp, C.POINTER(BurstGeom)]
+    L.jaero_debug_burst_hilbert.argtypes = [vp, vp, ip, ip, vp]
+    L.jaero_debug_burst_read_hist.argtypes = [vp, ip, C.c_longlong, ip, vp]
+    L.jaero_debug_burst_poke_cv.argtypes = [vp, ip, C.c_longlong, ip, vp]
+    L.jaero_debug_burst_trident.argtypes = [vp, vp, vp, ip, C.c_longlong, ip, vp, C.POINTER(ip)]
     L.jaero_aerol_create.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_create_burst.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_read_packets.argtypes = [vp, ip, vp, ip, C.POINTER(ip)]

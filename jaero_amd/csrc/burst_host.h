@@ -233,11 +233,50 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
     return 0;
 }
 
-static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layout, int is_device_ptr, hipStream_t st)
+// The launch lines of a write's transform kernels, shared by burst_write and the test hooks jaero_debug_burst_* (below): the history push of
+// one write, k_hilbert_fft of one segment, k_ev_compact and the bank's trident kernel with `grid` workgroups (burst_write: c->trident.grid).
+static int burst_launch_hist_push(jaero_ctx *c, const int16_t *dsrc, int nsamples, int layout, int slot0, hipStream_t st)
 {
     const BGeom &g = c->bg;
     const BPtrs &p = c->bp;
     const int nch = g.nch, nchp = g.nchp;
+    if (layout == JAERO_PCM_FRAME_MAJOR)
+        hipLaunchKernelGGL(k_hist_push_frames, dim3((nchp + 255) / 256, nsamples), dim3(256), 0, st, dsrc, nch, nch, p.pcmhist, nchp, g.hist_len, slot0, nsamples);
+    else
+        hipLaunchKernelGGL(k_hist_push_chmajor, dim3(nchp / 64, (nsamples + 63) / 64), dim3(256), 0, st, dsrc, nch, nsamples, p.pcmhist, nchp, g.hist_len, slot0);
+    LAUNCHCHK("the burst history push");
+    return 0;
+}
+static int burst_launch_hilbert(jaero_ctx *c, int n, long long n0, hipStream_t st)
+{
+    const BGeom &g = c->bg;
+    const BPtrs &p = c->bp;
+    hipLaunchKernelGGL(k_hilbert_fft, dim3(g.nchp / 8, (int)(((n0 + n - 1) >> 11) - (n0 >> 11) + 1)), dim3(PF_THREADS), 4 * 2 * PRE_L * (int)sizeof(double), st, g, p, n, n0);
+    LAUNCHCHK("k_hilbert_fft");
+    return 0;
+}
+static int burst_launch_ev_compact(jaero_ctx *c, hipStream_t st)
+{
+    const BGeom &g = c->bg;
+    const BPtrs &p = c->bp;
+    hipLaunchKernelGGL(k_ev_compact, dim3(1), dim3(1024), 0, st, (const unsigned long long *)p.ev_mask, g.ngroups, p.ev_list, p.ev_count);
+    LAUNCHCHK("k_ev_compact");
+    return 0;
+}
+static int burst_launch_trident(jaero_ctx *c, int grid, long long n0, hipStream_t st)
+{
+    const KernelRec<TridentFn> &tri = c->trident;
+    hipLaunchKernelGGL(tri.fn, dim3(grid), dim3(tri.block), tri.lds, st, c->bg, c->bp, n0);
+    LAUNCHCHK("k_trident");
+    return 0;
+}
+
+static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layout, int is_device_ptr, hipStream_t st)
+{
+    const BGeom &g = c->bg;
+    const BPtrs &p = c->bp;
+    const int nch = g.nch;
+    int rc = 0;
     const int16_t *dsrc = pcm;
     if (!is_device_ptr)
     {
@@ -248,14 +287,9 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
     {
         const int pi = c->timer.begin(2, st);
         const int slot0 = (int)(c->nsamples_total % g.hist_len);
-        if (layout == JAERO_PCM_FRAME_MAJOR)
-            hipLaunchKernelGGL(k_hist_push_frames, dim3((nchp + 255) / 256, nsamples), dim3(256), 0, st, dsrc, nch, nch, p.pcmhist, nchp, g.hist_len, slot0, nsamples);
-        else
-            hipLaunchKernelGGL(k_hist_push_chmajor, dim3(nchp / 64, (nsamples + 63) / 64), dim3(256), 0, st, dsrc, nch, nsamples, p.pcmhist, nchp, g.hist_len, slot0);
-        LAUNCHCHK("the burst history push");
+        if ((rc = burst_launch_hist_push(c, dsrc, nsamples, layout, slot0, st))) return rc;
         c->timer.end(pi, st);
     }
-    const KernelRec<TridentFn> &tri = c->trident;
     const KernelRec<BurstDemodFn> &dm = c->bdemod;
     int first = 1;
     c->poisoned = true; // the history push above is idempotent (same slots if the write is repeated); from here on state advances
@@ -264,8 +298,7 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         const int n = (nsamples - pos) < g.maxseg ? (nsamples - pos) : g.maxseg;
         const long long n0 = c->nsamples_total;
         int pi = c->timer.begin(3, st);
-        hipLaunchKernelGGL(k_hilbert_fft, dim3(g.nchp / 8, (int)(((n0 + n - 1) >> 11) - (n0 >> 11) + 1)), dim3(PF_THREADS), 4 * 2 * PRE_L * (int)sizeof(double), st, g, p, n, n0);
-        LAUNCHCHK("k_hilbert_fft");
+        if ((rc = burst_launch_hilbert(c, n, n0, st))) return rc;
         c->timer.end(pi, st);
         pi = c->timer.begin(4, st);
         // bt_hold_left is an UPPER BOUND of every lane's BI_BT_HOLD (the per-lane, per-sample counter the kernel obeys): each setSettings sets
@@ -279,12 +312,10 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         }
         else hipLaunchKernelGGL(k_burst_front<false>, dim3(g.ngroups), dim3(64), 0, st, g, p, n, n0);
         LAUNCHCHK("k_burst_front");
-        hipLaunchKernelGGL(k_ev_compact, dim3(1), dim3(1024), 0, st, (const unsigned long long *)p.ev_mask, g.ngroups, p.ev_list, p.ev_count);
-        LAUNCHCHK("k_ev_compact");
+        if ((rc = burst_launch_ev_compact(c, st))) return rc;
         c->timer.end(pi, st);
         pi = c->timer.begin(1, st);
-        hipLaunchKernelGGL(tri.fn, dim3(tri.grid), dim3(tri.block), tri.lds, st, g, p, n0);
-        LAUNCHCHK("k_trident");
+        if ((rc = burst_launch_trident(c, c->trident.grid, n0, st))) return rc;
         c->timer.end(pi, st);
         pi = c->timer.begin(0, st);
         hipLaunchKernelGGL(dm.fn, dim3(dm.grid), dim3(dm.block), dm.lds, st, g, p, n, n0, first);
@@ -369,5 +400,126 @@ static int burst_set_settings(jaero_ctx *c, int channel, const jaero_settings *s
         if (g.kind == JAERO_KIND_BURST_MSK) c->m.flags[ch] &= ~JF_DCD; // dcd = false at the end of BurstMskDemodulator::setSettings
     }
     c->bt_hold_left = g.bt_lag;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ test hooks: the burst banks' transform kernels alone
+// (tests/test_gpu_burst_acq.py), through burst_launch_hist_push / _hilbert / _ev_compact / _trident as burst_write calls them.  hilbert, poke_cv
+// and trident leave the bank's state where no write would: poisoned, as after a write that failed part-way.
+static int burst_hook_enter(jaero_ctx *c, const char *who, int channel, bool poison)
+{
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (!c->burst) return fail(JAERO_EINVAL, "%s: not a burst bank", who);
+    if (channel < 0 || channel >= c->bg.nch) return fail(JAERO_EINVAL, "%s: channel %d outside [0, %d)", who, channel, c->bg.nch);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    if (poison) c->poisoned = true;
+    return 0;
+}
+extern "C" int jaero_debug_burst_geom(jaero_ctx *c, jaero_burst_geom *out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_debug_burst_geom: null output");
+    int rc = burst_hook_enter(c, "jaero_debug_burst_geom", 0, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    out->kind = g.kind; out->nch = g.nch; out->nchp = g.nchp; out->maxseg = g.maxseg; out->hist_len = g.hist_len; out->hil_lat = g.hil_lat;
+    out->cv_len = g.cv_len; out->D1 = g.D1; out->tri_sz = g.tri_sz; out->nb = g.nb; out->nt = g.nt; out->tri_grid = c->trident.grid;
+    out->nsamples = c->nsamples_total;
+    return 0;
+}
+extern "C" int jaero_debug_burst_hilbert(jaero_ctx *c, const int16_t *pcm, int layout, int nsamples, double *out_im)
+{
+    if (c && c->burst && (!pcm || !out_im || nsamples <= 0 || nsamples > c->max_write))
+        return fail(JAERO_EINVAL, "jaero_debug_burst_hilbert: nsamples %d (1 .. max_write_samples %d of host PCM, and an output)", nsamples, c->max_write);
+    if (layout != JAERO_PCM_CHANNEL_MAJOR && layout != JAERO_PCM_FRAME_MAJOR) return fail(JAERO_EINVAL, "jaero_debug_burst_hilbert: bad layout");
+    int rc = burst_hook_enter(c, "jaero_debug_burst_hilbert", 0, true);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    hipStream_t st = c->last_stream;
+    HIPCHK(hipMemcpyAsync(c->d_pcm_raw, pcm, sizeof(int16_t) * (size_t)g.nch * nsamples, hipMemcpyHostToDevice, st));
+    if ((rc = burst_launch_hist_push(c, c->d_pcm_raw, nsamples, layout, (int)(c->nsamples_total % g.hist_len), st))) return rc;
+    std::vector<double> him((size_t)g.ngroups * g.maxseg * 64);
+    for (int pos = 0; pos < nsamples;)
+    {
+        const int n = (nsamples - pos) < g.maxseg ? (nsamples - pos) : g.maxseg; // burst_write's segments
+        if ((rc = burst_launch_hilbert(c, n, c->nsamples_total, st))) return rc;
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpy(him.data(), c->bp.him, sizeof(double) * him.size(), hipMemcpyDeviceToHost));
+        for (int ch = 0; ch < g.nch; ch++)
+            for (int i = 0; i < n; i++) out_im[(size_t)ch * nsamples + pos + i] = him[((size_t)(ch >> 6) * g.maxseg + i) * 64 + (ch & 63)];
+        c->nsamples_total += n;
+        pos += n;
+    }
+    return 0;
+}
+extern "C" int jaero_debug_burst_read_hist(jaero_ctx *c, int ch, long long first, int n, int16_t *out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_debug_burst_read_hist: null output");
+    int rc = burst_hook_enter(c, "jaero_debug_burst_read_hist", ch, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    const long long H = g.hist_len, oldest = c->nsamples_total > H ? c->nsamples_total - H : 0;
+    if (n <= 0 || first < oldest || first > c->nsamples_total - n)
+        return fail(JAERO_EINVAL, "jaero_debug_burst_read_hist: samples [%lld, %lld + %d) are not all among the last %lld of the %lld written", first, first, n, H, (long long)c->nsamples_total);
+    // the channel's cells of four samples (hb_idx, k_burst_front.h), one row of the ring each
+    std::vector<int16_t> ring((size_t)H);
+    HIPCHK(hipMemcpy2D(ring.data(), sizeof(int16_t) * 4, c->bp.pcmhist + (size_t)ch * 4, sizeof(int16_t) * 4 * (size_t)g.nchp, sizeof(int16_t) * 4, (size_t)(H / 4), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) out[i] = ring[(size_t)((first + i) % H)];
+    return 0;
+}
+extern "C" int jaero_debug_burst_poke_cv(jaero_ctx *c, int ch, long long first, int n, const double *re)
+{
+    if (!re) return fail(JAERO_EINVAL, "jaero_debug_burst_poke_cv: null input");
+    if (c && c->burst && (n <= 0 || n > c->bg.cv_len || first < -(1LL << 40) || first > (1LL << 40)))
+        return fail(JAERO_EINVAL, "jaero_debug_burst_poke_cv: n %d (1 .. cv_len %d samples from an index within +- 2^40)", n, c->bg.cv_len);
+    int rc = burst_hook_enter(c, "jaero_debug_burst_poke_cv", ch, true);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    const long long R = g.cv_len;
+    const int slot = (int)(((first % R) + R) % R), n1 = n < g.cv_len - slot ? n : g.cv_len - slot; // sample a lives at a mod cv_len (k_burst_front: s_cv = n0 % cv_len)
+    double *row = c->bp.cvre + (size_t)(ch >> 6) * g.cv_len * 64 + (ch & 63);
+    HIPCHK(hipMemcpy2D(row + (size_t)slot * 64, sizeof(double) * 64, re, sizeof(double), sizeof(double), (size_t)n1, hipMemcpyHostToDevice));
+    if (n > n1) HIPCHK(hipMemcpy2D(row, sizeof(double) * 64, re + n1, sizeof(double), sizeof(double), (size_t)(n - n1), hipMemcpyHostToDevice));
+    return 0;
+}
+static_assert(sizeof(jaero_trident_result) == sizeof(TriResult) && offsetof(jaero_trident_result, metric) == offsetof(TriResult, metric), "jaero_trident_result is TriResult");
+extern "C" int jaero_debug_burst_trident(jaero_ctx *c, const int *channels, const int *ev_pos, int nlist, long long n0, int grid, jaero_trident_result *results, int *nchanged)
+{
+    int rc = burst_hook_enter(c, "jaero_debug_burst_trident", 0, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    const int nch = g.nch, nchp = g.nchp;
+    if (nlist < 0 || nlist > nch || (nlist > 0 && (!channels || !ev_pos || !results)))
+        return fail(JAERO_EINVAL, "jaero_debug_burst_trident: nlist %d (0 .. %d channels with their event positions and room for their results)", nlist, nch);
+    if (n0 < 0 || n0 > (1LL << 40)) return fail(JAERO_EINVAL, "jaero_debug_burst_trident: n0 %lld outside [0, 2^40]", n0);
+    if (grid < 0 || grid > c->trident.grid) return fail(JAERO_EINVAL, "jaero_debug_burst_trident: grid %d (0 = as jaero_write, else 1 .. %d)", grid, c->trident.grid);
+    std::vector<int> evp((size_t)nchp, -1);
+    std::vector<unsigned long long> mask((size_t)g.ngroups, 0ULL);
+    for (int k = 0; k < nlist; k++)
+    {
+        const int ch = channels[k];
+        if (ch < 0 || ch >= nch || evp[(size_t)ch] >= 0)
+            return fail(JAERO_EINVAL, "jaero_debug_burst_trident: entry %d (channel %d) is outside [0, %d) or listed twice", k, ch, nch);
+        if (ev_pos[k] < 0 || ev_pos[k] >= g.maxseg) return fail(JAERO_EINVAL, "jaero_debug_burst_trident: entry %d: event position %d outside [0, %d)", k, ev_pos[k], g.maxseg);
+        evp[(size_t)ch] = ev_pos[k];
+        mask[(size_t)(ch >> 6)] |= 1ULL << (ch & 63);
+    }
+    hipStream_t st = c->last_stream;
+    c->poisoned = true;
+    const int sentinel = 0xA5;
+    HIPCHK(hipMemset(c->bp.tri, sentinel, sizeof(TriResult) * (size_t)nchp));
+    HIPCHK(hipMemcpy(c->bp.I + (size_t)BI_EV_POS * nchp, evp.data(), sizeof(int) * (size_t)nchp, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->bp.ev_mask, mask.data(), sizeof(unsigned long long) * mask.size(), hipMemcpyHostToDevice));
+    if ((rc = burst_launch_ev_compact(c, st))) return rc;
+    if ((rc = burst_launch_trident(c, grid ? grid : c->trident.grid, n0, st))) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<TriResult> tri((size_t)nchp);
+    HIPCHK(hipMemcpy(tri.data(), c->bp.tri, sizeof(TriResult) * (size_t)nchp, hipMemcpyDeviceToHost));
+    TriResult untouched;
+    memset(&untouched, sentinel, sizeof untouched);
+    int changed = 0;
+    for (int ch = 0; ch < nchp; ch++) changed += memcmp(&tri[(size_t)ch], &untouched, sizeof untouched) != 0;
+    for (int k = 0; k < nlist; k++) memcpy(&results[k], &tri[(size_t)channels[k]], sizeof(TriResult));
+    if (nchanged) *nchanged = changed;
     return 0;
 }

@@ -111,6 +111,9 @@ long jo_burst_take_soft(jo_burst *d, int16_t *dst, long cap);
  * (value = +metric accepted / -metric rejected) */
 long jo_burst_take_events(jo_burst *d, double *dst, long caprows);
 void jo_burst_trace(jo_burst *d, int on);
+/* with trace on: the window (tridentbuffer, *row_len doubles) of every trident check so far, one row per kind-4 event, in their order; a bank
+ * whose settings change its bit rate between checks must be drained before the change (rows are cut at the current length) */
+long jo_burst_take_trident_windows(jo_burst *d, double *dst, long caprows, int *row_len);
 /* rows [re, im, mse] of pt_qpsk (burst OQPSK, while startstop>0) / pt_msk (burst MSK, every symbol instant) */
 void jo_burst_capture_symbols(jo_burst *d, int on);
 long jo_burst_take_symbols(jo_burst *d, double *dst, long caprows);
@@ -118,6 +121,15 @@ int jo_burst_pending_soft(jo_burst *d);
 double jo_burst_get_mse(jo_burst *d);
 double jo_burst_get_freq_est(jo_burst *d);
 /* QJHilbertFilter pieces (JAERO/DSP.cpp:754-794) */
+/* The signal-only part of the trident checks (burstoqpskdemodulator.cpp:412-481, burstmskdemodulator.cpp:444-520) on a window of tri_sz samples,
+ * what tridentbuffer holds when the check runs: the functions the demodulators above call.  ok leaves out burst MSK's dcd and cntr terms.
+ * base_abs / top_abs (16384 doubles each, or NULL): |base| and |top| of the bins the searches run over.  Returns 0, or -1 for bad arguments. */
+typedef struct jo_trident_result
+{
+    int ok, pad;
+    double freq, phase_deg, vol_gain, metric; /* metric: maxval (burst OQPSK) / minval (burst MSK), the traced value */
+} jo_trident_result;
+int jo_trident(int kind, double Fs, double fb, const double *window, int tri_sz, jo_trident_result *result, double *base_abs, double *top_abs);
 int jo_hilbert_kernel(int N, double *re_im);
 typedef struct jo_hilbert jo_hilbert;
 jo_hilbert *jo_hilbert_create(int N);

@@ -230,7 +230,7 @@ struct jo_burst
     cpx pt_d, sig2_last; double vol_gain;
     /* RxDataBits */
     short rx[96]; int nrx;
-    gbuf soft, events, symbols;
+    gbuf soft, events, symbols, triwin; /* triwin: with trace on, the window of every trident check (tridentbuffer_sz doubles each) */
     int capture_symbols, trace;
 };
 typedef struct jo_burst jo_burst;
@@ -322,7 +322,10 @@ static void boqpsk_ctor(jo_burst *d) /* burstoqpskdemodulator.cpp:4-131 */
     d->rotator_freq = 0; /* uninitialised in the reference */
 }
 
-static void boqpsk_trident_check(jo_burst *d, long sample) /* burstoqpskdemodulator.cpp:412-515 */
+/* The part of the trident check that depends on the window alone (burstoqpskdemodulator.cpp:412-471 and the values :473-481 sets from it): the two
+ * transforms, the searches, the acceptance terms, the frequency, the phase in degrees, vol_gain and the metric.  boqpsk_trident_check applies it;
+ * jo_trident exports it. */
+static void boqpsk_trident_signal(jo_burst *d, jo_trident_result *r)
 {
     const double SPS = d->SamplesPerSymbol;
     const int nb = qRound_(128.0 * SPS);
@@ -352,15 +355,29 @@ static void boqpsk_trident_check(jo_burst *d, long sample) /* burstoqpskdemodula
         double a = hypot(d->out_base[i].re, d->out_base[i].im);
         if (a > minval) { minval = a; minvalbin = i; }
     }
-    int ok = (maxval > 500.0) && (fabs((((double)(maxvalbin - minvalbin))) * hzperbin) < 20.0);
+    r->ok = (maxval > 500.0) && (fabs((((double)(maxvalbin - minvalbin))) * hzperbin) < 20.0);
+    r->pad = 0;
+    double carrierphase = atan2(d->out_base[(int)minvalbin].im, d->out_base[(int)minvalbin].re) - (M_PI / 4.0);
+    r->freq = hzperbin * minvalbin;
+    r->phase_deg = (180.0 / M_PI) * carrierphase;
+    r->vol_gain = 1.4142 * 500.0 / minval;
+    r->metric = maxval;
+}
+
+static void boqpsk_trident_check(jo_burst *d, long sample) /* burstoqpskdemodulator.cpp:412-515 */
+{
+    jo_trident_result r;
+    boqpsk_trident_signal(d, &r);
+    if (d->trace) gpush(&d->triwin, d->tridentbuffer, sizeof(double) * (size_t)d->tridentbuffer_sz);
+    const int ok = r.ok;
+    const double maxval = r.metric;
     if (d->trace) burst_event(d, sample, JO_EV_TRIDENT, ok ? maxval : -maxval);
     if (ok)
     {
-        double carrierphase = atan2(d->out_base[(int)minvalbin].im, d->out_base[(int)minvalbin].re) - (M_PI / 4.0);
-        wt_setfreq(&d->mixer2, hzperbin * minvalbin);
-        wt_set_phase_deg(&d->mixer2, (180.0 / M_PI) * carrierphase);
+        wt_setfreq(&d->mixer2, r.freq);
+        wt_set_phase_deg(&d->mixer2, r.phase_deg);
         burst_event(d, sample, JO_EV_FREQ, d->mixer2.freq);
-        d->vol_gain = 1.4142 * 500.0 / minval;
+        d->vol_gain = r.vol_gain;
         d->pointbuff_ptr = -128 - 128;
         wt_setfreq(&d->st_osc, d->st_osc_ref.freq);
         wt_set_phase_deg(&d->st_osc, 0);
@@ -677,7 +694,9 @@ static void bmsk_ctor(jo_burst *d) /* burstmskdemodulator.cpp:9-84 */
     d->vol_gain = 1; d->rotator_freq = 0;                         /* same */
 }
 
-static void bmsk_trident_check(jo_burst *d, long sample) /* burstmskdemodulator.cpp:444-569 */
+/* the same for burst MSK (burstmskdemodulator.cpp:444-510 and the values :512-520 sets from it); the acceptance terms that depend on the
+ * demodulator's state (dcd, cntr) stay in bmsk_trident_check */
+static void bmsk_trident_signal(jo_burst *d, jo_trident_result *r)
 {
     const double SPS = d->SamplesPerSymbol;
     int size_base = 126, size_top = 74;
@@ -709,15 +728,30 @@ static void bmsk_trident_check(jo_burst *d, long sample) /* burstmskdemodulator.
         }
     }
     int distfrompeak = abs(maxtoppos - minvalbin);
-    int ok = (minval > 500.0 && abs(distfrompeak - peakspacingbins) < abs(peakspacingbins / 20) && !(d->dcd) && !(d->cntr > 0 && d->cntr < (500 * SPS)));
+    r->ok = (minval > 500.0 && abs(distfrompeak - peakspacingbins) < abs(peakspacingbins / 20));
+    r->pad = 0;
+    r->vol_gain = 1.4142 * (500.0 / (minval / 3));
+    double carrierphase = atan2(d->out_base[minvalbin].im, d->out_base[minvalbin].re) - (M_PI / 4.0);
+    r->phase_deg = (180.0 / M_PI) * carrierphase;
+    r->freq = ((maxtopposhigh + maxtoppos) / 2) * hzperbin;
+    r->metric = minval;
+}
+
+static void bmsk_trident_check(jo_burst *d, long sample) /* burstmskdemodulator.cpp:444-569 */
+{
+    const double SPS = d->SamplesPerSymbol;
+    jo_trident_result r;
+    bmsk_trident_signal(d, &r);
+    if (d->trace) gpush(&d->triwin, d->tridentbuffer, sizeof(double) * (size_t)d->tridentbuffer_sz);
+    const double minval = r.metric;
+    int ok = (r.ok && !(d->dcd) && !(d->cntr > 0 && d->cntr < (500 * SPS)));
     if (d->trace) burst_event(d, sample, JO_EV_TRIDENT, ok ? minval : -minval);
     if (ok)
     {
-        d->vol_gain = 1.4142 * (500.0 / (minval / 3));
-        double carrierphase = atan2(d->out_base[minvalbin].im, d->out_base[minvalbin].re) - (M_PI / 4.0);
-        wt_set_phase_deg(&d->mixer2, (180.0 / M_PI) * carrierphase);
-        wt_setfreq(&d->mixer2, ((maxtopposhigh + maxtoppos) / 2) * hzperbin);
-        bmsk_center_freq_changed(d, ((maxtopposhigh + maxtoppos) / 2) * hzperbin, sample);
+        d->vol_gain = r.vol_gain;
+        wt_set_phase_deg(&d->mixer2, r.phase_deg);
+        wt_setfreq(&d->mixer2, r.freq);
+        bmsk_center_freq_changed(d, r.freq, sample);
         burst_event(d, sample, JO_EV_FREQ, d->mixer2.freq);
         ma_zero(d->pointmean);
         d->pointbuff_ptr = 0;
@@ -874,7 +908,7 @@ void jo_burst_destroy(jo_burst *d)
     fir_free(d->fir_re); fir_free(d->fir_im);
     ma_free(d->ebno.E); ma_free(d->ebno.E2); ma_free(d->msema); ma_free(d->pointmean);
     free(d->delayedsmpl.buffer);
-    free(d->soft.p); free(d->events.p); free(d->symbols.p);
+    free(d->soft.p); free(d->events.p); free(d->symbols.p); free(d->triwin.p);
     free(d);
 }
 /* setSettings on the LIVE object (a user pressing OK in the settings dialog): the same functions the constructor path runs -- new AGCs, EbNo
@@ -896,12 +930,47 @@ long jo_burst_write(jo_burst *d, const int16_t *pcm, long n)
 }
 long jo_burst_take_soft(jo_burst *d, int16_t *dst, long cap) { return gtake(&d->soft, dst, sizeof(int16_t), cap); }
 long jo_burst_take_events(jo_burst *d, double *dst, long caprows) { return gtake(&d->events, dst, 3 * sizeof(double), caprows); }
+/* with jo_burst_trace(d, 1): the windows the trident checks ran on, one row of *row_len doubles per JO_EV_TRIDENT event, in their order */
+long jo_burst_take_trident_windows(jo_burst *d, double *dst, long caprows, int *row_len)
+{
+    if (row_len) *row_len = d->tridentbuffer_sz;
+    return dst ? gtake(&d->triwin, dst, sizeof(double) * (size_t)d->tridentbuffer_sz, caprows) : 0;
+}
 void jo_burst_capture_symbols(jo_burst *d, int on) { d->capture_symbols = on; }
 long jo_burst_take_symbols(jo_burst *d, double *dst, long caprows) { return gtake(&d->symbols, dst, 3 * sizeof(double), caprows); }
 int jo_burst_pending_soft(jo_burst *d) { return d->nrx; }
 double jo_burst_get_mse(jo_burst *d) { return d->mse; }
 double jo_burst_get_freq_est(jo_burst *d) { return d->mixer2.freq; }
 /* streaming Hilbert filter alone (what hfir.update does to a real input), for the tests that pin the HIP FIR */
+/* The trident checks on a window the caller supplies (tri_sz samples, what the demodulator finds in tridentbuffer when the check runs):
+ * boqpsk_trident_signal / bmsk_trident_signal, the functions the demodulators call, on an object that holds nothing but what they read.
+ * base_abs / top_abs (N/2 = 16384 doubles each, optional): |base| and |top| of the bins the searches run over. */
+int jo_trident(int kind, double Fs, double fb, const double *window, int tri_sz, jo_trident_result *result, double *base_abs, double *top_abs)
+{
+    if ((kind != JO_KIND_BURST_OQPSK && kind != JO_KIND_BURST_MSK) || !window || !result || tri_sz <= 0 || !(Fs > 0) || !(fb > 0)) return -1;
+    jo_burst *d = (jo_burst *)calloc(1, sizeof(jo_burst));
+    d->kind = kind; d->Fs = Fs; d->fb = fb;
+    d->SamplesPerSymbol = (kind == JO_KIND_BURST_OQPSK) ? 2.0 * Fs / fb : (int)(Fs / fb); /* as the two setSettings form it */
+    d->N = 4096 * 4 * 2;
+    d->fftr = fft_plan(d->N);
+    d->tridentbuffer_sz = tri_sz;
+    d->tridentbuffer = (double *)malloc(sizeof(double) * (size_t)tri_sz);
+    memcpy(d->tridentbuffer, window, sizeof(double) * (size_t)tri_sz);
+    d->in = (double *)malloc(sizeof(double) * (size_t)d->N);
+    d->out_base = (cpx *)malloc(sizeof(cpx) * (size_t)d->N);
+    d->out_top = (cpx *)malloc(sizeof(cpx) * (size_t)d->N);
+    d->out_abs_diff = (double *)malloc(sizeof(double) * (size_t)(d->N / 2));
+    if (kind == JO_KIND_BURST_OQPSK) boqpsk_trident_signal(d, result); else bmsk_trident_signal(d, result);
+    for (int i = 0; i < d->N / 2; i++)
+    {
+        if (base_abs) base_abs[i] = hypot(d->out_base[i].re, d->out_base[i].im);
+        if (top_abs) top_abs[i] = hypot(d->out_top[i].re, d->out_top[i].im);
+    }
+    free(d->tridentbuffer); fft_free(d->fftr); free(d->out_base); free(d->out_top); free(d->out_abs_diff); free(d->in);
+    free(d);
+    return 0;
+}
+
 typedef struct jo_hilbert { fastfir_t f; } jo_hilbert;
 jo_hilbert *jo_hilbert_create(int N) { jo_hilbert *h = (jo_hilbert *)calloc(1, sizeof(jo_hilbert)); hilbert_set_size(&h->f, N); return h; }
 void jo_hilbert_destroy(jo_hilbert *h) { if (!h) return; fastfir_free(&h->f); free(h); }

@@ -140,6 +140,7 @@ def lib():
             f = getattr(L, name)
             f.restype = C.c_double
             f.argtypes = [C.c_void_p]
+        L.jo_trident.argtypes = [C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.POINTER(TridentResult), C.c_void_p, C.c_void_p]
         L.jo_hilbert_kernel.argtypes = [C.c_int, C.c_void_p]
         L.jo_hilbert_create.restype = C.c_void_p
         L.jo_hilbert_create.argtypes = [C.c_int]
@@ -444,6 +445,20 @@ class BurstDemod:
     def take_symbols(self):
         return _drain(self.L.jo_burst_take_symbols, self.h, 3, np.float64)
 
+    def take_trident_windows(self):
+        """With trace=True: the window of every trident check so far, one row per EV_TRIDENT event, in their order."""
+        f = self.L.jo_burst_take_trident_windows
+        f.restype, f.argtypes = C.c_long, [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_int)]
+        w = C.c_int(0)
+        f(self.h, None, 0, C.byref(w))
+        rows = []
+        while True:
+            buf = np.empty((64, w.value))
+            n = f(self.h, buf.ctypes.data, 64, C.byref(w))
+            rows.append(buf[:n].copy())
+            if n < 64:
+                return np.concatenate(rows)
+
     @property
     def pending(self):
         return self.L.jo_burst_pending_soft(self.h)
@@ -473,6 +488,8 @@ def run_burst(settings: Settings, pcm: np.ndarray, chunk: int = 4096, afc=False,
             set_at.pop(0)
         d.write(pcm[s:s + chunk])
     out = {"soft": d.take_soft(), "events": d.take_events(), "pending": d.pending, "mse": d.mse, "freq_est": d.freq_est}
+    if trace:
+        out["trident_windows"] = d.take_trident_windows()
     if capture_symbols:
         out["symbols"] = d.take_symbols()
     return out
@@ -487,6 +504,23 @@ def fastfir(x: np.ndarray, alpha=0.6, K=2048, nfft=4096, Fs=48000.0, fsym=5250.0
     out = np.empty_like(a)
     L.jo_fastfir_run(a.ctypes.data, len(a), alpha, K, nfft, Fs, fsym, out.ctypes.data)
     return out
+
+
+class TridentResult(C.Structure):
+    """struct jo_trident_result"""
+
+    _fields_ = [("ok", C.c_int), ("pad", C.c_int), ("freq", C.c_double), ("phase_deg", C.c_double), ("vol_gain", C.c_double), ("metric", C.c_double)]
+
+
+def trident(kind: int, Fs: float, fb: float, window: np.ndarray):
+    """The signal-only part of the burst demodulators' trident check on one window (tri_sz samples): (TridentResult, |base|, |top|) with the
+    magnitudes of the N/2 = 16384 bins the searches run over.  kind: 2 burst MSK, 3 burst OQPSK."""
+    w = np.ascontiguousarray(window, dtype=np.float64)
+    r = TridentResult()
+    base, top = np.empty(16384), np.empty(16384)
+    rc = lib().jo_trident(int(kind), float(Fs), float(fb), w.ctypes.data, len(w), C.byref(r), base.ctypes.data, top.ctypes.data)
+    assert rc == 0, "jo_trident: bad arguments"
+    return r, base, top
 
 
 def hilbert_kernel(N=2048) -> np.ndarray:

@@ -78,6 +78,28 @@ def test_coarse_hooks_refuse_a_null_context():
     assert b"jaero_debug_coarse_peek" in L.jaero_last_error()
 
 
+def test_burst_acquisition_hooks_refuse_a_null_context():
+    """jaero_debug_burst_geom / _hilbert / _read_hist / _poke_cv / _trident: JAERO_EINVAL before any HIP call (a bank that is not a burst bank, bad
+    channels, sizes, lists and grids: tests/test_gpu_burst_acq.py)."""
+    L = capi.lib()
+    assert C.sizeof(capi.BurstGeom) == 56 and C.sizeof(capi.TridentResult) == 40  # 12 ints + a long long; 2 ints + 4 doubles
+    buf = (C.c_double * 8)()
+    idx = (C.c_int * 2)()
+    n = C.c_int(7)
+    res = (capi.TridentResult * 2)()
+    assert L.jaero_debug_burst_geom(None, C.byref(capi.BurstGeom())) == capi.E_INVAL
+    assert b"jaero_debug_burst_geom" in L.jaero_last_error()
+    assert L.jaero_debug_burst_hilbert(None, buf, 0, 1, buf) == capi.E_INVAL
+    assert b"jaero_debug_burst_hilbert" in L.jaero_last_error()
+    assert L.jaero_debug_burst_hilbert(None, buf, 5, 1, buf) == capi.E_INVAL
+    assert L.jaero_debug_burst_read_hist(None, 0, 0, 1, buf) == capi.E_INVAL
+    assert b"jaero_debug_burst_read_hist" in L.jaero_last_error()
+    assert L.jaero_debug_burst_poke_cv(None, 0, 0, 1, buf) == capi.E_INVAL
+    assert b"jaero_debug_burst_poke_cv" in L.jaero_last_error()
+    assert L.jaero_debug_burst_trident(None, idx, idx, 1, 0, 0, res, C.byref(n)) == capi.E_INVAL
+    assert b"jaero_debug_burst_trident" in L.jaero_last_error() and n.value == 7
+
+
 @pytest.mark.parametrize("kind,power,fb,Fs,lbw,ok", [
     (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.0, True), (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.5, False),
     (capi.KIND_OQPSK, 14, 8400.0, 48000.0, 30000.0, False), (capi.KIND_MSK, 13, 1200.0, 48000.0, 24001.0, False),
