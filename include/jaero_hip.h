@@ -16,6 +16,7 @@
  *   setAFC / setSQL / setCPUReduce                                   jaero_set_flags
  *     JAERO/oqpskdemodulator.cpp:149-163, JAERO/mskdemodulator.cpp:105-118
  *   DCDstatSlot(bool)            JAERO/oqpskdemodulator.cpp:679-684   jaero_set_dcd
+ *   connect(AeroL::DataCarrierDetect -> DCDstatSlot)  JAERO/mainwindow.cpp:232-241   jaero_aerol_link_dcd
  *   CenterFreqChangedSlot(double) JAERO/oqpskdemodulator.cpp:291-310  jaero_center_freq_changed
  *   (two objects per stereo device: JAERO/audioburstoqpskdemodulator.cpp:8-10: channels are independent)  jaero_comm_* / jaero_fan_out_pcm / jaero_gather_softbits
  *   writeData(const char*,qint64) JAERO/oqpskdemodulator.cpp:334-627, jaero_write
@@ -243,6 +244,54 @@ int jaero_aerol_read_packets(jaero_aerol_ctx *ctx, int channel, int32_t *rows, i
 /* HIP-event time per kernel class since the last reset: which 0 = k_aerol_bits, 1 = Viterbi, 2 = k_aerol_post */
 int jaero_aerol_profile_enable(jaero_aerol_ctx *ctx, int on);
 int jaero_aerol_profile_read(jaero_aerol_ctx *ctx, int which, double *total_ms, int *launches, int reset);
+
+/* ---- the data-carrier-detect wire: AeroL::DataCarrierDetect(bool) -> demodulator DCDstatSlot (JAERO/mainwindow.cpp:232-241) ----
+ * jaero_aerol_link_dcd(ctx, bank) links an Aero-L bank to the demodulator bank that feeds it (bank = NULL: unlink).  The reference's direct
+ * connection delivers an emission in the middle of writeData; a bank runs a whole write before the Aero-L bank sees its soft bits, so the link
+ * is defined as the Qt adaptors of integration/qt behave, where soft bits are emitted after jaero_write returns:
+ *   After every jaero_aerol_write and every jaero_aerol_tick_dcd on a linked handle, for each channel c < nchannels: if channel c made at
+ *   least one DataCarrierDetect emission during that call, the bank's dcd of channel c becomes the value of the last one; if it made none,
+ *   the bank's dcd is left as it is.
+ * An emission is every `emit DataCarrierDetect(...)` of JAERO/aerol.cpp (:1120, :1607, :2008, :2025, :2383): what appends a kind-0 row to the
+ * event log, whether the log had room for it or not.  :2008 fires at every unique word, not only on a change.  Emissions from before the link
+ * was made (the constructor's `false` among them) are not replayed.  jaero_set_dcd keeps working on a linked bank and is overwritten by the
+ * next emission.  The update is enqueued on the stream of the Aero-L call, behind its last kernel: no host round trip, no synchronisation.
+ * Checks, in this order, before anything changes: null ctx (JAERO_EINVAL); bank on another device; channel counts differ; burst Aero-L bank
+ * with a continuous bank or the reverse; the Aero-L bank's fb differs from the bank's; either side already linked to something else (all
+ * JAERO_EINVAL); a burst bank (JAERO_ENOTSUP: the reference connects no slot of JAERO_KIND_BURST_OQPSK, mainwindow.cpp:234-237, and burst MSK
+ * banks are not linked yet: only continuous banks -- MSK, OQPSK, the 8400 bps C channel -- are); a poisoned bank (JAERO_EHIP).
+ * Streams: a linked jaero_aerol_write whose `stream` is not the stream of the bank's last jaero_write is JAERO_EINVAL and consumes nothing
+ * (the chain's order -- bank write, then Aero-L write, on one stream -- satisfies it); jaero_aerol_tick_dcd uses the handle's last stream, and is
+ * JAERO_EINVAL (nothing ticked) if the bank has written on another stream since.
+ * Lifetime: jaero_destroy of a linked bank unlinks it first, jaero_aerol_destroy unlinks.  Unlinking synchronises once and makes the device's
+ * dcd bits the bank's own.  While linked, a jaero_set_settings that would re-create the bank (another fb, Fs or FFT power, and every whole-bank
+ * change of an 8400 bps bank) is JAERO_EINVAL and the bank stays as it was: unlink, change, link a matching Aero-L bank.  In-place changes
+ * work as before.
+ * Deliberately not here: emission-exact timing inside a write; burst banks. */
+int jaero_aerol_link_dcd(jaero_aerol_ctx *ctx, jaero_ctx *bank);
+
+/* ---- one-call reads of every channel ----
+ * jaero_aerol_read_all hands over one output class of all channels.  With cnt_c the rows channel c holds and P_c = sum_{k <= c} cnt_k:
+ * channel c is taken iff P_c <= caprows, so the taken channels are a prefix [0, taken).  Each taken channel's rows are copied, oldest first,
+ * to rows + offsets[c] * rowbytes with offsets[c] = P_{c-1}; offsets[c] = offsets[taken] for c >= taken (offsets has nchannels + 1 entries);
+ * *nchannels_taken = taken; *rows_pending = P_{nchannels-1} before the call (size a buffer with a caprows = 0 call).  A taken channel is left
+ * as jaero_aerol_read_* with enough capacity leaves it (count 0, overflow bit of that class cleared); a channel not taken is not touched.
+ * If a taken channel had its overflow bit set, everything is filled in and the call returns JAERO_EOVERFLOW, overflowed[c] = 1 saying where.
+ * The rows are bit for bit the per-channel readers'.  Checks, in this order, before a device is touched: `what` is none of the four, caprows
+ * < 0, null offsets / nchannels_taken, null rows with caprows > 0, null ctx (JAERO_EINVAL); then a class the bank's mode does not have gets
+ * the per-channel reader's own error (SUS on a burst bank, PACKETS on any other: JAERO_ENOTSUP; VOICE on a bank that is not fb = 8400:
+ * JAERO_EINVAL).  Synchronises the handle's last stream (twice).
+ * jaero_aerol_profile2_read: as jaero_aerol_profile_read with which 0 .. 4; 3 = the kernels of jaero_aerol_read_all, 4 = the link kernel.
+ * Deliberately not here: rows handed over in device memory, the demodulator bank's own logs (status log, burst events, symbols). */
+#define JAERO_AEROL_SUS 0      /* P and C banks: rows of 16 int32, as jaero_aerol_read_sus        */
+#define JAERO_AEROL_PACKETS 1  /* burst banks:   rows of 16 int32, as jaero_aerol_read_packets    */
+#define JAERO_AEROL_EVENTS 2   /* every bank:    rows of 3 int64,  as jaero_aerol_read_events     */
+#define JAERO_AEROL_VOICE 3    /* C banks:       rows of 304 bytes, as jaero_aerol_read_voice     */
+int jaero_aerol_read_all(jaero_aerol_ctx *ctx, int what, void *rows, int caprows, int *offsets /* [nchannels + 1] */, int *nchannels_taken,
+                         long long *rows_pending /* optional */, unsigned char *overflowed /* optional [nchannels] */);
+int jaero_aerol_profile2_read(jaero_aerol_ctx *ctx, int which, double *total_ms, int *launches, int reset);
+/* test hook: bytes of device memory the link and jaero_aerol_read_all have allocated for this bank so far (0 for a bank that used neither) */
+long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *ctx);
 
 /* ---- batched ingest: the recAudio(QByteArray, quint32 sampleRate) -> dataReceived slot of every channel
  * (JAERO/zmq_audioreceiver.cpp:40-79 -> oqpskdemodulator.cpp:686-693, mskdemodulator.cpp:528-537) in front of one bank.

@@ -1,7 +1,20 @@
 // aerol_host.h -- C ABI of the Aero-L bit pipeline bank; included at the end of jaero_hip.hip.
 #pragma once
 
+#include <mutex>
 #include "aerolc.h"
+#include "k_aerol_sweep.h"
+
+// jaero_aerol_read_all's device scratch, allocated by the first sweep of a bank
+struct SweepBufs
+{
+    int nblk = 0;
+    size_t meta_bytes = 0, off_taken = 0, off_pending = 0, off_ovf = 0; // one block, copied to the host in one piece: offsets, taken counts, pending, flags
+    char *d_meta = nullptr;
+    long long *d_blk_sum = nullptr;
+    char *d_pack = nullptr; size_t pack_bytes = 0;
+    std::vector<char> h_meta;
+};
 
 struct jaero_aerol_ctx
 {
@@ -15,7 +28,12 @@ struct jaero_aerol_ctx
     int16_t *d_soft = nullptr; int *d_counts = nullptr; int stage_stride = 0;
     unsigned long long *d_vhist = nullptr; // k_viterbi_lanes history scratch (large banks only)
     hipStream_t last_stream = nullptr;
-    KernelTimer timer{3}; // the three kernel classes: 0 = the bit walk, 1 = k_viterbi + overlap update, 2 = the end of a block / frame
+    // the three kernel classes of a write: 0 = the bit walk, 1 = k_viterbi + overlap update, 2 = the end of a block / frame; 3 = the sweep's kernels
+    // (jaero_aerol_read_all), 4 = k_dcd_link (jaero_aerol_profile2_read)
+    KernelTimer timer{5};
+    SweepBufs sweep;
+    jaero_ctx *link = nullptr; // the demodulator bank whose dcd follows this bank's DataCarrierDetect emissions (jaero_aerol_link_dcd)
+    int *d_dcdmark = nullptr;  // [nchp], allocated by the first link
 };
 
 extern "C" int jaero_aerol_profile_enable(jaero_aerol_ctx *c, int on)
@@ -30,9 +48,89 @@ extern "C" int jaero_aerol_profile_read(jaero_aerol_ctx *c, int which, double *t
     return c->timer.read(c->device, which, total_ms, launches, reset);
 }
 
+extern "C" int jaero_aerol_profile2_read(jaero_aerol_ctx *c, int which, double *total_ms, int *launches, int reset)
+{
+    if (!c || which < 0 || which > 4) return fail(JAERO_EINVAL, "jaero_aerol_profile2_read: bad arguments");
+    return c->timer.read(c->device, which, total_ms, launches, reset);
+}
+
+// ------------------------------------------------------------------------------------------ the dcd link
+// The linked Aero-L banks of the process (jaero_aerol_ctx::link names the other side): how a demodulator bank finds the Aero-L bank it feeds.
+static std::mutex g_links_mu;
+static std::vector<jaero_aerol_ctx *> g_links;
+static jaero_aerol_ctx *link_of_bank(const jaero_ctx *b)
+{
+    std::lock_guard<std::mutex> lk(g_links_mu);
+    for (jaero_aerol_ctx *a : g_links) if (a->link == b) return a;
+    return nullptr;
+}
+static bool dcd_bank_linked(const jaero_ctx *b) { return link_of_bank(b) != nullptr; }
+// Ends a link: one synchronisation, then the bank's host mirror learns the JF_DCD bits the device holds (a later rate change carries the
+// mirror over, swap_in), and both sides forget each other.
+static void aerol_unlink(jaero_aerol_ctx *c)
+{
+    jaero_ctx *b = c->link;
+    if (!b) return;
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->last_stream);
+    hipStreamSynchronize(b->last_stream);
+    std::vector<int> f(b->o_nch);
+    if (!b->poisoned && hipMemcpy(f.data(), b->o_flags, sizeof(int) * f.size(), hipMemcpyDeviceToHost) == hipSuccess)
+        for (int ch = 0; ch < b->o_nch; ch++) b->m.flags[ch] = (b->m.flags[ch] & ~JF_DCD) | (f[ch] & JF_DCD);
+    c->p.dcdmark = nullptr; c->cp.dcdmark = nullptr;
+    std::lock_guard<std::mutex> lk(g_links_mu);
+    for (size_t k = 0; k < g_links.size(); k++) if (g_links[k] == c) { g_links.erase(g_links.begin() + k); break; }
+    c->link = nullptr;
+}
+static void dcd_unlink_bank(jaero_ctx *b)
+{
+    if (jaero_aerol_ctx *a = link_of_bank(b)) aerol_unlink(a);
+}
+
+extern "C" int jaero_aerol_link_dcd(jaero_aerol_ctx *c, jaero_ctx *b)
+{
+    const char *who = "jaero_aerol_link_dcd";
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (!b) { aerol_unlink(c); return 0; }
+    if (b->device != c->device) return fail(JAERO_EINVAL, "%s: the bank is on device %d, the Aero-L bank on device %d", who, b->device, c->device);
+    if (b->o_nch != c->g.nch) return fail(JAERO_EINVAL, "%s: the bank has %d channels, the Aero-L bank %d", who, b->o_nch, c->g.nch);
+    if (b->burst != (c->g.burst != 0)) return fail(JAERO_EINVAL, "%s: a burst Aero-L bank goes with a burst demodulator bank, a continuous one with a continuous one", who);
+    const double bank_fb = b->burst ? b->bg.fb : b->g.fb;
+    if (bank_fb != (double)c->g.fb) return fail(JAERO_EINVAL, "%s: the bank runs at %g bps, the Aero-L bank at %d", who, bank_fb, c->g.fb);
+    if (c->link == b) return 0; // the same pair again
+    if (c->link || dcd_bank_linked(b)) return fail(JAERO_EINVAL, "%s: already linked (unlink first: bank = NULL)", who);
+    if (b->burst && b->bg.kind == JAERO_KIND_BURST_OQPSK)
+        return fail(JAERO_ENOTSUP, "%s: the reference connects DataCarrierDetect to no slot of the burst OQPSK demodulator (mainwindow.cpp:234-237)", who);
+    if (b->burst) return fail(JAERO_ENOTSUP, "%s: burst MSK banks are not linked yet (only continuous banks are)", who);
+    if (b->poisoned) return fail(JAERO_EHIP, "%s: an earlier jaero_write of the bank failed part-way; destroy it and create a new one", who);
+    HIPCHK(hipSetDevice(c->device));
+    int rc = 0;
+    if (!c->d_dcdmark && (rc = dalloc(c->mem, &c->d_dcdmark, (size_t)c->g.nchp, false))) return rc;
+    // emissions from before the link are not replayed: the marks start empty, behind whatever the Aero-L bank still has in flight on its stream,
+    // and are empty before this call returns (a write on any stream, blocking or not, finds them so)
+    HIPCHK(hipMemsetAsync(c->d_dcdmark, 0, sizeof(int) * (size_t)c->g.nchp, c->last_stream));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    if (c->cchan) c->cp.dcdmark = c->d_dcdmark; else c->p.dcdmark = c->d_dcdmark;
+    c->link = b;
+    std::lock_guard<std::mutex> lk(g_links_mu);
+    g_links.push_back(c);
+    return 0;
+}
+// behind the last kernel of a jaero_aerol_write / jaero_aerol_tick_dcd of a linked handle, on its stream
+static int aerol_link_apply(jaero_aerol_ctx *c, hipStream_t st)
+{
+    if (!c->link) return 0;
+    const int pi = c->timer.begin(4, st);
+    hipLaunchKernelGGL(k_dcd_link, dim3((c->g.nch + 255) / 256), dim3(256), 0, st, c->d_dcdmark, c->link->o_flags, c->g.nch, (int)JF_DCD);
+    c->timer.end(pi, st);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" void jaero_aerol_destroy(jaero_aerol_ctx *c)
 {
     if (!c) return;
+    aerol_unlink(c);
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     delete c; // its device memory and timing events with it
@@ -239,8 +337,10 @@ static int aerolc_write(jaero_aerol_ctx *c, const int16_t *dsoft, const int *dco
 extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const int *counts, int stride, int max_count, int is_device_ptr, void *stream)
 {
     if (!c || !soft || !counts || stride <= 0 || max_count < 0 || max_count > stride) return fail(JAERO_EINVAL, "jaero_aerol_write: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
+    if (c->link && st != c->link->last_stream)
+        return fail(JAERO_EINVAL, "jaero_aerol_write: a linked Aero-L bank writes on the stream of the bank's last jaero_write (nothing was consumed)");
+    HIPCHK(hipSetDevice(c->device));
     c->last_stream = st;
     const AGeom &g = c->g;
     const int16_t *dsoft = soft;
@@ -255,7 +355,11 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
         dsoft = c->d_soft; dcounts = c->d_counts;
     }
     if (max_count == 0) return 0;
-    if (c->cchan) return aerolc_write(c, dsoft, dcounts, stride, max_count, st);
+    if (c->cchan)
+    {
+        const int rc = aerolc_write(c, dsoft, dcounts, stride, max_count, st);
+        return rc ? rc : aerol_link_apply(c, st);
+    }
     if (g.burst)
     {
         // R/T packet search: a round per trial length a channel can reach in this write (every 192 soft bits, plus 128 and 320)
@@ -281,7 +385,7 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
         }
         hipLaunchKernelGGL(k_aerol_end_write, grid, block, 0, st, g, c->p, dcounts);
         HIPCHK(hipGetLastError());
-        return 0;
+        return 0; // (a burst bank is never linked: jaero_aerol_link_dcd)
     }
     // every round finishes at most one interleaver block per channel (the reference completes a block -- Viterbi, descrambling,
     // CRC and its data-carrier-detect update -- before it looks at the next soft bit)
@@ -313,7 +417,7 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
     }
     hipLaunchKernelGGL(k_aerol_end_write, grid, block, 0, st, g, c->p, dcounts);
     HIPCHK(hipGetLastError());
-    return 0;
+    return aerol_link_apply(c, st);
 }
 
 // the readers of an Aero-L bank's per-channel outputs: drain channel ch of the rows whose count is column `cnt_field` of the bank's counters
@@ -351,6 +455,132 @@ extern "C" int jaero_aerol_read_voice(jaero_aerol_ctx *c, int ch, uint8_t *rows,
     if (!c || !c->cchan) return fail(JAERO_EINVAL, "jaero_aerol_read_voice: not a C-channel (fb = 8400) bank");
     return aerol_read(c, "jaero_aerol_read_voice", CI_V_CNT, c->cp.voice, c->cg.v_cap, 304, ch, rows, caprows, nrows, 4);
 }
+// ------------------------------------------------------------------------------------------ jaero_aerol_read_all
+// One log of every channel in one call (k_aerol_sweep.h).  Two synchronisations: after the offsets, after the rows.
+static int sweep_prepare(jaero_aerol_ctx *c)
+{
+    SweepBufs &w = c->sweep;
+    if (w.d_meta) return 0;
+    int rc;
+    const int nch = c->g.nch;
+    w.nblk = (nch + SWEEP_W - 1) / SWEEP_W;
+    w.off_taken = sizeof(int) * ((size_t)nch + 1);
+    w.off_pending = (w.off_taken + sizeof(int) * (size_t)w.nblk + 7) / 8 * 8;
+    w.off_ovf = w.off_pending + sizeof(long long);
+    w.meta_bytes = w.off_ovf + (size_t)nch;
+    DA(c->mem, w.d_blk_sum, w.nblk);
+    DA(c->mem, w.d_meta, w.meta_bytes);
+    w.h_meta.resize(w.meta_bytes);
+    return 0;
+}
+static int sweep_log(jaero_aerol_ctx *c, const RowBuf &b, int *ovword, int ovbit, void *rows, int caprows, int *offsets, int *nchannels_taken,
+                     long long *rows_pending, unsigned char *overflowed)
+{
+    int rc;
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = sweep_prepare(c))) return rc;
+    SweepBufs &w = c->sweep;
+    const int nch = c->g.nch;
+    hipStream_t st = c->last_stream;
+    int *d_off = (int *)w.d_meta, *d_taken = (int *)(w.d_meta + w.off_taken);
+    int pi = c->timer.begin(3, st);
+    hipLaunchKernelGGL(k_sweep_sums, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const int *)b.cnt, b.cap, nch, w.d_blk_sum);
+    hipLaunchKernelGGL(k_sweep_offsets, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const int *)b.cnt, b.cap, nch, (const long long *)w.d_blk_sum, (long long)caprows,
+                       (const int *)ovword, ovbit, d_off, d_taken, (long long *)(w.d_meta + w.off_pending), (unsigned char *)(w.d_meta + w.off_ovf));
+    c->timer.end(pi, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(w.h_meta.data(), w.d_meta, w.meta_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int *h_off = (const int *)w.h_meta.data(), *h_taken = (const int *)(w.h_meta.data() + w.off_taken);
+    const unsigned char *h_ovf = (const unsigned char *)(w.h_meta.data() + w.off_ovf);
+    int taken = 0;
+    for (int k = 0; k < w.nblk; k++) taken += h_taken[k];
+    const int total = h_off[taken]; // rows taken: P of the last taken channel (= offsets[nch] when every channel is taken)
+    memcpy(offsets, h_off, sizeof(int) * (size_t)taken);
+    for (int ch = taken; ch <= nch; ch++) offsets[ch] = total;
+    *nchannels_taken = taken;
+    if (rows_pending) memcpy(rows_pending, w.h_meta.data() + w.off_pending, sizeof(long long));
+    bool any_ov = false;
+    for (int ch = 0; ch < nch; ch++) any_ov |= h_ovf[ch] != 0;
+    if (overflowed) memcpy(overflowed, h_ovf, (size_t)nch);
+    if (total > 0 || any_ov)
+    {
+        const size_t bytes = (size_t)total * b.rowbytes;
+        if (bytes > w.pack_bytes)
+        {
+            // grown by half at least; the old buffer goes first (nothing is in flight: the stream was synchronised above), the new one is not zeroed
+            size_t want = w.pack_bytes + w.pack_bytes / 2;
+            if (want < bytes) want = bytes;
+            if (w.d_pack)
+            {
+                for (size_t k = 0; k < c->mem.ptrs.size(); k++) if (c->mem.ptrs[k] == (void *)w.d_pack) { c->mem.ptrs.erase(c->mem.ptrs.begin() + k); break; }
+                hipFree(w.d_pack);
+                w.d_pack = nullptr; w.pack_bytes = 0;
+            }
+            if ((rc = dalloc(c->mem, &w.d_pack, want, false))) return rc;
+            w.pack_bytes = want;
+        }
+        pi = c->timer.begin(3, st);
+        if (b.rowbytes % 16 == 0)
+            hipLaunchKernelGGL(k_sweep_gather<16>, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const char *)b.base, b.cnt, b.cap, (int)b.rowbytes, nch, (const int *)d_off,
+                               (const int *)d_taken, w.d_pack, ovword, ovbit);
+        else
+            hipLaunchKernelGGL(k_sweep_gather<8>, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const char *)b.base, b.cnt, b.cap, (int)b.rowbytes, nch, (const int *)d_off,
+                               (const int *)d_taken, w.d_pack, ovword, ovbit);
+        c->timer.end(pi, st);
+        HIPCHK(hipGetLastError());
+        if (bytes) HIPCHK(hipMemcpyAsync(rows, w.d_pack, bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (any_ov) return fail(JAERO_EOVERFLOW, "jaero_aerol_read_all: channels overflowed this output buffer (flag %d) since it was last read; rows were dropped", ovbit);
+    return 0;
+}
+// test hook: bytes of device memory the link and the sweep have allocated for this bank so far (0 for a bank that used neither)
+extern "C" long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *c)
+{
+    if (!c) return -1;
+    long long n = c->d_dcdmark ? (long long)sizeof(int) * c->g.nchp : 0;
+    if (c->sweep.d_meta) n += (long long)c->sweep.meta_bytes + (long long)sizeof(long long) * c->sweep.nblk;
+    return n + (long long)c->sweep.pack_bytes;
+}
+extern "C" int jaero_aerol_read_all(jaero_aerol_ctx *c, int what, void *rows, int caprows, int *offsets, int *nchannels_taken, long long *rows_pending,
+                                    unsigned char *overflowed)
+{
+    const char *who = "jaero_aerol_read_all";
+    if (what < JAERO_AEROL_SUS || what > JAERO_AEROL_VOICE) return fail(JAERO_EINVAL, "%s: what = %d is none of JAERO_AEROL_SUS / PACKETS / EVENTS / VOICE", who, what);
+    if (caprows < 0) return fail(JAERO_EINVAL, "%s: caprows < 0", who);
+    if (!offsets || !nchannels_taken) return fail(JAERO_EINVAL, "%s: null offsets / nchannels_taken", who);
+    if (!rows && caprows > 0) return fail(JAERO_EINVAL, "%s: null rows with caprows > 0", who);
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    const size_t nchp = c->g.nchp;
+    int *I = c->cchan ? c->cp.I : c->p.I;
+    int *ov = I + (size_t)(c->cchan ? CI_OVERFLOW : AI_OVERFLOW) * nchp;
+    RowBuf b{};
+    int ovbit = 0;
+    switch (what)
+    {
+    case JAERO_AEROL_SUS:
+        if (!c->cchan && c->g.burst) return fail(JAERO_ENOTSUP, "%s: burst-mode bank (use JAERO_AEROL_PACKETS)", who);
+        b = c->cchan ? RowBuf{c->cp.sus, I + (size_t)CI_SU_CNT * nchp, c->cg.su_cap, 16 * sizeof(int32_t)} : RowBuf{c->p.sus, I + (size_t)AI_SU_CNT * nchp, c->g.su_cap, 16 * sizeof(int32_t)};
+        ovbit = 1;
+        break;
+    case JAERO_AEROL_PACKETS:
+        if (c->cchan || !c->g.burst) return fail(JAERO_ENOTSUP, "%s: not a burst-mode bank (use JAERO_AEROL_SUS)", who);
+        b = RowBuf{c->p.sus, I + (size_t)AI_SU_CNT * nchp, c->g.su_cap, 16 * sizeof(int32_t)};
+        ovbit = 1;
+        break;
+    case JAERO_AEROL_EVENTS:
+        b = c->cchan ? RowBuf{c->cp.events, I + (size_t)CI_EV_CNT * nchp, c->cg.ev_cap, 3 * sizeof(long long)} : RowBuf{c->p.events, I + (size_t)AI_EV_CNT * nchp, c->g.ev_cap, 3 * sizeof(long long)};
+        ovbit = 2;
+        break;
+    default:
+        if (!c->cchan) return fail(JAERO_EINVAL, "%s: JAERO_AEROL_VOICE: not a C-channel (fb = 8400) bank", who);
+        b = RowBuf{c->cp.voice, I + (size_t)CI_V_CNT * nchp, c->cg.v_cap, 304};
+        ovbit = 4;
+        break;
+    }
+    return sweep_log(c, b, ov, ovbit, rows, caprows, offsets, nchannels_taken, rows_pending, overflowed);
+}
 // = AeroL::updateDCD (aerol.cpp:1109-1122), which the reference drives from a 1 s wall-clock QTimer: the caller ticks it once per
 // second of signal time.  dcd_out (optional, [nchannels]) receives the datacd flags afterwards.
 __global__ void k_aerol_tick_dcd(const AGeom g, const APtrs p, int *dcd_out)
@@ -372,10 +602,13 @@ __global__ void k_aerol_tick_dcd(const AGeom g, const APtrs p, int *dcd_out)
 extern "C" int jaero_aerol_tick_dcd(jaero_aerol_ctx *c, int *dcd_out_host)
 {
     if (!c) return fail(JAERO_EINVAL, "null ctx");
+    if (c->link && c->last_stream != c->link->last_stream)
+        return fail(JAERO_EINVAL, "jaero_aerol_tick_dcd: the bank has written on another stream since this linked Aero-L bank's last write (nothing was ticked)");
     HIPCHK(hipSetDevice(c->device));
     int *dout = dcd_out_host ? c->d_counts : nullptr;
     if (c->cchan) hipLaunchKernelGGL(k_aerolc_tick_dcd, dim3(c->g.nchp / 64), dim3(64), 0, c->last_stream, c->cg, c->cp, dout);
     else hipLaunchKernelGGL(k_aerol_tick_dcd, dim3(c->g.nchp / 64), dim3(64), 0, c->last_stream, c->g, c->p, dout);
+    { const int rc = aerol_link_apply(c, c->last_stream); if (rc) return rc; }
     if (dcd_out_host)
     {
         HIPCHK(hipMemcpyAsync(dcd_out_host, c->d_counts, sizeof(int) * c->g.nch, hipMemcpyDeviceToHost, c->last_stream));

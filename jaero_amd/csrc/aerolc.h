@@ -52,6 +52,7 @@ struct CPtrs
     int32_t *sus;                // [nchp][su_cap][16]  rows [frame, k, 12 bytes, crc_ok, 0]
     uint8_t *voice;              // [nchp][v_cap][304]  rows: uint32 frame, 300 voice bytes
     long long *events;           // [nchp][ev_cap][3]   rows [soft-bit index, kind (0 DCD, 2 sync), value]
+    int *dcdmark = nullptr;      // [nchp] linked banks only (jaero_aerol_link_dcd): 2 | value of the last DataCarrierDetect emission, 0 = none
 };
 #define CLD(f) p.I[(size_t)(f) * g.nchp + ch]
 
@@ -78,6 +79,7 @@ __device__ __forceinline__ void cc_event(const CGeom &g, const CPtrs &p, int ch,
         ev_cnt++;
     }
     else overflow |= 2;
+    if (kind == 0 && p.dcdmark) p.dcdmark[ch] = 2 | (value ? 1 : 0); // every emission, logged or not (k_dcd_link)
 }
 
 // received index cntr (post-increment, 0 .. CC_FRAME - 1) -> position in the deinterleaved + depunctured frame buffer, or -1 (the last

@@ -335,6 +335,7 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
 // the outputs not read yet are copied.  Control plane: allocates and synchronises.
 static int burst_rebank(jaero_ctx *c, const jaero_settings *s)
 {
+    LINKCHK(c);
     if (c->poisoned) return fail(JAERO_EHIP, "jaero_set_settings: a launch inside an earlier jaero_write failed; this bank's state cannot be carried over");
     const BGeom og = c->bg;
     HIPCHK(hipSetDevice(c->device));

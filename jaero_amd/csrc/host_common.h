@@ -237,3 +237,11 @@ static int check_tuning_range(double lockingbw, double freq_center, double Fs)
     if (lockingbw > Fs / 2) return fail(JAERO_EINVAL, "lockingbw %g Hz exceeds Fs / 2 = %g Hz", lockingbw, Fs / 2);
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------ the dcd link
+// What the demodulator banks need to know of jaero_aerol_link_dcd (aerol_host.h keeps the links): a bank that is destroyed ends its link first,
+// and a jaero_set_settings that would re-create a linked bank is refused.
+struct jaero_ctx;
+static void dcd_unlink_bank(jaero_ctx *b);
+static bool dcd_bank_linked(const jaero_ctx *b);
+#define LINKCHK(c) do { if (dcd_bank_linked(c)) return fail(JAERO_EINVAL, "jaero_set_settings: this change re-creates the bank, which is linked to an Aero-L bank (jaero_aerol_link_dcd): unlink, change, link a matching Aero-L bank"); } while (0)

@@ -542,6 +542,7 @@ extern "C" int jaero_num_channels(const jaero_ctx *ctx) { return ctx ? ctx->o_nc
 extern "C" void jaero_destroy(jaero_ctx *c)
 {
     if (!c) return;
+    dcd_unlink_bank(c);
     hipSetDevice(c->device);
     // this bank's work only (its last stream and the default stream its control-plane copies use): other banks keep running until hipFree's
     // own implicit synchronisation, which cannot be avoided
@@ -1015,6 +1016,7 @@ __global__ void k_carry_dly(const double2 *__restrict__ od, int Lo, const int *_
 static int rebank_with_carry_over(jaero_ctx *c, const jaero_settings *s)
 {
     const JGeom og = c->g;
+    LINKCHK(c);
     if (c->poisoned) return fail(JAERO_EHIP, "jaero_set_settings: a launch inside an earlier jaero_write failed; this bank's state cannot be carried over");
     if (og.kind == JAERO_KIND_OQPSK && s->Fs != og.Fs) return fail(JAERO_ENOTSUP, "jaero_set_settings: an OQPSK bank keeps its sample rate");
     HIPCHK(hipSetDevice(c->device));

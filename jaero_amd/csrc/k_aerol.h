@@ -43,6 +43,7 @@ struct APtrs
     const uint8_t *scr;  // [5000] scrambler sequence
     const unsigned *scrw; // the same, 32 per word (bit k of the sequence = bit k&31 of word k>>5), one spare word
     unsigned *dl2w;      // [nchp][dl2_words] the delay line as a bit ring (large banks: k_aerol_post_packed)
+    int *dcdmark = nullptr; // [nchp] linked banks only (jaero_aerol_link_dcd): 2 | value of the last DataCarrierDetect emission, 0 = none
 };
 #define ALD(f) (p.I[(size_t)(f) * g.nchp + ch])
 
@@ -55,6 +56,7 @@ __device__ __forceinline__ void aerol_event(const AGeom &g, const APtrs &p, int 
         ev_cnt++;
     }
     else overflow |= 2;
+    if (kind == 0 && p.dcdmark) p.dcdmark[ch] = 2 | (value ? 1 : 0); // every emission, logged or not (k_dcd_link)
 }
 
 // One soft bit of AeroL::Decode for one channel, in two parts: everything up to and including the block store (part A; returns true

@@ -528,6 +528,69 @@ class AeroLBank:
         capi.check(self.L.jaero_aerol_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
+    def profile2_read(self, which: int, reset: bool = False):
+        """As profile_read, with which 3 = the kernels of read_all and 4 = the dcd link kernel as well."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.L.jaero_aerol_profile2_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
+
+    # ---- the data-carrier-detect wire to the demodulator bank (jaero_aerol_link_dcd) ----
+    def link_dcd(self, bank: "DemodulatorBank"):
+        """From now on every DataCarrierDetect emission of channel c sets `bank`'s dcd of channel c, on the device, behind each write / tick_dcd.
+        Continuous banks (MSK, OQPSK, the 8400 bps C channel); burst banks are refused."""
+        capi.check(self.L.jaero_aerol_link_dcd(self.h, bank.h))
+
+    def unlink_dcd(self):
+        capi.check(self.L.jaero_aerol_link_dcd(self.h, None))
+
+    # ---- one call for every channel (jaero_aerol_read_all) ----
+    _ROWS = {capi.AEROL_SUS: (np.int32, 16), capi.AEROL_PACKETS: (np.int32, 16), capi.AEROL_EVENTS: (np.int64, 3), capi.AEROL_VOICE: (np.uint8, 304)}
+
+    def read_all_raw(self, what: int, caprows: int):
+        """One jaero_aerol_read_all call: (rc, offsets int32[nch + 1], rows[offsets[taken]], taken, rows_pending, overflowed bool[nch])."""
+        dt, width = self._ROWS[what]
+        rows = np.empty((max(caprows, 1), width), dtype=dt)
+        offsets = np.zeros(self.nch + 1, dtype=np.int32)
+        ovf = np.zeros(self.nch, dtype=np.uint8)
+        taken, pending = C.c_int(0), C.c_longlong(0)
+        rc = self.L.jaero_aerol_read_all(self.h, what, rows.ctypes.data, caprows, offsets.ctypes.data, C.byref(taken), C.byref(pending), ovf.ctypes.data)
+        if rc not in (capi.E_OK, capi.E_OVERFLOW):
+            capi.check(rc)
+        return rc, offsets, rows[: int(offsets[taken.value])].copy(), taken.value, pending.value, ovf.astype(bool)
+
+    def read_all(self, what: int):
+        """Every channel's rows of one class: (offsets int32[nch + 1], rows, overflowed bool[nch]); channel c's rows are
+        rows[offsets[c]:offsets[c + 1]].  Sizes its buffer with a caprows = 0 call and reads until every channel is taken; does not raise when
+        channels had overflowed (their rows were dropped by the bank): `overflowed` says which."""
+        _, offsets, rows, taken, pending, ovf = self.read_all_raw(what, 0)
+        counts, parts, done = [], [], taken  # channels [0, done) are read; the sizing call takes the leading channels without rows
+        counts.append(np.zeros(taken, dtype=np.int64))
+        while done < self.nch:
+            _, offsets, rows, taken, pending, o = self.read_all_raw(what, int(min(pending, (1 << 31) - 1)))
+            # a call takes a prefix of ALL channels: those read before hold no rows any more, so taken > done whenever rows fit an int
+            assert taken > done, (taken, done, pending)
+            counts.append(np.diff(offsets[done: taken + 1]).astype(np.int64))
+            parts.append(rows)
+            ovf |= o
+            done = taken
+        cnt = np.concatenate(counts) if counts else np.zeros(0, np.int64)
+        out = np.zeros(self.nch + 1, dtype=np.int32)
+        np.cumsum(cnt, out=out[1:])
+        dt, width = self._ROWS[what]
+        return out, (np.concatenate(parts) if parts else np.empty((0, width), dtype=dt)), ovf
+
+    def read_sus_all(self):
+        return self.read_all(capi.AEROL_SUS)
+
+    def read_events_all(self):
+        return self.read_all(capi.AEROL_EVENTS)
+
+    def read_packets_all(self):
+        return self.read_all(capi.AEROL_PACKETS)
+
+    def read_voice_all(self):
+        return self.read_all(capi.AEROL_VOICE)
+
     def tick_dcd(self) -> np.ndarray:
         out = np.zeros(self.nch, dtype=np.int32)
         capi.check(self.L.jaero_aerol_tick_dcd(self.h, out.ctypes.data))
