@@ -23,7 +23,7 @@
  *                                 JAERO/mskdemodulator.cpp:313-488
  *   signal processDemodulatedSoftBits(QVector<short>)                jaero_read_softbits / jaero_softbits_view
  *     JAERO/oqpskdemodulator.h:66, emitted at oqpskdemodulator.cpp:583-591, mskdemodulator.cpp:472-477
- *   signals Plottables / MSESignal / EbNoMeasurmentSignal / SignalStatus   jaero_read_status (+ status log)
+ *   signals Plottables / MSESignal / EbNoMeasurmentSignal / SignalStatus   jaero_read_status / jaero_read_status_all (+ status log)
  *     emitted together at JAERO/oqpskdemodulator.cpp:670-675, JAERO/mskdemodulator.cpp:510-517
  *   FreqOffsetEstimateSlot + CoarseFreqEstimate::ProcessBasebandData  internal (runs inside jaero_write at the
  *     JAERO/oqpskdemodulator.cpp:414-428,629-677; coarsefreqestimate.cpp:90-137   same sample the reference does)
@@ -35,6 +35,7 @@
  *     JAERO/burstoqpskdemodulator.cpp:300-737  JAERO/burstmskdemodulator.cpp:371-754
  *   their processDemodulatedSoftBits (with the -1 start-of-burst marker)  jaero_read_softbits (marker kept as -1)
  *   their SignalStatus / EbNoMeasurmentSignal / Plottables emissions   jaero_read_events
+ *   every object's emissions of one class collected at once (a bank is many objects: no counterpart)   jaero_read_all
  *   channel_stereo / channel_select_other (two objects fed the L and R     two channels of one bank fed with
  *     samples of one interleaved stream, audioburstoqpskdemodulator.cpp:8-10)  JAERO_PCM_FRAME_MAJOR input
  *   stop() / destructor                                               jaero_destroy
@@ -282,7 +283,8 @@ int jaero_aerol_link_dcd(jaero_aerol_ctx *ctx, jaero_ctx *bank);
  * the per-channel reader's own error (SUS on a burst bank, PACKETS on any other: JAERO_ENOTSUP; VOICE on a bank that is not fb = 8400:
  * JAERO_EINVAL).  Synchronises the handle's last stream (twice).
  * jaero_aerol_profile2_read: as jaero_aerol_profile_read with which 0 .. 4; 3 = the kernels of jaero_aerol_read_all, 4 = the link kernel.
- * Deliberately not here: rows handed over in device memory, the demodulator bank's own logs (status log, burst events, symbols). */
+ * jaero_read_all (below) is the same call for the demodulator bank's soft bits and logs: this paragraph defines both.
+ * Deliberately not here: rows handed over in device memory. */
 #define JAERO_AEROL_SUS 0      /* P and C banks: rows of 16 int32, as jaero_aerol_read_sus        */
 #define JAERO_AEROL_PACKETS 1  /* burst banks:   rows of 16 int32, as jaero_aerol_read_packets    */
 #define JAERO_AEROL_EVENTS 2   /* every bank:    rows of 3 int64,  as jaero_aerol_read_events     */
@@ -292,6 +294,35 @@ int jaero_aerol_read_all(jaero_aerol_ctx *ctx, int what, void *rows, int caprows
 int jaero_aerol_profile2_read(jaero_aerol_ctx *ctx, int which, double *total_ms, int *launches, int reset);
 /* test hook: bytes of device memory the link and jaero_aerol_read_all have allocated for this bank so far (0 for a bank that used neither) */
 long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *ctx);
+
+/* ---- one-call reads of every channel of a demodulator bank ----
+ * jaero_read_all is jaero_aerol_read_all (above: the prefix rule P_c <= caprows, offsets, *nchannels_taken, *rows_pending, the caprows = 0 sizing
+ * call, overflowed / JAERO_EOVERFLOW, taken channels left as the per-channel reader leaves them, others untouched) for the demodulator bank's four
+ * output classes, with cnt_c = the rows jaero_read_* of that class would hand over for channel c with unlimited capacity.  For the soft bits of a
+ * burst bank that is what has been emitted: the pending tail (the current, incomplete group) stays with the channel, moved to the front of its
+ * buffer, exactly as jaero_read_softbits leaves it; the -1 start-of-burst markers are handed over in place.  Overflow bits: 1 soft bits, 2 symbols,
+ * 4 status log / events.  Rows are bit for bit the per-channel readers'.  Checks, in this order, before a device is touched: `what` is none of the
+ * four, caprows < 0, null offsets / nchannels_taken, null rows with caprows > 0, null ctx (JAERO_EINVAL); a poisoned bank (JAERO_EHIP); then a
+ * class the bank does not have gets the per-channel reader's own error (STATUS_LOG on a burst bank, EVENTS on a continuous one: JAERO_ENOTSUP; a
+ * log or symbol buffer not enabled at create: JAERO_EINVAL).  Synchronises the bank's last stream (twice).  Works on a bank linked by
+ * jaero_aerol_link_dcd and touches no flags.  jaero_read_softbits_all keeps its dense form (and JAERO_ENOTSUP on burst banks).
+ * jaero_read_status_all: st[c] is bit for bit what the per-channel status call returns for channel c, for every kind: one kernel launch over all
+ * channels, one copy, one synchronisation.  Null ctx / st: JAERO_EINVAL; a poisoned bank: JAERO_EHIP.
+ * Their device scratch is allocated by the first call (a bank that never calls them allocates and launches what it always did) and belongs to the
+ * bank object: after a jaero_set_settings that re-creates the bank behind the handle the next call allocates afresh.
+ * jaero_profile2_read: as jaero_profile_read with which 0 .. 5; 5 = the kernels of these two calls (totals survive a rate change as the others). */
+#define JAERO_BANK_SOFTBITS 0   /* every kind: rows of one int16, as jaero_read_softbits (burst: only what has been emitted; the -1 markers stay) */
+#define JAERO_BANK_STATUS_LOG 1 /* continuous kinds, JAERO_FLAG_STATUS_LOG: rows of 6 doubles, as jaero_read_status_log */
+#define JAERO_BANK_EVENTS 2     /* burst kinds: rows of 3 doubles, as jaero_read_events */
+#define JAERO_BANK_SYMBOLS 3    /* JAERO_FLAG_CAPTURE_SYMBOLS: rows of 3 doubles, as jaero_read_symbols */
+int jaero_read_all(jaero_ctx *ctx, int what, void *rows, int caprows, int *offsets /* [nchannels + 1] */, int *nchannels_taken,
+                   long long *rows_pending /* optional */, unsigned char *overflowed /* optional [nchannels] */);
+int jaero_read_status_all(jaero_ctx *ctx, jaero_status *st /* [nchannels] */);
+int jaero_profile2_read(jaero_ctx *ctx, int which, double *total_ms, int *launches, int reset);
+/* test hooks: device bytes the two calls have allocated for the bank so far (0 for a bank that never used them; -1 for a null ctx); per channel, the
+ * soft bits held and (burst banks) how many of them are not yet emitted (synchronises, changes nothing) */
+long long jaero_debug_read_all_bytes(const jaero_ctx *ctx);
+int jaero_debug_softbit_counts(jaero_ctx *ctx, int *cnt, int *pending);
 
 /* ---- batched ingest: the recAudio(QByteArray, quint32 sampleRate) -> dataReceived slot of every channel
  * (JAERO/zmq_audioreceiver.cpp:40-79 -> oqpskdemodulator.cpp:686-693, mskdemodulator.cpp:528-537) in front of one bank.

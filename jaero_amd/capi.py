@@ -19,6 +19,7 @@ PCM_CHANNEL_MAJOR, PCM_FRAME_MAJOR = 0, 1
 W_RATE = 1  # jaero_ingest_push: sample rate differs from the bank (warning, data queued)
 IQ_CS16, IQ_CU8, IQ_CS8, IQ_CF32 = 0, 1, 2, 3
 AEROL_SUS, AEROL_PACKETS, AEROL_EVENTS, AEROL_VOICE = 0, 1, 2, 3  # jaero_aerol_read_all: what
+BANK_SOFTBITS, BANK_STATUS_LOG, BANK_EVENTS, BANK_SYMBOLS = 0, 1, 2, 3  # jaero_read_all: what
 E_OK, E_INVAL, E_NODEV, E_NOMEM, E_HIP, E_OVERFLOW, E_NOTSUP = 0, -1, -2, -3, -4, -5, -6
 
 EXPORTS = [
@@ -35,6 +36,7 @@ EXPORTS = [
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
     "jaero_aerol_link_dcd", "jaero_aerol_read_all", "jaero_aerol_profile2_read", "jaero_aerol_debug_extra_bytes",
+    "jaero_read_all", "jaero_read_status_all", "jaero_profile2_read", "jaero_debug_read_all_bytes", "jaero_debug_softbit_counts",
     "jaero_ingest_create", "jaero_ingest_destroy", "jaero_ingest_push", "jaero_ingest_queued", "jaero_ingest_pump",
     "jaero_ingest_stats",
     "jaero_chan_create", "jaero_chan_destroy", "jaero_chan_write", "jaero_chan_pcm_view", "jaero_chan_read_pcm", "jaero_chan_retune",
@@ -202,6 +204,12 @@ def lib():
     L.jaero_aerol_profile2_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_aerol_debug_extra_bytes.argtypes = [vp]
     L.jaero_aerol_debug_extra_bytes.restype = C.c_longlong
+    L.jaero_read_all.argtypes = [vp, ip, vp, ip, vp, C.POINTER(ip), C.POINTER(C.c_longlong), vp]
+    L.jaero_read_status_all.argtypes = [vp, vp]
+    L.jaero_profile2_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
+    L.jaero_debug_read_all_bytes.argtypes = [vp]
+    L.jaero_debug_read_all_bytes.restype = C.c_longlong
+    L.jaero_debug_softbit_counts.argtypes = [vp, vp, vp]
     L.jaero_ingest_create.argtypes = [vp, ip, ip, C.POINTER(vp)]
     L.jaero_ingest_destroy.argtypes = [vp]
     L.jaero_ingest_destroy.restype = None

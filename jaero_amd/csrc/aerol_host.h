@@ -3,18 +3,7 @@
 
 #include <mutex>
 #include "aerolc.h"
-#include "k_aerol_sweep.h"
-
-// jaero_aerol_read_all's device scratch, allocated by the first sweep of a bank
-struct SweepBufs
-{
-    int nblk = 0;
-    size_t meta_bytes = 0, off_taken = 0, off_pending = 0, off_ovf = 0; // one block, copied to the host in one piece: offsets, taken counts, pending, flags
-    char *d_meta = nullptr;
-    long long *d_blk_sum = nullptr;
-    char *d_pack = nullptr; size_t pack_bytes = 0;
-    std::vector<char> h_meta;
-};
+#include "sweep_host.h"
 
 struct jaero_aerol_ctx
 {
@@ -456,92 +445,12 @@ extern "C" int jaero_aerol_read_voice(jaero_aerol_ctx *c, int ch, uint8_t *rows,
     return aerol_read(c, "jaero_aerol_read_voice", CI_V_CNT, c->cp.voice, c->cg.v_cap, 304, ch, rows, caprows, nrows, 4);
 }
 // ------------------------------------------------------------------------------------------ jaero_aerol_read_all
-// One log of every channel in one call (k_aerol_sweep.h).  Two synchronisations: after the offsets, after the rows.
-static int sweep_prepare(jaero_aerol_ctx *c)
-{
-    SweepBufs &w = c->sweep;
-    if (w.d_meta) return 0;
-    int rc;
-    const int nch = c->g.nch;
-    w.nblk = (nch + SWEEP_W - 1) / SWEEP_W;
-    w.off_taken = sizeof(int) * ((size_t)nch + 1);
-    w.off_pending = (w.off_taken + sizeof(int) * (size_t)w.nblk + 7) / 8 * 8;
-    w.off_ovf = w.off_pending + sizeof(long long);
-    w.meta_bytes = w.off_ovf + (size_t)nch;
-    DA(c->mem, w.d_blk_sum, w.nblk);
-    DA(c->mem, w.d_meta, w.meta_bytes);
-    w.h_meta.resize(w.meta_bytes);
-    return 0;
-}
-static int sweep_log(jaero_aerol_ctx *c, const RowBuf &b, int *ovword, int ovbit, void *rows, int caprows, int *offsets, int *nchannels_taken,
-                     long long *rows_pending, unsigned char *overflowed)
-{
-    int rc;
-    HIPCHK(hipSetDevice(c->device));
-    if ((rc = sweep_prepare(c))) return rc;
-    SweepBufs &w = c->sweep;
-    const int nch = c->g.nch;
-    hipStream_t st = c->last_stream;
-    int *d_off = (int *)w.d_meta, *d_taken = (int *)(w.d_meta + w.off_taken);
-    int pi = c->timer.begin(3, st);
-    hipLaunchKernelGGL(k_sweep_sums, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const int *)b.cnt, b.cap, nch, w.d_blk_sum);
-    hipLaunchKernelGGL(k_sweep_offsets, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const int *)b.cnt, b.cap, nch, (const long long *)w.d_blk_sum, (long long)caprows,
-                       (const int *)ovword, ovbit, d_off, d_taken, (long long *)(w.d_meta + w.off_pending), (unsigned char *)(w.d_meta + w.off_ovf));
-    c->timer.end(pi, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(w.h_meta.data(), w.d_meta, w.meta_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const int *h_off = (const int *)w.h_meta.data(), *h_taken = (const int *)(w.h_meta.data() + w.off_taken);
-    const unsigned char *h_ovf = (const unsigned char *)(w.h_meta.data() + w.off_ovf);
-    int taken = 0;
-    for (int k = 0; k < w.nblk; k++) taken += h_taken[k];
-    const int total = h_off[taken]; // rows taken: P of the last taken channel (= offsets[nch] when every channel is taken)
-    memcpy(offsets, h_off, sizeof(int) * (size_t)taken);
-    for (int ch = taken; ch <= nch; ch++) offsets[ch] = total;
-    *nchannels_taken = taken;
-    if (rows_pending) memcpy(rows_pending, w.h_meta.data() + w.off_pending, sizeof(long long));
-    bool any_ov = false;
-    for (int ch = 0; ch < nch; ch++) any_ov |= h_ovf[ch] != 0;
-    if (overflowed) memcpy(overflowed, h_ovf, (size_t)nch);
-    if (total > 0 || any_ov)
-    {
-        const size_t bytes = (size_t)total * b.rowbytes;
-        if (bytes > w.pack_bytes)
-        {
-            // grown by half at least; the old buffer goes first (nothing is in flight: the stream was synchronised above), the new one is not zeroed
-            size_t want = w.pack_bytes + w.pack_bytes / 2;
-            if (want < bytes) want = bytes;
-            if (w.d_pack)
-            {
-                for (size_t k = 0; k < c->mem.ptrs.size(); k++) if (c->mem.ptrs[k] == (void *)w.d_pack) { c->mem.ptrs.erase(c->mem.ptrs.begin() + k); break; }
-                hipFree(w.d_pack);
-                w.d_pack = nullptr; w.pack_bytes = 0;
-            }
-            if ((rc = dalloc(c->mem, &w.d_pack, want, false))) return rc;
-            w.pack_bytes = want;
-        }
-        pi = c->timer.begin(3, st);
-        if (b.rowbytes % 16 == 0)
-            hipLaunchKernelGGL(k_sweep_gather<16>, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const char *)b.base, b.cnt, b.cap, (int)b.rowbytes, nch, (const int *)d_off,
-                               (const int *)d_taken, w.d_pack, ovword, ovbit);
-        else
-            hipLaunchKernelGGL(k_sweep_gather<8>, dim3(w.nblk), dim3(SWEEP_W), 0, st, (const char *)b.base, b.cnt, b.cap, (int)b.rowbytes, nch, (const int *)d_off,
-                               (const int *)d_taken, w.d_pack, ovword, ovbit);
-        c->timer.end(pi, st);
-        HIPCHK(hipGetLastError());
-        if (bytes) HIPCHK(hipMemcpyAsync(rows, w.d_pack, bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if (any_ov) return fail(JAERO_EOVERFLOW, "jaero_aerol_read_all: channels overflowed this output buffer (flag %d) since it was last read; rows were dropped", ovbit);
-    return 0;
-}
 // test hook: bytes of device memory the link and the sweep have allocated for this bank so far (0 for a bank that used neither)
 extern "C" long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *c)
 {
     if (!c) return -1;
     long long n = c->d_dcdmark ? (long long)sizeof(int) * c->g.nchp : 0;
-    if (c->sweep.d_meta) n += (long long)c->sweep.meta_bytes + (long long)sizeof(long long) * c->sweep.nblk;
-    return n + (long long)c->sweep.pack_bytes;
+    return n + c->sweep.bytes();
 }
 extern "C" int jaero_aerol_read_all(jaero_aerol_ctx *c, int what, void *rows, int caprows, int *offsets, int *nchannels_taken, long long *rows_pending,
                                     unsigned char *overflowed)
@@ -579,7 +488,9 @@ extern "C" int jaero_aerol_read_all(jaero_aerol_ctx *c, int what, void *rows, in
         ovbit = 4;
         break;
     }
-    return sweep_log(c, b, ov, ovbit, rows, caprows, offsets, nchannels_taken, rows_pending, overflowed);
+    // one log of every channel in one call (sweep_host.h); the sweep's kernels are class 3 of the bank's timer
+    return sweep_log({who, c->sweep, c->device, c->last_stream, c->mem, c->timer, 3, c->g.nch}, b, ov, ovbit, nullptr, rows, caprows, offsets, nchannels_taken,
+                     rows_pending, overflowed);
 }
 // = AeroL::updateDCD (aerol.cpp:1109-1122), which the reference drives from a 1 s wall-clock QTimer: the caller ticks it once per
 // second of signal time.  dcd_out (optional, [nchannels]) receives the datacd flags afterwards.

@@ -245,3 +245,16 @@ struct jaero_ctx;
 static void dcd_unlink_bank(jaero_ctx *b);
 static bool dcd_bank_linked(const jaero_ctx *b);
 #define LINKCHK(c) do { if (dcd_bank_linked(c)) return fail(JAERO_EINVAL, "jaero_set_settings: this change re-creates the bank, which is linked to an Aero-L bank (jaero_aerol_link_dcd): unlink, change, link a matching Aero-L bank"); } while (0)
+
+// ------------------------------------------------------------------------------------------ one-call reads
+// A bank's device scratch for the sweep both bank types share (jaero_aerol_read_all, jaero_read_all: sweep_host.h), allocated by its first sweep
+struct SweepBufs
+{
+    int nblk = 0;
+    size_t meta_bytes = 0, off_taken = 0, off_pending = 0, off_ovf = 0; // one block, copied to the host in one piece: offsets, taken counts, pending, flags
+    char *d_meta = nullptr;
+    long long *d_blk_sum = nullptr;
+    char *d_pack = nullptr; size_t pack_bytes = 0;
+    std::vector<char> h_meta;
+    long long bytes() const { return (d_meta ? (long long)meta_bytes + (long long)sizeof(long long) * nblk : 0) + (long long)pack_bytes; }
+};

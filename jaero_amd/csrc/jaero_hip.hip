@@ -214,7 +214,7 @@ struct jaero_ctx
     int16_t *o_soft = nullptr; double *o_sym = nullptr;
     int *o_soft_cnt = nullptr, *o_sym_cnt = nullptr, *o_overflow = nullptr, *o_flags = nullptr;
     int *o_nrx = nullptr; // burst: soft bits pushed but not yet emitted (RxDataBits.size()), kept at the tail of the buffer
-    KernelTimer timer{5}; // jaero_profile_read's five kernel classes
+    KernelTimer timer{6}; SweepBufs sweep; jaero_status *d_status_all = nullptr; // jaero_profile_read's five kernel classes + 5 = jaero_read_all / jaero_read_status_all's kernels; their scratch, allocated by the first call
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr; // a write on another stream than the previous one waits for what was enqueued on that one (setters included)
     bool poisoned = false;         // a launch inside a write failed: the host's schedule mirror has advanced past the device state
@@ -1137,6 +1137,12 @@ extern "C" int jaero_profile_read(jaero_ctx *c, int which, double *total_ms, int
     return c->timer.read(c->device, which, total_ms, launches, reset);
 }
 
+extern "C" int jaero_profile2_read(jaero_ctx *c, int which, double *total_ms, int *launches, int reset)
+{
+    if (!c || which < 0 || which > 5) return fail(JAERO_EINVAL, "jaero_profile2_read: bad arguments");
+    return c->timer.read(c->device, which, total_ms, launches, reset);
+}
+
 extern "C" int jaero_profile_kernel(jaero_ctx *c, int which, char *buf, int cap)
 {
     if (!c || !buf || cap < 2 || which < 0 || which > 4) return fail(JAERO_EINVAL, "jaero_profile_kernel: bad arguments");
@@ -1854,3 +1860,93 @@ extern "C" int jaero_viterbi_continuous(int device, const uint8_t *soft, int nst
 #include "ingest_host.h"
 #include "edge_host.h"
 #include "chan_host.h"
+
+// ------------------------------------------------------------------------------------------ one-call reads of every channel
+// (here, behind aerol_host.h: the sweep's kernels stay where they were in the code object, behind the banks' own)
+// jaero_read_all: one output class of every channel (sweep_host.h, k_aerol_sweep.h).  The RowBufs are the per-channel readers'; a burst
+// bank's soft bits keep their pending tail (o_nrx).  The scratch (jaero_ctx::sweep, d_status_all) is allocated by the first call and goes with
+// the bank object at a rate change (swap_in): the bank that takes its place allocates afresh.
+extern "C" int jaero_read_all(jaero_ctx *c, int what, void *rows, int caprows, int *offsets, int *nchannels_taken, long long *rows_pending,
+                              unsigned char *overflowed)
+{
+    const char *who = "jaero_read_all";
+    if (what < JAERO_BANK_SOFTBITS || what > JAERO_BANK_SYMBOLS) return fail(JAERO_EINVAL, "%s: what = %d is none of JAERO_BANK_SOFTBITS / STATUS_LOG / EVENTS / SYMBOLS", who, what);
+    if (caprows < 0) return fail(JAERO_EINVAL, "%s: caprows < 0", who);
+    if (!offsets || !nchannels_taken) return fail(JAERO_EINVAL, "%s: null offsets / nchannels_taken", who);
+    if (!rows && caprows > 0) return fail(JAERO_EINVAL, "%s: null rows with caprows > 0", who);
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    POISONCHK(c, "jaero_read_all");
+    RowBuf b{};
+    int ovbit = 0;
+    const int *pending = nullptr;
+    switch (what)
+    {
+    case JAERO_BANK_SOFTBITS:
+        b = RowBuf{c->o_soft, c->o_soft_cnt, c->o_soft_cap, sizeof(int16_t)};
+        ovbit = 1;
+        pending = c->burst ? c->o_nrx : nullptr;
+        break;
+    case JAERO_BANK_STATUS_LOG:
+        if (c->burst) return fail(JAERO_ENOTSUP, "%s: burst banks have an event log (JAERO_BANK_EVENTS), not a status log", who);
+        b = RowBuf{c->p.slog, c->p.I + (size_t)I_LOG_CNT * c->g.nchp, c->g.log_cap, 6 * sizeof(double)};
+        ovbit = 4;
+        break;
+    case JAERO_BANK_EVENTS:
+        if (!c->burst) return fail(JAERO_ENOTSUP, "%s: continuous banks have a status log (JAERO_BANK_STATUS_LOG), not an event log", who);
+        b = RowBuf{c->bp.evlog, c->bp.I + (size_t)BI_EV_CNT * c->bg.nchp, c->bg.ev_cap, 3 * sizeof(double)};
+        ovbit = 4;
+        break;
+    default:
+        b = RowBuf{c->o_sym, c->o_sym_cnt, c->o_sym_cap, 3 * sizeof(double)};
+        ovbit = 2;
+        break;
+    }
+    if (!b.base || !b.cnt) return fail(JAERO_EINVAL, "%s: this output was not enabled at create (or does not exist for this kind)", who);
+    return sweep_log({who, c->sweep, c->device, c->last_stream, c->mem, c->timer, 5, c->o_nch}, b, c->o_overflow, ovbit, pending, rows, caprows, offsets,
+                     nchannels_taken, rows_pending, overflowed);
+}
+
+// every channel's jaero_read_status in one launch, one copy and one synchronisation
+extern "C" int jaero_read_status_all(jaero_ctx *c, jaero_status *stt)
+{
+    if (!c || !stt) return fail(JAERO_EINVAL, "jaero_read_status_all: bad arguments");
+    POISONCHK(c, "jaero_read_status_all");
+    HIPCHK(hipSetDevice(c->device));
+    const int nch = c->o_nch;
+    if (!c->d_status_all)
+    {
+        const int rc = dalloc(c->mem, &c->d_status_all, nch, false);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->last_stream;
+    const int pi = c->timer.begin(5, st);
+    if (c->burst) hipLaunchKernelGGL(k_status_burst, dim3((nch + 255) / 256), dim3(256), 0, st, c->bg, c->bp, 0, nch, c->d_status_all);
+    else hipLaunchKernelGGL(k_status, dim3((nch + 255) / 256), dim3(256), 0, st, c->g, c->p, 0, nch, c->d_status_all);
+    c->timer.end(pi, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(stt, c->d_status_all, sizeof(jaero_status) * (size_t)nch, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// test hook: device bytes jaero_read_all / jaero_read_status_all have allocated for the bank so far
+extern "C" long long jaero_debug_read_all_bytes(const jaero_ctx *c)
+{
+    if (!c) return -1;
+    return c->sweep.bytes() + (c->d_status_all ? (long long)sizeof(jaero_status) * c->o_nch : 0);
+}
+
+// test hook: per channel, the soft bits held and (burst banks) how many of them are not yet emitted
+extern "C" int jaero_debug_softbit_counts(jaero_ctx *c, int *cnt, int *pending)
+{
+    if (!c || !cnt || !pending) return fail(JAERO_EINVAL, "jaero_debug_softbit_counts: bad arguments");
+    POISONCHK(c, "jaero_debug_softbit_counts");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    const size_t n = sizeof(int) * (size_t)c->o_nch;
+    HIPCHK(hipMemcpy(cnt, c->o_soft_cnt, n, hipMemcpyDeviceToHost));
+    if (c->burst && c->o_nrx) HIPCHK(hipMemcpy(pending, c->o_nrx, n, hipMemcpyDeviceToHost));
+    else memset(pending, 0, n);
+    return 0;
+}
+

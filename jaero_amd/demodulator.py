@@ -202,6 +202,63 @@ class DemodulatorBank:
         capi.check(self.L.jaero_read_events(self.h, channel, buf.ctypes.data, caprows, C.byref(n)))
         return buf[: n.value].copy()
 
+    # ---- one call for every channel (jaero_read_all, jaero_read_status_all) ----
+    _ROWS = {capi.BANK_SOFTBITS: (np.int16, 1), capi.BANK_STATUS_LOG: (np.float64, 6), capi.BANK_EVENTS: (np.float64, 3), capi.BANK_SYMBOLS: (np.float64, 3)}
+
+    def read_all_raw(self, what: int, caprows: int):
+        """One jaero_read_all call: (rc, rows[offsets[taken]], offsets int32[nch + 1], taken, rows_pending, overflowed bool[nch]).  rc is E_OK or
+        E_OVERFLOW (everything is filled in either way); other codes raise."""
+        dt, width = self._ROWS[what]
+        rows = np.empty((max(caprows, 1), width), dtype=dt)
+        offsets = np.zeros(self.nch + 1, dtype=np.int32)
+        ovf = np.zeros(self.nch, dtype=np.uint8)
+        taken, pending = C.c_int(0), C.c_longlong(0)
+        rc = self.L.jaero_read_all(self.h, what, rows.ctypes.data if caprows > 0 else None, caprows, offsets.ctypes.data, C.byref(taken), C.byref(pending),
+                                   ovf.ctypes.data)
+        if rc not in (capi.E_OK, capi.E_OVERFLOW):
+            capi.check(rc)
+        rows = rows[: int(offsets[taken.value])]  # (a view of the call's own buffer: no second copy of what may be hundreds of megabytes)
+        return rc, (rows.reshape(-1) if width == 1 else rows), offsets, taken.value, pending.value, ovf.astype(bool)
+
+    def read_all(self, what: int, caprows: Optional[int] = None, overflowed: bool = False):
+        """Channel c's rows of class `what` (capi.BANK_*) are rows[offsets[c]:offsets[c + 1]] for c < taken: (rows, offsets, taken).  rows is 1-D
+        int16 for soft bits, (n, 6) / (n, 3) float64 otherwise.  caprows=None sizes the buffer with a caprows = 0 call first, so every channel is
+        taken.  Channels that had overflowed raise JaeroError(E_OVERFLOW) after the arrays are filled -- they are the exception's `result`, with the
+        flags as its `overflowed` -- unless overflowed=True, which returns (rows, offsets, taken, overflowed bool[nch]) instead."""
+        rc0, ovf0 = capi.E_OK, False
+        if caprows is None:
+            rc0, _, _, _, pending, ovf0 = self.read_all_raw(what, 0)  # takes the leading channels without rows only
+            caprows = int(min(pending, (1 << 31) - 1))
+        rc, rows, offsets, taken, _, ovf = self.read_all_raw(what, caprows)
+        rc, ovf = rc or rc0, ovf | ovf0
+        if overflowed:
+            return rows, offsets, taken, ovf
+        if rc == capi.E_OVERFLOW:
+            err = capi.JaeroError(rc, self.L.jaero_last_error().decode())
+            err.result, err.overflowed = (rows, offsets, taken), ovf
+            raise err
+        return rows, offsets, taken
+
+    def read_softbits_ragged(self):
+        """Every channel's soft bits in one call: (flat int16, offsets int32[nch + 1]); channel c's are flat[offsets[c]:offsets[c + 1]]."""
+        flat, offsets, _ = self.read_all(capi.BANK_SOFTBITS)
+        return flat, offsets
+
+    def read_status_all(self) -> np.ndarray:
+        """Every channel's read_status in one call: a structured array over capi.Status (fields mse, ebno, freq_est, freq_center, signal, n_estimates)."""
+        st = np.zeros(self.nch, dtype=np.dtype(capi.Status))
+        capi.check(self.L.jaero_read_status_all(self.h, st.ctypes.data))
+        return st
+
+    def softbit_counts(self):
+        """Test hook (jaero_debug_softbit_counts): (held int32[nch], pending int32[nch])."""
+        cnt, pend = np.zeros(self.nch, dtype=np.int32), np.zeros(self.nch, dtype=np.int32)
+        capi.check(self.L.jaero_debug_softbit_counts(self.h, cnt.ctypes.data, pend.ctypes.data))
+        return cnt, pend
+
+    def read_all_bytes(self) -> int:
+        return int(self.L.jaero_debug_read_all_bytes(self.h))
+
     # ---- profiling ----
     def profile_enable(self, on: bool = True):
         capi.check(self.L.jaero_profile_enable(self.h, int(on)))
@@ -209,6 +266,12 @@ class DemodulatorBank:
     def profile_read(self, which: int, reset: bool = False):
         ms, n = C.c_double(0), C.c_int(0)
         capi.check(self.L.jaero_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
+
+    def profile2_read(self, which: int, reset: bool = False):
+        """As profile_read, with which 5 = the kernels of read_all / read_status_all as well."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.L.jaero_profile2_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
 
     def profile_kernel(self, which: int) -> str:
