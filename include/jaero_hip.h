@@ -609,6 +609,67 @@ int jaero_debug_burst_poke_cv(jaero_ctx *ctx, int channel, long long first_abs_i
 int jaero_debug_burst_trident(jaero_ctx *ctx, const int *channels, const int *ev_pos, int nlist, long long n0, int grid,
                               jaero_trident_result *results, int *nchanged);
 
+/* Test hooks: a burst bank's per-sample detector k_burst_front<false / true> with k_ev_compact behind it, launched by the lines jaero_write
+ * launches them with (the choice between the two instantiations and its count of samples included), and nothing behind them: no trident check, no
+ * demodulator.  The rules of the hooks above hold: all synchronise the bank first and return JAERO_EINVAL before any launch for a null ctx, a bank
+ * that is not a burst bank, a channel or a value out of range; front, front_poke and poke_bt mark the bank (a later jaero_write or setter returns
+ * JAERO_EHIP), front_geom, front_peek and front_events only read and may be called between real writes.  front_peek, front_events, front_poke and poke_bt take a channel in
+ * [0, nchp): the padding lanes of the last wavefront run the detector too, and a test has to show that what they find reaches no event list.
+ *   jaero_debug_burst_front_geom  the lengths of the detector's rings and what else jaero_burst_geom does not tell (that struct keeps its size).
+ *   jaero_debug_burst_front       ONE segment of 1 <= n <= min(maxseg, max_write_samples) samples: the history push of host PCM (either layout, as jaero_debug_burst_hilbert
+ *                                 takes it); then, with im == NULL, k_hilbert_fft as in jaero_write, else im[nchannels][n] (host) copied into the
+ *                                 segment's imaginary parts in the kernel's layout in its place (padding lanes get zeros), so that a test sets both
+ *                                 parts of the analytic sample: re of sample m is -pcm[m - hil_lat - 1024] / 32768; then k_burst_front and
+ *                                 k_ev_compact.  Advances the bank's sample count by n.  ev_pos[nchannels]: every channel's BI_EV_POS (the sample of
+ *                                 the segment at which its trident buffer filled, or -1); ev_list[nchannels]: its first *ev_count entries are the
+ *                                 channels k_ev_compact listed, the others are left alone.
+ *   jaero_debug_burst_front_peek  st (may be NULL): the detector's scalars of one channel.  ring >= 0 (JAERO_FRONT_RING_*) with n >= 1: n entries of
+ *                                 that ring from absolute sample index first on (sample a lives at slot a mod the ring's length, mathematical
+ *                                 modulo); the window lies wholly among the last `length` samples before the bank's sample count (before the
+ *                                 stream starts the rings hold zeros, or what poke_bt put there).  ring < 0: no ring is read.
+ *   jaero_debug_burst_front_events  the first min(ev_cnt, caprows) rows (sample, kind, value) of a channel's event log, which stay where they
+ *                                 are (jaero_read_events refuses a marked bank); *nrows = ev_cnt.  With JAERO_FLAG_TRACE the detector logs a
+ *                                 kind-3 row for every firing.
+ *   jaero_debug_burst_front_poke  one scalar of one channel: JAERO_FRONT_CNTDOWN in [0, 2 PL], _MAXPOSCD in [-1, 2 PL], _TRI_PTR in [0, tri_sz + 1],
+ *                                 _BT_HOLD in [0, bt_lag] (whole numbers), _LASTDY any finite value.  Poking BT_HOLD also raises the bank's own
+ *                                 count of samples to hold to at least that value, so that the launch line picks k_burst_front<true> as it does
+ *                                 behind a jaero_set_settings.
+ *   jaero_debug_burst_poke_bt     entries of the peak detector's ring (the burst-timing signal of the last 2 PL + 1 samples) by absolute sample
+ *                                 index, negative indices allowed as in poke_cv; 1 <= n <= bt_len.
+ *   jaero_debug_ev_compact        k_ev_compact alone on buffers of its own, no bank: masks[ngroups] (host; bit l of masks[g] = channel 64 g + l),
+ *                                 1 <= ngroups <= 65536.  The device list of 64 * ngroups entries is filled with bytes 0xA5 before the launch and
+ *                                 copied whole to list_out[64 * ngroups]: what lies behind *count_out must still hold 0xA5A5A5A5. */
+#define JAERO_FRONT_RING_AGC 0
+#define JAERO_FRONT_RING_CVRE 1
+#define JAERO_FRONT_RING_CVIM 2
+#define JAERO_FRONT_RING_MA1RE 3
+#define JAERO_FRONT_RING_MA1IM 4
+#define JAERO_FRONT_RING_MAV1 5
+#define JAERO_FRONT_RING_FA 6
+#define JAERO_FRONT_RING_BT 7
+#define JAERO_FRONT_CNTDOWN 0
+#define JAERO_FRONT_MAXPOSCD 1
+#define JAERO_FRONT_TRI_PTR 2
+#define JAERO_FRONT_BT_HOLD 3
+#define JAERO_FRONT_LASTDY 4
+typedef struct jaero_burst_front_geom
+{
+    int PL, bt_len, bt_lag, agc_len, ma1_len, mav1_len, fa_len, fa_lag, ev_cap, ngroups;
+    double pd_thr, bt_w, fa_w;
+} jaero_burst_front_geom;
+typedef struct jaero_burst_front_state
+{
+    double agc_sum, ma1_re, ma1_im, mav1_sum, lastdy;
+    int cntdown, maxposcd, tri_ptr, ev_pos, ev_cnt, bt_hold;
+} jaero_burst_front_state;
+int jaero_debug_burst_front_geom(jaero_ctx *ctx, jaero_burst_front_geom *out);
+int jaero_debug_burst_front(jaero_ctx *ctx, const int16_t *pcm, int layout, int n, const double *im, int *ev_pos, int *ev_list, int *ev_count);
+int jaero_debug_burst_front_peek(jaero_ctx *ctx, int channel, jaero_burst_front_state *st, int ring, long long first_abs_index, int n, double *out);
+int jaero_debug_burst_front_events(jaero_ctx *ctx, int channel, double *rows, int caprows, int *nrows);
+int jaero_debug_burst_front_poke(jaero_ctx *ctx, int channel, int field, double value);
+int jaero_debug_burst_poke_bt(jaero_ctx *ctx, int channel, long long first_abs_index, int n, const double *values);
+int jaero_debug_ev_compact(int device, const unsigned long long *masks, int ngroups, int *list_out, int *count_out);
+
 /* ------------------------------------------------------------------------------------------------ multi-GPU edge operations
  * The path shards by channel with no steady-state exchange (the reference runs its two stereo burst channels as two unrelated objects,
  * JAERO/audioburstoqpskdemodulator.cpp:8-10); the north star names two operations at the edges: fan out shared PCM, gather decoded bits.

@@ -32,6 +32,8 @@ EXPORTS = [
     "jaero_debug_coarse_poke", "jaero_debug_coarse_launch", "jaero_debug_coarse_peek",
     "jaero_debug_schedule", "jaero_debug_schedule_lanes", "jaero_debug_prefilter", "jaero_debug_read_prefiltered", "jaero_read_events",
     "jaero_debug_burst_geom", "jaero_debug_burst_hilbert", "jaero_debug_burst_read_hist", "jaero_debug_burst_poke_cv", "jaero_debug_burst_trident",
+    "jaero_debug_burst_front_geom", "jaero_debug_burst_front", "jaero_debug_burst_front_peek", "jaero_debug_burst_front_events", "jaero_debug_burst_front_poke", "jaero_debug_burst_poke_bt",
+    "jaero_debug_ev_compact",
     "jaero_debug_pre8400_write", "jaero_debug_pre8400_poke", "jaero_debug_pre8400_peek", "jaero_debug_pre8400_restart", "jaero_debug_pre8400_read_ring",
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
@@ -98,6 +100,24 @@ class TridentResult(C.Structure):
     """struct jaero_trident_result: one channel's result of jaero_debug_burst_trident."""
 
     _fields_ = [("ok", C.c_int), ("pad", C.c_int), ("freq", C.c_double), ("phase_deg", C.c_double), ("vol_gain", C.c_double), ("metric", C.c_double)]
+
+
+class BurstFrontGeom(C.Structure):
+    """struct jaero_burst_front_geom: what jaero_debug_burst_front_geom reports."""
+
+    _fields_ = [(n, C.c_int) for n in ("PL", "bt_len", "bt_lag", "agc_len", "ma1_len", "mav1_len", "fa_len", "fa_lag", "ev_cap", "ngroups")] + [
+        (n, C.c_double) for n in ("pd_thr", "bt_w", "fa_w")]
+
+
+class BurstFrontState(C.Structure):
+    """struct jaero_burst_front_state: the detector's scalars of one channel (jaero_debug_burst_front_peek)."""
+
+    _fields_ = [(n, C.c_double) for n in ("agc_sum", "ma1_re", "ma1_im", "mav1_sum", "lastdy")] + [
+        (n, C.c_int) for n in ("cntdown", "maxposcd", "tri_ptr", "ev_pos", "ev_cnt", "bt_hold")]
+
+
+FRONT_RINGS = {"agc_ring": 0, "cvre": 1, "cvim": 2, "ma1re": 3, "ma1im": 4, "mav1": 5, "fa": 6, "bt": 7}  # JAERO_FRONT_RING_*
+FRONT_CNTDOWN, FRONT_MAXPOSCD, FRONT_TRI_PTR, FRONT_BT_HOLD, FRONT_LASTDY = 0, 1, 2, 3, 4
 
 
 class ChanChannel(C.Structure):
@@ -187,6 +207,13 @@ def lib():
     L.jaero_debug_burst_read_hist.argtypes = [vp, ip, C.c_longlong, ip, vp]
     L.jaero_debug_burst_poke_cv.argtypes = [vp, ip, C.c_longlong, ip, vp]
     L.jaero_debug_burst_trident.argtypes = [vp, vp, vp, ip, C.c_longlong, ip, vp, C.POINTER(ip)]
+    L.jaero_debug_burst_front_geom.argtypes = [vp, C.POINTER(BurstFrontGeom)]
+    L.jaero_debug_burst_front.argtypes = [vp, vp, ip, ip, vp, vp, vp, C.POINTER(ip)]
+    L.jaero_debug_burst_front_peek.argtypes = [vp, ip, C.POINTER(BurstFrontState), ip, C.c_longlong, ip, vp]
+    L.jaero_debug_burst_front_events.argtypes = [vp, ip, vp, ip, C.POINTER(ip)]
+    L.jaero_debug_burst_front_poke.argtypes = [vp, ip, ip, dp]
+    L.jaero_debug_burst_poke_bt.argtypes = [vp, ip, C.c_longlong, ip, vp]
+    L.jaero_debug_ev_compact.argtypes = [ip, vp, ip, vp, C.POINTER(ip)]
     L.jaero_aerol_create.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_create_burst.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_read_packets.argtypes = [vp, ip, vp, ip, C.POINTER(ip)]

@@ -234,7 +234,8 @@ static int burst_create(jaero_ctx *c, const std::vector<jaero_settings> &sets, c
 }
 
 // The launch lines of a write's transform kernels, shared by burst_write and the test hooks jaero_debug_burst_* (below): the history push of
-// one write, k_hilbert_fft of one segment, k_ev_compact and the bank's trident kernel with `grid` workgroups (burst_write: c->trident.grid).
+// one write, k_hilbert_fft and k_burst_front of one segment, k_ev_compact and the bank's trident kernel with `grid` workgroups (burst_write:
+// c->trident.grid).
 static int burst_launch_hist_push(jaero_ctx *c, const int16_t *dsrc, int nsamples, int layout, int slot0, hipStream_t st)
 {
     const BGeom &g = c->bg;
@@ -255,13 +256,33 @@ static int burst_launch_hilbert(jaero_ctx *c, int n, long long n0, hipStream_t s
     LAUNCHCHK("k_hilbert_fft");
     return 0;
 }
-static int burst_launch_ev_compact(jaero_ctx *c, hipStream_t st)
+// k_burst_front of one segment: the HOLD instantiation while a lane may still hold (see burst_write), and the count of what is left of that
+static int burst_launch_front(jaero_ctx *c, int n, long long n0, hipStream_t st)
 {
     const BGeom &g = c->bg;
     const BPtrs &p = c->bp;
-    hipLaunchKernelGGL(k_ev_compact, dim3(1), dim3(1024), 0, st, (const unsigned long long *)p.ev_mask, g.ngroups, p.ev_list, p.ev_count);
+    // bt_hold_left is an UPPER BOUND of every lane's BI_BT_HOLD (the per-lane, per-sample counter the kernel obeys): each setSettings sets
+    // both to bt_lag at the same moment, the lane's falls by one per sample, this one by n per segment of n samples -- so while any lane
+    // still holds, the HOLD instantiation runs (for all lanes: those whose counter is 0 compute what <false> computes).  A write that
+    // poisons the bank leaves the counter alone: a poisoned bank accepts nothing but jaero_destroy.
+    if (c->bt_hold_left > 0)
+    {
+        hipLaunchKernelGGL(k_burst_front<true>, dim3(g.ngroups), dim3(64), 0, st, g, p, n, n0);
+        c->bt_hold_left -= n;
+    }
+    else hipLaunchKernelGGL(k_burst_front<false>, dim3(g.ngroups), dim3(64), 0, st, g, p, n, n0);
+    LAUNCHCHK("k_burst_front");
+    return 0;
+}
+static int burst_launch_ev_compact_on(const unsigned long long *mask, int ngroups, int *ev_list, int *ev_count, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_ev_compact, dim3(1), dim3(1024), 0, st, mask, ngroups, ev_list, ev_count);
     LAUNCHCHK("k_ev_compact");
     return 0;
+}
+static int burst_launch_ev_compact(jaero_ctx *c, hipStream_t st)
+{
+    return burst_launch_ev_compact_on((const unsigned long long *)c->bp.ev_mask, c->bg.ngroups, c->bp.ev_list, c->bp.ev_count, st);
 }
 static int burst_launch_trident(jaero_ctx *c, int grid, long long n0, hipStream_t st)
 {
@@ -301,17 +322,7 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         if ((rc = burst_launch_hilbert(c, n, n0, st))) return rc;
         c->timer.end(pi, st);
         pi = c->timer.begin(4, st);
-        // bt_hold_left is an UPPER BOUND of every lane's BI_BT_HOLD (the per-lane, per-sample counter the kernel obeys): each setSettings sets
-        // both to bt_lag at the same moment, the lane's falls by one per sample, this one by n per segment of n samples -- so while any lane
-        // still holds, the HOLD instantiation runs (for all lanes: those whose counter is 0 compute what <false> computes).  A write that
-        // poisons the bank leaves the counter alone: a poisoned bank accepts nothing but jaero_destroy.
-        if (c->bt_hold_left > 0)
-        {
-            hipLaunchKernelGGL(k_burst_front<true>, dim3(g.ngroups), dim3(64), 0, st, g, p, n, n0);
-            c->bt_hold_left -= n;
-        }
-        else hipLaunchKernelGGL(k_burst_front<false>, dim3(g.ngroups), dim3(64), 0, st, g, p, n, n0);
-        LAUNCHCHK("k_burst_front");
+        if ((rc = burst_launch_front(c, n, n0, st))) return rc;
         if ((rc = burst_launch_ev_compact(c, st))) return rc;
         c->timer.end(pi, st);
         pi = c->timer.begin(1, st);
@@ -522,5 +533,172 @@ extern "C" int jaero_debug_burst_trident(jaero_ctx *c, const int *channels, cons
     for (int ch = 0; ch < nchp; ch++) changed += memcmp(&tri[(size_t)ch], &untouched, sizeof untouched) != 0;
     for (int k = 0; k < nlist; k++) memcpy(&results[k], &tri[(size_t)channels[k]], sizeof(TriResult));
     if (nchanged) *nchanged = changed;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ test hooks: k_burst_front and k_ev_compact alone
+// (tests/test_gpu_burst_front.py), through burst_launch_hist_push / _hilbert / _front / _ev_compact as burst_write calls them.  front, front_poke
+// and poke_bt poison the bank; front_geom, front_peek and front_events only read.  Peek and the pokes reach the padding lanes of the last wavefront too.
+static int burst_front_enter(jaero_ctx *c, const char *who, int channel, bool poison)
+{
+    if (c && c->burst && (channel < 0 || channel >= c->bg.nchp)) return fail(JAERO_EINVAL, "%s: channel %d outside [0, %d) (padding lanes included)", who, channel, c->bg.nchp);
+    return burst_hook_enter(c, who, 0, poison);
+}
+extern "C" int jaero_debug_burst_front_geom(jaero_ctx *c, jaero_burst_front_geom *out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_debug_burst_front_geom: null output");
+    int rc = burst_hook_enter(c, "jaero_debug_burst_front_geom", 0, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    out->PL = g.PL; out->bt_len = g.bt_len; out->bt_lag = g.bt_lag; out->agc_len = g.agc_len; out->ma1_len = g.ma1_len; out->mav1_len = g.mav1_len;
+    out->fa_len = g.fa_len; out->fa_lag = g.fa_lag; out->ev_cap = g.ev_cap; out->ngroups = g.ngroups;
+    out->pd_thr = g.pd_thr; out->bt_w = g.bt_w; out->fa_w = g.fa_w;
+    return 0;
+}
+extern "C" int jaero_debug_burst_front(jaero_ctx *c, const int16_t *pcm, int layout, int n, const double *im, int *ev_pos, int *ev_list, int *ev_count)
+{
+    if (c && c->burst && (!pcm || !ev_pos || !ev_list || !ev_count || n <= 0 || n > c->bg.maxseg || n > c->max_write))
+        return fail(JAERO_EINVAL, "jaero_debug_burst_front: n %d (one segment: 1 .. min(maxseg %d, max_write_samples %d) samples of host PCM, and the three outputs)", n, c->bg.maxseg, c->max_write);
+    if (layout != JAERO_PCM_CHANNEL_MAJOR && layout != JAERO_PCM_FRAME_MAJOR) return fail(JAERO_EINVAL, "jaero_debug_burst_front: bad layout");
+    int rc = burst_hook_enter(c, "jaero_debug_burst_front", 0, true);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    const int nch = g.nch, nchp = g.nchp;
+    hipStream_t st = c->last_stream;
+    const long long n0 = c->nsamples_total;
+    HIPCHK(hipMemcpyAsync(c->d_pcm_raw, pcm, sizeof(int16_t) * (size_t)nch * n, hipMemcpyHostToDevice, st));
+    if ((rc = burst_launch_hist_push(c, c->d_pcm_raw, n, layout, (int)(n0 % g.hist_len), st))) return rc;
+    if (im)
+    {
+        // k_hilbert_fft's output layout: sample i of channel ch at ((ch >> 6) * maxseg + i) * 64 + (ch & 63)
+        std::vector<double> him((size_t)g.ngroups * g.maxseg * 64, 0.0);
+        for (int ch = 0; ch < nch; ch++)
+            for (int i = 0; i < n; i++) him[((size_t)(ch >> 6) * g.maxseg + i) * 64 + (ch & 63)] = im[(size_t)ch * n + i];
+        HIPCHK(hipMemcpyAsync(c->bp.him, him.data(), sizeof(double) * him.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st)); // him leaves scope
+    }
+    else if ((rc = burst_launch_hilbert(c, n, n0, st))) return rc;
+    if ((rc = burst_launch_front(c, n, n0, st))) return rc;
+    if ((rc = burst_launch_ev_compact(c, st))) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    c->nsamples_total += n;
+    int count = 0;
+    HIPCHK(hipMemcpy(ev_pos, c->bp.I + (size_t)BI_EV_POS * nchp, sizeof(int) * (size_t)nch, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&count, c->bp.ev_count, sizeof(int), hipMemcpyDeviceToHost));
+    *ev_count = count;
+    if (count < 0 || count > nch) return fail(JAERO_EHIP, "jaero_debug_burst_front: k_ev_compact counted %d events among %d channels", count, nch);
+    if (count) HIPCHK(hipMemcpy(ev_list, c->bp.ev_list, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    return 0;
+}
+// a channel's column of a [group][slot][lane] ring, by absolute sample index (sample a lives at slot a mod len, mathematical modulo)
+static int burst_ring_column(double *ring, int len, int ch, long long first, int n, double *host, bool to_device)
+{
+    const long long R = len;
+    const int slot = (int)(((first % R) + R) % R), n1 = n < len - slot ? n : len - slot;
+    double *col = ring + (size_t)(ch >> 6) * len * 64 + (ch & 63);
+    if (to_device)
+    {
+        HIPCHK(hipMemcpy2D(col + (size_t)slot * 64, sizeof(double) * 64, host, sizeof(double), sizeof(double), (size_t)n1, hipMemcpyHostToDevice));
+        if (n > n1) HIPCHK(hipMemcpy2D(col, sizeof(double) * 64, host + n1, sizeof(double), sizeof(double), (size_t)(n - n1), hipMemcpyHostToDevice));
+    }
+    else
+    {
+        HIPCHK(hipMemcpy2D(host, sizeof(double), col + (size_t)slot * 64, sizeof(double) * 64, sizeof(double), (size_t)n1, hipMemcpyDeviceToHost));
+        if (n > n1) HIPCHK(hipMemcpy2D(host + n1, sizeof(double), col, sizeof(double) * 64, sizeof(double), (size_t)(n - n1), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+extern "C" int jaero_debug_burst_front_peek(jaero_ctx *c, int ch, jaero_burst_front_state *out, int ring, long long first, int n, double *ring_out)
+{
+    if (ring > JAERO_FRONT_RING_BT || (ring >= 0 && (!ring_out || n <= 0))) return fail(JAERO_EINVAL, "jaero_debug_burst_front_peek: ring %d, n %d (a ring 0 .. 7 with n >= 1 and an output, or ring < 0)", ring, n);
+    int rc = burst_front_enter(c, "jaero_debug_burst_front_peek", ch, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    const BPtrs &p = c->bp;
+    const int nchp = g.nchp;
+    if (ring >= 0)
+    {
+        double *const rings[8] = {p.agc_ring, p.cvre, p.cvim, p.ma1re, p.ma1im, p.mav1, p.fa, p.bt};
+        const int lens[8] = {g.agc_len, g.cv_len, g.cv_len, g.ma1_len, g.ma1_len, g.mav1_len, g.fa_len, g.bt_len};
+        const long long total = c->nsamples_total;
+        if (n > lens[ring] || first < total - lens[ring] || first > total - n)
+            return fail(JAERO_EINVAL, "jaero_debug_burst_front_peek: samples [%lld, %lld + %d) are not all among the last %d before sample %lld", first, first, n, lens[ring], total);
+        if ((rc = burst_ring_column(rings[ring], lens[ring], ch, first, n, ring_out, false))) return rc;
+    }
+    if (out)
+    {
+        double *d[5] = {&out->agc_sum, &out->ma1_re, &out->ma1_im, &out->mav1_sum, &out->lastdy};
+        const int df[5] = {BS_AGC_SUM, BS_MA1_RE, BS_MA1_IM, BS_MAV1_SUM, BS_LASTDY};
+        for (int k = 0; k < 5; k++) HIPCHK(hipMemcpy(d[k], p.S + (size_t)df[k] * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
+        int *q[6] = {&out->cntdown, &out->maxposcd, &out->tri_ptr, &out->ev_pos, &out->ev_cnt, &out->bt_hold};
+        const int qf[6] = {BI_CNTDOWN, BI_MAXPOSCD, BI_TRI_PTR, BI_EV_POS, BI_EV_CNT, BI_BT_HOLD};
+        for (int k = 0; k < 6; k++) HIPCHK(hipMemcpy(q[k], p.I + (size_t)qf[k] * nchp + ch, sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+extern "C" int jaero_debug_burst_front_events(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows)
+{
+    if (!rows || !nrows || caprows < 0) return fail(JAERO_EINVAL, "jaero_debug_burst_front_events: null output or negative capacity");
+    int rc = burst_front_enter(c, "jaero_debug_burst_front_events", ch, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    int cnt = 0;
+    HIPCHK(hipMemcpy(&cnt, c->bp.I + (size_t)BI_EV_CNT * g.nchp + ch, sizeof(int), hipMemcpyDeviceToHost));
+    if (cnt < 0 || cnt > g.ev_cap) return fail(JAERO_EHIP, "jaero_debug_burst_front_events: channel %d counts %d rows in a log of %d", ch, cnt, g.ev_cap);
+    *nrows = cnt;
+    const int take = cnt < caprows ? cnt : caprows;
+    if (take) HIPCHK(hipMemcpy(rows, c->bp.evlog + (size_t)ch * g.ev_cap * 3, sizeof(double) * 3 * (size_t)take, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int jaero_debug_burst_front_poke(jaero_ctx *c, int ch, int field, double value)
+{
+    if (c && c->burst)
+    {
+        const BGeom &g = c->bg;
+        const double lo[5] = {0, -1, 0, 0, 0}, hi[5] = {2.0 * g.PL, 2.0 * g.PL, g.tri_sz + 1.0, (double)g.bt_lag, 0};
+        const bool ok = field == JAERO_FRONT_LASTDY ? std::isfinite(value)
+                                                    : field >= 0 && field < JAERO_FRONT_LASTDY && value >= lo[field] && value <= hi[field] && value == (double)(int)value;
+        if (!ok) return fail(JAERO_EINVAL, "jaero_debug_burst_front_poke: field %d cannot take the value %g", field, value);
+    }
+    int rc = burst_front_enter(c, "jaero_debug_burst_front_poke", ch, true);
+    if (rc) return rc;
+    const int nchp = c->bg.nchp;
+    if (field == JAERO_FRONT_LASTDY)
+    {
+        HIPCHK(hipMemcpy(c->bp.S + (size_t)BS_LASTDY * nchp + ch, &value, sizeof(double), hipMemcpyHostToDevice));
+        return 0;
+    }
+    const int fld[4] = {BI_CNTDOWN, BI_MAXPOSCD, BI_TRI_PTR, BI_BT_HOLD};
+    const int v = (int)value;
+    HIPCHK(hipMemcpy(c->bp.I + (size_t)fld[field] * nchp + ch, &v, sizeof(int), hipMemcpyHostToDevice));
+    if (field == JAERO_FRONT_BT_HOLD && c->bt_hold_left < v) c->bt_hold_left = v; // the launch line's upper bound of every lane's counter
+    return 0;
+}
+extern "C" int jaero_debug_burst_poke_bt(jaero_ctx *c, int ch, long long first, int n, const double *values)
+{
+    if (!values) return fail(JAERO_EINVAL, "jaero_debug_burst_poke_bt: null input");
+    if (c && c->burst && (n <= 0 || n > c->bg.bt_len || first < -(1LL << 40) || first > (1LL << 40)))
+        return fail(JAERO_EINVAL, "jaero_debug_burst_poke_bt: n %d (1 .. bt_len %d samples from an index within +- 2^40)", n, c->bg.bt_len);
+    int rc = burst_front_enter(c, "jaero_debug_burst_poke_bt", ch, true);
+    if (rc) return rc;
+    return burst_ring_column(c->bp.bt, c->bg.bt_len, ch, first, n, const_cast<double *>(values), true);
+}
+extern "C" int jaero_debug_ev_compact(int device, const unsigned long long *masks, int ngroups, int *list_out, int *count_out)
+{
+    if (!masks || !list_out || !count_out || ngroups < 1 || ngroups > 65536)
+        return fail(JAERO_EINVAL, "jaero_debug_ev_compact: ngroups %d (1 .. 65536 masks, a list of 64 entries for each and a count)", ngroups);
+    int rc = open_device(device);
+    if (rc) return rc;
+    DevMem m;
+    unsigned long long *d_mask = nullptr;
+    int *d_list = nullptr, *d_count = nullptr;
+    DA(m, d_mask, ngroups); DA(m, d_list, (size_t)ngroups * 64); DA(m, d_count, 4);
+    HIPCHK(hipMemcpy(d_mask, masks, sizeof(unsigned long long) * (size_t)ngroups, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_list, 0xA5, sizeof(int) * (size_t)ngroups * 64));
+    HIPCHK(hipMemset(d_count, 0xA5, sizeof(int)));
+    if ((rc = burst_launch_ev_compact_on(d_mask, ngroups, d_list, d_count, 0))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(list_out, d_list, sizeof(int) * (size_t)ngroups * 64, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }

@@ -130,6 +130,16 @@ typedef struct jo_trident_result
     double freq, phase_deg, vol_gain, metric; /* metric: maxval (burst OQPSK) / minval (burst MSK), the traced value */
 } jo_trident_result;
 int jo_trident(int kind, double Fs, double fb, const double *window, int tri_sz, jo_trident_result *result, double *base_abs, double *top_abs);
+/* The front end alone (jaero_oracle_burst.c states the columns and the measured decisions): burst_front_end and the fire / tridentbuffer_ptr lines on
+ * supplied analytic samples, on an ordinary jo_burst; its scalars and lengths; the same recurrence from a fresh object in long double; and
+ * PeakDetector::update on given state. */
+int jo_burst_front_cols(void);
+long jo_burst_front_write(jo_burst *d, const double *re_im, long n, double *rows, int hold);
+void jo_burst_front_state(jo_burst *d, double *out8);
+void jo_burst_front_geom(jo_burst *d, double *out8);
+long jo_burst_front_exact(jo_burst *geom, const double *re_im, long n, long double *rows, long hold_at, int hold, double *info, long *trig, long trigcap);
+int jo_peakdet_run(int length, double threshold, const double *history, int cntdown, double lastdy, int maxposcntdown, const double *values, long n,
+                   int *fire, int *maxpos, double *state_out);
 int jo_hilbert_kernel(int N, double *re_im);
 typedef struct jo_hilbert jo_hilbert;
 jo_hilbert *jo_hilbert_create(int N);

@@ -402,7 +402,7 @@ static cpx cexp_i(double x) /* std::exp(imag*x): real part of the argument is +-
     cpx r; r.re = cos(x); r.im = sin(x); return r;
 }
 
-static void burst_front_end(jo_burst *d, cpx *cvalp, cpx *cval_d_out, double *val_to_demod_out, int *fire_out)
+static void burst_front_end(jo_burst *d, cpx *cvalp, cpx *cval_d_out, double *val_to_demod_out, int *fire_out, double *bt_sig_out)
 {
     /* burstoqpskdemodulator.cpp:372-396 == burstmskdemodulator.cpp:413-435 */
     cpx cval = *cvalp;
@@ -419,6 +419,7 @@ static void burst_front_end(jo_burst *d, cpx *cvalp, cpx *cval_d_out, double *va
     if (fastarm < 0) fastarm = 0;
     double bt_sig = fastarm * fastarm;
     if (bt_sig > 500) bt_sig = 500;
+    if (bt_sig_out) *bt_sig_out = bt_sig; /* jo_burst_front_write: the burst-timing signal as the peak detector receives it */
     *fire_out = peakdet_update(&d->pdet, &bt_sig);
     *cvalp = cval; *cval_d_out = cval_d; *val_to_demod_out = val_to_demod;
 }
@@ -435,7 +436,7 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
     {
         const long sample = d->nsamples_total + i;
         cpx cval = d->hfirbuff[i], cval_d; double val_to_demod; int fire;
-        burst_front_end(d, &cval, &cval_d, &val_to_demod, &fire);
+        burst_front_end(d, &cval, &cval_d, &val_to_demod, &fire, NULL);
         if (fire) { d->tridentbuffer_ptr = 0; if (d->trace) burst_event(d, sample, JO_EV_PEAK, 0); }
         if (d->tridentbuffer_ptr < d->tridentbuffer_sz) { d->tridentbuffer[d->tridentbuffer_ptr] = cval_d.re; d->tridentbuffer_ptr++; }
         else if (d->tridentbuffer_ptr == d->tridentbuffer_sz) { d->tridentbuffer_ptr++; boqpsk_trident_check(d, sample); }
@@ -784,7 +785,7 @@ static void bmsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstmskdemod
     {
         const long sample = d->nsamples_total + i;
         cpx cval = d->hfirbuff[i], cval_d; double val_to_demod; int fire;
-        burst_front_end(d, &cval, &cval_d, &val_to_demod, &fire);
+        burst_front_end(d, &cval, &cval_d, &val_to_demod, &fire, NULL);
         if (fire) { d->tridentbuffer_ptr = 0; if (d->trace) burst_event(d, sample, JO_EV_PEAK, 0); }
         if (d->tridentbuffer_ptr < d->tridentbuffer_sz) { d->tridentbuffer[d->tridentbuffer_ptr] = cval_d.re; d->tridentbuffer_ptr++; }
         else if (d->tridentbuffer_ptr == d->tridentbuffer_sz) { d->tridentbuffer_ptr++; bmsk_trident_check(d, sample); }
@@ -980,4 +981,174 @@ void jo_hilbert_update(jo_hilbert *h, const int16_t *pcm, long n, double *out_re
     cpx *o = (cpx *)out_re_im;
     for (long i = 0; i < n; i++) { o[i].re = ((double)pcm[i]) / 32768.0; o[i].im = 0; }
     fastfir_update(&h->f, o, n);
+}
+
+/* ------------------------------------------------------------------ the front end alone (tests/burst_front_cases.py)
+ * jo_burst_front_write: burst_front_end and the fire / tridentbuffer_ptr lines of boqpsk_write / bmsk_write (:439-441, :788-790) on analytic samples
+ * the caller supplies (what hfir.update leaves in hfirbuff), and nothing behind them: no trident check, no demodulator.  It works on an ordinary
+ * jo_burst, so jo_burst_set_settings in mid-stream does to the front end what it does in the reference.  Row i (JO_FRONT_COLS doubles) of sample i:
+ *   0, 1 the AGC'd cval; 2 bt_sig as the peak detector receives it; 3 fire; 4 whether the trident buffer filled on this sample;
+ *   5 |cval| as the AGC stored it; 6, 7 cval * conj(bt_d1's output) as bt_ma1 stored it; 8 |bt_ma1's mean| as mav1 stored it; 9 mav1's mean as
+ *   bt_ma_diff stored it; 10 - 13 the running sums behind this sample: the AGC's, bt_ma1's (re, im), mav1's.
+ * hold > 0: before the first sample the `hold` OLDEST of the last bt_lag = ceil(bt_d1.fractdelay) inputs of bt_d1 are replaced by zeros -- what the
+ * line holds when setSettings lies bt_lag - hold samples back (hold = bt_lag: right behind it). */
+enum { JO_FRONT_COLS = 14 };
+int jo_burst_front_cols(void) { return JO_FRONT_COLS; }
+long jo_burst_front_write(jo_burst *d, const double *re_im, long n, double *rows, int hold)
+{
+    const int lag = (int)ceil(d->bt_d1.fractdelay);
+    if (hold < 0 || hold > lag) return -1;
+    for (int k = lag; k > lag - hold; k--) /* the entry written k samples ago */
+    {
+        const int at = ((d->bt_d1.buffptr - k) % d->bt_d1.size + d->bt_d1.size) % d->bt_d1.size;
+        d->bt_d1.buff[at].re = 0; d->bt_d1.buff[at].im = 0;
+    }
+    for (long i = 0; i < n; i++)
+    {
+        const long sample = d->nsamples_total + i;
+        cpx cval = {re_im[2 * i], re_im[2 * i + 1]}, cval_d; double val_to_demod, bt_sig; int fire, filled = 0;
+        burst_front_end(d, &cval, &cval_d, &val_to_demod, &fire, &bt_sig);
+        if (fire) { d->tridentbuffer_ptr = 0; if (d->trace) burst_event(d, sample, JO_EV_PEAK, 0); }
+        if (d->tridentbuffer_ptr < d->tridentbuffer_sz) { d->tridentbuffer[d->tridentbuffer_ptr] = cval_d.re; d->tridentbuffer_ptr++; }
+        else if (d->tridentbuffer_ptr == d->tridentbuffer_sz) { d->tridentbuffer_ptr++; filled = 1; }
+        if (rows)
+        {
+            double *r = rows + (size_t)i * JO_FRONT_COLS;
+            const cpx pr = d->bt_ma1.buf[(d->bt_ma1.ptr + d->bt_ma1.sz - 1) % d->bt_ma1.sz];
+            r[0] = cval.re; r[1] = cval.im; r[2] = bt_sig; r[3] = fire; r[4] = filled;
+            r[5] = d->agc->buf[(d->agc->ptr + d->agc->sz - 1) % d->agc->sz];
+            r[6] = pr.re; r[7] = pr.im;
+            r[8] = d->mav1->buf[(d->mav1->ptr + d->mav1->sz - 1) % d->mav1->sz];
+            r[9] = d->bt_ma_diff.buff[(d->bt_ma_diff.buffptr + d->bt_ma_diff.size - 1) % d->bt_ma_diff.size];
+            r[10] = d->agc->sum; r[11] = d->bt_ma1.sum.re; r[12] = d->bt_ma1.sum.im; r[13] = d->mav1->sum;
+        }
+    }
+    d->nsamples_total += n;
+    return n;
+}
+/* the front end's scalars: agc sum, bt_ma1 sum (re, im), mav1 sum, lastdy, cntdown, maxposcntdown, tridentbuffer_ptr */
+void jo_burst_front_state(jo_burst *d, double *out8)
+{
+    out8[0] = d->agc->sum; out8[1] = d->bt_ma1.sum.re; out8[2] = d->bt_ma1.sum.im; out8[3] = d->mav1->sum; out8[4] = d->pdet.lastdy;
+    out8[5] = d->pdet.cntdown; out8[6] = d->pdet.maxposcntdown; out8[7] = d->tridentbuffer_ptr;
+}
+/* its lengths: agc, bt_d1.fractdelay, bt_ma1, mav1, bt_ma_diff.fractdelay, the peak detector's length and threshold, tridentbuffer_sz */
+void jo_burst_front_geom(jo_burst *d, double *out8)
+{
+    out8[0] = d->agc->sz; out8[1] = d->bt_d1.fractdelay; out8[2] = d->bt_ma1.sz; out8[3] = d->mav1->sz; out8[4] = d->bt_ma_diff.fractdelay;
+    out8[5] = d->pdet.d2.sz - 1; out8[6] = d->pdet.threshold; out8[7] = d->tridentbuffer_sz;
+}
+
+/* The same recurrence from a FRESH object in long double (the lengths are read from `geom`, whose state is not touched): rows as above.  Every
+ * decision the double run could take differently under rounding is measured: info[0] receives the smallest relative clearance of
+ *   the two clamps (fastarm < 0 on its two operands, bt_sig > 500 on 500), on every sample;
+ *   the three trigger terms vald > threshold, lastdy >= 0, dy < 0 (each on the larger of its two operands), on every sample with cntdown == 0;
+ *   every findmaxpos winner over the runner-up (on the winner);
+ * a term whose operands are all exactly 0 or 500 -- exact on both sides once the clamps are clear -- counts as decided and does not enter.
+ * hold_at, hold: as jo_burst_front_write's hold, applied before sample hold_at.  info[1] = the number of triggers; trig (rows of 3 longs, at most trigcap) = sample, maxpos, how many entries of the window equal the maximum. */
+static long double ldmax(long double a, long double b) { return a > b ? a : b; }
+static int ld_exact(long double v) { return v == 0.0L || v == 500.0L; }
+static long double ld_at(const long double *a, long i) { return i < 0 ? 0.0L : a[i]; }
+long jo_burst_front_exact(jo_burst *geom, const double *re_im, long n, long double *rows, long hold_at, int hold, double *info, long *trig, long trigcap)
+{
+    const int agc_len = geom->agc->sz, ma1_len = geom->bt_ma1.sz, mav1_len = geom->mav1->sz, PL = geom->pdet.d2.sz - 1, tri_sz = geom->tridentbuffer_sz;
+    const int bt_lag = (int)ceil(geom->bt_d1.fractdelay), fa_lag = (int)ceil(geom->bt_ma_diff.fractdelay);
+    const long double btw = (long double)bt_lag - (long double)geom->bt_d1.fractdelay, faw = (long double)fa_lag - (long double)geom->bt_ma_diff.fractdelay;
+    const long double thr = (long double)geom->pdet.threshold;
+    if (hold < 0 || hold > bt_lag || hold_at < 0) return -1;
+    long double *a = (long double *)calloc((size_t)n * 8, sizeof(long double));
+    long double *cr = a + n, *ci = cr + n, *pr = ci + n, *pi = pr + n, *fm = pi + n, *fa = fm + n, *bt = fa + n;
+    long double agc_sum = 0, m1r = 0, m1i = 0, mav = 0, lastdy = 0, last_a = 0, last_b = 0, worst = 1.0L;
+    int cntdown = 2 * PL, maxposcd = -1, tri_ptr = 0;
+    long ntrig = 0;
+    for (long k = 0; k < n; k++)
+    {
+        const long double xr = re_im[2 * k], xi = re_im[2 * k + 1];
+        a[k] = sqrtl(xr * xr + xi * xi);
+        agc_sum = agc_sum - ld_at(a, k - agc_len) + a[k];
+        long double gain = 1.414213562L / ldmax(agc_sum / agc_len, 0.000001L);
+        gain = ldmax(gain, 0.000001L);
+        cr[k] = xr * gain; ci[k] = xi * gain;
+        /* hold (see jo_burst_front_write): from sample hold_at on the `hold` oldest inputs of bt_d1 read as zeros */
+        const long left = (k >= hold_at && k < hold_at + hold) ? hold - (k - hold_at) : 0;
+        const long double nr = left > 1 ? 0.0L : ld_at(cr, k - bt_lag + 1), ni = left > 1 ? 0.0L : ld_at(ci, k - bt_lag + 1);
+        const long double orr = left > 0 ? 0.0L : ld_at(cr, k - bt_lag), oi = left > 0 ? 0.0L : ld_at(ci, k - bt_lag);
+        const long double dr = btw * nr + (1 - btw) * orr, di = btw * ni + (1 - btw) * oi;
+        pr[k] = cr[k] * dr + ci[k] * di; pi[k] = ci[k] * dr - cr[k] * di;
+        m1r = m1r - ld_at(pr, k - ma1_len) + pr[k]; m1i = m1i - ld_at(pi, k - ma1_len) + pi[k];
+        const long double mr = m1r / ma1_len, mi = m1i / ma1_len;
+        fm[k] = sqrtl(mr * mr + mi * mi);
+        mav = mav - ld_at(fm, k - mav1_len) + fm[k];
+        fa[k] = mav / mav1_len;
+        const long double del = faw * ld_at(fa, k - fa_lag + 1) + (1 - faw) * ld_at(fa, k - fa_lag);
+        long double f = fa[k] - del;
+        if (!(fa[k] == 0 && del == 0)) { const long double c = fabsl(f) / ldmax(fabsl(fa[k]), fabsl(del)); if (c < worst) worst = c; }
+        if (f < 0) f = 0;
+        long double b = f * f;
+        if (b != 0) { const long double c = fabsl(b - 500.0L) / 500.0L; if (c < worst) worst = c; }
+        if (b > 500) b = 500;
+        bt[k] = b;
+        const long double b2 = ld_at(bt, k - 2 * PL), vald = ld_at(bt, k - PL), dy = b - b2;
+        int fire = 0, filled = 0;
+        if (!cntdown)
+        {
+            if (!ld_exact(vald)) { const long double c = fabsl(vald - thr) / ldmax(vald, thr); if (c < worst) worst = c; }
+            if (!(ld_exact(last_a) && ld_exact(last_b))) { const long double c = fabsl(lastdy) / ldmax(last_a, last_b); if (c < worst) worst = c; }
+            if (!(ld_exact(b) && ld_exact(b2))) { const long double c = fabsl(dy) / ldmax(b, b2); if (c < worst) worst = c; }
+        }
+        if ((!cntdown) && (vald > thr) && (lastdy >= 0 && dy < 0))
+        {
+            long double mx = ld_at(bt, k - 2 * PL), second = -1;
+            int q0 = 0; long ties = 0;
+            for (int q = 0; q <= 2 * PL; q++) { const long double v = ld_at(bt, k - 2 * PL + q); if (v > mx) { mx = v; q0 = q; } }
+            for (int q = 0; q <= 2 * PL; q++) { const long double v = ld_at(bt, k - 2 * PL + q); if (v == mx) ties++; else if (v > second) second = v; }
+            if (ties > 1 && !ld_exact(mx)) worst = 0; /* two equal values that are not clamps: decided by rounding */
+            if (second >= 0 && mx > 0) { const long double c = (mx - second) / mx; if (c < worst) worst = c; }
+            cntdown = 2 * PL; maxposcd = q0;
+            if (trig && ntrig < trigcap) { trig[3 * ntrig] = k; trig[3 * ntrig + 1] = q0; trig[3 * ntrig + 2] = ties; }
+            ntrig++;
+        }
+        if (cntdown > 0) cntdown--;
+        lastdy = dy; last_a = b; last_b = b2;
+        if (!maxposcd) { maxposcd--; fire = 1; }
+        else if (maxposcd > 0) maxposcd--;
+        if (fire) tri_ptr = 0;
+        if (tri_ptr < tri_sz) tri_ptr++;
+        else if (tri_ptr == tri_sz) { tri_ptr++; filled = 1; }
+        if (rows)
+        {
+            long double *r = rows + (size_t)k * JO_FRONT_COLS;
+            r[0] = cr[k]; r[1] = ci[k]; r[2] = b; r[3] = fire; r[4] = filled; r[5] = a[k]; r[6] = pr[k]; r[7] = pi[k]; r[8] = fm[k]; r[9] = fa[k];
+            r[10] = agc_sum; r[11] = m1r; r[12] = m1i; r[13] = mav;
+        }
+    }
+    if (info) { info[0] = (double)worst; info[1] = (double)ntrig; info[2] = (double)agc_sum; info[3] = (double)m1r; info[4] = (double)m1i; info[5] = (double)mav; }
+    free(a);
+    return n;
+}
+
+/* PeakDetector::update (peakdet_update, dthing_findmaxpos) on given state: a detector of `length` whose three delay lines hold the last
+ * 2 * length + 1 values history[] (oldest first; d2 the last length + 1 of them), with the given counters; fire[i] for values[i], and with maxpos
+ * (optional) the winner of the search a trigger on sample i ran, else -1.  state_out: cntdown, lastdy, maxposcntdown behind the last value. */
+int jo_peakdet_run(int length, double threshold, const double *history, int cntdown, double lastdy, int maxposcntdown, const double *values, long n,
+                   int *fire, int *maxpos, double *state_out)
+{
+    if (length < 1 || !history || (n > 0 && (!values || !fire)) || cntdown < 0 || cntdown > 2 * length) return -1;
+    peakdet_t p;
+    memset(&p, 0, sizeof p);
+    peakdet_set(&p, length, threshold);
+    /* a DelayThing of size sz with ptr = 0 behind a whole number of turns: buffer[j] is the value written sz - j updates ago */
+    for (int j = 0; j <= 2 * length; j++) { p.d1.buffer[j] = history[j]; p.d3.buffer[j] = history[j]; }
+    for (int j = 0; j <= length; j++) p.d2.buffer[j] = history[length + j];
+    p.cntdown = cntdown; p.lastdy = lastdy; p.maxposcntdown = maxposcntdown;
+    for (long i = 0; i < n; i++)
+    {
+        double v = values[i];
+        const int before = p.cntdown;
+        fire[i] = peakdet_update(&p, &v);
+        if (maxpos) maxpos[i] = (before == 0 && p.cntdown == p.maxcntdown - 1) ? p.maxpos : -1;
+    }
+    if (state_out) { state_out[0] = p.cntdown; state_out[1] = p.lastdy; state_out[2] = p.maxposcntdown; }
+    free(p.d1.buffer); free(p.d2.buffer); free(p.d3.buffer);
+    return 0;
 }

@@ -459,6 +459,53 @@ class BurstDemod:
             if n < 64:
                 return np.concatenate(rows)
 
+    # ---- the front end alone (jaero_oracle_burst.c: jo_burst_front_*) ----
+    FRONT_COLS = ("cre", "cim", "bt", "fire", "filled", "agc_ring", "ma1re", "ma1im", "mav1", "fa", "agc_sum", "ma1_re", "ma1_im", "mav1_sum")
+    FRONT_STATE = ("agc_sum", "ma1_re", "ma1_im", "mav1_sum", "lastdy", "cntdown", "maxposcd", "tri_ptr")
+    FRONT_GEOM = ("agc_len", "bt_delay", "ma1_len", "mav1_len", "fa_delay", "PL", "pd_thr", "tri_sz")
+
+    def _front_protos(self):
+        L = self.L
+        L.jo_burst_front_write.restype = C.c_long
+        L.jo_burst_front_write.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_int]
+        L.jo_burst_front_exact.restype = C.c_long
+        L.jo_burst_front_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_long]
+        L.jo_burst_front_state.argtypes = [C.c_void_p, C.c_void_p]
+        L.jo_burst_front_geom.argtypes = [C.c_void_p, C.c_void_p]
+        assert L.jo_burst_front_cols() == len(self.FRONT_COLS)
+        return L
+
+    def front_write(self, z: np.ndarray, hold: int = 0) -> np.ndarray:
+        """burst_front_end and the fire / trident-buffer-pointer lines on analytic samples z (complex), nothing behind them: rows of FRONT_COLS.
+        hold: the `hold` oldest of bt_d1's last bt_lag inputs are zeroed first."""
+        z = np.ascontiguousarray(z, dtype=np.complex128)
+        rows = np.empty((len(z), len(self.FRONT_COLS)))
+        assert self._front_protos().jo_burst_front_write(self.h, z.ctypes.data, len(z), rows.ctypes.data, int(hold)) == len(z)
+        return rows
+
+    def front_exact(self, z: np.ndarray, trigcap: int = 4096, hold_at: int = 0, hold: int = 0):
+        """The same recurrence from a fresh object in long double on z: (rows of FRONT_COLS as long double, the smallest relative clearance of a
+        decision, triggers as rows (sample, maxpos, entries equal to the maximum), final sums agc, ma1 re, ma1 im, mav1).  hold_at, hold: as front_write's
+        hold, applied before sample hold_at."""
+        z = np.ascontiguousarray(z, dtype=np.complex128)
+        rows = np.empty((len(z), len(self.FRONT_COLS)), dtype=np.longdouble)
+        info = np.zeros(8)
+        trig = np.zeros((trigcap, 3), dtype=np.int64)
+        assert C.sizeof(C.c_long) == 8
+        assert self._front_protos().jo_burst_front_exact(self.h, z.ctypes.data, len(z), rows.ctypes.data, int(hold_at), int(hold), info.ctypes.data, trig.ctypes.data, trigcap) == len(z)
+        assert info[1] <= trigcap
+        return rows, float(info[0]), trig[:int(info[1])], info[2:6].copy()
+
+    def front_state(self) -> dict:
+        out = np.zeros(8)
+        self._front_protos().jo_burst_front_state(self.h, out.ctypes.data)
+        return {k: (float(v) if i < 5 else int(v)) for i, (k, v) in enumerate(zip(self.FRONT_STATE, out))}
+
+    def front_geom(self) -> dict:
+        out = np.zeros(8)
+        self._front_protos().jo_burst_front_geom(self.h, out.ctypes.data)
+        return dict(zip(self.FRONT_GEOM, (float(v) for v in out)))
+
     @property
     def pending(self):
         return self.L.jo_burst_pending_soft(self.h)
@@ -521,6 +568,20 @@ def trident(kind: int, Fs: float, fb: float, window: np.ndarray):
     rc = lib().jo_trident(int(kind), float(Fs), float(fb), w.ctypes.data, len(w), C.byref(r), base.ctypes.data, top.ctypes.data)
     assert rc == 0, "jo_trident: bad arguments"
     return r, base, top
+
+
+def peakdet_run(length: int, threshold: float, history: np.ndarray, cntdown: int, lastdy: float, maxposcd: int, values: np.ndarray):
+    """PeakDetector::update (DSP.h:528-560) on given state: the three delay lines hold history (the last 2 * length + 1 values, oldest first).
+    Returns (fire[n], maxpos[n] (-1 where no trigger), (cntdown, lastdy, maxposcntdown) behind the last value)."""
+    L = lib()
+    L.jo_peakdet_run.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
+    h = np.ascontiguousarray(history, dtype=np.float64)
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    assert len(h) == 2 * length + 1
+    fire, mp, st = np.zeros(len(v), dtype=np.int32), np.zeros(len(v), dtype=np.int32), np.zeros(3)
+    rc = L.jo_peakdet_run(length, threshold, h.ctypes.data, cntdown, lastdy, maxposcd, v.ctypes.data, len(v), fire.ctypes.data, mp.ctypes.data, st.ctypes.data)
+    assert rc == 0, "jo_peakdet_run: bad arguments"
+    return fire, mp, (int(st[0]), float(st[1]), int(st[2]))
 
 
 def hilbert_kernel(N=2048) -> np.ndarray:

@@ -100,6 +100,26 @@ def test_burst_acquisition_hooks_refuse_a_null_context():
     assert b"jaero_debug_burst_trident" in L.jaero_last_error() and n.value == 7
 
 
+def test_burst_front_hooks_refuse_a_null_context():
+    """jaero_debug_burst_front_geom / _front / _front_peek / _front_events / _front_poke / _poke_bt: JAERO_EINVAL before any HIP call, and
+    jaero_debug_ev_compact's argument checks (the rest: tests/test_gpu_burst_front.py).  jaero_burst_geom keeps its size."""
+    L = capi.lib()
+    assert C.sizeof(capi.BurstFrontGeom) == 64 and C.sizeof(capi.BurstFrontState) == 64  # 10 ints + 3 doubles; 5 doubles + 6 ints
+    buf = (C.c_double * 64)()
+    idx = (C.c_int * 64)()
+    n = C.c_int(7)
+    for name, args in (("jaero_debug_burst_front_geom", (C.byref(capi.BurstFrontGeom()),)), ("jaero_debug_burst_front", (buf, 0, 1, None, idx, idx, C.byref(n))),
+                       ("jaero_debug_burst_front_peek", (0, C.byref(capi.BurstFrontState()), 7, 0, 1, buf)), ("jaero_debug_burst_front_events", (0, buf, 4, C.byref(n))),
+                       ("jaero_debug_burst_front_poke", (0, 0, 0.0)), ("jaero_debug_burst_poke_bt", (0, 0, 1, buf))):
+        assert getattr(L, name)(None, *args) == capi.E_INVAL, name
+        assert name.encode() in L.jaero_last_error(), name
+    assert n.value == 7
+    masks = (C.c_uint64 * 1)()
+    for m, ng in ((None, 1), (masks, 0), (masks, 65537)):
+        assert L.jaero_debug_ev_compact(0, m, ng, idx, C.byref(n)) == capi.E_INVAL and b"jaero_debug_ev_compact" in L.jaero_last_error()
+    assert L.jaero_debug_ev_compact(0, masks, 1, None, C.byref(n)) == capi.E_INVAL and L.jaero_debug_ev_compact(0, masks, 1, idx, None) == capi.E_INVAL
+
+
 @pytest.mark.parametrize("kind,power,fb,Fs,lbw,ok", [
     (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.0, True), (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.5, False),
     (capi.KIND_OQPSK, 14, 8400.0, 48000.0, 30000.0, False), (capi.KIND_MSK, 13, 1200.0, 48000.0, 24001.0, False),
