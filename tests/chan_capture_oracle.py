@@ -9,8 +9,6 @@ from math import gcd
 
 import numpy as np
 
-import chan_oracle as CO
-
 CS16, CU8, CS8, CF32 = 0, 1, 2, 3
 FORMATS = {"cs16": CS16, "cu8": CU8, "cs8": CS8, "cf32": CF32}
 DTYPES = {CS16: np.int16, CU8: np.uint8, CS8: np.int8, CF32: np.float32}
@@ -117,19 +115,3 @@ class CaptureOracle:
 def gain_bound(h, L):
     """S = max_phi sum_j |h[phi + j L]|: the most a unit input can make of one output."""
     return float(np.abs(np.asarray(h)).reshape(-1, L).sum(axis=0).max())
-
-
-def assert_rule(got, ystar, gain, where=""):
-    """tests/test_gpu_chan.py's rule, restated: got == rint(y*), or off by one with the oracle's unrounded y* within 1e-7 max(1, g) of a
-    half-integer; and the output's RMS above 100 LSB."""
-    got = np.asarray(got).astype(np.int64)
-    ref = CO.to_int16(ystar).astype(np.int64)
-    assert got.shape == ref.shape, (where, got.shape, ref.shape)
-    d = np.abs(got - ref)
-    assert d.max(initial=0) <= 1, (where, "differs by more than one", int(d.max()))
-    tau = 1e-7 * max(1.0, gain)
-    off = np.nonzero(d)[0]
-    edge = np.abs(ystar[off] - (np.floor(ystar[off]) + 0.5))
-    print(f"{where}: {got.size} samples, {off.size} differ by one, rms {got.astype(float).std():.1f}")
-    assert (edge <= tau).all(), (where, "a sample differs away from a rounding edge", float(edge.max(initial=0)), int(off.size))
-    assert got.astype(float).std() > 100.0, (where, "output RMS below 100 LSB")

@@ -5,6 +5,7 @@ import numpy as np
 
 N = 16384
 HP = N // 2
+DECIMS = (16, 32, 64, 128, 256)  # the arithmetic depends on decim only through M = N / decim; the output rate (48, 24 or 12 kHz) is a label
 
 
 def words(tune, audio, decim):
@@ -39,7 +40,7 @@ class ChanOracle:
     this write produce.  channels: (tune, audio, gain) per channel; retune() replaces one from the next write on."""
 
     def __init__(self, decim, channels, taps):
-        assert decim in (16, 32, 64)
+        assert decim in DECIMS
         taps = np.asarray(taps, dtype=np.float64)
         assert 1 <= len(taps) <= N // 2 + 1
         self.D, self.M = decim, N // decim

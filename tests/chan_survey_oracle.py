@@ -1,13 +1,13 @@
 """The channeliser survey's definition (include/jaero_hip.h, "survey of a channeliser's capture") in numpy, literally, streaming, on top of
-`chan_rates_oracle.ChanRatesOracle`: the Welch spectrum S with the Hann window applied in the frequency domain, the per-channel levels E_c
+`chan_oracle.ChanOracle`: the Welch spectrum S with the Hann window applied in the frequency domain, the per-channel levels E_c
 with their block counts n_c, reset, and the restart of a channel whose tune word a retune changes.  The GPU kernels (k_chan_psd,
 k_chan_level) are tested against this (tests/test_gpu_chan_survey.py); this against itself and the time-domain Hann on the CPU
 (tests/test_chan_survey_host.py)."""
 import numpy as np
 
-import chan_rates_oracle as RO
+import chan_oracle as CO
 
-N, HP = RO.N, RO.HP
+N, HP = CO.N, CO.HP
 
 
 def hann_spectrum_time(s):
@@ -22,8 +22,8 @@ def normalise_psd(S, nblocks):
     return S / (nblocks * float(N) * N * 0.375)
 
 
-class ChanSurveyOracle(RO.ChanRatesOracle):
-    """write() is ChanRatesOracle's (the unrounded output) and surveys the blocks it completes; survey() only surveys (for tests that
+class ChanSurveyOracle(CO.ChanOracle):
+    """write() is ChanOracle's (the unrounded output) and surveys the blocks it completes; survey() only surveys (for tests that
     need no output).  Use one of the two on an instance: each advances its own copy of the input history."""
 
     def __init__(self, decim, channels, taps, psd=True, levels=True):
@@ -62,7 +62,7 @@ class ChanSurveyOracle(RO.ChanRatesOracle):
                 self.nblocks += 1
             if self.want_levels:
                 for c, (tune, audio, _gain) in enumerate(self.channels):
-                    b = RO.words(tune, audio, self.D)[0]
+                    b = CO.words(tune, audio, self.D)[0]
                     Y = X[(b + q) % N] * self.G[q % N] / N
                     self.E[c] += np.sum(Y.real ** 2 + Y.imag ** 2)
                     self.n[c] += 1

@@ -9,7 +9,7 @@ broadcast."""
 import numpy as np
 import pytest
 
-N = 16384
+from chan_cases import N, model_item
 
 
 class Shape:
@@ -28,40 +28,6 @@ class Shape:
 
     def xaddr(self, k1, n2):
         return k1 * self.ROW + n2
-
-
-def model_item(S, X, G, b):
-    """One (channel, block) item as the kernel computes it: returns (ml[T, P2 / 2], w[T, P2 / 2]): output index r - Mo and value held by
-    thread u in its slot jj."""
-    M, R1, R2, P2, T = S.M, S.R1, S.R2, S.P2, S.T
-    u = np.arange(T)
-    # gather + pass 1: thread n2 = u holds k = R2 n1 + u; planes swapped (inverse = forward of the swapped planes)
-    a = np.zeros((T, R1), complex)
-    for n1 in range(R1):
-        k = R2 * n1 + u
-        q = np.where(k < M // 2, k, k - M)
-        Y = X[(b + q) % N] * G[q % N] / N
-        a[:, n1] = Y.imag + 1j * Y.real
-    A = np.fft.fft(a, axis=1) * np.exp(-2j * np.pi * u / M)[:, None] ** np.arange(R1)[None, :]
-    # exchange
-    L = np.full(S.XCH, np.nan, complex)
-    for k in range(R1):
-        L[S.xaddr(k, u)] = A[:, k]
-    k1, h = u % R1, u // R1
-    if S.SPLIT == 2:
-        e = np.stack([L[S.xaddr(k1, n)] + np.where(h, -1.0, 1.0) * L[S.xaddr(k1, n + P2)] for n in range(P2)], axis=1)
-        e = e * np.where(h, np.exp(-2j * np.pi / 32), 1.0)[:, None] ** np.arange(P2)[None, :]
-    else:
-        e = np.stack([L[S.xaddr(k1, n)] for n in range(P2)], axis=1)
-    E = np.fft.fft(e, axis=1)
-    ml = np.zeros((T, P2 // 2), int)
-    w = np.zeros((T, P2 // 2), complex)
-    for jj in range(P2 // 2):
-        k2 = 2 * (jj + P2 // 2) + h if S.SPLIT == 2 else jj + P2 // 2 + 0 * h
-        ml[:, jj] = k1 + R1 * (k2 - R2 // 2)
-        s = E[:, jj + P2 // 2]
-        w[:, jj] = s.imag + 1j * s.real
-    return ml, w
 
 
 @pytest.mark.parametrize("D", [16, 32, 64])

@@ -1,12 +1,13 @@
 """CPU: the channeliser's C ABI without a device (exports, refusals, no CPU fallback), the integer frequency arithmetic of the Python
-helpers against the oracle's, and the oracle against itself: the block (fast-convolution) form the kernels implement against the ideal
-mix -> FIR -> decimate form, and fed in pieces against fed at once."""
+helpers against the oracle's, and the oracle against itself at every total decimation 16 .. 256: the block (fast-convolution) form the
+kernels implement against the ideal mix -> FIR -> decimate form, and fed in pieces against fed at once."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import chan_oracle as CO
+from chan_cases import FS_OUT, boundary_words, tone_capture
 from jaero_amd import capi, channeliser as CH
 
 CHAN_SYMBOLS = [s for s in capi.EXPORTS if s.startswith("jaero_chan_")]
@@ -93,17 +94,9 @@ def test_tune_word_round_trip(fs):
     assert CH.word_hz(1 << 31, fs) == -fs / 2 and CH.word_hz((1 << 32) - 1, fs) == -fs / 2 ** 32 and CH.word_hz(0, fs) == 0.0
 
 
-def _boundary_words():
-    ws = {0, 1, (1 << 31) - 1, 1 << 31, (1 << 31) + 1, (1 << 32) - 1, (1 << 32) - 2}
-    for b in (0, 1, -1, 5, -5, 8191, -8191, 8192 - 1, -8192, 4096, -4097):
-        for d in (-(1 << 17) - 1, -(1 << 17), -(1 << 17) + 1, -1, 0, 1, (1 << 17) - 1, 1 << 17, (1 << 17) + 1):
-            ws.add((b * (1 << 18) + d) % (1 << 32))
-    return sorted(ws)
-
-
-@pytest.mark.parametrize("decim", [16, 32, 64])
+@pytest.mark.parametrize("decim", CO.DECIMS)
 def test_channel_words_agree_with_the_oracle_at_every_boundary(decim):
-    for t in _boundary_words():
+    for t in boundary_words():
         for audio in (0, 715827883, (1 << 32) - 1, 1 << 31):
             got = CH.channel_words(t, audio, decim)
             assert got == CO.words(t, audio, decim), (t, audio)
@@ -125,35 +118,27 @@ def test_design_taps():
 
 
 # ---------------------------------------------------------------------------------------------- oracle against itself
-def _capture(decim, fc, nhops, rng):
-    """The input the definition was checked on: a tone of 3000 LSB 1.5 kHz above the centre, one of 9000 LSB 40 kHz above it (outside the
-    +-24 kHz the channel keeps), noise of 300 LSB per rail; rounded to integers."""
-    fs = 48000.0 * decim
-    n = CO.HP * nhops
-    t = np.arange(n)
-    x = (3000 * np.exp(2j * np.pi * (((fc + 1500.0) / fs * t) % 1.0)) + 9000 * np.exp(2j * np.pi * (((fc + 40000.0) / fs * t) % 1.0))
-         + 300 * (rng.normal(size=n) + 1j * rng.normal(size=n)))
-    return np.rint(x.real) + 1j * np.rint(x.imag)
-
-
-@pytest.mark.parametrize("decim", [16, 32, 64])
+@pytest.mark.parametrize("decim", CO.DECIMS)
 @pytest.mark.parametrize("centre", ["off_grid", "negative", "wrap_high", "wrap_low"])
 def test_block_form_equals_direct_form(decim, centre):
-    """max |block - direct| <= 1e-3 output LSB at the default taps (measured: at most 5.2e-6; the bound keeps the two forms on the same int16
-    in all but ~0.2 % of samples and is 200 x what was measured).  wrap_*: centres at +-(Fs_in / 2 - 10 kHz), whose +-24 kHz bin run
-    wraps at N."""
-    fs = 48000.0 * decim
-    fc = {"off_grid": 33.3, "negative": -123456.7, "wrap_high": fs / 2 - 10000.0, "wrap_low": -(fs / 2 - 10000.0)}[centre]
+    """max |block - direct| <= 1e-3 output LSB at the default taps of the output rate, at every decimation (measured: at most 5.2e-6 at
+    48 kHz, 2.9e-5 at D = 128 and 1.3e-4 at D = 256; the bound keeps the two forms on the same int16 in all but ~0.2 % of samples).
+    wrap_*: centres at +-(Fs_in / 2 - fs_out 10 / 48), 10 kHz from the edge at 48 kHz, whose run of bins wraps at N."""
+    fs_out = FS_OUT[decim]
+    fs = fs_out * decim
+    edge = fs / 2 - fs_out * 10 / 48
+    fc = {"off_grid": 33.3, "negative": -123456.7, "wrap_high": edge, "wrap_low": -edge}[centre]
     rng = np.random.default_rng(decim)
-    x = _capture(decim, CH.word_hz(CH.tune_word(fc, fs), fs), 6, rng)
-    tune, audio = CH.tune_word(fc, fs), CH.tune_word(8000.0, 48000.0)
+    nhops = 6
+    x = tone_capture(decim, fs_out, CH.word_hz(CH.tune_word(fc, fs), fs), nhops, rng)
+    tune, audio = CH.tune_word(fc, fs), CH.tune_word(fs_out / 6, fs_out)
     b, _, _ = CO.words(tune, audio, decim)
     M = CO.N // decim
     if centre.startswith("wrap"):
         assert b - M // 2 < -CO.N // 2 or b + M // 2 > CO.N // 2  # the run of bins crosses the seam of the spectrum
-    h = CH.design_taps(decim)
+    h = CH.design_taps(decim, fs_out=fs_out)
     yb = CO.block_form(x, decim, [(tune, audio, 2.0)], h)[0]
-    assert len(yb) == 6 * (M // 2)
+    assert len(yb) == nhops * (M // 2)
     yd = CO.direct_form(x, decim, tune, audio, 2.0, h, len(yb))
     err = np.abs(yb - yd).max()
     print(f"D={decim} {centre}: max |block - direct| = {err:.3g} LSB, rms out {yb.std():.1f}")
@@ -161,12 +146,13 @@ def test_block_form_equals_direct_form(decim, centre):
     assert err <= 1e-3
 
 
-def test_oracle_in_pieces_equals_oracle_at_once():
+@pytest.mark.parametrize("decim,audio_hz,gain", [(64, 8000.0, 0.04), (256, 2000.0, 0.1)])
+def test_oracle_in_pieces_equals_oracle_at_once(decim, audio_hz, gain):
     rng = np.random.default_rng(5)
-    decim = 64
+    fs_out = FS_OUT[decim]
     x = rng.integers(-32768, 32768, 5 * CO.HP + 77) + 1j * rng.integers(-32768, 32768, 5 * CO.HP + 77)
-    chans = [(CH.tune_word(-300000.3, 48000.0 * decim), CH.tune_word(8000.0, 48000.0), 0.04), (12345678, 999, 1.0)]
-    h = CH.design_taps(decim, ntaps=2049, beta=10.0)
+    chans = [(CH.tune_word(-300000.3, fs_out * decim), CH.tune_word(audio_hz, fs_out), gain), (12345678, 999, 1.0)]
+    h = CH.design_taps(decim, ntaps=2049, beta=10.0, fs_out=fs_out)
     whole = CO.block_form(x, decim, chans, h)
     o = CO.ChanOracle(decim, chans, h)
     parts, pos, total = [], 0, 0

@@ -8,7 +8,7 @@ Every thread ends with 4 outputs; the item's Mo int16 are T 8-byte words of the 
 import numpy as np
 import pytest
 
-from test_chan_fft_model import N, model_item
+from chan_cases import N, model_item
 
 
 class Shape:
@@ -31,7 +31,7 @@ class Shape:
 
 
 def model_item_small(S, X, G, b):
-    """tests/test_chan_fft_model.py's model_item with the split step's twiddle W_R2^(h n) instead of its literal W_32^(h n)."""
+    """chan_cases.model_item with the split step's twiddle W_R2^(h n) instead of its literal W_32^(h n)."""
     if S.SPLIT == 1:
         return model_item(S, X, G, b)
     M, R1, R2, P2, T = S.M, S.R1, S.R2, S.P2, S.T

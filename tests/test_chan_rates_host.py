@@ -1,14 +1,12 @@
 """CPU: the channeliser at total decimations 128 / 256 and output rates 24 / 12 kHz (jaero_chan2_create) without a device: the export, the
-refusals, no CPU fallback, the integer frequency arithmetic and the default taps of the Python helpers, and the oracle at the new
-decimations against itself (block form against mix -> FIR -> decimate, fed in pieces against fed at once)."""
+refusals, no CPU fallback and the default taps of the Python helpers.  The integer frequency arithmetic and the oracle against itself at
+these decimations are cases of tests/test_chan_host.py's tests."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import chan_rates_oracle as RO
 from jaero_amd import capi, channeliser as CH
-from test_chan_host import _boundary_words
 
 
 def test_library_exports_the_new_entry():
@@ -75,19 +73,7 @@ def test_python_wrapper_passes_the_rate_on():
     assert e.value.code == capi.E_INVAL and "decim" in str(e.value)
 
 
-# ---------------------------------------------------------------------------------------------- words
-@pytest.mark.parametrize("decim", [128, 256])
-def test_channel_words_agree_with_the_oracle_at_every_boundary(decim):
-    for t in _boundary_words():
-        for audio in (0, 715827883, (1 << 32) - 1, 1 << 31):
-            got = CH.channel_words(t, audio, decim)
-            assert got == RO.words(t, audio, decim), (t, audio)
-            b, rho, w = got
-            ts = t - (1 << 32) if t >= 1 << 31 else t
-            assert b * (1 << 18) + rho == ts and -(1 << 17) <= rho < (1 << 17) and -8192 <= b <= 8192 and 0 <= w < 1 << 32
-            assert (b * (1 << 18) * decim + audio - w) % (1 << 32) == (ts * decim) % (1 << 32)
-
-
+# ---------------------------------------------------------------------------------------------- taps
 @pytest.mark.parametrize("decim,fs_out", [(64, 12000.0), (128, 12000.0), (256, 12000.0), (32, 24000.0), (128, 24000.0)])
 def test_default_taps(decim, fs_out):
     h = CH.design_taps(decim, fs_out=fs_out)
@@ -108,59 +94,3 @@ def test_default_taps_at_48_khz_are_unchanged():
     assert np.array_equal(CH.design_taps(32), old)
     assert np.array_equal(CH.design_taps(32, 9000.0), old) and np.array_equal(CH.design_taps(32, fs_out=48000.0), old)
     assert CH.design_taps(256, ntaps=1, fs_out=12000.0).tolist() == [1.0]
-
-
-# ---------------------------------------------------------------------------------------------- oracle against itself
-def _capture(decim, fs_out, fc, nhops, rng):
-    """tests/test_chan_host.py's input scaled to the output rate: a tone of 3000 LSB fs_out / 32 above the centre, one of 9000 LSB
-    fs_out 40 / 48 above it (outside the +-fs_out / 2 the channel keeps), noise of 300 LSB per rail; rounded to integers."""
-    fs = fs_out * decim
-    n = RO.HP * nhops
-    t = np.arange(n)
-    x = (3000 * np.exp(2j * np.pi * (((fc + fs_out / 32) / fs * t) % 1.0)) + 9000 * np.exp(2j * np.pi * (((fc + fs_out * 40 / 48) / fs * t) % 1.0))
-         + 300 * (rng.normal(size=n) + 1j * rng.normal(size=n)))
-    return np.rint(x.real) + 1j * np.rint(x.imag)
-
-
-@pytest.mark.parametrize("decim,fs_out", [(128, 24000.0), (256, 12000.0)])
-@pytest.mark.parametrize("centre", ["off_grid", "negative", "wrap_high", "wrap_low"])
-def test_block_form_equals_direct_form(decim, fs_out, centre):
-    """max |block - direct| <= 1e-3 output LSB at the default taps, the bound of the 48 kHz test (measured: at most 2.9e-5 at D = 128 and
-    1.3e-4 at D = 256).  wrap_*: centres at +-(Fs_in / 2 - fs_out 10 / 48), whose run of bins wraps at N."""
-    fs = fs_out * decim
-    edge = fs / 2 - fs_out * 10 / 48
-    fc = {"off_grid": 33.3, "negative": -123456.7, "wrap_high": edge, "wrap_low": -edge}[centre]
-    rng = np.random.default_rng(decim)
-    nhops = 6
-    x = _capture(decim, fs_out, CH.word_hz(CH.tune_word(fc, fs), fs), nhops, rng)
-    tune, audio = CH.tune_word(fc, fs), CH.tune_word(fs_out / 6, fs_out)
-    b, _, _ = RO.words(tune, audio, decim)
-    M = RO.N // decim
-    if centre.startswith("wrap"):
-        assert b - M // 2 < -RO.N // 2 or b + M // 2 > RO.N // 2  # the run of bins crosses the seam of the spectrum
-    h = CH.design_taps(decim, fs_out=fs_out)
-    yb = RO.block_form(x, decim, [(tune, audio, 2.0)], h)[0]
-    assert len(yb) == nhops * (M // 2)
-    yd = RO.direct_form(x, decim, tune, audio, 2.0, h, len(yb))
-    err = np.abs(yb - yd).max()
-    print(f"D={decim} {centre}: max |block - direct| = {err:.3g} LSB, rms out {yb.std():.1f}")
-    assert yb.std() > 100.0
-    assert err <= 1e-3
-
-
-def test_oracle_in_pieces_equals_oracle_at_once():
-    rng = np.random.default_rng(5)
-    decim, fs_out = 256, 12000.0
-    x = rng.integers(-32768, 32768, 5 * RO.HP + 77) + 1j * rng.integers(-32768, 32768, 5 * RO.HP + 77)
-    chans = [(CH.tune_word(-300000.3, fs_out * decim), CH.tune_word(2000.0, fs_out), 0.1), (12345678, 999, 1.0)]
-    h = CH.design_taps(decim, ntaps=2049, beta=10.0, fs_out=fs_out)
-    whole = RO.block_form(x, decim, chans, h)
-    o = RO.ChanRatesOracle(decim, chans, h)
-    parts, pos, total = [], 0, 0
-    for n in (1, 8191, 8193, 0, 3 * 8192 + 5, 77, 8000, 10 ** 6):
-        parts.append(o.write(x[pos:pos + n]))
-        pos = min(len(x), pos + n)
-        total += parts[-1].shape[1]
-        assert total == (pos // RO.HP) * o.Mo
-    got = np.concatenate(parts, axis=1)
-    assert got.shape == whole.shape and np.array_equal(got, whole)

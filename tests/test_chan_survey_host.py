@@ -6,18 +6,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import chan_rates_oracle as RO
+import chan_oracle as CO
 import chan_survey_oracle as SO
-from jaero_amd import aerol_frames as AF
+from chan_cases import AUDIO, CHAIN_CENTRES, pchannel_chain_capture
 from jaero_amd import capi, channeliser as CH
 from jaero_amd import signalgen as G
 
 N, HP = SO.N, SO.HP
-AUDIO = 715827883
 SURVEY_SYMBOLS = ("jaero_survey_enable", "jaero_survey_reset", "jaero_survey_read_psd", "jaero_survey_read_levels",
                   "jaero_survey_profile_read", "jaero_chan2_retune_all")
-CHAIN_CENTRES = [-150000.0, -137500.0, -125000.0, 200003.0]
-CHAIN_AMPS = [1.0, 1.5, 2.0, 2.5]
 
 
 def test_exports_and_refusals_without_a_device():
@@ -42,21 +39,9 @@ def test_exports_and_refusals_without_a_device():
         assert callable(getattr(CH.Channeliser, name))
 
 
-def chain_capture():
-    """tests/test_gpu_chan.py's chain capture: D = 16, four 10.5 kbps P channels of 8 frames, Eb/N0 13 dB on the weakest, 0.1 of full scale."""
-    fb, nfr, decim = 10500, 8, 16
-    bits = []
-    for c in range(4):
-        b, _ = AF.p_channel_bits(AF.random_payloads(nfr, fb, seed=50 + c), fb)
-        bits.append(np.concatenate([b, np.zeros(64, np.uint8)]))
-    n48 = int(len(bits[0]) / 2 * 48000 / 5250) + 2000
-    n = (n48 * decim // HP) * HP
-    return G.wideband_oqpsk(bits, CHAIN_CENTRES, CHAIN_AMPS, decim, fb=fb, ebno_db=13.0, rms=0.1, seed=7, nsamples=n)
-
-
 @pytest.fixture(scope="module")
 def chain_iq():
-    return chain_capture()
+    return pchannel_chain_capture()[1]
 
 
 def white(n, seed, amp=8000.0):
@@ -127,7 +112,7 @@ def test_level_predicts_the_output_rms_chain_capture(chain_iq):
     """The first 48 hops at D = 16; measured 0.9945 .. 0.9957 (the shortfall is block 0's half window of zeros)."""
     fs = 48000.0 * 16
     chans = [(CH.tune_word(f, fs), AUDIO, 1.0) for f in CHAIN_CENTRES]
-    ratio = level_against_output(16, chans, CH.design_taps(16), RO.as_complex(chain_iq[:48 * HP]))
+    ratio = level_against_output(16, chans, CH.design_taps(16), CO.as_complex(chain_iq[:48 * HP]))
     assert np.all(np.abs(ratio - 1.0) <= 0.03)
 
 
@@ -140,7 +125,7 @@ def test_level_predicts_the_output_rms_msk_capture_d256():
     bits = [rng.integers(0, 2, size=int(n / (fs / fb)) + 20, dtype=np.uint8) for _ in centres]
     iq = G.wideband_msk(bits, centres, amps, fs, fb=fb, ebno_db=13.0, rms=0.1, seed=7, nsamples=n)
     chans = [(CH.tune_word(f, fs), CH.tune_word(1000.0, fs_out), 1.0) for f in centres]
-    ratio = level_against_output(decim, chans, CH.design_taps(decim, fs_out=fs_out), RO.as_complex(iq))
+    ratio = level_against_output(decim, chans, CH.design_taps(decim, fs_out=fs_out), CO.as_complex(iq))
     assert np.all(np.abs(ratio - 1.0) <= 0.03)
 
 
@@ -149,7 +134,7 @@ def test_find_carriers_on_the_chain_capture(chain_iq):
     the demodulator's own acquisition takes over)."""
     fs = 48000.0 * 16
     o = SO.ChanSurveyOracle(16, [(0, AUDIO, 1.0)], np.ones(1), levels=False)
-    o.survey(RO.as_complex(chain_iq[:16 * HP]))
+    o.survey(CO.as_complex(chain_iq[:16 * HP]))
     assert o.nblocks == 16
     found = CH.find_carriers(o.psd(), fs, 10500.0)
     print("found", np.round(found, 1), "errors", np.round(np.array(found) - np.array(sorted(CHAIN_CENTRES)), 1) if len(found) == 4 else None)

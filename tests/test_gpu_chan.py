@@ -1,79 +1,17 @@
 """GPU (-m gpu): the wideband I/Q channeliser (jaero_chan_*, jaero_amd/csrc/k_chan.h) against its definition (tests/chan_oracle.py).
 
-The rule every comparison of int16 output uses (`assert_rule`): got == rint(y*), or |got - rint(y*)| == 1 AND the oracle's unrounded y* lies
-within tau = 1e-7 max(1, g) LSB of a half-integer.  tau is 10^4 x the round-off measured between two fp64 summation orders of the definition
-on the CPU (1.0e-11 LSB at gain 1); it says WHERE a difference may occur, so no share of samples is written off.  Every compared channel
-must have an output RMS above 100 LSB, so that nothing passes empty."""
+Every comparison of int16 output uses `chan_cases.assert_rule`: got == rint(y*), or off by one where the oracle's unrounded y* lies within
+tau = 1e-7 max(1, g) LSB of a half-integer; and an output RMS above 100 LSB.  The inputs and the twelve channels are tests/chan_cases.py's."""
 import numpy as np
 import pytest
 
 import chan_oracle as CO
+from chan_cases import AUDIO, CH, CHAIN_AMPS, CHAIN_CENTRES, assert_rule, channel_set, pchannel_chain_capture, synthetic_capture, white_full_scale
 from conftest import assert_soft_bytes
-from jaero_amd import aerol_frames as AF
-from jaero_amd import signalgen as G
 
 pytestmark = pytest.mark.gpu
 
 HP = CO.HP
-AUDIO = 715827883  # round(8000 / 48000 * 2^32)
-
-
-@pytest.fixture(scope="module")
-def CH():
-    from jaero_amd import capi
-    from jaero_amd import channeliser
-
-    capi.lib()
-    return channeliser
-
-
-def assert_rule(got, ystar, gain, where=""):
-    got = np.asarray(got).astype(np.int64)
-    ref = CO.to_int16(ystar).astype(np.int64)
-    assert got.shape == ref.shape, (where, got.shape, ref.shape)
-    d = np.abs(got - ref)
-    assert d.max(initial=0) <= 1, (where, "differs by more than one", int(d.max()))
-    tau = 1e-7 * max(1.0, gain)
-    off = np.nonzero(d)[0]
-    edge = np.abs(ystar[off] - (np.floor(ystar[off]) + 0.5))  # distance to the half-integer between the two candidates
-    print(f"{where}: {got.size} samples, {off.size} differ by one, rms {got.astype(float).std():.1f}")
-    assert (edge <= tau).all(), (where, "a sample differs away from a rounding edge", float(edge.max(initial=0)), int(off.size))
-    assert got.astype(float).std() > 100.0, (where, "output RMS below 100 LSB")
-
-
-def white_full_scale(n, seed):
-    """White I/Q whose every sample is within 1 % of full scale (either sign, -32768 included): the strongest input there is, so that the
-    channel of gain 0.04 keeps an RMS above 100 LSB behind the narrowest filter at D = 64 (uniform white would leave it 58)."""
-    rng = np.random.default_rng(seed)
-    k = rng.integers(0, 256, size=(n, 2))
-    s = rng.integers(0, 2, size=(n, 2))
-    return np.where(s == 1, 32767 - k, -32768 + k).astype(np.int16)
-
-
-def synthetic_capture(decim, nhops, seed):
-    """Three OQPSK channels (amplitudes 1, 1, 3; Eb/N0 20 dB on the weak ones) at a quarter of full scale; returns (iq, centres)."""
-    fs = 48000.0 * decim
-    centres = [-123456.7, 33.3, fs / 2 - 10000.0]
-    rng = np.random.default_rng(seed)
-    n = HP * nhops
-    bits = [rng.integers(0, 2, size=2 * (int(n / (fs / 5250.0)) + 20), dtype=np.uint8) for _ in centres]
-    return G.wideband_oqpsk(bits, centres, [1.0, 1.0, 3.0], decim, ebno_db=20.0, rms=0.25, seed=seed, nsamples=n), centres
-
-
-def channel_set(CHm, decim, strong_hz):
-    """12 channels: centres off grid, negative, at +-(Fs_in / 2 - 10 kHz) (the +-24 kHz run of bins wraps at N), two on one bin with different
-    words; gains 1 except channel 2 (0.04, on `strong_hz`) and channel 3 (set by the caller so that about 1 % of its samples clip)."""
-    fs = 48000.0 * decim
-    hz = [33.3, -123456.7, strong_hz, strong_hz, fs / 2 - 10000.0, -(fs / 2 - 10000.0), 200003.0, -0.01, 7 * fs / CO.N + 3.0, 7 * fs / CO.N - 11.0,
-          -fs / 2 + 1.0, fs / 2 - 1.0]
-    chans = [[CHm.tune_word(f, fs), AUDIO, 1.0] for f in hz]
-    assert CO.words(chans[8][0], AUDIO, decim)[0] == CO.words(chans[9][0], AUDIO, decim)[0] == 7 and chans[8][0] != chans[9][0]
-    for i in (4, 5, 10, 11):
-        b = CO.words(chans[i][0], AUDIO, decim)[0]
-        assert abs(b) + CO.N // decim // 2 > CO.N // 2  # wraps
-    chans[6][1] = CHm.tune_word(11000.0, 48000.0)
-    chans[2][2] = 0.04
-    return chans
 
 
 @pytest.mark.parametrize("decim", [16, 32, 64])
@@ -89,7 +27,7 @@ def test_kernel_equals_definition(CH, decim, ntaps, source):
         iq, centres = synthetic_capture(decim, nhops, 200 + decim)
         strong = centres[2]
     taps = np.ones(1) if ntaps == 1 else CH.design_taps(decim, cutoff_hz=20000.0, ntaps=ntaps, beta=8.0 if ntaps == 2049 else 16.0)
-    chans = channel_set(CH, decim, strong)
+    chans = channel_set(CH, decim, strong, 0.04)
     x = CO.as_complex(iq)
     y1 = CO.block_form(x, decim, [tuple(chans[3])], taps)[0]
     chans[3][2] = 32767.5 / np.quantile(np.abs(y1), 0.99)  # 1 % of the oracle's own samples lie beyond the rails
@@ -184,27 +122,7 @@ def test_retune_mid_stream(CH):
 
 
 # ---------------------------------------------------------------------------------------------- the chain
-CHAIN_CENTRES = [-150000.0, -137500.0, -125000.0, 200003.0]
-CHAIN_AMPS = [1.0, 1.5, 2.0, 2.5]
-
-
-@pytest.fixture(scope="module")
-def chain_capture():
-    """D = 16, four 10.5 kbps P channels of 8 frames each, Eb/N0 13 dB on the weakest, 0.1 of full scale RMS."""
-    fb, nfr, decim = 10500, 8, 16
-    pays, bits = [], []
-    for c in range(4):
-        pay = AF.random_payloads(nfr, fb, seed=50 + c)
-        b, _ = AF.p_channel_bits(pay, fb)
-        pays.append(pay)
-        bits.append(np.concatenate([b, np.zeros(64, np.uint8)]))
-    n48 = int(len(bits[0]) / 2 * 48000 / 5250) + 2000
-    n = (n48 * decim // HP) * HP
-    iq, info = G.wideband_oqpsk(bits, CHAIN_CENTRES, CHAIN_AMPS, decim, fb=fb, ebno_db=13.0, rms=0.1, seed=7, nsamples=n, return_info=True)
-    return pays, iq, info
-
-
-def test_capture_to_signal_units_on_device(CH, oracle_mod, chain_capture):
+def test_capture_to_signal_units_on_device(CH, oracle_mod):
     """Channeliser.feed -> DemodulatorBank -> AeroLBank.write_from_bank, nothing through the host: every channel yields >= 52 CRC-clean
     signal units that are a contiguous, in-order run of the transmitted ones (the same chain in numpy + oracle gives 78; 52 = two whole
     frames only keeps the check from passing empty).  And a second bank handed the same device PCM gives the oracle demodulator's soft bits
@@ -215,7 +133,7 @@ def test_capture_to_signal_units_on_device(CH, oracle_mod, chain_capture):
     from jaero_amd import demodulator as B
 
     O = oracle_mod
-    pays, iq, info = chain_capture
+    pays, iq, info = pchannel_chain_capture()
     decim, fb, nch = 16, 10500, 4
     fs = 48000.0 * decim
     # the level signalgen.oqpsk produces: RMS = 0.1 of full scale; a channel's audio is the real part of amp * scale * (i + j q)

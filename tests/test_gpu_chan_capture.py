@@ -1,6 +1,6 @@
 """GPU (-m gpu): the channeliser's capture front end (jaero_chan3_*, jaero_amd/csrc/k_chan_capture.h) against its definition
 (tests/chan_capture_oracle.py): the staged stream bit for bit where no rotation is involved, within 2^-46 S X where one is, and the int16
-output by the rule of tests/test_gpu_chan.py (restated in the oracle module).
+output by `chan_cases.assert_rule`.
 
 CAP_RUN = 256 is the staging kernel's run of outputs per workgroup; write sizes are chosen around it."""
 import ctypes as C
@@ -11,24 +11,13 @@ import pytest
 import chan_capture_oracle as CC
 import chan_oracle as CO
 import chan_survey_oracle as SO
-from jaero_amd import aerol_frames as AF
-from jaero_amd import signalgen as G
+from chan_cases import AUDIO, CH, CHAIN_AMPS, CHAIN_CENTRES, assert_rule, channel_set, pchannel_chain_capture
 
 pytestmark = pytest.mark.gpu
 
 HP = CO.HP
-AUDIO = 715827883  # round(8000 / 48000 * 2^32)
 CAP_RUN = 256
 ONE = [(12345678, AUDIO, 1.0)]
-
-
-@pytest.fixture(scope="module")
-def CH():
-    from jaero_amd import capi
-    from jaero_amd import channeliser
-
-    capi.lib()
-    return channeliser
 
 
 def raw_samples(fmt, n, seed, full_scale=False):
@@ -253,28 +242,6 @@ def test_shift_within_bound(CH, decim, fs_in, fmt, shift_hz):
 
 
 # ---------------------------------------------------------------------------------------------- 4. output against the definition
-def channel_set(CHm, decim, fs_in, strong_hz):
-    """tests/test_gpu_chan.py's twelve channels: centres off grid, negative, at the edges of the occupied band, two on one bin with
-    different words; gains 1 except channel 2 (0.04, on `strong_hz`) and channel 3 (set by the caller so that about 1 % of its samples
-    clip).  The occupied band is B = min(fs_in, Fs_c): where the capture covers Fs_c the edge channels' runs of bins wrap at N as in
-    that file; where it is narrower (a capture that is raised to Fs_c) they sit on the capture's own edges, since nothing lies beyond."""
-    fs = 48000.0 * decim
-    B = min(float(fs_in), fs)
-    hz = [33.3, -123456.7, strong_hz, strong_hz, B / 2 - 10000.0, -(B / 2 - 10000.0), 200003.0, -0.01, 7 * fs / CO.N + 3.0, 7 * fs / CO.N - 11.0,
-          -B / 2 + 1.0, B / 2 - 1.0]
-    chans = [[CHm.tune_word(f, fs), AUDIO, 1.0] for f in hz]
-    assert CO.words(chans[8][0], AUDIO, decim)[0] == CO.words(chans[9][0], AUDIO, decim)[0] == 7 and chans[8][0] != chans[9][0]
-    for i in (4, 5, 10, 11):
-        b = CO.words(chans[i][0], AUDIO, decim)[0]
-        if B == fs:
-            assert abs(b) + CO.N // decim // 2 > CO.N // 2  # wraps
-        else:  # on the capture's own edge, inside the band it fills, and no run of bins wraps
-            assert abs(hz[i]) <= B / 2 < fs / 2 and abs(b) + CO.N // decim // 2 <= CO.N // 2
-    chans[6][1] = CHm.tune_word(11000.0, 48000.0)
-    chans[2][2] = 0.04
-    return chans
-
-
 OUTPUT_CASES = [(16, 1200000, "cu8"), (64, 4800000, "cs16"), (16, 600000, "cs16"), (64, 2400000, "cu8")]  # 16 / 25 twice, 32 / 25 twice
 
 
@@ -288,7 +255,7 @@ def output_case(CHm, decim, fs_in, fmt):
     raw = raw_samples(fmt, n, 100 + decim, full_scale=True)
     taps = CHm.design_taps(decim, cutoff_hz=20000.0, ntaps=8193, beta=16.0)
     rtaps = CHm.design_resampler(fs_in, fs_c, K)[0]
-    chans = channel_set(CHm, decim, fs_in, 54321.0)
+    chans = channel_set(CHm, decim, 54321.0, 0.04, fs_in=fs_in)
     z = CC.CaptureOracle(fmt, fs_in, fs_c, 0, K, rtaps).write(raw)
     y1 = CO.block_form(z, decim, [tuple(chans[3])], taps)[0]
     chans[3][2] = 32767.5 / np.quantile(np.abs(y1), 0.99)
@@ -314,7 +281,6 @@ def test_output_equals_definition(CH, decim, fs_in, fmt):
     ch.close()
     assert got.shape == ystar.shape and got.shape[1] == 6 * ch.Mo
     for c in range(len(chans)):
-        assert_rule = CC.assert_rule
         assert_rule(got[c], ystar[c], chans[c][2], f"D={decim} {fmt} {fs_in} ch{c}")
     clipped = np.mean(np.abs(got[3].astype(int)) >= 32767)
     print(f"clipping channel: {100 * clipped:.2f} % of samples at the rails")
@@ -346,24 +312,10 @@ def test_survey_on_a_capture_handle(CH):
 
 
 # ---------------------------------------------------------------------------------------------- 6. the chain, from an RTL-style capture
-CHAIN_CENTRES = [-150000.0, -137500.0, -125000.0, 200003.0]
-CHAIN_AMPS = [1.0, 1.5, 2.0, 2.5]
-
-
 def chain_capture_cu8(CHm):
-    """tests/test_gpu_chan.py's chain capture (D = 16, four 10.5 kbps P channels of 8 frames, Eb/N0 13 dB on the weakest, 0.1 of full
-    scale RMS at 768 kS/s), raised to 1.2 MS/s by the ORACLE resampler at 25 / 16 and quantised to cu8 (the inverse of the format's
-    conversion, rounded).  Returns (payloads, raw cu8 [n, 2], info)."""
-    fb, nfr, decim = 10500, 8, 16
-    pays, bits = [], []
-    for c in range(4):
-        pay = AF.random_payloads(nfr, fb, seed=50 + c)
-        b, _ = AF.p_channel_bits(pay, fb)
-        pays.append(pay)
-        bits.append(np.concatenate([b, np.zeros(64, np.uint8)]))
-    n48 = int(len(bits[0]) / 2 * 48000 / 5250) + 2000
-    n = (n48 * decim // HP) * HP
-    iq, info = G.wideband_oqpsk(bits, CHAIN_CENTRES, CHAIN_AMPS, decim, fb=fb, ebno_db=13.0, rms=0.1, seed=7, nsamples=n, return_info=True)
+    """`chan_cases.pchannel_chain_capture` (768 kS/s) raised to 1.2 MS/s by the ORACLE resampler at 25 / 16 and quantised to cu8 (the inverse
+    of the format's conversion, rounded).  Returns (payloads, raw cu8 [n, 2], info)."""
+    pays, iq, info = pchannel_chain_capture()
     h, L, Mr = CHm.design_resampler(768000, 1200000, 32)
     assert (L, Mr) == (25, 16)
     re, im = CC.Resampler(h, L, Mr, 32).write(iq[:, 0].astype(np.float64), iq[:, 1].astype(np.float64))
@@ -432,7 +384,7 @@ def test_scale_4096_channels_cu8_at_2400000(CH):
     pick = sorted({0, 1, 63, 64, nch - 1, nch - 2} | set(int(v) for v in rng.integers(0, nch, size=10)))
     ystar = CO.block_form(z, decim, [chans[c] for c in pick], CH.design_taps(decim))
     for k, c in enumerate(pick):
-        CC.assert_rule(got[c], ystar[k], 1.0, f"scale ch{c}")
+        assert_rule(got[c], ystar[k], 1.0, f"scale ch{c}")
     ch.close()
     plain = CH.Channeliser(decim, chans, max_write_iq=nhops * HP)
     plain.profile_enable(True)

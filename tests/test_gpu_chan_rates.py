@@ -1,100 +1,37 @@
 """GPU (-m gpu): the channeliser at total decimations 128 / 256 and output rates 24 / 12 kHz (jaero_chan2_create, k_chan_synth<128> / <256>)
-against its definition (tests/chan_rates_oracle.py), and the capture -> channeliser -> MSK bank chain at the reference's default MSK rates.
+against its definition (tests/chan_oracle.py), and the capture -> channeliser -> MSK bank chain at the reference's default MSK rates.
 
-The rule every comparison of int16 output uses (`assert_rule`, tests/test_gpu_chan.py's restated): got == rint(y*), or |got - rint(y*)| == 1
-AND the oracle's unrounded y* lies within tau = 1e-7 max(1, g) LSB of a half-integer.  Every compared channel must have an output RMS above
-100 LSB, so that nothing passes empty."""
+Every comparison of int16 output uses `chan_cases.assert_rule`; the inputs and the twelve channels are tests/chan_cases.py's, at the output
+rate."""
 import numpy as np
 import pytest
 
-import chan_rates_oracle as RO
+import chan_oracle as CO
+from chan_cases import AUDIO, CH, FS_OUT, assert_rule, channel_set, synthetic_capture, white_full_scale
 from conftest import assert_soft_bytes
 from jaero_amd import signalgen as G
 
 pytestmark = pytest.mark.gpu
 
-HP = RO.HP
-AUDIO = 715827883  # round(2^32 / 6): 8 kHz at 48 kHz, 4 kHz at 24 kHz, 2 kHz at 12 kHz
-FS_OUT = {128: 24000.0, 256: 12000.0}  # both cut a 3.072 MS/s capture
-
-
-@pytest.fixture(scope="module")
-def CH():
-    from jaero_amd import capi
-    from jaero_amd import channeliser
-
-    capi.lib()
-    return channeliser
-
-
-def assert_rule(got, ystar, gain, where=""):
-    got = np.asarray(got).astype(np.int64)
-    ref = RO.to_int16(ystar).astype(np.int64)
-    assert got.shape == ref.shape, (where, got.shape, ref.shape)
-    d = np.abs(got - ref)
-    assert d.max(initial=0) <= 1, (where, "differs by more than one", int(d.max()))
-    tau = 1e-7 * max(1.0, gain)
-    off = np.nonzero(d)[0]
-    edge = np.abs(ystar[off] - (np.floor(ystar[off]) + 0.5))  # distance to the half-integer between the two candidates
-    print(f"{where}: {got.size} samples, {off.size} differ by one, rms {got.astype(float).std():.1f}")
-    assert (edge <= tau).all(), (where, "a sample differs away from a rounding edge", float(edge.max(initial=0)), int(off.size))
-    assert got.astype(float).std() > 100.0, (where, "output RMS below 100 LSB")
-
-
-def white_full_scale(n, seed):
-    """White I/Q whose every sample is within 1 % of full scale (either sign, -32768 included): the strongest input there is."""
-    rng = np.random.default_rng(seed)
-    k = rng.integers(0, 256, size=(n, 2))
-    s = rng.integers(0, 2, size=(n, 2))
-    return np.where(s == 1, 32767 - k, -32768 + k).astype(np.int16)
-
-
-def msk_capture(decim, nhops, seed):
-    """Three MSK channels (fb = fs_out / 20; amplitudes 1, 1, 3; Eb/N0 20 dB on the weak ones) at a quarter of full scale; returns (iq, centres)."""
-    fs_out = FS_OUT[decim]
-    fs, fb = fs_out * decim, fs_out / 20.0
-    centres = [-123456.7, 33.3, fs / 2 - fs_out * 10 / 48]
-    rng = np.random.default_rng(seed)
-    n = HP * nhops
-    bits = [rng.integers(0, 2, size=int(n / (fs / fb)) + 20, dtype=np.uint8) for _ in centres]
-    return G.wideband_msk(bits, centres, [1.0, 1.0, 3.0], fs, fb=fb, ebno_db=20.0, rms=0.25, seed=seed, nsamples=n), centres
-
-
-def channel_set(CHm, decim, strong_hz):
-    """tests/test_gpu_chan.py's 12 channels at the output rate: centres off grid, negative, at +-(Fs_in / 2 - fs_out 10 / 48) and
-    +-(Fs_in / 2 - 1) (the run of bins wraps at N), two on one bin with different words; gains 1 except channel 2 (0.1, on `strong_hz`)
-    and channel 3 (set by the caller so that about 1 % of its samples clip)."""
-    fs_out = FS_OUT[decim]
-    fs, r = fs_out * decim, fs_out / 48000.0
-    edge = fs / 2 - fs_out * 10 / 48
-    hz = [33.3, -123456.7, strong_hz, strong_hz, edge, -edge, 200003.0, -0.01, 7 * fs / RO.N + 3.0 * r, 7 * fs / RO.N - 11.0 * r,
-          -fs / 2 + 1.0, fs / 2 - 1.0]
-    chans = [[CHm.tune_word(f, fs), AUDIO, 1.0] for f in hz]
-    assert RO.words(chans[8][0], AUDIO, decim)[0] == RO.words(chans[9][0], AUDIO, decim)[0] == 7 and chans[8][0] != chans[9][0]
-    for i in (4, 5, 10, 11):
-        b = RO.words(chans[i][0], AUDIO, decim)[0]
-        assert abs(b) + RO.N // decim // 2 > RO.N // 2  # wraps
-    chans[6][1] = CHm.tune_word(11000.0 * r, fs_out)
-    chans[2][2] = 0.1
-    return chans
+HP = CO.HP
 
 
 def definition_case(CHm, decim, ntaps, source):
     """(iq, taps, channels, y*) of one case of test_kernel_equals_definition: 768 samples per channel."""
     fs_out = FS_OUT[decim]
-    nhops = 768 // (RO.N // decim // 2)
+    nhops = 768 // (CO.N // decim // 2)
     if source == "white":
         iq, strong = white_full_scale(nhops * HP, 100 + decim), 54321.0
     else:
-        iq, centres = msk_capture(decim, nhops, 200 + decim)
+        iq, centres = synthetic_capture(decim, nhops, 200 + decim)
         strong = centres[2]
     taps = np.ones(1) if ntaps == 1 else CHm.design_taps(decim, cutoff_hz=fs_out * 5 / 12, ntaps=ntaps, beta=8.0 if ntaps == 2049 else 16.0,
                                                          fs_out=fs_out)
-    chans = channel_set(CHm, decim, strong)
-    x = RO.as_complex(iq)
-    y1 = RO.block_form(x, decim, [tuple(chans[3])], taps)[0]
+    chans = channel_set(CHm, decim, strong, 0.1)
+    x = CO.as_complex(iq)
+    y1 = CO.block_form(x, decim, [tuple(chans[3])], taps)[0]
     chans[3][2] = 32767.5 / np.quantile(np.abs(y1), 0.99)  # 1 % of the oracle's own samples lie beyond the rails
-    ystar = RO.block_form(x, decim, [tuple(c) for c in chans], taps)
+    ystar = CO.block_form(x, decim, [tuple(c) for c in chans], taps)
     return iq, taps, chans, ystar, nhops
 
 
@@ -107,7 +44,7 @@ def test_kernel_equals_definition(CH, decim, ntaps, source):
     iq, taps, chans, ystar, nhops = definition_case(CH, decim, ntaps, source)
     assert nhops == {128: 12, 256: 24}[decim]
     ch = CH.Channeliser(decim, chans, taps=taps, max_write_iq=nhops * HP, fs_out=FS_OUT[decim])
-    assert ch.fs_out == FS_OUT[decim] and ch.Mo == RO.N // decim // 2
+    assert ch.fs_out == FS_OUT[decim] and ch.Mo == CO.N // decim // 2
     assert ch.write(iq) == nhops * ch.Mo == 768
     got = ch.read_pcm()
     ptr, n = ch.pcm_view()
@@ -170,13 +107,13 @@ def test_retune_mid_stream(CH):
     fs = fs_out * decim
     nhops = 12
     iq = white_full_scale(nhops * HP, 7)
-    x = RO.as_complex(iq)
+    x = CO.as_complex(iq)
     taps = CH.design_taps(decim, cutoff_hz=fs_out * 5 / 12, fs_out=fs_out)
     chans = [(CH.tune_word(-50000.0, fs), AUDIO, 1.0), (CH.tune_word(123456.7, fs), AUDIO, 1.0), (CH.tune_word(123460.0, fs), AUDIO, 0.5)]
     new = (CH.tune_word(-400000.3, fs), CH.tune_word(1250.0, fs_out), 0.25)
     plain = CH.Channeliser(decim, chans, taps=taps, max_write_iq=8 * HP, fs_out=fs_out)
     ch = CH.Channeliser(decim, chans, taps=taps, max_write_iq=8 * HP, fs_out=fs_out)
-    o = RO.ChanRatesOracle(decim, chans, taps)
+    o = CO.ChanOracle(decim, chans, taps)
     cut = 6 * HP + 100  # the write ends inside a hop: the new words hold from block 6 on, whose input began under the old ones
     outs, refs, base = [], [], []
     for a, b in ((0, cut), (cut, nhops * HP)):
@@ -222,7 +159,7 @@ def test_the_rate_is_a_label(CH):
 
     mw = 9 * HP
     mk = lambda rate: CH.Channeliser(decim, chans, taps=taps, max_write_iq=mw, fs_out=rate)
-    bank = lambda rate: B.DemodulatorBank(B.MskSettings(fb=600.0, lockingbw=900.0, Fs=rate), nch, max_write_samples=(mw // HP + 1) * (RO.N // decim // 2),
+    bank = lambda rate: B.DemodulatorBank(B.MskSettings(fb=600.0, lockingbw=900.0, Fs=rate), nch, max_write_samples=(mw // HP + 1) * (CO.N // decim // 2),
                                           softbit_capacity=4096)
     c12, twin, c48 = mk(12000.0), mk(12000.0), mk(48000.0)
     b12, btwin, b48 = bank(12000.0), bank(12000.0), bank(48000.0)
@@ -250,18 +187,18 @@ def test_the_rate_is_a_label(CH):
 
 
 # ---------------------------------------------------------------------------------------------- the chains
-CHAIN_CENTRES = [-150000.0, 200003.0]
-CHAIN_AMPS = [1.0, 2.0]
+MSK_CHAIN_CENTRES = [-150000.0, 200003.0]
+MSK_CHAIN_AMPS = [1.0, 2.0]
 
 
-def chain_capture(fb, fs_out, decim, seconds):
+def msk_chain_capture(fb, fs_out, decim, seconds):
     """Two continuous MSK channels of amplitudes 1 and 2, Eb/N0 13 dB on the weaker, 0.1 of full scale RMS; whole hops, at most 8 M samples."""
     fs = fs_out * decim
     n = int(seconds * fs) // HP * HP
     assert n <= 8_000_000
     rng = np.random.default_rng(int(fb + decim))
-    bits = [rng.integers(0, 2, size=int(n / (fs / fb)) + 20, dtype=np.uint8) for _ in CHAIN_CENTRES]
-    iq, info = G.wideband_msk(bits, CHAIN_CENTRES, CHAIN_AMPS, fs, fb=fb, ebno_db=13.0, rms=0.1, seed=7, nsamples=n, return_info=True)
+    bits = [rng.integers(0, 2, size=int(n / (fs / fb)) + 20, dtype=np.uint8) for _ in MSK_CHAIN_CENTRES]
+    iq, info = G.wideband_msk(bits, MSK_CHAIN_CENTRES, MSK_CHAIN_AMPS, fs, fb=fb, ebno_db=13.0, rms=0.1, seed=7, nsamples=n, return_info=True)
     return bits, iq, info
 
 
@@ -269,8 +206,8 @@ def chain_channels(CHm, fb, fs_out, decim, info):
     fs = fs_out * decim
     audio_hz = 1000.0 if fb == 600 else 2000.0
     # a channel's audio is the real part of amp * scale * e^(j phase): RMS amp * scale * sqrt(p_unit / 2); brought to 0.1 of full scale
-    gains = [0.1 * 32768.0 / (a * info["scale"] * np.sqrt(info["p_unit"] / 2.0)) for a in CHAIN_AMPS]
-    return [(CHm.tune_word(f, fs), CHm.tune_word(audio_hz, fs_out), g) for f, g in zip(CHAIN_CENTRES, gains)], audio_hz, gains
+    gains = [0.1 * 32768.0 / (a * info["scale"] * np.sqrt(info["p_unit"] / 2.0)) for a in MSK_CHAIN_AMPS]
+    return [(CHm.tune_word(f, fs), CHm.tune_word(audio_hz, fs_out), g) for f, g in zip(MSK_CHAIN_CENTRES, gains)], audio_hz, gains
 
 
 def bits_match(hard, sent, fb, where):
@@ -295,11 +232,11 @@ def test_capture_to_msk_soft_bits_on_device(CH, oracle_mod, fb, fs_out, decim, s
     from jaero_amd import demodulator as B
 
     O = oracle_mod
-    bits, iq, info = chain_capture(fb, fs_out, decim, seconds)
+    bits, iq, info = msk_chain_capture(fb, fs_out, decim, seconds)
     chans, audio_hz, gains = chain_channels(CH, fb, fs_out, decim, info)
     nch, hops = len(chans), 40
     ch = CH.Channeliser(decim, chans, max_write_iq=hops * HP, fs_out=fs_out)
-    assert ch.Mo == RO.N // decim // 2
+    assert ch.Mo == CO.N // decim // 2
     st = B.MskSettings(fb=float(fb), lockingbw=1.5 * fb, freq_center=audio_hz, Fs=fs_out)
     demod = B.DemodulatorBank(st, nch, max_write_samples=(hops + 1) * ch.Mo, softbit_capacity=1 << 14)
     pcm, sizes = [], []
@@ -343,7 +280,7 @@ def test_scale_33091_channels(CH):
     assert ch.profile_read(0)[1] == 1 and ch.profile_read(1)[1] == 1
     pick = sorted({0, 1, 63, 64, nch - 1, nch - 2} | set(int(v) for v in rng.integers(0, nch, size=10)))
     assert len(pick) == 16
-    ystar = RO.block_form(RO.as_complex(iq), decim, [chans[c] for c in pick], CH.design_taps(decim, fs_out=fs_out))
+    ystar = CO.block_form(CO.as_complex(iq), decim, [chans[c] for c in pick], CH.design_taps(decim, fs_out=fs_out))
     for k, c in enumerate(pick):
         assert_rule(got[c], ystar[k], 1.0, f"scale ch{c}")
     del got

@@ -8,27 +8,15 @@ Cut independence is exact: np.array_equal on the float64."""
 import numpy as np
 import pytest
 
-import chan_rates_oracle as RO
+import chan_oracle as CO
 import chan_survey_oracle as SO
+from chan_cases import AUDIO, CH, CHAIN_CENTRES, FS_OUT, channel_set, pchannel_chain_capture, synthetic_capture, white_full_scale
 from conftest import assert_soft_bytes
-from jaero_amd import aerol_frames as AF
-from jaero_amd import signalgen as G
 
 pytestmark = pytest.mark.gpu
 
 N, HP = SO.N, SO.HP
-AUDIO = 715827883  # round(2^32 / 6)
-FS_OUT = {16: 48000.0, 32: 48000.0, 64: 48000.0, 128: 24000.0, 256: 12000.0}
 RTOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def CH():
-    from jaero_amd import capi
-    from jaero_amd import channeliser
-
-    capi.lib()
-    return channeliser
 
 
 def assert_close(got, want, ref, where):
@@ -38,49 +26,6 @@ def assert_close(got, want, ref, where):
     err = float(np.max(np.abs(got - want) / (want + ref)))
     print(f"{where}: largest |got - want| / (want + ref) = {err:.2e} over {got.size} values")
     assert err <= RTOL, (where, err)
-
-
-def white_full_scale(n, seed):
-    """White I/Q whose every sample is within 1 % of full scale (either sign, -32768 included): the strongest input there is."""
-    rng = np.random.default_rng(seed)
-    k = rng.integers(0, 256, size=(n, 2))
-    s = rng.integers(0, 2, size=(n, 2))
-    return np.where(s == 1, 32767 - k, -32768 + k).astype(np.int16)
-
-
-def synthetic_capture(decim, nhops, seed):
-    """Three carriers (amplitudes 1, 1, 3; Eb/N0 20 dB on the weak ones) at a quarter of full scale: OQPSK at 48 kHz x D as
-    tests/test_gpu_chan.py's, MSK at the 24 / 12 kHz rates as tests/test_gpu_chan_rates.py's.  Returns (iq, centres)."""
-    fs_out = FS_OUT[decim]
-    fs = fs_out * decim
-    rng = np.random.default_rng(seed)
-    n = HP * nhops
-    if decim <= 64:
-        centres = [-123456.7, 33.3, fs / 2 - 10000.0]
-        bits = [rng.integers(0, 2, size=2 * (int(n / (fs / 5250.0)) + 20), dtype=np.uint8) for _ in centres]
-        return G.wideband_oqpsk(bits, centres, [1.0, 1.0, 3.0], decim, ebno_db=20.0, rms=0.25, seed=seed, nsamples=n), centres
-    fb = fs_out / 20.0
-    centres = [-123456.7, 33.3, fs / 2 - fs_out * 10 / 48]
-    bits = [rng.integers(0, 2, size=int(n / (fs / fb)) + 20, dtype=np.uint8) for _ in centres]
-    return G.wideband_msk(bits, centres, [1.0, 1.0, 3.0], fs, fb=fb, ebno_db=20.0, rms=0.25, seed=seed, nsamples=n), centres
-
-
-def channel_set(CHm, decim, strong_hz):
-    """tests/test_gpu_chan.py's 12 channels, scaled to the output rate as tests/test_gpu_chan_rates.py does: centres off grid, negative, at
-    +-(Fs_in / 2 - fs_out 10 / 48) and +-(Fs_in / 2 - 1) (the run of bins wraps at N), two on one bin with different words, two on the
-    capture's strongest carrier."""
-    fs_out = FS_OUT[decim]
-    fs, r = fs_out * decim, fs_out / 48000.0
-    edge = fs / 2 - fs_out * 10 / 48
-    hz = [33.3, -123456.7, strong_hz, strong_hz, edge, -edge, 200003.0, -0.01, 7 * fs / N + 3.0 * r, 7 * fs / N - 11.0 * r, -fs / 2 + 1.0,
-          fs / 2 - 1.0]
-    chans = [[CHm.tune_word(f, fs), AUDIO, 1.0] for f in hz]
-    assert RO.words(chans[8][0], AUDIO, decim)[0] == RO.words(chans[9][0], AUDIO, decim)[0] == 7 and chans[8][0] != chans[9][0]
-    for i in (4, 5, 10, 11):
-        assert abs(RO.words(chans[i][0], AUDIO, decim)[0]) + N // decim // 2 > N // 2  # wraps
-    chans[6][1] = CHm.tune_word(11000.0 * r, fs_out)
-    chans[2][2] = 0.1
-    return [tuple(c) for c in chans]
 
 
 def tone(nhops, k, amp_i=20000.0, amp_q=12000.0):
@@ -120,7 +65,7 @@ def test_spectrum_equals_definition(CH, case):
     launches = ch.survey_profile_read(0)[1]
     ch.close()
     o = SO.ChanSurveyOracle(decim, chans, taps, levels=False)
-    o.survey(RO.as_complex(iq))
+    o.survey(CO.as_complex(iq))
     assert nblocks == nb2 == o.nblocks == len(iq) // HP
     assert launches == 1  # all the blocks of the one write that completed any
     assert_close(S, o.S, float(o.S.mean()), f"spectrum, {case}")
@@ -146,8 +91,8 @@ def test_levels_equal_definition(CH, decim, ntaps, source):
         strong = centres[2]
     taps = np.ones(1) if ntaps == 1 else CH.design_taps(decim, cutoff_hz=fs_out * 5 / 12, ntaps=ntaps, beta=8.0 if ntaps == 2049 else 16.0,
                                                          fs_out=fs_out)
-    chans = channel_set(CH, decim, strong)
-    x = RO.as_complex(iq)
+    chans = [tuple(c) for c in channel_set(CH, decim, strong, 0.1)]
+    x = CO.as_complex(iq)
     for hops in (1, 3):
         ch = CH.Channeliser(decim, chans, taps=taps, max_write_iq=hops * HP, fs_out=fs_out)
         ch.survey_enable(psd=False, levels=True)
@@ -195,7 +140,7 @@ def test_cut_independence(CH, nch, decim):
     assert np.array_equal(S, S1), "the spectrum depends on how the writes were cut"
     assert np.array_equal(E, E1), "the levels depend on how the writes were cut"
     o = SO.ChanSurveyOracle(decim, chans, taps)
-    o.survey(RO.as_complex(iq))
+    o.survey(CO.as_complex(iq))
     assert_close(S, o.S, float(o.S.mean()), f"spectrum, ragged, {nch} channels D={decim}")
     assert_close(E, o.E, float(o.E.max()), f"levels, ragged, {nch} channels D={decim}")
 
@@ -207,7 +152,7 @@ def test_retune_retune_all_reset(CH):
 
     decim, fs = 32, 48000.0 * 32
     iq = white_full_scale(8 * HP, 7)
-    x = RO.as_complex(iq)
+    x = CO.as_complex(iq)
     taps = CH.design_taps(decim, cutoff_hz=20000.0)
     chans = [(CH.tune_word(-50000.0, fs), AUDIO, 1.0), (CH.tune_word(123456.7, fs), AUDIO, 1.0), (CH.tune_word(123460.0, fs), AUDIO, 0.5)]
     ch, same, plain = (CH.Channeliser(decim, chans, taps=taps, max_write_iq=4 * HP) for _ in range(3))
@@ -355,32 +300,12 @@ def test_scale_33091_channels(CH, decim):
     pick = sorted({0, 1, 15, 16, nch - 1, nch - 2} | set(int(v) for v in rng.integers(0, nch, size=10)))
     assert len(pick) == 16
     o = SO.ChanSurveyOracle(decim, [chans[c] for c in pick], CH.design_taps(decim, fs_out=fs_out))
-    o.survey(RO.as_complex(iq))
+    o.survey(CO.as_complex(iq))
     assert_close(E[pick], o.E, float(o.E.max()), f"levels of 16 of {nch} channels, D={decim}")
     assert_close(S, o.S, float(o.S.mean()), f"spectrum, D={decim}")
 
 
 # ---------------------------------------------------------------------------------------------- 7. the blind chain
-CHAIN_CENTRES = [-150000.0, -137500.0, -125000.0, 200003.0]
-CHAIN_AMPS = [1.0, 1.5, 2.0, 2.5]
-
-
-def chain_capture():
-    """tests/test_gpu_chan.py's chain capture built afresh: D = 16, four 10.5 kbps P channels of 8 frames each, Eb/N0 13 dB on the weakest,
-    0.1 of full scale RMS."""
-    fb, nfr, decim = 10500, 8, 16
-    pays, bits = [], []
-    for c in range(4):
-        pay = AF.random_payloads(nfr, fb, seed=50 + c)
-        b, _ = AF.p_channel_bits(pay, fb)
-        pays.append(pay)
-        bits.append(np.concatenate([b, np.zeros(64, np.uint8)]))
-    n48 = int(len(bits[0]) / 2 * 48000 / 5250) + 2000
-    n = (n48 * decim // HP) * HP
-    iq = G.wideband_oqpsk(bits, CHAIN_CENTRES, CHAIN_AMPS, decim, fb=fb, ebno_db=13.0, rms=0.1, seed=7, nsamples=n)
-    return pays, iq
-
-
 def test_blind_capture_to_signal_units(CH, oracle_mod):
     """Nothing about the capture is given to the chain but the carriers' width.  Four placeholder channels (tune 0, gain 1) survey the
     first 16 hops for the spectrum; find_carriers gives the centres, retune_all sets them at gain 1; the next 8 hops are surveyed for
@@ -394,7 +319,7 @@ def test_blind_capture_to_signal_units(CH, oracle_mod):
     from jaero_amd import demodulator as B
 
     O = oracle_mod
-    pays, iq = chain_capture()
+    pays, iq, _ = pchannel_chain_capture()
     decim, fb, nch = 16, 10500, 4
     fs = 48000.0 * decim
     hops = 40
