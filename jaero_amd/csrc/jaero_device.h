@@ -282,9 +282,55 @@ __device__ __forceinline__ void jd_lds_barrier()
 #define JD_EBNO_TAIL 192
 
 // Matched-filter taps: every kernel reads its bank's own taps (JPtrs::taps2 / BPtrs::taps2, uploaded by *_create): the sample kernels
-// copy them into LDS once per launch (jd_fir_eval) or take them as scalar kernel arguments (JTaps28); the burst MSK kernel reads
+// copy them into LDS once per launch (jd_fir_sum) or take them as scalar kernel arguments (JTaps28); the burst MSK kernel reads
 // p.taps2 inside its loop with a wave-uniform index (scalar loads).  There is NO process-global tap table: the values depend on
 // (kind, fb, Fs) and banks of different (fb, Fs) are alive together (tests/test_gpu_scale.py::test_msk_family_banks_alive_together).
+
+// The matched filters' history: the oldest inputs in registers, the newest LDSN in an LDS ring ([slot][lane], oldest at fir_slot).  How
+// jd_fir_sum (below) finds ring entry k, k = 0 the oldest, is a RING policy's business: read(k, re, im).
+
+// The ring walked from fir_slot: entry k is slot (fir_slot + k) mod LDSN, formed step by step (read() is called with k ascending).
+template <int LDSN> struct JdRingWalk
+{
+    const double *lre, *lim;
+    int slot, lane; // slot: fir_slot at construction
+    __device__ __forceinline__ void read(int, double &re, double &im)
+    {
+        re = lre[slot * 64 + lane];
+        im = lim[slot * 64 + lane];
+        slot++;
+        if (slot >= LDSN) slot = 0;
+    }
+};
+// The ring without per-term address arithmetic (round 6).  A wavefront that is alone on its SIMD issues at most one instruction of ANY kind
+// per four cycles, so the sample loops are bound by their instruction COUNT, scalar bookkeeping included (profiles/r6_msk600_trace.md): walked,
+// a term of the LDS part costs ~15 instructions, six of them useful (2 mul, 2 add, one ds_read2st64_b64 for both arms, one tap read) -- the rest
+// forms the ring address (fir_slot + k) mod LDSN (five scalar and two vector instructions) and moves the tap's constant address into a register.
+// Here the ring is seen as NB = LDSN / BS blocks of BS slots and fir_slot = a BS + BV: entry k of the LDS part lies in block ((a + m) mod NB) at slot
+// r of it, m = (BV + k) / BS and r = (BV + k) % BS -- both compile-time constants once BV is (a switch over the BS values of BV picks the version, as
+// k_oqpsk_fb's filter does over all its 36 ring positions).  The NB + 1 block addresses blk[m] = ((a + m) mod NB) BS 64 + lane are formed once per
+// sample; every read is then `base register + immediate offset`, and so are the tap reads (tap0 = jd_vzero(): a zero the compiler cannot see
+// through).  The im ring lies directly behind the re ring.  Same terms, same order, same sums.
+template <int LDSN, int BS, int BV, int NBA> struct JdRingBlocks
+{
+    static_assert(LDSN % BS == 0 && NBA == LDSN / BS + 1, "ring blocks");
+    const double *lre;
+    const int (&blk)[NBA];
+    __device__ __forceinline__ void read(int k, double &re, double &im) const
+    {
+        const int m = (BV + k) / BS, r = (BV + k) % BS;
+        re = lre[blk[m] + r * 64];
+        im = lre[blk[m] + r * 64 + LDSN * 64];
+    }
+};
+// a zero in a vector register: added to a wave-uniform LDS index it makes the read `register + immediate offset` instead of a v_mov of a
+// constant address each
+__device__ __forceinline__ int jd_vzero()
+{
+    int z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+    return z;
+}
 
 // Matched-filter evaluation for one sample of 64 channels (one per lane): sum over i of taps[i] * x[n-FIRN+i], oldest first,
 // re and im chains, one multiplication and one addition per tap and chain, each rounded: FIR::FIRUpdateAndProcess (DSP.cpp:292-304) as the
@@ -300,29 +346,26 @@ __device__ __forceinline__ void jd_lds_barrier()
 // round-off is not the reference FFT's, and measured on a bank of bursts the op-for-op filter, glibc's hypot and the correctly rounded atan2
 // change neither a soft byte nor the distribution of soft-symbol differences there, while costing 10 % of both burst workloads
 // (profiles/r5_burst_ab.json).  The continuous demodulators, whose whole chain IS the reference's op for op, never fuse.
-template <int FIRN, int LDSN, int D, bool FUSED = false, int TAILA = 1>
-__device__ __forceinline__ void jd_fir_eval(const double *lre, const double *lim, const double *ltap, const double (&tre)[TAILA],
-                                            const double (&tim)[TAILA], int fir_slot, int lane, double &ore, double &oim)
+// jd_fir_sum continues a sum: taps T0 .. FIRN-1 over the TAILN = FIRN-T0-LDSN register entries and the LDSN ring entries, starting from
+// (are0, aim0) = the sum over taps 0 .. T0-1 (formed by another wavefront: k_msk_fb's back half; T0 = 0 and zeros: the whole sum).  The taps are
+// ltap[tap0 + t], tap0 a run-time zero (jd_vzero) or the constant 0.
+template <int FIRN, int LDSN, int D, bool FUSED, int T0, class RING, int TAILA>
+__device__ __forceinline__ void jd_fir_sum(RING ring, const double *ltap, int tap0, const double (&tre)[TAILA], const double (&tim)[TAILA], double are0,
+                                           double aim0, double &ore, double &oim)
 {
-    constexpr int TAILN = FIRN - LDSN;
+    constexpr int NT = FIRN - T0, TAILN = NT - LDSN;
+    static_assert(TAILN >= 0 && TAILA == (TAILN > 0 ? TAILN : 1), "the register tail holds the entries between tap T0 and the ring");
     double pr[D], pi[D], pt[D];
-    int slot = fir_slot;
-    auto fetch = [&](int s, int q) {
-        pt[q] = ltap[s];
-        if (s >= TAILN)
-        {
-            pr[q] = lre[slot * 64 + lane];
-            pi[q] = lim[slot * 64 + lane];
-            slot++;
-            if (slot >= LDSN) slot = 0;
-        }
+    auto fetch = [&](int s, int q) __attribute__((always_inline)) {
+        pt[q] = ltap[tap0 + T0 + s];
+        if (s >= TAILN) ring.read(s - TAILN, pr[q], pi[q]);
     };
 #pragma unroll
     for (int s = 0; s < D; s++) fetch(s, s);
     __builtin_amdgcn_sched_barrier(0);
-    double are = 0, aim = 0;
+    double are = are0, aim = aim0;
 #pragma unroll
-    for (int s = 0; s < FIRN; s++)
+    for (int s = 0; s < NT; s++)
     {
         const int q = s % D;
         const double xr = (s < TAILN) ? tre[(TAILN - 1 - s) < 0 ? 0 : (TAILN - 1 - s)] : pr[q];
@@ -332,10 +375,41 @@ __device__ __forceinline__ void jd_fir_eval(const double *lre, const double *lim
         // keep the software pipeline as written: the empty asm orders the two sums before the next read (without it instruction
         // selection places every pure arithmetic instruction after the last read: all 94 reads first, 260 registers of them)
         asm volatile("" : "+v"(are), "+v"(aim));
-        if (s + D < FIRN) fetch(s + D, q);
+        if (s + D < NT) fetch(s + D, q);
         __builtin_amdgcn_sched_barrier(0);
     }
     ore = are; oim = aim;
+}
+// the whole sum, op for op, over the walked ring: the continuous MSK kernels (k_msk.h, k_msk_fb.h without a back-half tail)
+template <int FIRN, int LDSN, int D, int TAILA = 1>
+__device__ __forceinline__ void jd_fir_eval(const double *lre, const double *lim, const double *ltap, const double (&tre)[TAILA],
+                                            const double (&tim)[TAILA], int fir_slot, int lane, double &ore, double &oim)
+{
+    jd_fir_sum<FIRN, LDSN, D, false, 0>(JdRingWalk<LDSN>{lre, lim, fir_slot, lane}, ltap, 0, tre, tim, 0.0, 0.0, ore, oim);
+}
+// jd_fir_sum over ring blocks of BS slots: the block addresses, then one of BS versions by fir_slot % BS (JdRingBlocks).  ab < NB and
+// m <= NB, so ab + m < 2 NB and ONE subtraction would do; the second is the text k_msk_fb has always had, and the compiler does not see
+// through it: without it all twelve k_msk_fb instantiations compile to other (62 to 148 lines shorter) listings, which nobody has
+// timed (profiles/fir_refactor_isa.md).
+template <int FIRN, int LDSN, int D, bool FUSED, int T0, int BS, int TAILA>
+__device__ __forceinline__ void jd_fir_sum_blocks(const double *lre, const double *ltap, int tap0, const double (&tre)[TAILA], const double (&tim)[TAILA],
+                                                  int fir_slot, int lane, double are0, double aim0, double &ore, double &oim)
+{
+    static_assert(BS <= 8, "the switch below has eight cases");
+    constexpr int NB = LDSN / BS;
+    int blk[NB + 1];
+    const int ab = fir_slot / BS; // wave-uniform
+#pragma unroll
+    for (int m = 0; m <= NB; m++)
+    {
+        int t = ab + m;
+        if (t >= NB) t -= NB;
+        if (t >= NB) t -= NB;
+        blk[m] = t * BS * 64 + lane;
+    }
+#define JD_FIR_V(B) case B: if constexpr (B < BS) jd_fir_sum<FIRN, LDSN, D, FUSED, T0>(JdRingBlocks<LDSN, BS, B, NB + 1>{lre, blk}, ltap, tap0, tre, tim, are0, aim0, ore, oim); break;
+    switch (fir_slot % BS) { JD_FIR_V(0) JD_FIR_V(1) JD_FIR_V(2) JD_FIR_V(3) JD_FIR_V(4) JD_FIR_V(5) JD_FIR_V(6) JD_FIR_V(7) default: break; }
+#undef JD_FIR_V
 }
 
 // The 55 root-raised-cosine taps are bitwise symmetric (t[i] == t[54 - i]; checked by jaero_create): 28 distinct values, handed to the
@@ -366,20 +440,17 @@ __device__ __forceinline__ void jd_fir_lds_part(jd_lds_cdouble *lre_l, jd_lds_cd
         if (q + 1 < NQ) { nr = tap_of(q + 1) * pr[(q + 1) % D]; ni = tap_of(q + 1) * pi[(q + 1) % D]; }
         are = are + mr;
         aim = aim + mi;
-        // keep the software pipeline as written (see jd_fir_eval)
+        // keep the software pipeline as written (see jd_fir_sum)
         asm volatile("" : "+v"(are), "+v"(aim));
         if (q + D < NQ) { pr[q % D] = lre_l[((S + q + D) % LDSN) * 64]; pi[q % D] = lim_l[((S + q + D) % LDSN) * 64]; }
         mr = nr; mi = ni;
         __builtin_amdgcn_sched_barrier(0);
     }
 }
-// the same sum with run-time ring addresses (one call per launch: the first sample's output from the saved history)
-template <int FIRN, int LDSN, int D, int TAILA>
-__device__ __forceinline__ void jd_fir_eval_sym(const double *lre, const double *lim, const JTaps28 &tp, const double (&tre)[TAILA],
-                                                const double (&tim)[TAILA], int fir_slot, int lane, double &ore, double &oim)
+// the register-tail part of the symmetric sums, oldest first: taps 0 .. TAILN-1 over tre[TAILN-1] .. tre[0]; returns {re, im}
+template <int TAILN>
+__device__ __forceinline__ double2 jd_fir_sym_tail(const JTaps28 &tp, const double (&tre)[TAILN], const double (&tim)[TAILN])
 {
-    static_assert(FIRN == 55, "symmetric-tap filter is the 55-tap RRC");
-    constexpr int TAILN = FIRN - LDSN;
     double are = 0, aim = 0;
 #pragma unroll
     for (int s = 0; s < TAILN; s++)
@@ -388,6 +459,17 @@ __device__ __forceinline__ void jd_fir_eval_sym(const double *lre, const double 
         are = are + tap * tre[TAILN - 1 - s];
         aim = aim + tap * tim[TAILN - 1 - s];
     }
+    return make_double2(are, aim);
+}
+// the same sum with run-time ring addresses (one call per launch: the first sample's output from the saved history)
+template <int FIRN, int LDSN, int D, int TAILA>
+__device__ __forceinline__ void jd_fir_eval_sym(const double *lre, const double *lim, const JTaps28 &tp, const double (&tre)[TAILA],
+                                                const double (&tim)[TAILA], int fir_slot, int lane, double &ore, double &oim)
+{
+    static_assert(FIRN == 55 && TAILA == FIRN - LDSN, "symmetric-tap filter is the 55-tap RRC");
+    constexpr int TAILN = FIRN - LDSN;
+    const double2 a0 = jd_fir_sym_tail(tp, tre, tim);
+    double are = a0.x, aim = a0.y;
     int slot = fir_slot;
 #pragma unroll 1
     for (int q = 0; q < LDSN; q++)
@@ -401,23 +483,19 @@ __device__ __forceinline__ void jd_fir_eval_sym(const double *lre, const double 
     }
     ore = are; oim = aim;
 }
-template <int FIRN, int LDSN, int D, int TAILA>
-__device__ __forceinline__ void jd_fir_eval_sym_static(const double *lre, const double *lim, const JTaps28 &tp, const double (&tre)[TAILA],
-                                                       const double (&tim)[TAILA], int fir_slot, int lane, double &ore, double &oim)
+// the static form: the tail, then the version of jd_fir_lds_part for ring position `slot`.  BUT_LAST: the ring part starts at the slot after
+// `slot` and leaves out the newest term (jd_fir_eval_sym_static_but_last below)
+template <int FIRN, int LDSN, int D, bool BUT_LAST, int TAILA>
+__device__ __forceinline__ void jd_fir_eval_sym_static_t(const double *lre, const double *lim, const JTaps28 &tp, const double (&tre)[TAILA],
+                                                         const double (&tim)[TAILA], int slot, int lane, double &ore, double &oim)
 {
-    static_assert(FIRN == 55 && LDSN <= 40, "symmetric-tap filter is the 55-tap RRC; the switch below has 40 cases");
-    constexpr int TAILN = FIRN - LDSN;
+    static_assert(FIRN == 55 && TAILA == FIRN - LDSN && LDSN <= 40 && (!BUT_LAST || LDSN >= 8),
+                  "symmetric-tap filter is the 55-tap RRC; the switch below has 40 cases");
     jd_lds_cdouble *lre_l = (jd_lds_cdouble *)lre + lane, *lim_l = (jd_lds_cdouble *)lim + lane;
-    double are = 0, aim = 0;
-#pragma unroll
-    for (int s = 0; s < TAILN; s++)
-    {
-        const double tap = tp.t[s <= 27 ? s : 54 - s];
-        are = are + tap * tre[TAILN - 1 - s];
-        aim = aim + tap * tim[TAILN - 1 - s];
-    }
-#define JD_FIR_CASE(S) case S: if constexpr (S < LDSN) jd_fir_lds_part<FIRN, LDSN, D, (S < LDSN ? S : 0), FIRN - LDSN>(lre_l, lim_l, tp, are, aim); break;
-    switch (fir_slot)
+    const double2 a0 = jd_fir_sym_tail(tp, tre, tim);
+    double are = a0.x, aim = a0.y;
+#define JD_FIR_CASE(S) case S: if constexpr (S < LDSN) jd_fir_lds_part<FIRN, LDSN, D, (S < LDSN ? (S + BUT_LAST) % LDSN : 0), FIRN - LDSN, LDSN - BUT_LAST>(lre_l, lim_l, tp, are, aim); break;
+    switch (slot)
     {
         JD_FIR_CASE(0) JD_FIR_CASE(1) JD_FIR_CASE(2) JD_FIR_CASE(3) JD_FIR_CASE(4) JD_FIR_CASE(5) JD_FIR_CASE(6) JD_FIR_CASE(7)
         JD_FIR_CASE(8) JD_FIR_CASE(9) JD_FIR_CASE(10) JD_FIR_CASE(11) JD_FIR_CASE(12) JD_FIR_CASE(13) JD_FIR_CASE(14) JD_FIR_CASE(15)
@@ -429,8 +507,14 @@ __device__ __forceinline__ void jd_fir_eval_sym_static(const double *lre, const 
 #undef JD_FIR_CASE
     ore = are; oim = aim;
 }
+template <int FIRN, int LDSN, int D, int TAILA>
+__device__ __forceinline__ void jd_fir_eval_sym_static(const double *lre, const double *lim, const JTaps28 &tp, const double (&tre)[TAILA],
+                                                       const double (&tim)[TAILA], int fir_slot, int lane, double &ore, double &oim)
+{
+    jd_fir_eval_sym_static_t<FIRN, LDSN, D, false>(lre, lim, tp, tre, tim, fir_slot, lane, ore, oim);
+}
 
-// (Round 6: the same sum in 4 or 6 versions over ring BLOCKS -- k_msk_fb.h's mfb_fir_continue_v -- instead of 36 over ring positions, a sixth of the code,
+// (Round 6: the same sum in 4 or 6 versions over ring BLOCKS -- JdRingBlocks -- instead of 36 over ring positions, a sixth of the code,
 // was built for this kernel too and changes nothing: 10.44 - 10.49 against 10.43 - 10.45 ms per step.  The front half is not this loop's long pole.)
 // The same sum WITHOUT its last term (the newest input): the 54 older terms do not depend on the sample being formed, so a front half that
 // is alone on its SIMD (one pair per workgroup: banks of at most 2 x #CUs groups) evaluates them while the carrier oscillator's table value
@@ -440,29 +524,7 @@ template <int FIRN, int LDSN, int D, int TAILA>
 __device__ __forceinline__ void jd_fir_eval_sym_static_but_last(const double *lre, const double *lim, const JTaps28 &tp, const double (&tre)[TAILA],
                                                                 const double (&tim)[TAILA], int slot_old, int lane, double &ore, double &oim)
 {
-    static_assert(FIRN == 55 && LDSN <= 40 && LDSN >= 8, "symmetric-tap filter is the 55-tap RRC; the switch below has 40 cases");
-    constexpr int TAILN = FIRN - LDSN;
-    jd_lds_cdouble *lre_l = (jd_lds_cdouble *)lre + lane, *lim_l = (jd_lds_cdouble *)lim + lane;
-    double are = 0, aim = 0;
-#pragma unroll
-    for (int s = 0; s < TAILN; s++)
-    {
-        const double tap = tp.t[s <= 27 ? s : 54 - s];
-        are = are + tap * tre[TAILN - 1 - s];
-        aim = aim + tap * tim[TAILN - 1 - s];
-    }
-#define JD_FIR_CASE(S) case S: if constexpr (S < LDSN) jd_fir_lds_part<FIRN, LDSN, D, (S < LDSN ? (S + 1) % LDSN : 0), FIRN - LDSN, LDSN - 1>(lre_l, lim_l, tp, are, aim); break;
-    switch (slot_old)
-    {
-        JD_FIR_CASE(0) JD_FIR_CASE(1) JD_FIR_CASE(2) JD_FIR_CASE(3) JD_FIR_CASE(4) JD_FIR_CASE(5) JD_FIR_CASE(6) JD_FIR_CASE(7)
-        JD_FIR_CASE(8) JD_FIR_CASE(9) JD_FIR_CASE(10) JD_FIR_CASE(11) JD_FIR_CASE(12) JD_FIR_CASE(13) JD_FIR_CASE(14) JD_FIR_CASE(15)
-        JD_FIR_CASE(16) JD_FIR_CASE(17) JD_FIR_CASE(18) JD_FIR_CASE(19) JD_FIR_CASE(20) JD_FIR_CASE(21) JD_FIR_CASE(22) JD_FIR_CASE(23)
-        JD_FIR_CASE(24) JD_FIR_CASE(25) JD_FIR_CASE(26) JD_FIR_CASE(27) JD_FIR_CASE(28) JD_FIR_CASE(29) JD_FIR_CASE(30) JD_FIR_CASE(31)
-        JD_FIR_CASE(32) JD_FIR_CASE(33) JD_FIR_CASE(34) JD_FIR_CASE(35) JD_FIR_CASE(36) JD_FIR_CASE(37) JD_FIR_CASE(38) JD_FIR_CASE(39)
-    default: break;
-    }
-#undef JD_FIR_CASE
-    ore = are; oim = aim;
+    jd_fir_eval_sym_static_t<FIRN, LDSN, D, true>(lre, lim, tp, tre, tim, slot_old, lane, ore, oim);
 }
 
 // tanh as glibc 2.35 computes it (sysdeps/ieee754/dbl-64/s_tanh.c over s_expm1.c, the fdlibm algorithms with glibc's grouping of the

@@ -48,53 +48,13 @@ __device__ __forceinline__ void bd_cmul(double &ar, double &ai, double br, doubl
     ar = r; ai = i;
 }
 
-// jd_fir_eval (jaero_device.h) without per-term address arithmetic (round 6; the 600 bps MSK kernel's mfb_fir_continue_v, k_msk_fb.h, for this filter).  The
-// wavefront is alone on its SIMD and issues one instruction of any kind per four cycles, so the loop is bound by its instruction COUNT: a term of the
-// LDS part cost ~11 instructions of which four or two (fused) were arithmetic -- the rest formed the ring address (slot + k) mod LDSN and fetched the tap
-// through a v_mov of its constant address.  The ring as NB = LDSN / BS blocks of BS slots, fir_slot = a BS + BV: entry k lies in block (a + m) mod NB at
-// slot r, m = (BV + k) / BS, r = (BV + k) % BS, compile-time constants per version BV; the NB + 1 block addresses are formed once per sample and every
-// read is `register + immediate` (taps too: tapz is a zero the compiler cannot see through).  Same terms, same order, same operations.
-template <int FIRN, int LDSN, int D, bool FUSED, int BS, int BV, int TAILA, int NBA>
-__device__ __forceinline__ void bd_fir_eval_v(const double *lre, const double *ltap, const double (&tre)[TAILA], const double (&tim)[TAILA], const int (&blk)[NBA],
-                                              int tapz, double &ore, double &oim)
-{
-    constexpr int TAILN = FIRN - LDSN;
-    static_assert(LDSN % BS == 0 && NBA == LDSN / BS + 1 && TAILA == TAILN, "ring blocks");
-    double pr[D], pi[D], pt[D];
-    auto fetch = [&](int s, int q) __attribute__((always_inline)) {
-        pt[q] = ltap[tapz + s];
-        if (s >= TAILN)
-        {
-            const int k = s - TAILN, m = (BV + k) / BS, r = (BV + k) % BS;
-            pr[q] = lre[blk[m] + r * 64];
-            pi[q] = lre[blk[m] + r * 64 + LDSN * 64]; // the other arm's ring follows this one
-        }
-    };
-#pragma unroll
-    for (int s = 0; s < D; s++) fetch(s, s);
-    __builtin_amdgcn_sched_barrier(0);
-    double are = 0, aim = 0;
-#pragma unroll
-    for (int s = 0; s < FIRN; s++)
-    {
-        const int q = s % D;
-        const double xr = (s < TAILN) ? tre[(TAILN - 1 - s) < 0 ? 0 : (TAILN - 1 - s)] : pr[q];
-        const double xi = (s < TAILN) ? tim[(TAILN - 1 - s) < 0 ? 0 : (TAILN - 1 - s)] : pi[q];
-        if constexpr (FUSED) { are = fma(pt[q], xr, are); aim = fma(pt[q], xi, aim); }
-        else { are = are + pt[q] * xr; aim = aim + pt[q] * xi; }
-        asm volatile("" : "+v"(are), "+v"(aim)); // keeps the software pipeline as written (see jd_fir_eval)
-        if (s + D < FIRN) fetch(s + D, q);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    ore = are; oim = aim;
-}
-
 // Arithmetic policy of this kernel: fused matched filter + the device library's hypot / atan2.  The A/B build
 // (make -C jaero_amd/csrc ab_burst -> gpurun_tmp/libjaero_hip_burstexact.so, -DJD_BURST_EXACT) takes the continuous kernels' arithmetic instead --
 // filter op for op, glibc's hypot, correctly rounded atan2 -- so that scripts/burst_recording_ab.py can count on the reference's own off-air
 // recording what the choice moves (round 6: profiles/r6_burst_recording_ab.json).
-#define BD_LDSN 36 // filter history slots in LDS (39 until round 6): six blocks of six for bd_fir_eval_v
+#define BD_LDSN 36 // filter history slots in LDS (39 until round 6): six blocks of six for the filter's ring reads (JdRingBlocks)
 #define BD_BS 6
+static_assert(BD_LDSN % BD_BS == 0 && BD_BS <= 6, "ring blocks: k_burst_oqpsk_demod's switch has six cases");
 #ifdef JD_BURST_EXACT
 #define BD_FUSED false
 #define BD_HYPOT(x, y) jd_hypot(x, y)
@@ -110,7 +70,7 @@ template <bool CAPSYM>
 __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const BPtrs p, int n, long long n0, int first_of_write)
 {
     // matched-filter history as in k_oqpsk_fb.h: the LDSN newest entries of each arm in LDS ([slot][lane]), the FIRN-LDSN oldest in a
-    // VGPR shift register, plus this wavefront's copy of the taps (jd_fir_eval) -> 36.5 KiB of LDS per wavefront (bd_lds_bytes), four per CU
+    // VGPR shift register, plus this wavefront's copy of the taps (jd_fir_sum) -> 36.5 KiB of LDS per wavefront (bd_lds_bytes), four per CU
     constexpr int FIRN = 55, LDSN = BD_LDSN, TAILN = FIRN - LDSN;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double *lre = lds, *lim = lds + LDSN * 64, *ltap = lds + 2 * LDSN * 64;
@@ -160,8 +120,7 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
 
     stg_hist_load<FIRN, LDSN, TAILN>(p.firsave + (size_t)grp * 2 * FIRN * 64 + lane, lre, lim, lane, tre, tim);
     if (lane < FIRN) ltap[lane] = taps[lane];
-    int tapz; // a zero in a vector register: tap reads become `register + immediate offset` (bd_fir_eval_v)
-    asm volatile("v_mov_b32 %0, 0" : "=v"(tapz));
+    const int tapz = jd_vzero(); // tap reads become `register + immediate offset` (JdRingBlocks)
     int fir_slot = (int)(n0 % LDSN), s_eb = (int)(n0 % g.win_ring);
     int s_agc2 = s_eb - g.agc2_len; if (s_agc2 < 0) s_agc2 += g.win_ring; // the entry written agc2_len samples ago (slot s_eb itself holds the one written win_ring ago)
     int s_e = s_eb - g.eb_len; if (s_e < 0) s_e += g.win_ring;             // the entry written eb_len samples ago
@@ -224,6 +183,9 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
         double sre = 0, sim = 0;
         {
             // output from x[n-FIRN .. n-1] (FIR::FIRUpdateAndProcess excludes the sample being pushed): taps[i] <-> x[n-FIRN+i]
+            // The block addresses and the switch of jd_fir_sum_blocks stay written out here, with one wrap-around subtraction and six plain
+            // cases: through the shared dispatcher both instantiations of this kernel compile to longer listings (and, with one
+            // subtraction there, 80 instead of 64 B of scratch): profiles/fir_refactor_isa.md.
             constexpr int NB = LDSN / BD_BS;
             int blk[NB + 1];
             const int ab = fir_slot / BD_BS; // wave-uniform
@@ -234,7 +196,7 @@ __global__ __launch_bounds__(64) void k_burst_oqpsk_demod(const BGeom g, const B
                 if (t >= NB) t -= NB;
                 blk[m] = t * BD_BS * 64 + lane;
             }
-#define BD_V(B) case B: bd_fir_eval_v<FIRN, LDSN, 8, BD_FUSED, BD_BS, B>(lre, ltap, tre, tim, blk, tapz, sre, sim); break;
+#define BD_V(B) case B: jd_fir_sum<FIRN, LDSN, 8, BD_FUSED, 0>(JdRingBlocks<LDSN, BD_BS, B, NB + 1>{lre, blk}, ltap, tapz, tre, tim, 0.0, 0.0, sre, sim); break;
             switch (fir_slot % BD_BS) { BD_V(0) BD_V(1) BD_V(2) BD_V(3) BD_V(4) BD_V(5) default: break; }
 #undef BD_V
             // push x[n]: the oldest LDS entry moves into the register tail

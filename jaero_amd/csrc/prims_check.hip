@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(TPB) k_jp_bd_set_phase_deg(const double *phase
 // ---- the matched-filter evaluators ------------------------------------------------------------------------------------------------
 // One wavefront per block, block b evaluating with the ring at position fir_slot = b (b = 0 .. LDSN-1): the same register tail
 // (tail[j][lane] = x[n-LDSN-1-j]), the same LDS ring ([slot][lane]) and taps in every block.  out[b][lane].
-// FORM 0: jd_fir_eval (taps from LDS), 1: jd_fir_eval_sym, 2: jd_fir_eval_sym_static, 3: jd_fir_eval_sym_static_but_last (JTaps28: the first
+// FORM 0: jd_fir_eval (taps from LDS, the ring walked; FUSED: jd_fir_sum over the walked ring with one fma per tap, which jd_fir_eval does not offer), 1: jd_fir_eval_sym, 2: jd_fir_eval_sym_static, 3: jd_fir_eval_sym_static_but_last (JTaps28: the first
 // 28 of 55 bitwise symmetric taps; form 3 reads no ring slot fir_slot and sums taps 0..53).
 template <int FORM, int FIRN, int LDSN, int D, bool FUSED>
 __global__ void __launch_bounds__(64) k_jp_fir(const double *taps, const double *tail_re, const double *tail_im, const double *ring_re,
@@ -203,7 +203,8 @@ __global__ void __launch_bounds__(64) k_jp_fir(const double *taps, const double 
     for (int j = 0; j < TAILA; j++) { tre[j] = TAILN > 0 ? tail_re[j * 64 + lane] : 0.0; tim[j] = TAILN > 0 ? tail_im[j * 64 + lane] : 0.0; }
     __syncthreads();
     double ore = 0, oim = 0;
-    if constexpr (FORM == 0) jd_fir_eval<FIRN, LDSN, D, FUSED, TAILA>(lre, lim, ltap, tre, tim, fir_slot, lane, ore, oim);
+    if constexpr (FORM == 0 && FUSED) jd_fir_sum<FIRN, LDSN, D, true, 0>(JdRingWalk<LDSN>{lre, lim, fir_slot, lane}, ltap, 0, tre, tim, 0.0, 0.0, ore, oim);
+    else if constexpr (FORM == 0) jd_fir_eval<FIRN, LDSN, D>(lre, lim, ltap, tre, tim, fir_slot, lane, ore, oim);
     else if constexpr (FORM == 1) jd_fir_eval_sym<FIRN, LDSN, D>(lre, lim, tp, tre, tim, fir_slot, lane, ore, oim);
     else if constexpr (FORM == 2) jd_fir_eval_sym_static<FIRN, LDSN, D>(lre, lim, tp, tre, tim, fir_slot, lane, ore, oim);
     else jd_fir_eval_sym_static_but_last<FIRN, LDSN, D>(lre, lim, tp, tre, tim, fir_slot, lane, ore, oim);
@@ -222,6 +223,43 @@ static int run_fir(const double *taps, const double *tail_re, const double *tail
     const double *drr = b.in(ring_re, LDSN * 64), *dri = b.in(ring_im, LDSN * 64);
     double *dor = b.io(out_re, LDSN * 64), *doi = b.io(out_im, LDSN * 64);
     if (b.ok()) k_jp_fir<FORM, FIRN, LDSN, D, FUSED><<<LDSN, 64>>>(dt, dtr, dti, drr, dri, tp, dor, doi);
+    return b.sync();
+}
+// jd_fir_sum_blocks: the sum over taps T0 .. FIRN-1 continued from start[lane], ring reads by blocks of BS slots.  The same blocks, tail
+// (FIRN-T0-LDSN entries) and ring as above; the im ring lies directly behind the re ring, as the block form reads it, and the LDS is taken
+// dynamically (160 / 72: 73 728 B of rings plus the taps, above the static limit).
+template <int FIRN, int LDSN, int D, bool FUSED, int T0, int BS>
+__global__ void __launch_bounds__(64) k_jp_fir_blocks(const double *taps, const double *tail_re, const double *tail_im, const double *ring_re,
+                                                      const double *ring_im, const double *start_re, const double *start_im, double *out_re, double *out_im)
+{
+    constexpr int TAILN = FIRN - T0 - LDSN, TAILA = TAILN > 0 ? TAILN : 1;
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *lre = lds, *lim = lds + LDSN * 64, *ltap = lds + 2 * LDSN * 64;
+    const int lane = threadIdx.x, fir_slot = blockIdx.x;
+    for (int s = 0; s < LDSN; s++) { lre[s * 64 + lane] = ring_re[s * 64 + lane]; lim[s * 64 + lane] = ring_im[s * 64 + lane]; }
+    for (int k = lane; k < FIRN; k += 64) ltap[k] = taps[k];
+    double tre[TAILA], tim[TAILA];
+#pragma unroll
+    for (int j = 0; j < TAILA; j++) { tre[j] = TAILN > 0 ? tail_re[j * 64 + lane] : 0.0; tim[j] = TAILN > 0 ? tail_im[j * 64 + lane] : 0.0; }
+    __syncthreads();
+    double ore = 0, oim = 0;
+    jd_fir_sum_blocks<FIRN, LDSN, D, FUSED, T0, BS>(lre, ltap, jd_vzero(), tre, tim, fir_slot, lane, start_re[lane], start_im[lane], ore, oim);
+    out_re[fir_slot * 64 + lane] = ore;
+    out_im[fir_slot * 64 + lane] = oim;
+}
+template <int FIRN, int LDSN, int D, bool FUSED, int T0, int BS>
+static int run_fir_blocks(const double *taps, const double *tail_re, const double *tail_im, const double *ring_re, const double *ring_im,
+                          const double *start_re, const double *start_im, double *out_re, double *out_im)
+{
+    constexpr int TAILA = FIRN - T0 - LDSN > 0 ? FIRN - T0 - LDSN : 1, LDS_BYTES = (2 * LDSN * 64 + FIRN) * (int)sizeof(double);
+    const auto kernel = k_jp_fir_blocks<FIRN, LDSN, D, FUSED, T0, BS>;
+    const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e != hipSuccess) return (int)e;
+    Bufs b;
+    const double *dt = b.in(taps, FIRN), *dtr = b.in(tail_re, TAILA * 64), *dti = b.in(tail_im, TAILA * 64);
+    const double *drr = b.in(ring_re, LDSN * 64), *dri = b.in(ring_im, LDSN * 64), *dsr = b.in(start_re, 64), *dsi = b.in(start_im, 64);
+    double *dor = b.io(out_re, LDSN * 64), *doi = b.io(out_im, LDSN * 64);
+    if (b.ok()) kernel<<<LDSN, 64, LDS_BYTES>>>(dt, dtr, dti, drr, dri, dsr, dsi, dor, doi);
     return b.sync();
 }
 
@@ -378,4 +416,14 @@ JP_FIR(jp_fir_eval_fused_55_36_8, 0, 55, 36, 8, true)
 JP_FIR(jp_fir_eval_sym_55_36_6, 1, 55, 36, 6, false)
 JP_FIR(jp_fir_eval_sym_static_55_36_6, 2, 55, 36, 6, false)
 JP_FIR(jp_fir_eval_sym_static_but_last_55_36_6, 3, 55, 36, 6, false)
+#define JP_FIR_BLOCKS(NAME, FIRN, LDSN, D, FUSED, T0, BS)                                                                                            \
+    int NAME(const double *taps, const double *tail_re, const double *tail_im, const double *ring_re, const double *ring_im,                       \
+             const double *start_re, const double *start_im, double *out_re, double *out_im)                                                        \
+    {                                                                                                                                                \
+        return run_fir_blocks<FIRN, LDSN, D, FUSED, T0, BS>(taps, tail_re, tail_im, ring_re, ring_im, start_re, start_im, out_re, out_im);         \
+    }
+JP_FIR_BLOCKS(jp_fir_sum_blocks_80_36_8_t32_b4, 80, 36, 8, false, 32, 4)
+JP_FIR_BLOCKS(jp_fir_sum_blocks_80_32_8_t18_b4, 80, 32, 8, false, 18, 4)
+JP_FIR_BLOCKS(jp_fir_sum_blocks_160_72_8_t64_b4, 160, 72, 8, false, 64, 4)
+JP_FIR_BLOCKS(jp_fir_sum_blocks_fused_55_36_8_t0_b6, 55, 36, 8, true, 0, 6)
 }

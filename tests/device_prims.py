@@ -50,16 +50,26 @@ class FirRow:
     d: int
     fused: bool
     site: str  # the call site this instantiation stands for (file:line under jaero_amd/csrc)
+    t0: int = 0  # block rows: the sum continues behind tap t0 - 1 from per-lane start sums ...
+    bs: int = 0  # ... and reads the ring by blocks of bs slots (jd_fir_sum_blocks); 0: the ring walked or the 55-tap symmetric forms
 
 
-# every matched-filter instantiation of jaero_device.h a kernel launches, plus the FUSED form of jd_fir_eval, which the template offers
+# every matched-filter instantiation of jaero_device.h a kernel launches, plus the fused sum over the walked ring, which jd_fir_sum offers
 FIR_ROWS = [
     FirRow("jp_fir_eval_40_24_8", "jd_fir_eval", 40, 24, 8, False, "k_msk.h:80"),  # MSK_LDSN_40: 1200 bps at 24 kHz, 600 bps at 12 kHz
     FirRow("jp_fir_eval_20_12_8", "jd_fir_eval", 20, 12, 8, False, "k_msk.h:80"),  # MSK_LDSN_20: 1200 bps at 12 kHz
-    FirRow("jp_fir_eval_fused_55_36_8", "jd_fir_eval", 55, 36, 8, True, ""),  # no kernel launches it (the burst demodulator has bd_fir_eval_v)
+    # jd_fir_sum<55, 36, 8, true, 0> over JdRingWalk: no kernel launches it (jd_fir_eval no longer fuses; the burst demodulator reads by blocks,
+    # last row); the one combination of jd_fir_sum's two compile-time choices that has no call site, kept under its export's earlier name
+    FirRow("jp_fir_eval_fused_55_36_8", "jd_fir_sum", 55, 36, 8, True, ""),
     FirRow("jp_fir_eval_sym_55_36_6", "jd_fir_eval_sym", 55, 36, 6, False, "k_oqpsk_fb.h:204"),  # FB_LDSN
     FirRow("jp_fir_eval_sym_static_55_36_6", "jd_fir_eval_sym_static", 55, 36, 6, False, "k_oqpsk_fb.h:266"),
     FirRow("jp_fir_eval_sym_static_but_last_55_36_6", "jd_fir_eval_sym_static_but_last", 55, 36, 6, False, "k_oqpsk_fb.h:236"),  # D = FB_SOLO_D
+    # k_msk_fb's front half (TB > 0: all twelve instantiations), T0 = the back half's share of the tail, BS = mfb_bs<LDSN>()
+    FirRow("jp_fir_sum_blocks_80_36_8_t32_b4", "jd_fir_sum_blocks", 80, 36, 8, False, "k_msk_fb.h:149", 32, 4),  # MFB_LDSN, MFB1_TB
+    FirRow("jp_fir_sum_blocks_80_32_8_t18_b4", "jd_fir_sum_blocks", 80, 32, 8, False, "k_msk_fb.h:149", 18, 4),  # MFB4_LDSN, MFB4_TB
+    FirRow("jp_fir_sum_blocks_160_72_8_t64_b4", "jd_fir_sum_blocks", 160, 72, 8, False, "k_msk_fb.h:149", 64, 4),  # MFB2_LDSN, MFB2_TB
+    # k_burst_oqpsk_demod forms its block addresses itself and calls jd_fir_sum over JdRingBlocks<BD_LDSN, BD_BS, ..>: the same sums, from zero
+    FirRow("jp_fir_sum_blocks_fused_55_36_8_t0_b6", "jd_fir_sum", 55, 36, 8, True, "k_burst_demod.h:199", 0, 6),  # BD_LDSN, BD_BS, BD_FUSED
 ]
 
 NOT_LAUNCHED = {
@@ -68,6 +78,9 @@ NOT_LAUNCHED = {
     "jd_atan_lane_table": "built at entry of jp_atan2's kernel exactly as the sample kernels build it",
     "jd_atan2_t": "the template behind jd_atan2 (its only instantiation)",
     "jd_lds_barrier": "s_waitcnt lgkmcnt(0) + s_barrier, no arithmetic; every front / back pair and workgroup FFT the kernel tests run goes through it",
+    "jd_vzero": "a v_mov of zero, no arithmetic; the tap offset of every jd_fir_sum_blocks row",
+    "jd_fir_sym_tail": "the register-tail part of the three jd_fir_eval_sym* forms, checked through them",
+    "jd_fir_eval_sym_static_t": "the template behind jd_fir_eval_sym_static and _but_last (its only instantiations)",
     "jd_fir_lds_part": "the ring part of jd_fir_eval_sym_static and _but_last, checked through them at every ring position",
 }
 
@@ -87,13 +100,13 @@ DIV_CONSTS = [
     DivConst(96000.0, "OQPSK ebno_len = 2 Fs, k_oqpsk_fb.h:122", "jaero_hip.hip:426", "g.ebno_len = (int)(2 * s.Fs)"),
     DivConst(800.0, "OQPSK marg_len, k_oqpsk_fb.h:322", "jaero_hip.hip:432", "g.marg_len = 800"),
     DivConst(400.0, "OQPSK pm_len and msema_len, k_oqpsk_fb.h:322", "jaero_hip.hip:432", "g.pm_len = 400; g.msema_len = 400"),
-    DivConst(48000.0, "samplerate = Fs (also k_burst_demod.h:172)", "k_oqpsk_fb.h:319", "r_samplerate = 1.0 / samplerate"),
-    DivConst(360.0, "degrees (also k_burst_demod.h:172)", "k_oqpsk_fb.h:320", "r_360 = 1.0 / 360.0"),
+    DivConst(48000.0, "samplerate = Fs (also k_burst_demod.h:131)", "k_oqpsk_fb.h:319", "r_samplerate = 1.0 / samplerate"),
+    DivConst(360.0, "degrees (also k_burst_demod.h:131)", "k_oqpsk_fb.h:320", "r_360 = 1.0 / 360.0"),
     DivConst(360.0, "degrees in bd_set_phase_deg", "jaero_device.h:222", "jd_div_const(phase_deg, 360.0, 1.0 / 360.0)"),
-    DivConst(19999.0, "JD_WTSIZE (also k_burst_demod.h:172)", "k_oqpsk_fb.h:320", "r_wtsize = 1.0 / wtsize_d"),
-    DivConst(585.0, "burst OQPSK agc2_len = round(64 SPS), SPS = 2 Fs / fb, k_burst_demod.h:172", "burst_host.h:23",
+    DivConst(19999.0, "JD_WTSIZE (also k_burst_demod.h:131)", "k_oqpsk_fb.h:320", "r_wtsize = 1.0 / wtsize_d"),
+    DivConst(585.0, "burst OQPSK agc2_len = round(64 SPS), SPS = 2 Fs / fb, k_burst_demod.h:131", "burst_host.h:23",
              "g.agc2_len = (int)round((SPS * 64.0 / s.Fs) * s.Fs)"),
-    DivConst(128.0, "burst OQPSK msema_len, k_burst_demod.h:173", "burst_host.h:36", "g.msema_len = 128"),
+    DivConst(128.0, "burst OQPSK msema_len, k_burst_demod.h:132", "burst_host.h:36", "g.msema_len = 128"),
 ]
 
 
@@ -142,7 +155,7 @@ def prims():
     for name in ("jp_tanh", "jp_tanh_full", "jp_expm1", "jp_log10", "jp_qround", "jp_softbit", "jp_cisidx", "jp_fb_fmod360"):
         sig[name] = [P, P, n]
     for r in FIR_ROWS:
-        sig[r.export] = [P] * 7
+        sig[r.export] = [P] * (9 if r.bs else 7)  # block rows: start_re, start_im in front of the outputs
     for name, args in sig.items():
         fn = getattr(L, name)
         fn.argtypes = args

@@ -79,19 +79,43 @@ def test_fir_rows_match_their_call_sites():
     val = lambda src, name: int(re.search(rf"#define {name} (\d+)", src).group(1))  # noqa: E731
     fb_ldsn, solo_d = val(oq, "FB_LDSN"), val(oq, "FB_SOLO_D")
     msk40, msk20 = val(hip, "MSK_LDSN_40"), val(hip, "MSK_LDSN_20")
+    # the block rows: k_msk_fb's front half calls jd_fir_sum_blocks<FIRN, LDSN, 8, false, TB, mfb_bs<LDSN>()> for the three msk_fb_rec<FIRN, LDSN,
+    # PAIRS, TB> of jaero_hip.hip; k_burst_oqpsk_demod calls jd_fir_sum<55, BD_LDSN, 8, BD_FUSED, 0> over JdRingBlocks<BD_LDSN, BD_BS, ..>
+    mfb, bd = read("k_msk_fb.h"), read("k_burst_demod.h")
+    bs_max = val(mfb, "MFB_BS_MAX")
+    assert "constexpr int mfb_bs() { return (LDSN % 8 == 0 && MFB_BS_MAX >= 8) ? 8 : (MFB_BS_MAX >= 4 ? 4 : 2); }" in mfb
+    mfb_bs = lambda ldsn: 8 if (ldsn % 8 == 0 and bs_max >= 8) else (4 if bs_max >= 4 else 2)  # noqa: E731
+    recs = re.findall(r"msk_fb_rec<(\d+), (\w+), \d+, (\w+)>", hip)
+    assert sorted(recs) == sorted([("160", "MFB2_LDSN", "MFB2_TB"), ("80", "MFB4_LDSN", "MFB4_TB"), ("80", "MFB_LDSN", "MFB1_TB")]), recs
+    blocks = {(int(firn), val(mfb, ldsn), 8, False, val(mfb, tb), mfb_bs(val(mfb, ldsn))) for firn, ldsn, tb in recs}
+    bd_fused = re.search(r"#ifdef JD_BURST_EXACT\n#define BD_FUSED false\n.*?#else\n#define BD_FUSED true\n", bd, re.S) is not None
+    blocks.add((55, val(bd, "BD_LDSN"), 8, bd_fused, 0, val(bd, "BD_BS")))
+    assert {(r.firn, r.ldsn, r.d, r.fused, r.t0, r.bs) for r in DP.FIR_ROWS if r.bs} == blocks
+    assert blocks == {(80, 36, 8, False, 32, 4), (80, 32, 8, False, 18, 4), (160, 72, 8, False, 64, 4), (55, 36, 8, True, 0, 6)}
     want = {
         "jp_fir_eval_40_24_8": (40, msk40, 8), "jp_fir_eval_20_12_8": (20, msk20, 8), "jp_fir_eval_fused_55_36_8": (55, fb_ldsn, 8),
         "jp_fir_eval_sym_55_36_6": (55, fb_ldsn, 6), "jp_fir_eval_sym_static_55_36_6": (55, fb_ldsn, 6),
         "jp_fir_eval_sym_static_but_last_55_36_6": (55, fb_ldsn, solo_d),
     }
-    assert {r.export: (r.firn, r.ldsn, r.d) for r in DP.FIR_ROWS} == want
+    assert {r.export: (r.firn, r.ldsn, r.d) for r in DP.FIR_ROWS if not r.bs} == want
+    # the only row without a call site is the fused sum over the walked ring; no row without blocks continues a sum
+    assert [r.export for r in DP.FIR_ROWS if not r.site] == ["jp_fir_eval_fused_55_36_8"]
+    assert [r.export for r in DP.FIR_ROWS if r.fused and not r.bs] == ["jp_fir_eval_fused_55_36_8"] and not any(r.t0 for r in DP.FIR_ROWS if not r.bs)
     prims = read("prims_check.hip")
     for r in DP.FIR_ROWS:
-        assert f"JP_FIR({r.export}, " in prims and f", {r.firn}, {r.ldsn}, {r.d}, {'true' if r.fused else 'false'})" in prims, r
+        if r.bs:
+            assert f"JP_FIR_BLOCKS({r.export}, {r.firn}, {r.ldsn}, {r.d}, {'true' if r.fused else 'false'}, {r.t0}, {r.bs})" in prims, r
+        else:
+            assert f"JP_FIR({r.export}, " in prims and f", {r.firn}, {r.ldsn}, {r.d}, {'true' if r.fused else 'false'})" in prims, r
         if r.site:
             f, line = r.site.split(":")
             text = read(f).splitlines()[int(line) - 1]
             assert f"{r.func}<" in text, (r.site, text)
+    assert "jd_fir_sum_blocks<FIRN, LDSN, 8, false, TB, mfb_bs<LDSN>()>(" in mfb and mfb.count("jd_fir_sum_blocks<") == 1
+    assert "jd_fir_sum<FIRN, LDSN, 8, BD_FUSED, 0>(JdRingBlocks<LDSN, BD_BS, B, NB + 1>{" in bd and "constexpr int FIRN = 55, LDSN = BD_LDSN" in bd
+    # the launcher of the block rows runs the dispatcher, and the dispatcher the same jd_fir_sum over JdRingBlocks
+    assert "jd_fir_sum_blocks<FIRN, LDSN, D, FUSED, T0, BS>(" in prims
+    assert "jd_fir_sum<FIRN, LDSN, D, FUSED, T0>(JdRingBlocks<LDSN, BS, B, NB + 1>{" in read("jaero_device.h")
     # the template arguments at the call sites: jd_fir_eval<FIRN, LDSN, 8> in k_msk.h (FIRN 40 / 20 from jaero_hip.hip), the 55-tap forms
     assert re.search(r"msk_samples_rec<40, MSK_LDSN_40>", hip) and re.search(r"msk_samples_rec<20, MSK_LDSN_20>", hip)
     assert "k_oqpsk_fb<55, FB_LDSN," in hip

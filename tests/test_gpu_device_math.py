@@ -674,7 +674,7 @@ def fma_exact(a, b, c):
 def test_fir_evaluator_sums_in_the_reference_order_at_every_ring_position(L, row):
     rng = np.random.default_rng(21 + row.firn + row.ldsn + 7 * row.fused)
     firn, ldsn = row.firn, row.ldsn
-    tailn = firn - ldsn
+    tailn = firn - row.t0 - ldsn  # block rows sum taps t0 .. firn-1 on top of per-lane start sums
     data = lambda *shape: f64(rng.standard_normal(shape) * np.exp2(rng.uniform(-6, 6, shape)))  # noqa: E731
     taps = data(firn)
     if firn == 55:
@@ -682,7 +682,12 @@ def test_fir_evaluator_sums_in_the_reference_order_at_every_ring_position(L, row
         assert np.array_equal(taps, taps[::-1])
     tre, tim, rre, rim = data(max(tailn, 1), 64), data(max(tailn, 1), 64), data(ldsn, 64), data(ldsn, 64)
     ore, oim = np.full((ldsn, 64), np.nan), np.full((ldsn, 64), np.nan)
-    call(L, row.export, taps, tre, tim, rre, rim, ore, oim)
+    start = (data(64), data(64)) if row.bs else (np.zeros(64), np.zeros(64))
+    if row.bs:
+        assert ldsn % row.bs == 0 and np.all(start[0] != 0) and np.all(start[1] != 0)
+        call(L, row.export, taps, tre, tim, rre, rim, start[0], start[1], ore, oim)
+    else:
+        call(L, row.export, taps, tre, tim, rre, rim, ore, oim)
     last = row.func == "jd_fir_eval_sym_static_but_last"
     for slot in range(ldsn):
         # oldest first: the register tail (tre[j] = x[n-LDSN-1-j]), then the ring from fir_slot (but_last: from the slot after slot_old,
@@ -692,14 +697,14 @@ def test_fir_evaluator_sums_in_the_reference_order_at_every_ring_position(L, row
         order += [(rre[(first + q) % ldsn], rim[(first + q) % ldsn]) for q in range(ldsn - 1 if last else ldsn)]
         if row.fused:
             for arm, out in ((0, ore), (1, oim)):
-                acc = [0.0] * 64
+                acc = [float(v) for v in start[arm]]
                 for k, xs in enumerate(order):
-                    acc = [fma_exact(float(taps[k]), float(xs[arm][ln]), acc[ln]) for ln in range(64)]
+                    acc = [fma_exact(float(taps[row.t0 + k]), float(xs[arm][ln]), acc[ln]) for ln in range(64)]
                 check_elementwise(f"{row.export} fir_slot {slot} arm {arm}", out[slot], acc)
             continue
-        are, aim = np.zeros(64), np.zeros(64)
+        are, aim = start[0].copy(), start[1].copy()
         for k, (xr, xi) in enumerate(order):
-            are = are + taps[k] * xr
-            aim = aim + taps[k] * xi
+            are = are + taps[row.t0 + k] * xr
+            aim = aim + taps[row.t0 + k] * xi
         check_elementwise(f"{row.export} fir_slot {slot} re", ore[slot], are)
         check_elementwise(f"{row.export} fir_slot {slot} im", oim[slot], aim)
