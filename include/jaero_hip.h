@@ -481,7 +481,8 @@ int jaero_chan3_profile_read(jaero_chan *c, int which, double *total_ms, int *la
  *   jaero_survey_read_psd      synchronises on the handle's last stream; sums[16384] = S, *nblocks = the blocks in it.
  *   jaero_survey_read_levels   the same for sums[nchannels] = E_c, nblocks[nchannels] = n_c.  Reading a part that is not enabled: JAERO_EINVAL.
  *   jaero_survey_profile_read  HIP-event time since the last reset: which 0 = k_chan_psd, 1 = k_chan_level; switched by
- *                              jaero_chan_profile_enable.
+ *                              jaero_chan_profile_enable.  A launch that also serves the activity below (spectrum + peak, levels + block
+ *                              statistics: one fused launch each) is timed once, under the activity's slot, and does not count here.
  *   jaero_chan2_retune_all     jaero_chan_retune of every channel (ch: nchannels entries) behind one synchronisation, with one copy: the
  *                              call that applies surveyed centres and gains to a bank.  Every gain is checked before anything changes;
  *                              a channel's level restarts by the same rule.
@@ -493,6 +494,54 @@ int jaero_survey_read_psd(jaero_chan *c, double *sums, long long *nblocks);
 int jaero_survey_read_levels(jaero_chan *c, double *sums, long long *nblocks);
 int jaero_survey_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset);
 int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *ch);
+
+/* ---- activity: the second, independent part of the survey.  The survey's two measurements are means over every block, so a carrier that
+ * is on in 5 % of the blocks is diluted by 13 dB in S and its level is low by the duty cycle.  The activity keeps the EXTREMES and the
+ * DISTRIBUTION of the same per-block terms instead of their sum: where the burst channels of a capture are, how strong a burst is and how
+ * often a channel is on.  Measured on the device behind every write (it hangs off the same place as the survey, so it works on every
+ * handle, jaero_chan3_create's included), under the survey's determinism rules: a function of absolute block indices only, no
+ * floating-point atomics, bit-identical however the writes are cut.  Off at create; a handle that never enables it allocates and launches
+ * nothing more than before.  Notation: the channeliser's and the survey's above.  This text is the definition;
+ * tests/chan_activity_oracle.py implements it literally in numpy.
+ *   peak-hold spectrum
+ *              P[k] = max_p |H_p[k]|^2, k < N, over every block completed since the part was enabled or reset; 0 before the first block.
+ *              |H_p[k]|^2 is formed by exactly the instructions the spectrum uses: after one block with both parts on, P == S bit for
+ *              bit.  P[k] / (N^2 3 / 8) is LSB^2 per bin, the spectrum's unit.
+ *   block statistics, per channel c
+ *              e_{c,p} = sum_{-M/2 <= q < M/2} |X_p[(b_c + q) mod N] G[q mod N] / N|^2: the term the level adds for block p, formed exactly
+ *              as the level forms it (same products, same 16-lane partial sums, same xor butterfly): after one block with levels on too,
+ *              emax_c == emin_c == E_c bit for bit.  The statistics run over the n_c blocks since the part was enabled or reset, or since a
+ *              retune last changed channel c's TUNE word (the level's restart rule; a retune that changes only audio or gain keeps
+ *              everything):
+ *              emax_c = max_p e_{c,p};  when_c = the smallest absolute block index p (counted from create, as blocks_done counts) at which
+ *              the maximum is reached;  emin_c = min_p e_{c,p};  hist_c[i], i < 64 = the number of blocks with bin(e_{c,p}) = i, uint32;
+ *              bin(e) = min(63, max(0, ilogb(e) + 32)), bin(0) = 0: each bin is one binary order of magnitude (3.01 dB), an integer
+ *              function of the fp64 exponent, no logarithm.  With n_c = 0: emax = 0, emin = +inf, when = -1, hist all zero.
+ *   jaero_activity_enable      what: JAERO_ACT_PEAK | JAERO_ACT_BLOCKS, 0 = off (JAERO_EINVAL for bits outside 0..3, checked before the null
+ *                              ctx as jaero_survey_enable does).  Synchronises, allocates what is enabled for the first time (the
+ *                              |G|^2 / N^2 table too when the levels never built it), clears what is enabled.
+ *   jaero_activity_reset       synchronises, then clears what is enabled.  It does not touch the survey, nor jaero_survey_reset the activity.
+ *   jaero_activity_read_peak   synchronises on the handle's last stream; peak[16384] = P, *nblocks = the blocks in it.
+ *   jaero_activity_read_blocks the same for emax, emin, when, nblocks (nchannels entries each) and hist ([nchannels][JAERO_ACT_BINS], may be
+ *                              NULL).  Reading a part that is not enabled: JAERO_EINVAL.
+ *   jaero_activity_profile_read HIP-event time since the last reset: which 0 = k_chan_psd launches that keep the peak, 1 = k_chan_level
+ *                              launches that take the block statistics; switched by jaero_chan_profile_enable.  The spectrum and the
+ *                              peak are kept by one launch over one pass of the three loads, the levels and the statistics by one launch
+ *                              over one walk of the channels' bins; such a fused launch is timed once, here, and not under
+ *                              jaero_survey_profile_read.
+ *   jaero_chan_retune, jaero_chan2_retune_all restart a moved channel's block statistics together with its level.
+ * Null arguments: JAERO_EINVAL before a device is touched.  A poisoned handle: JAERO_EHIP; a HIP failure inside the activity's launches
+ * poisons the handle as any other failure inside a write.  Deliberately not here: thresholds or detection decisions on the device (the
+ * histogram and the extremes are the measurement; jaero_amd.channeliser.duty_cycle and find_carriers decide in numpy), a time series of
+ * block levels, modulation or bit-rate recognition. */
+#define JAERO_ACT_PEAK 1
+#define JAERO_ACT_BLOCKS 2
+#define JAERO_ACT_BINS 64
+int jaero_activity_enable(jaero_chan *c, int what);
+int jaero_activity_reset(jaero_chan *c);
+int jaero_activity_read_peak(jaero_chan *c, double *peak, long long *nblocks);
+int jaero_activity_read_blocks(jaero_chan *c, double *emax, double *emin, long long *when, long long *nblocks, unsigned *hist);
+int jaero_activity_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset);
 
 /* Host-only debugging aid (no device needed): the sample indices at which jaero_write would run the coarse-frequency
  * estimate for a fresh channel fed `nwrites` writes of write_sizes[i] samples.  Returns the number of triggers

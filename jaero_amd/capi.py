@@ -18,6 +18,7 @@ EV_SIGNAL, EV_EBNO, EV_FREQ, EV_PEAK, EV_TRIDENT = 0, 1, 2, 3, 4
 PCM_CHANNEL_MAJOR, PCM_FRAME_MAJOR = 0, 1
 W_RATE = 1  # jaero_ingest_push: sample rate differs from the bank (warning, data queued)
 IQ_CS16, IQ_CU8, IQ_CS8, IQ_CF32 = 0, 1, 2, 3
+ACT_PEAK, ACT_BLOCKS, ACT_BINS = 1, 2, 64  # jaero_activity_enable: what; bins of a channel's histogram
 AEROL_SUS, AEROL_PACKETS, AEROL_EVENTS, AEROL_VOICE = 0, 1, 2, 3  # jaero_aerol_read_all: what
 BANK_SOFTBITS, BANK_STATUS_LOG, BANK_EVENTS, BANK_SYMBOLS = 0, 1, 2, 3  # jaero_read_all: what
 E_OK, E_INVAL, E_NODEV, E_NOMEM, E_HIP, E_OVERFLOW, E_NOTSUP = 0, -1, -2, -3, -4, -5, -6
@@ -45,6 +46,7 @@ EXPORTS = [
     "jaero_chan_feed", "jaero_chan_profile_enable", "jaero_chan_profile_read", "jaero_chan2_create",
     "jaero_survey_enable", "jaero_survey_reset", "jaero_survey_read_psd", "jaero_survey_read_levels", "jaero_survey_profile_read",
     "jaero_chan2_retune_all",
+    "jaero_activity_enable", "jaero_activity_reset", "jaero_activity_read_peak", "jaero_activity_read_blocks", "jaero_activity_profile_read",
     "jaero_chan3_create", "jaero_chan3_write", "jaero_chan3_feed", "jaero_chan3_read_staged", "jaero_chan3_profile_read",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
@@ -261,6 +263,11 @@ def lib():
     L.jaero_survey_read_levels.argtypes = [vp, vp, vp]
     L.jaero_survey_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_chan2_retune_all.argtypes = [vp, vp]
+    L.jaero_activity_enable.argtypes = [vp, ip]
+    L.jaero_activity_reset.argtypes = [vp]
+    L.jaero_activity_read_peak.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
+    L.jaero_activity_read_blocks.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.jaero_activity_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_chan3_create.argtypes = [ip, C.POINTER(Capture), ip, ip, ip, vp, vp, ip, ip, C.POINTER(vp)]
     L.jaero_chan3_write.argtypes = [vp, vp, ip, ip, vp, C.POINTER(ip)]
     L.jaero_chan3_feed.argtypes = [vp, vp, vp, ip, ip, vp, C.POINTER(ip)]

@@ -6,7 +6,9 @@ caller.  Frequencies are 32-bit words: `tune_word(hz, fs)` is the word nearest a
 frequency a word really is, `channel_words(tune, audio, decim)` the integers the kernels derive from a channel's words.
 The survey (`survey_enable`, `read_psd`, `read_levels`) measures the capture's spectrum and every channel's level on the device;
 `find_carriers` (host numpy, no hot path) turns the spectrum into centre frequencies, `suggest_gains` the levels into gains, and
-`retune_all` applies both.  `Channeliser(..., capture=Capture(fs_in=..., fmt=...))` takes an SDR capture in its own format (cs16, cu8, cs8,
+`retune_all` applies both.  The activity (`activity_enable`, `read_peak_psd`, `read_activity`) keeps the extremes and the distribution of
+the same per-block terms: the peak-hold spectrum finds carriers that are seldom on, `duty_cycle` says how often a channel is on and
+`suggest_gains(peak=True)` sets a burst channel's gain from its strongest block.  `Channeliser(..., capture=Capture(fs_in=..., fmt=...))` takes an SDR capture in its own format (cs16, cu8, cs8,
 cf32) and at its own integer rate: the device converts, shifts the centre by an exact phase word and resamples by the exact rational ratio
 to fs_out x decim (jaero_chan3_*); `design_resampler` is the prototype it uses by default.  All device arithmetic happens in
 libjaero_hip.so; there is no CPU fallback.
@@ -16,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -110,7 +112,9 @@ def find_carriers(psd: np.ndarray, fs_in: float, bw_hz: float, threshold_db: flo
     Smooth by a circular boxcar mean of bw_hz (in bins, forced odd); the noise floor is the median of `psd`; repeatedly take the largest
     smoothed bin that lies at least `threshold_db` above the floor, refine it by the centroid of max(psd - floor, 0) over +-bw / 2 around
     it and once more around the rounded first estimate, blank +-bw around the pick.  The median is the noise floor only while carriers
-    fill less than half of the band: in a fuller capture it lies on the carriers and nothing is found."""
+    fill less than half of the band: in a fuller capture it lies on the carriers and nothing is found.  It may be handed the peak-hold
+    spectrum (`read_peak_psd`) to find carriers that are seldom on: the median of a maximum over n blocks lies above the mean floor by
+    the same factor in every bin, so the threshold keeps its meaning."""
     psd = np.asarray(psd, dtype=np.float64)
     n = psd.size
     w = int(round(bw_hz / fs_in * n)) | 1
@@ -135,6 +139,31 @@ def find_carriers(psd: np.ndarray, fs_in: float, bw_hz: float, threshold_db: flo
         c = centre % n
         found.append((c - n if c >= n / 2 else c) * fs_in / n)
     return sorted(found)
+
+
+class Activity(NamedTuple):
+    """What `Channeliser.read_activity` returns (the block statistics of include/jaero_hip.h's "activity")."""
+    emax: np.ndarray   # [nch] largest block term e_{c,p}; nan where n == 0
+    emin: np.ndarray   # [nch] smallest; nan where n == 0
+    when: np.ndarray   # [nch] absolute index of the first block that reached emax; -1 where n == 0
+    n: np.ndarray      # [nch] blocks counted
+    hist: np.ndarray   # [nch, 64] uint32: blocks whose term has ilogb(e) + 32 == i (clamped to 0 .. 63)
+
+
+def duty_cycle(hist: np.ndarray, rise_bins: int = 2) -> np.ndarray:
+    """The share of a channel's blocks that stand out of its own floor, from the activity's histogram `hist` [nch, 64] (or one row).
+
+    Per channel the floor bin is the most populated bin (the lowest on ties); the active blocks are those in bins >= floor + `rise_bins`
+    (each bin is a factor of 2, 3.01 dB); the result is active / n, nan for an empty row.  What it cannot tell: a channel that is always
+    on has its own signal as its floor and a duty of 0 here -- its level against the capture's noise floor (`read_levels` beside the
+    other channels', or the spectrum) says that it is a carrier.  Nor does a channel that is on for more than half of its blocks read as
+    its duty: the floor bin is then the signal's."""
+    h = np.atleast_2d(np.asarray(hist)).astype(np.int64)
+    n = h.sum(axis=1)
+    floor = np.argmax(h, axis=1)  # the first of equal maxima: the lowest bin
+    active = np.where(np.arange(h.shape[1])[None, :] >= (floor + int(rise_bins))[:, None], h, 0).sum(axis=1)
+    out = np.where(n > 0, active / np.maximum(n, 1), np.nan)
+    return out if np.ndim(hist) > 1 else out[0]
 
 
 class Channeliser:
@@ -320,14 +349,54 @@ class Channeliser:
         e, n = self.read_level_sums()
         return np.where(n > 0, e / np.maximum(n, 1), np.nan), n
 
-    def suggest_gains(self, target_rms: float = 0.1 * 32768) -> np.ndarray:
+    def suggest_gains(self, target_rms: float = 0.1 * 32768, peak: bool = False) -> np.ndarray:
         """The gain that brings each channel's int16 output to `target_rms`: target / sqrt(level / 2).  Raises ValueError for a
-        channel that has no block yet or whose level is 0: it has no such gain (and retune_all would refuse the whole set for it)."""
-        level, counts = self.read_levels()
+        channel that has no block yet or whose level is 0: it has no such gain (and retune_all would refuse the whole set for it).
+        peak=True: target / sqrt(emax / 2) from the activity's block statistics, the gain that puts the STRONGEST BLOCK at the target
+        (a burst channel's mean level is low by its duty cycle)."""
+        if peak:
+            act = self.read_activity()
+            level, counts = act.emax, act.n
+        else:
+            level, counts = self.read_levels()
         empty = np.nonzero((counts == 0) | ~(level > 0.0))[0]
         if empty.size:
             raise ValueError(f"suggest_gains: channels {empty[:8].tolist()} have no surveyed block or a level of 0")
         return target_rms / np.sqrt(level / 2.0)
+
+    def activity_enable(self, peak: bool = True, blocks: bool = True):
+        """Switches the activity's two parts (peak-hold spectrum, per-channel block statistics) on or off; clears what is on."""
+        capi.check(self.L.jaero_activity_enable(self.h, (capi.ACT_PEAK if peak else 0) | (capi.ACT_BLOCKS if blocks else 0)))
+
+    def activity_reset(self):
+        capi.check(self.L.jaero_activity_reset(self.h))
+
+    def read_peak_sums(self) -> Tuple[np.ndarray, int]:
+        """(P[N] raw, nblocks) as the ABI returns them."""
+        p, n = np.empty(N, dtype=np.float64), C.c_longlong(0)
+        capi.check(self.L.jaero_activity_read_peak(self.h, p.ctypes.data, C.byref(n)))
+        return p, n.value
+
+    def read_peak_psd(self) -> Tuple[np.ndarray, int]:
+        """(peak[N], nblocks): P / (N^2 3 / 8), each bin's largest block in LSB^2 per bin, natural bin order (nan before the first block)."""
+        p, n = self.read_peak_sums()
+        return (p / (float(N) * N * 0.375) if n else np.full(N, np.nan)), n
+
+    def read_activity(self) -> "Activity":
+        """Activity(emax, emin, when, n, hist): every channel's largest and smallest block term (nan where n == 0), the absolute index of
+        the block of the largest (-1 where n == 0), the blocks counted, and hist[nch, 64], the blocks per binary order of magnitude."""
+        emax, emin = np.empty(self.nch, dtype=np.float64), np.empty(self.nch, dtype=np.float64)
+        when, n = np.empty(self.nch, dtype=np.int64), np.empty(self.nch, dtype=np.int64)
+        hist = np.empty((self.nch, capi.ACT_BINS), dtype=np.uint32)
+        capi.check(self.L.jaero_activity_read_blocks(self.h, emax.ctypes.data, emin.ctypes.data, when.ctypes.data, n.ctypes.data, hist.ctypes.data))
+        return Activity(np.where(n > 0, emax, np.nan), np.where(n > 0, emin, np.nan), when, n, hist)
+
+    def activity_profile_read(self, which: int, reset: bool = False):
+        """(total ms, launches) of the launches that serve the activity: which 0 = k_chan_psd keeping the peak, 1 = k_chan_level taking the
+        block statistics.  A launch fused with the survey's part counts here and not in survey_profile_read."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.L.jaero_activity_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
 
     def survey_profile_read(self, which: int, reset: bool = False):
         """(total ms, launches) of survey kernel `which`: 0 = spectrum (k_chan_psd), 1 = levels (k_chan_level)."""

@@ -41,7 +41,8 @@ struct jaero_chan
     int16_t *d_pcm = nullptr;  // [nch][nout of the last write], capacity nch * nblk_max * Mo
     int last_nout = 0;
     std::vector<jaero_chan_channel> channels;
-    KernelTimer timer{6};      // 0 k_chan_fwd, 1 k_chan_synth, 2 k_chan_psd, 3 k_chan_level, 4 k_capture_stage, 5 k_capture_fwd
+    KernelTimer timer{8};      // 0 k_chan_fwd, 1 k_chan_synth, 2 k_chan_psd, 3 k_chan_level, 4 k_capture_stage, 5 k_capture_fwd,
+                               // 6 k_chan_psd and 7 k_chan_level whenever the launch serves the activity (fused with the survey's part or not)
     std::unique_ptr<ChanCapture> cap; // null unless the handle came from jaero_chan3_create
     // the survey (jaero_survey_*): nothing below exists before the first enable
     int survey = 0;            // bit 0 spectrum, bit 1 levels
@@ -51,6 +52,13 @@ struct jaero_chan
     long long psd_blocks = 0;  // blocks in S
     long long lvl_blocks = 0;  // blocks surveyed for levels since enable / reset; channel c's count is lvl_blocks - lvl_start[c]
     std::vector<long long> lvl_start;
+    // the activity (jaero_activity_*): nothing below exists before the first enable
+    int activity = 0;          // bit 0 peak-hold spectrum, bit 1 block statistics
+    double *d_peak = nullptr;  // [N]: P
+    ChanAct act{};             // emax, emin, when [nch], hist [nch][64]
+    long long peak_blocks = 0; // blocks in P
+    long long act_blocks = 0;  // blocks whose statistics were taken since enable / reset; channel c's count is act_blocks - act_start[c]
+    std::vector<long long> act_start;
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
     bool poisoned = false;
@@ -176,18 +184,20 @@ extern "C" int jaero_chan_create(int device, int decim, int nchannels, const jae
     return jaero_chan2_create(device, decim, 48000, nchannels, ch, taps, ntaps, max_write_iq, out);
 }
 
-static void chan_launch_level(const jaero_chan *c, int nblk, hipStream_t st)
+// levels, block statistics or both in one pass over spec (p0: absolute index of the write's first block, for `when`)
+template <bool LEVEL, bool ACT>
+static void chan_launch_level(const jaero_chan *c, int nblk, long long p0, hipStream_t st)
 {
     auto go = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)((c->nch + CHAN_LVL_THREADS / CHAN_LVL_T - 1) / (CHAN_LVL_THREADS / CHAN_LVL_T))),
                            dim3(CHAN_LVL_THREADS), 0, st, (const double2 *)c->d_spec, (const double *)c->d_g2, (const ChanParam *)c->d_par,
-                           c->d_lvl, c->nch, nblk);
+                           c->d_lvl, c->nch, nblk, c->act, p0);
     };
-    if (c->decim == 16) go(k_chan_level<16>);
-    else if (c->decim == 32) go(k_chan_level<32>);
-    else if (c->decim == 64) go(k_chan_level<64>);
-    else if (c->decim == 128) go(k_chan_level<128>);
-    else go(k_chan_level<256>);
+    if (c->decim == 16) go(k_chan_level<16, LEVEL, ACT>);
+    else if (c->decim == 32) go(k_chan_level<32, LEVEL, ACT>);
+    else if (c->decim == 64) go(k_chan_level<64, LEVEL, ACT>);
+    else if (c->decim == 128) go(k_chan_level<128, LEVEL, ACT>);
+    else go(k_chan_level<256, LEVEL, ACT>);
 }
 
 static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipStream_t st)
@@ -204,7 +214,7 @@ static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipSt
     else go(k_chan_synth<256>, ChanShape<256>::ITEMS, ChanShape<256>::THREADS);
 }
 
-// What every write does behind its forward transform of nblk > 0 blocks: the synthesis, the survey's kernels when enabled, then the last
+// What every write does behind its forward transform of nblk > 0 blocks: the synthesis, the survey's and the activity's kernels when enabled, then the last
 // hop and what lies behind it (`total` samples wait in `hist`, of `elem` bytes each) become the head of the other history buffer `other`.
 static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, void *other, size_t elem, hipStream_t st)
 {
@@ -212,21 +222,35 @@ static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, 
     chan_launch_synth(c, nblk, c->blocks_done, st);
     LAUNCHCHK("k_chan_synth");
     c->timer.end(pi, st);
-    if (c->survey & 1)
+    // one launch of k_chan_psd serves the survey's spectrum, the activity's peak or both; timed under the activity's slot when it serves that
+    const bool sum = c->survey & 1, peak = c->activity & 1;
+    if (sum || peak)
     {
-        pi = c->timer.begin(2, st);
-        hipLaunchKernelGGL(k_chan_psd, dim3(CHAN_N / CHAN_PSD_THREADS), dim3(CHAN_PSD_THREADS), 0, st, (const double2 *)c->d_spec, c->d_psd, nblk);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(CHAN_N / CHAN_PSD_THREADS), dim3(CHAN_PSD_THREADS), 0, st, (const double2 *)c->d_spec, c->d_psd, nblk,
+                               c->d_peak);
+        };
+        pi = c->timer.begin(peak ? 6 : 2, st);
+        if (sum && peak) go(k_chan_psd<true, true>);
+        else if (sum) go(k_chan_psd<true, false>);
+        else go(k_chan_psd<false, true>);
         LAUNCHCHK("k_chan_psd");
         c->timer.end(pi, st);
-        c->psd_blocks += nblk;
+        if (sum) c->psd_blocks += nblk;
+        if (peak) c->peak_blocks += nblk;
     }
-    if (c->survey & 2)
+    // and one of k_chan_level the levels, the block statistics or both
+    const bool lvl = c->survey & 2, blk = c->activity & 2;
+    if (lvl || blk)
     {
-        pi = c->timer.begin(3, st);
-        chan_launch_level(c, nblk, st);
+        pi = c->timer.begin(blk ? 7 : 3, st);
+        if (lvl && blk) chan_launch_level<true, true>(c, nblk, c->blocks_done, st);
+        else if (lvl) chan_launch_level<true, false>(c, nblk, c->blocks_done, st);
+        else chan_launch_level<false, true>(c, nblk, c->blocks_done, st);
         LAUNCHCHK("k_chan_level");
         c->timer.end(pi, st);
-        c->lvl_blocks += nblk;
+        if (lvl) c->lvl_blocks += nblk;
+        if (blk) c->act_blocks += nblk;
     }
     const int rest = total - nblk * CHAN_HP;
     HIPCHK(hipMemcpyAsync(other, (const char *)hist + (size_t)nblk * CHAN_HP * elem, elem * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
@@ -305,6 +329,19 @@ extern "C" int jaero_chan_read_pcm(jaero_chan *c, int16_t *dst, int cap_per_chan
     return 0;
 }
 
+// The block statistics of channels [first, end) as they are before a channel's first block: when = -1 (what the kernel reads as "no block
+// yet"; emax and emin are then not read, and are zeroed only so that the memory is defined), hist = 0.
+static int activity_clear_blocks(jaero_chan *c, int first, int end)
+{
+    const size_t n = (size_t)(end - first);
+    HIPCHK(hipMemset(c->act.emax + first, 0, sizeof(double) * n));
+    HIPCHK(hipMemset(c->act.emin + first, 0, sizeof(double) * n));
+    HIPCHK(hipMemset(c->act.when + first, 0xff, sizeof(long long) * n));
+    HIPCHK(hipMemset(c->act.hist + (size_t)first * CHAN_ACT_BINS, 0, sizeof(unsigned) * CHAN_ACT_BINS * n));
+    for (int i = first; i < end; i++) c->act_start[i] = c->act_blocks;
+    return 0;
+}
+
 extern "C" int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_channel *ch)
 {
     if (!c || !ch || channel < 0 || channel >= c->nch) return fail(JAERO_EINVAL, "jaero_chan_retune: bad arguments");
@@ -319,6 +356,11 @@ extern "C" int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_ch
     {
         HIPCHK(hipMemset(c->d_lvl + channel, 0, sizeof(double)));
         c->lvl_start[channel] = c->lvl_blocks;
+    }
+    if ((c->activity & 2) && ch->tune != c->channels[channel].tune) // and so do its block statistics
+    {
+        const int rc = activity_clear_blocks(c, channel, channel + 1);
+        if (rc) return rc;
     }
     c->channels[channel] = *ch;
     c->poisoned = false;
@@ -338,19 +380,20 @@ extern "C" int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *c
     for (int i = 0; i < c->nch; i++) par[i] = chan_param(ch[i], c->decim);
     c->poisoned = true; // the words, the sums and the counts change together or not at all
     HIPCHK(hipMemcpy(c->d_par, par.data(), sizeof(ChanParam) * c->nch, hipMemcpyHostToDevice));
-    if (c->survey & 2)
+    if ((c->survey & 2) || (c->activity & 2))
     {
-        int first = -1; // the channels whose tune word changes, zeroed a run at a time
+        int first = -1; // the channels whose tune word changes, cleared a run at a time
         for (int i = 0; i <= c->nch; i++)
         {
             const bool moved = i < c->nch && ch[i].tune != c->channels[i].tune;
             if (moved && first < 0) first = i;
             if (!moved && first >= 0)
             {
-                HIPCHK(hipMemset(c->d_lvl + first, 0, sizeof(double) * (size_t)(i - first)));
+                if (c->survey & 2) HIPCHK(hipMemset(c->d_lvl + first, 0, sizeof(double) * (size_t)(i - first)));
+                if (c->activity & 2) { const int rc = activity_clear_blocks(c, first, i); if (rc) return rc; }
                 first = -1;
             }
-            if (moved) c->lvl_start[i] = c->lvl_blocks;
+            if (moved && (c->survey & 2)) c->lvl_start[i] = c->lvl_blocks;
         }
     }
     c->channels.assign(ch, ch + c->nch);
@@ -411,6 +454,27 @@ static int survey_clear(jaero_chan *c)
     return 0;
 }
 
+// The table k_chan_level multiplies by, built by whichever of the levels and the block statistics is enabled first: |G / N|^2 of the
+// response the synthesis multiplies by, from its order (k < M / 2: q = k, else q = k - M) to ascending q
+static int chan_build_g2(jaero_chan *c)
+{
+    if (c->d_g2) return 0;
+    int rc = 0;
+    double *d_g2 = nullptr;
+    DA(c->mem, d_g2, c->M);
+    std::vector<double2> gm(c->M);
+    std::vector<double> g2(c->M);
+    HIPCHK(hipMemcpy(gm.data(), c->d_gm, sizeof(double2) * c->M, hipMemcpyDeviceToHost));
+    for (int i = 0; i < c->M; i++)
+    {
+        const double2 g = gm[(i - c->M / 2) & (c->M - 1)];
+        g2[i] = g.x * g.x + g.y * g.y;
+    }
+    HIPCHK(hipMemcpy(d_g2, g2.data(), sizeof(double) * c->M, hipMemcpyHostToDevice));
+    c->d_g2 = d_g2;
+    return 0;
+}
+
 extern "C" int jaero_survey_enable(jaero_chan *c, int what)
 {
     if (what < 0 || what > 3) return fail(JAERO_EINVAL, "jaero_survey_enable: what %d has bits outside 0..3", what);
@@ -420,22 +484,10 @@ extern "C" int jaero_survey_enable(jaero_chan *c, int what)
     HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far are surveyed as they were enqueued
     int rc = 0;
     if ((what & 1) && !c->d_psd) DA(c->mem, c->d_psd, CHAN_N);
-    if ((what & 2) && !c->d_g2)
+    if (what & 2)
     {
         if (!c->d_lvl) DA(c->mem, c->d_lvl, c->nch);
-        double *d_g2 = nullptr;
-        DA(c->mem, d_g2, c->M);
-        // |G / N|^2 of the response the synthesis multiplies by, from its order (k < M / 2: q = k, else q = k - M) to ascending q
-        std::vector<double2> gm(c->M);
-        std::vector<double> g2(c->M);
-        HIPCHK(hipMemcpy(gm.data(), c->d_gm, sizeof(double2) * c->M, hipMemcpyDeviceToHost));
-        for (int i = 0; i < c->M; i++)
-        {
-            const double2 g = gm[(i - c->M / 2) & (c->M - 1)];
-            g2[i] = g.x * g.x + g.y * g.y;
-        }
-        HIPCHK(hipMemcpy(d_g2, g2.data(), sizeof(double) * c->M, hipMemcpyHostToDevice));
-        c->d_g2 = d_g2; // the levels can be enabled only with the table in place
+        if ((rc = chan_build_g2(c))) return rc; // the levels can be enabled only with the table in place
     }
     c->survey = what;
     rc = survey_clear(c);
@@ -480,6 +532,94 @@ extern "C" int jaero_survey_profile_read(jaero_chan *c, int which, double *total
 {
     if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_survey_profile_read: bad arguments");
     return c->timer.read(c->device, 2 + which, total_ms, launches, reset);
+}
+
+// ------------------------------------------------------------------------------------------ activity
+static_assert(CHAN_ACT_BINS == JAERO_ACT_BINS, "the kernel's row of hist is the ABI's");
+static int activity_clear(jaero_chan *c)
+{
+    if (c->activity & 1)
+    {
+        HIPCHK(hipMemset(c->d_peak, 0, sizeof(double) * CHAN_N));
+        c->peak_blocks = 0;
+    }
+    if (c->activity & 2)
+    {
+        c->act_blocks = 0;
+        c->act_start.assign(c->nch, 0);
+        return activity_clear_blocks(c, 0, c->nch);
+    }
+    return 0;
+}
+
+extern "C" int jaero_activity_enable(jaero_chan *c, int what)
+{
+    if (what < 0 || what > 3) return fail(JAERO_EINVAL, "jaero_activity_enable: what %d has bits outside 0..3", what);
+    if (!c) return fail(JAERO_EINVAL, "jaero_activity_enable: null ctx");
+    CHANPOISONCHK(c, "jaero_activity_enable");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far are measured as they were enqueued
+    int rc = 0;
+    if ((what & 1) && !c->d_peak) DA(c->mem, c->d_peak, CHAN_N);
+    if (what & 2)
+    {
+        if (!c->act.emax) DA(c->mem, c->act.emax, c->nch);
+        if (!c->act.emin) DA(c->mem, c->act.emin, c->nch);
+        if (!c->act.when) DA(c->mem, c->act.when, c->nch);
+        if (!c->act.hist) DA(c->mem, c->act.hist, (size_t)c->nch * CHAN_ACT_BINS);
+        if ((rc = chan_build_g2(c))) return rc; // the statistics can be enabled only with the table in place
+    }
+    c->activity = what;
+    rc = activity_clear(c);
+    if (rc) c->activity = 0; // a failed clear leaves the activity off
+    return rc;
+}
+
+extern "C" int jaero_activity_reset(jaero_chan *c)
+{
+    if (!c) return fail(JAERO_EINVAL, "jaero_activity_reset: null ctx");
+    CHANPOISONCHK(c, "jaero_activity_reset");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    return activity_clear(c);
+}
+
+extern "C" int jaero_activity_read_peak(jaero_chan *c, double *peak, long long *nblocks)
+{
+    if (!c || !peak || !nblocks) return fail(JAERO_EINVAL, "jaero_activity_read_peak: null argument");
+    if (!(c->activity & 1)) return fail(JAERO_EINVAL, "jaero_activity_read_peak: the peak-hold spectrum is not enabled (jaero_activity_enable bit 0)");
+    CHANPOISONCHK(c, "jaero_activity_read_peak");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    HIPCHK(hipMemcpy(peak, c->d_peak, sizeof(double) * CHAN_N, hipMemcpyDeviceToHost));
+    *nblocks = c->peak_blocks;
+    return 0;
+}
+
+extern "C" int jaero_activity_read_blocks(jaero_chan *c, double *emax, double *emin, long long *when, long long *nblocks, unsigned *hist)
+{
+    if (!c || !emax || !emin || !when || !nblocks) return fail(JAERO_EINVAL, "jaero_activity_read_blocks: null argument");
+    if (!(c->activity & 2)) return fail(JAERO_EINVAL, "jaero_activity_read_blocks: the block statistics are not enabled (jaero_activity_enable bit 1)");
+    CHANPOISONCHK(c, "jaero_activity_read_blocks");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    const size_t n = (size_t)c->nch;
+    HIPCHK(hipMemcpy(emax, c->act.emax, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(emin, c->act.emin, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(when, c->act.when, sizeof(long long) * n, hipMemcpyDeviceToHost));
+    if (hist) HIPCHK(hipMemcpy(hist, c->act.hist, sizeof(unsigned) * CHAN_ACT_BINS * n, hipMemcpyDeviceToHost));
+    for (int i = 0; i < c->nch; i++)
+    {
+        nblocks[i] = c->act_blocks - c->act_start[i];
+        if (nblocks[i] == 0) { emax[i] = 0.0; emin[i] = __builtin_inf(); when[i] = -1; } // the definition's values of a channel without a block
+    }
+    return 0;
+}
+
+extern "C" int jaero_activity_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset)
+{
+    if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_activity_profile_read: bad arguments");
+    return c->timer.read(c->device, 6 + which, total_ms, launches, reset);
 }
 
 #include "capture_host.h"

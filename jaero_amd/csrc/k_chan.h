@@ -233,19 +233,30 @@ __global__ __launch_bounds__(ChanShape<D>::THREADS) void k_chan_synth(const doub
 // thread and block the walk over the blocks is bound by latency, and this spreads it over every CU.  Neither choice has been measured
 // against its alternative (neighbours by shuffle, wider workgroups); the whole kernel is timed in DESIGN 18.
 #define CHAN_PSD_THREADS 64
-__global__ __launch_bounds__(CHAN_PSD_THREADS) void k_chan_psd(const double2 *__restrict__ spec, double *__restrict__ S, int nblk)
+// SUM: S[k] += |H_p[k]|^2 (the survey's spectrum).  PEAK: P[k] = max(P[k], |H_p[k]|^2) (the activity's peak-hold spectrum, jaero_activity_*):
+// the same term, formed once, so that S and P of one block are the same bits.  Either or both in one pass over the three loads; a pointer
+// whose part is off is never touched.  <true, false> must stay the code of a kernel that only sums (profiles/chan_activity_isa.md).
+template <bool SUM, bool PEAK>
+__global__ __launch_bounds__(CHAN_PSD_THREADS) void k_chan_psd(const double2 *__restrict__ spec, double *__restrict__ S, int nblk,
+                                                               double *__restrict__ P)
 {
+    static_assert(SUM || PEAK, "a launch that keeps nothing");
     const int k = blockIdx.x * CHAN_PSD_THREADS + threadIdx.x; // the grid is N / CHAN_PSD_THREADS workgroups: k < N
     const int km = (k - 1) & (CHAN_N - 1), kp = (k + 1) & (CHAN_N - 1);
-    double s = S[k];
+    double s = 0.0, pk = 0.0;
+    if constexpr (SUM) s = S[k];
+    if constexpr (PEAK) pk = P[k];
     for (int j = 0; j < nblk; j++)
     {
         const double2 *__restrict__ X = spec + (size_t)j * CHAN_N;
         const double2 a = X[km], x = X[k], b = X[kp];
         const double hr = 0.5 * x.x - 0.25 * (a.x + b.x), hi = 0.5 * x.y - 0.25 * (a.y + b.y);
-        s += hr * hr + hi * hi;
+        const double v = hr * hr + hi * hi;
+        if constexpr (SUM) s += v;
+        if constexpr (PEAK) pk = v > pk ? v : pk;
     }
-    S[k] = s;
+    if constexpr (SUM) S[k] = s;
+    if constexpr (PEAK) P[k] = pk;
 }
 
 // Per-channel level: E[c] += sum_q |X_p[(b + q) mod N]|^2 g2[q + M / 2], -M/2 <= q < M/2, g2 = |G[q mod N]|^2 / N^2 (built at enable from
@@ -255,12 +266,38 @@ __global__ __launch_bounds__(CHAN_PSD_THREADS) void k_chan_psd(const double2 *__
 // fixed), and lane 0 adds the block's sum to the running one it loaded once and stores once.  T = 16 for every M: 16 channels per
 // workgroup fill the chip from 4096 channels on, and M / 16 = 4 .. 64 independent 16-byte loads per lane and block hide the L2 latency.
 // The table sits in LDS (M doubles).  Spare groups of the last workgroup redo the last channel and store nothing.
+//
+// ACT: the activity's block statistics (jaero_activity_*) of the same block sums e_{c,p} = acc, so that levels + statistics walk spec once.
+// Behind the butterfly every lane of the group holds acc, so nothing is exchanged: lane 0 keeps emax / emin / when over the write's
+// blocks in registers (one load and one store of each per write), and the 64-bin histogram lives in the group's registers too -- lane u
+// counts the bins u, u + 16, u + 32, u + 48 with four compares per block and adds its four counts to its own words of the channel's row
+// once per write.  One owner per word, plain loads and stores, integers: no atomics, and the result is independent of how the writes were
+// cut.  when[c] < 0 says that the channel has no block yet (emax / emin are then not read).  <D, true, false> must stay the code of a
+// kernel that only sums the levels (profiles/chan_activity_isa.md).
 #define CHAN_LVL_T 16
 #define CHAN_LVL_THREADS 256
-template <int D>
-__global__ __launch_bounds__(CHAN_LVL_THREADS) void k_chan_level(const double2 *__restrict__ spec, const double *__restrict__ g2,
-                                                                 const ChanParam *__restrict__ par, double *__restrict__ E, int nch, int nblk)
+#define CHAN_ACT_BINS 64
+struct ChanAct // the block statistics' state, one entry (one row of hist) per channel
 {
+    double *emax, *emin;   // [nch]
+    long long *when;       // [nch]: absolute block index of emax, -1 before the first block
+    unsigned *hist;        // [nch][CHAN_ACT_BINS]
+};
+
+// bin(e) = min(63, max(0, ilogb(e) + 32)), bin(0) = 0: from the exponent field (0 and the subnormals have field 0: bin 0)
+__device__ __forceinline__ int chan_act_bin(double e)
+{
+    const int ex = (int)((unsigned long long)__double_as_longlong(e) >> 52 & 0x7ff) - 1023 + 32;
+    return ex < 0 ? 0 : ex > CHAN_ACT_BINS - 1 ? CHAN_ACT_BINS - 1 : ex;
+}
+
+template <int D, bool LEVEL, bool ACT>
+__global__ __launch_bounds__(CHAN_LVL_THREADS) void k_chan_level(const double2 *__restrict__ spec, const double *__restrict__ g2,
+                                                                 const ChanParam *__restrict__ par, double *__restrict__ E, int nch, int nblk,
+                                                                 ChanAct act, long long p0)
+{
+    static_assert(LEVEL || ACT, "a launch that keeps nothing");
+    static_assert(CHAN_ACT_BINS == 4 * CHAN_LVL_T, "four bins per lane");
     constexpr int M = CHAN_N / D, T = CHAN_LVL_T, PER = M / T, UNROLL = PER < 8 ? PER : 8;
     __shared__ double tbl[M];
     for (int i = threadIdx.x; i < M; i += CHAN_LVL_THREADS) tbl[i] = g2[i];
@@ -271,7 +308,16 @@ __global__ __launch_bounds__(CHAN_LVL_THREADS) void k_chan_level(const double2 *
     const int c = live ? c_raw : nch - 1;
     const int k0 = par[c].b - M / 2 + u;
     const bool owner = live && u == 0;
-    double e = owner ? E[c] : 0.0;
+    double e = 0.0;
+    if constexpr (LEVEL) e = owner ? E[c] : 0.0;
+    double emax = 0.0, emin = 0.0;
+    long long when = -1;
+    unsigned h0 = 0, h1 = 0, h2 = 0, h3 = 0;
+    if constexpr (ACT)
+    {
+        when = act.when[c];
+        if (when >= 0) { emax = act.emax[c]; emin = act.emin[c]; }
+    }
     for (int j = 0; j < nblk; j++)
     {
         const double2 *__restrict__ X = spec + (size_t)j * CHAN_N;
@@ -284,7 +330,24 @@ __global__ __launch_bounds__(CHAN_LVL_THREADS) void k_chan_level(const double2 *
         }
 #pragma unroll
         for (int m = T / 2; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, T);
-        e += acc;
+        if constexpr (LEVEL) e += acc;
+        if constexpr (ACT)
+        {
+            const bool first = when < 0;
+            if (first || acc > emax) { emax = acc; when = p0 + j; } // strictly above: the smallest block index of the maximum stays
+            if (first || acc < emin) emin = acc;
+            const int bin = chan_act_bin(acc) - u;
+            h0 += bin == 0; h1 += bin == T; h2 += bin == 2 * T; h3 += bin == 3 * T;
+        }
     }
-    if (owner) E[c] = e;
+    if constexpr (LEVEL) { if (owner) E[c] = e; }
+    if constexpr (ACT)
+    {
+        if (owner) { act.emax[c] = emax; act.emin[c] = emin; act.when[c] = when; }
+        if (live)
+        {
+            unsigned *__restrict__ row = act.hist + (size_t)c * CHAN_ACT_BINS + u;
+            row[0] += h0; row[T] += h1; row[2 * T] += h2; row[3 * T] += h3;
+        }
+    }
 }

@@ -3,10 +3,13 @@ channel) per step.  Prints one JSON line: HIP-event time per step of k_chan_fwd 
 from the same steps, their ratio (the yardstick: the two channeliser kernels together against the demodulator bank's own step time), the
 same per second of signal and per output sample, the engine clock over the timed steps.  Defaults: the headline OQPSK bank behind D = 32.
 --survey: the survey (spectrum and levels) is on during the same steps; k_chan_psd and k_chan_level per step are printed beside the rest.
+--activity: the activity (peak-hold spectrum and block statistics) is on during the same steps.  Alone it launches the peak-only k_chan_psd and
+the statistics-only k_chan_level; with --survey every launch is the fused one (spectrum + peak, levels + statistics), timed once, under
+the activity's slots, so the survey's own slots then read zero.
 --capture FMT:FS_IN: the channeliser takes a capture of that format (cs16, cu8, cs8, cf32) at that rate through its capture front end; a step
 is then the capture samples that stage 16 hops, and k_capture_stage and k_capture_fwd are timed beside k_chan_synth (k_chan_fwd does not run).
 usage: python scripts/ubench/time_chan.py [channels] [steps] [warmup] [--decim D] [--fs-out 48000|24000|12000] [--bank oqpsk|msk600|msk1200] [--survey]
-       [--capture FMT:FS_IN]"""
+       [--activity] [--capture FMT:FS_IN]"""
 import argparse
 import json
 import os
@@ -30,6 +33,7 @@ ap.add_argument("--decim", type=int, default=32, help="total decimation, capture
 ap.add_argument("--fs-out", type=float, default=48000.0, help="the channeliser's output rate = the bank's Fs")
 ap.add_argument("--bank", choices=("oqpsk", "msk600", "msk1200"), default="oqpsk")
 ap.add_argument("--survey", action="store_true", help="survey the capture (spectrum and levels) in every step and time its two kernels")
+ap.add_argument("--activity", action="store_true", help="keep the peak-hold spectrum and the block statistics in every step and time their launches")
 ap.add_argument("--capture", default=None, metavar="FMT:FS_IN", help="feed a capture of this format and rate through the capture front end")
 args = ap.parse_args()
 nch, K, W, decim, fs_out, hops = args.channels, args.steps, args.warmup, args.decim, args.fs_out, 16
@@ -59,6 +63,8 @@ else:
     settings = MskSettings(fb=fb, lockingbw=1.5 * fb, Fs=fs_out)
 if args.survey:
     chan.survey_enable(psd=True, levels=True)
+if args.activity:
+    chan.activity_enable(peak=True, blocks=True)
 bank = DemodulatorBank(settings, nch, ebno=True, max_write_samples=(hops + 1) * chan.Mo, softbit_capacity=4096)
 st = torch.cuda.current_stream().cuda_stream
 for _ in range(W):
@@ -85,6 +91,13 @@ if args.survey:
     survey = {"k_chan_psd_ms_per_step": round(psd / K, 4), "k_chan_psd_launches": npsd,
               "k_chan_level_ms_per_step": round(lvl / K, 4), "k_chan_level_launches": nlvl,
               "k_chan_level_over_synth": round(lvl / syn, 4), "survey_blocks": int(chan.read_psd()[1])}
+if args.activity:
+    (pk, npk), (blk, nblk) = chan.activity_profile_read(0), chan.activity_profile_read(1)
+    fused = bool(args.survey)
+    survey.update({"activity_fused_with_survey": fused,
+                   "k_chan_psd_peak_ms_per_step": round(pk / K, 4), "k_chan_psd_peak_launches": npk,
+                   "k_chan_level_act_ms_per_step": round(blk / K, 4), "k_chan_level_act_launches": nblk,
+                   "k_chan_level_act_over_synth": round(blk / syn, 4), "activity_blocks": int(chan.read_peak_sums()[1])})
 cap = {}
 if capture is not None:
     (stg, nstg), (cfwd, ncf) = chan.capture_profile_read(0), chan.capture_profile_read(1)
