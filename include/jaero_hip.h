@@ -391,7 +391,7 @@ int jaero_ingest_stats(const jaero_ingest *ing, long long *three);
  * burst and OQPSK banks at other rates than 48 kHz (the reference has none either), the multi-GPU fan-out of a capture (every rank creates a
  * channeliser over its shard and is handed the same I/Q), automatic gain control inside the synthesis (it would change the output's
  * definition: the survey below measures, the caller sets the gains), carrier finding on the device (jaero_amd.channeliser.find_carriers is
- * host numpy over the surveyed spectrum), modulation recognition. */
+ * host numpy over the surveyed spectrum), modulation recognition beyond what the bit rate implies (the rate lines below measure that). */
 typedef struct jaero_chan jaero_chan;
 typedef struct jaero_chan_channel { uint32_t tune, audio; double gain; } jaero_chan_channel;
 int jaero_chan_create(int device, int decim, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps, int max_write_iq,
@@ -533,7 +533,7 @@ int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *ch);
  * Null arguments: JAERO_EINVAL before a device is touched.  A poisoned handle: JAERO_EHIP; a HIP failure inside the activity's launches
  * poisons the handle as any other failure inside a write.  Deliberately not here: thresholds or detection decisions on the device (the
  * histogram and the extremes are the measurement; jaero_amd.channeliser.duty_cycle and find_carriers decide in numpy), a time series of
- * block levels, modulation or bit-rate recognition. */
+ * block levels, modulation recognition (the bit rate is measured by the rate lines below). */
 #define JAERO_ACT_PEAK 1
 #define JAERO_ACT_BLOCKS 2
 #define JAERO_ACT_BINS 64
@@ -542,6 +542,49 @@ int jaero_activity_reset(jaero_chan *c);
 int jaero_activity_read_peak(jaero_chan *c, double *peak, long long *nblocks);
 int jaero_activity_read_blocks(jaero_chan *c, double *emax, double *emin, long long *when, long long *nblocks, unsigned *hist);
 int jaero_activity_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset);
+
+/* ---- rate lines: what a channel's bit rate is, measured from the int16 PCM a bank is fed (a channeliser's output or any other).  The
+ * spectrum of the SQUARED signal is the measurement JAERO trusts for acquisition (CoarseFreqEstimate): MSK with h = 0.5, squared, is
+ * Sunde's FSK with two lines at 2 f_audio +- fb / 2; OQPSK with the reference's RRC pulses, squared, has two lines at 2 f_audio +- 1 / T =
+ * 2 f_audio +- fb / 2.  Either way the lines are fb apart whatever the carrier offset is, and their midpoint gives the offset.  The device
+ * measures (one 4096-point fp64 transform per channel and segment), jaero_amd.ratemeter.classify_rates decides in numpy.  A handle
+ * jaero_rate is independent of every other handle: nchannels rows of int16, one row per channel; the sample rate enters no device
+ * arithmetic.  This text is the definition; tests/rate_oracle.py implements it literally in numpy.
+ *   L = 4096.  Segment j of a row y is y[j L .. (j + 1) L), samples counted from create: consecutive, not overlapping.
+ *   q[i]   = y[i]^2 - (sum_i y[i]^2) / L over the segment.  EXACT in fp64: the squares are integers below 2^31, their sum an integer below
+ *            2^43, the mean a multiple of 2^-12 below 2^31, the difference a multiple of 2^-12 below 2^31 in magnitude -- 43 bits.
+ *   Z      = DFT_L(q), Z[k] = sum_i q[i] e^(-j 2 pi k i / L).
+ *   H[k]   = Z[k] / 2 - (Z[(k - 1) mod L] + Z[(k + 1) mod L]) / 4: the Hann window, applied in the frequency domain as the survey does.
+ *   R_c[k] = sum_j |H_j[k]|^2 for 0 <= k <= L / 2: JAERO_RATE_BINS = 2049 doubles per channel, bin k at k fs / L Hz of the squared signal.
+ *            The sum runs over every segment completed since create or the last reset, added in ascending j; nseg is their number, the
+ *            same for every channel.
+ * Rules, the survey's: after T samples per row exactly floor(T / L) segments are in R, however the writes were cut; R is bit-identical for
+ * every cutting of the same rows and for host and device input (no floating-point atomics; a segment's terms are formed by the same
+ * instructions whatever the launch shape; terms join the sum in segment order); a row of zeros, or of any constant, gives R_c == 0
+ * exactly (q is then exactly zero; no two rows and no two segments share a transform).
+ *   jaero_rate_create    arguments are checked before a device is looked for: nchannels < 1, max_write_samples < 1 or out == NULL are
+ *                        JAERO_EINVAL; then JAERO_ENODEV off gfx950.
+ *   jaero_rate_write     pcm is compact channel-major [nchannels][nsamples]: what jaero_chan_pcm_view hands out and jaero_write takes with
+ *                        JAERO_PCM_CHANNEL_MAJOR; host or device memory.  *nseg_done = the segments this write completed.  nsamples < 0 or
+ *                        > max_write_samples: JAERO_EINVAL, nothing consumed.  Asynchronous on `stream`; a write on another stream than the
+ *                        previous one waits for it.  A failure behind the first launch that advances state poisons the handle (JAERO_EHIP
+ *                        from then on), as a channeliser's write does.
+ *   jaero_rate_reset     synchronises on the handle's last stream, clears R and nseg.  The pending partial segment is kept: the segment
+ *                        grid stays absolute.
+ *   jaero_rate_read      synchronises on the handle's last stream; sums[nchannels][2049] = R, *nseg.
+ *   jaero_rate_profile_* HIP-event time since the last reset: which 0 = the line kernel (k_rate_lines).
+ * Deliberately not here: the decision (classify_rates is host numpy over 16 KB per channel), gating by activity (a burst channel's lines
+ * are diluted by its duty cycle; its rate must be taken while it is on), modulation recognition beyond what the rate implies, other L. */
+typedef struct jaero_rate jaero_rate;
+#define JAERO_RATE_L 4096
+#define JAERO_RATE_BINS 2049
+int jaero_rate_create(int device, int nchannels, int max_write_samples, jaero_rate **out);
+void jaero_rate_destroy(jaero_rate *r);
+int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples, int is_device_ptr, void *stream, int *nseg_done);
+int jaero_rate_reset(jaero_rate *r);
+int jaero_rate_read(jaero_rate *r, double *sums /* [nchannels][2049] */, long long *nseg);
+int jaero_rate_profile_enable(jaero_rate *r, int on);
+int jaero_rate_profile_read(jaero_rate *r, int which /* 0 = the line kernel */, double *total_ms, int *launches, int reset);
 
 /* Host-only debugging aid (no device needed): the sample indices at which jaero_write would run the coarse-frequency
  * estimate for a fresh channel fed `nwrites` writes of write_sizes[i] samples.  Returns the number of triggers

@@ -19,6 +19,7 @@ PCM_CHANNEL_MAJOR, PCM_FRAME_MAJOR = 0, 1
 W_RATE = 1  # jaero_ingest_push: sample rate differs from the bank (warning, data queued)
 IQ_CS16, IQ_CU8, IQ_CS8, IQ_CF32 = 0, 1, 2, 3
 ACT_PEAK, ACT_BLOCKS, ACT_BINS = 1, 2, 64  # jaero_activity_enable: what; bins of a channel's histogram
+RATE_L, RATE_BINS = 4096, 2049  # jaero_rate: segment length, bins of a channel's row
 AEROL_SUS, AEROL_PACKETS, AEROL_EVENTS, AEROL_VOICE = 0, 1, 2, 3  # jaero_aerol_read_all: what
 BANK_SOFTBITS, BANK_STATUS_LOG, BANK_EVENTS, BANK_SYMBOLS = 0, 1, 2, 3  # jaero_read_all: what
 E_OK, E_INVAL, E_NODEV, E_NOMEM, E_HIP, E_OVERFLOW, E_NOTSUP = 0, -1, -2, -3, -4, -5, -6
@@ -48,6 +49,8 @@ EXPORTS = [
     "jaero_chan2_retune_all",
     "jaero_activity_enable", "jaero_activity_reset", "jaero_activity_read_peak", "jaero_activity_read_blocks", "jaero_activity_profile_read",
     "jaero_chan3_create", "jaero_chan3_write", "jaero_chan3_feed", "jaero_chan3_read_staged", "jaero_chan3_profile_read",
+    "jaero_rate_create", "jaero_rate_destroy", "jaero_rate_write", "jaero_rate_reset", "jaero_rate_read", "jaero_rate_profile_enable",
+    "jaero_rate_profile_read",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -273,7 +276,15 @@ def lib():
     L.jaero_chan3_feed.argtypes = [vp, vp, vp, ip, ip, vp, C.POINTER(ip)]
     L.jaero_chan3_read_staged.argtypes = [vp, vp, ip, C.POINTER(ip), C.POINTER(C.c_longlong)]
     L.jaero_chan3_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
-    L.jaero_shard_range.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
+    L.jaero_rate_create.argtypes = [ip, ip, ip, C.POINTER(vp)]
+    L.jaero_rate_destroy.argtypes = [vp]
+    L.jaero_rate_destroy.restype = None
+    L.jaero_rate_write.argtypes = [vp, vp, ip, ip, vp, C.POINTER(ip)]
+    L.jaero_rate_reset.argtypes = [vp]
+    L.jaero_rate_read.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
+    L.jaero_rate_profile_enable.argtypes = [vp, ip]
+    L.jaero_rate_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
+    L.jaero_shard_range.argtypes =[ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.jaero_comm_get_unique_id.argtypes = [vp]
     L.jaero_comm_create.argtypes = [ip, ip, ip, vp, C.POINTER(vp)]
     L.jaero_comm_destroy.argtypes = [vp]

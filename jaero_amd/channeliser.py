@@ -209,6 +209,7 @@ class Channeliser:
         self.M = N // self.decim
         self.Mo = self.M // 2
         self.last_nout = 0
+        self.last_stream = 0  # the stream of the last write / feed (RateMeter.write_from follows it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -267,7 +268,7 @@ class Channeliser:
         nout = C.c_int(0)
         fn = self.L.jaero_chan_write if self.capture is None else self.L.jaero_chan3_write
         capi.check(fn(self.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
-        self.last_nout = nout.value
+        self.last_nout, self.last_stream = nout.value, stream
         return nout.value
 
     def feed(self, bank, iq, stream: int = 0) -> int:
@@ -276,7 +277,7 @@ class Channeliser:
         nout = C.c_int(0)
         fn = self.L.jaero_chan_feed if self.capture is None else self.L.jaero_chan3_feed
         capi.check(fn(self.h, bank.h, ptr, n, dev, C.c_void_p(stream), C.byref(nout)))
-        self.last_nout = nout.value
+        self.last_nout, self.last_stream = nout.value, stream
         return nout.value
 
     def read_staged(self) -> Tuple[np.ndarray, int]:

@@ -1860,6 +1860,7 @@ extern "C" int jaero_viterbi_continuous(int device, const uint8_t *soft, int nst
 #include "ingest_host.h"
 #include "edge_host.h"
 #include "chan_host.h"
+#include "rate_host.h"
 
 // ------------------------------------------------------------------------------------------ one-call reads of every channel
 // (here, behind aerol_host.h: the sweep's kernels stay where they were in the code object, behind the banks' own)

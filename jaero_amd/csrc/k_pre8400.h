@@ -145,30 +145,34 @@ __global__ __launch_bounds__(64) void k_pre8400_commit(const JGeom g, const JPtr
 //   with the direct form; the soft-symbol tolerance applies.
 #define PF_THREADS 1024
 
+// NC: channels per workgroup (the LDS address of entry L of channel c is NC L + c); 4 in both overlap-save filters, 2 in k_rate_lines
+template <int NC = 4>
 __device__ __forceinline__ void pf_exchange1(double (&v)[16], double *xch, int T, int c)
 {
-    const int wb = T * 4 + c, rb = ((T >> 4) * 256 + (T & 15)) * 4 + c;
+    const int wb = T * NC + c, rb = ((T >> 4) * 256 + (T & 15)) * NC + c;
 #pragma unroll
-    for (int s = 0; s < 16; s++) xch[wb + s * 1024] = v[s];
+    for (int s = 0; s < 16; s++) xch[wb + s * 256 * NC] = v[s];
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 16; s++) v[s] = xch[rb + s * 64];
+    for (int s = 0; s < 16; s++) v[s] = xch[rb + s * 16 * NC];
     jd_lds_barrier();
 }
 
+template <int NC = 4>
 __device__ __forceinline__ void pf_exchange2(double (&v)[16], double *xch, int T, int c)
 {
     const int hi = T >> 4, lo = T & 15;
     // writer: k1 = hi, m2 = lo, slot q1; reader: q1 = hi, k1 = lo, slot m2
-    const int wb = (lo * 16 + (hi ^ lo)) * 4 + c;
+    const int wb = (lo * 16 + (hi ^ lo)) * NC + c;
 #pragma unroll
-    for (int s = 0; s < 16; s++) xch[wb + s * 1024] = v[s];
+    for (int s = 0; s < 16; s++) xch[wb + s * 256 * NC] = v[s];
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 16; s++) v[s] = xch[((hi * 16 + s) * 16 + (lo ^ s)) * 4 + c];
+    for (int s = 0; s < 16; s++) v[s] = xch[((hi * 16 + s) * 16 + (lo ^ s)) * NC + c];
     jd_lds_barrier();
 }
 
+template <int NC = 4>
 __device__ __forceinline__ void pf_fft4096(CV<16> &d, double *xch, const double2 *__restrict__ tw, int T, int c)
 {
 #pragma clang fp contract(fast)
@@ -176,12 +180,12 @@ __device__ __forceinline__ void pf_fft4096(CV<16> &d, double *xch, const double2
     CV<16> o;
     regfft<16>(d, o);
     c4_twiddle16(o, st1);
-    pf_exchange1(o.r, xch, T, c);
-    pf_exchange1(o.i, xch, T, c);
+    pf_exchange1<NC>(o.r, xch, T, c);
+    pf_exchange1<NC>(o.i, xch, T, c);
     regfft<16>(o, d);
     c4_twiddle16(d, st2);
-    pf_exchange2(d.r, xch, T, c);
-    pf_exchange2(d.i, xch, T, c);
+    pf_exchange2<NC>(d.r, xch, T, c);
+    pf_exchange2<NC>(d.i, xch, T, c);
     regfft<16>(d, o);
 #pragma unroll
     for (int s = 0; s < 16; s++) { d.r[s] = o.r[s]; d.i[s] = o.i[s]; }

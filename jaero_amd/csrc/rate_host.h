@@ -1,0 +1,162 @@
+// rate_host.h -- host side of the rate meter (k_rate.h; include/jaero_hip.h, "rate lines"; DESIGN 18, "Rate lines").
+//
+// One jaero_rate keeps, for nch rows of int16 PCM, the sums R [nch][2049] of the squared signal's windowed power spectrum over every
+// completed 4096-sample segment.  State between writes: the pending partial segment ([nch][4096] int16, `fill` samples a row), the sums and
+// the segment count.  A write that completes a segment launches k_rate_lines over (pending, write) and then stores the write's tail as the
+// new pending segment; one that completes none appends to it.  Two pending buffers take turns, as the channeliser's history does: the
+// tail is stored into the one the launch did not read.
+#pragma once
+#include "k_rate.h"
+
+static_assert(RATE_L == JAERO_RATE_L && RATE_BINS == JAERO_RATE_BINS, "the kernel's segment and row are the ABI's");
+
+struct jaero_rate
+{
+    int device = 0, nch = 0, max_write = 0;
+    DevMem mem;
+    int16_t *d_pend[2] = {nullptr, nullptr}; // [nch][4096] each; d_pend[cur] holds `fill` samples a row
+    int cur = 0, fill = 0;
+    int16_t *d_in = nullptr;                 // [nch][max_write]: where a write from host memory is staged; allocated by the first one
+    double2 *d_tw = nullptr;                 // [4096]: exp(-2 pi i k / 4096)
+    double *d_R = nullptr;                   // [nch][2049]
+    long long nseg = 0;
+    KernelTimer timer{1};                    // 0 k_rate_lines
+    hipStream_t last_stream = nullptr;
+    hipEvent_t order_ev = nullptr;
+    bool poisoned = false;
+};
+
+#define RATEPOISONCHK(r, who) do { if ((r)->poisoned) return fail(JAERO_EHIP, who ": an earlier write of this rate meter failed part-way; destroy it and create a new one"); } while (0)
+
+extern "C" void jaero_rate_destroy(jaero_rate *r)
+{
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    (void)hipStreamSynchronize(r->last_stream);
+    if (r->order_ev) (void)hipEventDestroy(r->order_ev);
+    delete r;
+}
+
+static int rate_build(std::unique_ptr<jaero_rate> &r, int device, int nchannels, int max_write_samples)
+{
+    int rc = 0;
+    r->device = device; r->nch = nchannels; r->max_write = max_write_samples;
+    DA(r->mem, r->d_pend[0], (size_t)nchannels * RATE_L);
+    DA(r->mem, r->d_pend[1], (size_t)nchannels * RATE_L);
+    DA(r->mem, r->d_R, (size_t)nchannels * RATE_BINS);
+    DA(r->mem, r->d_tw, RATE_L);
+    std::vector<double2> tw(RATE_L); // rounded from long double, as the overlap-save filters' table is (fft4096_tables)
+    for (int k = 0; k < RATE_L; k++)
+    {
+        const long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)RATE_L;
+        tw[k].x = (double)cosl(a); tw[k].y = (double)sinl(a);
+    }
+    HIPCHK(hipMemcpy(r->d_tw, tw.data(), sizeof(double2) * RATE_L, hipMemcpyHostToDevice));
+    HIPCHK(hipFuncSetAttribute((const void *)k_rate_lines, hipFuncAttributeMaxDynamicSharedMemorySize, RATE_NC * RATE_L * (int)sizeof(double)));
+    return 0;
+}
+
+extern "C" int jaero_rate_create(int device, int nchannels, int max_write_samples, jaero_rate **out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_rate_create: out is null");
+    *out = nullptr;
+    if (nchannels < 1) return fail(JAERO_EINVAL, "jaero_rate_create: nchannels %d < 1", nchannels);
+    if (max_write_samples < 1) return fail(JAERO_EINVAL, "jaero_rate_create: max_write_samples %d < 1", max_write_samples);
+    { const int rc = open_device(device); if (rc) return rc; }
+    std::unique_ptr<jaero_rate> r(new (std::nothrow) jaero_rate());
+    if (!r) return fail(JAERO_ENOMEM, "jaero_rate_create: out of memory");
+    const int rc = rate_build(r, device, nchannels, max_write_samples);
+    if (rc) return rc;
+    *out = r.release();
+    return 0;
+}
+
+extern "C" int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples, int is_device_ptr, void *stream, int *nseg_done)
+{
+    if (!r || !nseg_done || (nsamples > 0 && !pcm)) return fail(JAERO_EINVAL, "jaero_rate_write: null argument");
+    if (nsamples < 0 || nsamples > r->max_write)
+        return fail(JAERO_EINVAL, "jaero_rate_write: nsamples %d outside [0, max_write_samples = %d]", nsamples, r->max_write);
+    RATEPOISONCHK(r, "jaero_rate_write");
+    HIPCHK(hipSetDevice(r->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (st != r->last_stream) // a write on another stream than the previous one waits for what was enqueued there
+    {
+        if (!r->order_ev) HIPCHK(hipEventCreateWithFlags(&r->order_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(r->order_ev, r->last_stream));
+        HIPCHK(hipStreamWaitEvent(st, r->order_ev, 0));
+        r->last_stream = st;
+    }
+    *nseg_done = 0;
+    if (nsamples == 0) return 0;
+    const int n = nsamples, fill = r->fill;
+    const int nseg = (int)(((long long)fill + n) / RATE_L), rest = (int)((long long)fill + n - (long long)nseg * RATE_L);
+    const size_t row = sizeof(int16_t) * (size_t)n;
+    const hipMemcpyKind kind = is_device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (nseg == 0) // no segment completes: the write joins the pending one
+    {
+        r->poisoned = true;
+        HIPCHK(hipMemcpy2DAsync(r->d_pend[r->cur] + fill, sizeof(int16_t) * RATE_L, pcm, row, row, (size_t)r->nch, kind, st));
+        r->fill = fill + n;
+        r->poisoned = false;
+        return 0;
+    }
+    const int16_t *src = pcm;
+    if (!is_device_ptr)
+    {
+        if (!r->d_in) { const int rc = dalloc(r->mem, &r->d_in, (size_t)r->nch * r->max_write, false); if (rc) return rc; }
+        HIPCHK(hipMemcpyAsync(r->d_in, pcm, row * (size_t)r->nch, hipMemcpyHostToDevice, st));
+        src = r->d_in;
+    }
+    r->poisoned = true; // from here on the sums, the count and the pending segment advance together or not at all
+    const int pi = r->timer.begin(0, st);
+    hipLaunchKernelGGL(k_rate_lines, dim3((unsigned)((r->nch + RATE_NC - 1) / RATE_NC)), dim3(RATE_THREADS), RATE_NC * RATE_L * sizeof(double), st,
+                       (const int16_t *)r->d_pend[r->cur], fill, src, n, r->nch, nseg, (const double2 *)r->d_tw, r->d_R);
+    LAUNCHCHK("k_rate_lines");
+    r->timer.end(pi, st);
+    // the tail behind the last completed segment lies wholly in this write (fill < 4096 <= 4096 nseg)
+    if (rest > 0)
+        HIPCHK(hipMemcpy2DAsync(r->d_pend[r->cur ^ 1], sizeof(int16_t) * RATE_L, src + (n - rest), row, sizeof(int16_t) * (size_t)rest,
+                                (size_t)r->nch, hipMemcpyDeviceToDevice, st));
+    r->cur ^= 1;
+    r->fill = rest;
+    r->nseg += nseg;
+    HIPCHK(hipGetLastError());
+    *nseg_done = nseg;
+    r->poisoned = false;
+    return 0;
+}
+
+extern "C" int jaero_rate_reset(jaero_rate *r)
+{
+    if (!r) return fail(JAERO_EINVAL, "jaero_rate_reset: null handle");
+    RATEPOISONCHK(r, "jaero_rate_reset");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    HIPCHK(hipMemset(r->d_R, 0, sizeof(double) * (size_t)r->nch * RATE_BINS));
+    r->nseg = 0; // the pending segment stays: the segment grid is absolute
+    return 0;
+}
+
+extern "C" int jaero_rate_read(jaero_rate *r, double *sums, long long *nseg)
+{
+    if (!r || !sums || !nseg) return fail(JAERO_EINVAL, "jaero_rate_read: null argument");
+    RATEPOISONCHK(r, "jaero_rate_read");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    HIPCHK(hipMemcpy(sums, r->d_R, sizeof(double) * (size_t)r->nch * RATE_BINS, hipMemcpyDeviceToHost));
+    *nseg = r->nseg;
+    return 0;
+}
+
+extern "C" int jaero_rate_profile_enable(jaero_rate *r, int on)
+{
+    if (!r) return fail(JAERO_EINVAL, "jaero_rate_profile_enable: null handle");
+    r->timer.on = on != 0;
+    return 0;
+}
+
+extern "C" int jaero_rate_profile_read(jaero_rate *r, int which, double *total_ms, int *launches, int reset)
+{
+    if (!r || which != 0) return fail(JAERO_EINVAL, "jaero_rate_profile_read: bad arguments");
+    return r->timer.read(r->device, which, total_ms, launches, reset);
+}

@@ -1,0 +1,129 @@
+"""Rate meter in front of the demodulator banks (jaero_rate_*, include/jaero_hip.h "rate lines").
+
+`RateMeter` keeps, on the GPU, the Hann-windowed power spectrum of the SQUARED int16 signal of every channel, summed over consecutive
+4096-sample segments: MSK (h = 0.5) and the reference's OQPSK both put two spectral lines fb apart there, at 2 f_audio +- fb / 2.
+`classify_rates` (host numpy, no hot path) reads a channel's bit rate and audio offset off those sums.  The chain it closes:
+capture -> `find_carriers` -> `suggest_gains` -> `duty_cycle` -> `classify_rates` -> the bank and `Channeliser(..., fs_out=...)` a
+carrier belongs to.  All device arithmetic happens in libjaero_hip.so; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence, Tuple
+
+import numpy as np
+
+from . import capi
+
+L = capi.RATE_L        # segment length, samples
+BINS = capi.RATE_BINS  # bins 0 .. L / 2 of a channel's row
+RATES = (600, 1200, 8400, 10500)
+
+
+class RateMeter:
+    """The rate lines of `nch` rows of int16 PCM (thin wrapper over jaero_rate).  fs: the rows' sample rate in Hz, a label kept
+    for `classify_rates` -- it enters no device arithmetic.  max_write_samples: most samples per row one write may bring."""
+
+    def __init__(self, nch: int, fs: float, device: int = 0, max_write_samples: int = 4 * L):
+        self.lib = capi.lib()
+        h = C.c_void_p()
+        capi.check(self.lib.jaero_rate_create(device, int(nch), int(max_write_samples), C.byref(h)))
+        self.h = h
+        self.nch, self.fs, self.device, self.max_write_samples = int(nch), float(fs), device, int(max_write_samples)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.jaero_rate_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def write(self, pcm: np.ndarray, stream: int = 0) -> int:
+        """Consumes a host int16 array [nch, n]; returns the segments this write completed."""
+        a = np.ascontiguousarray(pcm, dtype=np.int16)
+        if a.ndim != 2 or a.shape[0] != self.nch:
+            raise ValueError(f"write takes [{self.nch}, n] int16, not {a.shape}")
+        return self._write(a.ctypes.data, a.shape[1], 0, stream)
+
+    def write_device(self, ptr: int, n: int, stream: int = 0) -> int:
+        """The same for int16 [nch][n] in device memory at `ptr` (it must stay valid until the stream has passed the write)."""
+        return self._write(ptr, n, 1, stream)
+
+    def write_from(self, chan, stream: int = None) -> int:
+        """Writes a channeliser's last output (`chan.pcm_view()`) with no host copy, on the stream the channeliser's last write used
+        (stream None) -- behind that write, and in front of the channeliser's next one on that stream, which overwrites the output."""
+        if chan.nch != self.nch:
+            raise ValueError(f"the channeliser has {chan.nch} channels, the rate meter {self.nch}")
+        ptr, n = chan.pcm_view()
+        return self._write(ptr, n, 1, chan.last_stream if stream is None else stream) if n > 0 else 0
+
+    def _write(self, ptr, n, dev, stream):
+        done = C.c_int(0)
+        capi.check(self.lib.jaero_rate_write(self.h, ptr, int(n), dev, C.c_void_p(stream), C.byref(done)))
+        return done.value
+
+    def read(self) -> Tuple[np.ndarray, int]:
+        """(R [nch, 2049], nseg): the sums and the number of segments in them (synchronises)."""
+        R = np.empty((self.nch, BINS), dtype=np.float64)
+        n = C.c_longlong(0)
+        capi.check(self.lib.jaero_rate_read(self.h, R.ctypes.data, C.byref(n)))
+        return R, n.value
+
+    def reset(self):
+        """Clears the sums and the count (synchronises); the pending partial segment stays, so the segment grid stays absolute."""
+        capi.check(self.lib.jaero_rate_reset(self.h))
+
+    def profile_enable(self, on: bool = True):
+        capi.check(self.lib.jaero_rate_profile_enable(self.h, int(on)))
+
+    def profile_read(self, reset: bool = False) -> Tuple[float, int]:
+        """(total ms, launches) of the line kernel since the last reset."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.lib.jaero_rate_profile_read(self.h, 0, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
+
+
+def classify_rates(R: np.ndarray, fs: float, rates: Sequence[float] = RATES, threshold_db: float = 10.0, kmin: int = 8):
+    """(rate [nch], audio_hz [nch], score_db [nch, len(rates)]) from the rate lines R [nch, 2049] (or one row) of rows sampled at `fs`.
+
+    Per row: bw = fs / L is a bin; floor = median(R[kmin:]); P[k] = max(R[k - 1], R[k], R[k + 1]) (clipped at the ends) lets a line sit
+    between two bins.  For each rate fb, d = round(fb / bw) is the distance of its two lines; the rate is skipped (score_db = -inf) when
+    kmin + d >= 2049.  score = max over kmin <= a < 2049 - d of min(P[a], P[a + d]), the first maximum; score_db = 10 log10(score /
+    floor).  The row's rate is the one with the largest score if that reaches `threshold_db`, else 0; its audio offset is the lines'
+    midpoint halved, (2 a + d) bw / 4, nan when the rate is 0.
+
+    What the min of the two lines buys: one CW carrier (one line in the squared signal) does not read as a rate, however strong.  What
+    it cannot tell: two CW carriers exactly fb apart read as that rate.  The lines must lie inside the measured band: 2 f_audio + fb / 2
+    below fs / 2 and 2 f_audio - fb / 2 above kmin bw.  A burst channel's lines are diluted by its duty cycle, because the sums are
+    means over every segment: its rate must be taken while it is on.  Gating by activity is deliberately not built here."""
+    R2 = np.atleast_2d(np.asarray(R, dtype=np.float64))
+    nch, nb = R2.shape
+    bw = float(fs) / L
+    P = np.maximum(R2, np.maximum(np.concatenate([R2[:, :1], R2[:, :-1]], axis=1), np.concatenate([R2[:, 1:], R2[:, -1:]], axis=1)))
+    floor = np.median(R2[:, kmin:], axis=1)
+    score_db = np.full((nch, len(rates)), -np.inf)
+    where = np.zeros((nch, len(rates)), dtype=np.int64)
+    ds = []
+    for i, fb in enumerate(rates):
+        d = int(round(fb / bw))
+        ds.append(d)
+        if kmin + d >= nb:
+            continue
+        m = np.minimum(P[:, kmin:nb - d], P[:, kmin + d:nb])
+        a = np.argmax(m, axis=1)  # the first of equal maxima
+        where[:, i] = a + kmin
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = 10.0 * np.log10(m[np.arange(nch), a] / floor)
+        score_db[:, i] = np.where(np.isnan(s), -np.inf, s)  # an all-zero row scores nothing
+    best = np.argmax(score_db, axis=1)
+    top = score_db[np.arange(nch), best]
+    hit = top >= threshold_db
+    rate = np.where(hit, np.asarray(rates)[best], 0)
+    audio = np.where(hit, (2 * where[np.arange(nch), best] + np.asarray(ds)[best]) * bw / 4.0, np.nan)
+    if np.ndim(R) == 1:
+        return rate[0], audio[0], score_db[0]
+    return rate, audio, score_db
