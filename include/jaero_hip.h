@@ -572,9 +572,10 @@ int jaero_activity_profile_read(jaero_chan *c, int which, double *total_ms, int 
  *   jaero_rate_reset     synchronises on the handle's last stream, clears R and nseg.  The pending partial segment is kept: the segment
  *                        grid stays absolute.
  *   jaero_rate_read      synchronises on the handle's last stream; sums[nchannels][2049] = R, *nseg.
- *   jaero_rate_profile_* HIP-event time since the last reset: which 0 = the line kernel (k_rate_lines).
- * Deliberately not here: the decision (classify_rates is host numpy over 16 KB per channel), gating by activity (a burst channel's lines
- * are diluted by its duty cycle; its rate must be taken while it is on), modulation recognition beyond what the rate implies, other L. */
+ *   jaero_rate_profile_* HIP-event time since the last reset: which 0 = the line kernel (k_rate_lines; k_rate_lines_gated on a gated handle).
+ * Deliberately not here: the decision (classify_rates is host numpy over 16 KB per channel), modulation recognition beyond what the rate
+ * implies, other L.  A burst channel's lines are diluted by its duty cycle, R being a sum over every segment: the gated rate lines below
+ * take its rate while it is on. */
 typedef struct jaero_rate jaero_rate;
 #define JAERO_RATE_L 4096
 #define JAERO_RATE_BINS 2049
@@ -585,6 +586,39 @@ int jaero_rate_reset(jaero_rate *r);
 int jaero_rate_read(jaero_rate *r, double *sums /* [nchannels][2049] */, long long *nseg);
 int jaero_rate_profile_enable(jaero_rate *r, int on);
 int jaero_rate_profile_read(jaero_rate *r, int which /* 0 = the line kernel */, double *total_ms, int *launches, int reset);
+
+/* ---- gated rate lines: the rate lines of a channel summed over the segments in which it is on.  R above is a sum over every segment; a
+ * segment in which a burst channel is off adds noise floor and no line, so a burst channel's score falls for as long as it stays off.
+ * The measurement that decides is one the line kernel makes anyway: the exact integer sum of y^2 over the segment.  A jaero_rate handle
+ * switched over by jaero_gate_enable compares it with a gate per channel and adds a segment to a channel's R only where it reaches the
+ * gate.  This text is the definition; tests/rate_gate_oracle.py implements it literally on tests/rate_oracle.py's segment_terms.
+ *   E_j(c) = sum_i y[i]^2 over segment j of channel c (L = 4096 and the segment grid of the rate lines): an unsigned 64-bit integer below 2^43.
+ *   g(c)   the channel's gate, an unsigned 64-bit integer, 0 at create.  Any value is allowed.
+ *   Segment j JOINS channel c iff E_j(c) >= g(c), with the gate in force when the write that completes the segment is made.
+ *   R_c[k] = sum of |H_j[k]|^2 over the joined segments only, in ascending j; the arithmetic of a term is exactly that of the rate lines.
+ *   Per channel, over the segments completed since the last reset, four unsigned 64-bit numbers: emax = max E_j, emin = min E_j (over every
+ *            segment, joined or not), njoin = the segments joined, ejoin = sum of E_j over the joined.  With no segment yet: 0, 2^64 - 1, 0, 0.
+ *            nseg counts every completed segment, joined or not, and is the same for every channel.
+ * What follows: with every gate 0, R is bit-identical to the ungated handle's; a channel's R is bit-identical to the R of an ungated handle
+ * that was fed only that channel's joined segments, in order; R and the four numbers are bit-identical for every cutting of the writes and
+ * for host and device input; a row of zeros joins under gate 0 with R == 0 exactly and never joins under a gate > 0; whether a neighbour
+ * joins changes no bit of a channel's R (a channel that does not join does not touch its row).
+ *   jaero_gate_enable  on != 0: the gated state; on == 0: the state at create, in which the handle behaves as it did before these calls
+ *                      existed (k_rate_lines alone is launched, no gate is looked at, no number kept).  Every call synchronises on the
+ *                      handle's last stream and clears R, nseg and the four numbers, as a reset does; the pending partial segment and the
+ *                      gates stay.
+ *   jaero_gate_set     gate[nchannels].  Synchronises on the handle's last stream; holds for the segments completed by later writes; clears
+ *                      nothing.  JAERO_EINVAL while off.
+ *   jaero_gate_read    synchronises; stats[nchannels][4] = emax, emin, njoin, ejoin; gate[nchannels] (may be NULL) = the gates; *nseg.
+ *                      JAERO_EINVAL while off.
+ * jaero_rate_reset additionally clears the four numbers and keeps the gates; jaero_rate_read, _write and _profile_* keep their meaning, and
+ * timer slot 0 counts whichever line kernel ran (k_rate_lines or k_rate_lines_gated).  A null handle or argument is JAERO_EINVAL with the
+ * function's name in jaero_last_error(), before any device is touched; a poisoned handle answers JAERO_EHIP here as everywhere.
+ * Deliberately not here: choosing the gates on the device (jaero_amd.ratemeter.suggest_gate is host arithmetic over the four numbers), a
+ * histogram of segment energies, gating by the channeliser's activity blocks (another grid). */
+int jaero_gate_enable(jaero_rate *r, int on);
+int jaero_gate_set(jaero_rate *r, const unsigned long long *gate /* [nchannels] */);
+int jaero_gate_read(jaero_rate *r, unsigned long long *stats /* [nchannels][4]: emax, emin, njoin, ejoin */, unsigned long long *gate /* [nchannels], may be null */, long long *nseg);
 
 /* Host-only debugging aid (no device needed): the sample indices at which jaero_write would run the coarse-frequency
  * estimate for a fresh channel fed `nwrites` writes of write_sizes[i] samples.  Returns the number of triggers

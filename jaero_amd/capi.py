@@ -51,6 +51,7 @@ EXPORTS = [
     "jaero_chan3_create", "jaero_chan3_write", "jaero_chan3_feed", "jaero_chan3_read_staged", "jaero_chan3_profile_read",
     "jaero_rate_create", "jaero_rate_destroy", "jaero_rate_write", "jaero_rate_reset", "jaero_rate_read", "jaero_rate_profile_enable",
     "jaero_rate_profile_read",
+    "jaero_gate_enable", "jaero_gate_set", "jaero_gate_read",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -284,6 +285,9 @@ def lib():
     L.jaero_rate_read.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
     L.jaero_rate_profile_enable.argtypes = [vp, ip]
     L.jaero_rate_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
+    L.jaero_gate_enable.argtypes = [vp, ip]
+    L.jaero_gate_set.argtypes = [vp, vp]
+    L.jaero_gate_read.argtypes = [vp, vp, vp, C.POINTER(C.c_longlong)]
     L.jaero_shard_range.argtypes =[ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.jaero_comm_get_unique_id.argtypes = [vp]
     L.jaero_comm_create.argtypes = [ip, ip, ip, vp, C.POINTER(vp)]

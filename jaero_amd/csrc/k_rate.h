@@ -1,5 +1,6 @@
-// k_rate.h -- the rate meter's line kernel (include/jaero_hip.h, "rate lines"; DESIGN 18, "Rate lines"): the Hann-windowed power spectrum
-// of the SQUARED int16 signal of every channel, one 4096-point fp64 transform per channel and segment, summed over segments.
+// k_rate.h -- the rate meter's line kernels (include/jaero_hip.h, "rate lines" and "gated rate lines"; DESIGN 18, "Rate lines"): the
+// Hann-windowed power spectrum of the SQUARED int16 signal of every channel, one 4096-point fp64 transform per channel and segment, summed
+// over segments.  The body of both kernels is k_rate_body.h.
 //
 //   grid ceil(nch / 2), 512 threads = 2 channels x 256 threads, 64 KiB LDS.  The transform is k_pre8400_fft's (pf_fft4096<NC>: thread
 //   (c = tid % NC, T = tid / NC) holds index T + 256 s of channel NC blockIdx.x + c in slot s on entry and on exit) with NC = 2 channels
@@ -21,6 +22,17 @@
 //             indices mod 4096.
 //     R[k]   += |H[k]|^2 for k <= 2048: slots 0 .. 7 of every thread, slot 8 of T = 0.
 //   A channel past nch (the last workgroup's) is staged as zeros and stores nothing.
+//
+//   k_rate_lines_gated (a handle switched over by jaero_gate_enable launches it in place of k_rate_lines) differs in four places:
+//     decision    where the partial sums meet in LDS every thread adds up the sum E of EVERY channel of the workgroup, not only its own, and
+//                 compares each with the channel's gate: channel cc joins iff it lies below nch and E >= gate.  The result is a bit mask in
+//                 one scalar register, the same in every thread.
+//     statistics  thread cc < NC keeps emax, emin, njoin, ejoin of channel cc in registers over the launch's segments: plain 64-bit loads
+//                 in front of the first segment, plain stores behind the last, no atomics (a workgroup owns its channels).
+//     skip        nobody joins: the workgroup goes on to the next segment behind the barrier that ends the reading of the partial sums
+//                 -- no transform, no Hann step, no access to R.
+//     R           somebody joins: transform and Hann step run for the whole workgroup (the exchanges are shared), and only a joining
+//                 channel's threads do the read-modify-write.  The others do not touch their rows; they do not add zero.
 #pragma once
 #include "k_pre8400.h" // pf_fft4096
 
@@ -56,91 +68,17 @@ __device__ __forceinline__ void rate_stage_run(const int16_t *__restrict__ src, 
 __global__ __launch_bounds__(RATE_THREADS) void k_rate_lines(const int16_t *__restrict__ pend, int fill, const int16_t *__restrict__ pcm, int n,
                                                              int nch, int nseg, const double2 *__restrict__ tw, double *__restrict__ R)
 {
-    constexpr int NC = RATE_NC;
-    extern __shared__ double rt_xch[]; // NC channels x 4096 doubles; the staging area and the partial sums lie in it before the transform
-    int16_t *stg = (int16_t *)rt_xch;
-    unsigned long long *part = (unsigned long long *)(rt_xch + NC * RATE_STG / 4); // behind the staging area: [4 NC wavefronts][NC channels]
-    for (int j = 0; j < nseg; j++)
-    {
-        // what a thread derives from its index is formed anew in every segment, and once more behind the transform: held across the
-        // transform instead, those registers are the ones it lacks
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const int c = tid % NC, T = tid / NC;
-        // ---- stage
-        {
-            const int lc = tid >> 8, lt = tid & 255, lch = blockIdx.x * NC + lc; // the staging's channel and thread
-            int16_t *dst = stg + lc * RATE_STG;
-            if (lch < nch)
-            {
-                const int p0 = j * RATE_L;                       // first sample of the segment in (pending, write)
-                const int npend = fill > p0 ? fill - p0 : 0;     // of it, from the pending buffer (only in segment 0)
-                rate_stage_run(pend + (size_t)lch * RATE_L + p0, npend, dst, lt);
-                rate_stage_run(pcm + (size_t)lch * n + (p0 + npend - fill), RATE_L - npend, dst + npend, lt);
-            }
-            else
-                for (int i = lt; i < RATE_L; i += 256) dst[i] = 0;
-        }
-        jd_lds_barrier();
-        // ---- square, sum, subtract the mean
-        int sq[16];
-        unsigned long long sum = 0;
-#pragma unroll
-        for (int s = 0; s < 16; s++)
-        {
-            const int y = stg[c * RATE_STG + T + 256 * s];
-            sq[s] = y * y;
-            sum += (unsigned long long)sq[s];
-        }
-#pragma unroll
-        for (int m = NC; m < 64; m <<= 1) sum += __shfl_xor(sum, m); // the 64 / NC T of this wavefront: lanes NC (T mod (64 / NC)) + c
-        if ((tid & 63) < NC) part[(tid >> 6) * NC + c] = sum;
-        jd_lds_barrier();
-        sum = 0;
-#pragma unroll
-        for (int w = 0; w < 4 * NC; w++) sum += part[w * NC + c];
-        jd_lds_barrier(); // the transform's exchanges overwrite the staging area and the partial sums
-        const double mean = (double)(long long)sum * (1.0 / RATE_L);
-        CV<16> d;
-#pragma unroll
-        for (int s = 0; s < 16; s++) { d.r[s] = (double)sq[s] - mean; d.i[s] = 0.0; }
-        // ---- Z
-        pf_fft4096<NC>(d, rt_xch, tw, T, c);
-        // ---- Hann, plane by plane: Z[k] of channel c at rt_xch[NC k + c].  k - 1 and k + 1 stay inside 0 .. 4095 but for k = 0 (slot 0 of T = 0)
-        int tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));
-        const int c2 = tid2 % NC, T2 = tid2 / NC, ch = blockIdx.x * NC + c2;
-        const int ns = T2 == 0 ? 9 : 8;
-        double *zc = rt_xch + T2 * NC + c2;
-        const double *zm = rt_xch + ((T2 - 1) & (RATE_L - 1)) * NC + c2;
-        double hr[9], hi[9];
-#pragma unroll
-        for (int s = 0; s < 16; s++) zc[256 * NC * s] = d.r[s];
-        jd_lds_barrier();
-        hr[0] = 0.5 * d.r[0] - 0.25 * (zm[0] + zc[NC]);
-#pragma unroll
-        for (int s = 1; s < 9; s++)
-            if (s < ns) hr[s] = 0.5 * d.r[s] - 0.25 * (zc[256 * NC * s - NC] + zc[256 * NC * s + NC]);
-        jd_lds_barrier();
-#pragma unroll
-        for (int s = 0; s < 16; s++) zc[256 * NC * s] = d.i[s];
-        jd_lds_barrier();
-        hi[0] = 0.5 * d.i[0] - 0.25 * (zm[0] + zc[NC]);
-#pragma unroll
-        for (int s = 1; s < 9; s++)
-            if (s < ns) hi[s] = 0.5 * d.i[s] - 0.25 * (zc[256 * NC * s - NC] + zc[256 * NC * s + NC]);
-        jd_lds_barrier(); // the next segment's staging overwrites the plane
-        // ---- R += |H|^2
-        if (ch < nch)
-        {
-            double *__restrict__ Rk = R + (size_t)ch * RATE_BINS + T2;
-#pragma unroll
-            for (int s = 0; s < 9; s++)
-                if (s < ns)
-                {
-                    const double t = hr[s] * hr[s] + hi[s] * hi[s];
-                    Rk[256 * s] = Rk[256 * s] + t;
-                }
-        }
-    }
+#define RATE_GATED 0
+#include "k_rate_body.h"
+#undef RATE_GATED
+}
+
+// the same, gated: gate [nch]; stats [nch][4] = emax, emin, njoin, ejoin
+__global__ __launch_bounds__(RATE_THREADS) void k_rate_lines_gated(const int16_t *__restrict__ pend, int fill, const int16_t *__restrict__ pcm, int n,
+                                                                   int nch, int nseg, const double2 *__restrict__ tw, double *__restrict__ R,
+                                                                   const unsigned long long *__restrict__ gate, unsigned long long *__restrict__ stats)
+{
+#define RATE_GATED 1
+#include "k_rate_body.h"
+#undef RATE_GATED
 }

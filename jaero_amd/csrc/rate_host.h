@@ -5,6 +5,10 @@
 // the segment count.  A write that completes a segment launches k_rate_lines over (pending, write) and then stores the write's tail as the
 // new pending segment; one that completes none appends to it.  Two pending buffers take turns, as the channeliser's history does: the
 // tail is stored into the one the launch did not read.
+//
+// Gated rate lines (jaero_gate_*): the handle also keeps a gate per channel and four numbers per channel, and, once jaero_gate_enable has
+// switched it over, a write launches k_rate_lines_gated in place of k_rate_lines.  Nothing else in a write differs; a handle that never
+// enables the gate launches k_rate_lines alone, as before.
 #pragma once
 #include "k_rate.h"
 
@@ -20,7 +24,10 @@ struct jaero_rate
     double2 *d_tw = nullptr;                 // [4096]: exp(-2 pi i k / 4096)
     double *d_R = nullptr;                   // [nch][2049]
     long long nseg = 0;
-    KernelTimer timer{1};                    // 0 k_rate_lines
+    bool gated = false;                      // jaero_gate_enable: a write launches k_rate_lines_gated
+    unsigned long long *d_gate = nullptr;    // [nch]: the gates, 0 at create; every reset and switch keeps them
+    unsigned long long *d_stats = nullptr;   // [nch][4]: emax, emin, njoin, ejoin over the segments since the last reset (gated only)
+    KernelTimer timer{1};                    // 0 k_rate_lines or k_rate_lines_gated, whichever ran
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
     bool poisoned = false;
@@ -35,6 +42,15 @@ extern "C" void jaero_rate_destroy(jaero_rate *r)
     (void)hipStreamSynchronize(r->last_stream);
     if (r->order_ev) (void)hipEventDestroy(r->order_ev);
     delete r;
+}
+
+// the four numbers with no segment yet: 0, 2^64 - 1, 0, 0
+static int rate_clear_stats(jaero_rate *r)
+{
+    std::vector<unsigned long long> st((size_t)r->nch * 4, 0ull);
+    for (int c = 0; c < r->nch; c++) st[(size_t)c * 4 + 1] = ~0ull;
+    HIPCHK(hipMemcpy(r->d_stats, st.data(), sizeof(unsigned long long) * st.size(), hipMemcpyHostToDevice));
+    return 0;
 }
 
 static int rate_build(std::unique_ptr<jaero_rate> &r, int device, int nchannels, int max_write_samples)
@@ -53,7 +69,10 @@ static int rate_build(std::unique_ptr<jaero_rate> &r, int device, int nchannels,
     }
     HIPCHK(hipMemcpy(r->d_tw, tw.data(), sizeof(double2) * RATE_L, hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute((const void *)k_rate_lines, hipFuncAttributeMaxDynamicSharedMemorySize, RATE_NC * RATE_L * (int)sizeof(double)));
-    return 0;
+    HIPCHK(hipFuncSetAttribute((const void *)k_rate_lines_gated, hipFuncAttributeMaxDynamicSharedMemorySize, RATE_NC * RATE_L * (int)sizeof(double)));
+    DA(r->mem, r->d_gate, nchannels);
+    DA(r->mem, r->d_stats, (size_t)nchannels * 4);
+    return rate_clear_stats(r.get());
 }
 
 extern "C" int jaero_rate_create(int device, int nchannels, int max_write_samples, jaero_rate **out)
@@ -109,9 +128,19 @@ extern "C" int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples,
     }
     r->poisoned = true; // from here on the sums, the count and the pending segment advance together or not at all
     const int pi = r->timer.begin(0, st);
-    hipLaunchKernelGGL(k_rate_lines, dim3((unsigned)((r->nch + RATE_NC - 1) / RATE_NC)), dim3(RATE_THREADS), RATE_NC * RATE_L * sizeof(double), st,
-                       (const int16_t *)r->d_pend[r->cur], fill, src, n, r->nch, nseg, (const double2 *)r->d_tw, r->d_R);
-    LAUNCHCHK("k_rate_lines");
+    if (r->gated)
+    {
+        hipLaunchKernelGGL(k_rate_lines_gated, dim3((unsigned)((r->nch + RATE_NC - 1) / RATE_NC)), dim3(RATE_THREADS), RATE_NC * RATE_L * sizeof(double), st,
+                           (const int16_t *)r->d_pend[r->cur], fill, src, n, r->nch, nseg, (const double2 *)r->d_tw, r->d_R,
+                           (const unsigned long long *)r->d_gate, r->d_stats);
+        LAUNCHCHK("k_rate_lines_gated");
+    }
+    else
+    {
+        hipLaunchKernelGGL(k_rate_lines, dim3((unsigned)((r->nch + RATE_NC - 1) / RATE_NC)), dim3(RATE_THREADS), RATE_NC * RATE_L * sizeof(double), st,
+                           (const int16_t *)r->d_pend[r->cur], fill, src, n, r->nch, nseg, (const double2 *)r->d_tw, r->d_R);
+        LAUNCHCHK("k_rate_lines");
+    }
     r->timer.end(pi, st);
     // the tail behind the last completed segment lies wholly in this write (fill < 4096 <= 4096 nseg)
     if (rest > 0)
@@ -134,6 +163,43 @@ extern "C" int jaero_rate_reset(jaero_rate *r)
     HIPCHK(hipStreamSynchronize(r->last_stream));
     HIPCHK(hipMemset(r->d_R, 0, sizeof(double) * (size_t)r->nch * RATE_BINS));
     r->nseg = 0; // the pending segment stays: the segment grid is absolute
+    return r->gated ? rate_clear_stats(r) : 0; // off, the four numbers are the empty ones already; the gates stay either way
+}
+
+// ---- gated rate lines (include/jaero_hip.h, "gated rate lines")
+extern "C" int jaero_gate_enable(jaero_rate *r, int on)
+{
+    if (!r) return fail(JAERO_EINVAL, "jaero_gate_enable: null handle");
+    RATEPOISONCHK(r, "jaero_gate_enable");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    HIPCHK(hipMemset(r->d_R, 0, sizeof(double) * (size_t)r->nch * RATE_BINS));
+    r->nseg = 0; // as a reset: the pending segment stays, and so do the gates
+    r->gated = on != 0;
+    return rate_clear_stats(r);
+}
+
+extern "C" int jaero_gate_set(jaero_rate *r, const unsigned long long *gate)
+{
+    if (!r || !gate) return fail(JAERO_EINVAL, "jaero_gate_set: null argument");
+    RATEPOISONCHK(r, "jaero_gate_set");
+    if (!r->gated) return fail(JAERO_EINVAL, "jaero_gate_set: the gate is off (jaero_gate_enable)");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream)); // the launches enqueued so far read the old gates
+    HIPCHK(hipMemcpy(r->d_gate, gate, sizeof(unsigned long long) * (size_t)r->nch, hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int jaero_gate_read(jaero_rate *r, unsigned long long *stats, unsigned long long *gate, long long *nseg)
+{
+    if (!r || !stats || !nseg) return fail(JAERO_EINVAL, "jaero_gate_read: null argument");
+    RATEPOISONCHK(r, "jaero_gate_read");
+    if (!r->gated) return fail(JAERO_EINVAL, "jaero_gate_read: the gate is off (jaero_gate_enable)");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    HIPCHK(hipMemcpy(stats, r->d_stats, sizeof(unsigned long long) * (size_t)r->nch * 4, hipMemcpyDeviceToHost));
+    if (gate) HIPCHK(hipMemcpy(gate, r->d_gate, sizeof(unsigned long long) * (size_t)r->nch, hipMemcpyDeviceToHost));
+    *nseg = r->nseg;
     return 0;
 }
 

@@ -5,6 +5,24 @@
 `classify_rates` (host numpy, no hot path) reads a channel's bit rate and audio offset off those sums.  The chain it closes:
 capture -> `find_carriers` -> `suggest_gains` -> `duty_cycle` -> `classify_rates` -> the bank and `Channeliser(..., fs_out=...)` a
 carrier belongs to.  All device arithmetic happens in libjaero_hip.so; there is no CPU fallback.
+
+Burst channels (jaero_gate_*, include/jaero_hip.h "gated rate lines").  R is a sum over every segment, so the lines of a channel that
+is mostly off drown in the segments in which it is off.  A gated meter adds a segment to a channel's R only where the segment's energy
+E = sum y^2 reaches the channel's gate, and keeps emax, emin, njoin and ejoin per channel.  The flow:
+
+    m.gate_enable()                            # every gate is 0 at create: everything joins
+    ... m.write(...) ...                       # measure the energies
+    emax, emin, njoin, ejoin, gate, nseg = m.read_gate()
+    m.set_gate(suggest_gate(emax, emin))       # the midpoint for a channel whose segments differ, 0 for one that is continuous
+    m.reset()                                  # keeps the gates and the segment grid
+    ... m.write(...) ...                       # measure again
+    R, nseg = m.read()
+    rate, audio, score = classify_rates(R, m.fs)
+    duty = m.read_gate()[2] / nseg             # njoin / nseg: how often a channel was on
+
+Limits.  A single click sets emax, and with it the midpoint.  A burst's preamble (a carrier plus lines fb / 2 off it) puts lines fb / 2
+apart into the squared signal, so a short 1200 bps burst can read 600: on the CPU oracle a 500-bit burst did exactly that, which is
+why the bursts of the tests are long.
 """
 from __future__ import annotations
 
@@ -74,8 +92,32 @@ class RateMeter:
         return R, n.value
 
     def reset(self):
-        """Clears the sums and the count (synchronises); the pending partial segment stays, so the segment grid stays absolute."""
+        """Clears the sums, the count and (gated) the four numbers (synchronises); the pending partial segment stays, so the segment grid
+        stays absolute, and so do the gates."""
         capi.check(self.lib.jaero_rate_reset(self.h))
+
+    def gate_enable(self, on: bool = True):
+        """Switches between the gated meter and the ungated one it is at create (synchronises).  Either way the sums, the count and the
+        four numbers are cleared as by reset(); the pending partial segment and the gates stay."""
+        capi.check(self.lib.jaero_gate_enable(self.h, int(on)))
+
+    def set_gate(self, g):
+        """g: `nch` non-negative integers below 2^64, one gate per channel; they hold for the segments that later writes complete
+        (synchronises, clears nothing).  A segment joins its channel's R iff its energy sum y^2 reaches the gate."""
+        if np.ndim(g) != 1 or len(g) != self.nch or any(int(v) < 0 or int(v) >= 1 << 64 for v in g):
+            raise ValueError(f"set_gate takes {self.nch} integers in [0, 2^64)")
+        a = np.array([int(v) for v in g], dtype=np.uint64)
+        capi.check(self.lib.jaero_gate_set(self.h, a.ctypes.data))
+
+    def read_gate(self):
+        """(emax, emin, njoin, ejoin, gate, nseg): per channel, as uint64 arrays, the largest and the smallest segment energy, the number
+        of segments that joined and the sum of their energies since the last reset, and the gates; nseg counts every completed segment
+        (synchronises).  With no segment yet: 0, 2^64 - 1, 0, 0."""
+        st = np.empty((self.nch, 4), dtype=np.uint64)
+        gate = np.empty(self.nch, dtype=np.uint64)
+        n = C.c_longlong(0)
+        capi.check(self.lib.jaero_gate_read(self.h, st.ctypes.data, gate.ctypes.data, C.byref(n)))
+        return st[:, 0].copy(), st[:, 1].copy(), st[:, 2].copy(), st[:, 3].copy(), gate, n.value
 
     def profile_enable(self, on: bool = True):
         capi.check(self.lib.jaero_rate_profile_enable(self.h, int(on)))
@@ -85,6 +127,21 @@ class RateMeter:
         ms, n = C.c_double(0), C.c_int(0)
         capi.check(self.lib.jaero_rate_profile_read(self.h, 0, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
+
+
+def suggest_gate(emax, emin, min_ratio: float = 1.5):
+    """Gates from `read_gate`'s emax and emin, in exact integer arithmetic (a list of Python ints, as `set_gate` takes them): the midpoint
+    (emax + emin) // 2 where emax > 0 and emax >= min_ratio emin, else 0.  min_ratio is taken as the exact fraction it is written as
+    (1.5 = 3 / 2: 2 emax >= 3 emin).  A channel whose strongest and weakest segment differ by less than 1.8 dB counts as continuous and
+    joins everything: 256 segments of white noise or of continuous MSK differ by 1.15.  A single click sets emax."""
+    from fractions import Fraction
+
+    r = Fraction(str(min_ratio))
+    out = []
+    for hi, lo in zip(emax, emin):
+        hi, lo = int(hi), int(lo)
+        out.append((hi + lo) // 2 if hi > 0 and hi * r.denominator >= lo * r.numerator else 0)
+    return out
 
 
 def classify_rates(R: np.ndarray, fs: float, rates: Sequence[float] = RATES, threshold_db: float = 10.0, kmin: int = 8):
@@ -99,7 +156,8 @@ def classify_rates(R: np.ndarray, fs: float, rates: Sequence[float] = RATES, thr
     What the min of the two lines buys: one CW carrier (one line in the squared signal) does not read as a rate, however strong.  What
     it cannot tell: two CW carriers exactly fb apart read as that rate.  The lines must lie inside the measured band: 2 f_audio + fb / 2
     below fs / 2 and 2 f_audio - fb / 2 above kmin bw.  A burst channel's lines are diluted by its duty cycle, because the sums are
-    means over every segment: its rate must be taken while it is on.  Gating by activity is deliberately not built here."""
+    means over every segment: its rate must be taken while it is on.  `RateMeter.gate_enable` / `set_gate` / `suggest_gate` do that
+    (the module docstring has the flow); R of a gated meter is classified here like any other."""
     R2 = np.atleast_2d(np.asarray(R, dtype=np.float64))
     nch, nb = R2.shape
     bw = float(fs) / L
