@@ -614,11 +614,57 @@ int jaero_rate_profile_read(jaero_rate *r, int which /* 0 = the line kernel */, 
  * jaero_rate_reset additionally clears the four numbers and keeps the gates; jaero_rate_read, _write and _profile_* keep their meaning, and
  * timer slot 0 counts whichever line kernel ran (k_rate_lines or k_rate_lines_gated).  A null handle or argument is JAERO_EINVAL with the
  * function's name in jaero_last_error(), before any device is touched; a poisoned handle answers JAERO_EHIP here as everywhere.
- * Deliberately not here: choosing the gates on the device (jaero_amd.ratemeter.suggest_gate is host arithmetic over the four numbers), a
- * histogram of segment energies, gating by the channeliser's activity blocks (another grid). */
+ * Deliberately not here: gating by the channeliser's activity blocks (another grid).  Gates chosen on the device and a histogram of segment
+ * energies are the one-pass gates below. */
 int jaero_gate_enable(jaero_rate *r, int on);
 int jaero_gate_set(jaero_rate *r, const unsigned long long *gate /* [nchannels] */);
 int jaero_gate_read(jaero_rate *r, unsigned long long *stats /* [nchannels][4]: emax, emin, njoin, ejoin */, unsigned long long *gate /* [nchannels], may be null */, long long *nseg);
+
+/* ---- one-pass gates: the flow above needs the signal twice (measure under gate 0, set the gates, measure again), and one click sets emax
+ * and with it the midpoint.  Here the device chooses every gate itself, segment by segment, from the SECOND largest energy, and can count
+ * every segment's energy in a histogram.  This text is the definition; tests/rate_auto_oracle.py implements it literally.  Everything is
+ * an unsigned 64-bit integer; there is no tolerance anywhere.
+ *   Per channel: the four numbers above; e2, the second largest segment energy, with multiplicity (two segments of the largest energy:
+ *   e2 == emax), 0 at reset; start, 2^64 - 1 at reset; the gate g, 0 at reset.
+ *   Segment number s (0-based since the last reset, every completed segment counted) with energy E, under JAERO_GATE_AUTO, in this order:
+ *     if E > emax: e2 = emax, emax = E; else if E > e2: e2 = E
+ *     emin = min(emin, E)
+ *     g' = (e2 + emin) / 2 (rounded down) if e2 > 0 and 2 e2 >= 3 emin, else 0
+ *     join = E >= g';  restart = g == 0 and g' > 0 and join
+ *     restart:   R_c = |H_s|^2 (assigned, not added), njoin = 1, ejoin = E, start = s
+ *     else join: R_c += |H_s|^2, njoin += 1, ejoin += E
+ *     g = g'
+ *   What follows: the result depends only on the sequence of E -- cuts and input memory change no bit of R and none of the numbers; a
+ *   channel's R is bit-identical to an ungated handle's that was fed only its joined segments from `start` on, in order; a channel whose
+ *   segments differ by less than 3 / 2 never leaves gate 0, is the ungated handle bit for bit, and keeps start == 2^64 - 1; a row of zeros
+ *   keeps gate 0, joins everything and has R == 0 exactly; a channel that starts inside a burst and then falls silent never restarts (the
+ *   quiet segment lowers emin, the gate rises, the quiet segment does not join); one that is quiet first restarts at its second loud
+ *   segment, and what it summed under gate 0 is thrown away; one click cannot move the gate, because it only ever becomes emax; a
+ *   neighbour in the same workgroup changes nothing.  njoin / (nseg - start) is the duty cycle since the restart.
+ *   Limits: two clicks set e2; a dropout (a segment of zeros) sets emin for good; the segments joined while the gate was still rising
+ *   stay in R.
+ *   The histogram (JAERO_GATE_HIST): every completed segment, joined or not, adds 1 to bin E for E < 8, else to bin
+ *   8 (e - 2) + ((E >> (e - 3)) & 7) with e = floor(log2 E): eight bins an octave, 0.28 to 0.51 dB wide.  The lower edge of bin b >= 8 is
+ *   (8 + b mod 8) << (b div 8 - 1).  E <= 4096 * 32768^2 = 2^42 lands in bin 320, the last.  Counts are 32-bit.
+ *   jaero_gate2_enable     mode 0, JAERO_GATE_MANUAL, JAERO_GATE_AUTO, or either of the two | JAERO_GATE_HIST; anything else is JAERO_EINVAL
+ *                          and leaves the handle as it was.  jaero_gate_enable(r, on) is jaero_gate2_enable(r, on ? 1 : 0).  Every call
+ *                          synchronises and clears R, nseg, the four numbers, e2, start and the histogram; the pending partial segment
+ *                          stays; the gates stay, except that a new mode with AUTO sets them all to 0 (going AUTO -> MANUAL therefore
+ *                          freezes the device's gates for a second pass).  Under MANUAL | HIST the decision is E >= g with the given gate.
+ *   jaero_gate2_read       stats[nchannels][6] = emax, emin, njoin, ejoin, e2, start; gate (may be NULL); *nseg.  JAERO_EINVAL unless AUTO.
+ *   jaero_gate2_read_hist  hist[nchannels][321], *nseg.  JAERO_EINVAL unless HIST.
+ * jaero_gate_read works in every mode but 0; jaero_gate_set is JAERO_EINVAL under AUTO and changes nothing; jaero_rate_reset under AUTO
+ * also zeroes the gates, e2 and start, and under HIST the histogram.  A handle that never uses these calls launches k_rate_lines and
+ * k_rate_lines_gated alone; a mode with AUTO or HIST launches k_rate_lines_auto, which timer slot 0 then counts.
+ * Deliberately not here: a gate taken from the histogram on the device (jaero_amd.ratemeter.hist_extremes and suggest_gate are host
+ * arithmetic), ratios other than 3 / 2. */
+#define JAERO_GATE_MANUAL 1   /* what jaero_gate_enable(r, 1) gives */
+#define JAERO_GATE_AUTO   2   /* the device chooses every gate, segment by segment */
+#define JAERO_GATE_HIST   4   /* also count every completed segment in a histogram of E; only together with MANUAL or AUTO */
+#define JAERO_GATE_HBINS  321
+int jaero_gate2_enable(jaero_rate *r, int mode);
+int jaero_gate2_read(jaero_rate *r, unsigned long long *stats /* [nchannels][6]: emax, emin, njoin, ejoin, e2, start */, unsigned long long *gate /* [nchannels], may be null */, long long *nseg);
+int jaero_gate2_read_hist(jaero_rate *r, unsigned *hist /* [nchannels][321] */, long long *nseg);
 
 /* Host-only debugging aid (no device needed): the sample indices at which jaero_write would run the coarse-frequency
  * estimate for a fresh channel fed `nwrites` writes of write_sizes[i] samples.  Returns the number of triggers

@@ -20,6 +20,7 @@ W_RATE = 1  # jaero_ingest_push: sample rate differs from the bank (warning, dat
 IQ_CS16, IQ_CU8, IQ_CS8, IQ_CF32 = 0, 1, 2, 3
 ACT_PEAK, ACT_BLOCKS, ACT_BINS = 1, 2, 64  # jaero_activity_enable: what; bins of a channel's histogram
 RATE_L, RATE_BINS = 4096, 2049  # jaero_rate: segment length, bins of a channel's row
+GATE_MANUAL, GATE_AUTO, GATE_HIST, GATE_HBINS = 1, 2, 4, 321  # jaero_gate2_enable: mode; bins of a channel's histogram of E
 AEROL_SUS, AEROL_PACKETS, AEROL_EVENTS, AEROL_VOICE = 0, 1, 2, 3  # jaero_aerol_read_all: what
 BANK_SOFTBITS, BANK_STATUS_LOG, BANK_EVENTS, BANK_SYMBOLS = 0, 1, 2, 3  # jaero_read_all: what
 E_OK, E_INVAL, E_NODEV, E_NOMEM, E_HIP, E_OVERFLOW, E_NOTSUP = 0, -1, -2, -3, -4, -5, -6
@@ -52,6 +53,7 @@ EXPORTS = [
     "jaero_rate_create", "jaero_rate_destroy", "jaero_rate_write", "jaero_rate_reset", "jaero_rate_read", "jaero_rate_profile_enable",
     "jaero_rate_profile_read",
     "jaero_gate_enable", "jaero_gate_set", "jaero_gate_read",
+    "jaero_gate2_enable", "jaero_gate2_read", "jaero_gate2_read_hist",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -288,6 +290,9 @@ def lib():
     L.jaero_gate_enable.argtypes = [vp, ip]
     L.jaero_gate_set.argtypes = [vp, vp]
     L.jaero_gate_read.argtypes = [vp, vp, vp, C.POINTER(C.c_longlong)]
+    L.jaero_gate2_enable.argtypes = [vp, ip]
+    L.jaero_gate2_read.argtypes = [vp, vp, vp, C.POINTER(C.c_longlong)]
+    L.jaero_gate2_read_hist.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
     L.jaero_shard_range.argtypes =[ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.jaero_comm_get_unique_id.argtypes = [vp]
     L.jaero_comm_create.argtypes = [ip, ip, ip, vp, C.POINTER(vp)]

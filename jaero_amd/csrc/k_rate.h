@@ -1,6 +1,6 @@
 // k_rate.h -- the rate meter's line kernels (include/jaero_hip.h, "rate lines" and "gated rate lines"; DESIGN 18, "Rate lines"): the
 // Hann-windowed power spectrum of the SQUARED int16 signal of every channel, one 4096-point fp64 transform per channel and segment, summed
-// over segments.  The body of both kernels is k_rate_body.h.
+// over segments.  The body of all three kernels is k_rate_body.h.
 //
 //   grid ceil(nch / 2), 512 threads = 2 channels x 256 threads, 64 KiB LDS.  The transform is k_pre8400_fft's (pf_fft4096<NC>: thread
 //   (c = tid % NC, T = tid / NC) holds index T + 256 s of channel NC blockIdx.x + c in slot s on entry and on exit) with NC = 2 channels
@@ -33,6 +33,17 @@
 //                 -- no transform, no Hann step, no access to R.
 //     R           somebody joins: transform and Hann step run for the whole workgroup (the exchanges are shared), and only a joining
 //                 channel's threads do the read-modify-write.  The others do not touch their rows; they do not add zero.
+//
+//   k_rate_lines_auto (launched in place of the other two while the handle's mode has JAERO_GATE_AUTO or JAERO_GATE_HIST; include/jaero_hip.h,
+//   "one-pass gates") follows k_rate_lines_gated in every respect but three:
+//     decision    under AUTO the rule of the one-pass gates: emax, e2, emin are brought up to date with E, the gate becomes (e2 + emin) / 2 or
+//                 0, and the segment joins iff E reaches the NEW gate; a channel whose gate rises from 0 on a segment that joins RESTARTS.
+//                 Under MANUAL | HIST the plain comparison with the given gate.  E goes through readfirstlane, so the state of both
+//                 channels (7 numbers each) is uniform and sits in scalar registers over the launch's segments: loaded in front of the
+//                 first, stored behind the last by thread cc < NC with vector stores -- the gate too, under AUTO.
+//     R           a restarting channel's threads store |H|^2 where a joining one's add it.
+//     histogram   thread cc < NC does the read-modify-write of the one counter of channel cc's row that E falls into, every segment, joined
+//                 or not (hist == nullptr: no histogram).  The workgroup owns its channels: no atomics.
 #pragma once
 #include "k_pre8400.h" // pf_fft4096
 
@@ -40,6 +51,7 @@
 #define RATE_BINS 2049
 #define RATE_NC 2                // channels per workgroup
 #define RATE_THREADS (256 * RATE_NC)
+#define RATE_HBINS 321           // bins of a channel's histogram of E (one-pass gates)
 #define RATE_STG (RATE_L + 32)   // int16 per channel of the staging area: the channels' reads of a wavefront's 32 T fall on different banks
 
 // the int16 src[0 .. count) to dst[0 .. count) in LDS, by the 256 threads t of one channel, in aligned 16-byte loads
@@ -64,6 +76,13 @@ __device__ __forceinline__ void rate_stage_run(const int16_t *__restrict__ src, 
     }
 }
 
+// x, the same in every lane, as a value the compiler knows to be uniform: it then lives in a pair of scalar registers
+__device__ __forceinline__ unsigned long long rate_uniform(unsigned long long x)
+{
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)x), hi = __builtin_amdgcn_readfirstlane((unsigned)(x >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 // pend [nch][4096]: the partial segment in front of this write (`fill` samples a row); pcm [nch][n]: the write; nseg = (fill + n) / 4096 > 0
 __global__ __launch_bounds__(RATE_THREADS) void k_rate_lines(const int16_t *__restrict__ pend, int fill, const int16_t *__restrict__ pcm, int n,
                                                              int nch, int nseg, const double2 *__restrict__ tw, double *__restrict__ R)
@@ -79,6 +98,19 @@ __global__ __launch_bounds__(RATE_THREADS) void k_rate_lines_gated(const int16_t
                                                                    const unsigned long long *__restrict__ gate, unsigned long long *__restrict__ stats)
 {
 #define RATE_GATED 1
+#include "k_rate_body.h"
+#undef RATE_GATED
+}
+
+// the one-pass gates: gate [nch] (written back under autom); stats [nch][4] as above; stats2 [nch][2] = e2, start; hist [nch][321] or null;
+// autom != 0: the device chooses the gates; seg0 = the segments completed since the last reset in front of this launch
+__global__ __launch_bounds__(RATE_THREADS) void k_rate_lines_auto(const int16_t *__restrict__ pend, int fill, const int16_t *__restrict__ pcm, int n,
+                                                                  int nch, int nseg, const double2 *__restrict__ tw, double *__restrict__ R,
+                                                                  unsigned long long *__restrict__ gate, unsigned long long *__restrict__ stats,
+                                                                  unsigned long long *__restrict__ stats2, unsigned *__restrict__ hist, int autom,
+                                                                  unsigned long long seg0)
+{
+#define RATE_GATED 2
 #include "k_rate_body.h"
 #undef RATE_GATED
 }

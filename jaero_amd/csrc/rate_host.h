@@ -9,6 +9,10 @@
 // Gated rate lines (jaero_gate_*): the handle also keeps a gate per channel and four numbers per channel, and, once jaero_gate_enable has
 // switched it over, a write launches k_rate_lines_gated in place of k_rate_lines.  Nothing else in a write differs; a handle that never
 // enables the gate launches k_rate_lines alone, as before.
+//
+// One-pass gates (jaero_gate2_*): `mode` is 0, JAERO_GATE_MANUAL or JAERO_GATE_AUTO, with or without JAERO_GATE_HIST.  Mode 0 launches
+// k_rate_lines and mode 1 k_rate_lines_gated, as before; every mode with AUTO or HIST launches k_rate_lines_auto, which also keeps e2 and
+// start per channel (d_stats2), writes the gates under AUTO and counts the histogram (d_hist, allocated by the first mode with HIST).
 #pragma once
 #include "k_rate.h"
 
@@ -24,10 +28,12 @@ struct jaero_rate
     double2 *d_tw = nullptr;                 // [4096]: exp(-2 pi i k / 4096)
     double *d_R = nullptr;                   // [nch][2049]
     long long nseg = 0;
-    bool gated = false;                      // jaero_gate_enable: a write launches k_rate_lines_gated
+    int mode = 0;                            // jaero_gate2_enable: 0 k_rate_lines, JAERO_GATE_MANUAL k_rate_lines_gated, else k_rate_lines_auto
     unsigned long long *d_gate = nullptr;    // [nch]: the gates, 0 at create; every reset and switch keeps them
     unsigned long long *d_stats = nullptr;   // [nch][4]: emax, emin, njoin, ejoin over the segments since the last reset (gated only)
-    KernelTimer timer{1};                    // 0 k_rate_lines or k_rate_lines_gated, whichever ran
+    unsigned long long *d_stats2 = nullptr;  // [nch][2]: e2, start (k_rate_lines_auto only)
+    unsigned *d_hist = nullptr;              // [nch][321]: the histogram of E; allocated by the first enable with JAERO_GATE_HIST
+    KernelTimer timer{1};                    // 0 k_rate_lines, k_rate_lines_gated or k_rate_lines_auto, whichever ran
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
     bool poisoned = false;
@@ -44,12 +50,18 @@ extern "C" void jaero_rate_destroy(jaero_rate *r)
     delete r;
 }
 
-// the four numbers with no segment yet: 0, 2^64 - 1, 0, 0
+// the four numbers with no segment yet: 0, 2^64 - 1, 0, 0; e2 and start: 0, 2^64 - 1; an empty histogram where there is one; and under
+// AUTO every gate 0, the gate being a function of the numbers cleared here
 static int rate_clear_stats(jaero_rate *r)
 {
     std::vector<unsigned long long> st((size_t)r->nch * 4, 0ull);
     for (int c = 0; c < r->nch; c++) st[(size_t)c * 4 + 1] = ~0ull;
     HIPCHK(hipMemcpy(r->d_stats, st.data(), sizeof(unsigned long long) * st.size(), hipMemcpyHostToDevice));
+    st.assign((size_t)r->nch * 2, 0ull);
+    for (int c = 0; c < r->nch; c++) st[(size_t)c * 2 + 1] = ~0ull;
+    HIPCHK(hipMemcpy(r->d_stats2, st.data(), sizeof(unsigned long long) * st.size(), hipMemcpyHostToDevice));
+    if (r->d_hist) HIPCHK(hipMemset(r->d_hist, 0, sizeof(unsigned) * (size_t)r->nch * RATE_HBINS));
+    if (r->mode & JAERO_GATE_AUTO) HIPCHK(hipMemset(r->d_gate, 0, sizeof(unsigned long long) * (size_t)r->nch));
     return 0;
 }
 
@@ -70,8 +82,10 @@ static int rate_build(std::unique_ptr<jaero_rate> &r, int device, int nchannels,
     HIPCHK(hipMemcpy(r->d_tw, tw.data(), sizeof(double2) * RATE_L, hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute((const void *)k_rate_lines, hipFuncAttributeMaxDynamicSharedMemorySize, RATE_NC * RATE_L * (int)sizeof(double)));
     HIPCHK(hipFuncSetAttribute((const void *)k_rate_lines_gated, hipFuncAttributeMaxDynamicSharedMemorySize, RATE_NC * RATE_L * (int)sizeof(double)));
+    HIPCHK(hipFuncSetAttribute((const void *)k_rate_lines_auto, hipFuncAttributeMaxDynamicSharedMemorySize, RATE_NC * RATE_L * (int)sizeof(double)));
     DA(r->mem, r->d_gate, nchannels);
     DA(r->mem, r->d_stats, (size_t)nchannels * 4);
+    DA(r->mem, r->d_stats2, (size_t)nchannels * 2);
     return rate_clear_stats(r.get());
 }
 
@@ -128,7 +142,15 @@ extern "C" int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples,
     }
     r->poisoned = true; // from here on the sums, the count and the pending segment advance together or not at all
     const int pi = r->timer.begin(0, st);
-    if (r->gated)
+    if (r->mode & (JAERO_GATE_AUTO | JAERO_GATE_HIST))
+    {
+        hipLaunchKernelGGL(k_rate_lines_auto, dim3((unsigned)((r->nch + RATE_NC - 1) / RATE_NC)), dim3(RATE_THREADS), RATE_NC * RATE_L * sizeof(double), st,
+                           (const int16_t *)r->d_pend[r->cur], fill, src, n, r->nch, nseg, (const double2 *)r->d_tw, r->d_R, r->d_gate, r->d_stats,
+                           r->d_stats2, (r->mode & JAERO_GATE_HIST) ? r->d_hist : (unsigned *)nullptr, (r->mode & JAERO_GATE_AUTO) ? 1 : 0,
+                           (unsigned long long)r->nseg);
+        LAUNCHCHK("k_rate_lines_auto");
+    }
+    else if (r->mode == JAERO_GATE_MANUAL)
     {
         hipLaunchKernelGGL(k_rate_lines_gated, dim3((unsigned)((r->nch + RATE_NC - 1) / RATE_NC)), dim3(RATE_THREADS), RATE_NC * RATE_L * sizeof(double), st,
                            (const int16_t *)r->d_pend[r->cur], fill, src, n, r->nch, nseg, (const double2 *)r->d_tw, r->d_R,
@@ -163,27 +185,38 @@ extern "C" int jaero_rate_reset(jaero_rate *r)
     HIPCHK(hipStreamSynchronize(r->last_stream));
     HIPCHK(hipMemset(r->d_R, 0, sizeof(double) * (size_t)r->nch * RATE_BINS));
     r->nseg = 0; // the pending segment stays: the segment grid is absolute
-    return r->gated ? rate_clear_stats(r) : 0; // off, the four numbers are the empty ones already; the gates stay either way
+    return r->mode ? rate_clear_stats(r) : 0; // off, the numbers are the empty ones already; the gates stay but under AUTO
 }
 
 // ---- gated rate lines (include/jaero_hip.h, "gated rate lines")
+static int rate_set_mode(jaero_rate *r, int mode)
+{
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    if ((mode & JAERO_GATE_HIST) && !r->d_hist)
+    {
+        const int rc = dalloc(r->mem, &r->d_hist, (size_t)r->nch * RATE_HBINS);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemset(r->d_R, 0, sizeof(double) * (size_t)r->nch * RATE_BINS));
+    r->nseg = 0; // as a reset: the pending segment stays, and so do the gates unless the new mode has AUTO
+    r->mode = mode;
+    return rate_clear_stats(r);
+}
+
 extern "C" int jaero_gate_enable(jaero_rate *r, int on)
 {
     if (!r) return fail(JAERO_EINVAL, "jaero_gate_enable: null handle");
     RATEPOISONCHK(r, "jaero_gate_enable");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
-    HIPCHK(hipMemset(r->d_R, 0, sizeof(double) * (size_t)r->nch * RATE_BINS));
-    r->nseg = 0; // as a reset: the pending segment stays, and so do the gates
-    r->gated = on != 0;
-    return rate_clear_stats(r);
+    return rate_set_mode(r, on ? JAERO_GATE_MANUAL : 0);
 }
 
 extern "C" int jaero_gate_set(jaero_rate *r, const unsigned long long *gate)
 {
     if (!r || !gate) return fail(JAERO_EINVAL, "jaero_gate_set: null argument");
     RATEPOISONCHK(r, "jaero_gate_set");
-    if (!r->gated) return fail(JAERO_EINVAL, "jaero_gate_set: the gate is off (jaero_gate_enable)");
+    if (!r->mode) return fail(JAERO_EINVAL, "jaero_gate_set: the gate is off (jaero_gate_enable)");
+    if (r->mode & JAERO_GATE_AUTO) return fail(JAERO_EINVAL, "jaero_gate_set: under JAERO_GATE_AUTO the device chooses the gates");
     HIPCHK(hipSetDevice(r->device));
     HIPCHK(hipStreamSynchronize(r->last_stream)); // the launches enqueued so far read the old gates
     HIPCHK(hipMemcpy(r->d_gate, gate, sizeof(unsigned long long) * (size_t)r->nch, hipMemcpyHostToDevice));
@@ -194,11 +227,51 @@ extern "C" int jaero_gate_read(jaero_rate *r, unsigned long long *stats, unsigne
 {
     if (!r || !stats || !nseg) return fail(JAERO_EINVAL, "jaero_gate_read: null argument");
     RATEPOISONCHK(r, "jaero_gate_read");
-    if (!r->gated) return fail(JAERO_EINVAL, "jaero_gate_read: the gate is off (jaero_gate_enable)");
+    if (!r->mode) return fail(JAERO_EINVAL, "jaero_gate_read: the gate is off (jaero_gate_enable)");
     HIPCHK(hipSetDevice(r->device));
     HIPCHK(hipStreamSynchronize(r->last_stream));
     HIPCHK(hipMemcpy(stats, r->d_stats, sizeof(unsigned long long) * (size_t)r->nch * 4, hipMemcpyDeviceToHost));
     if (gate) HIPCHK(hipMemcpy(gate, r->d_gate, sizeof(unsigned long long) * (size_t)r->nch, hipMemcpyDeviceToHost));
+    *nseg = r->nseg;
+    return 0;
+}
+
+// ---- one-pass gates (include/jaero_hip.h, "one-pass gates")
+static_assert(RATE_HBINS == JAERO_GATE_HBINS, "the kernel's histogram row is the ABI's");
+
+extern "C" int jaero_gate2_enable(jaero_rate *r, int mode)
+{
+    if (!r) return fail(JAERO_EINVAL, "jaero_gate2_enable: null handle");
+    const int who = mode & ~JAERO_GATE_HIST; // HIST only together with MANUAL or AUTO, and never both of those
+    if (mode != 0 && who != JAERO_GATE_MANUAL && who != JAERO_GATE_AUTO)
+        return fail(JAERO_EINVAL, "jaero_gate2_enable: mode %d is none of 0, 1, 2, 1|4, 2|4", mode);
+    RATEPOISONCHK(r, "jaero_gate2_enable");
+    return rate_set_mode(r, mode);
+}
+
+extern "C" int jaero_gate2_read(jaero_rate *r, unsigned long long *stats, unsigned long long *gate, long long *nseg)
+{
+    if (!r || !stats || !nseg) return fail(JAERO_EINVAL, "jaero_gate2_read: null argument");
+    RATEPOISONCHK(r, "jaero_gate2_read");
+    if (!(r->mode & JAERO_GATE_AUTO)) return fail(JAERO_EINVAL, "jaero_gate2_read: the mode has no JAERO_GATE_AUTO (jaero_gate2_enable)");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    const size_t w = sizeof(unsigned long long);
+    HIPCHK(hipMemcpy2D(stats, 6 * w, r->d_stats, 4 * w, 4 * w, (size_t)r->nch, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy2D(stats + 4, 6 * w, r->d_stats2, 2 * w, 2 * w, (size_t)r->nch, hipMemcpyDeviceToHost));
+    if (gate) HIPCHK(hipMemcpy(gate, r->d_gate, w * (size_t)r->nch, hipMemcpyDeviceToHost));
+    *nseg = r->nseg;
+    return 0;
+}
+
+extern "C" int jaero_gate2_read_hist(jaero_rate *r, unsigned *hist, long long *nseg)
+{
+    if (!r || !hist || !nseg) return fail(JAERO_EINVAL, "jaero_gate2_read_hist: null argument");
+    RATEPOISONCHK(r, "jaero_gate2_read_hist");
+    if (!(r->mode & JAERO_GATE_HIST)) return fail(JAERO_EINVAL, "jaero_gate2_read_hist: the mode has no JAERO_GATE_HIST (jaero_gate2_enable)");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    HIPCHK(hipMemcpy(hist, r->d_hist, sizeof(unsigned) * (size_t)r->nch * RATE_HBINS, hipMemcpyDeviceToHost));
     *nseg = r->nseg;
     return 0;
 }

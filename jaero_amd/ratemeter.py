@@ -23,6 +23,27 @@ E = sum y^2 reaches the channel's gate, and keeps emax, emin, njoin and ejoin pe
 Limits.  A single click sets emax, and with it the midpoint.  A burst's preamble (a carrier plus lines fb / 2 off it) puts lines fb / 2
 apart into the squared signal, so a short 1200 bps burst can read 600: on the CPU oracle a 500-bit burst did exactly that, which is
 why the bursts of the tests are long.
+
+One-pass gates (jaero_gate2_*, include/jaero_hip.h "one-pass gates").  The flow above needs the signal twice.  Under
+gate_enable(auto=True) the device chooses every gate itself, segment by segment, as suggest_gate would from emin and e2, the SECOND
+largest segment energy: a channel runs under gate 0 until its segments differ by 3 / 2, then restarts -- R is assigned, not added to --
+at the first segment that reaches the new gate, and `start` is that segment's number.  The one-pass flow:
+
+    m.gate_enable(auto=True); ... m.write(...) ...; R, nseg = m.read(); classify_rates(R, m.fs); duty = njoin / (nseg - start)
+
+with emax, emin, njoin, ejoin, e2, start, gate, nseg = m.read_gate_auto() (start is 2^64 - 1 for a channel that never restarted: its
+duty cycle is njoin / nseg).  One click cannot move the gate, because it only ever becomes emax.  gate_enable(hist=True), alone or with
+auto, also counts every completed segment's energy in a histogram of 321 bins, eight an octave (`energy_bin`, `bin_edge`), which gives
+the click-proof two-pass flow for a caller who wants the gates fixed before the pass that counts:
+
+    m.gate_enable(hist=True); ... m.write(...) ...; hist, nseg = m.read_gate_hist()
+    m.set_gate(suggest_gate(*hist_extremes(hist))); m.reset(); ... m.write(...) ...; R, nseg = m.read()
+
+hist_extremes takes the highest and the lowest bin that hold at least two segments, so one click and one dropout fall out.
+gate_enable(auto=True) followed by gate_enable() freezes the device's gates for a second pass in the same way.
+
+Limits of the one-pass gates.  Two clicks set e2.  A dropout (a segment of zeros) sets emin for good.  The segments joined while the
+gate was still rising stay in R: on the burst rows of the tests that is one of 26.
 """
 from __future__ import annotations
 
@@ -35,6 +56,7 @@ from . import capi
 
 L = capi.RATE_L        # segment length, samples
 BINS = capi.RATE_BINS  # bins 0 .. L / 2 of a channel's row
+HBINS = capi.GATE_HBINS  # bins of a channel's histogram of segment energies
 RATES = (600, 1200, 8400, 10500)
 
 
@@ -96,10 +118,18 @@ class RateMeter:
         stays absolute, and so do the gates."""
         capi.check(self.lib.jaero_rate_reset(self.h))
 
-    def gate_enable(self, on: bool = True):
+    def gate_enable(self, on: bool = True, auto: bool = False, hist: bool = False):
         """Switches between the gated meter and the ungated one it is at create (synchronises).  Either way the sums, the count and the
-        four numbers are cleared as by reset(); the pending partial segment and the gates stay."""
-        capi.check(self.lib.jaero_gate_enable(self.h, int(on)))
+        four numbers are cleared as by reset(); the pending partial segment and the gates stay.  auto: the device chooses every gate,
+        segment by segment (the gates start from 0; `set_gate` is refused).  hist: every completed segment's energy is also counted in
+        a histogram (`read_gate_hist`), under the device's gates (auto) or the caller's.  Both need `on`."""
+        if not auto and not hist:
+            capi.check(self.lib.jaero_gate_enable(self.h, int(on)))
+            return
+        if not on:
+            raise ValueError("gate_enable(False) takes neither auto nor hist")
+        mode = (capi.GATE_AUTO if auto else capi.GATE_MANUAL) | (capi.GATE_HIST if hist else 0)
+        capi.check(self.lib.jaero_gate2_enable(self.h, mode))
 
     def set_gate(self, g):
         """g: `nch` non-negative integers below 2^64, one gate per channel; they hold for the segments that later writes complete
@@ -119,6 +149,24 @@ class RateMeter:
         capi.check(self.lib.jaero_gate_read(self.h, st.ctypes.data, gate.ctypes.data, C.byref(n)))
         return st[:, 0].copy(), st[:, 1].copy(), st[:, 2].copy(), st[:, 3].copy(), gate, n.value
 
+    def read_gate_auto(self):
+        """(emax, emin, njoin, ejoin, e2, start, gate, nseg) of a meter under gate_enable(auto=True): `read_gate`'s numbers, the second
+        largest segment energy e2, the segment (counted from the last reset) at which the channel restarted -- 2^64 - 1: it never
+        did --, and the gates the device holds now (synchronises).  njoin and ejoin count from the restart."""
+        st = np.empty((self.nch, 6), dtype=np.uint64)
+        gate = np.empty(self.nch, dtype=np.uint64)
+        n = C.c_longlong(0)
+        capi.check(self.lib.jaero_gate2_read(self.h, st.ctypes.data, gate.ctypes.data, C.byref(n)))
+        return tuple(st[:, i].copy() for i in range(6)) + (gate, n.value)
+
+    def read_gate_hist(self):
+        """(hist uint32 [nch, 321], nseg) of a meter under gate_enable(hist=True): hist[c, b] counts the segments of channel c since the
+        last reset, joined or not, whose energy fell into bin b (`energy_bin`); a row sums to nseg (synchronises)."""
+        hist = np.empty((self.nch, HBINS), dtype=np.uint32)
+        n = C.c_longlong(0)
+        capi.check(self.lib.jaero_gate2_read_hist(self.h, hist.ctypes.data, C.byref(n)))
+        return hist, n.value
+
     def profile_enable(self, on: bool = True):
         capi.check(self.lib.jaero_rate_profile_enable(self.h, int(on)))
 
@@ -133,7 +181,8 @@ def suggest_gate(emax, emin, min_ratio: float = 1.5):
     """Gates from `read_gate`'s emax and emin, in exact integer arithmetic (a list of Python ints, as `set_gate` takes them): the midpoint
     (emax + emin) // 2 where emax > 0 and emax >= min_ratio emin, else 0.  min_ratio is taken as the exact fraction it is written as
     (1.5 = 3 / 2: 2 emax >= 3 emin).  A channel whose strongest and weakest segment differ by less than 1.8 dB counts as continuous and
-    joins everything: 256 segments of white noise or of continuous MSK differ by 1.15.  A single click sets emax."""
+    joins everything: 256 segments of white noise or of continuous MSK differ by 1.15.  A single click sets emax; it does not move
+    `hist_extremes`' pair, which this function takes as well (the empty pair 0, 2^64 - 1 gives gate 0)."""
     from fractions import Fraction
 
     r = Fraction(str(min_ratio))
@@ -142,6 +191,42 @@ def suggest_gate(emax, emin, min_ratio: float = 1.5):
         hi, lo = int(hi), int(lo)
         out.append((hi + lo) // 2 if hi > 0 and hi * r.denominator >= lo * r.numerator else 0)
     return out
+
+
+def energy_bin(E: int) -> int:
+    """The histogram bin of a segment energy E >= 0, in exact integers as the device forms it: E itself below 8, else
+    8 (e - 2) + ((E >> (e - 3)) & 7) with e = floor(log2 E) -- eight bins an octave -- and never past the last bin, 320, which is where
+    the largest possible energy 4096 * 32768^2 = 2^42 lands."""
+    E = int(E)
+    if E < 0:
+        raise ValueError("an energy is not negative")
+    if E < 8:
+        return E
+    e = E.bit_length() - 1
+    return min(8 * (e - 2) + ((E >> (e - 3)) & 7), HBINS - 1)
+
+
+def bin_edge(b: int) -> int:
+    """The smallest energy of bin b (0 .. 320): b below 8, else (8 + b mod 8) << (b div 8 - 1)."""
+    b = int(b)
+    if not 0 <= b < HBINS:
+        raise ValueError(f"bins run 0 .. {HBINS - 1}")
+    return b if b < 8 else (8 + b % 8) << (b // 8 - 1)
+
+
+def hist_extremes(hist, min_count: int = 2):
+    """(emax~, emin~) from `read_gate_hist`'s histogram [nch, 321] (or one row), as uint64 arrays: the lower edges of the highest and of the
+    lowest bin that hold at least `min_count` segments; (0, 2^64 - 1), the empty pair, for a row with no such bin.  With min_count 2 one
+    click and one dropout fall out, so suggest_gate(*hist_extremes(hist)) is a gate that one click cannot move."""
+    h = np.atleast_2d(np.asarray(hist))
+    if h.shape[1] != HBINS:
+        raise ValueError(f"a histogram row has {HBINS} bins, not {h.shape[1]}")
+    hi, lo = [], []
+    for row in h:
+        bins = np.flatnonzero(row >= min_count)
+        hi.append(bin_edge(bins[-1]) if len(bins) else 0)
+        lo.append(bin_edge(bins[0]) if len(bins) else (1 << 64) - 1)
+    return np.array(hi, dtype=np.uint64), np.array(lo, dtype=np.uint64)
 
 
 def classify_rates(R: np.ndarray, fs: float, rates: Sequence[float] = RATES, threshold_db: float = 10.0, kmin: int = 8):

@@ -12,7 +12,16 @@ k_chan_synth 1.40 ms, the OQPSK bank's kernels 23.07 ms).
              full scale on and 0.02 off), the gates at the midpoint of the two levels' segment energies: a workgroup holds channels 2 b and
              2 b + 1, so in 14 writes of 16 neither joins and it skips the transform.  The share of workgroups that skipped is counted from
              njoin (a workgroup skips a write iff none of its channels joins) and recorded beside the time.
-usage: python scripts/ubench/time_rate.py [channels] [steps] [warmup] [--gated] [--out FILE]"""
+
+--auto (default --out profiles/rate_auto_timing.json): k_rate_lines_auto, three meters in one process, each beside k_rate_lines_gated of
+the same build on the same input (the reference: the two kernels do the same work but for the decision and the histogram):
+  level       noise at one level under JAERO_GATE_AUTO: no channel leaves gate 0 (asserted), R bit-identical to the gated kernel's under
+              gate 0 (asserted);
+  burst_bank  the burst bank above under JAERO_GATE_AUTO, beside k_rate_lines_gated with the gates at the midpoint.  A channel runs under
+              gate 0 until its second loud write, so fewer workgroups skip than under gates known in advance; the share is counted
+              from where the rule makes each channel join, which start and njoin must confirm (asserted);
+  manual_hist JAERO_GATE_MANUAL | JAERO_GATE_HIST with every gate 0 on the level noise: what the histogram costs, R bit-identical again.
+usage: python scripts/ubench/time_rate.py [channels] [steps] [warmup] [--gated | --auto] [--out FILE]"""
 import argparse
 import json
 import os
@@ -32,10 +41,11 @@ ap.add_argument("channels", nargs="?", type=int, default=65536)
 ap.add_argument("steps", nargs="?", type=int, default=50)
 ap.add_argument("warmup", nargs="?", type=int, default=5)
 ap.add_argument("--gated", action="store_true")
+ap.add_argument("--auto", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 nch, K, W = args.channels, args.steps, args.warmup
-out = args.out or os.path.join(ROOT, "profiles", "rate_gate_timing.json" if args.gated else "rate_timing.json")
+out = args.out or os.path.join(ROOT, "profiles", "rate_auto_timing.json" if args.auto else "rate_gate_timing.json" if args.gated else "rate_timing.json")
 g = torch.Generator(device="cuda")
 g.manual_seed(1)
 pcm = torch.randint(-8000, 8000, (nch, L), device="cuda", dtype=torch.int32, generator=g).to(torch.int16)
@@ -60,7 +70,79 @@ def timed(m, src):
     return ms / K, 1e3 * dt / K, state.summary()
 
 
+def burst_bank():
+    """16 tensors, channel c loud in tensor c mod 16; the midpoint of the two levels' expected segment energies"""
+    on, off = 0.1 * 32768.0, 0.02 * 32768.0
+    phase = torch.arange(nch, device="cuda") % 16
+    bank = []
+    for p in range(16):
+        amp = torch.where(phase == p, on, off).to(torch.float32)[:, None]
+        bank.append((torch.randn((nch, L), device="cuda", generator=g) * amp).round().clamp(-32768, 32767).to(torch.int16))
+    return bank, int(L * (on * on + off * off) / 2.0)
+
+
+def auto_legs():
+    line = dict(shape)
+    # level noise: the gated kernel under gate 0, then the new kernel under AUTO and under MANUAL | HIST
+    m = RateMeter(nch, 48000.0, max_write_samples=L)
+    m.gate_enable()
+    ms_g, wall_g, box = timed(m, lambda w: pcm)
+    Rg, _ = m.read()
+    m.close()
+    line["level_gated_reference"] = {"k_rate_lines_gated_ms_per_step": round(ms_g, 4), "wall_ms_per_step": round(wall_g, 3), "gpu_state": box}
+    for name, kw in (("level_auto", {"auto": True}), ("manual_hist", {"hist": True})):
+        m = RateMeter(nch, 48000.0, max_write_samples=L)
+        m.gate_enable(**kw)
+        ms1, wall1, box = timed(m, lambda w: pcm)
+        R1, nseg = m.read()
+        assert nseg == W + K and np.array_equal(R1, Rg), name + ": R is not the gated kernel's under gate 0"
+        del R1
+        if "auto" in kw:
+            *_, start, gate, _ = m.read_gate_auto()
+            assert not gate.any() and (start == np.uint64(2 ** 64 - 1)).all(), "a level channel left gate 0"
+        else:
+            hist, _ = m.read_gate_hist()
+            assert (hist.sum(axis=1) == W + K).all()
+        m.close()
+        line[name] = {"k_rate_lines_auto_ms_per_step": round(ms1, 4), "wall_ms_per_step": round(wall1, 3),
+                      "over_gated": round(ms1 / ms_g, 4), "gpu_state": box}
+    del Rg
+    # the burst bank: the gated kernel under the midpoint gates, then the new kernel choosing its own
+    bank, gate = burst_bank()
+    m = RateMeter(nch, 48000.0, max_write_samples=L)
+    m.gate_enable()
+    m.set_gate([gate] * nch)
+    ms_b, wall_b, box = timed(m, lambda w: bank[w % 16])
+    m.close()
+    line["burst_bank_gated_reference"] = {"k_rate_lines_gated_ms_per_step": round(ms_b, 4), "wall_ms_per_step": round(wall_b, 3),
+                                          "workgroups_skipped_share": 0.875, "gate": gate, "gpu_state": box}
+    m = RateMeter(nch, 48000.0, max_write_samples=L)
+    m.gate_enable(auto=True)
+    ms2, wall2, box = timed(m, lambda w: bank[w % 16])
+    _, _, njoin, _, _, start, gates, nseg = m.read_gate_auto()
+    m.close()
+    # by the rule channel c, loud in the writes w with w mod 16 == p = c mod 16, joins every write below p + 16 (gate 0) and restarts there
+    p = np.arange(nch) % 16
+    w = np.arange(W + K)[:, None]
+    joins = (w < p + 16) | (w % 16 == p)                                  # [writes][channels]
+    assert nseg == W + K and np.array_equal(start, (p + 16).astype(np.uint64)) and gates.all()
+    assert np.array_equal(njoin, ((w >= p + 16) & (w % 16 == p)).sum(axis=0).astype(np.uint64)), "the bank's channels did not restart where the rule says"
+    pad = np.concatenate([joins, np.zeros((W + K, nch % 2), dtype=bool)], axis=1)
+    ran = pad.reshape(W + K, -1, 2).any(axis=2)[W:]                       # [timed writes][workgroups]
+    line["burst_bank_auto"] = {"k_rate_lines_auto_ms_per_step": round(ms2, 4), "wall_ms_per_step": round(wall2, 3),
+                               "over_gated": round(ms2 / ms_b, 4), "workgroups_skipped_share": round(1.0 - float(ran.mean()), 4),
+                               "gpu_state": box}
+    return line
+
+
 shape = {"channels": nch, "steps": K, "warmup": W, "samples_per_channel_per_step": L}
+if args.auto:
+    line = auto_legs()
+    print(json.dumps(line))
+    with open(out, "w") as f:
+        json.dump(line, f, indent=1)
+        f.write("\n")
+    sys.exit(0)
 m = RateMeter(nch, 48000.0, max_write_samples=L)
 ms, wall, box = timed(m, lambda w: pcm)
 R, nseg = m.read()
@@ -90,13 +172,7 @@ else:
     line["gate_zero"] = {"k_rate_lines_gated_ms_per_step": round(ms0, 4), "wall_ms_per_step": round(wall0, 3),
                          "over_ungated": round(ms0 / ms, 4), "gpu_state": box}
     # the burst bank: 16 tensors, channel c loud in tensor c mod 16
-    on, off = 0.1 * 32768.0, 0.02 * 32768.0
-    phase = torch.arange(nch, device="cuda") % 16
-    bank = []
-    for p in range(16):
-        amp = torch.where(phase == p, on, off).to(torch.float32)[:, None]
-        bank.append((torch.randn((nch, L), device="cuda", generator=g) * amp).round().clamp(-32768, 32767).to(torch.int16))
-    gate = int(L * (on * on + off * off) / 2.0)  # the midpoint of the two levels' expected segment energies
+    bank, gate = burst_bank()
     m = RateMeter(nch, 48000.0, max_write_samples=L)
     m.gate_enable()
     m.set_gate([gate] * nch)
