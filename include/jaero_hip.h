@@ -573,7 +573,8 @@ int jaero_activity_profile_read(jaero_chan *c, int which, double *total_ms, int 
  *                        grid stays absolute.
  *   jaero_rate_read      synchronises on the handle's last stream; sums[nchannels][2049] = R, *nseg.
  *   jaero_rate_profile_* HIP-event time since the last reset: which 0 = the line kernel (k_rate_lines; k_rate_lines_gated on a gated handle).
- * Deliberately not here: the decision (classify_rates is host numpy over 16 KB per channel), modulation recognition beyond what the rate
+ * Deliberately not here: the decision (classify_rates is host numpy over 16 KB per channel; its selections run on the device since: "rate
+ * lines, read on the device" below), modulation recognition beyond what the rate
  * implies, other L.  A burst channel's lines are diluted by its duty cycle, R being a sum over every segment: the gated rate lines below
  * take its rate while it is on. */
 typedef struct jaero_rate jaero_rate;
@@ -665,6 +666,35 @@ int jaero_gate_read(jaero_rate *r, unsigned long long *stats /* [nchannels][4]: 
 int jaero_gate2_enable(jaero_rate *r, int mode);
 int jaero_gate2_read(jaero_rate *r, unsigned long long *stats /* [nchannels][6]: emax, emin, njoin, ejoin, e2, start */, unsigned long long *gate /* [nchannels], may be null */, long long *nseg);
 int jaero_gate2_read_hist(jaero_rate *r, unsigned *hist /* [nchannels][321] */, long long *nseg);
+
+/* ---- rate lines, read on the device: what jaero_amd.ratemeter.classify_rates does to R before its log10 is selection -- a median, a
+ * three-bin maximum, a search over pairs of bins -- and jaero_lines_classify does it where R lies, so that about 8 + 12 nd bytes a channel
+ * come back in place of 16 392.  This text is the definition; tests/rate_lines_oracle.py implements it literally.
+ *   Inputs: a handle's sums R_c[0 .. 2048] (non-negative doubles); kmin; nd distances d[0 .. nd), integers that the host forms as
+ *   round(fb / (fs / 4096)): the device never sees fs.
+ *   Per channel c:
+ *   floor     the median of R_c[kmin .. 2048]: the middle order statistic for an odd count, (lo + hi) / 2 of the two middle ones for an
+ *             even count (what numpy.median gives).
+ *   P[k]      max(R_c[k - 1], R_c[k], R_c[k + 1]), clipped at k = 0 and k = 2048.
+ *   per distance i: skipped when kmin + d[i] >= 2049: score[i] = 0, where[i] = -1.  Otherwise
+ *   score[i]  = max over kmin <= a < 2049 - d[i] of min(P[a], P[a + d[i]]), and
+ *   where[i]  = the SMALLEST a that attains that maximum (the three-bin maximum makes plateaus of equal P: ties are the normal case).
+ *   No arithmetic but the one halving: floor and score are elements of R (or that mean) bit for bit, and a channel's result does not depend
+ *   on nchannels or on its neighbours.  jaero_amd.ratemeter.decide_rates takes the decision from there on the host (log10, argmax,
+ *   threshold), which makes it equal to classify_rates' unconditionally.
+ *   jaero_lines_classify  checked before any HIP call, JAERO_EINVAL with the argument's name: a null handle or output pointer, nd outside
+ *                         1 .. 8, a d[i] < 1, kmin outside 1 .. 2047.  Then as jaero_rate_read: synchronises on the handle's last stream,
+ *                         launches k_rate_classify on it, copies out floor[nchannels], score[nchannels][nd], where[nchannels][nd] and
+ *                         *nseg.  kernel_ms (may be NULL) receives the launch's HIP-event time.  Works in every gate mode and changes no
+ *                         state of the handle: R, nseg, the gates, the numbers and the pending segment stay.  The result buffers are
+ *                         device allocations of the handle, made by the first call.
+ * jaero_rate_profile_read keeps refusing which != 0: this launch is timed by its own argument.
+ * Deliberately not here: the decision itself (log10 and the threshold are host arithmetic over nd numbers a channel), other row lengths. */
+int jaero_lines_classify(jaero_rate *r, int kmin, int nd, const int *d, double *floor /* [nchannels] */, double *score /* [nchannels][nd] */,
+                         int *where /* [nchannels][nd] */, long long *nseg, double *kernel_ms /* may be null */);
+/* Test hook: overwrites R with sums[nchannels][2049] and the segment count with nseg >= 0 (synchronises), so that the classifier can be run
+ * on rows that no signal produces. */
+int jaero_debug_rate_poke(jaero_rate *r, const double *sums /* [nchannels][2049] */, long long nseg);
 
 /* Host-only debugging aid (no device needed): the sample indices at which jaero_write would run the coarse-frequency
  * estimate for a fresh channel fed `nwrites` writes of write_sizes[i] samples.  Returns the number of triggers

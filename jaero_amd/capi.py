@@ -54,6 +54,7 @@ EXPORTS = [
     "jaero_rate_profile_read",
     "jaero_gate_enable", "jaero_gate_set", "jaero_gate_read",
     "jaero_gate2_enable", "jaero_gate2_read", "jaero_gate2_read_hist",
+    "jaero_lines_classify", "jaero_debug_rate_poke",
     "jaero_shard_range", "jaero_comm_get_unique_id", "jaero_comm_create", "jaero_comm_destroy", "jaero_fan_out_pcm", "jaero_gather_softbits",
 ]
 
@@ -293,6 +294,8 @@ def lib():
     L.jaero_gate2_enable.argtypes = [vp, ip]
     L.jaero_gate2_read.argtypes = [vp, vp, vp, C.POINTER(C.c_longlong)]
     L.jaero_gate2_read_hist.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
+    L.jaero_lines_classify.argtypes = [vp, ip, ip, vp, vp, vp, vp, C.POINTER(C.c_longlong), C.POINTER(dp)]
+    L.jaero_debug_rate_poke.argtypes = [vp, vp, C.c_longlong]
     L.jaero_shard_range.argtypes =[ip, ip, ip, C.POINTER(ip), C.POINTER(ip)]
     L.jaero_comm_get_unique_id.argtypes = [vp]
     L.jaero_comm_create.argtypes = [ip, ip, ip, vp, C.POINTER(vp)]

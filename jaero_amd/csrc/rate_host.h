@@ -13,8 +13,12 @@
 // One-pass gates (jaero_gate2_*): `mode` is 0, JAERO_GATE_MANUAL or JAERO_GATE_AUTO, with or without JAERO_GATE_HIST.  Mode 0 launches
 // k_rate_lines and mode 1 k_rate_lines_gated, as before; every mode with AUTO or HIST launches k_rate_lines_auto, which also keeps e2 and
 // start per channel (d_stats2), writes the gates under AUTO and counts the histogram (d_hist, allocated by the first mode with HIST).
+//
+// Rate lines, read on the device (jaero_lines_classify): k_rate_classify (k_rate_classify.h) reads R and leaves floor, score and where in
+// three buffers of the handle that the first call allocates; the call changes nothing else of the handle.
 #pragma once
 #include "k_rate.h"
+#include "k_rate_classify.h"
 
 static_assert(RATE_L == JAERO_RATE_L && RATE_BINS == JAERO_RATE_BINS, "the kernel's segment and row are the ABI's");
 
@@ -33,6 +37,9 @@ struct jaero_rate
     unsigned long long *d_stats = nullptr;   // [nch][4]: emax, emin, njoin, ejoin over the segments since the last reset (gated only)
     unsigned long long *d_stats2 = nullptr;  // [nch][2]: e2, start (k_rate_lines_auto only)
     unsigned *d_hist = nullptr;              // [nch][321]: the histogram of E; allocated by the first enable with JAERO_GATE_HIST
+    double *d_lfloor = nullptr;              // [nch], [nch][8], [nch][8]: jaero_lines_classify's results; allocated by the first call
+    unsigned long long *d_lscore = nullptr;
+    int *d_lwhere = nullptr;
     KernelTimer timer{1};                    // 0 k_rate_lines, k_rate_lines_gated or k_rate_lines_auto, whichever ran
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
@@ -298,4 +305,74 @@ extern "C" int jaero_rate_profile_read(jaero_rate *r, int which, double *total_m
 {
     if (!r || which != 0) return fail(JAERO_EINVAL, "jaero_rate_profile_read: bad arguments");
     return r->timer.read(r->device, which, total_ms, launches, reset);
+}
+
+// ---- rate lines, read on the device (include/jaero_hip.h, "rate lines, read on the device")
+extern "C" int jaero_lines_classify(jaero_rate *r, int kmin, int nd, const int *d, double *floor, double *score, int *where, long long *nseg,
+                                    double *kernel_ms)
+{
+    if (!r) return fail(JAERO_EINVAL, "jaero_lines_classify: null handle");
+    if (!d) return fail(JAERO_EINVAL, "jaero_lines_classify: d is null");
+    if (!floor) return fail(JAERO_EINVAL, "jaero_lines_classify: floor is null");
+    if (!score) return fail(JAERO_EINVAL, "jaero_lines_classify: score is null");
+    if (!where) return fail(JAERO_EINVAL, "jaero_lines_classify: where is null");
+    if (!nseg) return fail(JAERO_EINVAL, "jaero_lines_classify: nseg is null");
+    if (nd < 1 || nd > RCL_MAXD) return fail(JAERO_EINVAL, "jaero_lines_classify: nd %d outside 1 .. %d", nd, RCL_MAXD);
+    rcl_dist dd = {};
+    for (int i = 0; i < nd; i++)
+    {
+        if (d[i] < 1) return fail(JAERO_EINVAL, "jaero_lines_classify: d[%d] = %d < 1", i, d[i]);
+        dd.d[i] = d[i];
+    }
+    if (kmin < 1 || kmin > RATE_BINS - 2) return fail(JAERO_EINVAL, "jaero_lines_classify: kmin %d outside 1 .. %d", kmin, RATE_BINS - 2);
+    RATEPOISONCHK(r, "jaero_lines_classify");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    if (!r->d_lwhere)
+    {
+        int rc = 0;
+        if (!r->d_lfloor) DA(r->mem, r->d_lfloor, r->nch);
+        if (!r->d_lscore) DA(r->mem, r->d_lscore, (size_t)r->nch * RCL_MAXD);
+        DA(r->mem, r->d_lwhere, (size_t)r->nch * RCL_MAXD);
+    }
+    hipStream_t st = r->last_stream;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (kernel_ms)
+    {
+        HIPCHK(hipEventCreate(&ev[0]));
+        const hipError_t e = hipEventCreate(&ev[1]);
+        if (e != hipSuccess) { (void)hipEventDestroy(ev[0]); HIPCHK(e); }
+        (void)hipEventRecord(ev[0], st);
+    }
+    hipLaunchKernelGGL(k_rate_classify, dim3((unsigned)((r->nch + RCL_NC - 1) / RCL_NC)), dim3(RCL_THREADS), 0, st,
+                       (const unsigned long long *)r->d_R, r->nch, kmin, nd, dd, r->d_lfloor, r->d_lscore, r->d_lwhere);
+    hipError_t e = hipGetLastError();
+    if (kernel_ms) (void)hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    float ms = 0.0f;
+    if (kernel_ms)
+    {
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+    }
+    if (e != hipSuccess) return fail(JAERO_EHIP, "jaero_lines_classify: k_rate_classify failed: %s", hipGetErrorString(e));
+    HIPCHK(hipMemcpy(floor, r->d_lfloor, sizeof(double) * (size_t)r->nch, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(score, r->d_lscore, sizeof(double) * (size_t)r->nch * nd, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(where, r->d_lwhere, sizeof(int) * (size_t)r->nch * nd, hipMemcpyDeviceToHost));
+    if (kernel_ms) *kernel_ms = (double)ms;
+    *nseg = r->nseg;
+    return 0;
+}
+
+extern "C" int jaero_debug_rate_poke(jaero_rate *r, const double *sums, long long nseg)
+{
+    if (!r || !sums) return fail(JAERO_EINVAL, "jaero_debug_rate_poke: null argument");
+    if (nseg < 0) return fail(JAERO_EINVAL, "jaero_debug_rate_poke: nseg %lld < 0", nseg);
+    RATEPOISONCHK(r, "jaero_debug_rate_poke");
+    HIPCHK(hipSetDevice(r->device));
+    HIPCHK(hipStreamSynchronize(r->last_stream));
+    HIPCHK(hipMemcpy(r->d_R, sums, sizeof(double) * (size_t)r->nch * RATE_BINS, hipMemcpyHostToDevice));
+    r->nseg = nseg;
+    return 0;
 }

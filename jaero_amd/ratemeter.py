@@ -44,6 +44,15 @@ gate_enable(auto=True) followed by gate_enable() freezes the device's gates for 
 
 Limits of the one-pass gates.  Two clicks set e2.  A dropout (a segment of zeros) sets emin for good.  The segments joined while the
 gate was still rising stay in R: on the burst rows of the tests that is one of 26.
+
+Rate lines, read on the device (jaero_lines_classify, include/jaero_hip.h "rate lines, read on the device").  `read()` brings 16 KB a
+channel to the host; everything `classify_rates` does to them before its log10 is selection -- a median, a three-bin maximum, a search
+over pairs of bins -- and `classify_lines` does that where R lies, bit for bit, so that floor, nd scores and nd positions a channel
+come back.  `decide_rates` finishes on those.  In every flow above
+
+    R, nseg = m.read(); rate, audio, score = classify_rates(R, m.fs)      becomes      rate, audio, score = m.classify()
+
+with equal results (np.array_equal), in every gate mode; classify_rates stays, and is the reference the one-call form is tested against.
 """
 from __future__ import annotations
 
@@ -167,6 +176,39 @@ class RateMeter:
         capi.check(self.lib.jaero_gate2_read_hist(self.h, hist.ctypes.data, C.byref(n)))
         return hist, n.value
 
+    def classify_lines(self, d: Sequence[int], kmin: int = 8):
+        """(floor [nch], score [nch, nd], where [nch, nd] int32, nseg): the rate lines read on the device (jaero_lines_classify).  d: 1 to
+        8 line distances in bins (`rate_distances`).  floor is the median of R[kmin:]; score[i] the largest min(P[a], P[a + d[i]]) over
+        kmin <= a < 2049 - d[i], P the three-bin maximum, and where[i] the smallest a that attains it; a distance with kmin + d[i] >= 2049
+        is skipped (score 0, where -1).  floor and score are elements of R (or the mean of two) bit for bit.  Synchronises; changes nothing
+        of the meter.  `kernel_ms` holds the HIP-event time of this call's launch."""
+        dd = np.ascontiguousarray(d, dtype=np.int32).reshape(-1)
+        if dd.size and not np.array_equal(dd, np.asarray(d).reshape(-1)):
+            raise ValueError("classify_lines takes integer distances")
+        nd = int(dd.size)
+        floor = np.empty(self.nch, dtype=np.float64)
+        score = np.empty((self.nch, max(nd, 1)), dtype=np.float64)
+        where = np.empty((self.nch, max(nd, 1)), dtype=np.int32)
+        n, ms = C.c_longlong(0), C.c_double(0.0)
+        capi.check(self.lib.jaero_lines_classify(self.h, int(kmin), nd, dd.ctypes.data, floor.ctypes.data, score.ctypes.data, where.ctypes.data,
+                                                 C.byref(n), C.byref(ms)))
+        self.kernel_ms = ms.value
+        return floor, score, where, n.value
+
+    def classify(self, rates: Sequence[float] = RATES, threshold_db: float = 10.0, kmin: int = 8):
+        """(rate [nch], audio_hz [nch], score_db [nch, len(rates)]): `classify_rates(self.read()[0], self.fs, ...)` without the copy of R --
+        `classify_lines` on the device, `decide_rates` on its few numbers a channel.  The two are equal, not merely close."""
+        d = rate_distances(self.fs, rates)
+        floor, score, where, _ = self.classify_lines(d, kmin)
+        return decide_rates(floor, score, where, d, self.fs, rates, threshold_db)
+
+    def poke(self, R: np.ndarray, nseg: int):
+        """Test hook (jaero_debug_rate_poke): overwrites the sums with R [nch, 2049] and the segment count with nseg (synchronises)."""
+        a = np.ascontiguousarray(R, dtype=np.float64)
+        if a.shape != (self.nch, BINS):
+            raise ValueError(f"poke takes [{self.nch}, {BINS}] float64, not {a.shape}")
+        capi.check(self.lib.jaero_debug_rate_poke(self.h, a.ctypes.data, int(nseg)))
+
     def profile_enable(self, on: bool = True):
         capi.check(self.lib.jaero_rate_profile_enable(self.h, int(on)))
 
@@ -268,5 +310,42 @@ def classify_rates(R: np.ndarray, fs: float, rates: Sequence[float] = RATES, thr
     rate = np.where(hit, np.asarray(rates)[best], 0)
     audio = np.where(hit, (2 * where[np.arange(nch), best] + np.asarray(ds)[best]) * bw / 4.0, np.nan)
     if np.ndim(R) == 1:
+        return rate[0], audio[0], score_db[0]
+    return rate, audio, score_db
+
+
+def rate_distances(fs: float, rates: Sequence[float] = RATES):
+    """The distance in bins of each rate's two lines at sample rate `fs`, round(fb / (fs / 4096)) as `classify_rates` forms it: what
+    `RateMeter.classify_lines` takes."""
+    bw = float(fs) / L
+    return [int(round(fb / bw)) for fb in rates]
+
+
+def decide_rates(floor, score, where, d: Sequence[int], fs: float, rates: Sequence[float] = RATES, threshold_db: float = 10.0):
+    """(rate [nch], audio_hz [nch], score_db [nch, len(rates)]) from `RateMeter.classify_lines`' floor [nch], score and where [nch, nd] for
+    the distances d = rate_distances(fs, rates): what `classify_rates` does behind its search, on nd numbers a channel.  score_db = 10
+    log10(score / floor), nan -> -inf, a skipped distance (where < 0) -inf; the winner is the first largest score_db -- taken here, on the
+    dB values, as classify_rates takes it, so that two raw scores that round to one dB value tie in both --; then the threshold; audio =
+    (2 where + d) bw / 4.  One row in (floor a scalar), scalars out."""
+    one = np.ndim(floor) == 0
+    floor = np.atleast_1d(np.asarray(floor, dtype=np.float64))
+    score = np.atleast_2d(np.asarray(score, dtype=np.float64))
+    where = np.atleast_2d(np.asarray(where)).astype(np.int64)
+    nch = floor.shape[0]
+    if len(d) != len(rates) or score.shape != (nch, len(rates)) or where.shape != score.shape:
+        raise ValueError("decide_rates takes one distance, one score and one position per rate and channel")
+    bw = float(fs) / L
+    score_db = np.full((nch, len(rates)), -np.inf)
+    for i in range(len(rates)):
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            s = 10.0 * np.log10(score[:, i] / floor)
+        score_db[:, i] = np.where(np.isnan(s) | (where[:, i] < 0), -np.inf, s)
+    where = np.where(where < 0, 0, where)
+    best = np.argmax(score_db, axis=1)  # the first of equal maxima
+    top = score_db[np.arange(nch), best]
+    hit = top >= threshold_db
+    rate = np.where(hit, np.asarray(rates)[best], 0)
+    audio = np.where(hit, (2 * where[np.arange(nch), best] + np.asarray(d)[best]) * bw / 4.0, np.nan)
+    if one:
         return rate[0], audio[0], score_db[0]
     return rate, audio, score_db

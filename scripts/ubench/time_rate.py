@@ -21,7 +21,13 @@ the same build on the same input (the reference: the two kernels do the same wor
               gate 0 until its second loud write, so fewer workgroups skip than under gates known in advance; the share is counted
               from where the rule makes each channel join, which start and njoin must confirm (asserted);
   manual_hist JAERO_GATE_MANUAL | JAERO_GATE_HIST with every gate 0 on the level noise: what the histogram costs, R bit-identical again.
-usage: python scripts/ubench/time_rate.py [channels] [steps] [warmup] [--gated | --auto] [--out FILE]"""
+
+--classify (default --out profiles/rate_classify_timing.json): the rate lines read on the device, k_rate_classify, after 8 written
+segments of the noise above.  RateMeter.classify_lines `steps` times (default 20) after `warmup` (default 3): the HIP-event time of the
+launch and the wall time per call (launch, synchronise, copy out 56 bytes a channel).  Then once, in the same process, the host path it
+replaces, its wall time split into read() (16 392 bytes a channel over PCIe) and classify_rates (numpy); the two decisions are asserted
+equal.  Beside them what one read of R costs at the rate on record for k_rate_lines (2.5 TB/s), and the two ratios.
+usage: python scripts/ubench/time_rate.py [channels] [steps] [warmup] [--gated | --auto | --classify] [--out FILE]"""
 import argparse
 import json
 import os
@@ -34,18 +40,22 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from bench_state import GpuStateSampler  # noqa: E402
-from jaero_amd.ratemeter import L, RateMeter  # noqa: E402
+from jaero_amd.ratemeter import BINS, L, RATES, RateMeter, classify_rates, decide_rates, rate_distances  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("channels", nargs="?", type=int, default=65536)
-ap.add_argument("steps", nargs="?", type=int, default=50)
-ap.add_argument("warmup", nargs="?", type=int, default=5)
+ap.add_argument("steps", nargs="?", type=int, default=None)
+ap.add_argument("warmup", nargs="?", type=int, default=None)
 ap.add_argument("--gated", action="store_true")
 ap.add_argument("--auto", action="store_true")
+ap.add_argument("--classify", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
-nch, K, W = args.channels, args.steps, args.warmup
-out = args.out or os.path.join(ROOT, "profiles", "rate_auto_timing.json" if args.auto else "rate_gate_timing.json" if args.gated else "rate_timing.json")
+nch = args.channels
+K = args.steps if args.steps is not None else (20 if args.classify else 50)
+W = args.warmup if args.warmup is not None else (3 if args.classify else 5)
+out = args.out or os.path.join(ROOT, "profiles", "rate_classify_timing.json" if args.classify else "rate_auto_timing.json" if args.auto
+                               else "rate_gate_timing.json" if args.gated else "rate_timing.json")
 g = torch.Generator(device="cuda")
 g.manual_seed(1)
 pcm = torch.randint(-8000, 8000, (nch, L), device="cuda", dtype=torch.int32, generator=g).to(torch.int16)
@@ -135,9 +145,49 @@ def auto_legs():
     return line
 
 
+def classify_legs():
+    segs = 8
+    m = RateMeter(nch, 48000.0, max_write_samples=L)
+    for _ in range(segs):
+        assert m.write_device(pcm.data_ptr(), L, stream=st) == 1
+    d = rate_distances(m.fs)
+    for _ in range(W):
+        m.classify_lines(d)
+    kernel, wall = [], []
+    state = GpuStateSampler().start("timed")
+    for _ in range(K):
+        t0 = time.perf_counter()
+        floor, score, where, nseg = m.classify_lines(d)
+        wall.append(1e3 * (time.perf_counter() - t0))
+        kernel.append(m.kernel_ms)
+    state.stop()
+    assert nseg == segs
+    got = decide_rates(floor, score, where, d, m.fs)
+    t0 = time.perf_counter()
+    R, _ = m.read()
+    t1 = time.perf_counter()
+    want = classify_rates(R, m.fs)
+    t2 = time.perf_counter()
+    m.close()
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1], equal_nan=True) and np.array_equal(got[2], want[2]), \
+        "the two paths decide differently"
+    k_ms, w_ms = float(np.mean(kernel)), float(np.mean(wall))
+    read_ms, host_ms = 1e3 * (t1 - t0), 1e3 * (t2 - t1)
+    r_bytes = nch * BINS * 8
+    one_read_ms = 1e3 * r_bytes / 2.5e12  # what one read of R costs at the rate on record for k_rate_lines
+    return {"channels": nch, "calls": K, "warmup": W, "segments_written": segs, "distances": d, "rates": list(RATES),
+            "R_bytes": r_bytes, "result_bytes_per_channel": 8 + 12 * len(d),
+            "k_rate_classify_ms_per_call": round(k_ms, 4), "k_rate_classify_ms_min_max": [round(min(kernel), 4), round(max(kernel), 4)],
+            "classify_lines_wall_ms_per_call": round(w_ms, 3),
+            "one_read_of_R_at_2p5_TBps_ms": round(one_read_ms, 4), "kernel_over_one_read": round(k_ms / one_read_ms, 3),
+            "host_path_once": {"read_wall_ms": round(read_ms, 1), "classify_rates_wall_ms": round(host_ms, 1),
+                               "wall_ms": round(read_ms + host_ms, 1)},
+            "host_wall_over_device_wall": round((read_ms + host_ms) / w_ms, 1), "decisions_equal": True, "gpu_state": state.summary()}
+
+
 shape = {"channels": nch, "steps": K, "warmup": W, "samples_per_channel_per_step": L}
-if args.auto:
-    line = auto_legs()
+if args.auto or args.classify:
+    line = classify_legs() if args.classify else auto_legs()
     print(json.dumps(line))
     with open(out, "w") as f:
         json.dump(line, f, indent=1)
