@@ -450,18 +450,28 @@ __device__ __forceinline__ void fb_back(const JGeom &g, const JPtrs &p, FbLds &L
             if (st_freq > (g.stref_freq + 0.1)) fb_wt_setfreq(st_freq, st_step, (g.stref_freq + 0.1), samplerate, r_samplerate);
         }
         if constexpr (!PRE8400) FB_TRACE(1); // mailbox read, symbol timing: delays, resonator, atan2, oscillator nudges
+        // queued output halves: all lanes together every FB_DEFER samples (a wave-uniform test) -- IN FRONT of this sample's record requests,
+        // and only for lanes whose records were requested in an earlier sample.  The batch reads px_*, and its wait for them is a wait for
+        // every load of the wavefront up to the newest: behind this sample's requests (one lane in nine has one: fresh HBM misses) the whole
+        // batch stood for the length of a miss, 3 us at the full bank.  A lane queued one sample ago keeps its symbol for
+        // the next batch point, FB_DEFER + 1 = 9 samples after it was queued, where it goes in front of the lane's next symbol: two symbols of
+        // a lane are 9 or 10 samples apart (11 or 12 at 8400 bps), so the one-deep queue still never overflows in lock.
+        if ((i & (FB_DEFER - 1)) == 0)
+        {
+            if (pend && !need_px) output_half();
+        }
+        if constexpr (!PRE8400) FB_TRACE(2); // queued output halves (every FB_DEFER-th sample)
         if (need_px) request_px(); // for the symbol queued in the previous sample
-        if constexpr (!PRE8400) FB_TRACE(5); // (finer split of the third row: the record requests)
+        if constexpr (!PRE8400) FB_TRACE(5); // (the record requests)
 
         // ---- K10..K14 at symbol instants (:487-595) ----
         if (!sig2l_init) { sig2l_re = sre; sig2l_im = sim; sig2l_init = 1; }
         double frac;
         const bool inst = jd_wt_passed(st_last, st_ptr, st_step, g.ee, frac);
         const bool full = inst && (yui == 0); // yui flips to 1 at this instant: the instant that closes a symbol pair
-        if constexpr (!PRE8400) FB_TRACE(6); // (the instant test)
-        // queued output halves: all lanes together every FB_DEFER samples; a lane about to queue a second one goes first
-        if (pend && (full || (i & (FB_DEFER - 1)) == 0)) output_half();
-        if constexpr (!PRE8400) FB_TRACE(2); // record requests, instant test, queued output halves (every 16th sample)
+        // a lane about to queue a second symbol runs its output half first (its records were requested above at the latest)
+        if (pend && full) output_half();
+        if constexpr (!PRE8400) FB_TRACE(6); // (the instant test, the output half of a lane about to queue a second symbol)
         if (inst)
         {
             const double pt_last = frac, pt_this = 1.0 - pt_last;
