@@ -719,3 +719,37 @@ __device__ __forceinline__ double jd_log10(double x)
     const double ef = (double)e;
     return fma(ef, ch, fma(ef, cl, u));
 }
+
+// 0.5 * jd_log10(x), bit for bit, without the product: the four constants are halved.  Every operation behind them is a product with one
+// of them or a sum of such terms, x >= 1 keeps all of them far from underflow, and a scaling by 2^-1 commutes with each rounding
+// (tests/test_gpu_log10_half.py compares the two on the families of tests/test_gpu_device_math.py).  Named for its one user, the
+// estimate kernels' epilogue (k_coarse6.h); it stands here because the test library includes this header alone.
+__device__ __forceinline__ double c6_log10_half(double x)
+{
+#pragma clang fp contract(fast)
+    int e;
+    double m = frexp(x, &e);
+    if (m < 0.70710678118654752440) { m *= 2.0; e -= 1; }
+    const double d = m + 1.0, n = m - 1.0; // both exact
+    double r = __builtin_amdgcn_rcp(d);
+    r = fma(fma(-d, r, 1.0), r, r);
+    r = fma(fma(-d, r, 1.0), r, r);
+    const double s = n * r;
+    const double sl = fma(-d, s, n) * r; // n / d = s + sl
+    const double z = s * s;
+    double q = 1.0 / 19.0;
+    q = fma(q, z, 1.0 / 17.0);
+    q = fma(q, z, 1.0 / 15.0);
+    q = fma(q, z, 1.0 / 13.0);
+    q = fma(q, z, 1.0 / 11.0);
+    q = fma(q, z, 1.0 / 9.0);
+    q = fma(q, z, 1.0 / 7.0);
+    q = fma(q, z, 1.0 / 5.0);
+    q = fma(q, z, 1.0 / 3.0);
+    const double t = fma(s * z, q, sl); // log(m) / 2 = s + t
+    const double kh = 0x1.bcb7b1526e50ep-2, kl = 0x1.95355baaafad3p-57;  // log10(e)
+    const double ch = 0x1.34413509f79ffp-3, cl = -0x1.9dc1da994fd21p-60; // log10(2) / 2
+    const double u = fma(s, kh, fma(t, kh, s * kl));                     // log10(m) / 2
+    const double ef = (double)e;
+    return fma(ef, ch, fma(ef, cl, u));
+}

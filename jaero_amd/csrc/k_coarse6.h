@@ -125,6 +125,26 @@ __device__ __forceinline__ void c6_twiddle32(CV<32> &x, const double2 p1)
 #define C6_ABSORB 2
 #endif
 
+// The instruction diet of DESIGN 9 item 34 (profiles/coarse_diet.md): one switch per item, 0 = the parent's code.
+#ifndef C6_HIADDR
+#define C6_HIADDR 1 // LDS bytes above 64 KiB addressed from a second per-thread base with immediate offsets
+#endif
+#ifndef C6_RINGADDR
+#define C6_RINGADDR 1 // ring entries addressed by a 32-bit byte offset from a scalar base: add + mask per slot
+#endif
+#ifndef C6_BAND1
+#define C6_BAND1 1 // band limit: one unsigned range test per slot
+#endif
+#ifndef C6_SQFMA
+#define C6_SQFMA 1 // the squaring and |X|^2 with one product and one fused multiply-add each
+#endif
+#ifndef C6_LOGHALF
+#define C6_LOGHALF 1 // 0.5 * log10 from halved constants (c6_log10_half)
+#endif
+#ifndef C6_P1FUSED
+#define C6_P1FUSED 1 // pass 1's butterflies with a constant root in the fused form of the absorbed passes
+#endif
+
 __device__ __forceinline__ constexpr int c6_brev(int v, int bits)
 {
     int r = 0;
@@ -152,6 +172,40 @@ __device__ __forceinline__ void c6_ratio_powers(const double2 r, double2 (&P)[5]
     P[0] = r;
 #pragma unroll
     for (int i = 1; i < 5; i++) P[i] = c6_sq(P[i - 1]);
+}
+
+// In-place forward 32-point DFT, natural order in, X[k] left in slot c6_brev(k, 5): c6_afft<32, 0, 0> for the ratio 1, whose multipliers
+// are the constant roots alone.  A first pass (no twiddle to absorb) in this form: the 34 butterflies with a root other than 1 and -i are
+// six fused multiply-adds instead of four additions and a complex product (two products, two fused), the 46 others four additions.
+__device__ __forceinline__ void c6_cfft32(CV<32> &x)
+{
+#pragma unroll
+    for (int lv = 0; lv < 5; lv++)
+    {
+#pragma unroll
+        for (int b = 0; b < (1 << lv); b++)
+        {
+            const int half = 16 >> lv, idx = half * 2 * c6_brev(b, lv), e = idx & 15; // the root W_64^idx, idx < 32
+            const double cr = jd_w64r(e), ci = jd_w64i(e);
+            const double wr = (idx & 16) ? ci : cr, wi = (idx & 16) ? -cr : ci;         // idx >= 16: -i times the root of idx - 16
+#pragma unroll
+            for (int j = 0; j < half; j++)
+            {
+                const int ia = 2 * half * b + j, ib = ia + half;
+                const double ar = x.r[ia], ai = x.i[ia], br = x.r[ib], bi = x.i[ib];
+                if (idx == 0) { x.r[ia] = ar + br; x.i[ia] = ai + bi; x.r[ib] = ar - br; x.i[ib] = ai - bi; }
+                else if (idx == 16) { x.r[ia] = ar + bi; x.i[ia] = ai - br; x.r[ib] = ar - bi; x.i[ib] = ai + br; }
+                else
+                {
+                    const double ur = __builtin_fma(-wi, bi, __builtin_fma(wr, br, ar));
+                    const double ui = __builtin_fma(wr, bi, __builtin_fma(wi, br, ai));
+                    x.r[ia] = ur; x.i[ia] = ui;
+                    x.r[ib] = __builtin_fma(2.0, ar, -ur); x.i[ib] = __builtin_fma(2.0, ai, -ui);
+                }
+            }
+        }
+        C6_FENCE;
+    }
 }
 
 // In-place forward L-point DFT (L = 32, 16) of x[OFF .. OFF + L) times (r W_64^Z)^j, r^(2^i) in P; X[k] is left in slot OFF + c6_brev(k).
@@ -248,7 +302,9 @@ __device__ __forceinline__ void c6_pass3(CV<32> &d, const double2 r)
 //   pass 3: two FFT16 over n3 of their input x W_N^((k1 + 32 k2) n3)
 // (AB 1: pass 2's outputs x W_N^((k1 + 32 k2) n3) instead, pass 3 as for AB 0.)  Index maps, ratios and bank behaviour of this form:
 // tests/test_coarse_fft14_absorbed_model.py.
-template <int AB = C6_ABSORB>
+// HI: the upper half of exchange 2 (byte offsets from 65 664, beyond the 16-bit offset field of a DS instruction) is addressed from bases
+// of its own, formed once per transform, instead of one literal add per access.
+template <int AB = C6_ABSORB, bool P1 = (AB > 0) && C6_P1FUSED, bool HI = false>
 __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const double2 *__restrict__ tw, int t)
 {
 #pragma clang fp contract(fast)
@@ -267,21 +323,24 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
     const int e2w = k1u + n3 * 513;                             // writer: + (k2 & 15) * 32 + (k2 >> 4) * 8208
     const int e2r = t;                                          // reader: + n3 * 513 + k2hi * 8208
     auto k2of = [](int s) __attribute__((always_inline)) { return AB ? c6_brev(s, 5) : c6_k(s); }; // the k2 that slot s holds behind pass 2
+    auto k1of = [](int s) __attribute__((always_inline)) { return P1 ? c6_brev(s, 5) : c6_k(s); }; // the k1 behind pass 1 (P1: c6_cfft32)
 
     // ---- pass 1 ----
-    c6_fft32(d);
+    static_assert(!(P1 && AB == 0), "the output twiddle of AB 0 expects split order");
+    if constexpr (P1) c6_cfft32(d);
+    else c6_fft32(d);
     if constexpr (AB == 0) c6_twiddle32(d, st1);
     C6_FENCE;
     // ---- exchange 1, a plane at a time ----
     jd_lds_barrier(); // the buffer is free (previous transform's last reads / the fold)
 #pragma unroll
-    for (int s = 0; s < 32; s++) xch[c6_k(s) * 512 + ((c6_k(s) & 1) ? e1w1 : e1w0)] = d.r[s];
+    for (int s = 0; s < 32; s++) xch[k1of(s) * 512 + ((k1of(s) & 1) ? e1w1 : e1w0)] = d.r[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = xch[(m < 31 ? e1r + 16 * m : e1rw)];
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) xch[c6_k(s) * 512 + ((c6_k(s) & 1) ? e1w1 : e1w0)] = d.i[s];
+    for (int s = 0; s < 32; s++) xch[k1of(s) * 512 + ((k1of(s) & 1) ? e1w1 : e1w0)] = d.i[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = xch[(m < 31 ? e1r + 16 * m : e1rw)];
@@ -301,18 +360,25 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
     }
     C6_FENCE;
     // ---- exchange 2 ----
+    // the upper half of k2: + 8208.  HI: in the base, opaque so that the constant does not return to each access as a literal
+    int e2wh = e2w + (HI ? 8208 : 0), e2rh = e2r + (HI ? 8208 : 0);
+    if constexpr (HI) asm volatile("" : "+v"(e2wh), "+v"(e2rh));
+    constexpr int UP = HI ? 0 : 8208;
+    // HI: the stores in the order of k2, so that neighbours 256 bytes apart stand next to each other and pair into ds_write2_b64 (stores
+    // from an opaque base are not moved past each other)
+    auto sof = [](int q) __attribute__((always_inline)) { return !HI ? q : AB ? c6_brev(q, 5) : (q & 1) ? 16 + (q >> 1) : (q >> 1); };
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) xch[e2w + (k2of(s) & 15) * 32 + (k2of(s) >> 4) * 8208] = d.r[s];
+    for (int q = 0; q < 32; q++) xch[(k2of(sof(q)) >> 4 ? e2wh + UP : e2w) + (k2of(sof(q)) & 15) * 32] = d.r[sof(q)];
     jd_lds_barrier();
 #pragma unroll
-    for (int m = 0; m < 32; m++) d.r[m] = xch[e2r + (m & 15) * 513 + (m >> 4) * 8208]; // slot m = n3 + 16 k2hi
+    for (int m = 0; m < 32; m++) d.r[m] = xch[(m >> 4 ? e2rh + UP : e2r) + (m & 15) * 513]; // slot m = n3 + 16 k2hi
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) xch[e2w + (k2of(s) & 15) * 32 + (k2of(s) >> 4) * 8208] = d.i[s];
+    for (int q = 0; q < 32; q++) xch[(k2of(sof(q)) >> 4 ? e2wh + UP : e2w) + (k2of(sof(q)) & 15) * 32] = d.i[sof(q)];
     jd_lds_barrier();
 #pragma unroll
-    for (int m = 0; m < 32; m++) d.i[m] = xch[e2r + (m & 15) * 513 + (m >> 4) * 8208];
+    for (int m = 0; m < 32; m++) d.i[m] = xch[(m >> 4 ? e2rh + UP : e2r) + (m & 15) * 513];
     C6_FENCE;
     // ---- pass 3: FFT16 over n3 for k2hi = 0, 1; X[.. + 1024 k3] -> slot 2 k3 + k2hi (= natural: k = slot * 512 + t) ----
     c6_pass3<AB == 2>(d, st2);
@@ -331,7 +397,7 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
 // Exchange 1: L = k1 * 256 + 16 n2 + n3 (both sides touch consecutive doubles per 16 lanes).  Exchange 2: L = k1 + 32 k2 + 513 n3 (the 16
 // lanes of a writer group differ in n3 only: the odd stride spreads them over the 16 bank pairs; readers touch 64 consecutive doubles).
 #define C6_XCH13 8208
-template <int AB = C6_ABSORB>
+template <int AB = C6_ABSORB, bool P1 = (AB > 0) && C6_P1FUSED>
 __device__ __forceinline__ void wg_fft13_e32(CV<32> &d, double *xch, const double2 *__restrict__ tw, int t)
 {
 #pragma clang fp contract(fast)
@@ -341,20 +407,23 @@ __device__ __forceinline__ void wg_fft13_e32(CV<32> &d, double *xch, const doubl
     const int e1r = k1a * 256 + n3;   // reader of exchange 1: + (m >> 4) * 4096 + (m & 15) * 16
     const int e2w = k1a + 513 * n3;   // writer of exchange 2: + 16 g + 32 k2
     auto k2of = [](int s) __attribute__((always_inline)) { return AB ? c6_brev(s & 15, 4) : (s & 15); }; // the k2 slot s holds behind pass 2
+    auto k1of = [](int s) __attribute__((always_inline)) { return P1 ? c6_brev(s, 5) : c6_k(s); };       // the k1 behind pass 1 (P1: c6_cfft32)
     // ---- pass 1 ----
-    c6_fft32(d);
+    static_assert(!(P1 && AB == 0), "the output twiddle of AB 0 expects split order");
+    if constexpr (P1) c6_cfft32(d);
+    else c6_fft32(d);
     if constexpr (AB == 0) c6_twiddle32(d, st1);
     C6_FENCE;
     // ---- exchange 1, a plane at a time ----
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) (xch + c6_k(s) * 256)[t] = d.r[s];
+    for (int s = 0; s < 32; s++) (xch + k1of(s) * 256)[t] = d.r[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.r[m] = (xch + (m >> 4) * 4096 + (m & 15) * 16)[e1r];
     jd_lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 32; s++) (xch + c6_k(s) * 256)[t] = d.i[s];
+    for (int s = 0; s < 32; s++) (xch + k1of(s) * 256)[t] = d.i[s];
     jd_lds_barrier();
 #pragma unroll
     for (int m = 0; m < 32; m++) d.i[m] = (xch + (m >> 4) * 4096 + (m & 15) * 16)[e1r];
@@ -408,8 +477,8 @@ __device__ __forceinline__ void c6_fft(CV<32> &d, double *xch, const double2 *__
 {
     int tt = t; // laundered per call: nothing derived from it inside is shared between the three calls of an estimate and kept live
     asm volatile("" : "+v"(tt));
-    if constexpr (LOG2N == 14) wg_fft14_e32(d, xch, tw, tt);
-    else wg_fft13_e32(d, xch, tw, tt);
+    if constexpr (LOG2N == 14) wg_fft14_e32<C6_ABSORB, (C6_ABSORB > 0) && C6_P1FUSED, C6_HIADDR != 0>(d, xch, tw, tt);
+    else wg_fft13_e32<C6_ABSORB, (C6_ABSORB > 0) && C6_P1FUSED>(d, xch, tw, tt);
 }
 
 // the 8400 bps window's startbin + 2 table entries (coarsefreqestimate.cpp:61-74).  Out of line on purpose: it runs when a channel's locking
@@ -475,10 +544,17 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         // previous estimate was in its peak search / state machine
         if (li == (int)blockIdx.x)
         {
+#if C6_RINGADDR
+            const unsigned boff = ((unsigned)(bb_ptr + t) & (unsigned)(N - 1)) << 4;
+#endif
 #pragma unroll
             for (int s = 0; s < E; s++)
             {
+#if C6_RINGADDR
+                const double2 v = *(const double2 *)((const char *)ring + ((boff + (unsigned)(s * NT * 16)) & (unsigned)(N * 16 - 1)));
+#else
                 const double2 v = ring[(bb_ptr + s * NT + t) & (N - 1)];
+#endif
                 d.r[s] = v.x; d.i[s] = v.y;
             }
         }
@@ -519,11 +595,21 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         }
         else
         {
+#if C6_BAND1
+            // one unsigned range test per slot instead of two compares: k in [startbin, stopbin] <=> (unsigned)(k - startbin) <= stopbin -
+            // startbin.  A locking bandwidth above Fs / 2 makes the range empty (stopbin < startbin): -1 and 0 match no k >= 0.
+            const int band_lo = stopbin < startbin ? -1 : startbin;
+            const unsigned band_w = stopbin < startbin ? 0u : (unsigned)(stopbin - startbin);
+#endif
 #pragma unroll
             for (int s = 0; s < E; s++)
             {
                 const int k = s * NT + t;
+#if C6_BAND1
+                const bool z = (unsigned)(k - band_lo) <= band_w;
+#else
                 const bool z = (k >= startbin) && (k <= stopbin);
+#endif
                 const double re = z ? 0.0 : d.r[s], im = z ? 0.0 : d.i[s];
                 d.r[s] = im; d.i[s] = re;
             }
@@ -535,8 +621,13 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         for (int s = 0; s < E; s++)
         {
             const double re = d.i[s], im = d.r[s];
+#if C6_SQFMA
+            d.r[s] = __builtin_fma(re, re, -(im * im));
+            d.i[s] = 2.0 * (re * im); // the bits of re * im + im * re
+#else
             d.r[s] = re * re - im * im;
             d.i[s] = re * im + im * re;
+#endif
         }
         c6_fft<LOG2N>(d, xch, tw, t);
         C6_TRACE(3);
@@ -559,7 +650,11 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             // one wavefront of a SIMD waits at a load while the other computes (12.6 -> 12.4 ms per 65 536 estimates).
             double yv[E];
 #pragma unroll
+#if C6_SQFMA
+            for (int s = 0; s < E; s++) d.r[s] = __builtin_fma(d.r[s], d.r[s], d.i[s] * d.i[s]);
+#else
             for (int s = 0; s < E; s++) d.r[s] = d.r[s] * d.r[s] + d.i[s] * d.i[s];
+#endif
             C6_FENCE; // d.i is dead from here: its registers take the y values
 #pragma unroll
             for (int s = 0; s < E; s++) yv[s] = __builtin_nontemporal_load((y + ((s * NT) ^ (N / 2))) + t); // (s*NT + t) ^ N/2: uniform base + t
@@ -570,10 +665,26 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             // laundered: known since the top of the estimate, the 32 ring addresses would otherwise be computed there and kept (spilled) across
             // the three transforms -- and every reload waits for all vector loads in flight
             int bpn = bp_next, chn = ch_next, tp = t;
+#if C6_RINGADDR
+            asm volatile("" : "+s"(bpn), "+s"(chn), "+v"(tp)); // wave-uniform: the ring's base stays in scalar registers
+#else
             asm volatile("" : "+v"(bpn), "+v"(chn), "+v"(tp));
+#endif
+            // the y copy's rows above 64 KiB: from a base of their own (LOG2N 13: the buffer ends below)
+            int tph = tp + ((C6_HIADDR && LOG2N == 14) ? N / 2 : 0);
+            if constexpr (C6_HIADDR && LOG2N == 14) asm volatile("" : "+v"(tph));
+            constexpr int UPH = (C6_HIADDR && LOG2N == 14) ? N / 2 : 0;
             typedef double c6_v2 __attribute__((ext_vector_type(2)));
+#if !C6_RINGADDR
             const c6_v2 *__restrict__ ringn = (const c6_v2 *)(p.bbring + (size_t)chn * N);
+#endif
+#if C6_RINGADDR
+            // byte offset of this thread's entry of slot 0, once; a slot adds its constant and wraps in bytes
+            const unsigned boffp = ((unsigned)(bpn + tp) & (unsigned)(N - 1)) << 4;
+            const char *__restrict__ ringnb = (const char *)(p.bbring + (size_t)chn * N);
+#else
             const int toffp = bpn + tp;
+#endif
 #pragma unroll
             for (int s = 0; s < E; s++)
             {
@@ -581,13 +692,22 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
                 // 0.1*10*log10(max(|X|,1)) -- C multiplies left to right: (0.1 * 10) * log10 = 1.0 * log10 -- == 0.5*log10(max(|X|^2,1)): no
                 // hypot.  (Until tests/test_gpu_coarse.py compared y itself this line had 5.0, ten times the reference's increment: the same
                 // peak bin as long as every candidate folds six terms, another one when y was 20 and the fold left the spectrum.)
+#if C6_LOGHALF
+                const double yn = yv[s] * 0.9 + c6_log10_half(fmax(d.r[s], 1.0));
+#else
                 const double yn = yv[s] * 0.9 + 0.5 * jd_log10(fmax(d.r[s], 1.0));
+#endif
                 __builtin_nontemporal_store(yn, (y + ib) + t);
-                (xch + ib)[t] = yn;
+                if (UPH && ib >= UPH) (xch + (ib - UPH))[tph] = yn;
+                else (xch + ib)[t] = yn;
                 {
                     // unconditional: without a next estimate ch_next / bp_next still name this one (valid memory, result unused) -- under
                     // `if (has_next)` the old contents of d.r[s] had to stay live beside the new ones (151 spilled registers)
+#if C6_RINGADDR
+                    const c6_v2 v = __builtin_nontemporal_load((const c6_v2 *)(ringnb + ((boffp + (unsigned)(s * NT * 16)) & (unsigned)(N * 16 - 1))));
+#else
                     const c6_v2 v = __builtin_nontemporal_load(ringn + ((toffp + s * NT) & (N - 1)));
+#endif
                     d.r[s] = v.x; d.i[s] = v.y;
                 }
                 if ((s & 3) == 3) C6_FENCE; // four slots at a time: the scheduler may not gather the loads at either end again

@@ -101,6 +101,12 @@ __global__ void __launch_bounds__(TPB) k_jp_log10(const double *x, double *o, lo
     JP_IDX;
     if (i < n) o[i] = jd_log10(x[i]);
 }
+// c6_log10_half beside the product it replaces in the estimate kernels' epilogue (tests/test_gpu_log10_half.py wants the same bits)
+__global__ void __launch_bounds__(TPB) k_jc_log10_half(const double *x, double *o_half, double *o_product, long n)
+{
+    JP_IDX;
+    if (i < n) { o_half[i] = c6_log10_half(x[i]); o_product[i] = 0.5 * jd_log10(x[i]); }
+}
 __global__ void __launch_bounds__(TPB) k_jp_qround(const double *x, int *o, long n)
 {
     JP_IDX;
@@ -300,6 +306,14 @@ JP_1IN_1OUT(jp_qround, int)
 JP_1IN_1OUT(jp_softbit, int)
 JP_1IN_1OUT(jp_cisidx, int)
 JP_1IN_1OUT(jp_fb_fmod360, double)
+int jc_log10_half(const double *x, double *o_half, double *o_product, long n)
+{
+    Bufs b;
+    const double *dx = b.in(x, n);
+    double *dh = b.io(o_half, n), *dp = b.io(o_product, n);
+    if (b.ok() && n > 0) k_jc_log10_half<<<nblocks(n), TPB>>>(dx, dh, dp, n);
+    return b.sync();
+}
 int jp_div(const double *a, const double *bb, double *o, double *o_ieee, long n)
 {
     Bufs b;
