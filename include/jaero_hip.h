@@ -774,6 +774,17 @@ typedef struct jaero_coarse_state
 int jaero_debug_coarse_poke(jaero_ctx *ctx, int channel, const double *ring_reim, const double *y, const jaero_coarse_state *st);
 int jaero_debug_coarse_launch(jaero_ctx *ctx, const int *channels, int nlist, int grid);
 int jaero_debug_coarse_peek(jaero_ctx *ctx, int channel, double *ring_reim, double *y, jaero_coarse_state *st);
+/* Test hooks: the band-aware estimate kernel.  A 2^14-point bank that is not an 8400 bps bank holds, beside its generic kernel (what
+ * jaero_debug_kernel_variant(ctx, 1) and jaero_profile_kernel(ctx, 1) keep naming), k_coarse6_b7 for channels whose locking band ends on the
+ * slot boundaries it is built for (startbin 7 * 512, expectedpeakbin 1792: lockingbw 10500 Hz at 48 kHz); jaero_write and
+ * jaero_debug_coarse_launch split every list of estimates by the channels' class, which follows jaero_set_settings.
+ *   jaero_debug_coarse_band          the band kernel's variant string ("" if the bank has none) and the estimates launched on the generic and
+ *                                    on the band kernel since jaero_create (either pointer may be NULL).
+ *   jaero_debug_coarse_force_generic on != 0: every estimate of this bank takes the generic kernel (what tests compare the band kernel with).
+ *   jaero_debug_coarse_band_class    host only: 1 if a channel with these settings is in the band kernel's class. */
+int jaero_debug_coarse_band(jaero_ctx *ctx, char *buf, int cap, long long *est_generic, long long *est_band);
+int jaero_debug_coarse_force_generic(jaero_ctx *ctx, int on);
+int jaero_debug_coarse_band_class(int fft_power, double Fs, double fb, double lockingbw);
 
 /* Test hooks: a burst bank's transform kernels on their own (k_hist_push_frames / _chmajor, k_hilbert_fft, k_ev_compact and the bank's k_trident
  * instantiation, jaero_debug_kernel_variant(ctx, 1)), launched by the lines jaero_write launches them with.  All synchronise the bank first.

@@ -33,6 +33,7 @@ EXPORTS = [
     "jaero_num_channels", "jaero_strerror", "jaero_last_error", "jaero_profile_enable", "jaero_profile_read", "jaero_profile_kernel", "jaero_debug_viterbi_layout",
     "jaero_debug_sample_loop_layout", "jaero_debug_kernel_variant",
     "jaero_debug_coarse_poke", "jaero_debug_coarse_launch", "jaero_debug_coarse_peek",
+    "jaero_debug_coarse_band", "jaero_debug_coarse_force_generic", "jaero_debug_coarse_band_class",
     "jaero_debug_schedule", "jaero_debug_schedule_lanes", "jaero_debug_prefilter", "jaero_debug_read_prefiltered", "jaero_read_events",
     "jaero_debug_burst_geom", "jaero_debug_burst_hilbert", "jaero_debug_burst_read_hist", "jaero_debug_burst_poke_cv", "jaero_debug_burst_trident",
     "jaero_debug_burst_front_geom", "jaero_debug_burst_front", "jaero_debug_burst_front_peek", "jaero_debug_burst_front_events", "jaero_debug_burst_front_poke", "jaero_debug_burst_poke_bt",
@@ -202,6 +203,9 @@ def lib():
     L.jaero_debug_coarse_poke.argtypes = [vp, ip, vp, vp, C.POINTER(CoarseState)]
     L.jaero_debug_coarse_launch.argtypes = [vp, vp, ip, ip]
     L.jaero_debug_coarse_peek.argtypes = [vp, ip, vp, vp, C.POINTER(CoarseState)]
+    L.jaero_debug_coarse_band.argtypes = [vp, C.c_char_p, ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.jaero_debug_coarse_force_generic.argtypes = [vp, ip]
+    L.jaero_debug_coarse_band_class.argtypes = [ip, dp, dp, dp]
     L.jaero_debug_schedule.argtypes = [ip, ip, ip, vp, ip, vp, ip, C.POINTER(ip)]
     L.jaero_debug_schedule_lanes.argtypes = [ip, ip, ip, vp, vp, ip, vp, ip, vp, ip, C.POINTER(ip)]
     L.jaero_debug_prefilter.argtypes = [ip, vp, ip, dp, dp, vp]

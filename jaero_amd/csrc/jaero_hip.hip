@@ -188,7 +188,7 @@ struct jaero_ctx
     // the sample loop (OQPSK: k_oqpsk_fb; MSK: k_msk_fb, or k_msk_samples for 40 and 20 taps) and the coarse estimate (k_coarse6*)
     KernelRec<OqpskSampleFn> oq_loop;
     KernelRec<MskSampleFn> msk_loop;
-    KernelRec<CoarseFn> coarse;
+    KernelRec<CoarseFn> coarse; CoarseBand<KernelRec<CoarseFn>> band; // band: k_coarse6_b7 beside the generic kernel (k_coarse6.h, update_band_class)
     JTaps28 oq_taps{}; // the 28 distinct values of the (bitwise symmetric) 55-tap RRC, scalar operands of k_oqpsk_fb's filter
     // fb == 8400 (k_pre8400.h): prefilter buffers, samples written so far, size of the previous write
     bool pre8400 = false;
@@ -336,7 +336,7 @@ static void swap_in(jaero_ctx *c, BankPtr n)
     c->timer.collect();
     n->timer.on = c->timer.on;
     n->timer.slots = c->timer.slots;
-    n->m.flags = c->m.flags;
+    n->m.flags = c->m.flags; n->band.force_generic = c->band.force_generic; n->band.est_generic = c->band.est_generic; n->band.est_band = c->band.est_band;
     std::swap(*c, *n);
 }
 
@@ -661,6 +661,18 @@ extern "C" int jaero_debug_sample_loop_layout(int mode)
     return 0;
 }
 
+// after every write of S_LOCKINGBW for channels [lo, hi): create, jaero_set_settings, the carry-over into a new bank
+static void update_band_class(jaero_ctx *c, int lo, int hi)
+{
+    if (c->band.cls.size() != c->settings.size()) c->band.cls.assign(c->settings.size(), 0);
+    for (int ch = lo; ch < hi; ch++)
+        c->band.cls[ch] = c->band.rec.fn && coarse_band_class_of(c->g.nfft_log2, c->g.Fs, c->g.fb, c->settings[ch].lockingbw);
+}
+extern "C" int jaero_debug_coarse_band_class(int fft_power, double Fs, double fb, double lockingbw)
+{
+    return coarse_band_class_of(fft_power, Fs, fb, lockingbw);
+}
+
 // The continuous bank's sample-loop and coarse-estimate kernels, with their LDS attributes
 static int choose_kernels(jaero_ctx *c, int ncu)
 {
@@ -700,6 +712,13 @@ static int choose_kernels(jaero_ctx *c, int ncu)
     else if (c->pre8400) c->coarse = {k_coarse6_w8400, ncu, C2_THREADS, (C6_XCH + C4_TABN) * (int)sizeof(double), 0, "k_coarse6_w8400", "k_coarse6_w8400"};
     else c->coarse = {k_coarse6, ncu, C2_THREADS, C6_XCH * (int)sizeof(double), 0, "k_coarse6", "k_coarse6"};
     HIPCHK(set_lds_attribute(c->coarse));
+    c->band.rec = {};
+    if (c->coarse.fn == (CoarseFn)k_coarse6)
+    {
+        c->band.rec = {k_coarse6_b7, ncu, C2_THREADS, C6_XCH * (int)sizeof(double), 0, "k_coarse6_b7", "k_coarse6_b7"};
+        HIPCHK(set_lds_attribute(c->band.rec));
+    }
+    update_band_class(c, 0, (int)c->settings.size());
     return 0;
 }
 
@@ -974,6 +993,7 @@ static int apply_live_settings(jaero_ctx *c, int lo, int hi, const jaero_setting
         c->settings[ch] = *s;
         c->m.bbptr[ch] = 0; c->m.cnt[ch] = 0;
     }
+    update_band_class(c, lo, hi);
     const int ny = (hi - lo) >= 256 ? 4 : 64; // one channel: 64 blocks share its 192 000-slot AGC column; the whole bank: four per channel
     if (g.kind == JAERO_KIND_MSK)
     {
@@ -1197,7 +1217,41 @@ static void launch_coarse_grid(jaero_ctx *c, const int *d_list, int nlist, int g
     hipLaunchKernelGGL(r.fn, dim3(grid), dim3(r.block), r.lds, st, c->g, c->p, d_list, nlist, c->d_tw);
 }
 static int coarse_grid(const jaero_ctx *c, int nlist) { return nlist < c->coarse.grid ? nlist : c->coarse.grid; }
-static void launch_coarse(jaero_ctx *c, const int *d_list, int nlist, hipStream_t st) { launch_coarse_grid(c, d_list, nlist, coarse_grid(c, nlist), st); }
+// The estimates of h_list[0 .. nlist) (nullptr: channels 0 .. nlist - 1, the whole bank) on at most `grid` workgroups per launch, each on the
+// kernel its channel's band class names: one launch when the list is of one class -- with d_chanlist filled from h_list, or no list at all --
+// and otherwise two, the band part first, the order within each part kept.  async: the list is copied on the stream (jaero_write).
+static int launch_coarse_lists(jaero_ctx *c, const int *h_list, int nlist, int grid, hipStream_t st, bool async)
+{
+    int nband = 0;
+    if (c->band.rec.fn && !c->band.force_generic)
+        for (int k = 0; k < nlist; k++) nband += c->band.cls[h_list ? h_list[k] : k];
+    const int *src = h_list;
+    if (nband != 0 && nband != nlist)
+    {
+        c->band.split.resize((size_t)nlist);
+        int a = 0, b = nband;
+        for (int k = 0; k < nlist; k++)
+        {
+            const int ch = h_list ? h_list[k] : k;
+            c->band.split[(size_t)(c->band.cls[ch] ? a++ : b++)] = ch;
+        }
+        src = c->band.split.data();
+    }
+    if (src)
+    {
+        if (async) HIPCHK(hipMemcpyAsync(c->d_chanlist, src, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice, st));
+        else HIPCHK(hipMemcpy(c->d_chanlist, src, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice));
+    }
+    const int ngen = nlist - nband;
+    if (nband)
+    {
+        const KernelRec<CoarseFn> &r = c->band.rec;
+        hipLaunchKernelGGL(r.fn, dim3(grid < nband ? grid : nband), dim3(r.block), r.lds, st, c->g, c->p, src ? c->d_chanlist : nullptr, nband, c->d_tw);
+    }
+    if (ngen) launch_coarse_grid(c, src ? c->d_chanlist + nband : nullptr, ngen, grid < ngen ? grid : ngen, st);
+    c->band.est_band += nband; c->band.est_generic += ngen;
+    return 0;
+}
 
 // Work enqueued on `st` is ordered behind everything the bank enqueued before (on last_stream), and `st` becomes last_stream: the rule for
 // every entry point that takes a caller stream and touches device state (jaero_write, jaero_discard_softbits) -- a discard on stream X
@@ -1262,14 +1316,8 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
         if (only_a)
         {
             const int nlist = (int)c->m.fired.size();
-            const int *dl = nullptr;
-            if (nlist != nch)
-            {
-                HIPCHK(hipMemcpyAsync(c->d_chanlist, c->m.fired.data(), sizeof(int) * nlist, hipMemcpyHostToDevice, st));
-                dl = c->d_chanlist;
-            }
             const int pi = c->timer.begin(1, st);
-            launch_coarse(c, dl, nlist, st);
+            { const int rc = launch_coarse_lists(c, nlist != nch ? c->m.fired.data() : nullptr, nlist, coarse_grid(c, nlist), st, true); if (rc) return rc; }
             LAUNCHCHK("the coarse-frequency estimate");
             c->timer.end(pi, st);
         }
@@ -1353,10 +1401,26 @@ extern "C" int jaero_debug_coarse_launch(jaero_ctx *c, const int *channels, int 
     }
     const int gmax = coarse_grid(c, nlist);
     if (grid < 0 || grid > gmax) return fail(JAERO_EINVAL, "jaero_debug_coarse_launch: grid %d (0 = as jaero_write, else 1 .. %d for %d channels)", grid, gmax, nlist);
-    if (channels) HIPCHK(hipMemcpy(c->d_chanlist, channels, sizeof(int) * (size_t)nlist, hipMemcpyHostToDevice));
-    launch_coarse_grid(c, channels ? c->d_chanlist : nullptr, nlist, grid ? grid : gmax, c->last_stream);
+    if ((rc = launch_coarse_lists(c, channels, nlist, grid ? grid : gmax, c->last_stream, false))) return rc;
     LAUNCHCHK("the coarse-frequency estimate");
     HIPCHK(hipStreamSynchronize(c->last_stream));
+    return 0;
+}
+extern "C" int jaero_debug_coarse_band(jaero_ctx *c, char *buf, int cap, long long *est_generic, long long *est_band)
+{
+    if (!c || !buf || cap < 2) return fail(JAERO_EINVAL, "jaero_debug_coarse_band: bad arguments");
+    if (c->burst) return fail(JAERO_EINVAL, "jaero_debug_coarse_band: a burst bank has no coarse-frequency estimate");
+    const std::string &v = c->band.rec.variant; // empty: the bank has no band-aware kernel
+    if ((int)v.size() >= cap) return fail(JAERO_EOVERFLOW, "jaero_debug_coarse_band: %zu characters do not fit in %d", v.size(), cap);
+    snprintf(buf, (size_t)cap, "%s", v.c_str());
+    if (est_generic) *est_generic = c->band.est_generic;
+    if (est_band) *est_band = c->band.est_band;
+    return 0;
+}
+extern "C" int jaero_debug_coarse_force_generic(jaero_ctx *c, int on)
+{
+    if (!c || c->burst) return fail(JAERO_EINVAL, "jaero_debug_coarse_force_generic: a continuous bank's handle");
+    c->band.force_generic = on != 0;
     return 0;
 }
 

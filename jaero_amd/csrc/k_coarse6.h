@@ -19,6 +19,7 @@
 // the channeliser run the form that moves them to the inputs of the next pass and absorbs them into its butterflies (C6_ABSORB 2 below,
 // DESIGN 9 item 32): no twiddle products and no power chains, 842 of 8 021 vector instructions per estimate less.
 #pragma once
+#include <vector>
 #include "k_coarse2.h"
 
 #ifndef C4_TABN
@@ -208,6 +209,69 @@ __device__ __forceinline__ void c6_cfft32(CV<32> &x)
     }
 }
 
+// c6_cfft32 for an input whose slots SB .. 31 - SB are +0.0 at compile time (the boxcar band limit of a locking band that ends on slot
+// boundaries).  Which slots hold a zero is followed through the network (`zero`, a constant once the loops are unrolled):
+//   both inputs zero: nothing to do;      b zero: u = a + r 0 = a, v = 2 a - u = a: a renaming;
+//   a zero: u = r b -- the product and the fused multiply-add the generic butterfly forms with a = 0 -- and v = 2 0 - u = -u.
+// The same bits as c6_cfft32 on that input but for the sign of an exact zero (0 + r 0 is +0 where a renamed -0 stays -0), which reaches no
+// |X|^2.  For SB = 7 the first level is renamings alone and the second has four of its 16 butterflies left as such; slot 32 - SB, zero as
+// data in thread 0 only, is an ordinary input.  tests/test_coarse_band_model.py.
+template <int SB>
+__device__ __forceinline__ void c6_cfft32_band(CV<32> &x)
+{
+    unsigned zero = 0;
+#pragma unroll
+    for (int s = SB; s <= 31 - SB; s++) zero |= 1u << s;
+#pragma unroll
+    for (int lv = 0; lv < 5; lv++)
+    {
+#pragma unroll
+        for (int b = 0; b < (1 << lv); b++)
+        {
+            const int half = 16 >> lv, idx = half * 2 * c6_brev(b, lv), e = idx & 15;
+            const double cr = jd_w64r(e), ci = jd_w64i(e);
+            const double wr = (idx & 16) ? ci : cr, wi = (idx & 16) ? -cr : ci;
+#pragma unroll
+            for (int j = 0; j < half; j++)
+            {
+                const int ia = 2 * half * b + j, ib = ia + half;
+                const bool za = (zero >> ia) & 1u, zb = (zero >> ib) & 1u;
+                const double ar = x.r[ia], ai = x.i[ia], br = x.r[ib], bi = x.i[ib];
+                if (za && zb) continue;
+                if (zb)
+                {
+                    x.r[ib] = ar; x.i[ib] = ai;
+                    zero &= ~(1u << ib);
+                }
+                else if (za)
+                {
+                    double ur, ui;
+                    if (idx == 0) { ur = br; ui = bi; }
+                    else if (idx == 16) { ur = bi; ui = -br; }
+                    else
+                    {
+                        ur = __builtin_fma(-wi, bi, wr * br);
+                        ui = __builtin_fma(wr, bi, wi * br);
+                    }
+                    x.r[ia] = ur; x.i[ia] = ui;
+                    x.r[ib] = -ur; x.i[ib] = -ui;
+                    zero &= ~(1u << ia);
+                }
+                else if (idx == 0) { x.r[ia] = ar + br; x.i[ia] = ai + bi; x.r[ib] = ar - br; x.i[ib] = ai - bi; }
+                else if (idx == 16) { x.r[ia] = ar + bi; x.i[ia] = ai - br; x.r[ib] = ar - bi; x.i[ib] = ai + br; }
+                else
+                {
+                    const double ur = __builtin_fma(-wi, bi, __builtin_fma(wr, br, ar));
+                    const double ui = __builtin_fma(wr, bi, __builtin_fma(wi, br, ai));
+                    x.r[ia] = ur; x.i[ia] = ui;
+                    x.r[ib] = __builtin_fma(2.0, ar, -ur); x.i[ib] = __builtin_fma(2.0, ai, -ui);
+                }
+            }
+        }
+        C6_FENCE;
+    }
+}
+
 // In-place forward L-point DFT (L = 32, 16) of x[OFF .. OFF + L) times (r W_64^Z)^j, r^(2^i) in P; X[k] is left in slot OFF + c6_brev(k).
 template <int L, int OFF, int Z>
 __device__ __forceinline__ void c6_afft(CV<32> &x, const double2 (&P)[5])
@@ -304,7 +368,8 @@ __device__ __forceinline__ void c6_pass3(CV<32> &d, const double2 r)
 // tests/test_coarse_fft14_absorbed_model.py.
 // HI: the upper half of exchange 2 (byte offsets from 65 664, beyond the 16-bit offset field of a DS instruction) is addressed from bases
 // of its own, formed once per transform, instead of one literal add per access.
-template <int AB = C6_ABSORB, bool P1 = (AB > 0) && C6_P1FUSED, bool HI = false>
+// ZB > 0: the input's slots ZB .. 31 - ZB are +0.0 at compile time (pass 1 = c6_cfft32_band).
+template <int AB = C6_ABSORB, bool P1 = (AB > 0) && C6_P1FUSED, bool HI = false, int ZB = 0>
 __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const double2 *__restrict__ tw, int t)
 {
 #pragma clang fp contract(fast)
@@ -327,7 +392,9 @@ __device__ __forceinline__ void wg_fft14_e32(CV<32> &d, double *xch, const doubl
 
     // ---- pass 1 ----
     static_assert(!(P1 && AB == 0), "the output twiddle of AB 0 expects split order");
-    if constexpr (P1) c6_cfft32(d);
+    static_assert(ZB == 0 || P1, "the band-aware pass 1 is a form of c6_cfft32");
+    if constexpr (ZB > 0) c6_cfft32_band<ZB>(d);
+    else if constexpr (P1) c6_cfft32(d);
     else c6_fft32(d);
     if constexpr (AB == 0) c6_twiddle32(d, st1);
     C6_FENCE;
@@ -472,12 +539,13 @@ __device__ __forceinline__ void wg_fft13_e32(CV<32> &d, double *xch, const doubl
     c6_pass3<AB == 2>(d, st2);
 }
 
-template <int LOG2N>
+template <int LOG2N, int ZB = 0>
 __device__ __forceinline__ void c6_fft(CV<32> &d, double *xch, const double2 *__restrict__ tw, int t)
 {
+    static_assert(ZB == 0 || LOG2N == 14, "the band-aware pass 1 exists for the 2^14-point transform");
     int tt = t; // laundered per call: nothing derived from it inside is shared between the three calls of an estimate and kept live
     asm volatile("" : "+v"(tt));
-    if constexpr (LOG2N == 14) wg_fft14_e32<C6_ABSORB, (C6_ABSORB > 0) && C6_P1FUSED, C6_HIADDR != 0>(d, xch, tw, tt);
+    if constexpr (LOG2N == 14) wg_fft14_e32<C6_ABSORB, (C6_ABSORB > 0) && C6_P1FUSED, C6_HIADDR != 0, ZB>(d, xch, tw, tt);
     else wg_fft13_e32<C6_ABSORB, (C6_ABSORB > 0) && C6_P1FUSED>(d, xch, tw, tt);
 }
 
@@ -493,7 +561,25 @@ __device__ __noinline__ void c6_build_window(double *wt, int startbin, int t, in
     }
 }
 
-template <bool W8400, int LOG2N = 14>
+#ifndef C6_YADDR
+#define C6_YADDR 0 // band-aware instantiation only: y[] addressed by a 32-bit byte offset from a scalar row base per slot.  Built and not
+                   // kept: the 32 row bases cost 46 more spilled scalar registers than the 64-bit adds they replace (profiles/coarse_band.md)
+#endif
+#ifndef C6_LOGSKIP
+#define C6_LOGSKIP 1 // band-aware instantiation only: no logarithm for slots outside the squared signal's spectrum unless a lane exceeds 1
+#endif
+
+// SB > 0: the band-aware instantiation for channels whose locking band ends on slot boundaries: startbin = SB * NT,
+// expectedpeakbin = EPB, i0 = N / 2 - startbin and i1 = N / 2 + startbin of the fold -- the host launches it for no other channel
+// (band_class in jaero_hip.hip, computed with the expressions below), and then
+//   * the band limit zeroes slots SB .. 31 - SB at compile time and tests thread 0 of slot 32 - SB, nothing else; with the zeros known,
+//     the butterflies of the first transform's pass 3 whose outputs land in those slots are never formed, and pass 1 of the second
+//     transform is c6_cfft32_band;
+//   * the squared signal's spectrum is empty for |k| >= 2 startbin: slots that lie wholly there take the logarithm only if a lane of the
+//     wavefront has |X|^2 > 1 (round-off of a very strong input), otherwise log10(fmax(., 1)) / 2 is the +0.0 that c6_log10_half(1) returns;
+//   * only the y rows the fold reads are copied to LDS, and the fold's range is constant.
+// SB = 0: the generic code, as before.
+template <bool W8400, int LOG2N = 14, int SB = 0, int EPB = 0>
 __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const int *__restrict__ chan_list, int nlist, const double2 *__restrict__ tw)
 {
     constexpr int N = 1 << LOG2N;
@@ -504,6 +590,7 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
     __shared__ double red_val[NT / 64]; // one entry per wavefront
     __shared__ int red_idx[NT / 64];
     const int t0 = threadIdx.x;
+    static_assert(SB == 0 || (!W8400 && LOG2N == 14 && SB >= 1 && SB <= 15 && EPB >= 1), "the band-aware instantiation is the 2^14-point boxcar's");
     const int nchp = g.nchp;
     int tab_startbin = -1; // W8400: the startbin the window table behind the exchange buffer was made for
 
@@ -532,6 +619,8 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         // doubles are formed again where the epilogue needs them -- left in vector registers they stay live across the three transforms
         // (k_coarse6_w8400 spilled 17 of them until round 4, and a reload's wait stands behind every load in flight)
         int startbin, expectedpeakbin;
+        if constexpr (SB > 0) { startbin = SB * NT; expectedpeakbin = EPB; }
+        else
         {
             const double hzperbin = fs_l * (1.0 / ((double)N)); // N a power of two: the same bits as the reference's quotient
             startbin = __builtin_amdgcn_readfirstlane((int)fmax(round(lockingbw / hzperbin), 1.0));
@@ -562,7 +651,22 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         c6_fft<LOG2N>(d, xch, tw, t);
         C6_TRACE(1);
         // band limit (fb != 8400 boxcar, coarsefreqestimate.cpp:99) then inverse transform = forward on swapped planes
-        if constexpr (W8400)
+        if constexpr (SB > 0)
+        {
+#pragma unroll
+            for (int s = 0; s < E; s++)
+            {
+                if (s >= SB && s <= E - 1 - SB) { d.r[s] = 0.0; d.i[s] = 0.0; } // bins startbin .. stopbin - 1
+                else if (s == E - SB)                                            // bin stopbin
+                {
+                    const bool z = t == 0;
+                    const double re = z ? 0.0 : d.r[s], im = z ? 0.0 : d.i[s];
+                    d.r[s] = im; d.i[s] = re;
+                }
+                else { const double re = d.r[s]; d.r[s] = d.i[s]; d.i[s] = re; }
+            }
+        }
+        else if constexpr (W8400)
         {
             // window[0] = 1, window[i] = window[N - i] = cos^2(pi/2 * i / startbin) for 1 <= i <= startbin, 0 elsewhere (:61-74).  Its
             // startbin + 1 distinct values come from a table in LDS behind the exchange buffer (entry startbin + 1 = 0 stands for every bin
@@ -614,7 +718,7 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
                 d.r[s] = im; d.i[s] = re;
             }
         }
-        c6_fft<LOG2N>(d, xch, tw, t);
+        c6_fft<LOG2N, SB>(d, xch, tw, t);
         C6_TRACE(2);
         // swap back (x N / N = 1), square
 #pragma unroll
@@ -649,6 +753,21 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             // wavefront of the workgroup at the same place for 7 us (a CU issues ~45 GB/s of loads that miss L2); spread over the logarithms,
             // one wavefront of a SIMD waits at a load while the other computes (12.6 -> 12.4 ms per 65 536 estimates).
             double yv[E];
+            // y[] of the band-aware instantiation: the slot's row from the channel's scalar base, this thread's entry by a 32-bit byte offset
+            [[maybe_unused]] unsigned yoff = 0;
+            if constexpr (SB > 0 && C6_YADDR) { yoff = (unsigned)t << 3; asm volatile("" : "+v"(yoff)); }
+            typedef __attribute__((address_space(1))) char c6_gchar;
+            typedef __attribute__((address_space(1))) double c6_gdouble;
+            [[maybe_unused]] auto yat = [&](int ib) __attribute__((always_inline)) {
+                if constexpr (SB > 0 && C6_YADDR)
+                {
+                    // the row's base opaque (and still a global pointer), or the rows are formed from one another as 64-bit vector addresses
+                    c6_gchar *row = (c6_gchar *)(y + ib);
+                    asm volatile("" : "+s"(row));
+                    return (c6_gdouble *)(row + yoff);
+                }
+                else return (c6_gdouble *)((y + ib) + t);
+            };
 #pragma unroll
 #if C6_SQFMA
             for (int s = 0; s < E; s++) d.r[s] = __builtin_fma(d.r[s], d.r[s], d.i[s] * d.i[s]);
@@ -656,8 +775,16 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             for (int s = 0; s < E; s++) d.r[s] = d.r[s] * d.r[s] + d.i[s] * d.i[s];
 #endif
             C6_FENCE; // d.i is dead from here: its registers take the y values
+            if constexpr (SB > 0)
+            {
+#pragma unroll
+                for (int s = 0; s < E; s++) yv[s] = __builtin_nontemporal_load(yat((s * NT) ^ (N / 2)));
+            }
+            else
+            {
 #pragma unroll
             for (int s = 0; s < E; s++) yv[s] = __builtin_nontemporal_load((y + ((s * NT) ^ (N / 2))) + t); // (s*NT + t) ^ N/2: uniform base + t
+            }
             C6_FENCE; // or the scheduler sinks every load to its use again
             // the channel's acquisition state, needed behind the peak search: in front of everything else that is requested below (vmcnt
             // retires in order), as ordinary loads
@@ -675,6 +802,20 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
             if constexpr (C6_HIADDR && LOG2N == 14) asm volatile("" : "+v"(tph));
             constexpr int UPH = (C6_HIADDR && LOG2N == 14) ? N / 2 : 0;
             typedef double c6_v2 __attribute__((ext_vector_type(2)));
+            // band-aware instantiation: the slots that take no logarithm, the y rows the fold reads (y[i0 - EPB - 1 .. i1 + EPB]: only they
+            // are copied to LDS), and what the slots without a logarithm leave for the pass behind the loop
+            [[maybe_unused]] auto skips = [](int s) __attribute__((always_inline)) {
+                return SB > 0 && C6_LOGSKIP && C6_LOGHALF && ((s < E / 2) ? (s >= 2 * SB) : (E - 1 - s >= 2 * SB));
+            };
+            [[maybe_unused]] auto copied = [](int ib) __attribute__((always_inline)) {
+                return ib / NT >= (N / 2 - SB * NT - EPB - 1) / NT && ib / NT <= (N / 2 + SB * NT + EPB) / NT;
+            };
+            [[maybe_unused]] auto ycopy = [&](int ib, double yn) __attribute__((always_inline)) {
+                if (UPH && ib >= UPH) (xch + (ib - UPH))[tph] = yn;
+                else (xch + ib)[t] = yn;
+            };
+            [[maybe_unused]] double kx[E], ky[E];
+            [[maybe_unused]] bool hot = false;
 #if !C6_RINGADDR
             const c6_v2 *__restrict__ ringn = (const c6_v2 *)(p.bbring + (size_t)chn * N);
 #endif
@@ -692,6 +833,24 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
                 // 0.1*10*log10(max(|X|,1)) -- C multiplies left to right: (0.1 * 10) * log10 = 1.0 * log10 -- == 0.5*log10(max(|X|^2,1)): no
                 // hypot.  (Until tests/test_gpu_coarse.py compared y itself this line had 5.0, ten times the reference's increment: the same
                 // peak bin as long as every candidate folds six terms, another one when y was 20 and the fold left the spectrum.)
+                if constexpr (SB > 0)
+                {
+                    // a slot wholly outside the squared signal's spectrum (s NT .. s NT + NT - 1 all at |k| >= 2 startbin): its |X|^2 is
+                    // round-off, the logarithm's argument 1.0 and its value the +0.0 added here -- unless a lane is above 1 (an input
+                    // strong enough for round-off of that size): remembered, and those slots are done again behind the loop
+                    double yn;
+                    if (skips(s))
+                    {
+                        yn = yv[s] * 0.9 + 0.0;
+                        kx[s] = d.r[s]; ky[s] = yv[s];
+                        hot = hot | (d.r[s] > 1.0);
+                    }
+                    else yn = yv[s] * 0.9 + c6_log10_half(fmax(d.r[s], 1.0));
+                    __builtin_nontemporal_store(yn, yat(ib));
+                    if (copied(ib)) ycopy(ib, yn);
+                }
+                else
+                {
 #if C6_LOGHALF
                 const double yn = yv[s] * 0.9 + c6_log10_half(fmax(d.r[s], 1.0));
 #else
@@ -700,6 +859,7 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
                 __builtin_nontemporal_store(yn, (y + ib) + t);
                 if (UPH && ib >= UPH) (xch + (ib - UPH))[tph] = yn;
                 else (xch + ib)[t] = yn;
+                }
                 {
                     // unconditional: without a next estimate ch_next / bp_next still name this one (valid memory, result unused) -- under
                     // `if (has_next)` the old contents of d.r[s] had to stay live beside the new ones (151 spilled registers)
@@ -712,6 +872,23 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
                 }
                 if ((s & 3) == 3) C6_FENCE; // four slots at a time: the scheduler may not gather the loads at either end again
             }
+            if constexpr (SB > 0)
+            {
+                // rare: a lane of this wavefront had |X|^2 > 1 in a slot that took no logarithm.  Those slots again with it; the second store
+                // of a thread to the same address lands behind its first
+                if (__builtin_amdgcn_ballot_w64(hot) != 0)
+                {
+#pragma unroll
+                    for (int s = 0; s < E; s++)
+                    {
+                        if (!skips(s)) continue;
+                        const int ib = (s * NT) ^ (N / 2);
+                        const double yn = ky[s] * 0.9 + c6_log10_half(fmax(kx[s], 1.0));
+                        __builtin_nontemporal_store(yn, yat(ib));
+                        if (copied(ib)) ycopy(ib, yn);
+                    }
+                }
+            }
             C6_TRACE(4);
             jd_lds_barrier(); // the fold reads the LDS copy; the stores to y[] drain in the background
             C6_TRACE(5);
@@ -721,8 +898,14 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         double fs_e = g.Fs; // opaque again: the value above must not be kept for this
         asm volatile("" : "+s"(fs_e));
         const double hzperbin = fs_e * (1.0 / ((double)N));
-        const int i0 = __builtin_amdgcn_readfirstlane((int)round((-lockingbw / hzperbin) + ((double)(N / 2))));
-        const int i1 = __builtin_amdgcn_readfirstlane((int)round((lockingbw / hzperbin) + ((double)(N / 2))));
+        int i0, i1;
+        if constexpr (SB > 0) { i0 = N / 2 - SB * NT; i1 = N / 2 + SB * NT; }
+        else
+        {
+            i0 = __builtin_amdgcn_readfirstlane((int)round((-lockingbw / hzperbin) + ((double)(N / 2))));
+            i1 = __builtin_amdgcn_readfirstlane((int)round((lockingbw / hzperbin) + ((double)(N / 2))));
+        }
+        static_assert(SB == 0 || ((N / 2 - SB * NT - EPB - 1 >= 0) && (N / 2 + SB * NT + EPB < N)), "the band-aware fold stays inside the spectrum");
         double best = 0;
         int besti = -1;
         // every index the fold touches lies inside the spectrum (always, unless lockingbw + fb/2 reaches Fs/2): no per-term range checks
@@ -730,7 +913,8 @@ __device__ __forceinline__ void coarse6_body(const JGeom g, const JPtrs p, const
         if (fold_inside)
         {
             // four candidate bins at a time, straight-line: their 24 LDS reads are requested together
-            const int nblk = (i1 - i0 + 4 * NT - 1) / (4 * NT);
+            int nblk = (i1 - i0 + 4 * NT - 1) / (4 * NT);
+            if constexpr (SB > 0) asm volatile("" : "+s"(nblk)); // a constant: opaque, so that the loop stays one
             for (int b = 0; b < nblk; b++)
             {
                 double val[4];
@@ -812,6 +996,14 @@ __global__ __launch_bounds__(C2_THREADS) void k_coarse6(const JGeom g, const JPt
 {
     coarse6_body<false>(g, p, chan_list, nlist, tw);
 }
+// the band-aware instantiation for lockingbw 10.5 kHz at 48 kHz (the defaults of 10.5 kbps): startbin = 7 * 512, expectedpeakbin = 1792
+#define C6_B7_SB 7
+#define C6_B7_EPB 1792
+__global__ __launch_bounds__(C2_THREADS) void k_coarse6_b7(const JGeom g, const JPtrs p, const int *__restrict__ chan_list,
+                                                              int nlist, const double2 *__restrict__ tw)
+{
+    coarse6_body<false, 14, C6_B7_SB, C6_B7_EPB>(g, p, chan_list, nlist, tw);
+}
 __global__ __launch_bounds__(C2_THREADS) void k_coarse6_w8400(const JGeom g, const JPtrs p, const int *__restrict__ chan_list,
                                                                  int nlist, const double2 *__restrict__ tw)
 {
@@ -822,4 +1014,31 @@ __global__ __launch_bounds__(256, 2) void k_coarse6_13(const JGeom g, const JPtr
                                                         int nlist, const double2 *__restrict__ tw)
 {
     coarse6_body<false, 13>(g, p, chan_list, nlist, tw);
+}
+
+// ---- host side of the band-aware kernel.  A 2^14-point bank that is not an 8400 bps bank holds k_coarse6_b7 beside its generic kernel
+// (rec.fn = nullptr: the bank has none).  A channel's estimates run it while cls[ch] is 1; lockingbw is live-settable per channel, so every
+// writer of S_LOCKINGBW refreshes the byte (update_band_class in jaero_hip.hip: create, jaero_set_settings, the carry-over into a new bank).
+// The kernel trusts the class: the host is the only gate.
+template <class Rec>
+struct CoarseBand
+{
+    Rec rec;
+    std::vector<unsigned char> cls;          // per channel: 1 = in the band kernel's class
+    std::vector<int> split;                  // a mixed list of estimates, the band part in front
+    bool force_generic = false;              // test switch (jaero_debug_coarse_force_generic): every estimate takes the generic kernel
+    long long est_generic = 0, est_band = 0; // estimates launched on either kernel since create (jaero_debug_coarse_band)
+};
+// 1: a channel with this locking bandwidth belongs to k_coarse6_b7 -- the expressions coarse6_body forms from the same doubles (startbin,
+// expectedpeakbin, and the fold's i0 and i1, which round another sum than startbin does) give the kernel's constants
+static inline int coarse_band_class_of(int nfft_log2, double Fs, double fb, double lockingbw)
+{
+    if (nfft_log2 != 14 || fb == 8400) return 0;
+    const int N = 1 << 14;
+    const double hzperbin = Fs * (1.0 / ((double)N));
+    const int startbin = (int)fmax(round(lockingbw / hzperbin), 1.0);
+    const int expectedpeakbin = (int)round(fb / (2.0 * hzperbin));
+    const int i0 = (int)round((-lockingbw / hzperbin) + ((double)(N / 2)));
+    const int i1 = (int)round((lockingbw / hzperbin) + ((double)(N / 2)));
+    return startbin == C6_B7_SB * (N / 32) && expectedpeakbin == C6_B7_EPB && i0 == N / 2 - startbin && i1 == N / 2 + startbin;
 }
