@@ -743,6 +743,35 @@ int jaero_debug_pre8400_read_ring(jaero_ctx *ctx, int channel, long long first_a
 /* Test hook: the Viterbi decoder picks its layout by size (one block per wavefront below 16 384 blocks, one per lane from there); tests
  * force one so that both meet the oracle at small sizes.  mode: 0 = by size (default), 1 = wave, 2 = lanes.  Process-wide. */
 int jaero_debug_viterbi_layout(int mode);
+/* Test hook: ONE launch of the Viterbi decoder through the library's own launch function, every parameter of that launch in the caller's
+ * hands (the public entry points fix most of them).  All buffers are host memory; the call stages them, launches, synchronises and copies back.
+ *   soft           row-major [nblocks][pitch] (pitch 0: nsoft), or tiled != 0: [wavefronts = ceil(nblocks / 64)][nsoft / 16][64][16] (whole wavefronts)
+ *   soft_misalign  0 .. 15 bytes added to the 16-byte aligned device address of soft (row-major only)
+ *   overlap        NULL, or [nblocks][64] as jaero_viterbi_continuous keeps it (byte 62 = the length, at most 62); with update_overlap != 0 the
+ *                  overlap update kernel runs behind the decoder with the same valid / tiled / pitch and the buffer is copied back
+ *   out            [out_rows][out_stride] bytes (out_rows 0: nblocks), copied to the device BEFORE the launch and NOT cleared, copied back whole:
+ *                  a byte the decoder did not write comes back as the caller left it.  Decoded bit k of the stream overlap[:len] ++ soft ++ pad x 128
+ *                  (k < (stream length) / 2 - 6) goes to position k - out_start when 0 <= k - out_start < min(out_want, row length / 2): one byte
+ *                  per bit, or packed != 0: bit (k - out_start) & 31 of the 32-bit word (k - out_start) >> 5 of the row, where a word that receives a
+ *                  bit is written whole (its other bits 0) and a word that receives none is not written
+ *   valid          NULL, or [nblocks]: rows with 0 are skipped (output and overlap untouched)
+ *   lens           NULL, or [nblocks]: each row's own length (even, 28 .. nsoft; row-major only)
+ *   layout         0 = as the library chooses by size, 1 = one block per wavefront (k_viterbi), 2 = one block per lane, k_viterbi_lanes,
+ *                  3 = one block per lane, k_viterbi_lanes_x2 (which the library itself takes above four wavefronts per compute unit)
+ * JAERO_EINVAL before any HIP call for what the kernels do not implement: tiled or packed in the wavefront layout, tiled with nsoft % 16 != 0 (or
+ * with lens, pitch, soft_misalign), a lane-layout row of fewer than 28 steps ((length + pad) / 2), lens[b] odd or above nsoft, out_stride below
+ * the window (packed: whole words, a multiple of 4), an overlap length above 62. */
+typedef struct jaero_viterbi_probe
+{
+    const uint8_t *soft;
+    int nblocks, nsoft, pitch, tiled, soft_misalign, pad;
+    uint8_t *overlap;
+    uint8_t *out;
+    int out_rows, out_stride, out_start, out_want, packed, layout, update_overlap;
+    const int *valid;
+    const int *lens;
+} jaero_viterbi_probe;
+int jaero_debug_viterbi(int device, const jaero_viterbi_probe *q);
 /* Test hook: a continuous bank picks its sample-loop layout at jaero_create by size (one front / back pair per workgroup up to two channel
  * groups per CU, four pairs above); tests force one so that both meet the oracle at small sizes.  mode: 0 = by size (default), 1 = one
  * pair, 2 = four pairs.  Affects only the kernels chosen by size (k_oqpsk_fb at both rates, k_msk_fb at 80 taps), and only banks created

@@ -30,7 +30,7 @@ EXPORTS = [
     "jaero_center_freq_changed", "jaero_write", "jaero_read_softbits", "jaero_read_softbits_all",
     "jaero_softbits_view", "jaero_discard_softbits", "jaero_read_status", "jaero_read_status_log",
     "jaero_read_symbols", "jaero_viterbi_decode_soft", "jaero_viterbi_continuous", "jaero_abi_version",
-    "jaero_num_channels", "jaero_strerror", "jaero_last_error", "jaero_profile_enable", "jaero_profile_read", "jaero_profile_kernel", "jaero_debug_viterbi_layout",
+    "jaero_num_channels", "jaero_strerror", "jaero_last_error", "jaero_profile_enable", "jaero_profile_read", "jaero_profile_kernel", "jaero_debug_viterbi_layout", "jaero_debug_viterbi",
     "jaero_debug_sample_loop_layout", "jaero_debug_kernel_variant",
     "jaero_debug_coarse_poke", "jaero_debug_coarse_launch", "jaero_debug_coarse_peek",
     "jaero_debug_coarse_band", "jaero_debug_coarse_force_generic", "jaero_debug_coarse_band_class",
@@ -126,6 +126,15 @@ class BurstFrontState(C.Structure):
         (n, C.c_int) for n in ("cntdown", "maxposcd", "tri_ptr", "ev_pos", "ev_cnt", "bt_hold")]
 
 
+class ViterbiProbe(C.Structure):
+    """struct jaero_viterbi_probe: one launch of the Viterbi decoder as jaero_debug_viterbi takes it."""
+
+    _fields_ = [("soft", C.c_void_p)] + [(n, C.c_int) for n in ("nblocks", "nsoft", "pitch", "tiled", "soft_misalign", "pad")] + [
+        ("overlap", C.c_void_p), ("out", C.c_void_p)] + [
+        (n, C.c_int) for n in ("out_rows", "out_stride", "out_start", "out_want", "packed", "layout", "update_overlap")] + [
+        ("valid", C.c_void_p), ("lens", C.c_void_p)]
+
+
 FRONT_RINGS = {"agc_ring": 0, "cvre": 1, "cvim": 2, "ma1re": 3, "ma1im": 4, "mav1": 5, "fa": 6, "bt": 7}  # JAERO_FRONT_RING_*
 FRONT_CNTDOWN, FRONT_MAXPOSCD, FRONT_TRI_PTR, FRONT_BT_HOLD, FRONT_LASTDY = 0, 1, 2, 3, 4
 
@@ -198,6 +207,7 @@ def lib():
     L.jaero_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_profile_kernel.argtypes = [vp, ip, C.c_char_p, ip]
     L.jaero_debug_viterbi_layout.argtypes = [ip]
+    L.jaero_debug_viterbi.argtypes = [ip, C.POINTER(ViterbiProbe)]
     L.jaero_debug_sample_loop_layout.argtypes = [ip]
     L.jaero_debug_kernel_variant.argtypes = [vp, ip, C.c_char_p, ip]
     L.jaero_debug_coarse_poke.argtypes = [vp, ip, vp, vp, C.POINTER(CoarseState)]

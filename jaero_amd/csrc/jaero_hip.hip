@@ -1791,15 +1791,17 @@ static inline bool viterbi_use_lanes(int nblocks, int nsoft, int pad)
     return nblocks >= VL_MIN_BLOCKS;
 }
 static void viterbi_launch(hipStream_t st, const uint8_t *d_soft, int nsoft, const uint8_t *d_ov, int pad, uint8_t *d_out, int out_stride,
-                           int out_start, int out_want, int nblocks, const int *valid, unsigned long long *hist, int tiled = 0, int packed = 0, int force_lanes = 0, int pitch = 0, const int *lens = nullptr)
+                           int out_start, int out_want, int nblocks, const int *valid, unsigned long long *hist, int tiled = 0, int packed = 0, int force_lanes = 0, int pitch = 0, const int *lens = nullptr,
+                           int entry = 0) // entry (jaero_debug_viterbi only): 0 = the lane layout's entry point by size, 1 = k_viterbi_lanes, 2 = k_viterbi_lanes_x2
 {
     if (pitch <= 0) pitch = nsoft; // distance between the rows of d_soft (row-major input only)
+    if (out_want > nsoft / 2) out_want = nsoft / 2; // a block of nsoft soft bytes yields at most nsoft / 2 bits (Decode_soft, Decode_Continuous' mid(pad + 1, n / 2))
     if (hist && (tiled || force_lanes || viterbi_use_lanes(nblocks, nsoft, pad))) // tiled input / packed output exist only in the lane layout
     {
         const int waves = (nblocks + 63) / 64;
         int ncu = 256;
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
-        if (waves <= ncu * 4) // one wavefront per SIMD is enough: use the entry point that cannot be stacked two to a SIMD
+        if (entry ? entry == 1 : waves <= ncu * 4) // one wavefront per SIMD is enough: use the entry point that cannot be stacked two to a SIMD
             hipLaunchKernelGGL(k_viterbi_lanes, dim3(waves), dim3(64), 0, st, d_soft, nsoft, d_ov, pad, d_out, out_stride, out_start, out_want, nblocks,
                                valid, hist, tiled, packed, pitch, lens);
         else
@@ -1917,6 +1919,83 @@ extern "C" int jaero_viterbi_continuous(int device, const uint8_t *soft, int nst
             ov[62] = 62;
         }
     }
+    return 0;
+}
+
+// Test hook: ONE viterbi_launch (and, on request, one k_viterbi_overlap_update) with every parameter of the launch in the caller's hands.
+// The output buffer goes to the device as the caller filled it and comes back whole: what the kernels did not write still holds the caller's bytes.
+extern "C" int jaero_debug_viterbi(int device, const jaero_viterbi_probe *q)
+{
+#define VPFAIL(...) return fail(JAERO_EINVAL, "jaero_debug_viterbi: " __VA_ARGS__)
+    if (!q || !q->soft || !q->out) VPFAIL("null probe, soft or out");
+    if (q->nblocks < 1 || q->nblocks > (1 << 20) || q->nsoft < 4 * VT_ORDER || q->nsoft > (1 << 20)) VPFAIL("nblocks %d (1 .. 2^20), nsoft %d (%d .. 2^20)", q->nblocks, q->nsoft, 4 * VT_ORDER);
+    if (q->layout < 0 || q->layout > 3) VPFAIL("layout %d: 0 = by size, 1 = wave, 2 = lanes (1, 1), 3 = lanes x2", q->layout);
+    if (q->pad < 0 || (q->pad & 1) || q->pad > 4096) VPFAIL("pad %d (even, 0 .. 4096)", q->pad);
+    if (q->out_start < 0 || q->out_want < 1) VPFAIL("out_start %d (>= 0), out_want %d (>= 1)", q->out_start, q->out_want);
+    if (q->soft_misalign < 0 || q->soft_misalign > 15) VPFAIL("soft_misalign %d (0 .. 15)", q->soft_misalign);
+    const int tiled = q->tiled != 0, packed = q->packed != 0;
+    const int pitch = q->pitch > 0 ? q->pitch : q->nsoft;
+    if (pitch < q->nsoft) VPFAIL("pitch %d below nsoft %d", pitch, q->nsoft);
+    const int out_rows = q->out_rows > 0 ? q->out_rows : q->nblocks;
+    if (out_rows < q->nblocks) VPFAIL("out_rows %d below nblocks %d", out_rows, q->nblocks);
+    if (q->update_overlap && !q->overlap) VPFAIL("update_overlap without an overlap buffer");
+    int minlen = q->nsoft;
+    if (q->lens)
+        for (int b = 0; b < q->nblocks; b++)
+        {
+            const int l = q->lens[b];
+            if (l < 4 * VT_ORDER || l > q->nsoft || (l & 1)) VPFAIL("lens[%d] = %d (even, %d .. nsoft %d)", b, l, 4 * VT_ORDER, q->nsoft);
+            if (l < minlen) minlen = l;
+        }
+    if (q->overlap)
+        for (int b = 0; b < q->nblocks; b++)
+            if (q->overlap[(size_t)b * 64 + 62] > 62) VPFAIL("overlap[%d][62] = %d: an overlap is at most 62 bytes", b, (int)q->overlap[(size_t)b * 64 + 62]);
+    // the layout the launch will take
+    const bool lanes = q->layout >= 2 || (q->layout == 0 && (tiled || viterbi_use_lanes(q->nblocks, q->nsoft, q->pad)));
+    if (!lanes && (tiled || packed)) VPFAIL("tiled input and packed output exist only in the lane layout");
+    if (tiled && (q->nsoft % 16 != 0 || q->lens || q->pitch > 0 || q->soft_misalign)) VPFAIL("tiled input: nsoft %d a multiple of 16, no lens, pitch or misalignment", q->nsoft);
+    if (lanes && (minlen + q->pad) / 2 < 4 * VT_ORDER) VPFAIL("the lane layout needs %d steps, the shortest row has %d", 4 * VT_ORDER, (minlen + q->pad) / 2);
+    if (packed ? (q->out_stride % 4 != 0 || q->out_stride < (q->out_want + 31) / 32 * 4) : q->out_stride < q->out_want)
+        VPFAIL("out_stride %d too small for a window of %d %s (packed rows: whole 32-bit words)", q->out_stride, q->out_want, packed ? "bits" : "bytes");
+#undef VPFAIL
+    int rc = open_device(device);
+    if (rc) return rc;
+    const int waves = (q->nblocks + 63) / 64;
+    const size_t soft_bytes = tiled ? (size_t)waves * 64 * q->nsoft : (size_t)q->nblocks * pitch;
+    const size_t out_bytes = (size_t)out_rows * q->out_stride;
+    DevMem m;
+    uint8_t *d_soft = nullptr, *d_out = nullptr, *d_ov = nullptr;
+    int *d_valid = nullptr, *d_lens = nullptr;
+    unsigned long long *d_hist = nullptr;
+    DA(m, d_soft, soft_bytes + q->soft_misalign);
+    const size_t guard = 256; // bytes in front of and behind the device copy of out: a store there is reported, not lost
+    DA(m, d_out, out_bytes + 2 * guard);
+    HIPCHK(hipMemset(d_out, 0xC3, out_bytes + 2 * guard));
+    d_out += guard;
+    d_soft += q->soft_misalign;
+    HIPCHK(hipMemcpy(d_soft, q->soft, soft_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_out, q->out, out_bytes, hipMemcpyHostToDevice)); // not cleared: the caller's bytes show what was not written
+    if (q->overlap) { DA(m, d_ov, (size_t)q->nblocks * 64); HIPCHK(hipMemcpy(d_ov, q->overlap, (size_t)q->nblocks * 64, hipMemcpyHostToDevice)); }
+    if (q->valid) { DA(m, d_valid, q->nblocks); HIPCHK(hipMemcpy(d_valid, q->valid, sizeof(int) * (size_t)q->nblocks, hipMemcpyHostToDevice)); }
+    if (q->lens) { DA(m, d_lens, q->nblocks); HIPCHK(hipMemcpy(d_lens, q->lens, sizeof(int) * (size_t)q->nblocks, hipMemcpyHostToDevice)); }
+    if (lanes) DA(m, d_hist, viterbi_hist_bytes(q->nblocks) / sizeof(unsigned long long));
+    // layout 1: no history scratch = the wave kernel whatever jaero_debug_viterbi_layout says; 2, 3: the lane layout forced, with its entry point
+    viterbi_launch(0, d_soft, q->nsoft, d_ov, q->pad, d_out, q->out_stride, q->out_start, q->out_want, q->nblocks, d_valid, q->layout == 1 ? nullptr : d_hist, tiled, packed,
+                   q->layout >= 2, q->pitch, d_lens, q->layout >= 2 ? q->layout - 1 : 0);
+    LAUNCHCHK("the Viterbi decoder");
+    if (q->update_overlap)
+    {
+        hipLaunchKernelGGL(k_viterbi_overlap_update, dim3(q->nblocks), dim3(64), 0, 0, (const uint8_t *)d_soft, q->nsoft, d_ov, q->nblocks, (const int *)d_valid, tiled, q->pitch);
+        LAUNCHCHK("k_viterbi_overlap_update");
+    }
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(q->out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    uint8_t g[2 * guard];
+    HIPCHK(hipMemcpy(g, d_out - guard, guard, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(g + guard, d_out + out_bytes, guard, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < 2 * guard; i++)
+        if (g[i] != 0xC3) return fail(JAERO_EHIP, "jaero_debug_viterbi: the decoder wrote %s the output buffer (guard byte %zu)", i < guard ? "in front of" : "behind", i % guard);
+    if (q->overlap) HIPCHK(hipMemcpy(q->overlap, d_ov, (size_t)q->nblocks * 64, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -120,6 +120,43 @@ def test_burst_front_hooks_refuse_a_null_context():
     assert L.jaero_debug_ev_compact(0, masks, 1, None, C.byref(n)) == capi.E_INVAL and L.jaero_debug_ev_compact(0, masks, 1, idx, None) == capi.E_INVAL
 
 
+def test_viterbi_probe_refuses_what_the_kernels_do_not_implement():
+    """jaero_debug_viterbi: JAERO_EINVAL before any HIP call for the combinations neither kernel implements (the launches themselves:
+    tests/test_gpu_viterbi_modes.py).  A probe that passes these checks gets as far as the device (JAERO_ENODEV here, 0 on a GPU)."""
+    L = capi.lib()
+    assert C.sizeof(capi.ViterbiProbe) == 96  # 5 pointers + 13 ints, padded
+    soft = np.full((64, 320), 128, np.uint8)
+    out = np.zeros((64, 256), np.uint8)
+    ov = np.zeros((64, 64), np.uint8)
+    lens = np.full(64, 320, np.int32)
+
+    def rc(**kw):
+        a = dict(soft=soft.ctypes.data, nblocks=64, nsoft=304, out=out.ctypes.data, out_stride=256, out_want=152, layout=2)
+        a.update(kw)
+        q = capi.ViterbiProbe(**a)
+        return L.jaero_debug_viterbi(0, C.byref(q))
+
+    assert rc() in (0, capi.E_NODEV)
+    assert rc(tiled=1, packed=1, out_want=150) in (0, capi.E_NODEV)
+    bad = [dict(soft=None), dict(out=None), dict(layout=4), dict(nblocks=0), dict(pad=3), dict(out_start=-1), dict(out_want=0),
+           dict(layout=1, tiled=1), dict(layout=1, packed=1),                      # tiled / packed exist only in the lane layout
+           dict(tiled=1, nsoft=300), dict(tiled=1, pitch=320), dict(tiled=1, soft_misalign=4), dict(tiled=1, lens=lens.ctypes.data),
+           dict(nsoft=54), dict(nsoft=40, pad=0), dict(layout=3, nsoft=54, pad=0),  # lanes below 4 * VT_ORDER steps
+           dict(out_stride=151), dict(packed=1, out_stride=16), dict(packed=1, out_stride=22), dict(out_rows=63), dict(pitch=300),
+           dict(update_overlap=1), dict(soft_misalign=16)]
+    for kw in bad:
+        assert rc(**kw) == capi.E_INVAL, kw
+        assert b"jaero_debug_viterbi" in L.jaero_last_error(), kw
+    assert rc(layout=1, nsoft=40) in (0, capi.E_NODEV)  # the wavefront layout takes what the lane layout is too short for
+    for l0 in (322, 129, 26):
+        lens[5] = l0
+        assert rc(nsoft=320, lens=lens.ctypes.data) == capi.E_INVAL and b"lens[5]" in L.jaero_last_error()
+    lens[5] = 128
+    assert rc(nsoft=320, lens=lens.ctypes.data) in (0, capi.E_NODEV)
+    ov[9, 62] = 63
+    assert rc(overlap=ov.ctypes.data) == capi.E_INVAL and b"overlap[9]" in L.jaero_last_error()
+
+
 @pytest.mark.parametrize("kind,power,fb,Fs,lbw,ok", [
     (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.0, True), (capi.KIND_OQPSK, 14, 10500.0, 48000.0, 24000.5, False),
     (capi.KIND_OQPSK, 14, 8400.0, 48000.0, 30000.0, False), (capi.KIND_MSK, 13, 1200.0, 48000.0, 24001.0, False),
