@@ -543,6 +543,72 @@ int jaero_activity_read_peak(jaero_chan *c, double *peak, long long *nblocks);
 int jaero_activity_read_blocks(jaero_chan *c, double *emax, double *emin, long long *when, long long *nblocks, unsigned *hist);
 int jaero_activity_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset);
 
+/* ---- splitter: one capture into several banks at their own rates.  A jaero_chan produces one output rate for one bank; a capture that holds
+ * 10.5 k and 8400 bps carriers (48 kHz) beside 1200 and 600 bps ones (24 and 12 kHz) would need one handle per bank, each copying the same
+ * I/Q and repeating the same capture-wide front end (staging, the 16384-point forward transform of every hop).  A jaero_split has ONE front
+ * end, one spectrum X_p per hop, and 1 .. 8 outputs, each with its own out_rate, channels and prototype.
+ *   definition output g is, bit for bit and in every reader (int16 PCM, *nout, the survey's levels and spectrum, the activity's block
+ *              statistics and peak-hold spectrum), what a stand-alone handle produces that was created with decim D_g = fs_c / out_rate_g,
+ *              out_rate_g, the output's channels and taps (jaero_chan2_create; with `cap`, jaero_chan3_create with the same jaero_capture)
+ *              and the same max_write_iq, and is fed the same writes, cut the same way.  It holds by construction: X_p is a function of the
+ *              input and of absolute block indices only and comes from the same forward-transform launches; the blocks a write completes
+ *              depend only on max_write_iq and the capture's ratio; each output launches the stand-alone handle's synthesis, survey and
+ *              activity kernels with the same (nchannels, blocks, first block).  No kernel is new.
+ *   jaero_split_create   cap NULL: int16 I/Q at fs_c; otherwise the capture front end above with Fs_c = fs_c, and max_write_iq counts CAPTURE
+ *                        samples.  Two outputs may share a D and differ in taps and channels.  Tune words are relative to fs_c, audio words
+ *                        to the output's out_rate.  All arguments are checked before a device is looked for, JAERO_EINVAL in this order: out
+ *                        null; outs null; noutputs outside 1 .. 8; fs_c < 1; for each output in order: out_rate not 48000 / 24000 / 12000,
+ *                        fs_c / out_rate not exactly 16, 32, 64, 128 or 256, then jaero_chan2_create's own checks of that output in their
+ *                        order (max_write_iq < 1 among them); with cap: jaero_chan3_create's checks of the capture in their order (format,
+ *                        fs_in, L, the ratio, taps_per_phase, rtaps, its taps), then the staged-sample bound on max_write_iq; then
+ *                        JAERO_ENODEV off gfx950 (no CPU fallback).
+ *   jaero_split_write    niq raw pairs in the handle's format (int16 without cap): one copy of the input, one staging launch on a capture
+ *                        handle, one forward-transform launch over the nblk blocks the write completes, then for each output in order its
+ *                        synthesis and, where enabled, its survey / activity launches, all on `stream`; nout[g] = nblk Mo_g (nout:
+ *                        noutputs entries).  niq < 0 or niq > max_write_iq: JAERO_EINVAL, nothing consumed.  Stream changes and poisoning
+ *                        are jaero_chan_write's: an event from the previous stream; an error behind the first launch that advances the
+ *                        state poisons the splitter and every view (JAERO_EHIP from every later call but the destroys).
+ *   jaero_split_output   *view = a borrowed jaero_chan for output g: owned by the splitter, valid until jaero_split_destroy, the same pointer
+ *                        at every call.  Every call that reads or tunes works on it as on a stand-alone handle: jaero_chan_pcm_view,
+ *                        jaero_chan_read_pcm, jaero_chan_retune, jaero_chan2_retune_all, jaero_survey_*, jaero_activity_*,
+ *                        jaero_chan_profile_read (which 0 reports 0 launches: the forward transform is the splitter's), jaero_survey_ /
+ *                        jaero_activity_profile_read; those that synchronise use the stream of the splitter's last write.  The spectrum and
+ *                        the peak-hold spectrum may be enabled on any view and are computed for it from the shared X_p: enabling them on
+ *                        several views repeats that work (the same numbers several times).  The calls that consume input or own the handle
+ *                        -- jaero_chan_write, jaero_chan_feed, jaero_chan3_write, jaero_chan3_feed, jaero_chan3_read_staged -- return
+ *                        JAERO_EINVAL on a view, change nothing and name the call to use; jaero_chan_destroy on a view does nothing.
+ *   jaero_split_feed     banks: noutputs entries, a NULL entry's output is produced and not fed.  Before anything advances: jaero_chan_feed's
+ *                        checks of every non-null bank against its output (device, channel count, every Fs == out_rate_g, max_write_samples
+ *                        >= nblk_max Mo_g), and one bank in two entries: JAERO_EINVAL.  Then the write; then, for each non-null bank with
+ *                        nout[g] > 0 in output order, jaero_write(bank_g, view g's pcm, nout[g], JAERO_PCM_CHANNEL_MAJOR, 1, stream).  A
+ *                        bank's failure is returned, the banks behind it are not fed and the splitter is poisoned: the banks are no longer
+ *                        at one point of the capture.
+ *   jaero_split_info     any of the three may be NULL; nblk_max = the most blocks a write completes.
+ *   jaero_split_profile_* enable switches the front end's and every view's timers; read: which 0 = the forward transform (k_chan_fwd, or
+ *                        k_capture_fwd with cap), 1 = the staging kernel (0 launches without cap).  The outputs' kernels are read on the views.
+ * Null handles: JAERO_EINVAL.  Deliberately not here: outputs on separate streams, other decimations, N or hop, adding or removing outputs
+ * or channels after create, jaero_chan3_read_staged on a splitter, the multi-GPU fan-out of a capture, a shared survey spectrum for
+ * several views. */
+typedef struct jaero_chan_output {
+    int out_rate;                    /* 48000, 24000 or 12000 */
+    int nchannels;
+    const jaero_chan_channel *ch;    /* tune words relative to fs_c, audio words to out_rate */
+    const double *taps; int ntaps;   /* this output's prototype, at fs_c */
+} jaero_chan_output;
+typedef struct jaero_split jaero_split;
+int  jaero_split_create(int device, const jaero_capture *cap /* NULL: int16 I/Q at fs_c */, int fs_c,
+                        int noutputs, const jaero_chan_output *outs, int max_write_iq, jaero_split **out);
+void jaero_split_destroy(jaero_split *s);
+int  jaero_split_write(jaero_split *s, const void *iq, int niq, int is_device_ptr, void *stream,
+                       int *nout /* [noutputs] */);
+int  jaero_split_feed(jaero_split *s, jaero_ctx *const *banks /* [noutputs]; a NULL entry: produced, not fed */,
+                      const void *iq, int niq, int is_device_ptr, void *stream, int *nout /* [noutputs] */);
+int  jaero_split_output(jaero_split *s, int output, jaero_chan **view);
+int  jaero_split_info(const jaero_split *s, int *noutputs, int *fs_c, int *nblk_max);
+int  jaero_split_profile_enable(jaero_split *s, int on);          /* the front end and every output */
+int  jaero_split_profile_read(jaero_split *s, int which /* 0 forward transform (either kind), 1 staging kernel */,
+                              double *total_ms, int *launches, int reset);
+
 /* ---- rate lines: what a channel's bit rate is, measured from the int16 PCM a bank is fed (a channeliser's output or any other).  The
  * spectrum of the SQUARED signal is the measurement JAERO trusts for acquisition (CoarseFreqEstimate): MSK with h = 0.5, squared, is
  * Sunde's FSK with two lines at 2 f_audio +- fb / 2; OQPSK with the reference's RRC pulses, squared, has two lines at 2 f_audio +- 1 / T =

@@ -51,6 +51,8 @@ EXPORTS = [
     "jaero_chan2_retune_all",
     "jaero_activity_enable", "jaero_activity_reset", "jaero_activity_read_peak", "jaero_activity_read_blocks", "jaero_activity_profile_read",
     "jaero_chan3_create", "jaero_chan3_write", "jaero_chan3_feed", "jaero_chan3_read_staged", "jaero_chan3_profile_read",
+    "jaero_split_create", "jaero_split_destroy", "jaero_split_write", "jaero_split_feed", "jaero_split_output", "jaero_split_info",
+    "jaero_split_profile_enable", "jaero_split_profile_read",
     "jaero_rate_create", "jaero_rate_destroy", "jaero_rate_write", "jaero_rate_reset", "jaero_rate_read", "jaero_rate_profile_enable",
     "jaero_rate_profile_read",
     "jaero_gate_enable", "jaero_gate_set", "jaero_gate_read",
@@ -150,6 +152,13 @@ class Capture(C.Structure):
     resampler prototype h[0 .. L K) (null when the capture already runs at out_rate x decim)."""
 
     _fields_ = [("format", C.c_int), ("fs_in", C.c_int), ("shift", C.c_uint32), ("taps_per_phase", C.c_int), ("rtaps", C.c_void_p)]
+
+
+class ChanOutput(C.Structure):
+    """struct jaero_chan_output: one output of a splitter -- its rate, its channels (tune words relative to fs_c, audio words to out_rate)
+    and its prototype at fs_c."""
+
+    _fields_ = [("out_rate", C.c_int), ("nchannels", C.c_int), ("ch", C.c_void_p), ("taps", C.c_void_p), ("ntaps", C.c_int)]
 
 
 class JaeroError(RuntimeError):
@@ -294,6 +303,15 @@ def lib():
     L.jaero_chan3_feed.argtypes = [vp, vp, vp, ip, ip, vp, C.POINTER(ip)]
     L.jaero_chan3_read_staged.argtypes = [vp, vp, ip, C.POINTER(ip), C.POINTER(C.c_longlong)]
     L.jaero_chan3_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
+    L.jaero_split_create.argtypes = [ip, C.POINTER(Capture), ip, ip, C.POINTER(ChanOutput), ip, C.POINTER(vp)]
+    L.jaero_split_destroy.argtypes = [vp]
+    L.jaero_split_destroy.restype = None
+    L.jaero_split_write.argtypes = [vp, vp, ip, ip, vp, C.POINTER(ip)]
+    L.jaero_split_feed.argtypes = [vp, C.POINTER(vp), vp, ip, ip, vp, C.POINTER(ip)]
+    L.jaero_split_output.argtypes = [vp, ip, C.POINTER(vp)]
+    L.jaero_split_info.argtypes = [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]
+    L.jaero_split_profile_enable.argtypes = [vp, ip]
+    L.jaero_split_profile_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_rate_create.argtypes = [ip, ip, ip, C.POINTER(vp)]
     L.jaero_rate_destroy.argtypes = [vp]
     L.jaero_rate_destroy.restype = None

@@ -10,7 +10,10 @@ The survey (`survey_enable`, `read_psd`, `read_levels`) measures the capture's s
 the same per-block terms: the peak-hold spectrum finds carriers that are seldom on, `duty_cycle` says how often a channel is on and
 `suggest_gains(peak=True)` sets a burst channel's gain from its strongest block.  `Channeliser(..., capture=Capture(fs_in=..., fmt=...))` takes an SDR capture in its own format (cs16, cu8, cs8,
 cf32) and at its own integer rate: the device converts, shifts the centre by an exact phase word and resamples by the exact rational ratio
-to fs_out x decim (jaero_chan3_*); `design_resampler` is the prototype it uses by default.  All device arithmetic happens in
+to fs_out x decim (jaero_chan3_*); `design_resampler` is the prototype it uses by default.  `Splitter(fs_c, outputs)` is one front end
+(one copy, one staging launch, one forward transform per hop) in front of several outputs, each with its own rate, channels and taps and
+each feeding its own bank (jaero_split_*); every output is bit for bit what a stand-alone `Channeliser` produces, and `plan_outputs` groups
+surveyed carriers by the bit rate the rate meter named into such outputs.  All device arithmetic happens in
 libjaero_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -412,4 +415,171 @@ class Channeliser:
         """(total ms, launches) of kernel `which`: 0 = forward transform, 1 = per-channel synthesis."""
         ms, n = C.c_double(0), C.c_int(0)
         capi.check(self.L.jaero_chan_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
+        return ms.value, n.value
+
+
+# ---------------------------------------------------------------------------------------------- splitter
+RATE_FS_OUT = {10500: 48000.0, 8400: 48000.0, 1200: 24000.0, 600: 12000.0}  # the bank rate of each bit rate `decide_rates` names
+
+
+class Plan(NamedTuple):
+    """What `plan_outputs` returns."""
+    outputs: list    # (fs_out, channels, None) per output: what `Splitter` takes
+    indices: list    # per output, the indices into carriers_hz of the carriers it took, ascending
+    rates: list      # per output, the bit rate of its carriers: what its bank is created for
+    left_out: list   # indices of the carriers whose rate is none of RATE_FS_OUT's (0, "no rate", included)
+
+
+def plan_outputs(carriers_hz: Sequence[float], rates_bps: Sequence[float], fs_c: float, audio_hz: Optional[float] = None,
+                 gain: float = 1.0) -> Plan:
+    """Groups surveyed carriers (`find_carriers`) by the bit rate the rate meter named (`decide_rates`): one output per rate that has a
+    carrier, in the order 10500, 8400 (both at 48 kHz), 1200 (24 kHz), 600 (12 kHz); a rate without a carrier makes no output, a carrier with
+    any other rate is left out and reported.  Each channel is (tune word of the carrier at fs_c, audio word of `audio_hz` at the output's
+    rate -- None: fs_out / 6 --, gain).  A pure function: what a caller does between the rate meter and the banks."""
+    if len(carriers_hz) != len(rates_bps):
+        raise ValueError(f"plan_outputs takes one rate per carrier: {len(carriers_hz)} carriers, {len(rates_bps)} rates")
+    outputs, indices, rates = [], [], []
+    for rate, fs_out in RATE_FS_OUT.items():
+        idx = [i for i, r in enumerate(rates_bps) if float(r) == rate]
+        if not idx:
+            continue
+        audio = tune_word(fs_out / 6.0 if audio_hz is None else audio_hz, fs_out)
+        outputs.append((fs_out, [(tune_word(float(carriers_hz[i]), float(fs_c)), audio, float(gain)) for i in idx], None))
+        indices.append(idx)
+        rates.append(rate)
+    left = [i for i, r in enumerate(rates_bps) if float(r) not in RATE_FS_OUT]
+    return Plan(outputs, indices, rates, left)
+
+
+class _Output(Channeliser):
+    """Output g of a `Splitter`: a `Channeliser` around the borrowed handle (jaero_split_output).  Every reader and retune method works as
+    on a stand-alone channeliser; `nch`, `decim`, `Mo`, `fs_out`, `last_nout` and `last_stream` are kept current by the splitter.  The
+    input goes to the splitter: `write`, `feed` and `close` raise."""
+
+    def __init__(self, split: "Splitter", h, decim: int, nch: int, fs_out: float):
+        self.L, self.h, self.split = split.L, h, split
+        self.capture, self.fmt, self.shift_word = split.capture, split.fmt, split.shift_word
+        self._fs_in = split._fs_in
+        self.fs_out = float(fs_out)
+        self.decim, self.nch, self.device, self.max_write_iq = int(decim), int(nch), split.device, split.max_write_iq
+        self.M = N // self.decim
+        self.Mo = self.M // 2
+        self.last_nout = 0
+        self.last_stream = 0
+
+    def write(self, iq, stream: int = 0):
+        raise RuntimeError("an output of a Splitter takes no input of its own: use Splitter.write")
+
+    def feed(self, bank, iq, stream: int = 0):
+        raise RuntimeError("an output of a Splitter takes no input of its own: use Splitter.feed")
+
+    def read_staged(self):
+        raise RuntimeError("a Splitter has no read_staged")
+
+    def close(self):
+        raise RuntimeError("an output of a Splitter is closed with it: use Splitter.close")
+
+    def __del__(self):
+        pass
+
+
+class Splitter:
+    """One capture into several banks at their own rates (thin wrapper over jaero_split): one front end, one spectrum per hop, and
+    `len(outputs)` outputs that are each, bit for bit, what a stand-alone `Channeliser(fs_c / fs_out, channels, taps, fs_out=fs_out,
+    capture=capture)` fed the same writes produces.
+
+    fs_c: the rate the front end runs at (an integer; fs_c / fs_out must be one of DECIMS for every output).  outputs: a list of
+    (fs_out, channels, taps-or-None); taps None: design_taps(fs_c / fs_out, fs_out=fs_out).  capture: a `Capture` whose rate and format the
+    writes are in (None: int16 I/Q at fs_c); max_write_iq then counts capture samples.  `outputs[g]` is the `Channeliser` object of
+    output g."""
+
+    def __init__(self, fs_c: int, outputs: Sequence, capture: Optional[Capture] = None, device: int = 0, max_write_iq: int = 16 * HP):
+        self.L = capi.lib()
+        fs_c = int(fs_c) if float(fs_c) == int(fs_c) else 0  # a rate that is no integer is none
+        keep, rows = [], []
+        for fs_out, channels, taps in outputs:
+            rate = int(fs_out) if float(fs_out) == int(fs_out) else 0
+            if taps is None:
+                if rate < 1 or fs_c % rate or fs_c // rate not in DECIMS:
+                    raise ValueError(f"Splitter: fs_c {fs_c} / fs_out {fs_out} is none of {DECIMS}; no default taps")
+                taps = design_taps(fs_c // rate, fs_out=float(fs_out))
+            t = np.ascontiguousarray(taps, dtype=np.float64)
+            arr = _channel_array(channels)
+            keep.append((t, arr))
+            rows.append(capi.ChanOutput(rate, len(arr), C.cast(arr, C.c_void_p), t.ctypes.data, int(t.size)))
+        outs = (capi.ChanOutput * max(len(rows), 1))(*rows)
+        self.capture, self.fmt, self.shift_word, self.rtaps = capture, "cs16", 0, None
+        self._fs_in = float(fs_c)
+        cs = None
+        if capture is not None:
+            if capture.fmt not in FORMATS:
+                raise ValueError(f"capture format {capture.fmt!r} is none of {sorted(FORMATS)}")
+            fs_in = int(capture.fs_in)
+            rt = capture.rtaps
+            if rt is None and fs_in != fs_c and fs_in >= 1 and fs_c >= 1 and resample_ratio(fs_in, fs_c)[0] <= 1024:
+                rt = design_resampler(fs_in, fs_c, capture.taps_per_phase)[0]
+            rt = None if rt is None else np.ascontiguousarray(rt, dtype=np.float64)
+            self.shift_word = tune_word(capture.shift_hz, float(fs_in)) if fs_in >= 1 else 0
+            cs = capi.Capture(FORMATS[capture.fmt], fs_in, self.shift_word, int(capture.taps_per_phase), None if rt is None else rt.ctypes.data)
+            self.fmt, self._fs_in, self.rtaps = capture.fmt, float(fs_in), rt
+        h = C.c_void_p()
+        capi.check(self.L.jaero_split_create(device, None if cs is None else C.byref(cs), fs_c, len(rows), outs, int(max_write_iq), C.byref(h)))
+        self.h = h
+        self.fs_c, self.device, self.max_write_iq = fs_c, device, int(max_write_iq)
+        nblk = C.c_int(0)
+        capi.check(self.L.jaero_split_info(self.h, None, None, C.byref(nblk)))
+        self.nblk_max = nblk.value
+        self.outputs = []
+        for g, row in enumerate(rows):
+            v = C.c_void_p()
+            capi.check(self.L.jaero_split_output(self.h, g, C.byref(v)))
+            self.outputs.append(_Output(self, v, fs_c // row.out_rate, row.nchannels, float(row.out_rate)))
+        self._nout = (C.c_int * len(rows))()
+
+    _input = Channeliser._input
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.jaero_split_destroy(self.h)
+            self.h = None
+            for o in getattr(self, "outputs", []):
+                o.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _done(self, stream: int) -> list:
+        nout = list(self._nout)
+        for o, n in zip(self.outputs, nout):
+            o.last_nout, o.last_stream = n, stream
+        return nout
+
+    def write(self, iq, stream: int = 0) -> list:
+        """Consumes the I/Q pairs; returns, per output, the samples per channel this write produced (blocks x Mo of the output)."""
+        ptr, n, dev, _keep = self._input(iq)
+        capi.check(self.L.jaero_split_write(self.h, ptr, n, dev, C.c_void_p(stream), self._nout))
+        return self._done(stream)
+
+    def feed(self, banks: Sequence, iq, stream: int = 0) -> list:
+        """write, then each bank's write of its output (device to device, no synchronisation), in output order.  banks: one
+        `DemodulatorBank` per output; None: that output is produced and not fed."""
+        if len(banks) != len(self.outputs):
+            raise ValueError(f"feed takes {len(self.outputs)} banks (None where an output is not fed), not {len(banks)}")
+        ptr, n, dev, _keep = self._input(iq)
+        arr = (C.c_void_p * len(banks))(*[None if b is None else b.h for b in banks])
+        capi.check(self.L.jaero_split_feed(self.h, arr, ptr, n, dev, C.c_void_p(stream), self._nout))
+        return self._done(stream)
+
+    def profile_enable(self, on: bool = True):
+        """Switches the timers of the front end and of every output."""
+        capi.check(self.L.jaero_split_profile_enable(self.h, int(on)))
+
+    def profile_read(self, which: int, reset: bool = False):
+        """(total ms, launches) of the front end's kernel `which`: 0 = forward transform (of either kind), 1 = staging kernel.  The
+        outputs' kernels are read on `outputs[g]`."""
+        ms, n = C.c_double(0), C.c_int(0)
+        capi.check(self.L.jaero_split_profile_read(self.h, which, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value

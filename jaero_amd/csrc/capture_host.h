@@ -11,47 +11,51 @@
 static long long cap_gcd(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
 static long long cap_ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 
-extern "C" int jaero_chan3_create(int device, const jaero_capture *cap, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch,
-                                  const double *taps, int ntaps, int max_write_iq, jaero_chan **out)
+// What jaero_chan3_create checks of the capture against Fs_c, in its documented order, before jaero_chan2_create's own checks (who: the
+// create the messages name).  rates: Fs_c is a rate at all (>= 1); where it is not, the later checks say so.  Leaves L / Mr and `resample`.
+static int capture_check(const char *who, const jaero_capture *cap, bool rates, long long fs_c, long long *Lo, long long *Mro, bool *resample)
 {
-    if (!out) return fail(JAERO_EINVAL, "jaero_chan3_create: out is null");
-    *out = nullptr;
-    if (!cap) return fail(JAERO_EINVAL, "jaero_chan3_create: cap is null");
+    if (!cap) return fail(JAERO_EINVAL, "%s: cap is null", who);
     if (cap->format != JAERO_IQ_CS16 && cap->format != JAERO_IQ_CU8 && cap->format != JAERO_IQ_CS8 && cap->format != JAERO_IQ_CF32)
-        return fail(JAERO_EINVAL, "jaero_chan3_create: format %d is not one of JAERO_IQ_*", cap->format);
-    if (cap->fs_in < 1) return fail(JAERO_EINVAL, "jaero_chan3_create: fs_in %d < 1", cap->fs_in);
-    // the rate checks need Fs_c = out_rate x decim; where that is no rate at all, jaero_chan2_create's own checks below say so
-    const long long fs_c = (long long)out_rate * decim;
+        return fail(JAERO_EINVAL, "%s: format %d is not one of JAERO_IQ_*", who, cap->format);
+    if (cap->fs_in < 1) return fail(JAERO_EINVAL, "%s: fs_in %d < 1", who, cap->fs_in);
     long long L = 1, Mr = 1;
-    if (out_rate >= 1 && decim >= 1)
+    if (rates)
     {
         const long long g = cap_gcd(fs_c, cap->fs_in);
         L = fs_c / g; Mr = cap->fs_in / g;
-        if (L > 1024) return fail(JAERO_EINVAL, "jaero_chan3_create: fs_in %d to Fs_c %lld is %lld / %lld in lowest terms; L above 1024", cap->fs_in, fs_c, L, Mr);
+        if (L > 1024) return fail(JAERO_EINVAL, "%s: fs_in %d to Fs_c %lld is %lld / %lld in lowest terms; L above 1024", who, cap->fs_in, fs_c, L, Mr);
         if ((long long)cap->fs_in > 8 * fs_c || fs_c > 8ll * cap->fs_in)
-            return fail(JAERO_EINVAL, "jaero_chan3_create: the ratio of fs_in %d and Fs_c %lld is beyond 8", cap->fs_in, fs_c);
+            return fail(JAERO_EINVAL, "%s: the ratio of fs_in %d and Fs_c %lld is beyond 8", who, cap->fs_in, fs_c);
     }
-    const bool resample = L != 1 || Mr != 1;
-    if (resample)
+    *resample = L != 1 || Mr != 1;
+    if (*resample)
     {
         if (cap->taps_per_phase < 1 || cap->taps_per_phase > CAP_MAXK)
-            return fail(JAERO_EINVAL, "jaero_chan3_create: taps_per_phase %d outside [1, %d]", cap->taps_per_phase, CAP_MAXK);
-        if (!cap->rtaps) return fail(JAERO_EINVAL, "jaero_chan3_create: rtaps is null and the rates differ");
+            return fail(JAERO_EINVAL, "%s: taps_per_phase %d outside [1, %d]", who, cap->taps_per_phase, CAP_MAXK);
+        if (!cap->rtaps) return fail(JAERO_EINVAL, "%s: rtaps is null and the rates differ", who);
         for (long long i = 0; i < L * cap->taps_per_phase; i++)
-            if (!__builtin_isfinite(cap->rtaps[i])) return fail(JAERO_EINVAL, "jaero_chan3_create: resampler tap %lld is not finite", i);
+            if (!__builtin_isfinite(cap->rtaps[i])) return fail(JAERO_EINVAL, "%s: resampler tap %lld is not finite", who, i);
     }
-    { const int rc = chan_check_create(decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq); if (rc) return rc; }
-    const long long smax = cap_ceil_div((long long)max_write_iq * L, Mr); // most staged samples a write can make (max_write_iq >= 1 by now)
-    if (smax + 1 + 2 * CHAN_HP > 0x7fffffffll)
-        return fail(JAERO_EINVAL, "jaero_chan3_create: max_write_iq %d stages %lld samples a write; the history holds fewer than 2^31", max_write_iq, smax);
-    { const int rc = open_device(device); if (rc) return rc; }
+    *Lo = L; *Mro = Mr;
+    return 0;
+}
 
-    std::unique_ptr<jaero_chan> c(new (std::nothrow) jaero_chan());
-    if (!c) return fail(JAERO_ENOMEM, "jaero_chan3_create: out of memory");
+// and behind them: the most staged samples a write can make (max_write_iq >= 1 by now), which the history must hold below 2^31
+static int capture_check_staged(const char *who, int max_write_iq, long long L, long long Mr, long long *smax)
+{
+    *smax = cap_ceil_div((long long)max_write_iq * L, Mr);
+    if (*smax + 1 + 2 * CHAN_HP > 0x7fffffffll)
+        return fail(JAERO_EINVAL, "%s: max_write_iq %d stages %lld samples a write; the history holds fewer than 2^31", who, max_write_iq, *smax);
+    return 0;
+}
+
+// The capture's half of a front end, behind chan_build_front: the raw and the fp64 histories and the resampler's phases.
+static int capture_build(jaero_chan *c, const jaero_capture *cap, long long L, long long Mr, bool resample, int max_write_iq, long long smax)
+{
+    int rc = 0;
     c->cap.reset(new (std::nothrow) ChanCapture());
     if (!c->cap) return fail(JAERO_ENOMEM, "jaero_chan3_create: out of memory");
-    int rc = chan_build(c, device, decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq, smax);
-    if (rc) return rc;
     ChanCapture &k = *c->cap;
     k.format = cap->format; k.fs_in = cap->fs_in; k.shift = cap->shift; k.resample = resample;
     k.L = (int)L; k.Mr = (int)Mr; k.K = resample ? cap->taps_per_phase : 1;
@@ -71,6 +75,27 @@ extern "C" int jaero_chan3_create(int device, const jaero_capture *cap, int deci
         HIPCHK(hipMemcpy(k.d_hp, hp.data(), sizeof(double) * hp.size(), hipMemcpyHostToDevice));
     }
     HIPCHK(hipFuncSetAttribute((const void *)k_capture_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH * (int)sizeof(double)));
+    return 0;
+}
+
+extern "C" int jaero_chan3_create(int device, const jaero_capture *cap, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch,
+                                  const double *taps, int ntaps, int max_write_iq, jaero_chan **out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_chan3_create: out is null");
+    *out = nullptr;
+    // the rate checks need Fs_c = out_rate x decim; where that is no rate at all, jaero_chan2_create's own checks below say so
+    long long L = 1, Mr = 1, smax = 0;
+    bool resample = false;
+    { const int rc = capture_check("jaero_chan3_create", cap, out_rate >= 1 && decim >= 1, (long long)out_rate * decim, &L, &Mr, &resample); if (rc) return rc; }
+    { const int rc = chan_check_create("jaero_chan2_create", decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq); if (rc) return rc; }
+    { const int rc = capture_check_staged("jaero_chan3_create", max_write_iq, L, Mr, &smax); if (rc) return rc; }
+    { const int rc = open_device(device); if (rc) return rc; }
+
+    std::unique_ptr<jaero_chan> c(new (std::nothrow) jaero_chan());
+    if (!c) return fail(JAERO_ENOMEM, "jaero_chan3_create: out of memory");
+    int rc = chan_build(c, device, decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq, smax);
+    if (rc) return rc;
+    if ((rc = capture_build(c.get(), cap, L, Mr, resample, max_write_iq, smax))) return rc;
     *out = c.release();
     return 0;
 }
@@ -168,6 +193,7 @@ static int capture_write(jaero_chan *c, const void *iq, int niq, int is_device_p
 extern "C" int jaero_chan3_write(jaero_chan *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "jaero_chan3_write: bad arguments");
+    CHANVIEWCHK(c, "jaero_chan3_write", "jaero_split_write");
     if (!c->cap) return jaero_chan_write(c, (const int16_t *)iq, niq, is_device_ptr, stream, nout);
     return capture_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan3_write");
 }
@@ -175,6 +201,7 @@ extern "C" int jaero_chan3_write(jaero_chan *c, const void *iq, int niq, int is_
 extern "C" int jaero_chan3_feed(jaero_chan *c, jaero_ctx *bank, const void *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !bank || !nout) return fail(JAERO_EINVAL, "jaero_chan3_feed: null argument");
+    CHANVIEWCHK(c, "jaero_chan3_feed", "jaero_split_feed");
     if (!c->cap) return jaero_chan_feed(c, bank, (const int16_t *)iq, niq, is_device_ptr, stream, nout);
     const int rc0 = chan_feed_check(c, bank, "jaero_chan3_feed");
     if (rc0) return rc0;
@@ -187,6 +214,7 @@ extern "C" int jaero_chan3_feed(jaero_chan *c, jaero_ctx *bank, const void *iq, 
 extern "C" int jaero_chan3_read_staged(jaero_chan *c, double *reim, int cap_pairs, int *npairs, long long *first_index)
 {
     if (!c || !npairs || !first_index || cap_pairs < 0 || (cap_pairs > 0 && !reim)) return fail(JAERO_EINVAL, "jaero_chan3_read_staged: bad arguments");
+    CHANVIEWCHK(c, "jaero_chan3_read_staged", "a stand-alone handle (a splitter has no jaero_chan3_read_staged)");
     if (!c->cap) return fail(JAERO_EINVAL, "jaero_chan3_read_staged: the handle has no capture front end (jaero_chan3_create)");
     CHANPOISONCHK(c, "jaero_chan3_read_staged");
     const ChanCapture &k = *c->cap;

@@ -62,9 +62,16 @@ struct jaero_chan
     hipStream_t last_stream = nullptr;
     hipEvent_t order_ev = nullptr;
     bool poisoned = false;
+    // the splitter (split_host.h): its front end is a handle without outputs (nch = 0) whose `split` names it; each output is a view, a handle
+    // without a front end whose `front` names the splitter's (d_spec is the front's, nblk_max and last_stream follow it).  Both null: stand-alone.
+    jaero_chan *front = nullptr;
+    jaero_split *split = nullptr;
 };
 
-#define CHANPOISONCHK(c, who) do { if ((c)->poisoned) return fail(JAERO_EHIP, who ": an earlier write of this channeliser failed part-way; destroy it and create a new one"); } while (0)
+#define CHANPOISONCHK(c, who) do { if ((c)->poisoned || ((c)->front && (c)->front->poisoned)) return fail(JAERO_EHIP, who ": an earlier write of this channeliser failed part-way; destroy it and create a new one"); } while (0)
+
+// a splitter's view refuses the calls that consume input or own the handle, and names the splitter's call
+#define CHANVIEWCHK(c, who, use) do { if ((c)->front) return fail(JAERO_EINVAL, who ": the handle is an output of a splitter (jaero_split_output); use " use); } while (0)
 
 static bool chan_channel_ok(const jaero_chan_channel &ch) { return __builtin_isfinite(ch.gain) && ch.gain > 0; }
 
@@ -103,40 +110,42 @@ static std::vector<double2> chan_response(const double *taps, int ntaps, int M)
 
 extern "C" void jaero_chan_destroy(jaero_chan *c)
 {
-    if (!c) return;
+    if (!c || c->front) return; // a view goes with its splitter (jaero_split_destroy)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->last_stream);
     if (c->order_ev) (void)hipEventDestroy(c->order_ev);
     delete c;
 }
 
-static int chan_check_create(int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps, int max_write_iq)
+// who: the create the messages name (a splitter names its own and the output)
+static int chan_check_create(const char *who, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps, int max_write_iq)
 {
-    if (!ch || !taps) return fail(JAERO_EINVAL, "jaero_chan2_create: null channels / taps");
+    if (!ch || !taps) return fail(JAERO_EINVAL, "%s: null channels / taps", who);
     if (decim != 16 && decim != 32 && decim != 64 && decim != 128 && decim != 256)
-        return fail(JAERO_EINVAL, "jaero_chan2_create: decim %d is not 16, 32, 64, 128 or 256", decim);
+        return fail(JAERO_EINVAL, "%s: decim %d is not 16, 32, 64, 128 or 256", who, decim);
     if (out_rate != 48000 && out_rate != 24000 && out_rate != 12000)
-        return fail(JAERO_EINVAL, "jaero_chan2_create: out_rate %d is not 48000, 24000 or 12000", out_rate);
-    if (nchannels < 1) return fail(JAERO_EINVAL, "jaero_chan2_create: nchannels %d < 1", nchannels);
-    if (ntaps < 1 || ntaps > CHAN_N / 2 + 1) return fail(JAERO_EINVAL, "jaero_chan2_create: ntaps %d outside [1, %d]", ntaps, CHAN_N / 2 + 1);
-    if (max_write_iq < 1) return fail(JAERO_EINVAL, "jaero_chan2_create: max_write_iq %d < 1", max_write_iq);
+        return fail(JAERO_EINVAL, "%s: out_rate %d is not 48000, 24000 or 12000", who, out_rate);
+    if (nchannels < 1) return fail(JAERO_EINVAL, "%s: nchannels %d < 1", who, nchannels);
+    if (ntaps < 1 || ntaps > CHAN_N / 2 + 1) return fail(JAERO_EINVAL, "%s: ntaps %d outside [1, %d]", who, ntaps, CHAN_N / 2 + 1);
+    if (max_write_iq < 1) return fail(JAERO_EINVAL, "%s: max_write_iq %d < 1", who, max_write_iq);
     for (int i = 0; i < nchannels; i++)
-        if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "jaero_chan2_create: channel %d: gain %g is not finite and positive", i, ch[i].gain);
+        if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "%s: channel %d: gain %g is not finite and positive", who, i, ch[i].gain);
     for (int i = 0; i < ntaps; i++)
-        if (!__builtin_isfinite(taps[i])) return fail(JAERO_EINVAL, "jaero_chan2_create: tap %d is not finite", i);
+        if (!__builtin_isfinite(taps[i])) return fail(JAERO_EINVAL, "%s: tap %d is not finite", who, i);
     return 0;
 }
 
 // Everything behind the checks and the device.  smax = 0: an int16 handle (history d_in, max_write_iq samples a write); smax > 0: a capture
 // handle, whose fp64 history (capture_host.h) takes at most smax staged samples a write -- d_in is not allocated.
-static int chan_build(std::unique_ptr<jaero_chan> &c, int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch,
-                      const double *taps, int ntaps, int max_write_iq, long long smax)
+//
+// A handle is two halves, built by two functions so that a splitter can build one front end and several outputs.  The front end: the
+// histories, the spectrum d_spec, the forward transform's twiddles d_tw, the counts (cur, pending, blocks_done) and the most blocks a write
+// completes.
+static int chan_build_front(jaero_chan *c, int device, int max_write_iq, long long smax)
 {
     int rc = 0;
-    c->device = device; c->decim = decim; c->out_rate = out_rate; c->nch = nchannels; c->max_write_iq = max_write_iq;
-    c->M = CHAN_N / decim; c->Mo = c->M / 2;
+    c->device = device; c->max_write_iq = max_write_iq;
     c->nblk_max = smax > 0 ? (int)((smax + 1) / CHAN_HP + 1) : max_write_iq / CHAN_HP + 1;
-    c->channels.assign(ch, ch + nchannels);
     if (smax == 0)
     {
         const size_t nin = 2 * (size_t)CHAN_HP + (size_t)max_write_iq;
@@ -144,9 +153,22 @@ static int chan_build(std::unique_ptr<jaero_chan> &c, int device, int decim, int
         DA(c->mem, c->d_in[1], nin);
     }
     DA(c->mem, c->d_spec, (size_t)c->nblk_max * CHAN_N);
+    DA(c->mem, c->d_tw, CHAN_N);
+    HIPCHK(hipMemcpy(c->d_tw, twiddles(CHAN_N, CHAN_N).data(), sizeof(double2) * CHAN_N, hipMemcpyHostToDevice));
+    HIPCHK(hipFuncSetAttribute((const void *)k_chan_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH * (int)sizeof(double)));
+    return 0;
+}
+
+// The output: the response d_gm, the synthesis' twiddles d_twm, the channels and their parameters d_par, the PCM d_pcm (and, once enabled,
+// the survey's and the activity's state).  Reads device and nblk_max, which the front end's half (or the splitter, for a view) has set.
+static int chan_build_out(jaero_chan *c, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps)
+{
+    int rc = 0;
+    c->decim = decim; c->out_rate = out_rate; c->nch = nchannels;
+    c->M = CHAN_N / decim; c->Mo = c->M / 2;
+    c->channels.assign(ch, ch + nchannels);
     DA(c->mem, c->d_gm, c->M);
     DA(c->mem, c->d_twm, 32);
-    DA(c->mem, c->d_tw, CHAN_N);
     DA(c->mem, c->d_par, nchannels);
     DA(c->mem, c->d_pcm, (size_t)nchannels * c->nblk_max * c->Mo);
     std::vector<ChanParam> par(nchannels);
@@ -154,9 +176,14 @@ static int chan_build(std::unique_ptr<jaero_chan> &c, int device, int decim, int
     HIPCHK(hipMemcpy(c->d_par, par.data(), sizeof(ChanParam) * nchannels, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_gm, chan_response(taps, ntaps, c->M).data(), sizeof(double2) * c->M, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_twm, twiddles(c->M, 32).data(), sizeof(double2) * 32, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->d_tw, twiddles(CHAN_N, CHAN_N).data(), sizeof(double2) * CHAN_N, hipMemcpyHostToDevice));
-    HIPCHK(hipFuncSetAttribute((const void *)k_chan_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH * (int)sizeof(double)));
     return 0;
+}
+
+static int chan_build(std::unique_ptr<jaero_chan> &c, int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch,
+                      const double *taps, int ntaps, int max_write_iq, long long smax)
+{
+    const int rc = chan_build_front(c.get(), device, max_write_iq, smax);
+    return rc ? rc : chan_build_out(c.get(), decim, out_rate, nchannels, ch, taps, ntaps);
 }
 
 // decim: the total decimation from the capture to the output; out_rate: what the output is called (jaero_chan_feed compares it with the bank's Fs)
@@ -165,7 +192,7 @@ extern "C" int jaero_chan2_create(int device, int decim, int out_rate, int nchan
 {
     if (!out) return fail(JAERO_EINVAL, "jaero_chan2_create: out is null");
     *out = nullptr;
-    { const int rc = chan_check_create(decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq); if (rc) return rc; }
+    { const int rc = chan_check_create("jaero_chan2_create", decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq); if (rc) return rc; }
     { const int rc = open_device(device); if (rc) return rc; }
     std::unique_ptr<jaero_chan> c(new (std::nothrow) jaero_chan());
     if (!c) return fail(JAERO_ENOMEM, "jaero_chan2_create: out of memory");
@@ -214,12 +241,12 @@ static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipSt
     else go(k_chan_synth<256>, ChanShape<256>::ITEMS, ChanShape<256>::THREADS);
 }
 
-// What every write does behind its forward transform of nblk > 0 blocks: the synthesis, the survey's and the activity's kernels when enabled, then the last
-// hop and what lies behind it (`total` samples wait in `hist`, of `elem` bytes each) become the head of the other history buffer `other`.
-static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, void *other, size_t elem, hipStream_t st)
+// An output's half of what a write does behind its forward transform of nblk > 0 blocks, the first of them block p0: the synthesis, then the
+// survey's and the activity's kernels when enabled, over c->d_spec (a view's is its splitter's).
+static int chan_outputs(jaero_chan *c, int nblk, long long p0, hipStream_t st)
 {
     int pi = c->timer.begin(1, st);
-    chan_launch_synth(c, nblk, c->blocks_done, st);
+    chan_launch_synth(c, nblk, p0, st);
     LAUNCHCHK("k_chan_synth");
     c->timer.end(pi, st);
     // one launch of k_chan_psd serves the survey's spectrum, the activity's peak or both; timed under the activity's slot when it serves that
@@ -244,14 +271,25 @@ static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, 
     if (lvl || blk)
     {
         pi = c->timer.begin(blk ? 7 : 3, st);
-        if (lvl && blk) chan_launch_level<true, true>(c, nblk, c->blocks_done, st);
-        else if (lvl) chan_launch_level<true, false>(c, nblk, c->blocks_done, st);
-        else chan_launch_level<false, true>(c, nblk, c->blocks_done, st);
+        if (lvl && blk) chan_launch_level<true, true>(c, nblk, p0, st);
+        else if (lvl) chan_launch_level<true, false>(c, nblk, p0, st);
+        else chan_launch_level<false, true>(c, nblk, p0, st);
         LAUNCHCHK("k_chan_level");
         c->timer.end(pi, st);
         if (lvl) c->lvl_blocks += nblk;
         if (blk) c->act_blocks += nblk;
     }
+    return 0;
+}
+
+static int split_outputs(jaero_split *s, int nblk, long long p0, hipStream_t st);
+
+// What every write does behind its forward transform of nblk > 0 blocks: the handle's own output (a splitter's front end: every view's, in
+// output order), then the last hop and what lies behind it (`total` samples wait in `hist`, of `elem` bytes each) become the head of the
+// other history buffer `other`.
+static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, void *other, size_t elem, hipStream_t st)
+{
+    { const int rc = c->split ? split_outputs(c->split, nblk, c->blocks_done, st) : chan_outputs(c, nblk, c->blocks_done, st); if (rc) return rc; }
     const int rest = total - nblk * CHAN_HP;
     HIPCHK(hipMemcpyAsync(other, (const char *)hist + (size_t)nblk * CHAN_HP * elem, elem * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
     c->cur ^= 1;
@@ -262,17 +300,12 @@ static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, 
 
 static int capture_write(jaero_chan *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who);
 
-extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
+// the write of an int16 handle (who: the entry point the messages name)
+static int chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who)
 {
-    if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "jaero_chan_write: bad arguments");
-    if (c->cap)
-    {
-        if (c->cap->format != JAERO_IQ_CS16)
-            return fail(JAERO_EINVAL, "jaero_chan_write: the handle's capture format is %d, not int16 I/Q; use jaero_chan3_write", c->cap->format);
-        return capture_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
-    }
-    if (niq > c->max_write_iq) return fail(JAERO_EINVAL, "jaero_chan_write: niq %d exceeds max_write_iq %d", niq, c->max_write_iq);
-    CHANPOISONCHK(c, "jaero_chan_write");
+    if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "%s: bad arguments", who);
+    if (niq > c->max_write_iq) return fail(JAERO_EINVAL, "%s: niq %d exceeds max_write_iq %d", who, niq, c->max_write_iq);
+    if (c->poisoned) return fail(JAERO_EHIP, "%s: an earlier write of this channeliser failed part-way; destroy it and create a new one", who);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
     if (st != c->last_stream) // a write on another stream than the previous one waits for what was enqueued there (a bank fed from it included)
@@ -303,6 +336,19 @@ extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int i
     c->last_nout = *nout = nblk * c->Mo;
     c->poisoned = false;
     return 0;
+}
+
+extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
+{
+    if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "jaero_chan_write: bad arguments");
+    CHANVIEWCHK(c, "jaero_chan_write", "jaero_split_write");
+    if (c->cap)
+    {
+        if (c->cap->format != JAERO_IQ_CS16)
+            return fail(JAERO_EINVAL, "jaero_chan_write: the handle's capture format is %d, not int16 I/Q; use jaero_chan3_write", c->cap->format);
+        return capture_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
+    }
+    return chan_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
 }
 
 extern "C" int jaero_chan_pcm_view(jaero_chan *c, void **dev_pcm, int *nsamples)
@@ -418,6 +464,7 @@ static int chan_feed_check(const jaero_chan *c, const jaero_ctx *bank, const cha
 extern "C" int jaero_chan_feed(jaero_chan *c, jaero_ctx *bank, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !bank || !nout) return fail(JAERO_EINVAL, "jaero_chan_feed: null argument");
+    CHANVIEWCHK(c, "jaero_chan_feed", "jaero_split_feed");
     { const int rc = chan_feed_check(c, bank, "jaero_chan_feed"); if (rc) return rc; }
     int rc = jaero_chan_write(c, iq, niq, is_device_ptr, stream, nout);
     if (rc || *nout <= 0) return rc;
@@ -623,3 +670,4 @@ extern "C" int jaero_activity_profile_read(jaero_chan *c, int which, double *tot
 }
 
 #include "capture_host.h"
+#include "split_host.h"
