@@ -210,8 +210,9 @@ int jaero_viterbi_continuous(int device, const uint8_t *soft, int nstreams, int 
  *   DataCarrierDetect(bool) and the "Error short frame" notice  :1593-1596,1995-2010   jaero_aerol_read_events: rows of 3 int64
  *                                               [soft-bit index, kind (0 = DCD, 1 = short frame (value = its length), 2 = unique word), value]
  *   updateDCD() from the 1 s QTimer            JAERO/aerol.cpp:1109-1122          jaero_aerol_tick_dcd (call once per second of signal)
- * What follows a CRC-clean signal unit in the reference (message names, ISU / ACARS reassembly, plane database) is text and control
- * plane and stays with the caller. */
+ * Of what follows a CRC-clean signal unit in the reference, the ISU / SSU reassembly and the ACARS header are here, off unless enabled
+ * (jaero_aerol_isu_enable, below); message names, the joining of ACARS blocks and the plane database are text and control plane and stay with
+ * the caller. */
 typedef struct jaero_aerol_ctx jaero_aerol_ctx;
 int jaero_aerol_create(int device, int nchannels, int fb, int max_softbits_per_write, int su_capacity, jaero_aerol_ctx **out);
 void jaero_aerol_destroy(jaero_aerol_ctx *ctx);
@@ -278,22 +279,77 @@ int jaero_aerol_link_dcd(jaero_aerol_ctx *ctx, jaero_ctx *bank);
  * *nchannels_taken = taken; *rows_pending = P_{nchannels-1} before the call (size a buffer with a caprows = 0 call).  A taken channel is left
  * as jaero_aerol_read_* with enough capacity leaves it (count 0, overflow bit of that class cleared); a channel not taken is not touched.
  * If a taken channel had its overflow bit set, everything is filled in and the call returns JAERO_EOVERFLOW, overflowed[c] = 1 saying where.
- * The rows are bit for bit the per-channel readers'.  Checks, in this order, before a device is touched: `what` is none of the four, caprows
- * < 0, null offsets / nchannels_taken, null rows with caprows > 0, null ctx (JAERO_EINVAL); then a class the bank's mode does not have gets
+ * The rows are bit for bit the per-channel readers'.  Checks, in this order, before a device is touched: `what` is none of the classes
+ * (JAERO_AEROL_MESSAGES is one only on a bank that has called jaero_aerol_isu_enable: with a null ctx or a bank that never enabled it is
+ * refused here, as every value above JAERO_AEROL_VOICE was before that class existed), caprows < 0, null offsets / nchannels_taken, null rows with caprows > 0, null ctx (JAERO_EINVAL); then a class the bank's mode does not have gets
  * the per-channel reader's own error (SUS on a burst bank, PACKETS on any other: JAERO_ENOTSUP; VOICE on a bank that is not fb = 8400:
  * JAERO_EINVAL).  Synchronises the handle's last stream (twice).
- * jaero_aerol_profile2_read: as jaero_aerol_profile_read with which 0 .. 4; 3 = the kernels of jaero_aerol_read_all, 4 = the link kernel.
+ * jaero_aerol_profile2_read: as jaero_aerol_profile_read with which 0 .. 5; 3 = the kernels of jaero_aerol_read_all, 4 = the link kernel,
+ * 5 = the reassembly kernel (jaero_aerol_isu_enable).
  * jaero_read_all (below) is the same call for the demodulator bank's soft bits and logs: this paragraph defines both.
  * Deliberately not here: rows handed over in device memory. */
 #define JAERO_AEROL_SUS 0      /* P and C banks: rows of 16 int32, as jaero_aerol_read_sus        */
 #define JAERO_AEROL_PACKETS 1  /* burst banks:   rows of 16 int32, as jaero_aerol_read_packets    */
 #define JAERO_AEROL_EVENTS 2   /* every bank:    rows of 3 int64,  as jaero_aerol_read_events     */
 #define JAERO_AEROL_VOICE 3    /* C banks:       rows of 304 bytes, as jaero_aerol_read_voice     */
+#define JAERO_AEROL_MESSAGES 4 /* P banks that enabled the reassembly: rows of jaero_aerol_msg, as jaero_aerol_read_msgs; any other: JAERO_EINVAL */
 int jaero_aerol_read_all(jaero_aerol_ctx *ctx, int what, void *rows, int caprows, int *offsets /* [nchannels + 1] */, int *nchannels_taken,
                          long long *rows_pending /* optional */, unsigned char *overflowed /* optional [nchannels] */);
 int jaero_aerol_profile2_read(jaero_aerol_ctx *ctx, int which, double *total_ms, int *launches, int reset);
-/* test hook: bytes of device memory the link and jaero_aerol_read_all have allocated for this bank so far (0 for a bank that used neither) */
+/* test hook: bytes of device memory the link, jaero_aerol_read_all and jaero_aerol_isu_enable have allocated for this bank so far (0 for a bank
+ * that used none of them) */
 long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *ctx);
+
+/* ---- ISU user data and ACARS headers, reassembled on the device (ISUData::update JAERO/aerol.cpp:117-219, aerol.h:113-228; the header part of
+ * ParserISU::parse aerol.cpp:340-470) ----
+ * Off by default: a bank that never calls jaero_aerol_isu_enable allocates and launches what it did without it.  Continuous P-channel banks
+ * (600 / 1200 / 10500 bps) only.  While enabled, each channel keeps one ISUData, updated with the 10 payload bytes d[0..9] of every CRC-clean
+ * signal unit in stream order (aerol.cpp:1616-1943), whether or not the signal-unit log had room for the unit's row.  The definition, with the
+ * reference's quirks (tests/isu_oracle.py restates it):
+ *   Scratch item `a`: AESID, GESID, QNO, REFNO, SEQNO, NOOCT (NOOCTLESTINLASTSSU: user-data octets in the last SSU).  Zero at enable; it
+ *     survives between units and is NOT cleared by a reset.
+ *   List of items, ordered, at most 11: only an ISU ages it, the survivors' counts are distinct, an item leaves once its count exceeds 10.
+ *   ISU, d[0] == 0x71: (1) count++ on every item, then every item with count > 10 is removed, in list order; (2) a.AESID = d[1..3] big-endian,
+ *     a.GESID = d[4], a.QNO = d[5] >> 4, a.REFNO = d[5] & 15, a.SEQNO = d[6] & 63, a.NOOCT = d[7] >> 4, count = 0, user data = d[8..9];
+ *     (3) the first item with equal (AESID, GESID, QNO, REFNO) is looked for -- none is found if a.NOOCT > 8; (4) found: overwritten in place,
+ *     otherwise `a` is appended.
+ *   SSU, (d[0] & 0xC0) == 0xC0: (1) only a.SEQNO = d[0] & 63, a.QNO = d[1] >> 4, a.REFNO = d[1] & 15 change; AESID, GESID and NOOCT stay what
+ *     the last ISU left, so an SSU can only continue an item of the most recent ISU's aircraft, and behind an ISU with NOOCT > 8 every SSU is
+ *     missing; (2) the first item with equal AESID and GESID, a.SEQNO + 1 == item.SEQNO, equal QNO and REFNO is looked for -- none is found if
+ *     a.NOOCT > 8; (3) none: the SSU is "missing", nothing else changes; (4) otherwise item.SEQNO--; at 0 the bytes d[2 .. item.NOOCT + 1] are
+ *     appended, the item is complete and a copy is emitted (it stays in the list with SEQNO 0); else d[2..9] are appended.  An SSU never
+ *     touches a count.  (The test in (2) looks at a.NOOCT, not at the item's: an item appended with NOOCT > 8 can be found once a later ISU
+ *     of the same aircraft has left a smaller a.NOOCT.  The reference then reads past the unit's ten bytes; here at most the eight bytes the
+ *     unit has, d[2..9], are appended, which keeps nbytes <= 506.)
+ *   Any other first byte: no effect.
+ *   Reset (the list is cleared): at the short-frame notice (aerol.cpp:1995-1998, the kind-1 event of jaero_aerol_read_events) and at enable.
+ *     (AeroL::setSettings resets it too; a bank's rate is fixed at create.)
+ *   Emission: one jaero_aerol_msg per completed item, classified as ParserISU::parse does.  flags bit 0: AESID == 0, then no other bit.  Bit 1:
+ *     the ACARS pattern, nbytes > 16, data[0] == data[1] == 0xFF, data[15] == 0x83 or 0x02.  With bit 1: bit 2 = text present (data[15] == 0x02),
+ *     bit 3 = more to come (data[nbytes - 4] == 0x97), bit 4 = parity error (a byte of data[4..10], or with text a byte of data[16 .. nbytes - 5],
+ *     has even parity), mode = data[3] & 0x7F, tak, label[0..1], bi = data[11..14] & 0x7F.  Without bit 1 those five bytes are 0.
+ * jaero_aerol_isu_enable(ctx, msg_capacity): msg_capacity >= 1 enables with a log of that many rows per channel -- synchronises, allocates on
+ * first use (about 6 KB per channel besides the log), clears the list, `a`, the log and the counters; 0 disables: later writes launch nothing
+ * extra, the log stays readable.  Checks, in this order, before a device is touched: null ctx, msg_capacity < 0 (JAERO_EINVAL); a burst bank,
+ * fb = 8400 (JAERO_ENOTSUP: DecodeC never calls ISUData; the R / T path -- RISUData and the T packets' units, aerol.cpp:1395,1504-1513 -- is
+ * deliberately not here).  An Aero-L bank has no poisoned state.
+ * jaero_aerol_read_msgs: the per-channel reader, with jaero_aerol_read_sus's semantics (overflow bit 8 of the channel: messages completed while
+ * the log was full were dropped; JAERO_EINVAL on a bank that never enabled).  JAERO_AEROL_MESSAGES of jaero_aerol_read_all: every channel's.
+ * jaero_aerol_isu_stats: per channel four counters since enable -- ISU updates, SSU updates, missing SSUs, completed messages -- counted
+ * whether or not the log had room.  Null ctx / stats, a bank that never enabled: JAERO_EINVAL. */
+typedef struct jaero_aerol_msg
+{
+    int32_t frame, k;      /* as the signal-unit rows' frame number and unit index: the unit that completed the message */
+    uint32_t aesid;
+    uint8_t gesid, qno, refno, nooct;
+    uint16_t nbytes;       /* 2 .. 506 */
+    uint16_t flags;
+    uint8_t mode, tak, label[2], bi, pad[7];
+    uint8_t data[512];     /* the raw user data, zero padded */
+} jaero_aerol_msg;         /* 544 bytes */
+int jaero_aerol_isu_enable(jaero_aerol_ctx *ctx, int msg_capacity);
+int jaero_aerol_read_msgs(jaero_aerol_ctx *ctx, int channel, void *rows /* jaero_aerol_msg[caprows] */, int caprows, int *nrows);
+int jaero_aerol_isu_stats(jaero_aerol_ctx *ctx, long long *stats /* [nchannels][4] */);
 
 /* ---- one-call reads of every channel of a demodulator bank ----
  * jaero_read_all is jaero_aerol_read_all (above: the prefix rule P_c <= caprows, offsets, *nchannels_taken, *rows_pending, the caprows = 0 sizing

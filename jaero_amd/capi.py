@@ -21,7 +21,9 @@ IQ_CS16, IQ_CU8, IQ_CS8, IQ_CF32 = 0, 1, 2, 3
 ACT_PEAK, ACT_BLOCKS, ACT_BINS = 1, 2, 64  # jaero_activity_enable: what; bins of a channel's histogram
 RATE_L, RATE_BINS = 4096, 2049  # jaero_rate: segment length, bins of a channel's row
 GATE_MANUAL, GATE_AUTO, GATE_HIST, GATE_HBINS = 1, 2, 4, 321  # jaero_gate2_enable: mode; bins of a channel's histogram of E
-AEROL_SUS, AEROL_PACKETS, AEROL_EVENTS, AEROL_VOICE = 0, 1, 2, 3  # jaero_aerol_read_all: what
+AEROL_SUS, AEROL_PACKETS, AEROL_EVENTS, AEROL_VOICE, AEROL_MESSAGES = 0, 1, 2, 3, 4  # jaero_aerol_read_all: what
+AEROL_OVF_SUS, AEROL_OVF_EVENTS, AEROL_OVF_VOICE, AEROL_OVF_MESSAGES = 1, 2, 4, 8  # a channel's overflow bits, one per output class
+MSG_AES0, MSG_ACARS, MSG_TEXT, MSG_MORE, MSG_PARITY = 1, 2, 4, 8, 16  # jaero_aerol_msg.flags
 BANK_SOFTBITS, BANK_STATUS_LOG, BANK_EVENTS, BANK_SYMBOLS = 0, 1, 2, 3  # jaero_read_all: what
 E_OK, E_INVAL, E_NODEV, E_NOMEM, E_HIP, E_OVERFLOW, E_NOTSUP = 0, -1, -2, -3, -4, -5, -6
 
@@ -42,6 +44,7 @@ EXPORTS = [
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
     "jaero_aerol_link_dcd", "jaero_aerol_read_all", "jaero_aerol_profile2_read", "jaero_aerol_debug_extra_bytes",
+    "jaero_aerol_isu_enable", "jaero_aerol_read_msgs", "jaero_aerol_isu_stats",
     "jaero_read_all", "jaero_read_status_all", "jaero_profile2_read", "jaero_debug_read_all_bytes", "jaero_debug_softbit_counts",
     "jaero_ingest_create", "jaero_ingest_destroy", "jaero_ingest_push", "jaero_ingest_queued", "jaero_ingest_pump",
     "jaero_ingest_stats",
@@ -161,6 +164,14 @@ class ChanOutput(C.Structure):
     _fields_ = [("out_rate", C.c_int), ("nchannels", C.c_int), ("ch", C.c_void_p), ("taps", C.c_void_p), ("ntaps", C.c_int)]
 
 
+class Msg(C.Structure):
+    """struct jaero_aerol_msg: one reassembled ISU (jaero_aerol_read_msgs); jaero_amd.acars.MSG_DTYPE is the same row for numpy."""
+
+    _fields_ = [("frame", C.c_int32), ("k", C.c_int32), ("aesid", C.c_uint32), ("gesid", C.c_uint8), ("qno", C.c_uint8), ("refno", C.c_uint8),
+                ("nooct", C.c_uint8), ("nbytes", C.c_uint16), ("flags", C.c_uint16), ("mode", C.c_uint8), ("tak", C.c_uint8),
+                ("label", C.c_uint8 * 2), ("bi", C.c_uint8), ("pad", C.c_uint8 * 7), ("data", C.c_uint8 * 512)]
+
+
 class JaeroError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libjaero_hip error {code}: {msg}")
@@ -263,6 +274,9 @@ def lib():
     L.jaero_aerol_profile2_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]
     L.jaero_aerol_debug_extra_bytes.argtypes = [vp]
     L.jaero_aerol_debug_extra_bytes.restype = C.c_longlong
+    L.jaero_aerol_isu_enable.argtypes = [vp, ip]
+    L.jaero_aerol_read_msgs.argtypes = [vp, ip, vp, ip, C.POINTER(ip)]
+    L.jaero_aerol_isu_stats.argtypes = [vp, vp]
     L.jaero_read_all.argtypes = [vp, ip, vp, ip, vp, C.POINTER(ip), C.POINTER(C.c_longlong), vp]
     L.jaero_read_status_all.argtypes = [vp, vp]
     L.jaero_profile2_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]

@@ -3,6 +3,7 @@
 
 #include <mutex>
 #include "aerolc.h"
+#include "k_aerol_isu.h"
 #include "sweep_host.h"
 
 struct jaero_aerol_ctx
@@ -18,11 +19,16 @@ struct jaero_aerol_ctx
     unsigned long long *d_vhist = nullptr; // k_viterbi_lanes history scratch (large banks only)
     hipStream_t last_stream = nullptr;
     // the three kernel classes of a write: 0 = the bit walk, 1 = k_viterbi + overlap update, 2 = the end of a block / frame; 3 = the sweep's kernels
-    // (jaero_aerol_read_all), 4 = k_dcd_link (jaero_aerol_profile2_read)
-    KernelTimer timer{5};
+    // (jaero_aerol_read_all), 4 = k_dcd_link, 5 = k_aerol_isu (jaero_aerol_profile2_read)
+    KernelTimer timer{6};
     SweepBufs sweep;
     jaero_ctx *link = nullptr; // the demodulator bank whose dcd follows this bank's DataCarrierDetect emissions (jaero_aerol_link_dcd)
     int *d_dcdmark = nullptr;  // [nchp], allocated by the first link
+    // ISU / SSU reassembly (jaero_aerol_isu_enable, k_aerol_isu.h): allocated by the first enable, launched while isu_on
+    IPtrs isu{};
+    int *d_isumark = nullptr;
+    bool isu_on = false;
+    long long isu_bytes = 0;
 };
 
 extern "C" int jaero_aerol_profile_enable(jaero_aerol_ctx *c, int on)
@@ -39,7 +45,7 @@ extern "C" int jaero_aerol_profile_read(jaero_aerol_ctx *c, int which, double *t
 
 extern "C" int jaero_aerol_profile2_read(jaero_aerol_ctx *c, int which, double *total_ms, int *launches, int reset)
 {
-    if (!c || which < 0 || which > 4) return fail(JAERO_EINVAL, "jaero_aerol_profile2_read: bad arguments");
+    if (!c || which < 0 || which > 5) return fail(JAERO_EINVAL, "jaero_aerol_profile2_read: bad arguments");
     return c->timer.read(c->device, which, total_ms, launches, reset);
 }
 
@@ -403,6 +409,12 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
         if (g.packed) hipLaunchKernelGGL(k_aerol_post_packed, grid, block, 0, st, g, c->p);
         else hipLaunchKernelGGL(k_aerol_post, grid, block, 0, st, g, c->p);
         c->timer.end(pi, st);
+        if (c->isu_on)
+        {
+            pi = c->timer.begin(5, st);
+            hipLaunchKernelGGL(k_aerol_isu, grid, block, 0, st, g, c->p, c->isu);
+            c->timer.end(pi, st);
+        }
     }
     hipLaunchKernelGGL(k_aerol_end_write, grid, block, 0, st, g, c->p, dcounts);
     HIPCHK(hipGetLastError());
@@ -444,19 +456,94 @@ extern "C" int jaero_aerol_read_voice(jaero_aerol_ctx *c, int ch, uint8_t *rows,
     if (!c || !c->cchan) return fail(JAERO_EINVAL, "jaero_aerol_read_voice: not a C-channel (fb = 8400) bank");
     return aerol_read(c, "jaero_aerol_read_voice", CI_V_CNT, c->cp.voice, c->cg.v_cap, 304, ch, rows, caprows, nrows, 4);
 }
+// ------------------------------------------------------------------------------------------ ISU / SSU reassembly (k_aerol_isu.h)
+static_assert(sizeof(jaero_aerol_msg) == ISU_ROW_BYTES && ISU_ROW_BYTES % 16 == 0, "a message row is what isu_emit writes and k_sweep_gather<16> moves");
+// Checks in the header's order, all before a device is touched.
+extern "C" int jaero_aerol_isu_enable(jaero_aerol_ctx *c, int msg_capacity)
+{
+    const char *who = "jaero_aerol_isu_enable";
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (msg_capacity < 0) return fail(JAERO_EINVAL, "%s: msg_capacity < 0", who);
+    if (c->g.burst) return fail(JAERO_ENOTSUP, "%s: burst-mode bank (the R / T channel reassembly, RISUData and the T packets' units, is not on the device)", who);
+    if (c->cchan) return fail(JAERO_ENOTSUP, "%s: fb = 8400 (AeroL::DecodeC never calls ISUData)", who);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    if (msg_capacity == 0)
+    {
+        c->isu_on = false;
+        c->p.isumark = nullptr; // the log, its counts and the counters stay where they are
+        return 0;
+    }
+    const AGeom &g = c->g;
+    int rc;
+    if (!c->d_isumark)
+    {
+        DA(c->mem, c->d_isumark, g.nchp);
+        DA(c->mem, c->isu.chan, (size_t)g.nchp * ISU_CHAN_WORDS);
+        DA(c->mem, c->isu.items, (size_t)g.nchp * ISU_MAX_ITEMS * ISU_ITEM_BYTES);
+        DA(c->mem, c->isu.msg_cnt, g.nchp);
+        DA(c->mem, c->isu.stats, (size_t)g.nchp * 4);
+        c->isu_bytes = (long long)g.nchp * (2 * sizeof(int) + 4 * ISU_CHAN_WORDS + ISU_MAX_ITEMS * ISU_ITEM_BYTES + 4 * sizeof(long long));
+    }
+    if (!c->isu.log || c->isu.msg_cap != msg_capacity)
+    {
+        if (c->isu.log)
+        {
+            for (size_t k = 0; k < c->mem.ptrs.size(); k++) if (c->mem.ptrs[k] == (void *)c->isu.log) { c->mem.ptrs.erase(c->mem.ptrs.begin() + k); break; }
+            hipFree(c->isu.log);
+            c->isu_bytes -= (long long)g.nchp * c->isu.msg_cap * ISU_ROW_BYTES;
+            c->isu.log = nullptr; c->isu.msg_cap = 0;
+        }
+        if ((rc = dalloc(c->mem, &c->isu.log, (size_t)g.nchp * msg_capacity * ISU_ROW_BYTES, false))) { c->isu_on = false; c->p.isumark = nullptr; return rc; }
+        c->isu.msg_cap = msg_capacity;
+        c->isu_bytes += (long long)g.nchp * msg_capacity * ISU_ROW_BYTES;
+    }
+    // an empty list, an empty log, counters at 0 and `a` zeroed; the messages' overflow bit cleared
+    HIPCHK(hipMemset(c->d_isumark, 0, sizeof(int) * (size_t)g.nchp));
+    HIPCHK(hipMemset(c->isu.chan, 0, sizeof(uint32_t) * (size_t)g.nchp * ISU_CHAN_WORDS));
+    HIPCHK(hipMemset(c->isu.msg_cnt, 0, sizeof(int) * (size_t)g.nchp));
+    HIPCHK(hipMemset(c->isu.stats, 0, sizeof(long long) * (size_t)g.nchp * 4));
+    hipLaunchKernelGGL(k_aerol_isu_clear_overflow, dim3(g.nchp / 64), dim3(64), 0, c->last_stream, g, c->p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    c->p.isumark = c->d_isumark;
+    c->isu_on = true;
+    return 0;
+}
+extern "C" int jaero_aerol_read_msgs(jaero_aerol_ctx *c, int ch, void *rows, int caprows, int *nrows)
+{
+    const char *who = "jaero_aerol_read_msgs";
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    const int rc = drain_rows(who, c->device, c->last_stream, c->g.nch, {c->isu.log, c->isu.msg_cnt, c->isu.msg_cap, ISU_ROW_BYTES}, ch, rows, caprows, nrows);
+    return rc ? rc : report_overflow(c->p.I + (size_t)AI_OVERFLOW * c->g.nchp + ch, ISU_OVERFLOW_BIT, ch);
+}
+extern "C" int jaero_aerol_isu_stats(jaero_aerol_ctx *c, long long *stats)
+{
+    const char *who = "jaero_aerol_isu_stats";
+    if (!c || !stats) return fail(JAERO_EINVAL, "%s: null ctx / stats", who);
+    if (!c->isu.stats) return fail(JAERO_EINVAL, "%s: this bank never enabled the reassembly (jaero_aerol_isu_enable)", who);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    HIPCHK(hipMemcpy(stats, c->isu.stats, sizeof(long long) * (size_t)c->g.nch * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ jaero_aerol_read_all
-// test hook: bytes of device memory the link and the sweep have allocated for this bank so far (0 for a bank that used neither)
+// test hook: bytes of device memory the link, the sweep and the reassembly have allocated for this bank so far (0 for a bank that used none)
 extern "C" long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *c)
 {
     if (!c) return -1;
     long long n = c->d_dcdmark ? (long long)sizeof(int) * c->g.nchp : 0;
-    return n + c->sweep.bytes();
+    return n + c->sweep.bytes() + c->isu_bytes;
 }
 extern "C" int jaero_aerol_read_all(jaero_aerol_ctx *c, int what, void *rows, int caprows, int *offsets, int *nchannels_taken, long long *rows_pending,
                                     unsigned char *overflowed)
 {
     const char *who = "jaero_aerol_read_all";
-    if (what < JAERO_AEROL_SUS || what > JAERO_AEROL_VOICE) return fail(JAERO_EINVAL, "%s: what = %d is none of JAERO_AEROL_SUS / PACKETS / EVENTS / VOICE", who, what);
+    // (the message log is a class only of a bank that enabled the reassembly: with no such bank behind it, 4 is as unknown as it was before the class existed)
+    if (what < JAERO_AEROL_SUS || what > JAERO_AEROL_MESSAGES || (what == JAERO_AEROL_MESSAGES && !(c && c->isu.log)))
+        return fail(JAERO_EINVAL, "%s: what = %d is none of JAERO_AEROL_SUS / PACKETS / EVENTS / VOICE%s", who, what,
+                    what == JAERO_AEROL_MESSAGES ? " (JAERO_AEROL_MESSAGES exists on a bank that has called jaero_aerol_isu_enable)" : " / MESSAGES");
     if (caprows < 0) return fail(JAERO_EINVAL, "%s: caprows < 0", who);
     if (!offsets || !nchannels_taken) return fail(JAERO_EINVAL, "%s: null offsets / nchannels_taken", who);
     if (!rows && caprows > 0) return fail(JAERO_EINVAL, "%s: null rows with caprows > 0", who);
@@ -481,6 +568,10 @@ extern "C" int jaero_aerol_read_all(jaero_aerol_ctx *c, int what, void *rows, in
     case JAERO_AEROL_EVENTS:
         b = c->cchan ? RowBuf{c->cp.events, I + (size_t)CI_EV_CNT * nchp, c->cg.ev_cap, 3 * sizeof(long long)} : RowBuf{c->p.events, I + (size_t)AI_EV_CNT * nchp, c->g.ev_cap, 3 * sizeof(long long)};
         ovbit = 2;
+        break;
+    case JAERO_AEROL_MESSAGES: // (enabled at some time: checked with `what`)
+        b = RowBuf{c->isu.log, c->isu.msg_cnt, c->isu.msg_cap, ISU_ROW_BYTES};
+        ovbit = ISU_OVERFLOW_BIT;
         break;
     default:
         if (!c->cchan) return fail(JAERO_EINVAL, "%s: JAERO_AEROL_VOICE: not a C-channel (fb = 8400) bank", who);

@@ -10,8 +10,8 @@
 //   k_aerol_post : DelayLine dl2 (:1560), AeroLScrambler (:1563), byte packing (:1566-1578), and at the end of a frame the CRC-16
 //                  of every 12-byte signal unit with the data-carrier-detect bookkeeping (:1583-1600)
 // The three run in rounds (at most one block per channel per round) because the reference finishes a block -- including its DCD
-// update, which gates unique-word detection -- before it looks at the next soft bit.  Everything after the CRC check (message
-// names, ISU/ACARS reassembly, plane database) is text / control plane and stays on the host.
+// update, which gates unique-word detection -- before it looks at the next soft bit.  The ISU / SSU reassembly and the ACARS header behind the
+// CRC check are k_aerol_isu.h's (off unless enabled); message names, ACARS block joining and the plane database stay on the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,6 +44,7 @@ struct APtrs
     const unsigned *scrw; // the same, 32 per word (bit k of the sequence = bit k&31 of word k>>5), one spare word
     unsigned *dl2w;      // [nchp][dl2_words] the delay line as a bit ring (large banks: k_aerol_post_packed)
     int *dcdmark = nullptr; // [nchp] linked banks only (jaero_aerol_link_dcd): 2 | value of the last DataCarrierDetect emission, 0 = none
+    int *isumark = nullptr; // [nchp] banks that reassemble user data only (jaero_aerol_isu_enable): 1 = a short-frame notice since k_aerol_isu last ran
 };
 #define ALD(f) (p.I[(size_t)(f) * g.nchp + ch])
 
@@ -57,6 +58,7 @@ __device__ __forceinline__ void aerol_event(const AGeom &g, const APtrs &p, int 
     }
     else overflow |= 2;
     if (kind == 0 && p.dcdmark) p.dcdmark[ch] = 2 | (value ? 1 : 0); // every emission, logged or not (k_dcd_link)
+    if (kind == 1 && p.isumark) p.isumark[ch] = 1;                   // isudata.reset() (aerol.cpp:1997), logged or not (k_aerol_isu.h)
 }
 
 // One soft bit of AeroL::Decode for one channel, in two parts: everything up to and including the block store (part A; returns true

@@ -509,7 +509,7 @@ class BurstMskDemodulator(_SingleChannelBurstDemodulator):
 
 class AeroLBank:
     """A bank of AeroL bit pipelines (continuous P-channel path of JAERO/aerol.cpp AeroL::Decode): soft bits in, CRC-checked
-    12-byte signal units out.  Thin wrapper over jaero_aerol_ctx."""
+    12-byte signal units out and, once isu_enable is called, the ISUs reassembled from them.  Thin wrapper over jaero_aerol_ctx."""
 
     def __init__(self, nchannels: int, fb: int, device: int = 0, max_softbits_per_write: int = 1 << 16, su_capacity: int = 0,
                  burst: bool = False):
@@ -607,7 +607,8 @@ class AeroLBank:
         capi.check(self.L.jaero_aerol_link_dcd(self.h, None))
 
     # ---- one call for every channel (jaero_aerol_read_all) ----
-    _ROWS = {capi.AEROL_SUS: (np.int32, 16), capi.AEROL_PACKETS: (np.int32, 16), capi.AEROL_EVENTS: (np.int64, 3), capi.AEROL_VOICE: (np.uint8, 304)}
+    _ROWS = {capi.AEROL_SUS: (np.int32, 16), capi.AEROL_PACKETS: (np.int32, 16), capi.AEROL_EVENTS: (np.int64, 3), capi.AEROL_VOICE: (np.uint8, 304),
+             capi.AEROL_MESSAGES: (np.uint8, 544)}
 
     def read_all_raw(self, what: int, caprows: int):
         """One jaero_aerol_read_all call: (rc, offsets int32[nch + 1], rows[offsets[taken]], taken, rows_pending, overflowed bool[nch])."""
@@ -653,6 +654,34 @@ class AeroLBank:
 
     def read_voice_all(self):
         return self.read_all(capi.AEROL_VOICE)
+
+    # ---- ISU user data and ACARS headers, reassembled on the device (jaero_aerol_isu_enable) ----
+    def isu_enable(self, msg_capacity: int = 64):
+        """From the next write on every channel keeps the reference's ISUData behind its CRC-clean signal units and logs each completed ISU as
+        one jaero_aerol_msg row (jaero_amd.acars.MSG_DTYPE; acars.parse_msg reads one).  Starts from an empty list, log and counters.
+        msg_capacity = 0 switches it off again; the log stays readable.  Continuous 600 / 1200 / 10500 bps banks only."""
+        capi.check(self.L.jaero_aerol_isu_enable(self.h, int(msg_capacity)))
+
+    def read_msgs(self, channel: int, caprows: int = 256) -> np.ndarray:
+        from .acars import MSG_DTYPE
+
+        buf = np.empty(max(caprows, 1), dtype=MSG_DTYPE)
+        n = C.c_int(0)
+        capi.check(self.L.jaero_aerol_read_msgs(self.h, channel, buf.ctypes.data, caprows, C.byref(n)))
+        return buf[: n.value].copy()
+
+    def read_msgs_all(self):
+        """(offsets int32[nch + 1], rows of acars.MSG_DTYPE, overflowed bool[nch]): read_all for the message log."""
+        from .acars import MSG_DTYPE
+
+        off, rows, ovf = self.read_all(capi.AEROL_MESSAGES)
+        return off, np.ascontiguousarray(rows).view(MSG_DTYPE).reshape(-1), ovf
+
+    def isu_stats(self) -> np.ndarray:
+        """int64 [nch, 4] since isu_enable: ISU updates, SSU updates, missing SSUs, completed messages."""
+        out = np.zeros((self.nch, 4), dtype=np.int64)
+        capi.check(self.L.jaero_aerol_isu_stats(self.h, out.ctypes.data))
+        return out
 
     def tick_dcd(self) -> np.ndarray:
         out = np.zeros(self.nch, dtype=np.int32)
