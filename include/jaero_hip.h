@@ -1034,6 +1034,44 @@ int jaero_debug_burst_front_poke(jaero_ctx *ctx, int channel, int field, double 
 int jaero_debug_burst_poke_bt(jaero_ctx *ctx, int channel, long long first_abs_index, int n, const double *values);
 int jaero_debug_ev_compact(int device, const unsigned long long *masks, int ngroups, int *list_out, int *count_out);
 
+/* Test hooks: a burst bank's tracking kernel (jaero_debug_kernel_variant(ctx, 0): k_burst_oqpsk_demod<CAPSYM> or k_burst_msk_fb<CAPSYM, FIRN, LDSN>)
+ * on its own, launched by the line jaero_write launches it with; no history push, no Hilbert transform, no detector and no trident check run.
+ * The rules of the hooks above hold: all synchronise the bank first and return JAERO_EINVAL before any launch for a null ctx, a bank that is not
+ * a burst bank, a channel or a value out of range; track and track_fill mark the bank (a later jaero_write or setter returns JAERO_EHIP: set the
+ * flags first), track_geom, track_peek and track_read only read.  track_peek and track_read take a channel in [0, nchp), track's list one in
+ * [0, nchannels): a padding lane never gets a verdict, and a test has to show that what the padding lanes compute reaches no row of a channel.
+ *   jaero_debug_burst_track_geom  the lengths the tracking chain runs with, FIRN / LDSN of the instantiation the bank launches and JD_EBNO_TAIL.
+ *   jaero_debug_burst_track       ONE segment of 1 <= n <= min(maxseg, max_write_samples) samples.  Every channel of the bank, padding lanes
+ *                                 included, gets event position -1; the listed channels (distinct, any order, nlist in 0 .. nchannels) get
+ *                                 ev_pos[k] in [0, n) and verdicts[k] as their trident result, taken as given.  Then the tracking kernel with n0 =
+ *                                 the bank's sample count and first_of_write (0 / 1) as given; the count advances by n.  The kernel reads val of
+ *                                 sample m at absolute index m - D1 - D2 of the ring jaero_debug_burst_poke_cv fills.
+ *   jaero_debug_burst_track_peek  the chain's scalars of one channel.  Burst OQPSK has no fir_pos .. gcnt, mc_freq and diff_last (0), burst MSK
+ *                                 no yui, insertpre and lastmse (0 / as created).
+ *   jaero_debug_burst_track_fill  every soft row (all soft_cap entries of all nchp channels) = soft_value, every symbol row entry = sym_value:
+ *                                 before the first launch, so that a store outside the counted part of a row shows.
+ *   jaero_debug_burst_track_read  what = 0: a channel's whole soft row (caprows >= soft_cap int16); what = 1: its whole symbol log (caprows >=
+ *                                 sym_cap rows of 3 doubles), entries behind the counts included.  Events: jaero_debug_burst_front_events. */
+typedef struct jaero_burst_track_geom
+{
+    int D2, soft_cap, sym_cap, ev_cap, msema_len, win_ring, agc2_len, eb_len, startstopstart, firn, ldsn, ebno_tail;
+} jaero_burst_track_geom;
+typedef struct jaero_burst_track_state
+{
+    int startstop, cntr, yui, insertpre, nrx, soft_cnt, sym_cnt, ev_cnt, overflow, msema_pos;
+    int fir_pos, eb_pos, dly_pos, d8_pos, a1_pos, gcnt; /* burst MSK: the rings that advance only while the channel's gate is open */
+    double mse, lastmse, m2_freq, st_freq, vol_gain, eb_ebno, rot_freq, agc2_sum, eb_esum, eb_e2sum, msema_sum;
+    double mc_freq, diff_last, m2_ptr, st_ptr, stq_ptr;
+} jaero_burst_track_state;
+int jaero_debug_burst_track_geom(jaero_ctx *ctx, jaero_burst_track_geom *out);
+int jaero_debug_burst_track(jaero_ctx *ctx, int n, int first_of_write, const int *channels, const int *ev_pos, const jaero_trident_result *verdicts, int nlist);
+int jaero_debug_burst_track_peek(jaero_ctx *ctx, int channel, jaero_burst_track_state *st);
+int jaero_debug_burst_track_fill(jaero_ctx *ctx, int soft_value, double sym_value);
+int jaero_debug_burst_track_read(jaero_ctx *ctx, int channel, int what, void *rows, int caprows);
+/* k_burst_msk_center_freq between two segments of the hook above: what jaero_center_freq_changed launches for one channel in [0, nchannels) of a
+ * burst MSK bank (any other bank: JAERO_EINVAL), stamped with the bank's sample count = the next segment's first sample.  Marks the bank. */
+int jaero_debug_burst_track_center_freq(jaero_ctx *ctx, int channel, double hz);
+
 /* ------------------------------------------------------------------------------------------------ multi-GPU edge operations
  * The path shards by channel with no steady-state exchange (the reference runs its two stereo burst channels as two unrelated objects,
  * JAERO/audioburstoqpskdemodulator.cpp:8-10); the north star names two operations at the edges: fan out shared PCM, gather decoded bits.

@@ -40,6 +40,8 @@ EXPORTS = [
     "jaero_debug_burst_geom", "jaero_debug_burst_hilbert", "jaero_debug_burst_read_hist", "jaero_debug_burst_poke_cv", "jaero_debug_burst_trident",
     "jaero_debug_burst_front_geom", "jaero_debug_burst_front", "jaero_debug_burst_front_peek", "jaero_debug_burst_front_events", "jaero_debug_burst_front_poke", "jaero_debug_burst_poke_bt",
     "jaero_debug_ev_compact",
+    "jaero_debug_burst_track_geom", "jaero_debug_burst_track", "jaero_debug_burst_track_peek", "jaero_debug_burst_track_fill", "jaero_debug_burst_track_read",
+    "jaero_debug_burst_track_center_freq",
     "jaero_debug_pre8400_write", "jaero_debug_pre8400_poke", "jaero_debug_pre8400_peek", "jaero_debug_pre8400_restart", "jaero_debug_pre8400_read_ring",
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
@@ -129,6 +131,23 @@ class BurstFrontState(C.Structure):
 
     _fields_ = [(n, C.c_double) for n in ("agc_sum", "ma1_re", "ma1_im", "mav1_sum", "lastdy")] + [
         (n, C.c_int) for n in ("cntdown", "maxposcd", "tri_ptr", "ev_pos", "ev_cnt", "bt_hold")]
+
+
+class BurstTrackGeom(C.Structure):
+    """struct jaero_burst_track_geom: what jaero_debug_burst_track_geom reports."""
+
+    _fields_ = [(n, C.c_int) for n in ("D2", "soft_cap", "sym_cap", "ev_cap", "msema_len", "win_ring", "agc2_len", "eb_len", "startstopstart", "firn", "ldsn",
+                                       "ebno_tail")]
+
+
+class BurstTrackState(C.Structure):
+    """struct jaero_burst_track_state: the tracking chain's scalars of one channel (jaero_debug_burst_track_peek)."""
+
+    INTS = ("startstop", "cntr", "yui", "insertpre", "nrx", "soft_cnt", "sym_cnt", "ev_cnt", "overflow", "msema_pos", "fir_pos", "eb_pos", "dly_pos", "d8_pos",
+            "a1_pos", "gcnt")
+    DBLS = ("mse", "lastmse", "m2_freq", "st_freq", "vol_gain", "eb_ebno", "rot_freq", "agc2_sum", "eb_esum", "eb_e2sum", "msema_sum", "mc_freq", "diff_last",
+            "m2_ptr", "st_ptr", "stq_ptr")
+    _fields_ = [(n, C.c_int) for n in INTS] + [(n, C.c_double) for n in DBLS]
 
 
 class ViterbiProbe(C.Structure):
@@ -257,6 +276,12 @@ def lib():
     L.jaero_debug_burst_front_poke.argtypes = [vp, ip, ip, dp]
     L.jaero_debug_burst_poke_bt.argtypes = [vp, ip, C.c_longlong, ip, vp]
     L.jaero_debug_ev_compact.argtypes = [ip, vp, ip, vp, C.POINTER(ip)]
+    L.jaero_debug_burst_track_geom.argtypes = [vp, C.POINTER(BurstTrackGeom)]
+    L.jaero_debug_burst_track.argtypes = [vp, ip, ip, vp, vp, vp, ip]
+    L.jaero_debug_burst_track_peek.argtypes = [vp, ip, C.POINTER(BurstTrackState)]
+    L.jaero_debug_burst_track_fill.argtypes = [vp, ip, dp]
+    L.jaero_debug_burst_track_read.argtypes = [vp, ip, ip, vp, ip]
+    L.jaero_debug_burst_track_center_freq.argtypes = [vp, ip, dp]
     L.jaero_aerol_create.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_create_burst.argtypes = [ip, ip, ip, ip, ip, C.POINTER(vp)]
     L.jaero_aerol_read_packets.argtypes = [vp, ip, vp, ip, C.POINTER(ip)]

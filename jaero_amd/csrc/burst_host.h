@@ -291,11 +291,27 @@ static int burst_launch_trident(jaero_ctx *c, int grid, long long n0, hipStream_
     LAUNCHCHK("k_trident");
     return 0;
 }
+// BurstMskDemodulator::CenterFreqChangedSlot for one channel or all (channel < 0), stamped with the first sample of the write that follows
+// (jaero_center_freq_changed and jaero_debug_burst_track_center_freq)
+static int burst_launch_center_freq(jaero_ctx *c, int channel, double hz)
+{
+    const int lo = channel < 0 ? 0 : channel, n = channel < 0 ? c->o_nch : 1;
+    hipLaunchKernelGGL(k_burst_msk_center_freq, dim3((n + 63) / 64), dim3(64), 0, c->last_stream, c->bg, c->bp, lo, n, hz, (long long)c->nsamples_total);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the bank's tracking kernel on one segment (burst_write and jaero_debug_burst_track)
+static int burst_launch_demod(jaero_ctx *c, int n, long long n0, int first_of_write, hipStream_t st)
+{
+    const KernelRec<BurstDemodFn> &dm = c->bdemod;
+    hipLaunchKernelGGL(dm.fn, dim3(dm.grid), dim3(dm.block), dm.lds, st, c->bg, c->bp, n, n0, first_of_write);
+    LAUNCHCHK("the burst demodulator");
+    return 0;
+}
 
 static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layout, int is_device_ptr, hipStream_t st)
 {
     const BGeom &g = c->bg;
-    const BPtrs &p = c->bp;
     const int nch = g.nch;
     int rc = 0;
     const int16_t *dsrc = pcm;
@@ -311,7 +327,6 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         if ((rc = burst_launch_hist_push(c, dsrc, nsamples, layout, slot0, st))) return rc;
         c->timer.end(pi, st);
     }
-    const KernelRec<BurstDemodFn> &dm = c->bdemod;
     int first = 1;
     c->poisoned = true; // the history push above is idempotent (same slots if the write is repeated); from here on state advances
     for (int pos = 0; pos < nsamples;)
@@ -329,8 +344,7 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         if ((rc = burst_launch_trident(c, c->trident.grid, n0, st))) return rc;
         c->timer.end(pi, st);
         pi = c->timer.begin(0, st);
-        hipLaunchKernelGGL(dm.fn, dim3(dm.grid), dim3(dm.block), dm.lds, st, g, p, n, n0, first);
-        LAUNCHCHK("the burst demodulator");
+        if ((rc = burst_launch_demod(c, n, n0, first, st))) return rc;
         c->timer.end(pi, st);
         first = 0;
         c->nsamples_total += n;
@@ -700,5 +714,110 @@ extern "C" int jaero_debug_ev_compact(int device, const unsigned long long *mask
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(list_out, d_list, sizeof(int) * (size_t)ngroups * 64, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ test hooks: the tracking kernel alone
+// (tests/test_gpu_burst_track.py), through burst_launch_demod as burst_write calls it.  track and track_fill poison the bank; track_geom,
+// track_peek and track_read only read.  Peek and read reach the padding lanes of the last wavefront too; track's list does not.
+extern "C" int jaero_debug_burst_track_geom(jaero_ctx *c, jaero_burst_track_geom *out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_debug_burst_track_geom: null output");
+    int rc = burst_hook_enter(c, "jaero_debug_burst_track_geom", 0, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    out->D2 = g.D2; out->soft_cap = g.soft_cap; out->sym_cap = g.sym_cap; out->ev_cap = g.ev_cap; out->msema_len = g.msema_len; out->win_ring = g.win_ring;
+    out->agc2_len = g.agc2_len; out->eb_len = g.eb_len; out->startstopstart = g.startstopstart;
+    // the instantiation burst_create chose (c->bdemod)
+    if (g.kind == JAERO_KIND_BURST_OQPSK) { out->firn = 55; out->ldsn = BD_LDSN; }
+    else { out->firn = g.fir_n; out->ldsn = g.fir_n == 80 ? BMSK_FB_LDSN_80 : BMSK_FB_LDSN_160; }
+    out->ebno_tail = JD_EBNO_TAIL;
+    return 0;
+}
+extern "C" int jaero_debug_burst_track(jaero_ctx *c, int n, int first_of_write, const int *channels, const int *ev_pos, const jaero_trident_result *verdicts, int nlist)
+{
+    if (c && c->burst && (n <= 0 || n > c->bg.maxseg || n > c->max_write))
+        return fail(JAERO_EINVAL, "jaero_debug_burst_track: n %d (one segment: 1 .. min(maxseg %d, max_write_samples %d) samples)", n, c->bg.maxseg, c->max_write);
+    if (first_of_write != 0 && first_of_write != 1) return fail(JAERO_EINVAL, "jaero_debug_burst_track: first_of_write %d (0 or 1)", first_of_write);
+    int rc = burst_hook_enter(c, "jaero_debug_burst_track", 0, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    const int nch = g.nch, nchp = g.nchp;
+    if (nlist < 0 || nlist > nch || (nlist > 0 && (!channels || !ev_pos || !verdicts)))
+        return fail(JAERO_EINVAL, "jaero_debug_burst_track: nlist %d (0 .. %d channels with their event positions and verdicts)", nlist, nch);
+    std::vector<int> evp((size_t)nchp, -1);
+    for (int k = 0; k < nlist; k++)
+    {
+        const int ch = channels[k];
+        if (ch < 0 || ch >= nch || evp[(size_t)ch] >= 0)
+            return fail(JAERO_EINVAL, "jaero_debug_burst_track: entry %d (channel %d) is outside [0, %d) or listed twice", k, ch, nch);
+        if (ev_pos[k] < 0 || ev_pos[k] >= n) return fail(JAERO_EINVAL, "jaero_debug_burst_track: entry %d: event position %d outside [0, %d)", k, ev_pos[k], n);
+        evp[(size_t)ch] = ev_pos[k];
+    }
+    hipStream_t st = c->last_stream;
+    c->poisoned = true;
+    HIPCHK(hipMemcpy(c->bp.I + (size_t)BI_EV_POS * nchp, evp.data(), sizeof(int) * (size_t)nchp, hipMemcpyHostToDevice));
+    for (int k = 0; k < nlist; k++) HIPCHK(hipMemcpy(c->bp.tri + channels[k], &verdicts[k], sizeof(TriResult), hipMemcpyHostToDevice));
+    if ((rc = burst_launch_demod(c, n, c->nsamples_total, first_of_write, st))) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    c->nsamples_total += n;
+    return 0;
+}
+extern "C" int jaero_debug_burst_track_peek(jaero_ctx *c, int ch, jaero_burst_track_state *out)
+{
+    if (!out) return fail(JAERO_EINVAL, "jaero_debug_burst_track_peek: null output");
+    int rc = burst_front_enter(c, "jaero_debug_burst_track_peek", ch, false);
+    if (rc) return rc;
+    const BPtrs &p = c->bp;
+    const int nchp = c->bg.nchp;
+    memset(out, 0, sizeof *out);
+    int *q[16] = {&out->startstop, &out->cntr, &out->yui, &out->insertpre, &out->nrx, &out->soft_cnt, &out->sym_cnt, &out->ev_cnt, &out->overflow, &out->msema_pos,
+                  &out->fir_pos, &out->eb_pos, &out->dly_pos, &out->d8_pos, &out->a1_pos, &out->gcnt};
+    const int qf[16] = {BI_STARTSTOP, BI_CNTR, BI_YUI, BI_INSERTPRE, BI_NRX, BI_SOFT_CNT, BI_SYM_CNT, BI_EV_CNT, BI_OVERFLOW, BI_MSEMA_POS,
+                        BI_FIR_POS, BI_EB_POS, BI_DLY_POS, BI_D8_POS, BI_A1_POS, BI_GCNT};
+    for (int k = 0; k < 16; k++) HIPCHK(hipMemcpy(q[k], p.I + (size_t)qf[k] * nchp + ch, sizeof(int), hipMemcpyDeviceToHost));
+    double *d[16] = {&out->mse, &out->lastmse, &out->m2_freq, &out->st_freq, &out->vol_gain, &out->eb_ebno, &out->rot_freq, &out->agc2_sum, &out->eb_esum, &out->eb_e2sum,
+                     &out->msema_sum, &out->mc_freq, &out->diff_last, &out->m2_ptr, &out->st_ptr, &out->stq_ptr};
+    const int df[16] = {BS_MSE, BS_LASTMSE, BS_M2_FREQ, BS_ST_FREQ, BS_VOL_GAIN, BS_EB_EBNO, BS_ROT_FREQ, BS_AGC2_SUM, BS_EB_ESUM, BS_EB_E2SUM,
+                        BS_MSEMA_SUM, BS_MC_FREQ, BS_DIFF_LAST, BS_M2_PTR, BS_ST_PTR, BS_STQ_PTR};
+    for (int k = 0; k < 16; k++) HIPCHK(hipMemcpy(d[k], p.S + (size_t)df[k] * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int jaero_debug_burst_track_fill(jaero_ctx *c, int soft_value, double sym_value)
+{
+    if (soft_value < -32768 || soft_value > 32767) return fail(JAERO_EINVAL, "jaero_debug_burst_track_fill: soft value %d is no int16", soft_value);
+    int rc = burst_hook_enter(c, "jaero_debug_burst_track_fill", 0, true);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    std::vector<int16_t> soft((size_t)g.nchp * g.soft_cap, (int16_t)soft_value);
+    HIPCHK(hipMemcpy(c->bp.soft, soft.data(), sizeof(int16_t) * soft.size(), hipMemcpyHostToDevice));
+    if (g.sym_cap)
+    {
+        std::vector<double> sym((size_t)g.nchp * g.sym_cap * 3, sym_value);
+        HIPCHK(hipMemcpy(c->bp.sym, sym.data(), sizeof(double) * sym.size(), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+extern "C" int jaero_debug_burst_track_read(jaero_ctx *c, int ch, int what, void *rows, int caprows)
+{
+    if (!rows || (what != 0 && what != 1)) return fail(JAERO_EINVAL, "jaero_debug_burst_track_read: null output or what %d (0 soft row, 1 symbol rows)", what);
+    int rc = burst_front_enter(c, "jaero_debug_burst_track_read", ch, false);
+    if (rc) return rc;
+    const BGeom &g = c->bg;
+    const int need = what == 0 ? g.soft_cap : g.sym_cap;
+    if (caprows < need) return fail(JAERO_EINVAL, "jaero_debug_burst_track_read: room for %d rows, the channel's whole log has %d", caprows, need);
+    if (what == 0) HIPCHK(hipMemcpy(rows, c->bp.soft + (size_t)ch * g.soft_cap, sizeof(int16_t) * (size_t)g.soft_cap, hipMemcpyDeviceToHost));
+    else if (g.sym_cap) HIPCHK(hipMemcpy(rows, c->bp.sym + (size_t)ch * g.sym_cap * 3, sizeof(double) * 3 * (size_t)g.sym_cap, hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int jaero_debug_burst_track_center_freq(jaero_ctx *c, int ch, double hz)
+{
+    if (!std::isfinite(hz)) return fail(JAERO_EINVAL, "jaero_debug_burst_track_center_freq: the frequency is not finite");
+    int rc = burst_hook_enter(c, "jaero_debug_burst_track_center_freq", ch, false);
+    if (rc) return rc;
+    if (c->bg.kind != JAERO_KIND_BURST_MSK) return fail(JAERO_EINVAL, "jaero_debug_burst_track_center_freq: not a burst MSK bank (burst OQPSK's slot is empty)");
+    c->poisoned = true;
+    if ((rc = burst_launch_center_freq(c, ch, hz))) return rc;
+    HIPCHK(hipStreamSynchronize(c->last_stream));
     return 0;
 }

@@ -910,10 +910,7 @@ extern "C" int jaero_center_freq_changed(jaero_ctx *c, int channel, double hz)
         // BurstOqpskDemodulator::CenterFreqChangedSlot does nothing (burstoqpskdemodulator.cpp:284-289)
         if (c->bg.kind == JAERO_KIND_BURST_OQPSK) return 0;
         // BurstMskDemodulator::CenterFreqChangedSlot (burstmskdemodulator.cpp:327-342), on the bank's stream like every other call
-        const int lo = channel < 0 ? 0 : channel, n = channel < 0 ? c->o_nch : 1;
-        hipLaunchKernelGGL(k_burst_msk_center_freq, dim3((n + 63) / 64), dim3(64), 0, c->last_stream, c->bg, c->bp, lo, n, hz, (long long)c->nsamples_total);
-        HIPCHK(hipGetLastError());
-        return 0;
+        return burst_launch_center_freq(c, channel, hz);
     }
     const int lo = channel < 0 ? 0 : channel, n = channel < 0 ? c->g.nch : 1;
     hipLaunchKernelGGL(k_center_freq, dim3(n), dim3(256), 0, c->last_stream, c->g, c->p, lo, n, hz);

@@ -140,6 +140,14 @@ void jo_burst_front_geom(jo_burst *d, double *out8);
 long jo_burst_front_exact(jo_burst *geom, const double *re_im, long n, long double *rows, long hold_at, int hold, double *info, long *trig, long trigcap);
 int jo_peakdet_run(int length, double threshold, const double *history, int cntdown, double lastdy, int maxposcntdown, const double *values, long n,
                    int *fire, int *maxpos, double *state_out);
+/* The tracking chain alone (jaero_oracle_burst.c): the per-sample bodies the writers run behind the front end on supplied val_to_demod, a
+ * supplied verdict applied in front of sample ev_at (-1: none); the recorder that takes both from an ordinary jo_burst_write; the scalars. */
+void jo_burst_record(jo_burst *d, int on);
+void jo_burst_coverage(jo_burst *d, long *out6); /* clip, ct_ec clamp, squelch drop, yui correction even / odd, time-out: times taken */
+long jo_burst_take_recorded_val(jo_burst *d, double *dst, long cap);
+long jo_burst_take_recorded_verdicts(jo_burst *d, double *dst, long caprows); /* rows of 6 doubles: sample, then a jo_trident_result */
+long jo_burst_track_write(jo_burst *d, const double *val, long n, const jo_trident_result *verdict, long ev_at);
+void jo_burst_track_state(jo_burst *d, long *ints8_96, double *dbl14);
 int jo_hilbert_kernel(int N, double *re_im);
 typedef struct jo_hilbert jo_hilbert;
 jo_hilbert *jo_hilbert_create(int N);

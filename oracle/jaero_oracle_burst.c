@@ -232,6 +232,8 @@ struct jo_burst
     short rx[96]; int nrx;
     gbuf soft, events, symbols, triwin; /* triwin: with trace on, the window of every trident check (tridentbuffer_sz doubles each) */
     int capture_symbols, trace;
+    long cov[6]; /* jo_burst_coverage: branches of the tracking chain taken so far */
+    int record; gbuf rec_val, rec_verdict; /* jo_burst_record: val_to_demod of every sample; rows {sample, jo_trident_result} of every trident check */
 };
 typedef struct jo_burst jo_burst;
 
@@ -364,11 +366,16 @@ static void boqpsk_trident_signal(jo_burst *d, jo_trident_result *r)
     r->metric = maxval;
 }
 
-static void boqpsk_trident_check(jo_burst *d, long sample) /* burstoqpskdemodulator.cpp:412-515 */
+static void burst_record_verdict(jo_burst *d, const jo_trident_result *r, long sample)
 {
-    jo_trident_result r;
-    boqpsk_trident_signal(d, &r);
-    if (d->trace) gpush(&d->triwin, d->tridentbuffer, sizeof(double) * (size_t)d->tridentbuffer_sz);
+    double at = (double)sample;
+    gpush(&d->rec_verdict, &at, sizeof at);
+    gpush(&d->rec_verdict, r, sizeof *r);
+}
+/* the part of the trident check that applies a result (:473-515); jo_burst_track_write calls it with a verdict the caller supplies */
+static void boqpsk_trident_apply(jo_burst *d, const jo_trident_result *rp, long sample)
+{
+    const jo_trident_result r = *rp;
     const int ok = r.ok;
     const double maxval = r.metric;
     if (d->trace) burst_event(d, sample, JO_EV_TRIDENT, ok ? maxval : -maxval);
@@ -395,6 +402,14 @@ static void boqpsk_trident_check(jo_burst *d, long sample) /* burstoqpskdemodula
         d->mse = 0;
         ma_zero(d->msema);
     }
+}
+static void boqpsk_trident_check(jo_burst *d, long sample) /* burstoqpskdemodulator.cpp:412-515 */
+{
+    jo_trident_result r;
+    boqpsk_trident_signal(d, &r);
+    if (d->trace) gpush(&d->triwin, d->tridentbuffer, sizeof(double) * (size_t)d->tridentbuffer_sz);
+    if (d->record) burst_record_verdict(d, &r, sample);
+    boqpsk_trident_apply(d, &r, sample);
 }
 
 static cpx cexp_i(double x) /* std::exp(imag*x): real part of the argument is +-0 -> exp()=1 */
@@ -424,14 +439,13 @@ static void burst_front_end(jo_burst *d, cpx *cvalp, cpx *cval_d_out, double *va
     *cvalp = cval; *cval_d_out = cval_d; *val_to_demod_out = val_to_demod;
 }
 
+static void boqpsk_track_sample(jo_burst *d, long sample, double val_to_demod, double lastmse);
 static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskdemodulator.cpp:315-737 (mono) */
 {
     double lastmse = d->mse;
     if (n > d->hfircap) { d->hfircap = n; d->hfirbuff = (cpx *)realloc(d->hfirbuff, sizeof(cpx) * (size_t)n); }
     for (long i = 0; i < n; i++) { d->hfirbuff[i].re = ((double)ptr[i]) / 32768.0; d->hfirbuff[i].im = 0; }
     fastfir_update(&d->hfir, d->hfirbuff, n);
-    const double SPS = d->SamplesPerSymbol;
-    const cpx imag = {0, 1};
     for (long i = 0; i < n; i++)
     {
         const long sample = d->nsamples_total + i;
@@ -440,7 +454,17 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
         if (fire) { d->tridentbuffer_ptr = 0; if (d->trace) burst_event(d, sample, JO_EV_PEAK, 0); }
         if (d->tridentbuffer_ptr < d->tridentbuffer_sz) { d->tridentbuffer[d->tridentbuffer_ptr] = cval_d.re; d->tridentbuffer_ptr++; }
         else if (d->tridentbuffer_ptr == d->tridentbuffer_sz) { d->tridentbuffer_ptr++; boqpsk_trident_check(d, sample); }
-
+        if (d->record) gpush(&d->rec_val, &val_to_demod, sizeof val_to_demod);
+        boqpsk_track_sample(d, sample, val_to_demod, lastmse);
+    }
+    d->nsamples_total += n;
+}
+/* the per-sample body behind the front end (:517-733) */
+static void boqpsk_track_sample(jo_burst *d, long sample, double val_to_demod, double lastmse)
+{
+    const double SPS = d->SamplesPerSymbol;
+    const cpx imag = {0, 1};
+    {
         /* mix + rrc :517-521 */
         cpx cval_dd = cscale(wt_cis(&d->mixer2), (d->vol_gain * val_to_demod));
         cpx sig2;
@@ -454,7 +478,7 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
             if (d->cntr < 1000000) d->cntr++;
             if (d->mse < 0.75) d->startstop = d->startstopstart;
         }
-        if (d->startstop == 0) { d->startstop--; burst_event(d, sample, JO_EV_SIGNAL, 0.0); }
+        if (d->startstop == 0) { d->startstop--; burst_event(d, sample, JO_EV_SIGNAL, 0.0); d->cov[5]++; }
         if ((d->cntr > ((256 - 10) * SPS)) && d->insertpreamble) { d->rx[d->nrx++] = -1; d->insertpreamble = 0; }
 
         /* symbol tone in preamble :547-566 */
@@ -485,7 +509,7 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
         if (fabs(d->cntr - ((128.0 + 128.0 + 128.0) * SPS)) < 0.5) burst_event(d, sample, JO_EV_EBNO, d->ebno.EbNo);
         sig2 = cscale(sig2, agc_update(d->agc2, sig2abs));
         double abval = hypot(sig2.re, sig2.im);
-        if (abval > 2.84) sig2 = cscale(sig2, (2.84 / abval)); /* (2.84/abval)*sig2 */
+        if (abval > 2.84) { sig2 = cscale(sig2, (2.84 / abval)); d->cov[0]++; } /* (2.84/abval)*sig2 */
 
         /* symbol timer :592-612 */
         double st_diff = delay_update(&d->delays, abval * abval) - (abval * abval);
@@ -519,7 +543,7 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
             d->yui++; d->yui %= 2;
             if (d->cntr < ((128 + 128) * SPS))
             {
-                if ((even && d->yui == 1) || (!even && d->yui == 0)) { d->yui++; d->yui %= 2; }
+                if ((even && d->yui == 1) || (!even && d->yui == 0)) { d->yui++; d->yui %= 2; d->cov[even ? 3 : 4]++; }
             }
             if (!d->yui) d->pt_d = pt;
             else
@@ -530,8 +554,8 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
                 double ct_ec = ct_xt_d - ct_xt;
                 if (ct_ec > M_PI) ct_ec = M_PI;
                 if (ct_ec < -M_PI) ct_ec = -M_PI;
-                if (ct_ec > M_PI_2) ct_ec = M_PI_2;
-                if (ct_ec < -M_PI_2) ct_ec = -M_PI_2;
+                if (ct_ec > M_PI_2) { ct_ec = M_PI_2; d->cov[1]++; }
+                if (ct_ec < -M_PI_2) { ct_ec = -M_PI_2; d->cov[1]++; }
                 if (d->cntr > ((128 + 10) * SPS))
                 {
                     d->rotator = cmul(d->rotator, cexp_i(ct_ec * 0.1));
@@ -558,6 +582,7 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
                     if (d->nrx >= 32)
                     {
                         if (!d->sql || d->mse < d->signalthreshold || lastmse < d->signalthreshold) burst_emit_soft(d);
+                        else d->cov[2]++;
                         d->nrx = 0;
                     }
                 }
@@ -569,7 +594,6 @@ static void boqpsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstoqpskd
         wt_next(&d->st_osc_ref);
         wt_next(&d->st_osc_quarter);
     }
-    d->nsamples_total += n;
 }
 
 /* ---------------- burst MSK ---------------- */
@@ -738,12 +762,11 @@ static void bmsk_trident_signal(jo_burst *d, jo_trident_result *r)
     r->metric = minval;
 }
 
-static void bmsk_trident_check(jo_burst *d, long sample) /* burstmskdemodulator.cpp:444-569 */
+/* the part of the trident check that applies a result (:512-568), with the acceptance terms that depend on the demodulator's state */
+static void bmsk_trident_apply(jo_burst *d, const jo_trident_result *rp, long sample)
 {
     const double SPS = d->SamplesPerSymbol;
-    jo_trident_result r;
-    bmsk_trident_signal(d, &r);
-    if (d->trace) gpush(&d->triwin, d->tridentbuffer, sizeof(double) * (size_t)d->tridentbuffer_sz);
+    const jo_trident_result r = *rp;
     const double minval = r.metric;
     int ok = (r.ok && !(d->dcd) && !(d->cntr > 0 && d->cntr < (500 * SPS)));
     if (d->trace) burst_event(d, sample, JO_EV_TRIDENT, ok ? minval : -minval);
@@ -773,14 +796,21 @@ static void bmsk_trident_check(jo_burst *d, long sample) /* burstmskdemodulator.
         wt_set_phase_deg(&d->st_osc_half, 0);
     }
 }
+static void bmsk_trident_check(jo_burst *d, long sample) /* burstmskdemodulator.cpp:444-569 */
+{
+    jo_trident_result r;
+    bmsk_trident_signal(d, &r);
+    if (d->trace) gpush(&d->triwin, d->tridentbuffer, sizeof(double) * (size_t)d->tridentbuffer_sz);
+    if (d->record) burst_record_verdict(d, &r, sample);
+    bmsk_trident_apply(d, &r, sample);
+}
 
+static void bmsk_track_sample(jo_burst *d, long sample, double val_to_demod);
 static void bmsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstmskdemodulator.cpp:371-754 */
 {
     if (n > d->hfircap) { d->hfircap = n; d->hfirbuff = (cpx *)realloc(d->hfirbuff, sizeof(cpx) * (size_t)n); }
     for (long i = 0; i < n; i++) { d->hfirbuff[i].re = ((double)ptr[i]) / 32768.0; d->hfirbuff[i].im = 0; }
     fastfir_update(&d->hfir, d->hfirbuff, n);
-    const double SPS = d->SamplesPerSymbol;
-    const cpx imag = {0, 1};
     for (long i = 0; i < n; i++)
     {
         const long sample = d->nsamples_total + i;
@@ -789,7 +819,18 @@ static void bmsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstmskdemod
         if (fire) { d->tridentbuffer_ptr = 0; if (d->trace) burst_event(d, sample, JO_EV_PEAK, 0); }
         if (d->tridentbuffer_ptr < d->tridentbuffer_sz) { d->tridentbuffer[d->tridentbuffer_ptr] = cval_d.re; d->tridentbuffer_ptr++; }
         else if (d->tridentbuffer_ptr == d->tridentbuffer_sz) { d->tridentbuffer_ptr++; bmsk_trident_check(d, sample); }
-
+        if (d->record) gpush(&d->rec_val, &val_to_demod, sizeof val_to_demod);
+        bmsk_track_sample(d, sample, val_to_demod);
+    }
+    d->nsamples_total += n;
+}
+/* the per-sample body behind the front end (:571-745) */
+static void bmsk_track_sample(jo_burst *d, long sample, double val_to_demod)
+{
+    const double SPS = d->SamplesPerSymbol;
+    const cpx imag = {0, 1};
+    cpx cval;
+    {
         /* sample counting :572-598 */
         if (d->startstop > 0)
         {
@@ -801,6 +842,7 @@ static void bmsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstmskdemod
         {
             d->startstop--;
             burst_event(d, sample, JO_EV_SIGNAL, 0.0);
+            d->cov[5]++;
             d->cntr = 0;
             d->mse = 1;
         }
@@ -836,7 +878,7 @@ static void bmsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstmskdemod
             if (d->cntr == d->endRotation + (200 * SPS)) burst_event(d, sample, JO_EV_EBNO, d->ebno.EbNo);
             sig2 = cscale(sig2, agc_update(d->agc2, hypot(sig2.re, sig2.im)));
             double abval = hypot(sig2.re, sig2.im);
-            if (abval > 2.84) sig2 = cscale(sig2, (2.84 / abval));
+            if (abval > 2.84) { sig2 = cscale(sig2, (2.84 / abval)); d->cov[0]++; }
             cpx pt_d = delaything_update_dont_touch(&d->delayedsmpl, sig2);
             cpx pt_msk; pt_msk.re = sig2.re; pt_msk.im = pt_d.im;
             double st_eta = hypot(pt_msk.re, pt_msk.im);
@@ -852,8 +894,8 @@ static void bmsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstmskdemod
                 double ct_ec = ct_xt_d - ct_xt;
                 if (ct_ec > M_PI) ct_ec = M_PI;
                 if (ct_ec < -M_PI) ct_ec = -M_PI;
-                if (ct_ec > M_PI_2) ct_ec = M_PI_2;
-                if (ct_ec < -M_PI_2) ct_ec = -M_PI_2;
+                if (ct_ec > M_PI_2) { ct_ec = M_PI_2; d->cov[1]++; }
+                if (ct_ec < -M_PI_2) { ct_ec = -M_PI_2; d->cov[1]++; }
                 if (d->cntr > (d->startProcessing * SPS))
                 {
                     d->rotator = cmul(d->rotator, cexp_i(ct_ec * 0.25));
@@ -885,7 +927,6 @@ static void bmsk_write(jo_burst *d, const int16_t *ptr, long n) /* burstmskdemod
             wt_next(&d->mixer_center);
         }
     }
-    d->nsamples_total += n;
 }
 
 /* ---------------- public API ---------------- */
@@ -909,7 +950,7 @@ void jo_burst_destroy(jo_burst *d)
     fir_free(d->fir_re); fir_free(d->fir_im);
     ma_free(d->ebno.E); ma_free(d->ebno.E2); ma_free(d->msema); ma_free(d->pointmean);
     free(d->delayedsmpl.buffer);
-    free(d->soft.p); free(d->events.p); free(d->symbols.p); free(d->triwin.p);
+    free(d->soft.p); free(d->events.p); free(d->symbols.p); free(d->triwin.p); free(d->rec_val.p); free(d->rec_verdict.p);
     free(d);
 }
 /* setSettings on the LIVE object (a user pressing OK in the settings dialog): the same functions the constructor path runs -- new AGCs, EbNo
@@ -970,6 +1011,53 @@ int jo_trident(int kind, double Fs, double fb, const double *window, int tri_sz,
     free(d->tridentbuffer); fft_free(d->fftr); free(d->out_base); free(d->out_top); free(d->out_abs_diff); free(d->in);
     free(d);
     return 0;
+}
+
+/* ------------------------------------------------------------------ the tracking chain alone (tests/burst_track_cases.py)
+ * jo_burst_record(d, 1): every following jo_burst_write keeps val_to_demod of each sample and {sample, result} of each trident check;
+ * jo_burst_take_recorded_val / _verdicts hand them out (verdict rows: 1 + sizeof(jo_trident_result) / 8 doubles).
+ * jo_burst_track_write: boqpsk_track_sample / bmsk_track_sample, the bodies the writers run behind the front end, on val_to_demod the caller
+ * supplies; the verdict (may be NULL with ev_at = -1) is applied in front of sample ev_at as the writers apply the result of their own check.
+ * lastmse = mse is taken once per call, as a write takes it.  No front end runs: the trident buffer, the Hilbert filter and the AGC stay idle. */
+void jo_burst_record(jo_burst *d, int on) { d->record = on; }
+/* how often so far: 0 the loop clipped (abval > 2.84), 1 ct_ec reached its clamp, 2 the squelch dropped a group, 3 / 4 the preamble's yui correction on an
+ * even / odd instant, 5 the signal timed out */
+void jo_burst_coverage(jo_burst *d, long *out6) { for (int k = 0; k < 6; k++) out6[k] = d->cov[k]; }
+long jo_burst_take_recorded_val(jo_burst *d, double *dst, long cap) { return gtake(&d->rec_val, dst, sizeof(double), cap); }
+long jo_burst_take_recorded_verdicts(jo_burst *d, double *dst, long caprows) { return gtake(&d->rec_verdict, dst, sizeof(double) + sizeof(jo_trident_result), caprows); }
+long jo_burst_track_write(jo_burst *d, const double *val, long n, const jo_trident_result *verdict, long ev_at)
+{
+    if (n <= 0 || !val || ev_at < -1 || ev_at >= n || (ev_at >= 0 && !verdict)) return -1;
+    const double lastmse = d->mse;
+    for (long i = 0; i < n; i++)
+    {
+        const long sample = d->nsamples_total;
+        if (d->kind == JO_KIND_BURST_OQPSK)
+        {
+            if (i == ev_at) boqpsk_trident_apply(d, verdict, sample);
+            boqpsk_track_sample(d, sample, val[i], lastmse);
+        }
+        else
+        {
+            if (i == ev_at) bmsk_trident_apply(d, verdict, sample);
+            bmsk_track_sample(d, sample, val[i]);
+        }
+        d->nsamples_total++;
+    }
+    return n;
+}
+/* the tracking chain's scalars.  ints: startstop, cntr, yui, insertpreamble, nrx, msema.ptr, samples consumed, the pending RxDataBits entries
+ * rx[0 .. nrx) from ints[8] on (ints has room for 8 + 96); doubles: mse, mixer2.freq, st_osc.freq, vol_gain, ebno.EbNo, rotator_freq, agc2's sum,
+ * the EbNo meter's E and E2 sums, msema's sum, mixer_center.freq, mixer2's, st_osc's and the quarter / half oscillator's table pointers (14). */
+void jo_burst_track_state(jo_burst *d, long *ints, double *dbl)
+{
+    ints[0] = d->startstop; ints[1] = d->cntr; ints[2] = d->yui; ints[3] = d->insertpreamble; ints[4] = d->nrx; ints[5] = d->msema->ptr;
+    ints[6] = d->nsamples_total; ints[7] = 0;
+    for (int k = 0; k < d->nrx; k++) ints[8 + k] = d->rx[k];
+    dbl[0] = d->mse; dbl[1] = d->mixer2.freq; dbl[2] = d->st_osc.freq; dbl[3] = d->vol_gain; dbl[4] = d->ebno.EbNo; dbl[5] = d->rotator_freq;
+    dbl[6] = d->agc2->sum; dbl[7] = d->ebno.E->sum; dbl[8] = d->ebno.E2->sum; dbl[9] = d->msema->sum;
+    dbl[10] = d->kind == JO_KIND_BURST_MSK ? d->mixer_center.freq : 0.0;
+    dbl[11] = d->mixer2.WTptr; dbl[12] = d->st_osc.WTptr; dbl[13] = d->kind == JO_KIND_BURST_MSK ? d->st_osc_half.WTptr : d->st_osc_quarter.WTptr;
 }
 
 typedef struct jo_hilbert { fastfir_t f; } jo_hilbert;

@@ -506,6 +506,66 @@ class BurstDemod:
         self._front_protos().jo_burst_front_geom(self.h, out.ctypes.data)
         return dict(zip(self.FRONT_GEOM, (float(v) for v in out)))
 
+    # ---- the tracking chain alone (jaero_oracle_burst.c: jo_burst_track_*, jo_burst_record) ----
+    TRACK_INTS = ("startstop", "cntr", "yui", "insertpre", "nrx", "msema_pos", "nsamples")
+    TRACK_DBLS = ("mse", "m2_freq", "st_freq", "vol_gain", "eb_ebno", "rot_freq", "agc2_sum", "eb_esum", "eb_e2sum", "msema_sum", "mc_freq",
+                  "m2_ptr", "st_ptr", "stq_ptr")
+
+    def _track_protos(self):
+        L = self.L
+        L.jo_burst_record.restype = None
+        L.jo_burst_record.argtypes = [C.c_void_p, C.c_int]
+        for name in ("jo_burst_take_recorded_val", "jo_burst_take_recorded_verdicts"):
+            getattr(L, name).restype = C.c_long
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+        L.jo_burst_track_write.restype = C.c_long
+        L.jo_burst_track_write.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long]
+        L.jo_burst_track_state.restype = None
+        L.jo_burst_track_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        return L
+
+    def record(self, on=True):
+        """Keep val_to_demod of every sample and the result of every trident check of the writes that follow."""
+        self._track_protos().jo_burst_record(self.h, int(on))
+
+    def take_recorded(self):
+        """(val_to_demod [n], verdicts: list of (sample, TridentResult)) recorded since the last call."""
+        L = self._track_protos()
+        val = _drain(L.jo_burst_take_recorded_val, self.h, 1, np.float64, 1 << 16)
+        rows = _drain(L.jo_burst_take_recorded_verdicts, self.h, 6, np.float64, 256)
+        out = []
+        for r in rows:
+            t = TridentResult.from_buffer_copy(r[1:].tobytes())
+            out.append((int(r[0]), t))
+        return val, out
+
+    def track_write(self, val: np.ndarray, verdict=None, ev_at: int = -1):
+        """The tracking chain on val_to_demod `val`; `verdict` (a TridentResult) is applied in front of sample ev_at of this call."""
+        val = np.ascontiguousarray(val, dtype=np.float64)
+        assert (verdict is None) == (ev_at < 0)
+        rc = self._track_protos().jo_burst_track_write(self.h, val.ctypes.data, len(val), None if verdict is None else C.addressof(verdict), int(ev_at))
+        assert rc == len(val), rc
+
+    COVERAGE = ("clip", "clamp", "squelch_drop", "yui_even", "yui_odd", "timeout")
+
+    def coverage(self) -> dict:
+        """How often each of these branches of the tracking chain was taken so far."""
+        out = np.zeros(6, dtype=np.int64)
+        self.L.jo_burst_coverage.restype = None
+        self.L.jo_burst_coverage.argtypes = [C.c_void_p, C.c_void_p]
+        self.L.jo_burst_coverage(self.h, out.ctypes.data)
+        return {k: int(v) for k, v in zip(self.COVERAGE, out)}
+
+    def track_state(self) -> dict:
+        """The chain's scalars (TRACK_INTS, TRACK_DBLS) and `rx`, the pending RxDataBits entries."""
+        assert C.sizeof(C.c_long) == 8
+        ints, dbl = np.zeros(8 + 96, dtype=np.int64), np.zeros(len(self.TRACK_DBLS))
+        self._track_protos().jo_burst_track_state(self.h, ints.ctypes.data, dbl.ctypes.data)
+        st = {k: int(v) for k, v in zip(self.TRACK_INTS, ints)}
+        st.update({k: float(v) for k, v in zip(self.TRACK_DBLS, dbl)})
+        st["rx"] = ints[8:8 + st["nrx"]].astype(np.int16)
+        return st
+
     @property
     def pending(self):
         return self.L.jo_burst_pending_soft(self.h)

@@ -120,6 +120,28 @@ def test_burst_front_hooks_refuse_a_null_context():
     assert L.jaero_debug_ev_compact(0, masks, 1, None, C.byref(n)) == capi.E_INVAL and L.jaero_debug_ev_compact(0, masks, 1, idx, None) == capi.E_INVAL
 
 
+def test_burst_track_hooks_refuse_a_null_context():
+    """jaero_debug_burst_track_geom / _track / _track_peek / _track_fill / _track_read: JAERO_EINVAL before any HIP call, and the argument checks
+    that need no bank (the rest: tests/test_gpu_burst_track.py)."""
+    L = capi.lib()
+    assert C.sizeof(capi.BurstTrackGeom) == 48 and C.sizeof(capi.BurstTrackState) == 192  # 12 ints; 16 ints + 16 doubles
+    buf = (C.c_double * 64)()
+    idx = (C.c_int * 4)()
+    res = (capi.TridentResult * 4)()
+    st = capi.BurstTrackState()
+    st.cntr = 7
+    for name, args in (("jaero_debug_burst_track_geom", (C.byref(capi.BurstTrackGeom()),)), ("jaero_debug_burst_track", (1, 1, idx, idx, res, 1)),
+                       ("jaero_debug_burst_track_peek", (0, C.byref(st))), ("jaero_debug_burst_track_fill", (-2, -2.0)),
+                       ("jaero_debug_burst_track_read", (0, 0, buf, 64)), ("jaero_debug_burst_track_center_freq", (0, 1000.0))):
+        assert getattr(L, name)(None, *args) == capi.E_INVAL, name
+        assert name.encode() in L.jaero_last_error(), name
+    assert st.cntr == 7
+    assert L.jaero_debug_burst_track_geom(None, None) == capi.E_INVAL and L.jaero_debug_burst_track_peek(None, 0, None) == capi.E_INVAL
+    assert L.jaero_debug_burst_track(None, 1, 2, idx, idx, res, 1) == capi.E_INVAL and b"first_of_write" in L.jaero_last_error()
+    assert L.jaero_debug_burst_track_fill(None, 40000, 0.0) == capi.E_INVAL and b"int16" in L.jaero_last_error()
+    assert L.jaero_debug_burst_track_read(None, 0, 2, buf, 64) == capi.E_INVAL and L.jaero_debug_burst_track_read(None, 0, 0, None, 64) == capi.E_INVAL
+
+
 def test_viterbi_probe_refuses_what_the_kernels_do_not_implement():
     """jaero_debug_viterbi: JAERO_EINVAL before any HIP call for the combinations neither kernel implements (the launches themselves:
     tests/test_gpu_viterbi_modes.py).  A probe that passes these checks gets as far as the device (JAERO_ENODEV here, 0 on a GPU)."""
