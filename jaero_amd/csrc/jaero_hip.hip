@@ -26,7 +26,7 @@
 #include "k_msk_fb.h"
 #include "k_pre8400.h"
 #include "k_coarse.h"
-#include "k_coarse2.h"
+#include "wg_fft.h"
 #include "k_coarse6.h"
 #include "k_viterbi.h"
 #include "k_viterbi_lanes.h"

@@ -4,9 +4,7 @@
 #pragma once
 #include "burst_device.h"
 #include "jaero_device.h"
-#include "k_coarse2.h"
-#include "k_coarse6.h" // wg_fft13_e32
-#include "k_pre8400.h" // pf_fft4096
+#include "wg_fft.h" // pf_fft4096, wg_fft13_e32
 
 #define BLDF(f) (p.S[(size_t)(f) * nchp + ch])
 #define BLDI(f) (p.I[(size_t)(f) * nchp + ch])
@@ -25,7 +23,7 @@ __device__ __forceinline__ size_t hb_idx(int slot, int nchp, int ch) { return ((
 //   (c = tid & 3, T = tid >> 2) serves channels ch0 + 2c, ch0 + 2c + 1: the four c of a T read one whole 64-byte history cell row
 //   (8 channels x 4 samples) and write 64 contiguous bytes of him.
 //   Block: outputs m0 .. m0 + 2047 (m0 an absolute multiple of 2048) = window indices 2048 .. 4095 of x[m0 - L - 2048 .. m0 - L + 2047]
-//   convolved with g (2048 taps): im y[m] = sum_k g[k] x[m - L - k].  4096-point transforms: pf_fft4096 (k_pre8400.h).
+//   convolved with g (2048 taps): im y[m] = sum_k g[k] x[m - L - k].  4096-point transforms: pf_fft4096 (wg_fft.h).
 // 1.4 ms per 2048-sample segment of 65 536 channels against 8.9 ms for the direct form it replaced.  Not
 // bit-identical to the direct form (other summation order: ~1e-15 of full scale), nor to the reference's transform.
 __global__ __launch_bounds__(PF_THREADS) void k_hilbert_fft(const BGeom g, const BPtrs p, int ns, long long n0)
@@ -328,7 +326,7 @@ __global__ __launch_bounds__(1024) void k_ev_compact(const unsigned long long *_
 // ------------------------------------------------------------------------------------------------ trident check
 // The two fftr->transform calls (burstoqpskdemodulator.cpp:416-426, burstmskdemodulator.cpp:458-473) are 2^15-point FFTs of
 // <= 2^14 real samples followed by zeros.  X[2q + r] = sum_n (x[n] W_32768^(n r)) W_16384^(n q): two 2^14-point transforms per
-// window, run register-resident with wg_fft<14> (k_coarse2.h).  Only bins below N/2 are ever read by the reference.
+// window, run register-resident (wg_fft.h; as four 2^13-point transforms since round 4, below).  Only bins below N/2 are ever read by the reference.
 #define TRI_N 32768
 #define TRI_H 16384
 
@@ -367,7 +365,7 @@ __device__ __forceinline__ void tri_argmax_first(double &v, int &idx, double *re
 //     LDS (32 KiB behind the exchange buffer) and are searched at once.
 //   burst MSK: d = |top| and the two searches are per-bin conditions around the strongest base bin: four base passes, the reduction, four top
 //     passes whose candidates are tracked on the fly.  Nothing is stored at all.
-// Round 4: 256 threads x 32 points on wg_fft13_e32 (k_coarse6.h: 32 x 16 x 16, two exchanges, natural order in and out) instead of 512 x 16
+// Round 4: 256 threads x 32 points on wg_fft13_e32 (wg_fft.h: 32 x 16 x 16, two exchanges, natural order in and out) instead of 512 x 16
 // on wg_fft<13> (16 x 32 x 16: half its threads idle in the middle pass, 74 spilled registers); two workgroups per CU (64 KiB of LDS each),
 // the residue class's differences share the exchange buffer (it is idle between a transform's last read and the next one's first barrier).
 #define TRI_THREADS 256

@@ -19,7 +19,7 @@
 // The inverse transform is the forward one on swapped planes.  Index maps and bank behaviour: tests/test_chan_fft_model.py,
 // tests/test_chan_rates_fft_model.py (the two small shapes).
 #pragma once
-#include "k_coarse6.h"
+#include "wg_fft.h" // wg_fft14_e32, regfft<>, regfft32_seq, c4_twiddle16
 
 #define CHAN_N 16384
 #define CHAN_HP 8192

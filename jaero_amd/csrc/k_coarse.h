@@ -1,6 +1,6 @@
 // k_coarse.h -- FreqOffsetEstimateSlot: what the demodulators do with a coarse-frequency estimate (acquisition countdowns, AFC,
 // status log), JAERO/oqpskdemodulator.cpp:629-677 and JAERO/mskdemodulator.cpp:490-519.  Called by thread 0 of the estimate kernels
-// (k_coarse2.h).  (The first estimate kernel, a four-step FFT through L2 scratch, lived here until round 2; k_coarse2<13> / k_coarse4
+// (k_coarse6.h).  (The first estimate kernel, a four-step FFT through L2 scratch, lived here until round 2; k_coarse2<13> / k_coarse4
 // replaced it and the A/B switch went with it.)
 #pragma once
 #include "jaero_device.h"

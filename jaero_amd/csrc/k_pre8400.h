@@ -16,7 +16,7 @@
 //                  filter of the burst path.  (The direct form k_pre8400_fir, 127 ms per step, left the library in round 3.)
 #pragma once
 #include "jaero_device.h"
-#include "k_coarse2.h" // CV<>, regfft<16>, c4_twiddle16
+#include "wg_fft.h" // pf_fft4096, PF_THREADS
 
 #define PRE_K 2049                 // taps
 #define PRE_L 2048                 // JFastFir latency nfft - K + 1
@@ -132,65 +132,8 @@ __global__ __launch_bounds__(64) void k_pre8400_commit(const JGeom g, const JPtr
 //   four lanes c of a T touch the four channels' 16-byte entries of one ring slot / output row = one complete 64-byte sector.
 //   Block b: window x[m0 - 4096 .. m0 - 1], m0 = 2048 (floor(n0 / 2048) + b); its circular convolution with h is the linear one at window indices
 //   2048 .. 4095, which are out[m0 .. m0 + 2047] (latency 2048 = nfft - K + 1 as in JFastFir).
-//   4096 = 16 x 16 x 16, 16 points per thread, thread T holds index T + 256 s in slot s on entry AND on exit of a transform:
-//     pass 1  n = 256 n1 + n2 (n2 = T): 16-point DFT over n1 -> k1, times W_4096^(n2 k1)
-//     exch 1  L = k1 * 256 + 16 m1 + m2          writer T = 16 m1 + m2 slot k1 -> reader T = 16 k1 + m2 slot m1
-//     pass 2  16-point DFT over m1 -> q1, times W_256^(m2 q1)
-//     exch 2  L = (q1 * 16 + m2) * 16 + (k1 ^ m2) writer T = 16 k1 + m2 slot q1 -> reader T = k1 + 16 q1 slot m2
-//     pass 3  16-point DFT over m2 -> q2: X[k1 + 16 q1 + 256 q2] = X[T + 256 s]
-//   LDS address = 4 L + c: a wavefront (16 T x 4 c) touches 64 consecutive doubles in every access but the writes of exchange 2, where
-//   the swizzle k1 ^ m2 spreads each half wavefront over all banks.  Planes (re, im) go through the buffer one after the other.
-//   The inverse transform is the forward one on the conjugate (1 / 4096 is folded into H).
-//   Not bit-identical to the reference's FFT (JFFT is not vendored; other butterfly order): differences ~1e-16 of the signal peak, as
-//   with the direct form; the soft-symbol tolerance applies.
-#define PF_THREADS 1024
-
-// NC: channels per workgroup (the LDS address of entry L of channel c is NC L + c); 4 in both overlap-save filters, 2 in k_rate_lines
-template <int NC = 4>
-__device__ __forceinline__ void pf_exchange1(double (&v)[16], double *xch, int T, int c)
-{
-    const int wb = T * NC + c, rb = ((T >> 4) * 256 + (T & 15)) * NC + c;
-#pragma unroll
-    for (int s = 0; s < 16; s++) xch[wb + s * 256 * NC] = v[s];
-    jd_lds_barrier();
-#pragma unroll
-    for (int s = 0; s < 16; s++) v[s] = xch[rb + s * 16 * NC];
-    jd_lds_barrier();
-}
-
-template <int NC = 4>
-__device__ __forceinline__ void pf_exchange2(double (&v)[16], double *xch, int T, int c)
-{
-    const int hi = T >> 4, lo = T & 15;
-    // writer: k1 = hi, m2 = lo, slot q1; reader: q1 = hi, k1 = lo, slot m2
-    const int wb = (lo * 16 + (hi ^ lo)) * NC + c;
-#pragma unroll
-    for (int s = 0; s < 16; s++) xch[wb + s * 256 * NC] = v[s];
-    jd_lds_barrier();
-#pragma unroll
-    for (int s = 0; s < 16; s++) v[s] = xch[((hi * 16 + s) * 16 + (lo ^ s)) * NC + c];
-    jd_lds_barrier();
-}
-
-template <int NC = 4>
-__device__ __forceinline__ void pf_fft4096(CV<16> &d, double *xch, const double2 *__restrict__ tw, int T, int c)
-{
-#pragma clang fp contract(fast)
-    const double2 st1 = tw[T], st2 = tw[16 * (T & 15)];
-    CV<16> o;
-    regfft<16>(d, o);
-    c4_twiddle16(o, st1);
-    pf_exchange1<NC>(o.r, xch, T, c);
-    pf_exchange1<NC>(o.i, xch, T, c);
-    regfft<16>(o, d);
-    c4_twiddle16(d, st2);
-    pf_exchange2<NC>(d.r, xch, T, c);
-    pf_exchange2<NC>(d.i, xch, T, c);
-    regfft<16>(d, o);
-#pragma unroll
-    for (int s = 0; s < 16; s++) { d.r[s] = o.r[s]; d.i[s] = o.i[s]; }
-}
-
+//   The transform is pf_fft4096 (wg_fft.h); the inverse is the forward one on the conjugate (1 / 4096 is folded into H).  Its round-off is
+//   not the reference's FFT's (~1e-16 of the signal peak, as with the direct form); the soft-symbol tolerance applies.
 __global__ __launch_bounds__(PF_THREADS) void k_pre8400_fft(const JGeom g, const JPtrs p, const JPre q, int n, long long n0)
 {
     extern __shared__ double pf_xch[]; // 4 channels x 4096 doubles

@@ -45,7 +45,7 @@
 //     histogram   thread cc < NC does the read-modify-write of the one counter of channel cc's row that E falls into, every segment, joined
 //                 or not (hist == nullptr: no histogram).  The workgroup owns its channels: no atomics.
 #pragma once
-#include "k_pre8400.h" // pf_fft4096
+#include "wg_fft.h" // pf_fft4096
 
 #define RATE_L 4096
 #define RATE_BINS 2049

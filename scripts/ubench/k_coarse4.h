@@ -1,7 +1,8 @@
 // k_coarse4.h -- the 2^14-point coarse-frequency kernel of rounds 1-2 (one stream, four barriers per exchange), kept OUTSIDE the product
 // library as the A/B partner of k_coarse5 in scripts/ubench/coarse_bench.hip (k_coarse5.h replaced it in libjaero_hip.so in round 3).
 #pragma once
-#include "../../jaero_amd/csrc/k_coarse2.h"
+#include "../../jaero_amd/csrc/wg_fft.h"
+#include "../../jaero_amd/csrc/k_coarse.h"
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // 2^14-point transform out of 16-point pieces only: 16384 = 16 x 16 x 16 x 4, four passes, natural order in AND out, all 512

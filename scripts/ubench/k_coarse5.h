@@ -19,7 +19,8 @@
 // every 64 B; y: 2 x 16 B of every 32 B), issued back to back.  Index maps, twiddles and LDS bank behaviour are pinned by the CPU model
 // tests/test_coarse_fft14_model.py.
 #pragma once
-#include "../../jaero_amd/csrc/k_coarse2.h"
+#include "../../jaero_amd/csrc/wg_fft.h"
+#include "../../jaero_amd/csrc/k_coarse.h"
 
 #ifndef C5_MIX
 #define C5_MIX 0 // experiment: one LDS instruction after every few VALU instructions (sched_group_barrier) -- measured, no gain

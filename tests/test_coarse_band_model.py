@@ -1,4 +1,4 @@
-"""CPU model of the band-aware estimate kernel k_coarse6_b7 (jaero_amd/csrc/k_coarse6.h: coarse6_body<false, 14, 7, 1792>, c6_cfft32_band;
+"""CPU model of the band-aware estimate kernel k_coarse6_b7 (jaero_amd/csrc/k_coarse6.h: coarse6_body<false, 14, 7, 1792>; wg_fft.h: c6_cfft32_band;
 DESIGN 9 item 35), beside tests/test_coarse_fft14_fused_pass1_model.py and tests/test_coarse_fft14_absorbed_model.py, whose networks it prunes.
 
 A locking band of startbin = 7 * 512 makes the boxcar band limit zero slots 7 .. 24 of every thread of the 32 x 32 x 16 transform (and slot 25

@@ -1,4 +1,4 @@
-"""CPU model of the absorbed-twiddle form of the workgroup transforms of k_coarse6 (jaero_amd/csrc/k_coarse6.h: wg_fft14_e32 and
+"""CPU model of the absorbed-twiddle form of the workgroup transforms of k_coarse6 (jaero_amd/csrc/wg_fft.h: wg_fft14_e32 and
 wg_fft13_e32 with C6_ABSORB 2, and C6_ABSORB 1), in the style of tests/test_coarse_fft14_e32_model.py, whose exchange-1 maps and split-order
 first pass it shares.
 

@@ -1,4 +1,4 @@
-"""CPU model of the 32 x 32 x 16 workgroup transform of k_coarse6 (jaero_amd/csrc/k_coarse6.h: wg_fft14_e32): two LDS exchanges per
+"""CPU model of the 32 x 32 x 16 workgroup transform of k_coarse6 (jaero_amd/csrc/wg_fft.h: wg_fft14_e32): two LDS exchanges per
 2^14-point transform instead of three.  n = 512 n1 + 16 n2 + n3, k = k1 + 32 k2 + 1024 k3; natural distribution on entry and exit (slot =
 index >> 9, thread = index & 511).  A 32-point register FFT leaves its outputs in SPLIT order (slot j < 16 holds X[2j], slot 16 + j holds
 X[2j + 1]: one radix-2 stage, then a 16-point FFT on each half in place), which only changes the compile-time addresses of the next

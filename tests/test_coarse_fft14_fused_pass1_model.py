@@ -1,4 +1,4 @@
-"""CPU model of the fused first pass of the workgroup transforms of k_coarse6 (jaero_amd/csrc/k_coarse6.h: c6_cfft32, C6_P1FUSED; DESIGN 9
+"""CPU model of the fused first pass of the workgroup transforms of k_coarse6 (jaero_amd/csrc/wg_fft.h: c6_cfft32, P1; DESIGN 9
 item 34), beside tests/test_coarse_fft14_absorbed_model.py, whose passes 2 and 3 and exchange 2 it shares.
 
 The pass in front of exchange 1 has no twiddle to absorb: it is the absorbed butterfly network for the ratio 1, whose multiplier for block b at

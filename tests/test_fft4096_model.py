@@ -1,4 +1,4 @@
-"""CPU model of the 4096-point workgroup transform behind k_pre8400_fft / k_hilbert_fft (jaero_amd/csrc/k_pre8400.h: pf_fft4096).
+"""CPU model of the 4096-point workgroup transform behind k_pre8400_fft / k_hilbert_fft (jaero_amd/csrc/wg_fft.h: pf_fft4096).
 
 The kernel itself only runs on the GPU (tests/test_jfastfir_vectors.py, tests/test_gpu_parity.py, tests/test_gpu_burst.py); what can be
 pinned without one is its index arithmetic: (i) the two exchange maps and the three twiddle sets turn "thread T holds x[T + 256 s]" into

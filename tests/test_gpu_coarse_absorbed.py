@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the estimate kernels' transforms with absorbed twiddles (jaero_amd/csrc/k_coarse6.h, C6_ABSORB) on inputs whose transform
+"""GPU (-m gpu): the estimate kernels' transforms with absorbed twiddles (jaero_amd/csrc/wg_fft.h, C6_ABSORB) on inputs whose transform
 is known in closed form, through jaero_debug_coarse_poke / _launch / _peek on banks of 3 channels, one estimate each: 10.5 kbps and 8400 bps
 (2^14 points), 1200 bps MSK (2^13 points).
 

@@ -414,7 +414,7 @@ def test_qround_and_softbit_are_qts(L):
 # Outside int's range the C casts of qRound are undefined; what each machine gives (x86-64 cvttsd2si: 0x80000000 for NaN and out of range;
 # gfx950 v_cvt_i32_f64: 0 for NaN, saturated otherwise).  Only +inf and v >= 2^31 differ, and no call site reaches them: every jd_softbit
 # argument is 128 + 127 k s (k = 1 or 0.75) with s a symbol formed from AGC'd samples clipped to magnitude 2.84 (demod_stages.h:161 and its
-# counterparts in the OQPSK and burst kernels), i.e. finite and small -- or NaN, where both give 0.  jd_qround's other call (k_burst_front.h:386-387) rounds
+# counterparts in the OQPSK and burst kernels), i.e. finite and small -- or NaN, where both give 0.  jd_qround's other call (k_burst_front.h:384-385) rounds
 # constants of the bank's geometry.
 #            v:        (device qRound, x86 qRound, device soft bit, x86 soft bit)
 QROUND_OUTSIDE = {
