@@ -925,6 +925,19 @@ typedef struct jaero_coarse_state
 int jaero_debug_coarse_poke(jaero_ctx *ctx, int channel, const double *ring_reim, const double *y, const jaero_coarse_state *st);
 int jaero_debug_coarse_launch(jaero_ctx *ctx, const int *channels, int nlist, int grid);
 int jaero_debug_coarse_peek(jaero_ctx *ctx, int channel, double *ring_reim, double *y, jaero_coarse_state *st);
+/* Test hooks: the slow state of a continuous bank's sample loop, which no signal of a few seconds moves far (tests/test_gpu_loop_branches.py):
+ * the symbol oscillator's frequency st_freq (OQPSK: held within 0.1 Hz of the bit rate by the loop; MSK: fb / 2, fixed), mixer2's frequency
+ * m2_freq, and the carrier loop filter's last two inputs lf_x1, lf_x2 and outputs lf_y1, lf_y2, newest first (OQPSK only; MSK banks keep
+ * what is poked and never read it).  Poke writes all six and sets the two wave tables' steps to match, as jaero_create forms them; the
+ * phases stay.  Both synchronise the bank.  Unlike the coarse hooks they leave the bank usable: the write schedule does not depend on these
+ * values, and a jaero_write behind a poke continues from them.  JAERO_EINVAL: null ctx or state, a burst bank, channel outside
+ * [0, nchannels), a negative frequency, a value that is not finite.  A poisoned bank: JAERO_EHIP. */
+typedef struct jaero_loop_state
+{
+    double st_freq, m2_freq, lf_x1, lf_x2, lf_y1, lf_y2;
+} jaero_loop_state;
+int jaero_debug_loop_poke(jaero_ctx *ctx, int channel, const jaero_loop_state *st);
+int jaero_debug_loop_peek(jaero_ctx *ctx, int channel, jaero_loop_state *st);
 /* Test hooks: the band-aware estimate kernel.  A 2^14-point bank that is not an 8400 bps bank holds, beside its generic kernel (what
  * jaero_debug_kernel_variant(ctx, 1) and jaero_profile_kernel(ctx, 1) keep naming), k_coarse6_b7 for channels whose locking band ends on the
  * slot boundaries it is built for (startbin 7 * 512, expectedpeakbin 1792: lockingbw 10500 Hz at 48 kHz); jaero_write and

@@ -36,6 +36,7 @@ EXPORTS = [
     "jaero_debug_sample_loop_layout", "jaero_debug_kernel_variant",
     "jaero_debug_coarse_poke", "jaero_debug_coarse_launch", "jaero_debug_coarse_peek",
     "jaero_debug_coarse_band", "jaero_debug_coarse_force_generic", "jaero_debug_coarse_band_class",
+    "jaero_debug_loop_poke", "jaero_debug_loop_peek",
     "jaero_debug_schedule", "jaero_debug_schedule_lanes", "jaero_debug_prefilter", "jaero_debug_read_prefiltered", "jaero_read_events",
     "jaero_debug_burst_geom", "jaero_debug_burst_hilbert", "jaero_debug_burst_read_hist", "jaero_debug_burst_poke_cv", "jaero_debug_burst_trident",
     "jaero_debug_burst_front_geom", "jaero_debug_burst_front", "jaero_debug_burst_front_peek", "jaero_debug_burst_front_events", "jaero_debug_burst_front_poke", "jaero_debug_burst_poke_bt",
@@ -97,6 +98,12 @@ class CoarseState(C.Structure):
 
     _fields_ = [(n, C.c_int) for n in ("bb_ptr", "emptying", "flags", "countdown", "countdown2", "coarse_cnt", "nest", "log_cnt")] + [
         (n, C.c_double) for n in ("mse", "m2_freq", "mc_freq")]
+
+
+class LoopState(C.Structure):
+    """struct jaero_loop_state: what jaero_debug_loop_poke / _peek exchange."""
+
+    _fields_ = [(n, C.c_double) for n in ("st_freq", "m2_freq", "lf_x1", "lf_x2", "lf_y1", "lf_y2")]
 
 
 class Pre8400State(C.Structure):
@@ -252,6 +259,8 @@ def lib():
     L.jaero_debug_coarse_poke.argtypes = [vp, ip, vp, vp, C.POINTER(CoarseState)]
     L.jaero_debug_coarse_launch.argtypes = [vp, vp, ip, ip]
     L.jaero_debug_coarse_peek.argtypes = [vp, ip, vp, vp, C.POINTER(CoarseState)]
+    L.jaero_debug_loop_poke.argtypes = [vp, ip, C.POINTER(LoopState)]
+    L.jaero_debug_loop_peek.argtypes = [vp, ip, C.POINTER(LoopState)]
     L.jaero_debug_coarse_band.argtypes = [vp, C.c_char_p, ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     L.jaero_debug_coarse_force_generic.argtypes = [vp, ip]
     L.jaero_debug_coarse_band_class.argtypes = [ip, dp, dp, dp]

@@ -1403,6 +1403,44 @@ extern "C" int jaero_debug_coarse_launch(jaero_ctx *c, const int *channels, int 
     HIPCHK(hipStreamSynchronize(c->last_stream));
     return 0;
 }
+// ------------------------------------------------------------------------------------------ test hooks: the sample loop's slow state
+// (tests/test_gpu_loop_branches.py).  The symbol oscillator's and mixer2's frequency and the carrier loop filter's history live in S between
+// launches and nowhere else: the schedule mirror does not depend on them, so the bank is not poisoned and goes on taking writes.
+static const int LOOP_FIELDS[6] = {S_ST_FREQ, S_M2_FREQ, S_LF_X1, S_LF_X2, S_LF_Y1, S_LF_Y2};
+#define LOOP_HOOK_ENTER(who)                                                                                                                       \
+    if (!c) return fail(JAERO_EINVAL, who ": null ctx");                                                                                           \
+    if (!st) return fail(JAERO_EINVAL, who ": null state");                                                                                        \
+    if (c->burst) return fail(JAERO_EINVAL, who ": a burst bank has no continuous sample loop");                                                   \
+    if (ch < 0 || ch >= c->g.nch) return fail(JAERO_EINVAL, who ": channel %d outside [0, %d)", ch, c->g.nch);                                     \
+    POISONCHK(c, who)
+extern "C" int jaero_debug_loop_poke(jaero_ctx *c, int ch, const jaero_loop_state *st)
+{
+    LOOP_HOOK_ENTER("jaero_debug_loop_poke");
+    const double v[6] = {st->st_freq, st->m2_freq, st->lf_x1, st->lf_x2, st->lf_y1, st->lf_y2};
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(JAERO_EINVAL, "jaero_debug_loop_poke: a value is not finite");
+    if (st->st_freq < 0 || st->m2_freq < 0) return fail(JAERO_EINVAL, "jaero_debug_loop_poke: st_freq and m2_freq must be >= 0");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    const size_t nchp = (size_t)c->g.nchp;
+    // WaveTable::SetFreq's step, in init_channel_scalars' order of operations: (freq * WTSIZE) / Fs, the quotient the kernels' own SetFreq forms
+    const float fs = (float)(double)c->g.Fs_int;
+    const std::pair<int, double> steps[] = {{S_ST_STEP, st->st_freq * ((double)JD_WTSIZE) / fs}, {S_M2_STEP, st->m2_freq * ((double)JD_WTSIZE) / fs}};
+    for (int k = 0; k < 6; k++) HIPCHK(hipMemcpy(c->p.S + (size_t)LOOP_FIELDS[k] * nchp + ch, &v[k], sizeof(double), hipMemcpyHostToDevice));
+    for (const auto &[f, x] : steps) HIPCHK(hipMemcpy(c->p.S + (size_t)f * nchp + ch, &x, sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+extern "C" int jaero_debug_loop_peek(jaero_ctx *c, int ch, jaero_loop_state *st)
+{
+    LOOP_HOOK_ENTER("jaero_debug_loop_peek");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->last_stream));
+    const size_t nchp = (size_t)c->g.nchp;
+    double *const v[6] = {&st->st_freq, &st->m2_freq, &st->lf_x1, &st->lf_x2, &st->lf_y1, &st->lf_y2};
+    for (int k = 0; k < 6; k++) HIPCHK(hipMemcpy(v[k], c->p.S + (size_t)LOOP_FIELDS[k] * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+#undef LOOP_HOOK_ENTER
 extern "C" int jaero_debug_coarse_band(jaero_ctx *c, char *buf, int cap, long long *est_generic, long long *est_band)
 {
     if (!c || !buf || cap < 2) return fail(JAERO_EINVAL, "jaero_debug_coarse_band: bad arguments");

@@ -233,11 +233,11 @@ static double ma_update_signed(ma_t *m, double sig) /* :418-426 */
 
 /* ------------------------------------------------------------------ MSEcalc (DSP.cpp:434-463) */
 typedef struct { ma_t *pointmean, *msema; double mse; } msecalc_t;
-static double msecalc_update(msecalc_t *m, cpx pt)
+static double msecalc_update(msecalc_t *m, cpx pt, long *cov) /* cov: the owner's branch counters, or NULL */
 {
     ma_update(m->pointmean, hypot(pt.re, pt.im)); /* std::abs(complex) */
     double mu = m->pointmean->val;
-    if (mu < 0.000001) mu = 0.000001;
+    if (mu < 0.000001) { mu = 0.000001; if (cov) cov[JO_COV_MU_FLOOR]++; }
     double s2 = sqrt(2.0);
     cpx t; t.re = (s2 * pt.re) / mu; t.im = (s2 * pt.im) / mu;
     double tda = (fabs(t.re) - 1.0);
@@ -247,8 +247,8 @@ static double msecalc_update(msecalc_t *m, cpx pt)
 }
 
 /* ------------------------------------------------------------------ EbNo meters (DSP.cpp:487-505,715-744) */
-typedef struct { ma_t *E, *E2; double EbNo, Var, Mean, Fs, fb; } ebno_t;
-static double oqpsk_ebno_update(ebno_t *e, double sig) /* :729-744 */
+typedef struct { ma_t *E, *E2; double EbNo, Var, Mean, Fs, fb, raw; } ebno_t; /* raw: tebno of the last update in front of its limits (tests) */
+static double oqpsk_ebno_update(ebno_t *e, double sig, long *cov) /* :729-744 */
 {
     ma_update(e->E2, sig * sig);
     e->Mean = ma_update(e->E, sig);
@@ -256,23 +256,25 @@ static double oqpsk_ebno_update(ebno_t *e, double sig) /* :729-744 */
     e->Var = (e->E2->val) - (e->E->val * e->E->val);
     e->Var -= (0.024709 * MeanSquared);
     double mvr = (((e->Fs * MeanSquared / (2.0 * e->fb * e->Var))) * 0.13743);
-    if (mvr < 0.000000001) mvr = 0.000000001;
+    if (mvr < 0.000000001) { mvr = 0.000000001; if (cov) cov[JO_COV_OQ_MVR_FLOOR]++; }
     double tebno = 10.0 * log10(mvr);
-    if (isnan(tebno)) tebno = 50;
-    if (tebno > 50.0) tebno = 50;
-    if (tebno < 0.0) tebno = 0;
+    e->raw = tebno;
+    if (isnan(tebno)) { tebno = 50; if (cov) cov[JO_COV_OQ_NAN]++; }
+    if (tebno > 50.0) { tebno = 50; if (cov) cov[JO_COV_OQ_TEBNO_HI]++; }
+    if (tebno < 0.0) { tebno = 0; if (cov) cov[JO_COV_OQ_TEBNO_LO]++; }
     e->EbNo = e->EbNo * 0.8 + 0.2 * tebno;
     return e->EbNo;
 }
-static double msk_ebno_update(ebno_t *e, double sig) /* :493-505 */
+static double msk_ebno_update(ebno_t *e, double sig, long *cov) /* :493-505 */
 {
     ma_update(e->E2, sig * sig);
     e->Mean = ma_update(e->E, sig);
     e->Var = (e->E2->val) - (e->E->val * e->E->val);
     double alpha = sqrt(2.0) / e->Mean;
     double tebno = 10.0 * (log10(2.0) - log10(((e->Var * alpha * alpha) - 0.0085))) - 5.0;
-    if (isnan(tebno)) tebno = 50;
-    if (tebno > 50.0) tebno = 50;
+    e->raw = tebno;
+    if (isnan(tebno)) { tebno = 50; if (cov) cov[JO_COV_MSK_NAN]++; }
+    if (tebno > 50.0) { tebno = 50; if (cov) cov[JO_COV_MSK_TEBNO_HI]++; }
     e->EbNo = e->EbNo * 0.8 + 0.2 * tebno;
     return e->EbNo;
 }
@@ -669,6 +671,7 @@ struct jo_demod
     int capture_symbols, capture_prefiltered;
     double pre_freq_sum; /* mixer2_freq_sum of the last OQPSK write (:447, :607-608) */
     double nest;
+    long cov[JO_DEMOD_NCOV]; /* jo_demod_coverage: branches taken so far */
 };
 
 static void set_resonator(iir_t *f, double b0, double b1, double b2, double a0, double a1, double a2)
@@ -791,20 +794,24 @@ static void oqpsk_freq_offset_estimate_slot(jo_demod *d, double freq_offset_est)
     if ((d->mse < d->signalthreshold) && (!d->dcd))
     {
         if (d->countdown2 > 0) d->countdown2--;
-        else wt_setfreq(&d->mixer2, d->mixer_center.freq + freq_offset_est);
+        else { wt_setfreq(&d->mixer2, d->mixer_center.freq + freq_offset_est); d->cov[JO_COV_M2_COUNTDOWN2]++; }
     }
     else d->countdown2 = 5;
 
     if ((d->mse > d->signalthreshold) && (fabs(d->mixer2.freq - (d->mixer_center.freq + freq_offset_est)) > 3.0))
+    {
         wt_setfreq(&d->mixer2, d->mixer_center.freq + freq_offset_est);
+        d->cov[JO_COV_M2_RULE]++;
+    }
     if ((d->afc) && (d->mse < d->signalthreshold) && (fabs(d->mixer2.freq - d->mixer_center.freq) > 3.0))
     {
         if (d->countdown > 0) d->countdown--;
         else
         {
             wt_setfreq(&d->mixer_center, d->mixer2.freq);
-            if (d->mixer_center.freq < d->lockingbw / 2.0) wt_setfreq(&d->mixer_center, d->lockingbw / 2.0);
-            if (d->mixer_center.freq > (d->Fs / 2.0 - d->lockingbw / 2.0)) wt_setfreq(&d->mixer_center, d->Fs / 2.0 - d->lockingbw / 2.0);
+            d->cov[JO_COV_AFC_RECENTRE]++;
+            if (d->mixer_center.freq < d->lockingbw / 2.0) { wt_setfreq(&d->mixer_center, d->lockingbw / 2.0); d->cov[JO_COV_AFC_CLAMP_LO]++; }
+            if (d->mixer_center.freq > (d->Fs / 2.0 - d->lockingbw / 2.0)) { wt_setfreq(&d->mixer_center, d->Fs / 2.0 - d->lockingbw / 2.0); d->cov[JO_COV_AFC_CLAMP_HI]++; }
             jo_coarse_bigchange(d->coarse);
             for (int j = 0; j < d->bbnfft; j++) { d->bbcycbuff[j].re = 0; d->bbcycbuff[j].im = 0; }
         }
@@ -840,12 +847,13 @@ static void coarse_ring_step(jo_demod *d, double dval, int is_oqpsk)
 /* The prefilter block of OqpskDemodulator::writeData at 8400 bps (oqpskdemodulator.cpp:343-381): the write mixed down with mixer_fir_pre
  * (:354-364), JFastFir::update over the whole write (:366-368), and mixed up again with the conjugate of the same oscillator restarted from
  * the phase it had before the write (:371-379).  buf receives cval_prefiltered; down (optional) the samples that went into the filter. */
-static void pre8400_write(wavetable *osc, fastfir_t *fir, const int16_t *ptr, long n, cpx *buf, cpx *down)
+/* fptr (tests only, jo_demod_write_f64): the same samples as doubles that need not be whole numbers, in place of ptr */
+static void pre8400_write(wavetable *osc, fastfir_t *fir, const int16_t *ptr, const double *fptr, long n, cpx *buf, cpx *down)
 {
     const double savedphase = wt_get_phase_deg(osc);
     for (long i = 0; i < n; i++)
     {
-        double dval = ((double)ptr[i]) / 32768.0;
+        double dval = (fptr ? fptr[i] : (double)ptr[i]) / 32768.0;
         buf[i] = cscale(wt_cis(osc), dval);
         wt_next(osc);
     }
@@ -885,7 +893,7 @@ jo_pre8400 *jo_pre8400_create(void)
 void jo_pre8400_destroy(jo_pre8400 *p) { if (!p) return; fastfir_free(&p->fir); free(p); }
 void jo_pre8400_write(jo_pre8400 *p, const int16_t *pcm, long n, double *down_re_im, double *out_re_im)
 {
-    pre8400_write(&p->osc, &p->fir, pcm, n, (cpx *)out_re_im, (cpx *)down_re_im);
+    pre8400_write(&p->osc, &p->fir, pcm, NULL, n, (cpx *)out_re_im, (cpx *)down_re_im);
 }
 /* mixer_fir_pre.SetFreq(mixer2_freq_sum / i) at the end of a write of n samples (oqpskdemodulator.cpp:607-608) */
 void jo_pre8400_end_of_write(jo_pre8400 *p, double mixer2_freq_sum, long n) { wt_setfreq(&p->osc, mixer2_freq_sum / ((double)n)); }
@@ -893,20 +901,20 @@ void jo_pre8400_end_of_write(jo_pre8400 *p, double mixer2_freq_sum, long n) { wt
 void jo_pre8400_restart(jo_pre8400 *p) { pre8400_set_kernel(&p->fir, p->fb, p->Fs); }
 void jo_pre8400_get_state(const jo_pre8400 *p, double *wtptr, double *wtstep) { *wtptr = p->osc.WTptr; *wtstep = p->osc.WTstep; }
 
-static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodulator.cpp:334-627 */
+static void oqpsk_write(jo_demod *d, const int16_t *ptr, const double *fptr, long n) /* oqpskdemodulator.cpp:334-627 */
 {
     if (!n) return;
     /* prefilter (:343-381): down with mixer_fir_pre, JFastFir over the whole write, up again from the saved phase */
     if (d->fb == 8400)
     {
         if (d->prefilt_cap < n) { d->prefilt = (cpx *)realloc(d->prefilt, sizeof(cpx) * (size_t)n); d->prefilt_cap = n; }
-        pre8400_write(&d->mixer_fir_pre, &d->fir_pre, ptr, n, d->prefilt, NULL);
+        pre8400_write(&d->mixer_fir_pre, &d->fir_pre, ptr, fptr, n, d->prefilt, NULL);
         if (d->capture_prefiltered) gpush(&d->prefiltered, d->prefilt, sizeof(cpx) * (size_t)n);
     }
     double mixer2_freq_sum = 0;
     for (long i = 0; i < n; i++)
     {
-        double dval = ((double)ptr[i]) / 32768.0;
+        double dval = (fptr ? fptr[i] : (double)ptr[i]) / 32768.0;
         coarse_ring_step(d, dval, 1);
 
         cpx sig2;
@@ -923,11 +931,11 @@ static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodul
         }
 
         double dabval = sqrt(sig2.re * sig2.re + sig2.im * sig2.im);
-        oqpsk_ebno_update(&d->ebno, dabval);
+        oqpsk_ebno_update(&d->ebno, dabval, d->cov);
         sig2 = cscale(sig2, agc_update(d->agc, dabval));
 
         double abval = hypot(sig2.re, sig2.im);
-        if (abval > 2.84) sig2 = cscale(sig2, (2.84 / abval));
+        if (abval > 2.84) { sig2 = cscale(sig2, (2.84 / abval)); d->cov[JO_COV_CLIP]++; }
 
         /* symbol timer :473-484 */
         double st_diff = delay_update(&d->delays, abval * abval) - (abval * abval);
@@ -940,8 +948,8 @@ static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodul
         double st_angle_error = atan2(st_out.im, st_out.re);
         wt_increase_freq(&d->st_osc, -st_angle_error * 0.00000001);
         wt_advance_fraction_of_wave(&d->st_osc, -st_angle_error * 0.01 / 360.0);
-        if (d->st_osc.freq < (d->st_osc_ref.freq - 0.1)) wt_setfreq(&d->st_osc, (d->st_osc_ref.freq - 0.1));
-        if (d->st_osc.freq > (d->st_osc_ref.freq + 0.1)) wt_setfreq(&d->st_osc, (d->st_osc_ref.freq + 0.1));
+        if (d->st_osc.freq < (d->st_osc_ref.freq - 0.1)) { wt_setfreq(&d->st_osc, (d->st_osc_ref.freq - 0.1)); d->cov[JO_COV_ST_LOW]++; }
+        if (d->st_osc.freq > (d->st_osc_ref.freq + 0.1)) { wt_setfreq(&d->st_osc, (d->st_osc_ref.freq + 0.1)); d->cov[JO_COV_ST_HIGH]++; }
 
         /* sample times :487-595 */
         if (!d->sig2_last_init) { d->sig2_last = sig2; d->sig2_last_init = 1; }
@@ -960,13 +968,13 @@ static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodul
                 double ct_xt = tanh(pt.im) * pt.re;
                 double ct_xt_d = tanh(d->pt_d.re) * d->pt_d.im;
                 double ct_ec = ct_xt_d - ct_xt;
-                if (ct_ec > M_PI) ct_ec = M_PI;
-                if (ct_ec < -M_PI) ct_ec = -M_PI;
+                if (ct_ec > M_PI) { ct_ec = M_PI; d->cov[JO_COV_EC_PI]++; }
+                if (ct_ec < -M_PI) { ct_ec = -M_PI; d->cov[JO_COV_EC_PI]++; }
                 if (d->fb > 8400) /* :518-525 */
                 {
                     ct_ec = iir_update(&d->ct_iir_loopfilter, ct_ec);
-                    if (ct_ec > M_PI_2) ct_ec = M_PI_2;
-                    if (ct_ec < -M_PI_2) ct_ec = -M_PI_2;
+                    if (ct_ec > M_PI_2) { ct_ec = M_PI_2; d->cov[JO_COV_LF_PI2_POS]++; }
+                    if (ct_ec < -M_PI_2) { ct_ec = -M_PI_2; d->cov[JO_COV_LF_PI2_NEG]++; }
                     wt_increase_phase_deg(&d->mixer2, 1.0 * ct_ec);
                     wt_increase_freq(&d->mixer2, 0.01 * ct_ec);
                 }
@@ -981,21 +989,22 @@ static void oqpsk_write(jo_demod *d, const int16_t *ptr, long n) /* oqpskdemodul
                 cpx rot; rot.re = cos(d->marg->val); rot.im = sin(d->marg->val);
                 pt_qpsk = cmul(pt_qpsk, rot);
 
-                d->mse = msecalc_update(&d->msecalc, pt_qpsk);
+                d->mse = msecalc_update(&d->msecalc, pt_qpsk, d->cov);
                 if (d->capture_symbols) { double row[3] = {pt_qpsk.re, pt_qpsk.im, d->mse}; gpush(&d->symbols, row, sizeof(row)); }
 
                 if (d->mse < d->signalthreshold)
                 {
                     int ibit = qRound_(0.75 * pt_qpsk.im * 127.0 + 128.0);
-                    if (ibit > 255) ibit = 255;
-                    if (ibit < 0) ibit = 0;
+                    if (ibit > 255) { ibit = 255; d->cov[JO_COV_SOFT_255]++; }
+                    if (ibit < 0) { ibit = 0; d->cov[JO_COV_SOFT_0]++; }
                     d->rx[d->nrx++] = (short)(unsigned char)ibit;
                     ibit = qRound_(0.75 * pt_qpsk.re * 127.0 + 128.0);
-                    if (ibit > 255) ibit = 255;
-                    if (ibit < 0) ibit = 0;
+                    if (ibit > 255) { ibit = 255; d->cov[JO_COV_SOFT_255]++; }
+                    if (ibit < 0) { ibit = 0; d->cov[JO_COV_SOFT_0]++; }
                     d->rx[d->nrx++] = (short)(unsigned char)ibit;
                     if (d->nrx >= 32) emit_soft(d); /* the sql test at :585 is always true inside mse<threshold */
                 }
+                else d->cov[JO_COV_SYM_GATED]++;
             }
         }
         d->sig2_last = sig2;
@@ -1118,15 +1127,19 @@ static void msk_set_settings(jo_demod *d, const jo_settings *s) /* mskdemodulato
 void jo__msk_slot(jo_demod *d, double freq_offset_est) /* mskdemodulator.cpp:490-519 */
 {
     if ((d->mse > d->signalthreshold) && (fabs(d->mixer2.freq - (d->mixer_center.freq + freq_offset_est)) > 0.0))
+    {
         wt_setfreq(&d->mixer2, d->mixer_center.freq + freq_offset_est);
+        d->cov[JO_COV_M2_RULE]++;
+    }
     if ((d->afc) && (d->dcd) && (fabs(d->mixer2.freq - d->mixer_center.freq) > 2.0))
     {
         if (d->countdown > 0) d->countdown--;
         else
         {
             wt_setfreq(&d->mixer_center, d->mixer2.freq);
-            if (d->mixer_center.freq < d->lockingbw / 2.0) wt_setfreq(&d->mixer_center, d->lockingbw / 2.0);
-            if (d->mixer_center.freq > (d->Fs / 2.0 - d->lockingbw / 2.0)) wt_setfreq(&d->mixer_center, d->Fs / 2.0 - d->lockingbw / 2.0);
+            d->cov[JO_COV_AFC_RECENTRE]++;
+            if (d->mixer_center.freq < d->lockingbw / 2.0) { wt_setfreq(&d->mixer_center, d->lockingbw / 2.0); d->cov[JO_COV_AFC_CLAMP_LO]++; }
+            if (d->mixer_center.freq > (d->Fs / 2.0 - d->lockingbw / 2.0)) { wt_setfreq(&d->mixer_center, d->Fs / 2.0 - d->lockingbw / 2.0); d->cov[JO_COV_AFC_CLAMP_HI]++; }
             jo_coarse_bigchange(d->coarse);
             for (int j = 0; j < d->bbnfft; j++) { d->bbcycbuff[j].re = 0; d->bbcycbuff[j].im = 0; }
         }
@@ -1135,11 +1148,11 @@ void jo__msk_slot(jo_demod *d, double freq_offset_est) /* mskdemodulator.cpp:490
     record_status(d);
 }
 
-static void msk_write(jo_demod *d, const int16_t *ptr, long n) /* mskdemodulator.cpp:313-488 */
+static void msk_write(jo_demod *d, const int16_t *ptr, const double *fptr, long n) /* mskdemodulator.cpp:313-488 */
 {
     for (long i = 0; i < n; i++)
     {
-        double dval = ((double)ptr[i]) / 32768.0;
+        double dval = (fptr ? fptr[i] : (double)ptr[i]) / 32768.0;
         coarse_ring_step(d, dval, 0);
 
         cpx cval = cscale(wt_cis(&d->mixer2), dval);
@@ -1147,10 +1160,10 @@ static void msk_write(jo_demod *d, const int16_t *ptr, long n) /* mskdemodulator
         sig2.re = fir_update_and_process(d->fir_re, cval.re);
         sig2.im = fir_update_and_process(d->fir_im, cval.im);
         double dabval = sqrt(sig2.re * sig2.re + sig2.im * sig2.im);
-        msk_ebno_update(&d->ebno, dabval);
+        msk_ebno_update(&d->ebno, dabval, d->cov);
         sig2 = cscale(sig2, agc_update(d->agc, dabval));
         double abval = sqrt(sig2.re * sig2.re + sig2.im * sig2.im);
-        if (abval > 2.84) sig2 = cscale(sig2, (2.84 / abval));
+        if (abval > 2.84) { sig2 = cscale(sig2, (2.84 / abval)); d->cov[JO_COV_CLIP]++; }
 
         cpx pt_d = delaything_update_dont_touch(&d->delayedsmpl, sig2);
         cpx pt_msk; pt_msk.re = sig2.re; pt_msk.im = pt_d.im;
@@ -1168,10 +1181,10 @@ static void msk_write(jo_demod *d, const int16_t *ptr, long n) /* mskdemodulator
             double ct_xt = tanh(sig2.im) * sig2.re;
             double ct_xt_d = tanh(pt_d.re) * pt_d.im;
             double ct_ec = ct_xt_d - ct_xt;
-            if (ct_ec > M_PI) ct_ec = M_PI;
-            if (ct_ec < -M_PI) ct_ec = -M_PI;
-            if (ct_ec > M_PI_2) ct_ec = M_PI_2;
-            if (ct_ec < -M_PI_2) ct_ec = -M_PI_2;
+            if (ct_ec > M_PI) { ct_ec = M_PI; d->cov[JO_COV_EC_PI]++; }
+            if (ct_ec < -M_PI) { ct_ec = -M_PI; d->cov[JO_COV_EC_PI]++; }
+            if (ct_ec > M_PI_2) { ct_ec = M_PI_2; d->cov[JO_COV_LF_PI2_POS]++; }
+            if (ct_ec < -M_PI_2) { ct_ec = -M_PI_2; d->cov[JO_COV_LF_PI2_NEG]++; }
             double carrier_aggression = 12.0 * d->correctionfactor;
             if (d->dcd) carrier_aggression = 8.0 * d->correctionfactor;
             wt_increase_phase_deg(&d->mixer2, carrier_aggression * 1.0 * ct_ec);
@@ -1189,14 +1202,14 @@ static void msk_write(jo_demod *d, const int16_t *ptr, long n) /* mskdemodulator
 
             double imagin = diffdecode_update_soft(&d->diff_lastsoftstate, pt_msk.im);
             int ibit = qRound_((imagin) * 127.0 + 128.0);
-            if (ibit > 255) ibit = 255;
-            if (ibit < 0) ibit = 0;
+            if (ibit > 255) { ibit = 255; d->cov[JO_COV_SOFT_255]++; }
+            if (ibit < 0) { ibit = 0; d->cov[JO_COV_SOFT_0]++; }
             d->rx[d->nrx++] = (short)(unsigned char)ibit;
             double real = diffdecode_update_soft(&d->diff_lastsoftstate, pt_msk.re);
             real = -real;
             ibit = qRound_((real) * 127.0 + 128.0);
-            if (ibit > 255) ibit = 255;
-            if (ibit < 0) ibit = 0;
+            if (ibit > 255) { ibit = 255; d->cov[JO_COV_SOFT_255]++; }
+            if (ibit < 0) { ibit = 0; d->cov[JO_COV_SOFT_0]++; }
             d->rx[d->nrx++] = (short)(unsigned char)ibit;
             if (d->nrx >= 12) emit_soft(d);
         }
@@ -1237,7 +1250,13 @@ void jo_demod_set_dcd(jo_demod *d, int dcd) { d->dcd = dcd; }
 void jo_demod_center_freq_changed(jo_demod *d, double f) { center_freq_changed(d, f); }
 long jo_demod_write(jo_demod *d, const int16_t *pcm, long n)
 {
-    if (d->kind == JO_KIND_OQPSK) oqpsk_write(d, pcm, n); else msk_write(d, pcm, n);
+    if (d->kind == JO_KIND_OQPSK) oqpsk_write(d, pcm, NULL, n); else msk_write(d, pcm, NULL, n);
+    return 2 * n;
+}
+/* tests only: a write whose samples are doubles on the int16 scale (a stream with noise far below one step added) */
+long jo_demod_write_f64(jo_demod *d, const double *x, long n)
+{
+    if (d->kind == JO_KIND_OQPSK) oqpsk_write(d, NULL, x, n); else msk_write(d, NULL, x, n);
     return 2 * n;
 }
 long jo_demod_take_soft(jo_demod *d, int16_t *dst, long cap) { return gtake(&d->soft, dst, sizeof(int16_t), cap); }
@@ -1255,6 +1274,30 @@ long jo_demod_take_prefiltered(jo_demod *d, double *dst, long caprows) { return 
 /* mixer_fir_pre's frequency, and the mixer2_freq_sum the last write set it from (oqpskdemodulator.cpp:607-608) */
 double jo_demod_get_pre_freq(jo_demod *d) { return d->mixer_fir_pre.freq; }
 double jo_demod_get_pre_freq_sum(jo_demod *d) { return d->pre_freq_sum; }
+/* times each branch of oqpsk_write / msk_write, the two slot functions and the meters was taken by this object (JO_COV_* order) */
+/* tebno of the meter's last update as computed, in front of the NaN / 50 / 0 lines */
+double jo_demod_get_tebno_raw(jo_demod *d) { return d->ebno.raw; }
+void jo_demod_coverage(jo_demod *d, long *out) { for (int k = 0; k < JO_DEMOD_NCOV; k++) out[k] = d->cov[k]; }
+/* The symbol oscillator's and mixer2's frequency and the carrier loop filter's history, read (set == 0) or written.  On set the two
+ * frequencies go through WaveTable::SetFreq(freq) (DSP.cpp:151-156), which also forms the step; the phases stay.  The filter's four
+ * values are those IIR::update will read next, by age: x1 / y1 the newest input / output, x2 / y2 the ones before, wherever px / py
+ * stand in the rings (update writes bx[px] and then reads bx[px+1] = x2, bx[px+2] = x1; it reads by[py] = y2, by[py+1] = y1). */
+void jo_demod_loop_state(jo_demod *d, int set, jo_loop_state *s)
+{
+    iir_t *f = &d->ct_iir_loopfilter;
+    const int px = f->px >= 3 ? 0 : f->px, py = f->py >= 2 ? 0 : f->py;
+    if (set)
+    {
+        wt_setfreq(&d->st_osc, s->st_freq);
+        wt_setfreq(&d->mixer2, s->m2_freq);
+        f->bx[(px + 2) % 3] = s->lf_x1; f->bx[(px + 1) % 3] = s->lf_x2;
+        f->by[(py + 1) % 2] = s->lf_y1; f->by[py] = s->lf_y2;
+        return;
+    }
+    s->st_freq = d->st_osc.freq; s->m2_freq = d->mixer2.freq;
+    s->lf_x1 = f->bx[(px + 2) % 3]; s->lf_x2 = f->bx[(px + 1) % 3];
+    s->lf_y1 = f->by[(py + 1) % 2]; s->lf_y2 = f->by[py];
+}
 
 /* JFastFir::SetKernel(rrc(alpha, K, Fs, fsym), nfft) + update(x) on n complex samples (re, im interleaved): the operation
  * JAERO/tests/jfastfir_tests.cpp:31-58 checks against the recorded output of JAERO v1.0.4.11 */

@@ -36,6 +36,8 @@ void jo_demod_set_dcd(jo_demod *d, int dcd);
 void jo_demod_center_freq_changed(jo_demod *d, double freq_center);
 /* = writeData(const char*, len) with len = 2*nsamples */
 long jo_demod_write(jo_demod *d, const int16_t *pcm, long nsamples);
+/* tests only: the same write with the samples given as doubles on the int16 scale, which need not be whole numbers */
+long jo_demod_write_f64(jo_demod *d, const double *x, long nsamples);
 
 /* captured outputs (drained by the calls below) */
 /* soft bits exactly as passed to processDemodulatedSoftBits, concatenated */
@@ -59,6 +61,40 @@ long jo_demod_take_prefiltered(jo_demod *d, double *dst, long caprows);
 /* mixer_fir_pre's frequency and the mixer2_freq_sum of the last write, which it was set from (JAERO/oqpskdemodulator.cpp:607-608) */
 double jo_demod_get_pre_freq(jo_demod *d);
 double jo_demod_get_pre_freq_sum(jo_demod *d);
+
+/* Branch counters of the continuous demodulators, per object: times taken in oqpsk_write / msk_write, the two slot functions and the meters.
+ * jo_demod_coverage fills JO_DEMOD_NCOV longs in this order (oracle.py: Demod.COVERAGE). */
+enum
+{
+    JO_COV_CLIP,          /* |sig2| > 2.84 */
+    JO_COV_EC_PI,         /* ct_ec clamped at +-pi */
+    JO_COV_LF_PI2_POS,    /* carrier loop: clamped at +pi/2 (10.5 kbps: behind the loop filter; MSK: the raw error) */
+    JO_COV_LF_PI2_NEG,    /* ... at -pi/2 */
+    JO_COV_ST_LOW,        /* OQPSK: st_osc held at st_osc_ref - 0.1 Hz */
+    JO_COV_ST_HIGH,       /* ... at st_osc_ref + 0.1 Hz */
+    JO_COV_SYM_GATED,     /* OQPSK: a symbol not output because mse >= signalthreshold */
+    JO_COV_SOFT_255,      /* a soft byte saturated at 255 */
+    JO_COV_SOFT_0,        /* ... at 0 */
+    JO_COV_MU_FLOOR,      /* OQPSK: MSEcalc's mean floored at 1e-6 */
+    JO_COV_OQ_MVR_FLOOR,  /* OQPSK meter: mvr floored at 1e-9 */
+    JO_COV_OQ_TEBNO_HI,   /* ... tebno > 50 */
+    JO_COV_OQ_TEBNO_LO,   /* ... tebno < 0 */
+    JO_COV_OQ_NAN,        /* ... tebno NaN */
+    JO_COV_MSK_NAN,       /* MSK meter: tebno NaN */
+    JO_COV_MSK_TEBNO_HI,  /* ... tebno > 50 */
+    JO_COV_M2_COUNTDOWN2, /* OQPSK slot: mixer2 set when countdown2 ran out */
+    JO_COV_M2_RULE,       /* slot: mixer2 set by the unlocked rule (OQPSK: more than 3 Hz off; MSK: any difference) */
+    JO_COV_AFC_RECENTRE,  /* slot: mixer_center moved to mixer2 */
+    JO_COV_AFC_CLAMP_LO,  /* ... and held at lockingbw / 2 */
+    JO_COV_AFC_CLAMP_HI,  /* ... at Fs / 2 - lockingbw / 2 */
+    JO_DEMOD_NCOV
+};
+void jo_demod_coverage(jo_demod *d, long *out);
+/* tebno of the EbNo meter's last update as computed, in front of its NaN / 50 / 0 lines: how far a taken line was from not being taken */
+double jo_demod_get_tebno_raw(jo_demod *d);
+/* st_osc's and mixer2's frequency, and the carrier loop filter's last two inputs and outputs, newest first (x1, y1) */
+typedef struct { double st_freq, m2_freq, lf_x1, lf_x2, lf_y1, lf_y2; } jo_loop_state;
+void jo_demod_loop_state(jo_demod *d, int set, jo_loop_state *s);
 
 /* stand-alone pieces for unit tests */
 /* RootRaisedCosine::design (JAERO/DSP.h:316-338); returns number of points written */

@@ -505,7 +505,7 @@ static void boqpsk_track_sample(jo_burst *d, long sample, double val_to_demod, d
         d->rotator = cmul(d->rotator, cexp_i(d->rotator_freq));
         sig2 = cmul(sig2, d->rotator);
         double sig2abs = hypot(sig2.re, sig2.im);
-        oqpsk_ebno_update(&d->ebno, sig2abs);
+        oqpsk_ebno_update(&d->ebno, sig2abs, NULL);
         if (fabs(d->cntr - ((128.0 + 128.0 + 128.0) * SPS)) < 0.5) burst_event(d, sample, JO_EV_EBNO, d->ebno.EbNo);
         sig2 = cscale(sig2, agc_update(d->agc2, sig2abs));
         double abval = hypot(sig2.re, sig2.im);
@@ -874,7 +874,7 @@ static void bmsk_track_sample(jo_burst *d, long sample, double val_to_demod)
             sig2 = cmul(sig2, d->symboltone_averotator);
             d->rotator = cmul(d->rotator, cexp_i(d->rotator_freq));
             sig2 = cmul(sig2, d->rotator);
-            msk_ebno_update(&d->ebno, hypot(sig2.re, sig2.im));
+            msk_ebno_update(&d->ebno, hypot(sig2.re, sig2.im), NULL);
             if (d->cntr == d->endRotation + (200 * SPS)) burst_event(d, sample, JO_EV_EBNO, d->ebno.EbNo);
             sig2 = cscale(sig2, agc_update(d->agc2, hypot(sig2.re, sig2.im)));
             double abval = hypot(sig2.re, sig2.im);

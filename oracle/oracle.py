@@ -84,11 +84,17 @@ def lib():
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
         L.jo_demod_capture_symbols.argtypes = [C.c_void_p, C.c_int]
         L.jo_demod_pending_soft.argtypes = [C.c_void_p]
-        for name in ("jo_demod_get_mse", "jo_demod_get_freq_est", "jo_demod_get_freq_center", "jo_demod_get_ebno"):
+        for name in ("jo_demod_get_mse", "jo_demod_get_freq_est", "jo_demod_get_freq_center", "jo_demod_get_ebno", "jo_demod_get_tebno_raw"):
             f = getattr(L, name)
             f.restype = C.c_double
             f.argtypes = [C.c_void_p]
         L.jo_demod_capture_prefiltered.argtypes = [C.c_void_p, C.c_int]
+        L.jo_demod_write_f64.restype = C.c_long
+        L.jo_demod_write_f64.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+        L.jo_demod_coverage.restype = None
+        L.jo_demod_coverage.argtypes = [C.c_void_p, C.c_void_p]
+        L.jo_demod_loop_state.restype = None
+        L.jo_demod_loop_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.jo_demod_take_prefiltered.restype = C.c_long
         L.jo_demod_take_prefiltered.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
         for name in ("jo_demod_get_pre_freq", "jo_demod_get_pre_freq_sum"):
@@ -168,8 +174,18 @@ def lib():
     return _lib
 
 
+class LoopState(C.Structure):
+    """jo_loop_state: st_osc's and mixer2's frequency, the carrier loop filter's last two inputs and outputs (x1, y1 the newest)"""
+    _fields_ = [(k, C.c_double) for k in ("st_freq", "m2_freq", "lf_x1", "lf_x2", "lf_y1", "lf_y2")]
+
+
 class Demod:
     """One reference-semantics demodulator object (OqpskDemodulator or MskDemodulator)."""
+
+    # jo_demod_coverage's order (jaero_oracle.h JO_COV_*)
+    COVERAGE = ("clip", "ec_pi", "lf_pi2_pos", "lf_pi2_neg", "st_low", "st_high", "sym_gated", "soft_255", "soft_0", "mu_floor",
+                "oq_mvr_floor", "oq_tebno_hi", "oq_tebno_lo", "oq_nan", "msk_nan", "msk_tebno_hi", "m2_countdown2", "m2_rule",
+                "afc_recentre", "afc_clamp_lo", "afc_clamp_hi")
 
     def __init__(self, settings: Settings, afc=False, sql=False, cpu_reduce=False, capture_symbols=False, capture_prefiltered=False):
         self.L = lib()
@@ -197,8 +213,30 @@ class Demod:
         self.L.jo_demod_center_freq_changed(self.h, float(f))
 
     def write(self, pcm: np.ndarray):
+        """int16 samples as writeData takes them; a float64 array (tests only) goes in as it is, on the same scale"""
+        if np.asarray(pcm).dtype == np.float64:
+            pcm = np.ascontiguousarray(pcm)
+            self.L.jo_demod_write_f64(self.h, pcm.ctypes.data, pcm.shape[0])
+            return
         pcm = np.ascontiguousarray(pcm, dtype=np.int16)
         self.L.jo_demod_write(self.h, pcm.ctypes.data, pcm.shape[0])
+
+    def coverage(self) -> dict:
+        """times each branch of the sample loop, the slot function and the meter was taken by this object so far"""
+        out = np.zeros(len(self.COVERAGE), dtype=np.int64)
+        self.L.jo_demod_coverage(self.h, out.ctypes.data)
+        return {k: int(v) for k, v in zip(self.COVERAGE, out)}
+
+    @property
+    def loop_state(self) -> dict:
+        st = LoopState()
+        self.L.jo_demod_loop_state(self.h, 0, C.byref(st))
+        return {k: getattr(st, k) for k, _ in LoopState._fields_}
+
+    def set_loop_state(self, **fields):
+        """the named fields of jo_loop_state replaced, the others written back as read"""
+        st = LoopState(**dict(self.loop_state, **{k: float(v) for k, v in fields.items()}))
+        self.L.jo_demod_loop_state(self.h, 1, C.byref(st))
 
     def take_soft(self) -> np.ndarray:
         out = []
@@ -259,6 +297,11 @@ class Demod:
     @property
     def ebno(self):
         return self.L.jo_demod_get_ebno(self.h)
+
+    @property
+    def tebno_raw(self):
+        """tebno of the meter's last update in front of its NaN / 50 / 0 lines"""
+        return self.L.jo_demod_get_tebno_raw(self.h)
 
     @property
     def pending(self):

@@ -78,6 +78,18 @@ def test_coarse_hooks_refuse_a_null_context():
     assert b"jaero_debug_coarse_peek" in L.jaero_last_error()
 
 
+def test_loop_hooks_refuse_a_null_context():
+    """jaero_debug_loop_poke / _peek: JAERO_EINVAL before any HIP call (burst bank, bad channel, bad values: tests/test_gpu_loop_branches.py)."""
+    L = capi.lib()
+    st = capi.LoopState(10500.0, 8000.0, 0.0, 0.0, 0.0, 0.0)
+    assert C.sizeof(capi.LoopState) == 48  # 6 doubles
+    assert L.jaero_debug_loop_poke(None, 0, C.byref(st)) == capi.E_INVAL
+    assert b"jaero_debug_loop_poke" in L.jaero_last_error()
+    assert L.jaero_debug_loop_peek(None, 0, C.byref(st)) == capi.E_INVAL
+    assert b"jaero_debug_loop_peek" in L.jaero_last_error()
+    assert st.st_freq == 10500.0 and st.lf_y2 == 0.0
+
+
 def test_burst_acquisition_hooks_refuse_a_null_context():
     """jaero_debug_burst_geom / _hilbert / _read_hist / _poke_cv / _trident: JAERO_EINVAL before any HIP call (a bank that is not a burst bank, bad
     channels, sizes, lists and grids: tests/test_gpu_burst_acq.py)."""
