@@ -6,9 +6,8 @@
 #include "k_aerol_isu.h"
 #include "sweep_host.h"
 
-struct jaero_aerol_ctx
+struct jaero_aerol_ctx : DevHandle // (never poisoned, and ordered by its caller: a write moves last_stream without an event)
 {
-    int device = 0;
     AGeom g{}; // fb = 8400: nch, nchp and fb only
     APtrs p{};
     bool cchan = false; // fb = 8400: the C-channel pipeline (aerolc.h) on cg / cp
@@ -17,7 +16,6 @@ struct jaero_aerol_ctx
     DevMem mem;
     int16_t *d_soft = nullptr; int *d_counts = nullptr; int stage_stride = 0;
     unsigned long long *d_vhist = nullptr; // k_viterbi_lanes history scratch (large banks only)
-    hipStream_t last_stream = nullptr;
     // the three kernel classes of a write: 0 = the bit walk, 1 = k_viterbi + overlap update, 2 = the end of a block / frame; 3 = the sweep's kernels
     // (jaero_aerol_read_all), 4 = k_dcd_link, 5 = k_aerol_isu (jaero_aerol_profile2_read)
     KernelTimer timer{6};
@@ -66,9 +64,8 @@ static void aerol_unlink(jaero_aerol_ctx *c)
 {
     jaero_ctx *b = c->link;
     if (!b) return;
-    hipSetDevice(c->device);
-    hipStreamSynchronize(c->last_stream);
-    hipStreamSynchronize(b->last_stream);
+    (void)c->quiesce();
+    (void)b->quiesce(); // (on the same device: jaero_aerol_link_dcd)
     std::vector<int> f(b->o_nch);
     if (!b->poisoned && hipMemcpy(f.data(), b->o_flags, sizeof(int) * f.size(), hipMemcpyDeviceToHost) == hipSuccess)
         for (int ch = 0; ch < b->o_nch; ch++) b->m.flags[ch] = (b->m.flags[ch] & ~JF_DCD) | (f[ch] & JF_DCD);
@@ -97,14 +94,14 @@ extern "C" int jaero_aerol_link_dcd(jaero_aerol_ctx *c, jaero_ctx *b)
     if (b->burst && b->bg.kind == JAERO_KIND_BURST_OQPSK)
         return fail(JAERO_ENOTSUP, "%s: the reference connects DataCarrierDetect to no slot of the burst OQPSK demodulator (mainwindow.cpp:234-237)", who);
     if (b->burst) return fail(JAERO_ENOTSUP, "%s: burst MSK banks are not linked yet (only continuous banks are)", who);
-    if (b->poisoned) return fail(JAERO_EHIP, "%s: an earlier jaero_write of the bank failed part-way; destroy it and create a new one", who);
+    POISONCHK(b, who, POISON_LINKED_BANK);
     HIPCHK(hipSetDevice(c->device));
     int rc = 0;
     if (!c->d_dcdmark && (rc = dalloc(c->mem, &c->d_dcdmark, (size_t)c->g.nchp, false))) return rc;
     // emissions from before the link are not replayed: the marks start empty, behind whatever the Aero-L bank still has in flight on its stream,
     // and are empty before this call returns (a write on any stream, blocking or not, finds them so)
     HIPCHK(hipMemsetAsync(c->d_dcdmark, 0, sizeof(int) * (size_t)c->g.nchp, c->last_stream));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     if (c->cchan) c->cp.dcdmark = c->d_dcdmark; else c->p.dcdmark = c->d_dcdmark;
     c->link = b;
     std::lock_guard<std::mutex> lk(g_links_mu);
@@ -466,8 +463,7 @@ extern "C" int jaero_aerol_isu_enable(jaero_aerol_ctx *c, int msg_capacity)
     if (msg_capacity < 0) return fail(JAERO_EINVAL, "%s: msg_capacity < 0", who);
     if (c->g.burst) return fail(JAERO_ENOTSUP, "%s: burst-mode bank (the R / T channel reassembly, RISUData and the T packets' units, is not on the device)", who);
     if (c->cchan) return fail(JAERO_ENOTSUP, "%s: fb = 8400 (AeroL::DecodeC never calls ISUData)", who);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     if (msg_capacity == 0)
     {
         c->isu_on = false;
@@ -505,7 +501,7 @@ extern "C" int jaero_aerol_isu_enable(jaero_aerol_ctx *c, int msg_capacity)
     HIPCHK(hipMemset(c->isu.stats, 0, sizeof(long long) * (size_t)g.nchp * 4));
     hipLaunchKernelGGL(k_aerol_isu_clear_overflow, dim3(g.nchp / 64), dim3(64), 0, c->last_stream, g, c->p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     c->p.isumark = c->d_isumark;
     c->isu_on = true;
     return 0;
@@ -522,8 +518,7 @@ extern "C" int jaero_aerol_isu_stats(jaero_aerol_ctx *c, long long *stats)
     const char *who = "jaero_aerol_isu_stats";
     if (!c || !stats) return fail(JAERO_EINVAL, "%s: null ctx / stats", who);
     if (!c->isu.stats) return fail(JAERO_EINVAL, "%s: this bank never enabled the reassembly (jaero_aerol_isu_enable)", who);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     HIPCHK(hipMemcpy(stats, c->isu.stats, sizeof(long long) * (size_t)c->g.nch * 4, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -614,7 +609,7 @@ extern "C" int jaero_aerol_tick_dcd(jaero_aerol_ctx *c, int *dcd_out_host)
     if (dcd_out_host)
     {
         HIPCHK(hipMemcpyAsync(dcd_out_host, c->d_counts, sizeof(int) * c->g.nch, hipMemcpyDeviceToHost, c->last_stream));
-        HIPCHK(hipStreamSynchronize(c->last_stream));
+        QUIESCE(c);
     }
     HIPCHK(hipGetLastError());
     return 0;

@@ -328,7 +328,7 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         c->timer.end(pi, st);
     }
     int first = 1;
-    c->poisoned = true; // the history push above is idempotent (same slots if the write is repeated); from here on state advances
+    PoisonGuard guard(*c); // the history push above is idempotent (same slots if the write is repeated); from here on state advances
     for (int pos = 0; pos < nsamples;)
     {
         const int n = (nsamples - pos) < g.maxseg ? (nsamples - pos) : g.maxseg;
@@ -351,6 +351,7 @@ static int burst_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layou
         pos += n;
     }
     HIPCHK(hipGetLastError());
+    guard.commit();
     return 0;
 }
 
@@ -363,8 +364,7 @@ static int burst_rebank(jaero_ctx *c, const jaero_settings *s)
     LINKCHK(c);
     if (c->poisoned) return fail(JAERO_EHIP, "jaero_set_settings: a launch inside an earlier jaero_write failed; this bank's state cannot be carried over");
     const BGeom og = c->bg;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     jaero_ctx *n = nullptr;
     int rc = jaero_create(c->device, og.nch, s, 0, c->flags, c->max_write, c->soft_cap_req, &n);
     if (rc) return rc;
@@ -437,8 +437,7 @@ static int burst_hook_enter(jaero_ctx *c, const char *who, int channel, bool poi
     if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
     if (!c->burst) return fail(JAERO_EINVAL, "%s: not a burst bank", who);
     if (channel < 0 || channel >= c->bg.nch) return fail(JAERO_EINVAL, "%s: channel %d outside [0, %d)", who, channel, c->bg.nch);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     if (poison) c->poisoned = true;
     return 0;
 }
@@ -493,6 +492,24 @@ extern "C" int jaero_debug_burst_read_hist(jaero_ctx *c, int ch, long long first
     for (int i = 0; i < n; i++) out[i] = ring[(size_t)((first + i) % H)];
     return 0;
 }
+// a channel's column of a [group][slot][lane] ring, by absolute sample index (sample a lives at slot a mod len, mathematical modulo)
+static int burst_ring_column(double *ring, int len, int ch, long long first, int n, double *host, bool to_device)
+{
+    const long long R = len;
+    const int slot = (int)(((first % R) + R) % R), n1 = n < len - slot ? n : len - slot;
+    double *col = ring + (size_t)(ch >> 6) * len * 64 + (ch & 63);
+    if (to_device)
+    {
+        HIPCHK(hipMemcpy2D(col + (size_t)slot * 64, sizeof(double) * 64, host, sizeof(double), sizeof(double), (size_t)n1, hipMemcpyHostToDevice));
+        if (n > n1) HIPCHK(hipMemcpy2D(col, sizeof(double) * 64, host + n1, sizeof(double), sizeof(double), (size_t)(n - n1), hipMemcpyHostToDevice));
+    }
+    else
+    {
+        HIPCHK(hipMemcpy2D(host, sizeof(double), col + (size_t)slot * 64, sizeof(double) * 64, sizeof(double), (size_t)n1, hipMemcpyDeviceToHost));
+        if (n > n1) HIPCHK(hipMemcpy2D(host + n1, sizeof(double), col, sizeof(double) * 64, sizeof(double), (size_t)(n - n1), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
 extern "C" int jaero_debug_burst_poke_cv(jaero_ctx *c, int ch, long long first, int n, const double *re)
 {
     if (!re) return fail(JAERO_EINVAL, "jaero_debug_burst_poke_cv: null input");
@@ -500,13 +517,7 @@ extern "C" int jaero_debug_burst_poke_cv(jaero_ctx *c, int ch, long long first, 
         return fail(JAERO_EINVAL, "jaero_debug_burst_poke_cv: n %d (1 .. cv_len %d samples from an index within +- 2^40)", n, c->bg.cv_len);
     int rc = burst_hook_enter(c, "jaero_debug_burst_poke_cv", ch, true);
     if (rc) return rc;
-    const BGeom &g = c->bg;
-    const long long R = g.cv_len;
-    const int slot = (int)(((first % R) + R) % R), n1 = n < g.cv_len - slot ? n : g.cv_len - slot; // sample a lives at a mod cv_len (k_burst_front: s_cv = n0 % cv_len)
-    double *row = c->bp.cvre + (size_t)(ch >> 6) * g.cv_len * 64 + (ch & 63);
-    HIPCHK(hipMemcpy2D(row + (size_t)slot * 64, sizeof(double) * 64, re, sizeof(double), sizeof(double), (size_t)n1, hipMemcpyHostToDevice));
-    if (n > n1) HIPCHK(hipMemcpy2D(row, sizeof(double) * 64, re + n1, sizeof(double), sizeof(double), (size_t)(n - n1), hipMemcpyHostToDevice));
-    return 0;
+    return burst_ring_column(c->bp.cvre, c->bg.cv_len, ch, first, n, const_cast<double *>(re), true); // sample a lives at a mod cv_len (k_burst_front: s_cv = n0 % cv_len)
 }
 static_assert(sizeof(jaero_trident_result) == sizeof(TriResult) && offsetof(jaero_trident_result, metric) == offsetof(TriResult, metric), "jaero_trident_result is TriResult");
 extern "C" int jaero_debug_burst_trident(jaero_ctx *c, const int *channels, const int *ev_pos, int nlist, long long n0, int grid, jaero_trident_result *results, int *nchanged)
@@ -604,24 +615,6 @@ extern "C" int jaero_debug_burst_front(jaero_ctx *c, const int16_t *pcm, int lay
     if (count) HIPCHK(hipMemcpy(ev_list, c->bp.ev_list, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
     return 0;
 }
-// a channel's column of a [group][slot][lane] ring, by absolute sample index (sample a lives at slot a mod len, mathematical modulo)
-static int burst_ring_column(double *ring, int len, int ch, long long first, int n, double *host, bool to_device)
-{
-    const long long R = len;
-    const int slot = (int)(((first % R) + R) % R), n1 = n < len - slot ? n : len - slot;
-    double *col = ring + (size_t)(ch >> 6) * len * 64 + (ch & 63);
-    if (to_device)
-    {
-        HIPCHK(hipMemcpy2D(col + (size_t)slot * 64, sizeof(double) * 64, host, sizeof(double), sizeof(double), (size_t)n1, hipMemcpyHostToDevice));
-        if (n > n1) HIPCHK(hipMemcpy2D(col, sizeof(double) * 64, host + n1, sizeof(double), sizeof(double), (size_t)(n - n1), hipMemcpyHostToDevice));
-    }
-    else
-    {
-        HIPCHK(hipMemcpy2D(host, sizeof(double), col + (size_t)slot * 64, sizeof(double) * 64, sizeof(double), (size_t)n1, hipMemcpyDeviceToHost));
-        if (n > n1) HIPCHK(hipMemcpy2D(host + n1, sizeof(double), col, sizeof(double) * 64, sizeof(double), (size_t)(n - n1), hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
 extern "C" int jaero_debug_burst_front_peek(jaero_ctx *c, int ch, jaero_burst_front_state *out, int ring, long long first, int n, double *ring_out)
 {
     if (ring > JAERO_FRONT_RING_BT || (ring >= 0 && (!ring_out || n <= 0))) return fail(JAERO_EINVAL, "jaero_debug_burst_front_peek: ring %d, n %d (a ring 0 .. 7 with n >= 1 and an output, or ring < 0)", ring, n);
@@ -641,12 +634,11 @@ extern "C" int jaero_debug_burst_front_peek(jaero_ctx *c, int ch, jaero_burst_fr
     }
     if (out)
     {
-        double *d[5] = {&out->agc_sum, &out->ma1_re, &out->ma1_im, &out->mav1_sum, &out->lastdy};
-        const int df[5] = {BS_AGC_SUM, BS_MA1_RE, BS_MA1_IM, BS_MAV1_SUM, BS_LASTDY};
-        for (int k = 0; k < 5; k++) HIPCHK(hipMemcpy(d[k], p.S + (size_t)df[k] * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
-        int *q[6] = {&out->cntdown, &out->maxposcd, &out->tri_ptr, &out->ev_pos, &out->ev_cnt, &out->bt_hold};
-        const int qf[6] = {BI_CNTDOWN, BI_MAXPOSCD, BI_TRI_PTR, BI_EV_POS, BI_EV_CNT, BI_BT_HOLD};
-        for (int k = 0; k < 6; k++) HIPCHK(hipMemcpy(q[k], p.I + (size_t)qf[k] * nchp + ch, sizeof(int), hipMemcpyDeviceToHost));
+        const std::pair<int, double *> d[] = {{BS_AGC_SUM, &out->agc_sum}, {BS_MA1_RE, &out->ma1_re}, {BS_MA1_IM, &out->ma1_im}, {BS_MAV1_SUM, &out->mav1_sum},
+                                              {BS_LASTDY, &out->lastdy}};
+        const std::pair<int, int *> q[] = {{BI_CNTDOWN, &out->cntdown}, {BI_MAXPOSCD, &out->maxposcd}, {BI_TRI_PTR, &out->tri_ptr}, {BI_EV_POS, &out->ev_pos},
+                                           {BI_EV_CNT, &out->ev_cnt}, {BI_BT_HOLD, &out->bt_hold}};
+        if ((rc = peek_fields(p.S, nchp, ch, d)) || (rc = peek_fields(p.I, nchp, ch, q))) return rc;
     }
     return 0;
 }
@@ -771,17 +763,16 @@ extern "C" int jaero_debug_burst_track_peek(jaero_ctx *c, int ch, jaero_burst_tr
     const BPtrs &p = c->bp;
     const int nchp = c->bg.nchp;
     memset(out, 0, sizeof *out);
-    int *q[16] = {&out->startstop, &out->cntr, &out->yui, &out->insertpre, &out->nrx, &out->soft_cnt, &out->sym_cnt, &out->ev_cnt, &out->overflow, &out->msema_pos,
-                  &out->fir_pos, &out->eb_pos, &out->dly_pos, &out->d8_pos, &out->a1_pos, &out->gcnt};
-    const int qf[16] = {BI_STARTSTOP, BI_CNTR, BI_YUI, BI_INSERTPRE, BI_NRX, BI_SOFT_CNT, BI_SYM_CNT, BI_EV_CNT, BI_OVERFLOW, BI_MSEMA_POS,
-                        BI_FIR_POS, BI_EB_POS, BI_DLY_POS, BI_D8_POS, BI_A1_POS, BI_GCNT};
-    for (int k = 0; k < 16; k++) HIPCHK(hipMemcpy(q[k], p.I + (size_t)qf[k] * nchp + ch, sizeof(int), hipMemcpyDeviceToHost));
-    double *d[16] = {&out->mse, &out->lastmse, &out->m2_freq, &out->st_freq, &out->vol_gain, &out->eb_ebno, &out->rot_freq, &out->agc2_sum, &out->eb_esum, &out->eb_e2sum,
-                     &out->msema_sum, &out->mc_freq, &out->diff_last, &out->m2_ptr, &out->st_ptr, &out->stq_ptr};
-    const int df[16] = {BS_MSE, BS_LASTMSE, BS_M2_FREQ, BS_ST_FREQ, BS_VOL_GAIN, BS_EB_EBNO, BS_ROT_FREQ, BS_AGC2_SUM, BS_EB_ESUM, BS_EB_E2SUM,
-                        BS_MSEMA_SUM, BS_MC_FREQ, BS_DIFF_LAST, BS_M2_PTR, BS_ST_PTR, BS_STQ_PTR};
-    for (int k = 0; k < 16; k++) HIPCHK(hipMemcpy(d[k], p.S + (size_t)df[k] * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    const std::pair<int, int *> q[] = {{BI_STARTSTOP, &out->startstop}, {BI_CNTR, &out->cntr}, {BI_YUI, &out->yui}, {BI_INSERTPRE, &out->insertpre},
+                                       {BI_NRX, &out->nrx}, {BI_SOFT_CNT, &out->soft_cnt}, {BI_SYM_CNT, &out->sym_cnt}, {BI_EV_CNT, &out->ev_cnt},
+                                       {BI_OVERFLOW, &out->overflow}, {BI_MSEMA_POS, &out->msema_pos}, {BI_FIR_POS, &out->fir_pos}, {BI_EB_POS, &out->eb_pos},
+                                       {BI_DLY_POS, &out->dly_pos}, {BI_D8_POS, &out->d8_pos}, {BI_A1_POS, &out->a1_pos}, {BI_GCNT, &out->gcnt}};
+    const std::pair<int, double *> d[] = {{BS_MSE, &out->mse}, {BS_LASTMSE, &out->lastmse}, {BS_M2_FREQ, &out->m2_freq}, {BS_ST_FREQ, &out->st_freq},
+                                          {BS_VOL_GAIN, &out->vol_gain}, {BS_EB_EBNO, &out->eb_ebno}, {BS_ROT_FREQ, &out->rot_freq}, {BS_AGC2_SUM, &out->agc2_sum},
+                                          {BS_EB_ESUM, &out->eb_esum}, {BS_EB_E2SUM, &out->eb_e2sum}, {BS_MSEMA_SUM, &out->msema_sum}, {BS_MC_FREQ, &out->mc_freq},
+                                          {BS_DIFF_LAST, &out->diff_last}, {BS_M2_PTR, &out->m2_ptr}, {BS_ST_PTR, &out->st_ptr}, {BS_STQ_PTR, &out->stq_ptr}};
+    if ((rc = peek_fields(p.I, nchp, ch, q))) return rc;
+    return peek_fields(p.S, nchp, ch, d);
 }
 extern "C" int jaero_debug_burst_track_fill(jaero_ctx *c, int soft_value, double sym_value)
 {
@@ -818,6 +809,6 @@ extern "C" int jaero_debug_burst_track_center_freq(jaero_ctx *c, int ch, double 
     if (c->bg.kind != JAERO_KIND_BURST_MSK) return fail(JAERO_EINVAL, "jaero_debug_burst_track_center_freq: not a burst MSK bank (burst OQPSK's slot is empty)");
     c->poisoned = true;
     if ((rc = burst_launch_center_freq(c, ch, hz))) return rc;
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     return 0;
 }

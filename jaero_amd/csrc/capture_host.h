@@ -1,6 +1,6 @@
 // capture_host.h -- host side of the channeliser's capture front end (k_chan_capture.h; jaero_chan3_*, DESIGN 18 "Capture front end").
 //
-// A capture handle is a jaero_chan whose input history is fp64 (ChanCapture::d_z, used exactly as d_in is: previous hop, then what waits;
+// A capture's front end is a ChanFront whose input history is fp64 (ChanCapture::d_z, used exactly as d_in is: previous hop, then what waits;
 // the tail of one buffer becomes the head of the other behind every write that completed a block) and is filled by k_capture_stage from
 // the raw samples.  The raw history is the last K - 1 pairs in the raw format (two buffers as well: a write shorter than K - 1 would
 // otherwise copy onto itself).  The counts T (capture samples taken) and m (staged samples made) live here, as 64-bit integers; every
@@ -51,7 +51,7 @@ static int capture_check_staged(const char *who, int max_write_iq, long long L, 
 }
 
 // The capture's half of a front end, behind chan_build_front: the raw and the fp64 histories and the resampler's phases.
-static int capture_build(jaero_chan *c, const jaero_capture *cap, long long L, long long Mr, bool resample, int max_write_iq, long long smax)
+static int capture_build(ChanFront *c, const jaero_capture *cap, long long L, long long Mr, bool resample, int max_write_iq, long long smax)
 {
     int rc = 0;
     c->cap.reset(new (std::nothrow) ChanCapture());
@@ -95,7 +95,7 @@ extern "C" int jaero_chan3_create(int device, const jaero_capture *cap, int deci
     if (!c) return fail(JAERO_ENOMEM, "jaero_chan3_create: out of memory");
     int rc = chan_build(c, device, decim, out_rate, nchannels, ch, taps, ntaps, max_write_iq, smax);
     if (rc) return rc;
-    if ((rc = capture_build(c.get(), cap, L, Mr, resample, max_write_iq, smax))) return rc;
+    if ((rc = capture_build(c->own.get(), cap, L, Mr, resample, max_write_iq, smax))) return rc;
     *out = c.release();
     return 0;
 }
@@ -124,25 +124,12 @@ static void capture_launch(const ChanCapture &k, const void *raw, long long nraw
     else go(std::integral_constant<int, JAERO_IQ_CF32>());
 }
 
-// jaero_chan_write for a capture handle: the raw copy, the staging kernel, then the channeliser's own kernels over the fp64 history
-static int capture_write(jaero_chan *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who)
+// chan_write for a capture's front end: the raw copy, the staging kernel, then the channeliser's own kernels over the fp64 history
+static int capture_write(ChanFront *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who)
 {
-    if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "%s: bad arguments", who);
-    if (niq > c->max_write_iq) return fail(JAERO_EINVAL, "%s: niq %d exceeds max_write_iq %d", who, niq, c->max_write_iq);
-    if (c->poisoned) return fail(JAERO_EHIP, "%s: an earlier write of this channeliser failed part-way; destroy it and create a new one", who);
-    ChanCapture &k = *c->cap;
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    if (st != c->last_stream) // as jaero_chan_write
-    {
-        if (!c->order_ev) HIPCHK(hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->order_ev, c->last_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->order_ev, 0));
-        c->last_stream = st;
-    }
-    *nout = 0;
-    c->last_nout = 0;
-    k.last_n = 0; k.last_first = k.m; k.last_ptr = nullptr;
+    { const int rc = chan_write_enter(c, iq, niq, st, nout, who); if (rc) return rc; }
+    ChanCapture &k = *c->cap;
     if (niq == 0) return 0;
     // every count of this write, before the first copy or launch
     const int hist = k.K - 1;
@@ -158,7 +145,7 @@ static int capture_write(jaero_chan *c, const void *iq, int niq, int is_device_p
 
     char *raw = k.d_raw[k.rcur];
     HIPCHK(hipMemcpyAsync(raw + (size_t)hist * k.bps, iq, (size_t)k.bps * (size_t)niq, is_device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    c->poisoned = true; // from here on the histories, the counts and the device buffers advance together or not at all
+    PoisonGuard guard(*c); // from here on the histories, the counts and the device buffers advance together or not at all
     double2 *z = k.d_z[c->cur];
     double2 *dst = z + CHAN_HP + c->pending;
     if (nst > 0)
@@ -184,28 +171,25 @@ static int capture_write(jaero_chan *c, const void *iq, int niq, int is_device_p
         c->timer.end(pi, st);
         { const int rc = chan_after_fwd(c, nblk, total, z, k.d_z[c->cur ^ 1], sizeof(double2), st); if (rc) return rc; }
     }
-    HIPCHK(hipGetLastError());
-    c->last_nout = *nout = nblk * c->Mo;
-    c->poisoned = false;
-    return 0;
+    return chan_write_leave(c, nblk, nout, guard);
 }
 
 extern "C" int jaero_chan3_write(jaero_chan *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "jaero_chan3_write: bad arguments");
     CHANVIEWCHK(c, "jaero_chan3_write", "jaero_split_write");
-    if (!c->cap) return jaero_chan_write(c, (const int16_t *)iq, niq, is_device_ptr, stream, nout);
-    return capture_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan3_write");
+    if (!c->own->cap) return jaero_chan_write(c, (const int16_t *)iq, niq, is_device_ptr, stream, nout);
+    return capture_write(c->own.get(), iq, niq, is_device_ptr, stream, nout, "jaero_chan3_write");
 }
 
 extern "C" int jaero_chan3_feed(jaero_chan *c, jaero_ctx *bank, const void *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !bank || !nout) return fail(JAERO_EINVAL, "jaero_chan3_feed: null argument");
     CHANVIEWCHK(c, "jaero_chan3_feed", "jaero_split_feed");
-    if (!c->cap) return jaero_chan_feed(c, bank, (const int16_t *)iq, niq, is_device_ptr, stream, nout);
+    if (!c->own->cap) return jaero_chan_feed(c, bank, (const int16_t *)iq, niq, is_device_ptr, stream, nout);
     const int rc0 = chan_feed_check(c, bank, "jaero_chan3_feed");
     if (rc0) return rc0;
-    const int rc = capture_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan3_feed");
+    const int rc = capture_write(c->own.get(), iq, niq, is_device_ptr, stream, nout, "jaero_chan3_feed");
     if (rc || *nout <= 0) return rc;
     return jaero_write(bank, c->d_pcm, *nout, JAERO_PCM_CHANNEL_MAJOR, 1, stream);
 }
@@ -215,12 +199,11 @@ extern "C" int jaero_chan3_read_staged(jaero_chan *c, double *reim, int cap_pair
 {
     if (!c || !npairs || !first_index || cap_pairs < 0 || (cap_pairs > 0 && !reim)) return fail(JAERO_EINVAL, "jaero_chan3_read_staged: bad arguments");
     CHANVIEWCHK(c, "jaero_chan3_read_staged", "a stand-alone handle (a splitter has no jaero_chan3_read_staged)");
-    if (!c->cap) return fail(JAERO_EINVAL, "jaero_chan3_read_staged: the handle has no capture front end (jaero_chan3_create)");
-    CHANPOISONCHK(c, "jaero_chan3_read_staged");
-    const ChanCapture &k = *c->cap;
+    if (!c->own->cap) return fail(JAERO_EINVAL, "jaero_chan3_read_staged: the handle has no capture front end (jaero_chan3_create)");
+    POISONCHK(c->front, "jaero_chan3_read_staged", POISON_CHAN);
+    const ChanCapture &k = *c->own->cap;
     if (cap_pairs < k.last_n) return fail(JAERO_EINVAL, "jaero_chan3_read_staged: cap_pairs %d is below the last write's %d staged samples", cap_pairs, k.last_n);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c->front);
     *npairs = k.last_n;
     *first_index = k.last_first;
     if (k.last_n > 0) HIPCHK(hipMemcpy(reim, k.last_ptr, sizeof(double2) * (size_t)k.last_n, hipMemcpyDeviceToHost));
@@ -230,5 +213,5 @@ extern "C" int jaero_chan3_read_staged(jaero_chan *c, double *reim, int cap_pair
 extern "C" int jaero_chan3_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset)
 {
     if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_chan3_profile_read: bad arguments");
-    return c->timer.read(c->device, 4 + which, total_ms, launches, reset);
+    return chan_timer_read(c, 4 + which, total_ms, launches, reset);
 }

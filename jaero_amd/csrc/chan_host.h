@@ -24,26 +24,38 @@ struct ChanCapture
     long long last_first = 0;
 };
 
-struct jaero_chan
+// A channeliser is two halves.  The front end consumes input: the histories, the spectrum d_spec of the blocks the last write completed, the
+// forward transform's twiddles, the counts, the optional capture, and the stream state every call of its outputs goes by.
+struct ChanOut;
+struct ChanFront : DevHandle
 {
-    int device = 0;
-    int decim = 0, out_rate = 0, nch = 0, max_write_iq = 0;
-    int M = 0, Mo = 0, nblk_max = 0;
+    int max_write_iq = 0, nblk_max = 0;
     DevMem mem;
     int *d_in[2] = {nullptr, nullptr}; // [2 Hp + max_write_iq] dwords (I, Q) each; d_in[cur] holds: previous hop, then `pending` samples
     int cur = 0, pending = 0;
     long long blocks_done = 0;
     double2 *d_spec = nullptr; // [nblk_max][N]
+    double2 *d_tw = nullptr;   // [N]: W_N^k (wg_fft14_e32)
+    std::unique_ptr<ChanCapture> cap; // null unless jaero_chan3_create or jaero_split_create gave a capture
+    KernelTimer timer{8};      // 0 k_chan_fwd, 4 k_capture_stage, 5 k_capture_fwd (the numbering is the outputs': their slots stay empty here)
+    std::vector<ChanOut *> outs; // whose kernels run behind the forward transform, in output order: one, or a splitter's
+};
+
+// An output turns d_spec into channels: the response, the synthesis' twiddles, the channels' parameters, the PCM, the survey and the activity.
+struct ChanOut
+{
+    ChanFront *front = nullptr; // whose d_spec it reads
+    int decim = 0, out_rate = 0, nch = 0;
+    int M = 0, Mo = 0;
+    DevMem mem;
     double2 *d_gm = nullptr;   // [M]
     double2 *d_twm = nullptr;  // [32]
-    double2 *d_tw = nullptr;   // [N]: W_N^k (wg_fft14_e32)
     ChanParam *d_par = nullptr;
     int16_t *d_pcm = nullptr;  // [nch][nout of the last write], capacity nch * nblk_max * Mo
     int last_nout = 0;
     std::vector<jaero_chan_channel> channels;
-    KernelTimer timer{8};      // 0 k_chan_fwd, 1 k_chan_synth, 2 k_chan_psd, 3 k_chan_level, 4 k_capture_stage, 5 k_capture_fwd,
+    KernelTimer timer{8};      // 1 k_chan_synth, 2 k_chan_psd, 3 k_chan_level,
                                // 6 k_chan_psd and 7 k_chan_level whenever the launch serves the activity (fused with the survey's part or not)
-    std::unique_ptr<ChanCapture> cap; // null unless the handle came from jaero_chan3_create
     // the survey (jaero_survey_*): nothing below exists before the first enable
     int survey = 0;            // bit 0 spectrum, bit 1 levels
     double *d_psd = nullptr;   // [N]: S
@@ -59,19 +71,15 @@ struct jaero_chan
     long long peak_blocks = 0; // blocks in P
     long long act_blocks = 0;  // blocks whose statistics were taken since enable / reset; channel c's count is act_blocks - act_start[c]
     std::vector<long long> act_start;
-    hipStream_t last_stream = nullptr;
-    hipEvent_t order_ev = nullptr;
-    bool poisoned = false;
-    // the splitter (split_host.h): its front end is a handle without outputs (nch = 0) whose `split` names it; each output is a view, a handle
-    // without a front end whose `front` names the splitter's (d_spec is the front's, nblk_max and last_stream follow it).  Both null: stand-alone.
-    jaero_chan *front = nullptr;
-    jaero_split *split = nullptr;
 };
 
-#define CHANPOISONCHK(c, who) do { if ((c)->poisoned || ((c)->front && (c)->front->poisoned)) return fail(JAERO_EHIP, who ": an earlier write of this channeliser failed part-way; destroy it and create a new one"); } while (0)
-
-// a splitter's view refuses the calls that consume input or own the handle, and names the splitter's call
-#define CHANVIEWCHK(c, who, use) do { if ((c)->front) return fail(JAERO_EINVAL, who ": the handle is an output of a splitter (jaero_split_output); use " use); } while (0)
+// The handle: an output, with the front end it owns -- or without one, as jaero_split_output hands it out: a view, whose front is its splitter's
+// (split_host.h).  A view refuses the calls that consume input or own the handle, and names the splitter's call.
+struct jaero_chan : ChanOut
+{
+    std::unique_ptr<ChanFront> own;
+};
+#define CHANVIEWCHK(c, who, use) do { if (!(c)->own) return fail(JAERO_EINVAL, who ": the handle is an output of a splitter (jaero_split_output); use " use); } while (0)
 
 static bool chan_channel_ok(const jaero_chan_channel &ch) { return __builtin_isfinite(ch.gain) && ch.gain > 0; }
 
@@ -110,10 +118,8 @@ static std::vector<double2> chan_response(const double *taps, int ntaps, int M)
 
 extern "C" void jaero_chan_destroy(jaero_chan *c)
 {
-    if (!c || c->front) return; // a view goes with its splitter (jaero_split_destroy)
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->last_stream);
-    if (c->order_ev) (void)hipEventDestroy(c->order_ev);
+    if (!c || !c->own) return; // a view goes with its splitter (jaero_split_destroy)
+    c->own->teardown();
     delete c;
 }
 
@@ -135,55 +141,56 @@ static int chan_check_create(const char *who, int decim, int out_rate, int nchan
     return 0;
 }
 
-// Everything behind the checks and the device.  smax = 0: an int16 handle (history d_in, max_write_iq samples a write); smax > 0: a capture
-// handle, whose fp64 history (capture_host.h) takes at most smax staged samples a write -- d_in is not allocated.
-//
-// A handle is two halves, built by two functions so that a splitter can build one front end and several outputs.  The front end: the
-// histories, the spectrum d_spec, the forward transform's twiddles d_tw, the counts (cur, pending, blocks_done) and the most blocks a write
-// completes.
-static int chan_build_front(jaero_chan *c, int device, int max_write_iq, long long smax)
+// Everything behind the checks and the device, in two functions so that a splitter can build one front end and several outputs.  smax = 0: an
+// int16 front end (history d_in, max_write_iq samples a write); smax > 0: a capture's, whose fp64 history (capture_host.h) takes at most smax
+// staged samples a write -- d_in is not allocated.
+static int chan_build_front(ChanFront *f, int device, int max_write_iq, long long smax)
 {
     int rc = 0;
-    c->device = device; c->max_write_iq = max_write_iq;
-    c->nblk_max = smax > 0 ? (int)((smax + 1) / CHAN_HP + 1) : max_write_iq / CHAN_HP + 1;
+    f->device = device; f->max_write_iq = max_write_iq;
+    f->nblk_max = smax > 0 ? (int)((smax + 1) / CHAN_HP + 1) : max_write_iq / CHAN_HP + 1; // the most blocks a write completes
     if (smax == 0)
     {
         const size_t nin = 2 * (size_t)CHAN_HP + (size_t)max_write_iq;
-        DA(c->mem, c->d_in[0], nin);
-        DA(c->mem, c->d_in[1], nin);
+        DA(f->mem, f->d_in[0], nin);
+        DA(f->mem, f->d_in[1], nin);
     }
-    DA(c->mem, c->d_spec, (size_t)c->nblk_max * CHAN_N);
-    DA(c->mem, c->d_tw, CHAN_N);
-    HIPCHK(hipMemcpy(c->d_tw, twiddles(CHAN_N, CHAN_N).data(), sizeof(double2) * CHAN_N, hipMemcpyHostToDevice));
+    DA(f->mem, f->d_spec, (size_t)f->nblk_max * CHAN_N);
+    DA(f->mem, f->d_tw, CHAN_N);
+    HIPCHK(hipMemcpy(f->d_tw, twiddles(CHAN_N, CHAN_N).data(), sizeof(double2) * CHAN_N, hipMemcpyHostToDevice));
     HIPCHK(hipFuncSetAttribute((const void *)k_chan_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, C6_XCH * (int)sizeof(double)));
     return 0;
 }
 
-// The output: the response d_gm, the synthesis' twiddles d_twm, the channels and their parameters d_par, the PCM d_pcm (and, once enabled,
-// the survey's and the activity's state).  Reads device and nblk_max, which the front end's half (or the splitter, for a view) has set.
-static int chan_build_out(jaero_chan *c, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps)
+// an output behind the front end `f`, which is built: the last of f's outputs so far
+static int chan_build_out(ChanOut *c, ChanFront *f, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch, const double *taps, int ntaps)
 {
     int rc = 0;
+    c->front = f;
     c->decim = decim; c->out_rate = out_rate; c->nch = nchannels;
     c->M = CHAN_N / decim; c->Mo = c->M / 2;
     c->channels.assign(ch, ch + nchannels);
     DA(c->mem, c->d_gm, c->M);
     DA(c->mem, c->d_twm, 32);
     DA(c->mem, c->d_par, nchannels);
-    DA(c->mem, c->d_pcm, (size_t)nchannels * c->nblk_max * c->Mo);
+    DA(c->mem, c->d_pcm, (size_t)nchannels * f->nblk_max * c->Mo);
     std::vector<ChanParam> par(nchannels);
     for (int i = 0; i < nchannels; i++) par[i] = chan_param(ch[i], decim);
     HIPCHK(hipMemcpy(c->d_par, par.data(), sizeof(ChanParam) * nchannels, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_gm, chan_response(taps, ntaps, c->M).data(), sizeof(double2) * c->M, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_twm, twiddles(c->M, 32).data(), sizeof(double2) * 32, hipMemcpyHostToDevice));
+    f->outs.push_back(c);
     return 0;
 }
 
+// a stand-alone handle: one of each
 static int chan_build(std::unique_ptr<jaero_chan> &c, int device, int decim, int out_rate, int nchannels, const jaero_chan_channel *ch,
                       const double *taps, int ntaps, int max_write_iq, long long smax)
 {
-    const int rc = chan_build_front(c.get(), device, max_write_iq, smax);
-    return rc ? rc : chan_build_out(c.get(), decim, out_rate, nchannels, ch, taps, ntaps);
+    c->own.reset(new (std::nothrow) ChanFront());
+    if (!c->own) return fail(JAERO_ENOMEM, "jaero_chan2_create: out of memory");
+    const int rc = chan_build_front(c->own.get(), device, max_write_iq, smax);
+    return rc ? rc : chan_build_out(c.get(), c->own.get(), decim, out_rate, nchannels, ch, taps, ntaps);
 }
 
 // decim: the total decimation from the capture to the output; out_rate: what the output is called (jaero_chan_feed compares it with the bank's Fs)
@@ -211,39 +218,42 @@ extern "C" int jaero_chan_create(int device, int decim, int nchannels, const jae
     return jaero_chan2_create(device, decim, 48000, nchannels, ch, taps, ntaps, max_write_iq, out);
 }
 
-// levels, block statistics or both in one pass over spec (p0: absolute index of the write's first block, for `when`)
-template <bool LEVEL, bool ACT>
-static void chan_launch_level(const jaero_chan *c, int nblk, long long p0, hipStream_t st)
+// f(D) with the output's decimation as a std::integral_constant: the instantiation of a kernel family that serves it
+template <class F>
+static void by_decim(int decim, F f)
 {
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((c->nch + CHAN_LVL_THREADS / CHAN_LVL_T - 1) / (CHAN_LVL_THREADS / CHAN_LVL_T))),
-                           dim3(CHAN_LVL_THREADS), 0, st, (const double2 *)c->d_spec, (const double *)c->d_g2, (const ChanParam *)c->d_par,
-                           c->d_lvl, c->nch, nblk, c->act, p0);
-    };
-    if (c->decim == 16) go(k_chan_level<16, LEVEL, ACT>);
-    else if (c->decim == 32) go(k_chan_level<32, LEVEL, ACT>);
-    else if (c->decim == 64) go(k_chan_level<64, LEVEL, ACT>);
-    else if (c->decim == 128) go(k_chan_level<128, LEVEL, ACT>);
-    else go(k_chan_level<256, LEVEL, ACT>);
+    if (decim == 16) f(std::integral_constant<int, 16>());
+    else if (decim == 32) f(std::integral_constant<int, 32>());
+    else if (decim == 64) f(std::integral_constant<int, 64>());
+    else if (decim == 128) f(std::integral_constant<int, 128>());
+    else f(std::integral_constant<int, 256>());
 }
 
-static void chan_launch_synth(const jaero_chan *c, int nblk, long long p0, hipStream_t st)
+// levels, block statistics or both in one pass over spec (p0: absolute index of the write's first block, for `when`)
+template <bool LEVEL, bool ACT>
+static void chan_launch_level(const ChanOut *c, int nblk, long long p0, hipStream_t st)
+{
+    by_decim(c->decim, [&](auto d) {
+        hipLaunchKernelGGL((k_chan_level<decltype(d)::value, LEVEL, ACT>), dim3((unsigned)((c->nch + CHAN_LVL_THREADS / CHAN_LVL_T - 1) / (CHAN_LVL_THREADS / CHAN_LVL_T))),
+                           dim3(CHAN_LVL_THREADS), 0, st, (const double2 *)c->front->d_spec, (const double *)c->d_g2, (const ChanParam *)c->d_par,
+                           c->d_lvl, c->nch, nblk, c->act, p0);
+    });
+}
+
+static void chan_launch_synth(const ChanOut *c, int nblk, long long p0, hipStream_t st)
 {
     const long long nitems = (long long)c->nch * nblk;
-    auto go = [&](auto kernel, int items, int threads) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((nitems + items - 1) / items)), dim3(threads), 0, st, (const double2 *)c->d_spec,
-                           (const double2 *)c->d_gm, (const double2 *)c->d_twm, (const ChanParam *)c->d_par, c->d_pcm, c->nch, nblk, p0);
-    };
-    if (c->decim == 16) go(k_chan_synth<16>, ChanShape<16>::ITEMS, ChanShape<16>::THREADS);
-    else if (c->decim == 32) go(k_chan_synth<32>, ChanShape<32>::ITEMS, ChanShape<32>::THREADS);
-    else if (c->decim == 64) go(k_chan_synth<64>, ChanShape<64>::ITEMS, ChanShape<64>::THREADS);
-    else if (c->decim == 128) go(k_chan_synth<128>, ChanShape<128>::ITEMS, ChanShape<128>::THREADS);
-    else go(k_chan_synth<256>, ChanShape<256>::ITEMS, ChanShape<256>::THREADS);
+    by_decim(c->decim, [&](auto d) {
+        using Shape = ChanShape<decltype(d)::value>;
+        hipLaunchKernelGGL(k_chan_synth<decltype(d)::value>, dim3((unsigned)((nitems + Shape::ITEMS - 1) / Shape::ITEMS)), dim3(Shape::THREADS), 0, st,
+                           (const double2 *)c->front->d_spec, (const double2 *)c->d_gm, (const double2 *)c->d_twm, (const ChanParam *)c->d_par, c->d_pcm,
+                           c->nch, nblk, p0);
+    });
 }
 
 // An output's half of what a write does behind its forward transform of nblk > 0 blocks, the first of them block p0: the synthesis, then the
-// survey's and the activity's kernels when enabled, over c->d_spec (a view's is its splitter's).
-static int chan_outputs(jaero_chan *c, int nblk, long long p0, hipStream_t st)
+// survey's and the activity's kernels when enabled, over its front end's d_spec.
+static int chan_outputs(ChanOut *c, int nblk, long long p0, hipStream_t st)
 {
     int pi = c->timer.begin(1, st);
     chan_launch_synth(c, nblk, p0, st);
@@ -254,7 +264,7 @@ static int chan_outputs(jaero_chan *c, int nblk, long long p0, hipStream_t st)
     if (sum || peak)
     {
         auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(CHAN_N / CHAN_PSD_THREADS), dim3(CHAN_PSD_THREADS), 0, st, (const double2 *)c->d_spec, c->d_psd, nblk,
+            hipLaunchKernelGGL(kernel, dim3(CHAN_N / CHAN_PSD_THREADS), dim3(CHAN_PSD_THREADS), 0, st, (const double2 *)c->front->d_spec, c->d_psd, nblk,
                                c->d_peak);
         };
         pi = c->timer.begin(peak ? 6 : 2, st);
@@ -282,79 +292,85 @@ static int chan_outputs(jaero_chan *c, int nblk, long long p0, hipStream_t st)
     return 0;
 }
 
-static int split_outputs(jaero_split *s, int nblk, long long p0, hipStream_t st);
-
-// What every write does behind its forward transform of nblk > 0 blocks: the handle's own output (a splitter's front end: every view's, in
-// output order), then the last hop and what lies behind it (`total` samples wait in `hist`, of `elem` bytes each) become the head of the
-// other history buffer `other`.
-static int chan_after_fwd(jaero_chan *c, int nblk, int total, const void *hist, void *other, size_t elem, hipStream_t st)
+// What every write does first (who: the entry point the messages name): the checks, the write's stream ordered behind the last one's (a bank
+// fed from it included), and the results of the write zeroed -- nout[g] and last_nout of output g, and what the capture staged.
+static int chan_write_enter(ChanFront *f, const void *iq, int niq, hipStream_t st, int *nout, const char *who)
 {
-    { const int rc = c->split ? split_outputs(c->split, nblk, c->blocks_done, st) : chan_outputs(c, nblk, c->blocks_done, st); if (rc) return rc; }
-    const int rest = total - nblk * CHAN_HP;
-    HIPCHK(hipMemcpyAsync(other, (const char *)hist + (size_t)nblk * CHAN_HP * elem, elem * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
-    c->cur ^= 1;
-    c->pending = rest;
-    c->blocks_done += nblk;
+    if (niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "%s: bad arguments", who);
+    if (niq > f->max_write_iq) return fail(JAERO_EINVAL, "%s: niq %d exceeds max_write_iq %d", who, niq, f->max_write_iq);
+    POISONCHK(f, who, POISON_CHAN);
+    HIPCHK(hipSetDevice(f->device));
+    { const int rc = f->order_behind(st); if (rc) return rc; }
+    for (size_t g = 0; g < f->outs.size(); g++) f->outs[g]->last_nout = nout[g] = 0;
+    if (f->cap) { f->cap->last_n = 0; f->cap->last_first = f->cap->m; f->cap->last_ptr = nullptr; }
     return 0;
 }
 
-static int capture_write(jaero_chan *c, const void *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who);
-
-// the write of an int16 handle (who: the entry point the messages name)
-static int chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who)
+// What every write does behind its forward transform of nblk > 0 blocks: every output's kernels, in output order (each with the (nch, nblk, p0)
+// it would launch with were it the only one), then the last hop and what lies behind it (`total` samples wait in `hist`, of `elem` bytes
+// each) become the head of the other history buffer `other`.
+static int chan_after_fwd(ChanFront *f, int nblk, int total, const void *hist, void *other, size_t elem, hipStream_t st)
 {
-    if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "%s: bad arguments", who);
-    if (niq > c->max_write_iq) return fail(JAERO_EINVAL, "%s: niq %d exceeds max_write_iq %d", who, niq, c->max_write_iq);
-    if (c->poisoned) return fail(JAERO_EHIP, "%s: an earlier write of this channeliser failed part-way; destroy it and create a new one", who);
-    HIPCHK(hipSetDevice(c->device));
+    for (ChanOut *o : f->outs) { const int rc = chan_outputs(o, nblk, f->blocks_done, st); if (rc) return rc; }
+    const int rest = total - nblk * CHAN_HP;
+    HIPCHK(hipMemcpyAsync(other, (const char *)hist + (size_t)nblk * CHAN_HP * elem, elem * (size_t)(CHAN_HP + rest), hipMemcpyDeviceToDevice, st));
+    f->cur ^= 1;
+    f->pending = rest;
+    f->blocks_done += nblk;
+    return 0;
+}
+
+// and last: the write is in, output g has nblk * Mo new samples a channel
+static int chan_write_leave(ChanFront *f, int nblk, int *nout, PoisonGuard &guard)
+{
+    HIPCHK(hipGetLastError());
+    for (size_t g = 0; g < f->outs.size(); g++) f->outs[g]->last_nout = nout[g] = nblk * f->outs[g]->Mo;
+    guard.commit();
+    return 0;
+}
+
+static int capture_write(ChanFront *f, const void *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who);
+
+// the write of an int16 front end; nout: one entry per output
+static int chan_write(ChanFront *f, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who)
+{
     hipStream_t st = (hipStream_t)stream;
-    if (st != c->last_stream) // a write on another stream than the previous one waits for what was enqueued there (a bank fed from it included)
-    {
-        if (!c->order_ev) HIPCHK(hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->order_ev, c->last_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->order_ev, 0));
-        c->last_stream = st;
-    }
-    *nout = 0;
-    c->last_nout = 0;
+    { const int rc = chan_write_enter(f, iq, niq, st, nout, who); if (rc) return rc; }
     if (niq == 0) return 0;
-    int *in = c->d_in[c->cur];
-    HIPCHK(hipMemcpyAsync(in + CHAN_HP + c->pending, iq, sizeof(int) * (size_t)niq, is_device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    c->poisoned = true; // from here on the history, the block count and the device buffers advance together or not at all
-    const int total = c->pending + niq;
+    int *in = f->d_in[f->cur];
+    HIPCHK(hipMemcpyAsync(in + CHAN_HP + f->pending, iq, sizeof(int) * (size_t)niq, is_device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    PoisonGuard guard(*f); // from here on the history, the block count and the device buffers advance together or not at all
+    const int total = f->pending + niq;
     const int nblk = total / CHAN_HP;
-    c->pending = total;
+    f->pending = total;
     if (nblk > 0)
     {
-        const int pi = c->timer.begin(0, st);
-        hipLaunchKernelGGL(k_chan_fwd, dim3(nblk), dim3(C2_THREADS), C6_XCH * sizeof(double), st, (const int *)in, c->d_spec, (const double2 *)c->d_tw);
+        const int pi = f->timer.begin(0, st);
+        hipLaunchKernelGGL(k_chan_fwd, dim3(nblk), dim3(C2_THREADS), C6_XCH * sizeof(double), st, (const int *)in, f->d_spec, (const double2 *)f->d_tw);
         LAUNCHCHK("k_chan_fwd");
-        c->timer.end(pi, st);
-        { const int rc = chan_after_fwd(c, nblk, total, in, c->d_in[c->cur ^ 1], sizeof(int), st); if (rc) return rc; }
+        f->timer.end(pi, st);
+        { const int rc = chan_after_fwd(f, nblk, total, in, f->d_in[f->cur ^ 1], sizeof(int), st); if (rc) return rc; }
     }
-    HIPCHK(hipGetLastError());
-    c->last_nout = *nout = nblk * c->Mo;
-    c->poisoned = false;
-    return 0;
+    return chan_write_leave(f, nblk, nout, guard);
 }
 
 extern "C" int jaero_chan_write(jaero_chan *c, const int16_t *iq, int niq, int is_device_ptr, void *stream, int *nout)
 {
     if (!c || !nout || niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "jaero_chan_write: bad arguments");
     CHANVIEWCHK(c, "jaero_chan_write", "jaero_split_write");
-    if (c->cap)
+    if (c->own->cap)
     {
-        if (c->cap->format != JAERO_IQ_CS16)
-            return fail(JAERO_EINVAL, "jaero_chan_write: the handle's capture format is %d, not int16 I/Q; use jaero_chan3_write", c->cap->format);
-        return capture_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
+        if (c->own->cap->format != JAERO_IQ_CS16)
+            return fail(JAERO_EINVAL, "jaero_chan_write: the handle's capture format is %d, not int16 I/Q; use jaero_chan3_write", c->own->cap->format);
+        return capture_write(c->own.get(), iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
     }
-    return chan_write(c, iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
+    return chan_write(c->own.get(), iq, niq, is_device_ptr, stream, nout, "jaero_chan_write");
 }
 
 extern "C" int jaero_chan_pcm_view(jaero_chan *c, void **dev_pcm, int *nsamples)
 {
     if (!c || !dev_pcm || !nsamples) return fail(JAERO_EINVAL, "jaero_chan_pcm_view: null argument");
-    CHANPOISONCHK(c, "jaero_chan_pcm_view");
+    POISONCHK(c->front, "jaero_chan_pcm_view", POISON_CHAN);
     *dev_pcm = c->d_pcm;
     *nsamples = c->last_nout;
     return 0;
@@ -363,11 +379,10 @@ extern "C" int jaero_chan_pcm_view(jaero_chan *c, void **dev_pcm, int *nsamples)
 extern "C" int jaero_chan_read_pcm(jaero_chan *c, int16_t *dst, int cap_per_channel, int *nsamples)
 {
     if (!c || !dst || !nsamples || cap_per_channel < 0) return fail(JAERO_EINVAL, "jaero_chan_read_pcm: bad arguments");
-    CHANPOISONCHK(c, "jaero_chan_read_pcm");
+    POISONCHK(c->front, "jaero_chan_read_pcm", POISON_CHAN);
     if (cap_per_channel < c->last_nout)
         return fail(JAERO_EINVAL, "jaero_chan_read_pcm: cap_per_channel %d is below the last write's %d samples", cap_per_channel, c->last_nout);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c->front);
     *nsamples = c->last_nout;
     if (c->last_nout > 0)
         HIPCHK(hipMemcpy2D(dst, sizeof(int16_t) * (size_t)cap_per_channel, c->d_pcm, sizeof(int16_t) * (size_t)c->last_nout,
@@ -377,7 +392,7 @@ extern "C" int jaero_chan_read_pcm(jaero_chan *c, int16_t *dst, int cap_per_chan
 
 // The block statistics of channels [first, end) as they are before a channel's first block: when = -1 (what the kernel reads as "no block
 // yet"; emax and emin are then not read, and are zeroed only so that the memory is defined), hist = 0.
-static int activity_clear_blocks(jaero_chan *c, int first, int end)
+static int activity_clear_blocks(ChanOut *c, int first, int end)
 {
     const size_t n = (size_t)(end - first);
     HIPCHK(hipMemset(c->act.emax + first, 0, sizeof(double) * n));
@@ -392,11 +407,10 @@ extern "C" int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_ch
 {
     if (!c || !ch || channel < 0 || channel >= c->nch) return fail(JAERO_EINVAL, "jaero_chan_retune: bad arguments");
     if (!chan_channel_ok(*ch)) return fail(JAERO_EINVAL, "jaero_chan_retune: gain %g is not finite and positive", ch->gain);
-    CHANPOISONCHK(c, "jaero_chan_retune");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far keep the old words
+    POISONCHK(c->front, "jaero_chan_retune", POISON_CHAN);
+    QUIESCE(c->front); // the writes enqueued so far keep the old words
     const ChanParam p = chan_param(*ch, c->decim);
-    c->poisoned = true; // the words, the sum and the count change together or not at all
+    PoisonGuard guard(*c->front); // the words, the sum and the count change together or not at all
     HIPCHK(hipMemcpy(c->d_par + channel, &p, sizeof p, hipMemcpyHostToDevice));
     if ((c->survey & 2) && ch->tune != c->channels[channel].tune) // another b: the level starts again with the next write
     {
@@ -409,7 +423,7 @@ extern "C" int jaero_chan_retune(jaero_chan *c, int channel, const jaero_chan_ch
         if (rc) return rc;
     }
     c->channels[channel] = *ch;
-    c->poisoned = false;
+    guard.commit();
     return 0;
 }
 
@@ -419,12 +433,11 @@ extern "C" int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *c
     if (!c || !ch) return fail(JAERO_EINVAL, "jaero_chan2_retune_all: null argument");
     for (int i = 0; i < c->nch; i++)
         if (!chan_channel_ok(ch[i])) return fail(JAERO_EINVAL, "jaero_chan2_retune_all: channel %d: gain %g is not finite and positive", i, ch[i].gain);
-    CHANPOISONCHK(c, "jaero_chan2_retune_all");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far keep the old words
+    POISONCHK(c->front, "jaero_chan2_retune_all", POISON_CHAN);
+    QUIESCE(c->front); // the writes enqueued so far keep the old words
     std::vector<ChanParam> par(c->nch);
     for (int i = 0; i < c->nch; i++) par[i] = chan_param(ch[i], c->decim);
-    c->poisoned = true; // the words, the sums and the counts change together or not at all
+    PoisonGuard guard(*c->front); // the words, the sums and the counts change together or not at all
     HIPCHK(hipMemcpy(c->d_par, par.data(), sizeof(ChanParam) * c->nch, hipMemcpyHostToDevice));
     if ((c->survey & 2) || (c->activity & 2))
     {
@@ -443,21 +456,22 @@ extern "C" int jaero_chan2_retune_all(jaero_chan *c, const jaero_chan_channel *c
         }
     }
     c->channels.assign(ch, ch + c->nch);
-    c->poisoned = false;
+    guard.commit();
     return 0;
 }
 
 // what a feed checks on the bank before anything advances
-static int chan_feed_check(const jaero_chan *c, const jaero_ctx *bank, const char *who)
+static int chan_feed_check(const ChanOut *c, const jaero_ctx *bank, const char *who)
 {
-    if (bank->device != c->device) return fail(JAERO_EINVAL, "%s: the bank is on device %d, the channeliser on %d", who, bank->device, c->device);
+    if (bank->device != c->front->device) return fail(JAERO_EINVAL, "%s: the bank is on device %d, the channeliser on %d", who, bank->device, c->front->device);
     if (bank->o_nch != c->nch) return fail(JAERO_EINVAL, "%s: the bank has %d channels, the channeliser %d", who, bank->o_nch, c->nch);
     for (const jaero_settings &s : bank->settings)
         if (s.Fs != (double)c->out_rate)
             return fail(JAERO_EINVAL, "%s: the bank runs at Fs = %g; the channeliser's output is %d", who, s.Fs, c->out_rate);
-    if (bank->max_write < c->nblk_max * c->Mo)
+    const int nblk_max = c->front->nblk_max;
+    if (bank->max_write < nblk_max * c->Mo)
         return fail(JAERO_EINVAL, "%s: the bank's max_write_samples %d is below the %d blocks a write can complete * %d = %d", who, bank->max_write,
-                    c->nblk_max, c->Mo, c->nblk_max * c->Mo);
+                    nblk_max, c->Mo, nblk_max * c->Mo);
     return 0;
 }
 
@@ -475,17 +489,26 @@ extern "C" int jaero_chan_profile_enable(jaero_chan *c, int on)
 {
     if (!c) return fail(JAERO_EINVAL, "jaero_chan_profile_enable: null ctx");
     c->timer.on = on != 0;
+    if (c->own) c->own->timer.on = on != 0; // (a view's front end is switched by jaero_split_profile_enable)
     return 0;
+}
+
+// The handle's total of timer slot `slot`: the front end's kernels (0, 4, 5) are timed by the front end the handle owns -- a view owns none, and
+// reports the empty slots of its own timer: those kernels are its splitter's (jaero_split_profile_read).
+static int chan_timer_read(jaero_chan *c, int slot, double *total_ms, int *launches, int reset)
+{
+    const bool fwd = slot == 0 || slot == 4 || slot == 5;
+    return (fwd && c->own ? c->own->timer : c->timer).read(c->front->device, slot, total_ms, launches, reset);
 }
 
 extern "C" int jaero_chan_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset)
 {
     if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_chan_profile_read: bad arguments");
-    return c->timer.read(c->device, which, total_ms, launches, reset);
+    return chan_timer_read(c, which, total_ms, launches, reset);
 }
 
 // ------------------------------------------------------------------------------------------ survey
-static int survey_clear(jaero_chan *c)
+static int survey_clear(ChanOut *c)
 {
     if (c->survey & 1)
     {
@@ -503,7 +526,7 @@ static int survey_clear(jaero_chan *c)
 
 // The table k_chan_level multiplies by, built by whichever of the levels and the block statistics is enabled first: |G / N|^2 of the
 // response the synthesis multiplies by, from its order (k < M / 2: q = k, else q = k - M) to ascending q
-static int chan_build_g2(jaero_chan *c)
+static int chan_build_g2(ChanOut *c)
 {
     if (c->d_g2) return 0;
     int rc = 0;
@@ -526,9 +549,8 @@ extern "C" int jaero_survey_enable(jaero_chan *c, int what)
 {
     if (what < 0 || what > 3) return fail(JAERO_EINVAL, "jaero_survey_enable: what %d has bits outside 0..3", what);
     if (!c) return fail(JAERO_EINVAL, "jaero_survey_enable: null ctx");
-    CHANPOISONCHK(c, "jaero_survey_enable");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far are surveyed as they were enqueued
+    POISONCHK(c->front, "jaero_survey_enable", POISON_CHAN);
+    QUIESCE(c->front); // the writes enqueued so far are surveyed as they were enqueued
     int rc = 0;
     if ((what & 1) && !c->d_psd) DA(c->mem, c->d_psd, CHAN_N);
     if (what & 2)
@@ -545,9 +567,8 @@ extern "C" int jaero_survey_enable(jaero_chan *c, int what)
 extern "C" int jaero_survey_reset(jaero_chan *c)
 {
     if (!c) return fail(JAERO_EINVAL, "jaero_survey_reset: null ctx");
-    CHANPOISONCHK(c, "jaero_survey_reset");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    POISONCHK(c->front, "jaero_survey_reset", POISON_CHAN);
+    QUIESCE(c->front);
     return survey_clear(c);
 }
 
@@ -555,9 +576,8 @@ extern "C" int jaero_survey_read_psd(jaero_chan *c, double *sums, long long *nbl
 {
     if (!c || !sums || !nblocks) return fail(JAERO_EINVAL, "jaero_survey_read_psd: null argument");
     if (!(c->survey & 1)) return fail(JAERO_EINVAL, "jaero_survey_read_psd: the spectrum is not enabled (jaero_survey_enable bit 0)");
-    CHANPOISONCHK(c, "jaero_survey_read_psd");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    POISONCHK(c->front, "jaero_survey_read_psd", POISON_CHAN);
+    QUIESCE(c->front);
     HIPCHK(hipMemcpy(sums, c->d_psd, sizeof(double) * CHAN_N, hipMemcpyDeviceToHost));
     *nblocks = c->psd_blocks;
     return 0;
@@ -567,9 +587,8 @@ extern "C" int jaero_survey_read_levels(jaero_chan *c, double *sums, long long *
 {
     if (!c || !sums || !nblocks) return fail(JAERO_EINVAL, "jaero_survey_read_levels: null argument");
     if (!(c->survey & 2)) return fail(JAERO_EINVAL, "jaero_survey_read_levels: the levels are not enabled (jaero_survey_enable bit 1)");
-    CHANPOISONCHK(c, "jaero_survey_read_levels");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    POISONCHK(c->front, "jaero_survey_read_levels", POISON_CHAN);
+    QUIESCE(c->front);
     HIPCHK(hipMemcpy(sums, c->d_lvl, sizeof(double) * (size_t)c->nch, hipMemcpyDeviceToHost));
     for (int i = 0; i < c->nch; i++) nblocks[i] = c->lvl_blocks - c->lvl_start[i];
     return 0;
@@ -578,12 +597,12 @@ extern "C" int jaero_survey_read_levels(jaero_chan *c, double *sums, long long *
 extern "C" int jaero_survey_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset)
 {
     if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_survey_profile_read: bad arguments");
-    return c->timer.read(c->device, 2 + which, total_ms, launches, reset);
+    return chan_timer_read(c, 2 + which, total_ms, launches, reset);
 }
 
 // ------------------------------------------------------------------------------------------ activity
 static_assert(CHAN_ACT_BINS == JAERO_ACT_BINS, "the kernel's row of hist is the ABI's");
-static int activity_clear(jaero_chan *c)
+static int activity_clear(ChanOut *c)
 {
     if (c->activity & 1)
     {
@@ -603,9 +622,8 @@ extern "C" int jaero_activity_enable(jaero_chan *c, int what)
 {
     if (what < 0 || what > 3) return fail(JAERO_EINVAL, "jaero_activity_enable: what %d has bits outside 0..3", what);
     if (!c) return fail(JAERO_EINVAL, "jaero_activity_enable: null ctx");
-    CHANPOISONCHK(c, "jaero_activity_enable");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream)); // the writes enqueued so far are measured as they were enqueued
+    POISONCHK(c->front, "jaero_activity_enable", POISON_CHAN);
+    QUIESCE(c->front); // the writes enqueued so far are measured as they were enqueued
     int rc = 0;
     if ((what & 1) && !c->d_peak) DA(c->mem, c->d_peak, CHAN_N);
     if (what & 2)
@@ -625,9 +643,8 @@ extern "C" int jaero_activity_enable(jaero_chan *c, int what)
 extern "C" int jaero_activity_reset(jaero_chan *c)
 {
     if (!c) return fail(JAERO_EINVAL, "jaero_activity_reset: null ctx");
-    CHANPOISONCHK(c, "jaero_activity_reset");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    POISONCHK(c->front, "jaero_activity_reset", POISON_CHAN);
+    QUIESCE(c->front);
     return activity_clear(c);
 }
 
@@ -635,9 +652,8 @@ extern "C" int jaero_activity_read_peak(jaero_chan *c, double *peak, long long *
 {
     if (!c || !peak || !nblocks) return fail(JAERO_EINVAL, "jaero_activity_read_peak: null argument");
     if (!(c->activity & 1)) return fail(JAERO_EINVAL, "jaero_activity_read_peak: the peak-hold spectrum is not enabled (jaero_activity_enable bit 0)");
-    CHANPOISONCHK(c, "jaero_activity_read_peak");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    POISONCHK(c->front, "jaero_activity_read_peak", POISON_CHAN);
+    QUIESCE(c->front);
     HIPCHK(hipMemcpy(peak, c->d_peak, sizeof(double) * CHAN_N, hipMemcpyDeviceToHost));
     *nblocks = c->peak_blocks;
     return 0;
@@ -647,9 +663,8 @@ extern "C" int jaero_activity_read_blocks(jaero_chan *c, double *emax, double *e
 {
     if (!c || !emax || !emin || !when || !nblocks) return fail(JAERO_EINVAL, "jaero_activity_read_blocks: null argument");
     if (!(c->activity & 2)) return fail(JAERO_EINVAL, "jaero_activity_read_blocks: the block statistics are not enabled (jaero_activity_enable bit 1)");
-    CHANPOISONCHK(c, "jaero_activity_read_blocks");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    POISONCHK(c->front, "jaero_activity_read_blocks", POISON_CHAN);
+    QUIESCE(c->front);
     const size_t n = (size_t)c->nch;
     HIPCHK(hipMemcpy(emax, c->act.emax, sizeof(double) * n, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(emin, c->act.emin, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -666,7 +681,7 @@ extern "C" int jaero_activity_read_blocks(jaero_chan *c, double *emax, double *e
 extern "C" int jaero_activity_profile_read(jaero_chan *c, int which, double *total_ms, int *launches, int reset)
 {
     if (!c || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_activity_profile_read: bad arguments");
-    return c->timer.read(c->device, 6 + which, total_ms, launches, reset);
+    return chan_timer_read(c, 6 + which, total_ms, launches, reset);
 }
 
 #include "capture_host.h"

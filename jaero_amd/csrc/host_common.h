@@ -1,5 +1,5 @@
 // host_common.h -- host plumbing every bank shares (included by jaero_hip.hip after fail / HIPCHK): device memory with one owner, the device
-// check, row drains and overflow reports of the read entry points, HIP-event kernel timing, the carry-over copies of a rate change, and the
+// check, the handle base (stream ordering, quiesce, poison), row drains and overflow reports of the read entry points, HIP-event kernel timing, the carry-over copies of a rate change, and the
 // host-built tables the banks upload.
 #pragma once
 
@@ -48,6 +48,65 @@ static int open_device(int device, hipDeviceProp_t *prop_out = nullptr)
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ device handles
+// What every handle that enqueues work keeps (banks, channeliser front ends, rate meters): its device, the stream of its last write, and
+// whether a call that advances state failed part-way -- host mirror and device state then disagree, and the handle accepts nothing but its
+// destroy: setters would change a state nobody can continue from, readers would hand out half-written outputs without saying so.
+struct DevHandle
+{
+    int device = 0;
+    hipStream_t last_stream = nullptr;
+    hipEvent_t order_ev = nullptr; // order_behind's, made by the first change of stream
+    bool poisoned = false;
+
+    // Work enqueued on `st` is ordered behind everything the handle enqueued before (on last_stream), and `st` becomes last_stream: the rule
+    // for every entry point that takes a caller stream and touches device state.  A discard on stream X followed by a call that synchronises
+    // last_stream only must not read the counters before the discard lands.
+    int order_behind(hipStream_t st)
+    {
+        if (st != last_stream)
+        {
+            if (!order_ev) HIPCHK(hipEventCreateWithFlags(&order_ev, hipEventDisableTiming));
+            HIPCHK(hipEventRecord(order_ev, last_stream));
+            HIPCHK(hipStreamWaitEvent(st, order_ev, 0));
+        }
+        last_stream = st;
+        return 0;
+    }
+    // everything enqueued so far has run: what control-plane calls and readers wait for
+    int quiesce() const
+    {
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamSynchronize(last_stream));
+        return 0;
+    }
+    // the destroy functions' prologue: cannot fail, and the owner is deleted behind it
+    void teardown()
+    {
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(last_stream);
+        if (order_ev) (void)hipEventDestroy(order_ev);
+        order_ev = nullptr;
+    }
+};
+#define QUIESCE(h) do { if (const int rc_ = (h)->quiesce()) return rc_; } while (0)
+
+// Raises `poisoned` where the first step that advances state is about to be enqueued; only commit() lowers it, so every early return in
+// between leaves the handle poisoned.  (The test hooks that leave a handle where no write would set the flag and never lower it.)
+struct PoisonGuard
+{
+    DevHandle &h;
+    explicit PoisonGuard(DevHandle &handle) : h(handle) { h.poisoned = true; }
+    void commit() { h.poisoned = false; }
+};
+
+// how the refusal of a poisoned handle words the object: "<who>: an earlier <write> failed part-way; destroy <it> and create a new one"
+struct PoisonWords { const char *write, *it; };
+static const PoisonWords POISON_BANK = {"jaero_write of this bank", "the bank"}, POISON_LINKED_BANK = {"jaero_write of the bank", "it"},
+                         POISON_CHAN = {"write of this channeliser", "it"}, POISON_SPLIT = {"write of this splitter", "it"},
+                         POISON_RATE = {"write of this rate meter", "it"};
+#define POISONCHK(h, who, words) do { if ((h) && (h)->poisoned) return fail(JAERO_EHIP, "%s: an earlier %s failed part-way; destroy %s and create a new one", who, (words).write, (words).it); } while (0)
+
 // ------------------------------------------------------------------------------------------ outputs
 // One channel's rows of a per-channel output buffer: channel ch's rows start at base + ch * cap * rowbytes, its row count is cnt[ch].
 struct RowBuf
@@ -95,6 +154,14 @@ static int report_overflow(int *dov, int bit, int ch)
     const int z = ov & ~bit;
     HIPCHK(hipMemcpy(dov, &z, sizeof(int), hipMemcpyHostToDevice));
     return fail(JAERO_EOVERFLOW, "channel %d overflowed an output buffer (flag %d); rows were dropped", ch, bit);
+}
+
+// The peek hooks: one channel's scalars of a [field][nchp] array, each to where the table says ({field, destination}; a copy per field)
+template <class T, size_t N>
+static int peek_fields(const T *base, size_t nchp, int ch, const std::pair<int, T *> (&table)[N])
+{
+    for (const auto &[f, dst] : table) HIPCHK(hipMemcpy(dst, base + (size_t)f * nchp + ch, sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------ kernel timing

@@ -170,9 +170,12 @@ using CoarseFn = void (*)(JGeom, JPtrs, const int *, int, const double2 *);
 using BurstDemodFn = void (*)(BGeom, BPtrs, int, long long, int);
 using TridentFn = void (*)(BGeom, BPtrs, long long);
 
-struct jaero_ctx
+// A demodulator bank.  What it keeps as a DevHandle (host_common.h):
+//   last_stream, order_ev  a write on another stream than the previous one waits for what was enqueued on that one (setters included)
+//   poisoned               a launch inside a write failed: the host's schedule mirror has advanced past the device state
+// (tests/device_prims.py cites lines of validate_settings and fill_geometry below by number)
+struct jaero_ctx : DevHandle
 {
-    int device = 0;
     JGeom g{};
     JPtrs p{};
     unsigned flags = 0;
@@ -215,9 +218,6 @@ struct jaero_ctx
     int *o_soft_cnt = nullptr, *o_sym_cnt = nullptr, *o_overflow = nullptr, *o_flags = nullptr;
     int *o_nrx = nullptr; // burst: soft bits pushed but not yet emitted (RxDataBits.size()), kept at the tail of the buffer
     KernelTimer timer{6}; SweepBufs sweep; jaero_status *d_status_all = nullptr; // jaero_profile_read's five kernel classes + 5 = jaero_read_all / jaero_read_status_all's kernels; their scratch, allocated by the first call
-    hipStream_t last_stream = nullptr;
-    hipEvent_t order_ev = nullptr; // a write on another stream than the previous one waits for what was enqueued on that one (setters included)
-    bool poisoned = false;         // a launch inside a write failed: the host's schedule mirror has advanced past the device state
 };
 
 // ------------------------------------------------------------------------------------------ small kernels
@@ -543,10 +543,9 @@ extern "C" void jaero_destroy(jaero_ctx *c)
 {
     if (!c) return;
     dcd_unlink_bank(c);
-    hipSetDevice(c->device);
     // this bank's work only (its last stream and the default stream its control-plane copies use): other banks keep running until hipFree's
     // own implicit synchronisation, which cannot be avoided
-    hipStreamSynchronize(c->last_stream);
+    c->teardown();
     hipStreamSynchronize(0);
 #ifdef FB_TRACE_BUILD
     if (!c->burst)
@@ -567,7 +566,6 @@ extern "C" void jaero_destroy(jaero_ctx *c)
         hipMemcpyToSymbol(HIP_SYMBOL(g_fb_trace), z, sizeof(z));
     }
 #endif
-    if (c->order_ev) hipEventDestroy(c->order_ev);
     delete c; // its device memory and timing events with it
 }
 
@@ -875,13 +873,9 @@ static int upload_flags(jaero_ctx *c, int lo, int hi, int mask, int bits)
     return 0;
 }
 
-// a bank whose write failed part-way (device state and the host's schedule mirror disagree) accepts nothing but jaero_destroy: setters would
-// change a state nobody can continue from, readers would hand out half-written outputs without saying so
-#define POISONCHK(c, who) do { if ((c) && (c)->poisoned) return fail(JAERO_EHIP, who ": an earlier jaero_write of this bank failed part-way; destroy the bank and create a new one"); } while (0)
-
 extern "C" int jaero_set_flags(jaero_ctx *c, int channel, int afc, int sql, int cpu_reduce)
 {
-    POISONCHK(c, "jaero_set_flags");
+    POISONCHK(c, "jaero_set_flags", POISON_BANK);
     if (!c || channel < -1 || channel >= c->o_nch) return fail(JAERO_EINVAL, "jaero_set_flags: bad channel");
     HIPCHK(hipSetDevice(c->device));
     const int lo = channel < 0 ? 0 : channel, hi = channel < 0 ? c->o_nchp : channel + 1;
@@ -892,7 +886,7 @@ extern "C" int jaero_set_flags(jaero_ctx *c, int channel, int afc, int sql, int 
 
 extern "C" int jaero_set_dcd(jaero_ctx *c, int channel, int dcd)
 {
-    POISONCHK(c, "jaero_set_dcd");
+    POISONCHK(c, "jaero_set_dcd", POISON_BANK);
     if (!c || channel < -1 || channel >= c->o_nch) return fail(JAERO_EINVAL, "jaero_set_dcd: bad channel");
     HIPCHK(hipSetDevice(c->device));
     const int lo = channel < 0 ? 0 : channel, hi = channel < 0 ? c->o_nchp : channel + 1;
@@ -902,7 +896,7 @@ extern "C" int jaero_set_dcd(jaero_ctx *c, int channel, int dcd)
 
 extern "C" int jaero_center_freq_changed(jaero_ctx *c, int channel, double hz)
 {
-    POISONCHK(c, "jaero_center_freq_changed");
+    POISONCHK(c, "jaero_center_freq_changed", POISON_BANK);
     if (!c || channel < -1 || channel >= c->o_nch) return fail(JAERO_EINVAL, "jaero_center_freq_changed: bad channel");
     HIPCHK(hipSetDevice(c->device));
     if (c->burst)
@@ -1036,8 +1030,7 @@ static int rebank_with_carry_over(jaero_ctx *c, const jaero_settings *s)
     LINKCHK(c);
     if (c->poisoned) return fail(JAERO_EHIP, "jaero_set_settings: a launch inside an earlier jaero_write failed; this bank's state cannot be carried over");
     if (og.kind == JAERO_KIND_OQPSK && s->Fs != og.Fs) return fail(JAERO_ENOTSUP, "jaero_set_settings: an OQPSK bank keeps its sample rate");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     jaero_ctx *n = nullptr;
     int rc = jaero_create(c->device, og.nch, s, 0, c->flags, c->max_write, c->soft_cap_req, &n);
     if (rc) return rc;
@@ -1104,7 +1097,7 @@ static int rebank_with_carry_over(jaero_ctx *c, const jaero_settings *s)
         if (!c->pre8400) HIPCHK(hipMemset(n->p.S + (size_t)S_PRE_FSUM * nchp, 0, sizeof(double) * (size_t)nchp));
     }
     if ((rc = apply_live_settings(n, 0, ng.nchp, s))) return rc; // the padding lanes too: their window positions came over with I and must fit the new lengths
-    if (hipStreamSynchronize(n->last_stream) != hipSuccess || hipStreamSynchronize(0) != hipSuccess) return fail(JAERO_EHIP, "jaero_set_settings: carry-over failed");
+    if (n->quiesce() || hipStreamSynchronize(0) != hipSuccess) return fail(JAERO_EHIP, "jaero_set_settings: carry-over failed");
     swap_in(c, std::move(nb));
     return 0;
 }
@@ -1114,7 +1107,7 @@ extern "C" int jaero_set_settings(jaero_ctx *c, int channel, const jaero_setting
     // setSettings on a live object (oqpskdemodulator.cpp:175-289, mskdemodulator.cpp:135-263): retunes the mixers
     // (phase kept), recreates AGC / matched filters / timing delays / resonator, restarts the coarse ring pointer.
     if (!c || !s || channel < -1 || channel >= c->o_nch) return fail(JAERO_EINVAL, "jaero_set_settings: bad arguments");
-    POISONCHK(c, "jaero_set_settings");
+    POISONCHK(c, "jaero_set_settings", POISON_BANK);
     int rc = validate_settings(*s);
     if (rc) return rc;
     if (c->burst) return burst_set_settings(c, channel, s);
@@ -1250,21 +1243,6 @@ static int launch_coarse_lists(jaero_ctx *c, const int *h_list, int nlist, int g
     return 0;
 }
 
-// Work enqueued on `st` is ordered behind everything the bank enqueued before (on last_stream), and `st` becomes last_stream: the rule for
-// every entry point that takes a caller stream and touches device state (jaero_write, jaero_discard_softbits) -- a discard on stream X
-// followed by a rate-changing jaero_set_settings (which synchronises last_stream only) must not read the counters before the discard lands.
-static int order_behind_last(jaero_ctx *c, hipStream_t st)
-{
-    if (st != c->last_stream)
-    {
-        if (!c->order_ev) HIPCHK(hipEventCreateWithFlags(&c->order_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->order_ev, c->last_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->order_ev, 0));
-    }
-    c->last_stream = st;
-    return 0;
-}
-
 extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int layout, int is_device_ptr, void *stream)
 {
     if (!c || !pcm || nsamples < 0) return fail(JAERO_EINVAL, "jaero_write: bad arguments");
@@ -1274,15 +1252,10 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
     if (c->poisoned) return fail(JAERO_EHIP, "jaero_write: an earlier write of this bank failed part-way (its schedule mirror is ahead of the device state): destroy the bank and create a new one");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    { const int rc = order_behind_last(c, st); if (rc) return rc; } // setters, discards and earlier writes were enqueued on last_stream
+    { const int rc = c->order_behind(st); if (rc) return rc; } // setters, discards and earlier writes were enqueued on last_stream
     // poisoned is raised where the first launch that advances device state or the schedule mirror is about to be enqueued (a failed copy of
     // the input, transpose or history push leaves both as they were: the caller may simply write again) and lowered when the whole write is in
-    if (c->burst)
-    {
-        const int rc = burst_write(c, pcm, nsamples, layout, is_device_ptr, st);
-        if (rc == 0) c->poisoned = false;
-        return rc;
-    }
+    if (c->burst) return burst_write(c, pcm, nsamples, layout, is_device_ptr, st);
     const JGeom &g = c->g;
     const int nch = g.nch;
 
@@ -1290,7 +1263,7 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
     int stride = 0;
     { const int rc = stage_pcm(c, pcm, nsamples, layout, is_device_ptr, st, &frames, &stride); if (rc) return rc; }
 
-    c->poisoned = true; // from here on device state and mirror advance together or not at all
+    PoisonGuard guard(*c); // from here on device state and mirror advance together or not at all
     if (c->pre8400)
     {
         const int rc = launch_pre8400_stage(c, frames, stride, nsamples, pre8400_stretches(g, nsamples), st);
@@ -1321,7 +1294,7 @@ extern "C" int jaero_write(jaero_ctx *c, const int16_t *pcm, int nsamples, int l
         pos = next;
     }
     HIPCHK(hipGetLastError());
-    c->poisoned = false;
+    guard.commit();
     return 0;
 }
 
@@ -1333,8 +1306,7 @@ static int coarse_hook_enter(jaero_ctx *c, const char *who, int channel)
     if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
     if (c->burst) return fail(JAERO_EINVAL, "%s: a burst bank has no coarse-frequency estimate", who);
     if (channel < 0 || channel >= c->g.nch) return fail(JAERO_EINVAL, "%s: channel %d outside [0, %d)", who, channel, c->g.nch);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     c->poisoned = true;
     return 0;
 }
@@ -1374,8 +1346,7 @@ extern "C" int jaero_debug_coarse_peek(jaero_ctx *c, int ch, double *ring_reim, 
         const std::pair<int, int *> iv[] = {{I_BB_PTR, &st->bb_ptr}, {I_EMPTYING, &st->emptying}, {I_FLAGS, &st->flags}, {I_COUNTDOWN, &st->countdown},
                                             {I_COUNTDOWN2, &st->countdown2}, {I_COARSE_CNT, &st->coarse_cnt}, {I_NEST, &st->nest}, {I_LOG_CNT, &st->log_cnt}};
         const std::pair<int, double *> dv[] = {{S_MSE, &st->mse}, {S_M2_FREQ, &st->m2_freq}, {S_MC_FREQ, &st->mc_freq}};
-        for (const auto &[f, v] : iv) HIPCHK(hipMemcpy(v, c->p.I + (size_t)f * nchp + ch, sizeof(int), hipMemcpyDeviceToHost));
-        for (const auto &[f, v] : dv) HIPCHK(hipMemcpy(v, c->p.S + (size_t)f * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
+        if ((rc = peek_fields(c->p.I, nchp, ch, iv)) || (rc = peek_fields(c->p.S, nchp, ch, dv))) return rc;
     }
     return 0;
 }
@@ -1400,7 +1371,7 @@ extern "C" int jaero_debug_coarse_launch(jaero_ctx *c, const int *channels, int 
     if (grid < 0 || grid > gmax) return fail(JAERO_EINVAL, "jaero_debug_coarse_launch: grid %d (0 = as jaero_write, else 1 .. %d for %d channels)", grid, gmax, nlist);
     if ((rc = launch_coarse_lists(c, channels, nlist, grid ? grid : gmax, c->last_stream, false))) return rc;
     LAUNCHCHK("the coarse-frequency estimate");
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     return 0;
 }
 // ------------------------------------------------------------------------------------------ test hooks: the sample loop's slow state
@@ -1412,7 +1383,7 @@ static const int LOOP_FIELDS[6] = {S_ST_FREQ, S_M2_FREQ, S_LF_X1, S_LF_X2, S_LF_
     if (!st) return fail(JAERO_EINVAL, who ": null state");                                                                                        \
     if (c->burst) return fail(JAERO_EINVAL, who ": a burst bank has no continuous sample loop");                                                   \
     if (ch < 0 || ch >= c->g.nch) return fail(JAERO_EINVAL, who ": channel %d outside [0, %d)", ch, c->g.nch);                                     \
-    POISONCHK(c, who)
+    POISONCHK(c, who, POISON_BANK)
 extern "C" int jaero_debug_loop_poke(jaero_ctx *c, int ch, const jaero_loop_state *st)
 {
     LOOP_HOOK_ENTER("jaero_debug_loop_poke");
@@ -1420,8 +1391,7 @@ extern "C" int jaero_debug_loop_poke(jaero_ctx *c, int ch, const jaero_loop_stat
     for (double x : v)
         if (!std::isfinite(x)) return fail(JAERO_EINVAL, "jaero_debug_loop_poke: a value is not finite");
     if (st->st_freq < 0 || st->m2_freq < 0) return fail(JAERO_EINVAL, "jaero_debug_loop_poke: st_freq and m2_freq must be >= 0");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     const size_t nchp = (size_t)c->g.nchp;
     // WaveTable::SetFreq's step, in init_channel_scalars' order of operations: (freq * WTSIZE) / Fs, the quotient the kernels' own SetFreq forms
     const float fs = (float)(double)c->g.Fs_int;
@@ -1433,12 +1403,10 @@ extern "C" int jaero_debug_loop_poke(jaero_ctx *c, int ch, const jaero_loop_stat
 extern "C" int jaero_debug_loop_peek(jaero_ctx *c, int ch, jaero_loop_state *st)
 {
     LOOP_HOOK_ENTER("jaero_debug_loop_peek");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
-    const size_t nchp = (size_t)c->g.nchp;
-    double *const v[6] = {&st->st_freq, &st->m2_freq, &st->lf_x1, &st->lf_x2, &st->lf_y1, &st->lf_y2};
-    for (int k = 0; k < 6; k++) HIPCHK(hipMemcpy(v[k], c->p.S + (size_t)LOOP_FIELDS[k] * nchp + ch, sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    QUIESCE(c);
+    const std::pair<int, double *> v[] = {{S_ST_FREQ, &st->st_freq}, {S_M2_FREQ, &st->m2_freq}, {S_LF_X1, &st->lf_x1}, {S_LF_X2, &st->lf_x2},
+                                          {S_LF_Y1, &st->lf_y1}, {S_LF_Y2, &st->lf_y2}};
+    return peek_fields(c->p.S, (size_t)c->g.nchp, ch, v);
 }
 #undef LOOP_HOOK_ENTER
 extern "C" int jaero_debug_coarse_band(jaero_ctx *c, char *buf, int cap, long long *est_generic, long long *est_band)
@@ -1586,8 +1554,7 @@ static int pre8400_hook_enter(jaero_ctx *c, const char *who, int channel, bool p
     if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
     if (c->burst || !c->pre8400) return fail(JAERO_EINVAL, "%s: not an 8400 bps bank", who);
     if (channel < 0 || channel >= c->g.nch) return fail(JAERO_EINVAL, "%s: channel %d outside [0, %d)", who, channel, c->g.nch);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     if (poison) c->poisoned = true;
     return 0;
 }
@@ -1638,7 +1605,7 @@ extern "C" int jaero_debug_pre8400_restart(jaero_ctx *c, int ch)
     int rc = pre8400_hook_enter(c, "jaero_debug_pre8400_restart", ch, true);
     if (rc) return rc;
     if ((rc = launch_pre8400_restart(c, ch, c->last_stream))) return rc;
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     return 0;
 }
 extern "C" int jaero_debug_pre8400_read_ring(jaero_ctx *c, int ch, long long first, int n, double *out_reim)
@@ -1659,7 +1626,7 @@ extern "C" int jaero_debug_pre8400_read_ring(jaero_ctx *c, int ch, long long fir
 extern "C" int jaero_debug_read_prefiltered(jaero_ctx *c, int ch, double *out_reim, int n)
 {
     if (!c || !out_reim || !c->pre8400 || ch < 0 || ch >= c->g.nch || n <= 0 || n > c->pre_nprev) return fail(JAERO_EINVAL, "jaero_debug_read_prefiltered: bad arguments");
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     HIPCHK(hipMemcpy2D(out_reim, sizeof(double2), c->pre.out + JD_G4(0, ch, c->pre.cap), sizeof(double2) * 4, sizeof(double2), (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1667,14 +1634,14 @@ extern "C" int jaero_debug_read_prefiltered(jaero_ctx *c, int ch, double *out_re
 // ------------------------------------------------------------------------------------------ outputs
 extern "C" int jaero_read_softbits(jaero_ctx *c, int ch, int16_t *dst, int cap, int *n)
 {
-    POISONCHK(c, "jaero_read_softbits");
+    POISONCHK(c, "jaero_read_softbits", POISON_BANK);
     if (!c) return fail(JAERO_EINVAL, "jaero_read_softbits: null ctx");
     return read_output(c, "jaero_read_softbits", {c->o_soft, c->o_soft_cnt, c->o_soft_cap, sizeof(int16_t)}, ch, dst, cap, n, 1, c->o_nrx);
 }
 
 extern "C" int jaero_read_softbits_all(jaero_ctx *c, int16_t *dst, int capc, int *counts)
 {
-    POISONCHK(c, "jaero_read_softbits_all");
+    POISONCHK(c, "jaero_read_softbits_all", POISON_BANK);
     if (!c || !dst || !counts || capc <= 0) return fail(JAERO_EINVAL, "jaero_read_softbits_all: bad arguments");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->last_stream;
@@ -1733,7 +1700,7 @@ __global__ void k_burst_keep_tail(int *__restrict__ cnt, const int *__restrict__
 
 extern "C" int jaero_softbits_view(jaero_ctx *c, void **dev_softbits, void **dev_counts, int *capacity)
 {
-    POISONCHK(c, "jaero_softbits_view");
+    POISONCHK(c, "jaero_softbits_view", POISON_BANK);
     if (!c) return fail(JAERO_EINVAL, "null ctx");
     if (dev_softbits) *dev_softbits = c->o_soft;
     if (c->burst && dev_counts)
@@ -1756,10 +1723,10 @@ extern "C" int jaero_softbits_view(jaero_ctx *c, void **dev_softbits, void **dev
 
 extern "C" int jaero_discard_softbits(jaero_ctx *c, void *stream)
 {
-    POISONCHK(c, "jaero_discard_softbits");
+    POISONCHK(c, "jaero_discard_softbits", POISON_BANK);
     if (!c) return fail(JAERO_EINVAL, "null ctx");
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = order_behind_last(c, (hipStream_t)stream); if (rc) return rc; }
+    { const int rc = c->order_behind((hipStream_t)stream); if (rc) return rc; }
     if (c->burst)
     {
         // what jaero_softbits_view reported as emitted is gone; the not yet emitted tail of every channel moves to the front
@@ -1774,32 +1741,32 @@ extern "C" int jaero_discard_softbits(jaero_ctx *c, void *stream)
 
 extern "C" int jaero_read_status(jaero_ctx *c, int ch, jaero_status *stt)
 {
-    POISONCHK(c, "jaero_read_status");
+    POISONCHK(c, "jaero_read_status", POISON_BANK);
     if (!c || !stt || ch < 0 || ch >= c->o_nch) return fail(JAERO_EINVAL, "jaero_read_status: bad arguments");
     HIPCHK(hipSetDevice(c->device));
     if (c->burst) hipLaunchKernelGGL(k_status_burst, dim3(1), dim3(64), 0, c->last_stream, c->bg, c->bp, ch, 1, c->d_status);
     else hipLaunchKernelGGL(k_status, dim3(1), dim3(64), 0, c->last_stream, c->g, c->p, ch, 1, c->d_status);
     HIPCHK(hipMemcpyAsync(stt, c->d_status, sizeof(jaero_status), hipMemcpyDeviceToHost, c->last_stream));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    QUIESCE(c);
     return 0;
 }
 
 extern "C" int jaero_read_status_log(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows)
 {
-    POISONCHK(c, "jaero_read_status_log");
+    POISONCHK(c, "jaero_read_status_log", POISON_BANK);
     if (!c) return fail(JAERO_EINVAL, "jaero_read_status_log: null ctx");
     if (c->burst) return fail(JAERO_ENOTSUP, "burst banks have an event log (jaero_read_events), not a status log");
     return read_output(c, "jaero_read_status_log", {c->p.slog, c->p.I + (size_t)I_LOG_CNT * c->g.nchp, c->g.log_cap, 6 * sizeof(double)}, ch, rows, caprows, nrows, 4);
 }
 extern "C" int jaero_read_symbols(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows)
 {
-    POISONCHK(c, "jaero_read_symbols");
+    POISONCHK(c, "jaero_read_symbols", POISON_BANK);
     if (!c) return fail(JAERO_EINVAL, "jaero_read_symbols: null ctx");
     return read_output(c, "jaero_read_symbols", {c->o_sym, c->o_sym_cnt, c->o_sym_cap, 3 * sizeof(double)}, ch, rows, caprows, nrows, 2);
 }
 extern "C" int jaero_read_events(jaero_ctx *c, int ch, double *rows, int caprows, int *nrows)
 {
-    POISONCHK(c, "jaero_read_events");
+    POISONCHK(c, "jaero_read_events", POISON_BANK);
     if (!c) return fail(JAERO_EINVAL, "jaero_read_events: null ctx");
     if (!c->burst) return fail(JAERO_ENOTSUP, "continuous banks have a status log (jaero_read_status_log), not an event log");
     return read_output(c, "jaero_read_events", {c->bp.evlog, c->bp.I + (size_t)BI_EV_CNT * c->bg.nchp, c->bg.ev_cap, 3 * sizeof(double)}, ch, rows, caprows, nrows, 4);
@@ -2054,7 +2021,7 @@ extern "C" int jaero_read_all(jaero_ctx *c, int what, void *rows, int caprows, i
     if (!offsets || !nchannels_taken) return fail(JAERO_EINVAL, "%s: null offsets / nchannels_taken", who);
     if (!rows && caprows > 0) return fail(JAERO_EINVAL, "%s: null rows with caprows > 0", who);
     if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
-    POISONCHK(c, "jaero_read_all");
+    POISONCHK(c, "jaero_read_all", POISON_BANK);
     RowBuf b{};
     int ovbit = 0;
     const int *pending = nullptr;
@@ -2089,7 +2056,7 @@ extern "C" int jaero_read_all(jaero_ctx *c, int what, void *rows, int caprows, i
 extern "C" int jaero_read_status_all(jaero_ctx *c, jaero_status *stt)
 {
     if (!c || !stt) return fail(JAERO_EINVAL, "jaero_read_status_all: bad arguments");
-    POISONCHK(c, "jaero_read_status_all");
+    POISONCHK(c, "jaero_read_status_all", POISON_BANK);
     HIPCHK(hipSetDevice(c->device));
     const int nch = c->o_nch;
     if (!c->d_status_all)
@@ -2119,9 +2086,8 @@ extern "C" long long jaero_debug_read_all_bytes(const jaero_ctx *c)
 extern "C" int jaero_debug_softbit_counts(jaero_ctx *c, int *cnt, int *pending)
 {
     if (!c || !cnt || !pending) return fail(JAERO_EINVAL, "jaero_debug_softbit_counts: bad arguments");
-    POISONCHK(c, "jaero_debug_softbit_counts");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->last_stream));
+    POISONCHK(c, "jaero_debug_softbit_counts", POISON_BANK);
+    QUIESCE(c);
     const size_t n = sizeof(int) * (size_t)c->o_nch;
     HIPCHK(hipMemcpy(cnt, c->o_soft_cnt, n, hipMemcpyDeviceToHost));
     if (c->burst && c->o_nrx) HIPCHK(hipMemcpy(pending, c->o_nrx, n, hipMemcpyDeviceToHost));

@@ -22,9 +22,9 @@
 
 static_assert(RATE_L == JAERO_RATE_L && RATE_BINS == JAERO_RATE_BINS, "the kernel's segment and row are the ABI's");
 
-struct jaero_rate
+struct jaero_rate : DevHandle
 {
-    int device = 0, nch = 0, max_write = 0;
+    int nch = 0, max_write = 0;
     DevMem mem;
     int16_t *d_pend[2] = {nullptr, nullptr}; // [nch][4096] each; d_pend[cur] holds `fill` samples a row
     int cur = 0, fill = 0;
@@ -41,19 +41,12 @@ struct jaero_rate
     unsigned long long *d_lscore = nullptr;
     int *d_lwhere = nullptr;
     KernelTimer timer{1};                    // 0 k_rate_lines, k_rate_lines_gated or k_rate_lines_auto, whichever ran
-    hipStream_t last_stream = nullptr;
-    hipEvent_t order_ev = nullptr;
-    bool poisoned = false;
 };
-
-#define RATEPOISONCHK(r, who) do { if ((r)->poisoned) return fail(JAERO_EHIP, who ": an earlier write of this rate meter failed part-way; destroy it and create a new one"); } while (0)
 
 extern "C" void jaero_rate_destroy(jaero_rate *r)
 {
     if (!r) return;
-    (void)hipSetDevice(r->device);
-    (void)hipStreamSynchronize(r->last_stream);
-    if (r->order_ev) (void)hipEventDestroy(r->order_ev);
+    r->teardown();
     delete r;
 }
 
@@ -116,16 +109,10 @@ extern "C" int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples,
     if (!r || !nseg_done || (nsamples > 0 && !pcm)) return fail(JAERO_EINVAL, "jaero_rate_write: null argument");
     if (nsamples < 0 || nsamples > r->max_write)
         return fail(JAERO_EINVAL, "jaero_rate_write: nsamples %d outside [0, max_write_samples = %d]", nsamples, r->max_write);
-    RATEPOISONCHK(r, "jaero_rate_write");
+    POISONCHK(r, "jaero_rate_write", POISON_RATE);
     HIPCHK(hipSetDevice(r->device));
     hipStream_t st = (hipStream_t)stream;
-    if (st != r->last_stream) // a write on another stream than the previous one waits for what was enqueued there
-    {
-        if (!r->order_ev) HIPCHK(hipEventCreateWithFlags(&r->order_ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(r->order_ev, r->last_stream));
-        HIPCHK(hipStreamWaitEvent(st, r->order_ev, 0));
-        r->last_stream = st;
-    }
+    { const int rc = r->order_behind(st); if (rc) return rc; } // a write on another stream than the previous one waits for what was enqueued there
     *nseg_done = 0;
     if (nsamples == 0) return 0;
     const int n = nsamples, fill = r->fill;
@@ -134,10 +121,10 @@ extern "C" int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples,
     const hipMemcpyKind kind = is_device_ptr ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (nseg == 0) // no segment completes: the write joins the pending one
     {
-        r->poisoned = true;
+        PoisonGuard guard(*r);
         HIPCHK(hipMemcpy2DAsync(r->d_pend[r->cur] + fill, sizeof(int16_t) * RATE_L, pcm, row, row, (size_t)r->nch, kind, st));
         r->fill = fill + n;
-        r->poisoned = false;
+        guard.commit();
         return 0;
     }
     const int16_t *src = pcm;
@@ -147,7 +134,7 @@ extern "C" int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples,
         HIPCHK(hipMemcpyAsync(r->d_in, pcm, row * (size_t)r->nch, hipMemcpyHostToDevice, st));
         src = r->d_in;
     }
-    r->poisoned = true; // from here on the sums, the count and the pending segment advance together or not at all
+    PoisonGuard guard(*r); // from here on the sums, the count and the pending segment advance together or not at all
     const int pi = r->timer.begin(0, st);
     if (r->mode & (JAERO_GATE_AUTO | JAERO_GATE_HIST))
     {
@@ -180,16 +167,15 @@ extern "C" int jaero_rate_write(jaero_rate *r, const int16_t *pcm, int nsamples,
     r->nseg += nseg;
     HIPCHK(hipGetLastError());
     *nseg_done = nseg;
-    r->poisoned = false;
+    guard.commit();
     return 0;
 }
 
 extern "C" int jaero_rate_reset(jaero_rate *r)
 {
     if (!r) return fail(JAERO_EINVAL, "jaero_rate_reset: null handle");
-    RATEPOISONCHK(r, "jaero_rate_reset");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    POISONCHK(r, "jaero_rate_reset", POISON_RATE);
+    QUIESCE(r);
     HIPCHK(hipMemset(r->d_R, 0, sizeof(double) * (size_t)r->nch * RATE_BINS));
     r->nseg = 0; // the pending segment stays: the segment grid is absolute
     return r->mode ? rate_clear_stats(r) : 0; // off, the numbers are the empty ones already; the gates stay but under AUTO
@@ -198,8 +184,7 @@ extern "C" int jaero_rate_reset(jaero_rate *r)
 // ---- gated rate lines (include/jaero_hip.h, "gated rate lines")
 static int rate_set_mode(jaero_rate *r, int mode)
 {
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    QUIESCE(r);
     if ((mode & JAERO_GATE_HIST) && !r->d_hist)
     {
         const int rc = dalloc(r->mem, &r->d_hist, (size_t)r->nch * RATE_HBINS);
@@ -214,18 +199,17 @@ static int rate_set_mode(jaero_rate *r, int mode)
 extern "C" int jaero_gate_enable(jaero_rate *r, int on)
 {
     if (!r) return fail(JAERO_EINVAL, "jaero_gate_enable: null handle");
-    RATEPOISONCHK(r, "jaero_gate_enable");
+    POISONCHK(r, "jaero_gate_enable", POISON_RATE);
     return rate_set_mode(r, on ? JAERO_GATE_MANUAL : 0);
 }
 
 extern "C" int jaero_gate_set(jaero_rate *r, const unsigned long long *gate)
 {
     if (!r || !gate) return fail(JAERO_EINVAL, "jaero_gate_set: null argument");
-    RATEPOISONCHK(r, "jaero_gate_set");
+    POISONCHK(r, "jaero_gate_set", POISON_RATE);
     if (!r->mode) return fail(JAERO_EINVAL, "jaero_gate_set: the gate is off (jaero_gate_enable)");
     if (r->mode & JAERO_GATE_AUTO) return fail(JAERO_EINVAL, "jaero_gate_set: under JAERO_GATE_AUTO the device chooses the gates");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream)); // the launches enqueued so far read the old gates
+    QUIESCE(r); // the launches enqueued so far read the old gates
     HIPCHK(hipMemcpy(r->d_gate, gate, sizeof(unsigned long long) * (size_t)r->nch, hipMemcpyHostToDevice));
     return 0;
 }
@@ -233,10 +217,9 @@ extern "C" int jaero_gate_set(jaero_rate *r, const unsigned long long *gate)
 extern "C" int jaero_gate_read(jaero_rate *r, unsigned long long *stats, unsigned long long *gate, long long *nseg)
 {
     if (!r || !stats || !nseg) return fail(JAERO_EINVAL, "jaero_gate_read: null argument");
-    RATEPOISONCHK(r, "jaero_gate_read");
+    POISONCHK(r, "jaero_gate_read", POISON_RATE);
     if (!r->mode) return fail(JAERO_EINVAL, "jaero_gate_read: the gate is off (jaero_gate_enable)");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    QUIESCE(r);
     HIPCHK(hipMemcpy(stats, r->d_stats, sizeof(unsigned long long) * (size_t)r->nch * 4, hipMemcpyDeviceToHost));
     if (gate) HIPCHK(hipMemcpy(gate, r->d_gate, sizeof(unsigned long long) * (size_t)r->nch, hipMemcpyDeviceToHost));
     *nseg = r->nseg;
@@ -252,17 +235,16 @@ extern "C" int jaero_gate2_enable(jaero_rate *r, int mode)
     const int who = mode & ~JAERO_GATE_HIST; // HIST only together with MANUAL or AUTO, and never both of those
     if (mode != 0 && who != JAERO_GATE_MANUAL && who != JAERO_GATE_AUTO)
         return fail(JAERO_EINVAL, "jaero_gate2_enable: mode %d is none of 0, 1, 2, 1|4, 2|4", mode);
-    RATEPOISONCHK(r, "jaero_gate2_enable");
+    POISONCHK(r, "jaero_gate2_enable", POISON_RATE);
     return rate_set_mode(r, mode);
 }
 
 extern "C" int jaero_gate2_read(jaero_rate *r, unsigned long long *stats, unsigned long long *gate, long long *nseg)
 {
     if (!r || !stats || !nseg) return fail(JAERO_EINVAL, "jaero_gate2_read: null argument");
-    RATEPOISONCHK(r, "jaero_gate2_read");
+    POISONCHK(r, "jaero_gate2_read", POISON_RATE);
     if (!(r->mode & JAERO_GATE_AUTO)) return fail(JAERO_EINVAL, "jaero_gate2_read: the mode has no JAERO_GATE_AUTO (jaero_gate2_enable)");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    QUIESCE(r);
     const size_t w = sizeof(unsigned long long);
     HIPCHK(hipMemcpy2D(stats, 6 * w, r->d_stats, 4 * w, 4 * w, (size_t)r->nch, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy2D(stats + 4, 6 * w, r->d_stats2, 2 * w, 2 * w, (size_t)r->nch, hipMemcpyDeviceToHost));
@@ -274,10 +256,9 @@ extern "C" int jaero_gate2_read(jaero_rate *r, unsigned long long *stats, unsign
 extern "C" int jaero_gate2_read_hist(jaero_rate *r, unsigned *hist, long long *nseg)
 {
     if (!r || !hist || !nseg) return fail(JAERO_EINVAL, "jaero_gate2_read_hist: null argument");
-    RATEPOISONCHK(r, "jaero_gate2_read_hist");
+    POISONCHK(r, "jaero_gate2_read_hist", POISON_RATE);
     if (!(r->mode & JAERO_GATE_HIST)) return fail(JAERO_EINVAL, "jaero_gate2_read_hist: the mode has no JAERO_GATE_HIST (jaero_gate2_enable)");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    QUIESCE(r);
     HIPCHK(hipMemcpy(hist, r->d_hist, sizeof(unsigned) * (size_t)r->nch * RATE_HBINS, hipMemcpyDeviceToHost));
     *nseg = r->nseg;
     return 0;
@@ -286,9 +267,8 @@ extern "C" int jaero_gate2_read_hist(jaero_rate *r, unsigned *hist, long long *n
 extern "C" int jaero_rate_read(jaero_rate *r, double *sums, long long *nseg)
 {
     if (!r || !sums || !nseg) return fail(JAERO_EINVAL, "jaero_rate_read: null argument");
-    RATEPOISONCHK(r, "jaero_rate_read");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    POISONCHK(r, "jaero_rate_read", POISON_RATE);
+    QUIESCE(r);
     HIPCHK(hipMemcpy(sums, r->d_R, sizeof(double) * (size_t)r->nch * RATE_BINS, hipMemcpyDeviceToHost));
     *nseg = r->nseg;
     return 0;
@@ -325,9 +305,8 @@ extern "C" int jaero_lines_classify(jaero_rate *r, int kmin, int nd, const int *
         dd.d[i] = d[i];
     }
     if (kmin < 1 || kmin > RATE_BINS - 2) return fail(JAERO_EINVAL, "jaero_lines_classify: kmin %d outside 1 .. %d", kmin, RATE_BINS - 2);
-    RATEPOISONCHK(r, "jaero_lines_classify");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    POISONCHK(r, "jaero_lines_classify", POISON_RATE);
+    QUIESCE(r);
     if (!r->d_lwhere)
     {
         int rc = 0;
@@ -369,9 +348,8 @@ extern "C" int jaero_debug_rate_poke(jaero_rate *r, const double *sums, long lon
 {
     if (!r || !sums) return fail(JAERO_EINVAL, "jaero_debug_rate_poke: null argument");
     if (nseg < 0) return fail(JAERO_EINVAL, "jaero_debug_rate_poke: nseg %lld < 0", nseg);
-    RATEPOISONCHK(r, "jaero_debug_rate_poke");
-    HIPCHK(hipSetDevice(r->device));
-    HIPCHK(hipStreamSynchronize(r->last_stream));
+    POISONCHK(r, "jaero_debug_rate_poke", POISON_RATE);
+    QUIESCE(r);
     HIPCHK(hipMemcpy(r->d_R, sums, sizeof(double) * (size_t)r->nch * RATE_BINS, hipMemcpyHostToDevice));
     r->nseg = nseg;
     return 0;

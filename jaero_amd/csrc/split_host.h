@@ -1,41 +1,24 @@
 // split_host.h -- host side of the channeliser's splitter (jaero_split_*, DESIGN 18 "Splitter"): one front end, any number of outputs.
 //
-// A jaero_split owns one front end -- a jaero_chan built by chan_build_front (and capture_build with a capture) that has no output of its own:
-// histories, staging, d_spec, d_tw, blocks_done -- and one view per output: a jaero_chan built by chan_build_out whose d_spec is the front's.
-// A write is the front end's own write (chan_write / capture_write); where that runs a stand-alone handle's output behind the forward
-// transform (chan_after_fwd), a front end runs every view's (split_outputs), with the (nch, nblk, p0) the view's stand-alone twin would launch
-// with.  No kernel is new and none is launched with other arguments than a stand-alone handle's: that is what makes a view's output its
-// twin's bit for bit.  Everything is enqueued on the one stream of the write, so the next write's forward transform, which overwrites
-// d_spec, runs behind every view's launches.
+// A jaero_split owns one ChanFront (built by chan_build_front, and capture_build with a capture) and one view per output: a jaero_chan built
+// by chan_build_out that owns no front end and reads the splitter's d_spec.  A write is the front end's own write (chan_write / capture_write),
+// which runs every output's kernels behind the forward transform (chan_after_fwd), each with the (nch, nblk, p0) the view's stand-alone twin
+// would launch with.  No kernel is new and none is launched with other arguments than a stand-alone handle's: that is what makes a view's
+// output its twin's bit for bit.  Everything is enqueued on the one stream of the write, so the next write's forward transform, which
+// overwrites d_spec, runs behind every view's launches.
 #pragma once
 
 struct jaero_split
 {
     int fs_c = 0;
-    std::unique_ptr<jaero_chan> front;
+    ChanFront front;
     std::vector<std::unique_ptr<jaero_chan>> views;
 };
-
-// every view's half of a write, in output order (chan_after_fwd of the front end)
-static int split_outputs(jaero_split *s, int nblk, long long p0, hipStream_t st)
-{
-    for (auto &v : s->views)
-    {
-        const int rc = chan_outputs(v.get(), nblk, p0, st);
-        if (rc) return rc;
-    }
-    return 0;
-}
 
 extern "C" void jaero_split_destroy(jaero_split *s)
 {
     if (!s) return;
-    if (s->front)
-    {
-        (void)hipSetDevice(s->front->device);
-        (void)hipStreamSynchronize(s->front->last_stream);
-        if (s->front->order_ev) (void)hipEventDestroy(s->front->order_ev);
-    }
+    s->front.teardown();
     delete s;
 }
 
@@ -73,55 +56,29 @@ extern "C" int jaero_split_create(int device, const jaero_capture *cap, int fs_c
     std::unique_ptr<jaero_split> s(new (std::nothrow) jaero_split());
     if (!s) return fail(JAERO_ENOMEM, "jaero_split_create: out of memory");
     s->fs_c = fs_c;
-    s->front.reset(new (std::nothrow) jaero_chan());
-    if (!s->front) return fail(JAERO_ENOMEM, "jaero_split_create: out of memory");
-    jaero_chan *f = s->front.get();
+    ChanFront *f = &s->front;
     int rc = chan_build_front(f, device, max_write_iq, smax);
     if (rc) return rc;
     if (cap && (rc = capture_build(f, cap, L, Mr, resample, max_write_iq, smax))) return rc;
-    f->split = s.get();
     for (int g = 0; g < noutputs; g++)
     {
         const jaero_chan_output &o = outs[g];
-        std::unique_ptr<jaero_chan> v(new (std::nothrow) jaero_chan());
-        if (!v) return fail(JAERO_ENOMEM, "jaero_split_create: out of memory");
-        v->device = device; v->max_write_iq = max_write_iq; v->nblk_max = f->nblk_max;
-        v->front = f;
-        v->d_spec = f->d_spec; // the front end's: v->mem does not own it
-        if ((rc = chan_build_out(v.get(), fs_c / o.out_rate, o.out_rate, o.nchannels, o.ch, o.taps, o.ntaps))) return rc;
-        s->views.push_back(std::move(v));
+        s->views.emplace_back(new (std::nothrow) jaero_chan());
+        if (!s->views.back()) return fail(JAERO_ENOMEM, "jaero_split_create: out of memory");
+        if ((rc = chan_build_out(s->views.back().get(), f, fs_c / o.out_rate, o.out_rate, o.nchannels, o.ch, o.taps, o.ntaps))) return rc;
     }
     *out = s.release();
     return 0;
 }
 
-static bool split_poisoned(const jaero_split *s)
-{
-    if (s->front->poisoned) return true;
-    for (const auto &v : s->views)
-        if (v->poisoned) return true; // a retune of the view that failed part-way
-    return false;
-}
-
-// the write behind the checks both entry points share; *nblk: the blocks it completed
+// the write both entry points share; nout: one entry per output.  Refused: nothing advanced; failed part-way: the front end is poisoned, and
+// with it every view
 static int split_write(jaero_split *s, const void *iq, int niq, int is_device_ptr, void *stream, int *nout, const char *who)
 {
     if (niq < 0 || (niq > 0 && !iq)) return fail(JAERO_EINVAL, "%s: bad arguments", who);
-    if (split_poisoned(s)) return fail(JAERO_EHIP, "%s: an earlier write of this splitter failed part-way; destroy it and create a new one", who);
-    jaero_chan *f = s->front.get();
-    const long long before = f->blocks_done;
-    int n0 = 0;
-    const int rc = f->cap ? capture_write(f, iq, niq, is_device_ptr, stream, &n0, who)
-                          : chan_write(f, (const int16_t *)iq, niq, is_device_ptr, stream, &n0, who);
-    if (rc) return rc; // refused: nothing advanced, the views keep their last write; failed part-way: the front end is poisoned, and with it every view
-    const int nblk = (int)(f->blocks_done - before);
-    for (size_t g = 0; g < s->views.size(); g++)
-    {
-        jaero_chan *v = s->views[g].get();
-        v->last_stream = f->last_stream;
-        v->last_nout = nout[g] = nblk * v->Mo;
-    }
-    return 0;
+    ChanFront *f = &s->front;
+    POISONCHK(f, who, POISON_SPLIT);
+    return f->cap ? capture_write(f, iq, niq, is_device_ptr, stream, nout, who) : chan_write(f, (const int16_t *)iq, niq, is_device_ptr, stream, nout, who);
 }
 
 extern "C" int jaero_split_write(jaero_split *s, const void *iq, int niq, int is_device_ptr, void *stream, int *nout)
@@ -148,7 +105,7 @@ extern "C" int jaero_split_feed(jaero_split *s, jaero_ctx *const *banks, const v
         if (!banks[g] || nout[g] <= 0) continue;
         if ((rc = jaero_write(banks[g], s->views[g]->d_pcm, nout[g], JAERO_PCM_CHANNEL_MAJOR, 1, stream)))
         {
-            s->front->poisoned = true; // the banks behind this one are not fed: they are no longer at one point of the capture
+            s->front.poisoned = true; // the banks behind this one are not fed: they are no longer at one point of the capture
             return rc;
         }
     }
@@ -169,14 +126,14 @@ extern "C" int jaero_split_info(const jaero_split *s, int *noutputs, int *fs_c, 
     if (!s) return fail(JAERO_EINVAL, "jaero_split_info: null handle");
     if (noutputs) *noutputs = (int)s->views.size();
     if (fs_c) *fs_c = s->fs_c;
-    if (nblk_max) *nblk_max = s->front->nblk_max;
+    if (nblk_max) *nblk_max = s->front.nblk_max;
     return 0;
 }
 
 extern "C" int jaero_split_profile_enable(jaero_split *s, int on)
 {
     if (!s) return fail(JAERO_EINVAL, "jaero_split_profile_enable: null handle");
-    s->front->timer.on = on != 0;
+    s->front.timer.on = on != 0;
     for (auto &v : s->views) v->timer.on = on != 0;
     return 0;
 }
@@ -185,6 +142,6 @@ extern "C" int jaero_split_profile_enable(jaero_split *s, int on)
 extern "C" int jaero_split_profile_read(jaero_split *s, int which, double *total_ms, int *launches, int reset)
 {
     if (!s || which < 0 || which > 1) return fail(JAERO_EINVAL, "jaero_split_profile_read: bad arguments");
-    jaero_chan *f = s->front.get();
-    return f->timer.read(f->device, which == 1 ? 4 : f->cap ? 5 : 0, total_ms, launches, reset);
+    ChanFront &f = s->front;
+    return f.timer.read(f.device, which == 1 ? 4 : f.cap ? 5 : 0, total_ms, launches, reset);
 }
