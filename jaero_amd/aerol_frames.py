@@ -36,9 +36,29 @@ def crc16(data: bytes) -> int:
 
 
 def make_su(payload10: bytes) -> bytes:
+    """10 payload bytes -> the 12-byte signal unit; 12 bytes are taken as a finished unit, CRC field and all (so that a test can send
+    a wrong, a zero or an all-zero unit)."""
+    if len(payload10) == 12:
+        return bytes(payload10)
     assert len(payload10) == 10
     c = crc16(payload10)
     return bytes(payload10) + bytes([c & 0xFF, c >> 8])
+
+
+def payload_with_crc(prefix8: bytes, target: int = 0) -> bytes:
+    """A 10-byte payload beginning with `prefix8` whose CRC-16 is `target`, found by trying all 65 536 values of the last two bytes
+    (they map one to one onto the CRC)."""
+    assert len(prefix8) == 8
+    tail = np.arange(65536, dtype=np.uint32)
+    reg = np.full(65536, (~crc16(prefix8)) & 0xFFFF, dtype=np.uint32)  # the register behind the prefix, before the final inversion
+    for k in range(16):
+        c = (reg ^ (tail >> k)) & 1
+        reg = (reg >> 1) ^ (c * 0x8408)
+    hit = np.flatnonzero(((~reg) & 0xFFFF) == target)
+    assert len(hit) == 1
+    out = bytes(prefix8) + bytes([int(hit[0]) & 0xFF, int(hit[0]) >> 8])
+    assert crc16(out) == target
+    return out
 
 
 def scrambler_sequence(n: int = 5000) -> np.ndarray:
@@ -154,22 +174,23 @@ def _bytes_to_bits(data: bytes) -> np.ndarray:
     return np.unpackbits(np.frombuffer(data, dtype=np.uint8), bitorder="little")
 
 
-def rt_packet_bits(kind: str, payload) -> np.ndarray:
+def rt_packet_bits(kind: str, payload, *, bad_crc=()) -> np.ndarray:
     """Channel bits of one R packet (`payload`: 17 bytes) or T packet (`payload`: (4-byte header, [10-byte SUs], at least two)) as
     RTChannelDeleaveFECScram::update expects them (aerol.h:785-873): [fields + CRC-16 each] -> scrambled -> K=7 r=1/2 from the zero
-    state, flushed -> 64 x cols block interleaver with cols = 5 (R) or 5 + 3 (n - 1) (T with n signal units)."""
+    state, flushed -> 64 x cols block interleaver with cols = 5 (R) or 5 + 3 (n - 1) (T with n signal units).  `bad_crc`: fields (0 =
+    the R payload / the T header, k = T unit k - 1) sent with a wrong CRC."""
     if kind == "R":
         assert len(payload) == 17
         b = _bytes_to_bits(bytes(payload))
-        info = np.concatenate([b, crc16_bits(b)])
+        info = np.concatenate([b, crc16_bits(b) ^ (1 if 0 in bad_crc else 0)])
         cols = 5
     else:
         hdr, sus = payload
         assert len(hdr) == 4 and len(sus) >= 2 and all(len(x) == 10 for x in sus)
         parts = []
-        for field in [bytes(hdr)] + [bytes(x) for x in sus]:
+        for k, field in enumerate([bytes(hdr)] + [bytes(x) for x in sus]):
             b = _bytes_to_bits(field)
-            parts += [b, crc16_bits(b)]
+            parts += [b, crc16_bits(b) ^ (1 if k in bad_crc else 0)]
         info = np.concatenate(parts)
         cols = 5 + 3 * (len(sus) - 1)
     ndec = 32 * cols
@@ -217,25 +238,29 @@ def interleave_msk(coded: np.ndarray) -> np.ndarray:
     return out
 
 
-def rt_packet_bits_msk(kind: str, payload) -> np.ndarray:
+def rt_packet_bits_msk(kind: str, payload, *, count=None, bad_crc=()) -> np.ndarray:
     """600 / 1200 bps R or T packet for RTChannelDeleaveFECScram::updateMSK (aerol.h:631-782).  A T packet is found through the count
     its SECOND signal unit carries in the low six bits of its first byte: targetSUSize = 2 + count (halved + 1 from 16 up), and the
     block is decoded at (targetSUSize + 1) * 3 + 2 columns, which hold targetSUSize + 1 units.  `payload` for T: (4-byte header,
-    list of 10-byte units, at least 4); the count field of unit 1 is overwritten accordingly."""
+    list of 10-byte units, at least 4); the count field of unit 1 is overwritten accordingly -- or, with `count` given, set to that
+    value whatever the number of units sent (at least 2).  `bad_crc` as in rt_packet_bits."""
     if kind == "R":
         b = _bytes_to_bits(bytes(payload))
-        info = np.concatenate([b, crc16_bits(b)])
+        info = np.concatenate([b, crc16_bits(b) ^ (1 if 0 in bad_crc else 0)])
         cols = 5
     else:
         hdr, sus = payload
         sus = [bytearray(x) for x in sus]
         T = len(sus) - 1
-        assert 3 <= T < 16
-        sus[1][0] = (sus[1][0] & 0xC0) | (T - 2)
+        if count is None:
+            assert 3 <= T < 16
+            count = T - 2
+        assert T >= 1 and 0 <= count < 64
+        sus[1][0] = (sus[1][0] & 0xC0) | count
         parts = []
-        for field in [bytes(hdr)] + [bytes(x) for x in sus]:
+        for k, field in enumerate([bytes(hdr)] + [bytes(x) for x in sus]):
             b = _bytes_to_bits(field)
-            parts += [b, crc16_bits(b)]
+            parts += [b, crc16_bits(b) ^ (1 if k in bad_crc else 0)]
         info = np.concatenate(parts)
         cols = (T + 1) * 3 + 2
     ndec = 32 * cols
@@ -273,8 +298,8 @@ C_UW1, C_UW2 = 216866263330005, 3012071630031408
 
 
 def c_channel_bits(frames, *, invert_real: bool = False, invert_imag: bool = False, uw=(C_UW1, C_UW2)):
-    """frames: list of (voice uint8[300], [three 10-byte payloads]) -> channel bits uint8 (4200 per frame).  The decoder hands out
-    frame f while it receives frame f + 1."""
+    """frames: list of (voice uint8[300], [three 10-byte payloads, or finished 12-byte units]) -> channel bits uint8 (4200 per frame).
+    The decoder hands out frame f while it receives frame f + 1."""
     scr = scrambler_sequence()
     info = []
     for voice, pays in frames:

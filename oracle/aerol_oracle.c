@@ -91,8 +91,53 @@ static uint16_t crc16_bytes(const unsigned char *bytes, int n) /* AeroLcrc16::ca
     return (uint16_t)~crc;
 }
 
+/* One counter per arm of every data-dependent decision of the three paths below (decisions that depend on a loop index alone -- "every
+ * eighth bit is a byte", "every 96 bits skip 13" -- are not counted).  jo_aerol_coverage reads them in this order, jo_aerol_coverage_name
+ * names them.  Prefixes say which chain a counter belongs to (tests/aerol_branch_cases.py: CHAINS). */
+#define AEROL_COV_LIST(X) \
+    /* jo_aerol_tick_dcd */ \
+    X(tick_pos) X(tick_neg) X(tick_zero) X(tick_drop) X(tick_keep) \
+    /* jo_aerol_write, every mode but the C channel */ \
+    X(w_marker) X(w_softbit) X(w_muw_inc) X(w_muw_sat) \
+    X(oq_det_window) X(oq_det_le0) X(oq_det_nodcd) X(oq_det_off) \
+    X(pi_inv_hit) X(pi_up_hit) X(pi_miss) \
+    X(gsl_first_hit) X(gsl_first_miss) X(gsl_second_hit) X(gsl_second_miss) \
+    X(bm_refuse) X(bm_accept) \
+    X(inv_on) X(inv_off) X(inv_soft_gt) X(inv_soft_lt) X(inv_soft_128) \
+    X(mk_refuse) X(mk_accept) X(mk_nosync) \
+    X(px_hit) X(px_miss) \
+    X(cn_inc) X(cn_sat) \
+    X(hd_first) X(hd_shift) X(hd_none) X(hd_done) X(hd_not_done) \
+    X(br_reset_bad) X(br_reset_nothing) X(br_bad_event) X(br_no_bad_event) \
+    X(bl_cntr16) X(bl_not_cntr16) X(bl_idx_neg) X(bl_idx_ok) X(bl_done) X(bl_done_sat) X(bl_fill) \
+    X(sy_sync) X(sy_nosync) X(sy_short) X(sy_exact_len) \
+    X(wr_wrap) X(wr_nowrap) X(wr_end_of_signal) \
+    /* block_done */ \
+    X(bd_scr_ok) X(bd_scr_clamp) X(bd_info_ok) X(bd_info_over) X(fe_frame) X(fe_not_frame) \
+    X(fe_zero_unit) X(fe_zero_crc_payload) X(fe_true_crc0) X(fe_crc_field_nonzero) \
+    X(fe_ok_inc) X(fe_ok_cap) X(fe_bad_dec) X(fe_bad_floor) X(fe_dcd_rise) X(fe_dcd_norise) \
+    /* rt_update (10500 bps R/T) */ \
+    X(rt_full) X(rt_room) X(rt_no_trial) X(rt_trial) X(rt_trial_128) X(rt_scr_ok) X(rt_scr_clamp) \
+    X(rt_r_fail) X(rt_r_ok) X(rt_t_hdr_bad) X(rt_t_hdr_ok) X(rt_t_su_bad) X(rt_t_su_ok) X(rt_t_bad_full) X(rt_t_test_failed) X(rt_t_ok) \
+    /* rt_update_msk (600 / 1200 bps R/T) */ \
+    X(mu_full) X(mu_room) X(mu_no_trial) X(mu_trial_5) X(mu_trial_target) X(mu_trial_11) X(mu_trial_50) X(mu_scr_ok) X(mu_scr_clamp) \
+    X(mu_r_ok) X(mu_r_fail) X(mu_hdr_bad) X(mu_11_plain) X(mu_11_halved) X(mu_t_ok) X(mu_hdr_ok_no_match) \
+    /* the C channel: cpd_update, c_write, c_frame_done */ \
+    X(c_p1_inv) X(c_p1_up) X(c_p2_inv) X(c_p2_up) X(c_miss) \
+    X(c_det_window) X(c_det_le0) X(c_det_off) X(c_sync) X(c_nosync) X(c_cntr_inc) X(c_cntr_sat) X(c_store) X(c_nostore) \
+    X(c_blk_done) X(c_blk_fill) X(c_cdel_ok) X(c_cdel_over) X(c_frame_end) X(c_not_frame_end) \
+    X(c_first_short) X(c_full_frame) X(c_scr_ok) X(c_scr_clamp) \
+    X(c_ok_inc) X(c_ok_cap) X(c_bad_dec) X(c_bad_floor) X(c_dcd_rise) X(c_dcd_norise) X(c_voice_ok) X(c_voice_over)
+#define AEROL_COV_ENUM(n) AC_##n,
+enum { AEROL_COV_LIST(AEROL_COV_ENUM) AC_NCOV };
+#define AEROL_COV_NAME(n) #n,
+static const char *const aerol_cov_names[AC_NCOV] = { AEROL_COV_LIST(AEROL_COV_NAME) };
+#define CV(n) (a->cov[AC_##n]++)
+#define CVIF(cond, yes, no) ((cond) ? (CV(yes), 1) : (CV(no), 0)) /* the condition's value, its arm counted */
+
 struct jo_aerol
 {
+    long cov[AC_NCOV];
     int ifb, useingOQPSK, N, blocksz, dl2_len;
     int NumberOfBits, BitsInHeader, TotalNumberOfBits;
     int cntr, datacd, datacdcountdown, gotsync_last, realimag, blockcnt, muw;
@@ -202,14 +247,30 @@ void jo_aerol_destroy(jo_aerol *a)
     free(a->block); free(a->dl2); jo_codec_destroy(a->codec); free(a->sus.p); free(a->events.p); free(a);
 }
 int jo_aerol_dcd(jo_aerol *a) { return a->datacd; }
+/* times each arm of the decisions above was taken by this object: up to cap longs in AEROL_COV_LIST order; returns the number of counters */
+long jo_aerol_coverage(jo_aerol *a, long *dst, long cap)
+{
+    for (long k = 0; k < AC_NCOV && k < cap; k++) dst[k] = a->cov[k];
+    return AC_NCOV;
+}
+const char *jo_aerol_coverage_name(long k) { return (k >= 0 && k < AC_NCOV) ? aerol_cov_names[k] : NULL; }
+/* read-only copy of the state that says where a write boundary fell: cntr, datacd, datacdcountdown, realimag, gotsync_last, scr_pos, muw,
+ * rt_blockptr, rt_last, rt_targetBlocks, rt_targetSUSize, ncdel */
+void jo_aerol_peek(jo_aerol *a, long *dst12)
+{
+    dst12[0] = a->cntr; dst12[1] = a->datacd; dst12[2] = a->datacdcountdown; dst12[3] = a->realimag; dst12[4] = a->gotsync_last;
+    dst12[5] = a->scr_pos; dst12[6] = a->muw; dst12[7] = a->rt_blockptr; dst12[8] = a->rt_last; dst12[9] = a->rt_targetBlocks;
+    dst12[10] = a->rt_targetSUSize; dst12[11] = a->ncdel;
+}
 
 /* AeroL::updateDCD (aerol.cpp:1109-1122); the reference calls it from a 1 s wall-clock QTimer, tests call it at chosen points of
  * the stream.  The DataCarrierDetect(false) it may emit is logged with the index of the next soft bit. */
 int jo_aerol_tick_dcd(jo_aerol *a)
 {
-    if (a->datacdcountdown > 0) a->datacdcountdown -= 3;
-    else if (a->datacdcountdown < 0) a->datacdcountdown = 0;
-    if (a->datacd && !a->datacdcountdown)
+    if (a->datacdcountdown > 0) { a->datacdcountdown -= 3; CV(tick_pos); }
+    else if (a->datacdcountdown < 0) { a->datacdcountdown = 0; CV(tick_neg); }
+    else CV(tick_zero);
+    if (CVIF(a->datacd && !a->datacdcountdown, tick_drop, tick_keep))
     {
         a->datacd = 0;
         ev(a, a->nbits_total, 0, 0);
@@ -237,7 +298,7 @@ static void block_done(jo_aerol *a, long bitidx) /* aerol.cpp:1553-1600 */
         a->dl2_ptr++; a->dl2_ptr %= a->dl2_sz;
         int v = a->dl2[a->dl2_ptr];
         /* scrambler.update :1563 */
-        v ^= a->scr[a->scr_pos < 5000 ? a->scr_pos : 4999];
+        v ^= a->scr[CVIF(a->scr_pos < 5000, bd_scr_ok, bd_scr_clamp) ? a->scr_pos : 4999];
         a->scr_pos++;
         bits[h] = (unsigned char)v;
     }
@@ -248,12 +309,12 @@ static void block_done(jo_aerol *a, long bitidx) /* aerol.cpp:1553-1600 */
         {
             ch |= bits[h] * 128;
             charptr++; charptr %= 8;
-            if (charptr == 0) { if (a->ninfo < (int)sizeof(a->infofield)) a->infofield[a->ninfo++] = ch; ch = 0; }
+            if (charptr == 0) { if (CVIF(a->ninfo < (int)sizeof(a->infofield), bd_info_ok, bd_info_over)) a->infofield[a->ninfo++] = ch; ch = 0; }
             else ch >>= 1;
         }
     }
     free(deleaved); free(bits);
-    if ((a->cntr - a->BitsInHeader) == (a->NumberOfBits - 1)) /* frame is done :1580 */
+    if (CVIF((a->cntr - a->BitsInHeader) == (a->NumberOfBits - 1), fe_frame, fe_not_frame)) /* frame is done :1580 */
     {
         for (int kk = 0; kk < a->ninfo / 12; kk++)
         {
@@ -264,11 +325,13 @@ static void block_done(jo_aerol *a, long bitidx) /* aerol.cpp:1553-1600 */
             {
                 int tsum = 0;
                 for (int ii = 0; ii < 10; ii++) tsum += su[ii];
-                if (tsum == 0) crc_calc = 0;
+                if (CVIF(tsum == 0, fe_zero_unit, fe_zero_crc_payload)) crc_calc = 0;
             }
-            if (crc_calc == crc_rec) { if (a->datacdcountdown < 12) a->datacdcountdown += 2; }
-            else { if (a->datacdcountdown > 0) a->datacdcountdown -= 3; }
-            if (!a->datacd && a->datacdcountdown > 2) { a->datacd = 1; ev(a, bitidx, 0, 1); }
+            else if (!crc_rec) CV(fe_true_crc0); /* a zero field that IS the payload's CRC */
+            else CV(fe_crc_field_nonzero);
+            if (crc_calc == crc_rec) { if (CVIF(a->datacdcountdown < 12, fe_ok_inc, fe_ok_cap)) a->datacdcountdown += 2; }
+            else { if (CVIF(a->datacdcountdown > 0, fe_bad_dec, fe_bad_floor)) a->datacdcountdown -= 3; }
+            if (CVIF(!a->datacd && a->datacdcountdown > 2, fe_dcd_rise, fe_dcd_norise)) { a->datacd = 1; ev(a, bitidx, 0, 1); }
             int32_t row[16];
             row[0] = (int32_t)a->nframes; row[1] = kk;
             for (int j = 0; j < 12; j++) row[2 + j] = su[j];
@@ -297,7 +360,7 @@ static int crc16_bits_check(const unsigned char *bits, int numberofbits) /* Aero
 static int rt_reset(jo_aerol *a) /* resetblockptr aerol.h:591-602 */
 {
     a->rt_blockptr = 0;
-    if (a->rt_last == RT_TEST_FAILED) { a->rt_last = RT_NOTHING; return RT_BAD; }
+    if (CVIF(a->rt_last == RT_TEST_FAILED, br_reset_bad, br_reset_nothing)) { a->rt_last = RT_NOTHING; return RT_BAD; }
     a->rt_last = RT_NOTHING;
     return RT_NOTHING;
 }
@@ -326,10 +389,11 @@ static void rt_emit(jo_aerol *a, const unsigned char *deconvol, int ndeconvol, i
 }
 static int rt_update(jo_aerol *a, int bit) /* RTChannelDeleaveFECScram::update aerol.h:785-873 */
 {
-    if (a->rt_blockptr >= RT_BLOCKSZ) return RT_FULL;
+    if (CVIF(a->rt_blockptr >= RT_BLOCKSZ, rt_full, rt_room)) return RT_FULL;
     a->rt_block[a->rt_blockptr] = bit;
     a->rt_blockptr++;
-    if (((a->rt_blockptr - (64 * 5)) % (64 * 3)) != 0) return RT_NOTHING; /* C '%': also true for negative multiples -- none occur below 64*5 except 128 */
+    if (CVIF(((a->rt_blockptr - (64 * 5)) % (64 * 3)) != 0, rt_no_trial, rt_trial)) return RT_NOTHING;
+    if (a->rt_blockptr == 128) CV(rt_trial_128); /* C '%': also true for negative multiples -- none occur below 64*5 except 128 */
     const int blockptr = a->rt_blockptr, cols = blockptr / 64;
     /* deinterleave_ba(block, cols) aerol.cpp:603-625 */
     unsigned char *del = (unsigned char *)malloc((size_t)blockptr);
@@ -339,27 +403,27 @@ static int rt_update(jo_aerol *a, int bit) /* RTChannelDeleaveFECScram::update a
     unsigned char *dec = (unsigned char *)malloc((size_t)blockptr);
     const int nd = jo_decode_soft(a->rt_codec, del, blockptr, dec); /* Decode_soft(delBlock, blockptr) */
     a->rt_scr_pos = 0; /* scrambler.reset(); scrambler.update(deconvol) */
-    for (int h = 0; h < nd; h++) dec[h] ^= a->scr[a->rt_scr_pos < 5000 ? a->rt_scr_pos : 4999], a->rt_scr_pos++;
+    for (int h = 0; h < nd; h++) dec[h] ^= a->scr[CVIF(a->rt_scr_pos < 5000, rt_scr_ok, rt_scr_clamp) ? a->rt_scr_pos : 4999], a->rt_scr_pos++;
     int result;
     if (blockptr == 64 * 5)
     {
-        if (!crc16_bits_check(dec, 8 * 19)) { a->rt_last = RT_TEST_FAILED; result = RT_TEST_FAILED; }
+        if (CVIF(!crc16_bits_check(dec, 8 * 19), rt_r_fail, rt_r_ok)) { a->rt_last = RT_TEST_FAILED; result = RT_TEST_FAILED; }
         else { rt_emit(a, dec, nd, 0, 1); a->rt_blockptr = RT_BLOCKSZ; a->rt_last = RT_OK_R; result = RT_OK_R; }
     }
     else
     {
         int ok = crc16_bits_check(dec, 8 * 6);
-        if (ok)
+        if (CVIF(ok, rt_t_hdr_ok, rt_t_hdr_bad))
         {
             a->rt_numberofsus = 1 + (blockptr - (64 * 5)) / (64 * 3);
-            for (int i = 0; i < a->rt_numberofsus && ok; i++) ok = crc16_bits_check(dec + (8 * 6) + (8 * 12) * i, 8 * 12);
+            for (int i = 0; i < a->rt_numberofsus && ok; i++) ok = CVIF(crc16_bits_check(dec + (8 * 6) + (8 * 12) * i, 8 * 12), rt_t_su_ok, rt_t_su_bad);
         }
         if (!ok)
         {
-            if (blockptr >= RT_BLOCKSZ) { a->rt_last = RT_BAD; result = RT_BAD; }
+            if (CVIF(blockptr >= RT_BLOCKSZ, rt_t_bad_full, rt_t_test_failed)) { a->rt_last = RT_BAD; result = RT_BAD; }
             else { a->rt_last = RT_TEST_FAILED; result = RT_TEST_FAILED; }
         }
-        else { rt_emit(a, dec, nd, 1, 2); a->rt_blockptr = RT_BLOCKSZ; a->rt_last = RT_OK_T; result = RT_OK_T; }
+        else { CV(rt_t_ok); rt_emit(a, dec, nd, 1, 2); a->rt_blockptr = RT_BLOCKSZ; a->rt_last = RT_OK_T; result = RT_OK_T; }
     }
     free(del); free(dec);
     return result;
@@ -367,11 +431,12 @@ static int rt_update(jo_aerol *a, int bit) /* RTChannelDeleaveFECScram::update a
 
 static int rt_update_msk(jo_aerol *a, int bit) /* RTChannelDeleaveFECScram::updateMSK aerol.h:631-782 */
 {
-    if (a->rt_blockptr >= RT_BLOCKSZ) return RT_FULL;
+    if (CVIF(a->rt_blockptr >= RT_BLOCKSZ, mu_full, mu_room)) return RT_FULL;
     a->rt_block[a->rt_blockptr] = bit;
     a->rt_blockptr++;
     const int blockptr = a->rt_blockptr, nb = blockptr / 64;
-    if (!((((blockptr - (64 * 5)) % (64 * 3)) == 0) && (nb == 5 || nb == a->rt_targetBlocks || nb == 11 || nb == 50))) return RT_NOTHING;
+    if (!((((blockptr - (64 * 5)) % (64 * 3)) == 0) && (nb == 5 || nb == a->rt_targetBlocks || nb == 11 || nb == 50))) { CV(mu_no_trial); return RT_NOTHING; }
+    if (nb == 5) CV(mu_trial_5); else if (nb == a->rt_targetBlocks) CV(mu_trial_target); else if (nb == 11) CV(mu_trial_11); else CV(mu_trial_50);
     /* deinterleaveMSK_ba(block, blocks) aerol.cpp:671-711: 5 columns, then groups of 3 */
     unsigned char *del = (unsigned char *)malloc((size_t)blockptr);
     int k = 0;
@@ -383,32 +448,34 @@ static int rt_update_msk(jo_aerol *a, int bit) /* RTChannelDeleaveFECScram::upda
     unsigned char *dec = (unsigned char *)malloc((size_t)blockptr);
     const int nd = jo_decode_soft(a->rt_codec, del, blockptr, dec);
     a->rt_scr_pos = 0;
-    for (int h = 0; h < nd; h++) dec[h] ^= a->scr[a->rt_scr_pos < 5000 ? a->rt_scr_pos : 4999], a->rt_scr_pos++;
+    for (int h = 0; h < nd; h++) dec[h] ^= a->scr[CVIF(a->rt_scr_pos < 5000, mu_scr_ok, mu_scr_clamp) ? a->rt_scr_pos : 4999], a->rt_scr_pos++;
     int result = RT_NOTHING;
     if (blockptr == 64 * 5)
     {
         a->rt_targetSUSize = 0; a->rt_targetBlocks = 0;
-        if (crc16_bits_check(dec, 8 * 19)) { rt_emit(a, dec, nd, 0, 1); a->rt_blockptr = RT_BLOCKSZ; a->rt_last = RT_OK_R; result = RT_OK_R; }
+        if (CVIF(crc16_bits_check(dec, 8 * 19), mu_r_ok, mu_r_fail)) { rt_emit(a, dec, nd, 0, 1); a->rt_blockptr = RT_BLOCKSZ; a->rt_last = RT_OK_R; result = RT_OK_R; }
         else result = RT_NOTHING; /* lastpacketstate untouched */
     }
-    else if (!crc16_bits_check(dec, 8 * 6)) { a->rt_last = RT_BAD; result = RT_BAD; }
+    else if (!crc16_bits_check(dec, 8 * 6)) { CV(mu_hdr_bad); a->rt_last = RT_BAD; result = RT_BAD; }
     else if (nb == 11)
     {
         /* the signal unit after the initial one tells how many there are :709-729 */
         const unsigned char *isu = dec + (8 * 6) + (8 * 12) * 1;
         int bin = 2 + (isu[0] * 1 + isu[1] * 2 + isu[2] * 4 + isu[3] * 8 + isu[4] * 16 + isu[5] * 32);
         a->rt_targetSUSize = bin;
-        if (a->rt_targetSUSize >= 16) a->rt_targetSUSize = a->rt_targetSUSize / 2 + 1;
+        if (CVIF(a->rt_targetSUSize >= 16, mu_11_halved, mu_11_plain)) a->rt_targetSUSize = a->rt_targetSUSize / 2 + 1;
         a->rt_targetBlocks = ((a->rt_targetSUSize + 1) * 3) + 2;
         result = RT_NOTHING;
     }
     else if (nb == a->rt_targetBlocks)
     {
         /* the per-unit CRCs are counted but cannot fail the packet (ok <= targetSUSize always) :732-766 */
+        CV(mu_t_ok);
         rt_emit(a, dec, nd, 1, 2);
         a->rt_numberofsus = a->rt_targetSUSize;
         a->rt_blockptr = RT_BLOCKSZ; a->rt_last = RT_OK_T; result = RT_OK_T;
     }
+    else CV(mu_hdr_ok_no_match); /* 50 blocks, or the announced count when that is 11 blocks: nothing */
     free(del); free(dec);
     return result;
 }
@@ -422,14 +489,15 @@ static int cpd_update(jo_aerol *a, int q, int val)
     for (int i = 0; i < n - 1; i++) { b1[i] = b1[i + 1]; xorsum += b1[i] ^ a->cpd[q].p1[i]; }
     xorsum += val ^ a->cpd[q].p1[n - 1];
     b1[n - 1] = val;
-    if (xorsum >= (n - tol)) { a->cpd[q].inverted = 1; return 1; }
-    if (xorsum <= tol) { a->cpd[q].inverted = 0; return 1; }
+    if (xorsum >= (n - tol)) { a->cpd[q].inverted = 1; CV(c_p1_inv); return 1; }
+    if (xorsum <= tol) { a->cpd[q].inverted = 0; CV(c_p1_up); return 1; }
     xorsum = 0;
     for (int i = 0; i < n - 1; i++) { b2[i] = b2[i + 1]; xorsum += b2[i] ^ a->cpd[q].p2[i]; }
     xorsum += val ^ a->cpd[q].p2[n - 1];
     b2[n - 1] = val;
-    if (xorsum >= (n - tol)) { a->cpd[q].inverted = 1; return 1; }
-    if (xorsum <= tol) { a->cpd[q].inverted = 0; return 1; }
+    if (xorsum >= (n - tol)) { a->cpd[q].inverted = 1; CV(c_p2_inv); return 1; }
+    if (xorsum <= tol) { a->cpd[q].inverted = 0; CV(c_p2_up); return 1; }
+    CV(c_miss);
     return 0;
 }
 
@@ -448,14 +516,15 @@ static void c_frame_done(jo_aerol *a, long bitidx)
     }
     unsigned char *bits = (unsigned char *)calloc((size_t)nd + 3000, 1);
     int nb = jo_decode_continuous(a->codec, dep, nd, bits);
-    (void)nb; /* deconvol.resize(2714): drops the trailing dummy bits (or zero-extends a short first frame) */
+    if (nb < 2714) CV(c_first_short); else CV(c_full_frame);
+    /* deconvol.resize(2714): drops the trailing dummy bits (or zero-extends a short first frame) */
     for (int h = 0; h < 2714; h++)
     {
         int v = (h < nb) ? bits[h] : 0;
         a->dl2[a->dl2_ptr] = v;
         a->dl2_ptr++; a->dl2_ptr %= a->dl2_sz;
         v = a->dl2[a->dl2_ptr];
-        v ^= a->scr[a->scr_pos < 5000 ? a->scr_pos : 4999];
+        v ^= a->scr[CVIF(a->scr_pos < 5000, c_scr_ok, c_scr_clamp) ? a->scr_pos : 4999];
         a->scr_pos++;
         bits[h] = (unsigned char)v;
     }
@@ -475,9 +544,9 @@ static void c_frame_done(jo_aerol *a, long bitidx)
         {
             uint16_t crc_calc = crc16_bytes(info, 10);
             uint16_t crc_rec = (uint16_t)((info[11] << 8) | info[10]);
-            if (crc_calc == crc_rec) { if (a->datacdcountdown < 12) a->datacdcountdown += 2; }
-            else { if (a->datacdcountdown > 0) a->datacdcountdown -= 5; }
-            if (!a->datacd && a->datacdcountdown > 2) { a->datacd = 1; ev(a, bitidx, 0, 1); }
+            if (crc_calc == crc_rec) { if (CVIF(a->datacdcountdown < 12, c_ok_inc, c_ok_cap)) a->datacdcountdown += 2; }
+            else { if (CVIF(a->datacdcountdown > 0, c_bad_dec, c_bad_floor)) a->datacdcountdown -= 5; }
+            if (CVIF(!a->datacd && a->datacdcountdown > 2, c_dcd_rise, c_dcd_norise)) { a->datacd = 1; ev(a, bitidx, 0, 1); }
             int32_t row[16];
             row[0] = (int32_t)a->nframes; row[1] = kk++;
             for (int j = 0; j < 12; j++) row[2 + j] = info[j];
@@ -495,7 +564,7 @@ static void c_frame_done(jo_aerol *a, long bitidx)
     {
         ch |= bits[h] * 128;
         charptr++; charptr %= 8;
-        if (charptr == 0) { if (nv < 300) row[4 + nv++] = ch; ch = 0; }
+        if (charptr == 0) { if (CVIF(nv < 300, c_voice_ok, c_voice_over)) row[4 + nv++] = ch; ch = 0; }
         else ch >>= 1;
         bitsin++;
         if (bitsin == 96) { bitsin = 0; h += 13; }
@@ -518,18 +587,20 @@ static void c_write(jo_aerol *a, const int16_t *sb, long n)
         const int q = a->realimag ? 0 : 1; /* realimag != 0: preambledetectorreal */
         if (a->cntr > a->NumberOfBits - 112 || a->cntr <= 0)
         {
+            if (a->cntr <= 0) CV(c_det_le0); else CV(c_det_window);
             gotsync = cpd_update(a, q, bit);
-            if (!a->gotsync_last) { a->gotsync_last = gotsync; gotsync = 0; }
-            else a->gotsync_last = 0;
+            if (!a->gotsync_last) { a->gotsync_last = gotsync; if (gotsync) CV(gsl_first_hit); else CV(gsl_first_miss); gotsync = 0; }
+            else { a->gotsync_last = 0; if (gotsync) CV(gsl_second_hit); else CV(gsl_second_miss); }
         }
-        else { gotsync = 0; a->gotsync_last = 0; }
-        if (a->cpd[q].inverted)
+        else { gotsync = 0; a->gotsync_last = 0; CV(c_det_off); }
+        if (CVIF(a->cpd[q].inverted, inv_on, inv_off))
         {
             bit = 1 - bit;
-            if (soft_bit > 128) soft_bit = 255 - soft_bit;
-            else if (soft_bit < 128) soft_bit = 255 - soft_bit;
+            if (soft_bit > 128) { soft_bit = 255 - soft_bit; CV(inv_soft_gt); }
+            else if (soft_bit < 128) { soft_bit = 255 - soft_bit; CV(inv_soft_lt); }
+            else CV(inv_soft_128);
         }
-        if (gotsync)
+        if (CVIF(gotsync, c_sync, c_nosync))
         {
             a->cntr = -1; a->cindex = -1;
             a->ncdel = 0;
@@ -538,17 +609,17 @@ static void c_write(jo_aerol *a, const int16_t *sb, long n)
         }
         else
         {
-            if (a->cntr < 1000000000) a->cntr++;
-            if (a->cntr <= a->NumberOfBits - 1) { a->cindex++; a->block[a->cindex] = soft_bit; }
-            if (a->cindex == 255)
+            if (CVIF(a->cntr < 1000000000, c_cntr_inc, c_cntr_sat)) a->cntr++;
+            if (CVIF(a->cntr <= a->NumberOfBits - 1, c_store, c_nostore)) { a->cindex++; a->block[a->cindex] = soft_bit; }
+            if (CVIF(a->cindex == 255, c_blk_done, c_blk_fill))
             {
                 /* leaver.deinterleave_ba(block, 4) appended to deleaveredBlock :2306-2316 */
                 for (int j = 0; j < 4; j++)
                     for (int k = 0; k < 64; k++)
-                        if (a->ncdel < (int)sizeof(a->cdel)) a->cdel[a->ncdel++] = (unsigned char)a->block[a->depermute[k] * 4 + j];
+                        if (CVIF(a->ncdel < (int)sizeof(a->cdel), c_cdel_ok, c_cdel_over)) a->cdel[a->ncdel++] = (unsigned char)a->block[a->depermute[k] * 4 + j];
                 a->cindex = -1;
             }
-            if (a->cntr == a->NumberOfBits - 1) { c_frame_done(a, bitidx); a->cindex = -1; }
+            if (CVIF(a->cntr == a->NumberOfBits - 1, c_frame_end, c_not_frame_end)) { c_frame_done(a, bitidx); a->cindex = -1; }
         }
     }
     a->nbits_total += n;
@@ -563,8 +634,8 @@ void jo_aerol_write(jo_aerol *a, const int16_t *sb, long n)
         const long bitidx = a->nbits_total + i;
         int bit = (((unsigned char)sb[i]) >= 128) ? 1 : 0;
         unsigned short soft_bit = (unsigned short)sb[i];
-        if (sb[i] < 0) { a->muw = 0; continue; }
-        if (a->muw < 100000) a->muw++;
+        if (CVIF(sb[i] < 0, w_marker, w_softbit)) { a->muw = 0; continue; }
+        if (CVIF(a->muw < 100000, w_muw_inc, w_muw_sat)) a->muw++;
         int gotsync;
         if (a->useingOQPSK)
         {
@@ -572,38 +643,45 @@ void jo_aerol_write(jo_aerol *a, const int16_t *sb, long n)
             pdet_t *pd = a->realimag ? &a->pd_imag : &a->pd_real;
             if (a->cntr > a->NumberOfBits - 68 || a->cntr <= 0 || !a->datacd)
             {
+                if (a->cntr > a->NumberOfBits - 68) CV(oq_det_window); else if (a->cntr <= 0) CV(oq_det_le0); else CV(oq_det_nodcd);
                 gotsync = pdet_update_pi(pd, bit);
-                if (!a->gotsync_last) { a->gotsync_last = gotsync; gotsync = 0; }
-                else a->gotsync_last = 0;
+                if (!gotsync) CV(pi_miss); else if (pd->inverted) CV(pi_inv_hit); else CV(pi_up_hit);
+                if (!a->gotsync_last) { a->gotsync_last = gotsync; if (gotsync) CV(gsl_first_hit); else CV(gsl_first_miss); gotsync = 0; }
+                else { a->gotsync_last = 0; if (gotsync) CV(gsl_second_hit); else CV(gsl_second_miss); }
             }
-            else { gotsync = 0; a->gotsync_last = 0; }
+            else { gotsync = 0; a->gotsync_last = 0; CV(oq_det_off); }
             /* burst mode: the unique word has to come about 80 soft bits after the demodulator's start-of-burst marker :1192-1200 */
-            if (gotsync && a->burstmode && a->ifb == 10500 && abs(a->muw - 80) > 150) gotsync = 0;
-            if (pd->inverted)
+            if (gotsync && a->burstmode && a->ifb == 10500) { if (CVIF(abs(a->muw - 80) > 150, bm_refuse, bm_accept)) gotsync = 0; }
+            if (CVIF(pd->inverted, inv_on, inv_off))
             {
                 bit = 1 - bit;
-                if (soft_bit > 128) soft_bit = 255 - soft_bit;
-                else if (soft_bit < 128) soft_bit = 255 - soft_bit;
+                if (soft_bit > 128) { soft_bit = 255 - soft_bit; CV(inv_soft_gt); }
+                else if (soft_bit < 128) { soft_bit = 255 - soft_bit; CV(inv_soft_lt); }
+                else CV(inv_soft_128);
             }
         }
         else if (a->burstmode) /* 600/1200 bps bursts: phase-invariant detector, the word has to come within 250 soft bits of the marker :1235-1267 */
         {
             const int inverted = a->pd_msk.inverted;
             gotsync = pdet_update_pi(&a->pd_msk, bit);
-            if (a->muw > 250 && gotsync) { a->pd_msk.inverted = inverted; gotsync = 0; }
-            if (a->pd_msk.inverted)
+            if (!gotsync) CV(pi_miss); else if (a->pd_msk.inverted) CV(pi_inv_hit); else CV(pi_up_hit);
+            if (!gotsync) CV(mk_nosync);
+            else if (CVIF(a->muw > 250, mk_refuse, mk_accept)) { a->pd_msk.inverted = inverted; gotsync = 0; }
+            if (CVIF(a->pd_msk.inverted, inv_on, inv_off))
             {
                 bit = 1 - bit;
-                if (soft_bit > 128) soft_bit = 255 - soft_bit;
-                else if (soft_bit < 128) soft_bit = 255 - soft_bit;
+                if (soft_bit > 128) { soft_bit = 255 - soft_bit; CV(inv_soft_gt); }
+                else if (soft_bit < 128) { soft_bit = 255 - soft_bit; CV(inv_soft_lt); }
+                else CV(inv_soft_128);
             }
         }
-        else gotsync = pdet_update_exact(&a->pd_exact, bit);
+        else gotsync = CVIF(pdet_update_exact(&a->pd_exact, bit), px_hit, px_miss);
 
-        if (a->cntr < 1000000000) a->cntr++;
+        if (CVIF(a->cntr < 1000000000, cn_inc, cn_sat)) a->cntr++;
+        if (a->cntr >= 16) CV(hd_none);
         if (a->cntr < 16)
         {
-            if (a->cntr == 0)
+            if (CVIF(a->cntr == 0, hd_first, hd_shift))
             {
                 a->frameinfo = (uint16_t)bit; a->ninfo = 0;
                 if (a->burstmode) /* R and T channels have no header: a dummy one :1281-1294 */
@@ -615,7 +693,7 @@ void jo_aerol_write(jo_aerol *a, const int16_t *sb, long n)
             }
             else { a->frameinfo <<= 1; a->frameinfo |= (uint16_t)bit; }
         }
-        if (a->cntr == 15)
+        if (CVIF(a->cntr == 15, hd_done, hd_not_done))
         {
             uint16_t tval = a->frameinfo;
             a->frameinfo = a->lastframeinfo;
@@ -625,28 +703,29 @@ void jo_aerol_write(jo_aerol *a, const int16_t *sb, long n)
         }
         if (a->cntr >= 16 && a->burstmode)
         {
-            if ((a->useingOQPSK ? rt_update(a, soft_bit) : rt_update_msk(a, soft_bit)) == RT_BAD) ev(a, bitidx, 3, 0); /* :1531 " Bad R/T Packet" */
+            if (CVIF((a->useingOQPSK ? rt_update(a, soft_bit) : rt_update_msk(a, soft_bit)) == RT_BAD, br_bad_event, br_no_bad_event)) ev(a, bitidx, 3, 0); /* :1531 " Bad R/T Packet" */
         }
         else if (a->cntr >= 16)
         {
-            if (a->cntr == 16) a->blockcnt = -1;
+            if (CVIF(a->cntr == 16, bl_cntr16, bl_not_cntr16)) a->blockcnt = -1;
             int idx = (a->cntr - a->BitsInHeader) % a->blocksz;
-            if (idx < 0) idx = 0;
+            if (CVIF(idx < 0, bl_idx_neg, bl_idx_ok)) idx = 0;
             a->block[idx] = soft_bit;
-            if (idx == (a->blocksz - 1)) block_done(a, bitidx);
+            if (CVIF(idx == (a->blocksz - 1), bl_done, bl_fill)) { if (a->cntr >= 1000000000) CV(bl_done_sat); block_done(a, bitidx); }
         }
-        if (gotsync)
+        if (CVIF(gotsync, sy_sync, sy_nosync))
         {
-            if (!a->burstmode && a->cntr + 1 != a->TotalNumberOfBits) ev(a, bitidx, 1, a->cntr + 1); /* "Error short frame!!!" (isudata.reset()) */
+            if (!a->burstmode && CVIF(a->cntr + 1 != a->TotalNumberOfBits, sy_short, sy_exact_len)) ev(a, bitidx, 1, a->cntr + 1); /* "Error short frame!!!" (isudata.reset()) */
             a->cntr = -1;
             a->datacd = 1; a->datacdcountdown = 12;
             ev(a, bitidx, 0, 1);
             ev(a, bitidx, 2, 0);
             a->scr_pos = 0;
         }
-        if (a->cntr + 1 == a->TotalNumberOfBits)
+        if (CVIF(a->cntr + 1 == a->TotalNumberOfBits, wr_wrap, wr_nowrap))
         {
             a->scr_pos = 0; a->cntr = -1;
+            if (a->burstmode) CV(wr_end_of_signal);
             if (a->burstmode) /* end of signal :2018-2027: stop, carrier detect low, and the REST OF THIS GROUP of soft bits is dropped */
             {
                 a->cntr = 1000000000;

@@ -23,6 +23,12 @@ long jo_aerol_take_events(jo_aerol *a, int64_t *dst, long caprows);
 long jo_aerol_take_voice(jo_aerol *a, unsigned char *dst, long caprows);
 int jo_aerol_dcd(jo_aerol *a);
 int jo_aerol_tick_dcd(jo_aerol *a); /* AeroL::updateDCD, returns the data-carrier-detect flag afterwards */
+/* branch counters of this object (aerol_oracle.c: AEROL_COV_LIST): fills up to cap longs, returns how many counters there are;
+ * jo_aerol_coverage_name(k) is counter k's name (NULL past the end).  oracle.py: AeroL.coverage() */
+long jo_aerol_coverage(jo_aerol *a, long *dst, long cap);
+const char *jo_aerol_coverage_name(long k);
+/* read-only: cntr, datacd, datacdcountdown, realimag, gotsync_last, scr_pos, muw, rt_blockptr, rt_last, rt_targetBlocks, rt_targetSUSize, ncdel */
+void jo_aerol_peek(jo_aerol *a, long *dst12);
 #ifdef __cplusplus
 }
 #endif

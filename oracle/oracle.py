@@ -170,6 +170,12 @@ def lib():
         L.jo_aerol_dcd.argtypes = [C.c_void_p]
         L.jo_aerol_tick_dcd.argtypes = [C.c_void_p]
         L.jo_aerol_tick_dcd.restype = C.c_int
+        L.jo_aerol_coverage.restype = C.c_long
+        L.jo_aerol_coverage.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+        L.jo_aerol_coverage_name.restype = C.c_char_p
+        L.jo_aerol_coverage_name.argtypes = [C.c_long]
+        L.jo_aerol_peek.restype = None
+        L.jo_aerol_peek.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -748,6 +754,30 @@ class AeroL:
     def tick_dcd(self) -> int:
         """AeroL::updateDCD (the reference's 1 s timer)."""
         return self.L.jo_aerol_tick_dcd(self.h)
+
+    # jo_aerol_peek's order
+    PEEK = ("cntr", "datacd", "datacdcountdown", "realimag", "gotsync_last", "scr_pos", "muw", "rt_blockptr", "rt_last", "rt_targetBlocks",
+            "rt_targetSUSize", "ncdel")
+
+    @staticmethod
+    def coverage_names() -> tuple:
+        """the oracle's own name table (aerol_oracle.c: AEROL_COV_LIST)"""
+        L = lib()
+        n = L.jo_aerol_coverage(None, None, 0)
+        return tuple(L.jo_aerol_coverage_name(k).decode() for k in range(n))
+
+    def coverage(self) -> dict:
+        """{name: times that arm of a decision was taken by this object}"""
+        names = self.coverage_names()
+        out = np.zeros(len(names), dtype=np.int64)
+        assert self.L.jo_aerol_coverage(self.h, out.ctypes.data, len(names)) == len(names)
+        return {k: int(v) for k, v in zip(names, out)}
+
+    def peek(self) -> dict:
+        """read-only copy of the state that tells where a write boundary fell (PEEK)"""
+        out = np.zeros(len(self.PEEK), dtype=np.int64)
+        self.L.jo_aerol_peek(self.h, out.ctypes.data)
+        return {k: int(v) for k, v in zip(self.PEEK, out)}
 
 
 def run_aerol(fb: int, soft: np.ndarray, group: int = 32):

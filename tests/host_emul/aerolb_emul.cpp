@@ -9,6 +9,7 @@
 #define AEROLB_EMUL_COUNT
 static long long g_aerolb_fast_groups = 0, g_aerolb_fast_fill_groups = 0; // groups of eight entries k_aerolb_bits<true> took in one go (all / while collecting)
 #include "../../jaero_amd/csrc/k_aerol_burst.h"
+#include "../../jaero_amd/csrc/k_aerol_tick.h"
 
 extern "C" {
 #include "../../oracle/viterbi_oracle.h"
@@ -137,6 +138,14 @@ extern "C" int emulb_write(EmulB *e, const int16_t *soft, const int *counts, int
     }
     each_thread(g.nchp, [&] { k_aerol_end_write(g, p, counts); });
     return 0;
+}
+
+// = jaero_aerol_tick_dcd: k_aerol_tick_dcd for every channel; dcd_out [nchp] (optional) receives the flags
+extern "C" void emulb_tick(EmulB *e, int *dcd_out)
+{
+    const AGeom &g = e->g;
+    const APtrs &p = e->p;
+    each_thread(g.nchp, [&] { k_aerol_tick_dcd(g, p, dcd_out); });
 }
 
 // which 0: packet rows (16 x int32), 1: event rows (3 x int64); returns the number of rows copied

@@ -131,6 +131,7 @@ extern "C" void emul_write(Emul *e, const int16_t *soft, const int *counts, int 
     launch(g.nchp / 64, 64, [&] { k_aerolc_end_write(g, e->p, cnt.data()); });
 }
 extern "C" void emul_tick(Emul *e) { launch(e->g.nchp / 64, 64, [&] { k_aerolc_tick_dcd(e->g, e->p, nullptr); }); }
+extern "C" void emul_tick_out(Emul *e, int *dcd_out) { launch(e->g.nchp / 64, 64, [&] { k_aerolc_tick_dcd(e->g, e->p, dcd_out); }); } // dcd_out [nchp]
 // drain: returns the count and copies rows
 extern "C" int emul_read(Emul *e, int ch, int which, void *dst, int caprows)
 {

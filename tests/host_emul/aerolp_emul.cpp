@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../jaero_amd/csrc/k_aerol.h"
+#include "../../jaero_amd/csrc/k_aerol_tick.h"
 
 extern "C" {
 #include "../../oracle/viterbi_oracle.h"
@@ -115,6 +116,14 @@ extern "C" int emulp_write(EmulP *e, const int16_t *soft, const int *counts, int
     }
     each_thread(g.nchp, [&] { k_aerol_end_write(g, p, counts); });
     return 0;
+}
+
+// = jaero_aerol_tick_dcd: k_aerol_tick_dcd for every channel; dcd_out [nchp] (optional) receives the flags
+extern "C" void emulp_tick(EmulP *e, int *dcd_out)
+{
+    const AGeom &g = e->g;
+    const APtrs &p = e->p;
+    each_thread(g.nchp, [&] { k_aerol_tick_dcd(g, p, dcd_out); });
 }
 
 // which 0: signal-unit rows (16 x int32), 1: event rows (3 x int64); returns the number of rows copied
