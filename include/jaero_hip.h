@@ -280,23 +280,23 @@ int jaero_aerol_link_dcd(jaero_aerol_ctx *ctx, jaero_ctx *bank);
  * as jaero_aerol_read_* with enough capacity leaves it (count 0, overflow bit of that class cleared); a channel not taken is not touched.
  * If a taken channel had its overflow bit set, everything is filled in and the call returns JAERO_EOVERFLOW, overflowed[c] = 1 saying where.
  * The rows are bit for bit the per-channel readers'.  Checks, in this order, before a device is touched: `what` is none of the classes
- * (JAERO_AEROL_MESSAGES is one only on a bank that has called jaero_aerol_isu_enable: with a null ctx or a bank that never enabled it is
+ * (JAERO_AEROL_MESSAGES is one only on a bank that has enabled a reassembly, jaero_aerol_isu_enable or jaero_aerol_rt_enable: with a null ctx or a bank that never enabled it is
  * refused here, as every value above JAERO_AEROL_VOICE was before that class existed), caprows < 0, null offsets / nchannels_taken, null rows with caprows > 0, null ctx (JAERO_EINVAL); then a class the bank's mode does not have gets
  * the per-channel reader's own error (SUS on a burst bank, PACKETS on any other: JAERO_ENOTSUP; VOICE on a bank that is not fb = 8400:
  * JAERO_EINVAL).  Synchronises the handle's last stream (twice).
  * jaero_aerol_profile2_read: as jaero_aerol_profile_read with which 0 .. 5; 3 = the kernels of jaero_aerol_read_all, 4 = the link kernel,
- * 5 = the reassembly kernel (jaero_aerol_isu_enable).
+ * 5 = the reassembly kernel (jaero_aerol_isu_enable; on a burst bank jaero_aerol_rt_enable's).
  * jaero_read_all (below) is the same call for the demodulator bank's soft bits and logs: this paragraph defines both.
  * Deliberately not here: rows handed over in device memory. */
 #define JAERO_AEROL_SUS 0      /* P and C banks: rows of 16 int32, as jaero_aerol_read_sus        */
 #define JAERO_AEROL_PACKETS 1  /* burst banks:   rows of 16 int32, as jaero_aerol_read_packets    */
 #define JAERO_AEROL_EVENTS 2   /* every bank:    rows of 3 int64,  as jaero_aerol_read_events     */
 #define JAERO_AEROL_VOICE 3    /* C banks:       rows of 304 bytes, as jaero_aerol_read_voice     */
-#define JAERO_AEROL_MESSAGES 4 /* P banks that enabled the reassembly: rows of jaero_aerol_msg, as jaero_aerol_read_msgs; any other: JAERO_EINVAL */
+#define JAERO_AEROL_MESSAGES 4 /* P and burst banks that enabled their reassembly: rows of jaero_aerol_msg, as jaero_aerol_read_msgs; any other: JAERO_EINVAL */
 int jaero_aerol_read_all(jaero_aerol_ctx *ctx, int what, void *rows, int caprows, int *offsets /* [nchannels + 1] */, int *nchannels_taken,
                          long long *rows_pending /* optional */, unsigned char *overflowed /* optional [nchannels] */);
 int jaero_aerol_profile2_read(jaero_aerol_ctx *ctx, int which, double *total_ms, int *launches, int reset);
-/* test hook: bytes of device memory the link, jaero_aerol_read_all and jaero_aerol_isu_enable have allocated for this bank so far (0 for a bank
+/* test hook: bytes of device memory the link, jaero_aerol_read_all, jaero_aerol_isu_enable and jaero_aerol_rt_enable have allocated for this bank so far (0 for a bank
  * that used none of them) */
 long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *ctx);
 
@@ -331,25 +331,70 @@ long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *ctx);
  * jaero_aerol_isu_enable(ctx, msg_capacity): msg_capacity >= 1 enables with a log of that many rows per channel -- synchronises, allocates on
  * first use (about 6 KB per channel besides the log), clears the list, `a`, the log and the counters; 0 disables: later writes launch nothing
  * extra, the log stays readable.  Checks, in this order, before a device is touched: null ctx, msg_capacity < 0 (JAERO_EINVAL); a burst bank,
- * fb = 8400 (JAERO_ENOTSUP: DecodeC never calls ISUData; the R / T path -- RISUData and the T packets' units, aerol.cpp:1395,1504-1513 -- is
- * deliberately not here).  An Aero-L bank has no poisoned state.
+ * fb = 8400 (JAERO_ENOTSUP: DecodeC never calls ISUData; a burst bank's reassembly -- RISUData and the T packets' units, aerol.cpp:1395,1504-1513 --
+ * is jaero_aerol_rt_enable, below).  An Aero-L bank has no poisoned state.
  * jaero_aerol_read_msgs: the per-channel reader, with jaero_aerol_read_sus's semantics (overflow bit 8 of the channel: messages completed while
  * the log was full were dropped; JAERO_EINVAL on a bank that never enabled).  JAERO_AEROL_MESSAGES of jaero_aerol_read_all: every channel's.
  * jaero_aerol_isu_stats: per channel four counters since enable -- ISU updates, SSU updates, missing SSUs, completed messages -- counted
  * whether or not the log had room.  Null ctx / stats, a bank that never enabled: JAERO_EINVAL. */
 typedef struct jaero_aerol_msg
 {
-    int32_t frame, k;      /* as the signal-unit rows' frame number and unit index: the unit that completed the message */
+    int32_t frame, k;      /* as the signal-unit rows' frame number and unit index: the unit that completed the message (burst banks: the packet
+                              number, and the unit's index inside the T packet; 0 for an R packet) */
     uint32_t aesid;
     uint8_t gesid, qno, refno, nooct;
-    uint16_t nbytes;       /* 2 .. 506 */
-    uint16_t flags;
+    uint16_t nbytes;       /* 2 .. 506; rows of an R channel (flags bit 5): 0 .. 33 */
+    uint16_t flags;        /* bits 0-4 as above; burst banks add bit 5 (32) = from RISUData, bit 6 (64) = an R signalling-information unit */
     uint8_t mode, tak, label[2], bi, pad[7];
     uint8_t data[512];     /* the raw user data, zero padded */
 } jaero_aerol_msg;         /* 544 bytes */
 int jaero_aerol_isu_enable(jaero_aerol_ctx *ctx, int msg_capacity);
 int jaero_aerol_read_msgs(jaero_aerol_ctx *ctx, int channel, void *rows /* jaero_aerol_msg[caprows] */, int caprows, int *nrows);
 int jaero_aerol_isu_stats(jaero_aerol_ctx *ctx, long long *stats /* [nchannels][4] */);
+
+/* ---- R / T user data of a burst bank, reassembled on the device (RISUData::update JAERO/aerol.cpp:6-113, aerol.h:135-146,231-243; ISUData::update
+ * behind the T packets' units, aerol.cpp:1488-1516; ParserISU::parse with downlink = burstmode, aerol.cpp:1397,1510) ----
+ * Off by default: a burst bank that never calls jaero_aerol_rt_enable allocates and launches what it did without it.  Burst banks at 600 / 1200 /
+ * 10500 bps.  While enabled, each channel keeps one ISUData and one RISUData, independent of each other, updated in stream order with every
+ * packet the search accepts, whether or not the packet log had room for its rows.  There is no short-frame reset in burst mode (aerol.cpp:1993
+ * guards it with !burstmode): the only reset is at enable.  The definition, with the reference's quirks (tests/rt_isu_oracle.py restates it):
+ *   T packet (type 2, info bytes f[0 ..)): every unit k < numberofsus goes to ISUData::update as defined above, in packet order, with
+ *     d = f[6 + 12 k .. 6 + 12 k + 9].  numberofsus = 1 + (blockptr - 320) / 192 at 10500 bps (C division: 0 for the two-column block), where
+ *     every unit is CRC-clean by the packet test; = targetSUSize at 600 / 1200 bps, where AeroL makes no CRC test of its own: a unit whose CRC fails
+ *     is fed all the same (aerol.h:732-766 counts, never rejects), and the block holds targetSUSize + 1 units, so the last unit sent is never looked at.
+ *   R packet (type 1, 17 info bytes d[0..16]): only with d[1] & 0x08 is it user data and goes to RISUData::update; any other R packet changes nothing.
+ *     (1) Ageing, on every update: count++ on every item, then every item with count > 10 is removed, in list order; so the list holds at most 11
+ *         items and the survivors' counts are distinct.
+ *     (2) The scratch item is cleared, then SEQINDICATOR = d[0] >> 4, SUTYPE = d[0] & 15, QNO = d[1] >> 4, REFNO = d[1] & 7,
+ *         AESID = d[2..4] big-endian, GESID = d[5].
+ *     (3) The first item with equal (GESID, AESID, QNO, REFNO) is looked for -- none is found if SUTYPE is 0 or above 11, so such a unit appends
+ *         a fresh item (empty user data, filledarray 0) every time, as does a unit whose key is not in the list.  The item's count becomes 0.
+ *     (4) SEQINDICATOR 1 -> (total, index) = (1, 0); 2, 3 -> (2, 0), (2, 1); 4, 5, 6 -> (3, 0), (3, 1), (3, 2); anything else (0, 0): total 0 never
+ *         completes.  bytes = SUTYPE for SUTYPE 1 .. 11, else 0.  thisnum = 11 total - 11 + bytes.
+ *     (5) When thisnum > 0: empty user data is sized to thisnum; user data longer than thisnum is cut to it; shorter user data is not grown by this step.
+ *     (6) SUTYPE 15 (a signalling-information unit): the user data is cleared.  Any other SUTYPE: d[6 .. 6 + bytes) is written at 11 index, then
+ *         filledarray |= 1 << index.
+ *     (7) Complete: SUTYPE 15, or (filledarray, total) in {(7, 3), (3, 2), (1, 1)}.  A completed item is copied out and REMOVED from the list (ISUData
+ *         keeps its item).
+ *     Two corners the reference leaves to chance are decided here: a write past the user data's end grows it to reach (Qt's QByteRef::operator= ->
+ *     expand, qbytearray.h:528-530; followed); and the bytes a resize or expand adds that no unit has written are indeterminate in the reference:
+ *     they are 0 here.
+ *   Emission: one jaero_aerol_msg per completed item, classified exactly as above (flags bits 0-4).  frame = the packet's number (row[0] of its rows
+ *     in jaero_aerol_read_packets), k = the index of the T packet's unit that completed the message, 0 for an R packet.  Two origin bits are set
+ *     whatever the classification says: bit 5 (32) the row comes from RISUData; bit 6 (64) it is an R signalling-information unit (nbytes 0).  R rows:
+ *     qno = d[1] >> 4, refno = d[1] & 7, nooct = 0, nbytes 0 .. 33.
+ * jaero_aerol_rt_enable(ctx, msg_capacity): msg_capacity >= 1 enables with a log of that many rows per channel -- synchronises, allocates on first
+ * use (about 6.6 KB per channel besides the log), clears both lists, both scratch items, the log, its overflow bit and the counters; 0 disables:
+ * later writes launch nothing extra, the log stays readable.  Checks, in this order, before a device is touched: null ctx, msg_capacity < 0
+ * (JAERO_EINVAL); a bank that is not a burst bank -- a P bank, fb = 8400 -- (JAERO_ENOTSUP).  jaero_aerol_isu_enable on a burst bank stays
+ * JAERO_ENOTSUP and jaero_aerol_isu_stats on one JAERO_EINVAL.
+ * The readers are jaero_aerol_read_msgs and JAERO_AEROL_MESSAGES of jaero_aerol_read_all, as on a P bank (overflow bit 8; JAERO_EINVAL on a bank
+ * that never enabled).
+ * jaero_aerol_rt_stats: per channel eight counters since enable, counted whether or not a log had room -- T path: ISU updates, SSU updates, missing
+ * SSUs, completed messages; R path: user-data packets fed, items newly appended, completed messages (signalling-information units among them),
+ * signalling-information units.  Null ctx / stats, a bank that never enabled: JAERO_EINVAL. */
+int jaero_aerol_rt_enable(jaero_aerol_ctx *ctx, int msg_capacity);
+int jaero_aerol_rt_stats(jaero_aerol_ctx *ctx, long long *stats /* [nchannels][8] */);
 
 /* ---- one-call reads of every channel of a demodulator bank ----
  * jaero_read_all is jaero_aerol_read_all (above: the prefix rule P_c <= caprows, offsets, *nchannels_taken, *rows_pending, the caprows = 0 sizing

@@ -2,6 +2,8 @@
 
   * generators, the inverse of what the reference decodes: isu_payloads (an ISU 0x71 and its SSUs, JAERO/aerol.cpp:152-219) and
     acars_userdata (the byte pattern ParserISU::parse looks for, aerol.cpp:365-396)
+  * r_isu_payloads (the one to three R packets RISUData::update puts back together, aerol.cpp:28-113) and t_packets (10-byte units as T packet
+    payloads) for the burst bank's reassembly (AeroLBank.rt_enable)
   * parse_msg: a log row -> the ACARSItem fields ParserISU::parse fills in (aerol.cpp:340-480), text included
   * AcarsDefragmenter: ACARSDefragmenter (aerol.cpp:221-329) restated, one per channel
 
@@ -17,8 +19,11 @@ MSG_DTYPE = np.dtype([("frame", "<i4"), ("k", "<i4"), ("aesid", "<u4"), ("gesid"
                       ("nbytes", "<u2"), ("flags", "<u2"), ("mode", "u1"), ("tak", "u1"), ("label", "u1", (2,)), ("bi", "u1"),
                       ("pad", "u1", (7,)), ("data", "u1", (512,))])  # struct jaero_aerol_msg
 MSG_AES0, MSG_ACARS, MSG_TEXT, MSG_MORE, MSG_PARITY = 1, 2, 4, 8, 16  # jaero_aerol_msg.flags
+MSG_RCHAN, MSG_RSIGNAL = 32, 64  # burst banks: the row comes from an R packet (RISUData); it is an R signalling-information unit
 SOH, STX, ETX, ETB, DEL = 0x01, 0x02, 0x03, 0x17, 0x7F
 MAX_USERDATA = 506  # 2 bytes in the ISU, 8 in each of at most 62 SSUs, at most 8 in the last
+MAX_R_USERDATA = 33  # three R packets of 11 bytes
+FILL_IN = bytes([0x01] + [0] * 9)
 
 
 def odd_parity(b: int) -> int:
@@ -43,6 +48,45 @@ def isu_payloads(aesid: int, gesid: int, qno: int, refno: int, userdata: bytes) 
     for i in range(nssu):
         chunk = rest[8 * i:8 * i + 8]
         out.append(bytes([0xC0 | (nssu - 1 - i), (qno << 4) | refno]) + chunk + bytes(8 - len(chunk)))
+    return out
+
+
+def r_isu_payloads(aesid: int, gesid: int, qno: int, refno: int, userdata: bytes) -> List[bytes]:
+    """The one to three 17-byte R packet payloads that carry `userdata` (1 .. 33 bytes): byte 0 = SEQINDICATOR << 4 | SUTYPE (1 of 1; 2, 3 of
+    two; 4, 5, 6 of three; SUTYPE = the bytes this unit holds, 1 .. 11), byte 1 = QNO << 4 | 8 | REFNO (three bits: bit 3 marks user data),
+    AESID, GESID, then eleven data bytes, zero padded."""
+    u = bytes(userdata)
+    if not 1 <= len(u) <= MAX_R_USERDATA:
+        raise ValueError(f"user data of {len(u)} bytes: R packets carry 1 .. {MAX_R_USERDATA}")
+    if not (0 <= aesid < 1 << 24 and 0 <= gesid < 256 and 0 <= qno < 16 and 0 <= refno < 8):
+        raise ValueError("aesid / gesid / qno / refno out of range (an R packet has three bits of REFNO)")
+    n = (len(u) + 10) // 11
+    first = {1: 1, 2: 2, 3: 4}[n]
+    out = []
+    for i in range(n):
+        chunk = u[11 * i:11 * i + 11]
+        out.append(bytes([((first + i) << 4) | len(chunk), (qno << 4) | 8 | refno, (aesid >> 16) & 255, (aesid >> 8) & 255, aesid & 255, gesid])
+                   + chunk + bytes(11 - len(chunk)))
+    return out
+
+
+def t_packets(aesid: int, gesid: int, units, per_packet: int, msk: bool = False):
+    """T packet payloads (4-byte header, [10-byte units]) for aerol_frames.rt_packet_bits, `per_packet` of `units` in each.  A 10 500 bps packet
+    has at least two units: fill-in units make up the number.  msk = True, for aerol_frames.rt_packet_bits_msk (600 / 1200 bps): the unit at
+    index 1 is a fill-in unit whose first byte the generator overwrites with the count, another closes the packet (the reference never looks at
+    the last unit sent), and at least four are sent."""
+    if per_packet < 1 or any(len(x) != 10 for x in units):
+        raise ValueError("per_packet >= 1 and 10-byte units")
+    hdr = bytes([(aesid >> 16) & 255, (aesid >> 8) & 255, aesid & 255, gesid])
+    out = []
+    for s in range(0, len(units), per_packet):
+        us = [bytes(x) for x in units[s:s + per_packet]]
+        if msk:
+            us = us[:1] + [FILL_IN] + us[1:]
+            us += [FILL_IN] * max(1, 4 - len(us))
+        else:
+            us += [FILL_IN] * max(0, 2 - len(us))
+        out.append((hdr, us))
     return out
 
 
@@ -103,14 +147,15 @@ class AcarsItem:
     dblookupresult: list = field(default_factory=list)
 
 
-def parse_msg(row) -> AcarsItem:
-    """One jaero_aerol_msg row (numpy record of MSG_DTYPE) -> what ParserISU::parse makes of it.  The header fields and the three decisions
+def parse_msg(row, downlink: bool = False) -> AcarsItem:
+    """One jaero_aerol_msg row (numpy record of MSG_DTYPE) -> what ParserISU::parse makes of it.  downlink: the row is a burst bank's (R and T
+    channels are the aircraft's side; a row that says it comes from an R packet is one anyway).  The header fields and the three decisions
     (AESID 0, ACARS or not, parity) are the row's, made on the device; the text is formed here: seven bits per byte, 0x7F as "<DEL>", and
     for anything that is not ACARS the upper-case hex of the user data."""
     n, flags = int(row["nbytes"]), int(row["flags"])
     u = bytes(row["data"][:n].tobytes())
     it = AcarsItem(aesid=int(row["aesid"]), gesid=int(row["gesid"]), qno=int(row["qno"]), refno=int(row["refno"]), frame=int(row["frame"]),
-                   k=int(row["k"]), userdata=u)
+                   k=int(row["k"]), userdata=u, downlink=bool(downlink or flags & MSG_RCHAN))
     if flags & MSG_AES0:
         it.error = "Error: AESID == 0"
         return it

@@ -47,7 +47,7 @@ EXPORTS = [
     "jaero_aerol_create", "jaero_aerol_create_burst", "jaero_aerol_read_packets", "jaero_aerol_destroy", "jaero_aerol_write", "jaero_aerol_read_sus", "jaero_aerol_read_events",
     "jaero_aerol_tick_dcd", "jaero_aerol_profile_enable", "jaero_aerol_profile_read", "jaero_aerol_read_voice",
     "jaero_aerol_link_dcd", "jaero_aerol_read_all", "jaero_aerol_profile2_read", "jaero_aerol_debug_extra_bytes",
-    "jaero_aerol_isu_enable", "jaero_aerol_read_msgs", "jaero_aerol_isu_stats",
+    "jaero_aerol_isu_enable", "jaero_aerol_read_msgs", "jaero_aerol_isu_stats", "jaero_aerol_rt_enable", "jaero_aerol_rt_stats",
     "jaero_read_all", "jaero_read_status_all", "jaero_profile2_read", "jaero_debug_read_all_bytes", "jaero_debug_softbit_counts",
     "jaero_ingest_create", "jaero_ingest_destroy", "jaero_ingest_push", "jaero_ingest_queued", "jaero_ingest_pump",
     "jaero_ingest_stats",
@@ -311,6 +311,8 @@ def lib():
     L.jaero_aerol_isu_enable.argtypes = [vp, ip]
     L.jaero_aerol_read_msgs.argtypes = [vp, ip, vp, ip, C.POINTER(ip)]
     L.jaero_aerol_isu_stats.argtypes = [vp, vp]
+    L.jaero_aerol_rt_enable.argtypes = [vp, ip]
+    L.jaero_aerol_rt_stats.argtypes = [vp, vp]
     L.jaero_read_all.argtypes = [vp, ip, vp, ip, vp, C.POINTER(ip), C.POINTER(C.c_longlong), vp]
     L.jaero_read_status_all.argtypes = [vp, vp]
     L.jaero_profile2_read.argtypes = [vp, ip, C.POINTER(dp), C.POINTER(ip), ip]

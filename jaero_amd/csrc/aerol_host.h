@@ -4,6 +4,7 @@
 #include <mutex>
 #include "aerolc.h"
 #include "k_aerol_isu.h"
+#include "k_aerolb_isu.h"
 #include "sweep_host.h"
 
 struct jaero_aerol_ctx : DevHandle // (never poisoned, and ordered by its caller: a write moves last_stream without an event)
@@ -17,7 +18,7 @@ struct jaero_aerol_ctx : DevHandle // (never poisoned, and ordered by its caller
     int16_t *d_soft = nullptr; int *d_counts = nullptr; int stage_stride = 0;
     unsigned long long *d_vhist = nullptr; // k_viterbi_lanes history scratch (large banks only)
     // the three kernel classes of a write: 0 = the bit walk, 1 = k_viterbi + overlap update, 2 = the end of a block / frame; 3 = the sweep's kernels
-    // (jaero_aerol_read_all), 4 = k_dcd_link, 5 = k_aerol_isu (jaero_aerol_profile2_read)
+    // (jaero_aerol_read_all), 4 = k_dcd_link, 5 = k_aerol_isu / k_aerolb_isu (jaero_aerol_profile2_read)
     KernelTimer timer{6};
     SweepBufs sweep;
     jaero_ctx *link = nullptr; // the demodulator bank whose dcd follows this bank's DataCarrierDetect emissions (jaero_aerol_link_dcd)
@@ -27,6 +28,11 @@ struct jaero_aerol_ctx : DevHandle // (never poisoned, and ordered by its caller
     int *d_isumark = nullptr;
     bool isu_on = false;
     long long isu_bytes = 0;
+    // R / T user data of a burst bank (jaero_aerol_rt_enable, k_aerolb_isu.h): the T path's list and the message log are isu's, the rest is here
+    RPtrs rt{};
+    long long *d_rtmark = nullptr;
+    bool rt_on = false;
+    long long rt_bytes = 0;
 };
 
 extern "C" int jaero_aerol_profile_enable(jaero_aerol_ctx *c, int on)
@@ -374,6 +380,12 @@ extern "C" int jaero_aerol_write(jaero_aerol_ctx *c, const int16_t *soft, const 
             pi = c->timer.begin(2, st);
             hipLaunchKernelGGL(k_aerolb_post, grid, block, 0, st, g, c->p);
             c->timer.end(pi, st);
+            if (c->rt_on)
+            {
+                pi = c->timer.begin(5, st);
+                hipLaunchKernelGGL(k_aerolb_isu, grid, block, 0, st, g, c->p, c->isu, c->rt);
+                c->timer.end(pi, st);
+            }
         }
         hipLaunchKernelGGL(k_aerol_end_write, grid, block, 0, st, g, c->p, dcounts);
         HIPCHK(hipGetLastError());
@@ -455,13 +467,31 @@ extern "C" int jaero_aerol_read_voice(jaero_aerol_ctx *c, int ch, uint8_t *rows,
 }
 // ------------------------------------------------------------------------------------------ ISU / SSU reassembly (k_aerol_isu.h)
 static_assert(sizeof(jaero_aerol_msg) == ISU_ROW_BYTES && ISU_ROW_BYTES % 16 == 0, "a message row is what isu_emit writes and k_sweep_gather<16> moves");
+// The message log of `msg_capacity` rows per channel, shared by both reassemblies (a bank has one of them): kept if it has that capacity, else
+// allocated anew; `bytes` follows what is held.
+static int aerol_msg_log(jaero_aerol_ctx *c, int msg_capacity, long long &bytes)
+{
+    const size_t nchp = c->g.nchp;
+    if (c->isu.log && c->isu.msg_cap == msg_capacity) return 0;
+    if (c->isu.log)
+    {
+        for (size_t k = 0; k < c->mem.ptrs.size(); k++) if (c->mem.ptrs[k] == (void *)c->isu.log) { c->mem.ptrs.erase(c->mem.ptrs.begin() + k); break; }
+        hipFree(c->isu.log);
+        bytes -= (long long)nchp * c->isu.msg_cap * ISU_ROW_BYTES;
+        c->isu.log = nullptr; c->isu.msg_cap = 0;
+    }
+    if (const int rc = dalloc(c->mem, &c->isu.log, nchp * msg_capacity * ISU_ROW_BYTES, false)) return rc;
+    c->isu.msg_cap = msg_capacity;
+    bytes += (long long)nchp * msg_capacity * ISU_ROW_BYTES;
+    return 0;
+}
 // Checks in the header's order, all before a device is touched.
 extern "C" int jaero_aerol_isu_enable(jaero_aerol_ctx *c, int msg_capacity)
 {
     const char *who = "jaero_aerol_isu_enable";
     if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
     if (msg_capacity < 0) return fail(JAERO_EINVAL, "%s: msg_capacity < 0", who);
-    if (c->g.burst) return fail(JAERO_ENOTSUP, "%s: burst-mode bank (the R / T channel reassembly, RISUData and the T packets' units, is not on the device)", who);
+    if (c->g.burst) return fail(JAERO_ENOTSUP, "%s: burst-mode bank (the R / T channel reassembly, RISUData and the T packets' units, is jaero_aerol_rt_enable)", who);
     if (c->cchan) return fail(JAERO_ENOTSUP, "%s: fb = 8400 (AeroL::DecodeC never calls ISUData)", who);
     QUIESCE(c);
     if (msg_capacity == 0)
@@ -481,19 +511,7 @@ extern "C" int jaero_aerol_isu_enable(jaero_aerol_ctx *c, int msg_capacity)
         DA(c->mem, c->isu.stats, (size_t)g.nchp * 4);
         c->isu_bytes = (long long)g.nchp * (2 * sizeof(int) + 4 * ISU_CHAN_WORDS + ISU_MAX_ITEMS * ISU_ITEM_BYTES + 4 * sizeof(long long));
     }
-    if (!c->isu.log || c->isu.msg_cap != msg_capacity)
-    {
-        if (c->isu.log)
-        {
-            for (size_t k = 0; k < c->mem.ptrs.size(); k++) if (c->mem.ptrs[k] == (void *)c->isu.log) { c->mem.ptrs.erase(c->mem.ptrs.begin() + k); break; }
-            hipFree(c->isu.log);
-            c->isu_bytes -= (long long)g.nchp * c->isu.msg_cap * ISU_ROW_BYTES;
-            c->isu.log = nullptr; c->isu.msg_cap = 0;
-        }
-        if ((rc = dalloc(c->mem, &c->isu.log, (size_t)g.nchp * msg_capacity * ISU_ROW_BYTES, false))) { c->isu_on = false; c->p.isumark = nullptr; return rc; }
-        c->isu.msg_cap = msg_capacity;
-        c->isu_bytes += (long long)g.nchp * msg_capacity * ISU_ROW_BYTES;
-    }
+    if ((rc = aerol_msg_log(c, msg_capacity, c->isu_bytes))) { c->isu_on = false; c->p.isumark = nullptr; return rc; }
     // an empty list, an empty log, counters at 0 and `a` zeroed; the messages' overflow bit cleared
     HIPCHK(hipMemset(c->d_isumark, 0, sizeof(int) * (size_t)g.nchp));
     HIPCHK(hipMemset(c->isu.chan, 0, sizeof(uint32_t) * (size_t)g.nchp * ISU_CHAN_WORDS));
@@ -523,13 +541,69 @@ extern "C" int jaero_aerol_isu_stats(jaero_aerol_ctx *c, long long *stats)
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ R / T user data of a burst bank (k_aerolb_isu.h)
+// an allocation of jaero_aerol_rt_enable: its size is counted where it is made (jaero_aerol_debug_extra_bytes)
+template <class T>
+static int rt_alloc(jaero_aerol_ctx *c, T *&ptr, size_t count)
+{
+    if (ptr) return 0; // the first enable's
+    if (const int rc = dalloc(c->mem, &ptr, count)) return rc;
+    c->rt_bytes += (long long)(count * sizeof(T));
+    return 0;
+}
+// Checks in the header's order, all before a device is touched.
+extern "C" int jaero_aerol_rt_enable(jaero_aerol_ctx *c, int msg_capacity)
+{
+    const char *who = "jaero_aerol_rt_enable";
+    if (!c) return fail(JAERO_EINVAL, "%s: null ctx", who);
+    if (msg_capacity < 0) return fail(JAERO_EINVAL, "%s: msg_capacity < 0", who);
+    if (c->cchan || !c->g.burst) return fail(JAERO_ENOTSUP, "%s: not a burst-mode bank (a continuous P-channel bank has jaero_aerol_isu_enable)", who);
+    QUIESCE(c);
+    if (msg_capacity == 0)
+    {
+        c->rt_on = false;
+        c->p.rtmark = nullptr; // the log, its counts and the counters stay where they are
+        return 0;
+    }
+    const AGeom &g = c->g;
+    const size_t nchp = g.nchp;
+    int rc;
+    if ((rc = rt_alloc(c, c->d_rtmark, nchp)) || (rc = rt_alloc(c, c->isu.chan, nchp * ISU_CHAN_WORDS)) ||
+        (rc = rt_alloc(c, c->isu.items, nchp * ISU_MAX_ITEMS * ISU_ITEM_BYTES)) || (rc = rt_alloc(c, c->isu.msg_cnt, nchp)) ||
+        (rc = rt_alloc(c, c->rt.chan, nchp * RISU_CHAN_WORDS)) || (rc = rt_alloc(c, c->rt.items, nchp * ISU_MAX_ITEMS * RISU_SLOT_BYTES)) ||
+        (rc = rt_alloc(c, c->rt.stats, nchp * RT_NSTATS)))
+        return rc;
+    if ((rc = aerol_msg_log(c, msg_capacity, c->rt_bytes))) { c->rt_on = false; c->p.rtmark = nullptr; return rc; }
+    // both lists empty, both scratch items zeroed, an empty log, counters at 0; the messages' overflow bit cleared
+    HIPCHK(hipMemset(c->d_rtmark, 0, sizeof(long long) * nchp));
+    HIPCHK(hipMemset(c->isu.chan, 0, sizeof(uint32_t) * nchp * ISU_CHAN_WORDS));
+    HIPCHK(hipMemset(c->rt.chan, 0, sizeof(uint32_t) * nchp * RISU_CHAN_WORDS));
+    HIPCHK(hipMemset(c->isu.msg_cnt, 0, sizeof(int) * nchp));
+    HIPCHK(hipMemset(c->rt.stats, 0, sizeof(long long) * nchp * RT_NSTATS));
+    hipLaunchKernelGGL(k_aerol_isu_clear_overflow, dim3(g.nchp / 64), dim3(64), 0, c->last_stream, g, c->p);
+    HIPCHK(hipGetLastError());
+    QUIESCE(c);
+    c->p.rtmark = c->d_rtmark;
+    c->rt_on = true;
+    return 0;
+}
+extern "C" int jaero_aerol_rt_stats(jaero_aerol_ctx *c, long long *stats)
+{
+    const char *who = "jaero_aerol_rt_stats";
+    if (!c || !stats) return fail(JAERO_EINVAL, "%s: null ctx / stats", who);
+    if (!c->rt.stats) return fail(JAERO_EINVAL, "%s: this bank never enabled the reassembly (jaero_aerol_rt_enable)", who);
+    QUIESCE(c);
+    HIPCHK(hipMemcpy(stats, c->rt.stats, sizeof(long long) * (size_t)c->g.nch * RT_NSTATS, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ jaero_aerol_read_all
 // test hook: bytes of device memory the link, the sweep and the reassembly have allocated for this bank so far (0 for a bank that used none)
 extern "C" long long jaero_aerol_debug_extra_bytes(const jaero_aerol_ctx *c)
 {
     if (!c) return -1;
     long long n = c->d_dcdmark ? (long long)sizeof(int) * c->g.nchp : 0;
-    return n + c->sweep.bytes() + c->isu_bytes;
+    return n + c->sweep.bytes() + c->isu_bytes + c->rt_bytes;
 }
 extern "C" int jaero_aerol_read_all(jaero_aerol_ctx *c, int what, void *rows, int caprows, int *offsets, int *nchannels_taken, long long *rows_pending,
                                     unsigned char *overflowed)
@@ -538,7 +612,7 @@ extern "C" int jaero_aerol_read_all(jaero_aerol_ctx *c, int what, void *rows, in
     // (the message log is a class only of a bank that enabled the reassembly: with no such bank behind it, 4 is as unknown as it was before the class existed)
     if (what < JAERO_AEROL_SUS || what > JAERO_AEROL_MESSAGES || (what == JAERO_AEROL_MESSAGES && !(c && c->isu.log)))
         return fail(JAERO_EINVAL, "%s: what = %d is none of JAERO_AEROL_SUS / PACKETS / EVENTS / VOICE%s", who, what,
-                    what == JAERO_AEROL_MESSAGES ? " (JAERO_AEROL_MESSAGES exists on a bank that has called jaero_aerol_isu_enable)" : " / MESSAGES");
+                    what == JAERO_AEROL_MESSAGES ? " (JAERO_AEROL_MESSAGES exists on a bank that has called jaero_aerol_isu_enable or jaero_aerol_rt_enable)" : " / MESSAGES");
     if (caprows < 0) return fail(JAERO_EINVAL, "%s: caprows < 0", who);
     if (!offsets || !nchannels_taken) return fail(JAERO_EINVAL, "%s: null offsets / nchannels_taken", who);
     if (!rows && caprows > 0) return fail(JAERO_EINVAL, "%s: null rows with caprows > 0", who);

@@ -45,6 +45,8 @@ struct APtrs
     unsigned *dl2w;      // [nchp][dl2_words] the delay line as a bit ring (large banks: k_aerol_post_packed)
     int *dcdmark = nullptr; // [nchp] linked banks only (jaero_aerol_link_dcd): 2 | value of the last DataCarrierDetect emission, 0 = none
     int *isumark = nullptr; // [nchp] banks that reassemble user data only (jaero_aerol_isu_enable): 1 = a short-frame notice since k_aerol_isu last ran
+    long long *rtmark = nullptr; // [nchp] burst banks that reassemble user data only (jaero_aerol_rt_enable): the packet k_aerolb_post accepted in this round,
+                                 // packet number << 16 | info bytes << 2 | type (1 R, 2 T); 0 = none (k_aerolb_isu.h)
 };
 #define ALD(f) (p.I[(size_t)(f) * g.nchp + ch])
 

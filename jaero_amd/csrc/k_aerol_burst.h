@@ -391,6 +391,7 @@ __global__ __launch_bounds__(64) void k_aerolb_post(const AGeom g, const APtrs p
             else overflow |= 1;
         }
         ALD(AI_SU_CNT) = row_cnt; ALD(BI_NPACKETS) = npk + 1;
+        if (p.rtmark) p.rtmark[ch] = ((long long)npk << 16) | (long long)((ninfo << 2) | type); // logged or not (k_aerolb_isu.h)
         ALD(BI_RT_BLOCKPTR) = RT_BLOCKSZ; // stop further testing
     }
     if (result == RT_BAD)

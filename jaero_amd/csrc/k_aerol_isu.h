@@ -74,8 +74,11 @@ __device__ __forceinline__ unsigned isu_range_mask(int base, int lo, int hi)
     return m;
 }
 
-// A completed item goes to the channel's message log, classified as ParserISU::parse classifies it.
-__device__ __forceinline__ void isu_emit(const IPtrs &q, int ch, const isu_item &it, const uint8_t *u, int frame, int kk, int &msg_cnt, int &overflow)
+// A completed item goes to the channel's message log, classified as ParserISU::parse classifies it.  NSRC: the 16-byte groups u holds (a P or T
+// channel item's 32; an R channel slot's 3, k_aerolb_isu.h: nothing is read behind them); origin: flag bits set whatever the classification says.
+template <int NSRC = 32>
+__device__ __forceinline__ void isu_emit(const IPtrs &q, int ch, const isu_item &it, const uint8_t *u, int frame, int kk, int &msg_cnt, int &overflow,
+                                         unsigned origin = 0)
 {
     if (msg_cnt >= q.msg_cap) { overflow |= ISU_OVERFLOW_BIT; return; }
     const int n = it.len;
@@ -94,7 +97,8 @@ __device__ __forceinline__ void isu_emit(const IPtrs &q, int ch, const isu_item 
     unsigned even = 0; // bytes with even parity among those that count
     for (int c = 0; c < 32; c++)
     {
-        uint4 v = src[c];
+        uint4 v = {0u, 0u, 0u, 0u};
+        if (c < NSRC) v = src[c];
         unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -107,6 +111,7 @@ __device__ __forceinline__ void isu_emit(const IPtrs &q, int ch, const isu_item 
         row[2 + c] = v;
     }
     if (even) flags |= ISU_F_PARITY;
+    flags |= origin;
     uint4 h0, h1;
     h0.x = (unsigned)frame; h0.y = (unsigned)kk; h0.z = it.aesid;
     h0.w = (unsigned)it.gesid | ((unsigned)it.qno << 8) | ((unsigned)it.refno << 16) | ((unsigned)it.nooct << 24);

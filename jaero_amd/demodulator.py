@@ -509,7 +509,8 @@ class BurstMskDemodulator(_SingleChannelBurstDemodulator):
 
 class AeroLBank:
     """A bank of AeroL bit pipelines (continuous P-channel path of JAERO/aerol.cpp AeroL::Decode): soft bits in, CRC-checked
-    12-byte signal units out and, once isu_enable is called, the ISUs reassembled from them.  Thin wrapper over jaero_aerol_ctx."""
+    12-byte signal units out and, once isu_enable is called, the ISUs reassembled from them; with burst=True the R / T packets and, once
+    rt_enable is called, the user data reassembled from those.  Thin wrapper over jaero_aerol_ctx."""
 
     def __init__(self, nchannels: int, fb: int, device: int = 0, max_softbits_per_write: int = 1 << 16, su_capacity: int = 0,
                  burst: bool = False):
@@ -681,6 +682,21 @@ class AeroLBank:
         """int64 [nch, 4] since isu_enable: ISU updates, SSU updates, missing SSUs, completed messages."""
         out = np.zeros((self.nch, 4), dtype=np.int64)
         capi.check(self.L.jaero_aerol_isu_stats(self.h, out.ctypes.data))
+        return out
+
+    # ---- R / T user data of a burst bank, reassembled on the device (jaero_aerol_rt_enable) ----
+    def rt_enable(self, msg_capacity: int = 64):
+        """Burst banks: from the next write on every channel keeps the reference's RISUData behind its R packets and its ISUData behind the
+        units of its T packets, and logs what completes as jaero_aerol_msg rows: read_msgs / read_msgs_all, frame = the packet number,
+        flags bit 5 = from an R packet, bit 6 = an R signalling-information unit.  Starts from empty lists, log and counters.
+        msg_capacity = 0 switches it off again; the log stays readable."""
+        capi.check(self.L.jaero_aerol_rt_enable(self.h, int(msg_capacity)))
+
+    def rt_stats(self) -> np.ndarray:
+        """int64 [nch, 8] since rt_enable: T path ISU updates, SSU updates, missing SSUs, completed messages; R path user-data packets fed,
+        items newly appended, completed messages, signalling-information units."""
+        out = np.zeros((self.nch, 8), dtype=np.int64)
+        capi.check(self.L.jaero_aerol_rt_stats(self.h, out.ctypes.data))
         return out
 
     def tick_dcd(self) -> np.ndarray:
